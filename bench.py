@@ -23,11 +23,17 @@ Launching: `python bench.py --gpus N` starts the N ranks itself (a child `python
 spawned BEFORE this process touches the GPU); under `torch.distributed.run` (WORLD_SIZE set) it is a rank.
 A rank whose WORLD_SIZE differs from --gpus exits non-zero.
 
+A plain run (`python bench.py --gpus 1 --steps N --warmup W`) does only what its headline figure needs: it sets up, warms up,
+times the N steps, counts the rays of one batch (untimed), writes the outputs if `--dump-outputs DIR` is given and prints the
+line.  Everything else it can measure or check runs with `--full` (off by default).
+
 Prints ONE JSON line on rank 0 (driver contract) extended with:
   roofline        the contract's fields (algorithmic bytes of one launch / its event-timed duration / 8 TB/s) PLUS what the
                   counters say the kernel is bound by: vector-instruction issue fraction, mean occupancy, measured HBM bytes
                   (PMC; from profiles/counters_latest.json when it was taken on this very kernel source with these settings),
-                  the HBM floor of a frame, and the lone frame's latency model (longest dependent chain x time per position)
+                  the HBM floor of a frame, and the lone frame's latency model (longest dependent chain x time per position);
+                  with --full also the gather ceilings measured in the run (measured_in_run.limiter_*)
+With --full (each leg null in a plain run):
   cpu_baseline    the scalar oracle on this host's cores (a reported baseline)
   latency         one frame per launch, one launch in flight: ms per frame as an application waiting for each frame sees it
   scale_anchor    the ONE-GPU rate with the settings an N-GPU run uses (RGBA8 tiles, 2 streams x 48 frames per launch): the
@@ -98,9 +104,9 @@ def parse_args(argv=None):
     ap.add_argument("--frames-per-step", type=int, default=96,
                     help="frames in the batch ONE step renders: consecutive views of a camera on a short orbit (0.25 degrees apart)")
     ap.add_argument("--launches-per-step", type=int, default=0,
-                    help="passes over the batch that make ONE step (each pass = --frames-per-step frames); 0 = default: 30 on the main "
-                         "line (a step is then 2 880 frames, about 0.11 s on one MI355X: the driver's --steps 20 --warmup 5 times 2 s after "
-                         "0.5 s of warm-up, long enough for clocks to settle and for SMI samples to see the GPU busy), 1 with --steps <= 2")
+                    help="passes over the batch that make ONE step (each pass = --frames-per-step frames); 0 = default: 30 whatever "
+                         "--steps is (a step is then 2 880 frames, about 0.11 s on one MI355X: the driver's --steps 20 --warmup 5 times 2 s "
+                         "after 0.5 s of warm-up, long enough for clocks to settle and for SMI samples to see the GPU busy)")
     ap.add_argument("--block-frames", type=int, default=0,
                     help="frames per vrt_render_block call = per march launch (up to 48; one event pair per launch); 0 = default")
     ap.add_argument("--per-frame-launches", action="store_true",
@@ -122,8 +128,16 @@ def parse_args(argv=None):
     ap.add_argument("--native-check", action="store_true",
                     help="N>1 with --gather torch: also bring up the C-ABI's own RCCL communicator and run a few frames through "
                          "vrt_gather_tiles after the timed region (native_gather_check)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-extra-legs", action="store_true", help="skip the latency / end_to_end / config4 legs")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure and check what the headline figure does not need: the gather ceilings of roofline.measured_in_run, "
+                         "the CPU baseline, the census of marching waves and the extra legs (latency, scale anchor, end to end, config 4, "
+                         "other formats and scenes; N>1: the other exchange and collective); off by default")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last march launch of the timed region rendered to DIR/<name>.npy "
+                         "(float32 / float64, at most 64 MB in all): the last frame, the pixels at fixed seeded positions of all "
+                         "the launch's frames and the last frame's counters")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full without the CPU baseline")
+    ap.add_argument("--no-extra-legs", action="store_true", help="--full without the latency / end_to_end / config4 / ... legs")
     ap.add_argument("--cpu-seconds", type=float, default=8.0, help="target CPU time of the baseline sample")
     ap.add_argument("--launch-check", action="store_true",
                     help="CPU-only check of the N-rank launch path: ranks rendezvous over gloo, gather synthetic tiles "
@@ -350,6 +364,14 @@ class Pipeline:
         None elsewhere."""
         return self.fg.frame(*self.last)
 
+    def last_block_frames(self):
+        """[(camera index, assembled frame)] of the frames of the last block issued that this rank holds (the whole block on one
+        GPU); call after drain()."""
+        b, last = self.last
+        first = self.frame_no - (last + 1)
+        held = [((first + g) % max(self.n_cameras, 1), self.fg.frame(b, g)) for g in range(last + 1)]
+        return [(c, f) for c, f in held if f is not None]
+
     def drain(self) -> None:
         torch = self.torch
         for b in range(self.K):
@@ -385,6 +407,50 @@ def timed_run(pipe: Pipeline, steps: int, warmup: int, world: int, cdev, frames_
         dist.all_reduce(te, op=dist.ReduceOp.MAX)
         elapsed = float(te.item())
     return elapsed
+
+
+COUNTER_KEYS = ("primary_rays", "shadow_rays", "bounce_rays", "primary_steps", "shadow_steps", "hits", "exhausted_rays")
+DUMP_BYTES_MAX = 64_000_000  # --dump-outputs writes at most this much
+DUMP_SAMPLE_PIXELS = 1 << 19
+DUMP_SAMPLE_SEED = 20251016
+
+
+def dump_outputs(out_dir: str, frames, counters: dict) -> dict:
+    """--dump-outputs: what the last march launch of the timed region rendered, as the caller of vrt_render_block receives it
+    (H x W x 4 float RGBA, or R8G8B8A8 bytes, written as float32 0..255), in .npy files of DUMP_BYTES_MAX bytes at most in all:
+      last_frame               [H, W, 4] float32  the launch's last frame, whole (when it fits next to a full sample: up to 1080p)
+      frames_sample            [n, 4]    float32  the pixels at n positions drawn over all the launch's frames with a fixed seed
+      frames_sample_index      [n, 3]    float32  ... those positions: (camera index in the batch, row, column)
+      last_frame_counters      [7]       float64  vrt_last_timing of the last frame, in COUNTER_KEYS order
+    frames: [(camera index, frame tensor)] (Pipeline.last_block_frames).  The same arguments draw the same positions in every run.
+    Returns {name: array}."""
+    import numpy as np
+    import torch
+
+    cams = np.array([c for c, _ in frames], dtype=np.int64)
+    imgs = [f for _, f in frames]
+    H, W = int(imgs[0].shape[0]), int(imgs[0].shape[1])
+    out = {}
+    per_pixel = 4 * 4 + 3 * 4  # a sampled pixel and its position
+    last = imgs[-1].float().cpu().numpy()
+    if last.nbytes + DUMP_SAMPLE_PIXELS * per_pixel + 4096 <= DUMP_BYTES_MAX:
+        out["last_frame"] = last
+    n = int(min(DUMP_SAMPLE_PIXELS, (DUMP_BYTES_MAX - sum(a.nbytes for a in out.values()) - 4096) // per_pixel))
+    rng = np.random.default_rng(DUMP_SAMPLE_SEED)
+    fi, yi, xi = rng.integers(0, len(imgs), n), rng.integers(0, H, n), rng.integers(0, W, n)
+    sample = np.empty((n, 4), dtype=np.float32)
+    for k, img in enumerate(imgs):
+        sel = np.nonzero(fi == k)[0]
+        if sel.size:
+            ys, xs = torch.from_numpy(yi[sel]).to(img.device), torch.from_numpy(xi[sel]).to(img.device)
+            sample[sel] = img[ys, xs].float().cpu().numpy()
+    out["frames_sample"] = sample
+    out["frames_sample_index"] = np.stack([cams[fi], yi, xi], axis=1).astype(np.float32)
+    out["last_frame_counters"] = np.array([counters[k] for k in COUNTER_KEYS], dtype=np.float64)
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a in out.items():
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+    return out
 
 
 def multi_gpu_summary(value, anchor_v, rotate, exchange_other, world, W, H, bytes_per_pixel, rays_per_frame, other_steps):
@@ -673,8 +739,8 @@ def main() -> None:
     # One STEP = one batch of B frames: consecutive views of a camera on a short orbit through the workload's own view
     # (frames of a moving camera, not B copies of one frame, so a frame does not find its predecessor's lines in L2).
     B = max(args.frames_per_step, 1)
-    # the main line's step: L passes over the batch (L launches of B frames on one GPU)
-    L = args.launches_per_step if args.launches_per_step > 0 else (30 if args.steps > 2 else 1)
+    # the main line's step: L passes over the batch (L launches of B frames on one GPU), the same step whatever --steps is
+    L = args.launches_per_step if args.launches_per_step > 0 else 30
     # frames per vrt_render_block call = per march launch: one GPU the whole step (96: a launch's latency-bound tail is paid once per
     # launch; beyond 48 frames the cameras are copied to the device ahead of the launch instead of travelling in the kernarg segment);
     # several GPUs: about 48 (a multiple of N), exchanged as ONE block per collective
@@ -683,7 +749,8 @@ def main() -> None:
         raise SystemExit(f"[bench] --exchange rotate needs --block-frames to be a multiple of the {world} ranks")
     cams = workloads.orbit_cameras(sc, B)
     cam_arr = r.camera_array(cams + cams)
-    KEYS = ("primary_rays", "shadow_rays", "bounce_rays", "primary_steps", "shadow_steps", "hits", "exhausted_rays")
+    KEYS = COUNTER_KEYS
+    extra_legs = args.full and not args.no_extra_legs
 
     def batch_counts(pp, w, h, alone=False):
         """The counters of one batch (every camera once, this rank's rows — the whole frame with alone=True —, untimed), summed
@@ -715,9 +782,11 @@ def main() -> None:
         return Pipeline(r, pp, w, h, world, rank, dev, rgba8, strip_rows, k, rehearsal, native=native, block_frames=g or G, cameras=cam_arr,
                         n_cameras=B, rotate=rotate if rot is None else rot)
 
-    ceilings, ceilings_measured = measure_gather_ceilings(r, _abi) if rank == 0 else (dict(GATHER_CEILING_GSAMPLES), False)
+    # (--full: the march's inner operation in isolation, the yardstick of roofline.measured_in_run.limiter_*)
+    ceilings, ceilings_measured = measure_gather_ceilings(r, _abi) if rank == 0 and args.full else (None, False)
     pipe = pipeline(p, W, H, K, use_native)
     elapsed = timed_run(pipe, args.steps, args.warmup, world, cdev, B * L)
+    last_counts = r.last_timing() if args.dump_outputs else None  # the counters of the timed region's last frame
     xchg_ms = pipe.exchange_ms(n_timed_blocks := len(list(block_plan(args.steps * B * L, G, K)))) if world > 1 else None
     # the event-timed march launches of the timed region: (ms, frames the launch covered); only whole blocks count
     n_timed = len(list(block_plan(args.steps * B * L, G, K)))  # launches of the timed region (the warm-up's come before them)
@@ -760,12 +829,20 @@ def main() -> None:
             del pipe
             pipe = pipeline(p, W, H, K, False)
             elapsed = timed_run(pipe, args.steps, args.warmup, world, cdev, B * L)
+            last_counts = r.last_timing() if args.dump_outputs else None
             hist = [(ms, fr) for ms, fr in r.launch_history(min(max(n_timed, 1), 200)) if ms > 0.0]
             fpl = max((fr for _, fr in hist), default=1)
             kms = [ms for ms, fr in hist if fr == fpl]
             verified = last_frame_ok(pipe, p, W, H)
         if not verified:
             raise SystemExit("[bench] the assembled frame differs from the single-GPU frame")
+
+    if args.dump_outputs and args.steps > 0:
+        held = pipe.last_block_frames()
+        if rank == 0 and held:
+            dumped = dump_outputs(args.dump_outputs, held, last_counts)
+            print(f"[bench] outputs of the last launch of the timed region in {args.dump_outputs}: " +
+                  ", ".join(f"{k} {list(a.shape)} {a.dtype}" for k, a in dumped.items()), file=sys.stderr)
 
     per_rank = None
     if world > 1:
@@ -827,7 +904,7 @@ def main() -> None:
         return out
 
     native_check = exchange_other = None
-    if world > 1 and not args.no_extra_legs and args.steps > 0:
+    if world > 1 and extra_legs and args.steps > 0:
         osteps = max(min(args.steps, 3), 1)
 
         def run_other(other):
@@ -844,7 +921,7 @@ def main() -> None:
         if isinstance(exchange_other, dict):
             exchange_other["exchange"] = exchange_label(not rotate, world, G_other, rehearsal)
     latency = end_to_end = config4 = scale_anchor = None
-    if not args.no_extra_legs and args.steps > 0:
+    if extra_legs and args.steps > 0:
         lsteps = max(min(args.steps, 4), 1)  # batches
 
         def run_latency(p1):
@@ -903,7 +980,7 @@ def main() -> None:
             r.ResizeRenderOutput(W, H)
 
     marching = no_cull = None
-    if world == 1 and args.steps > 0:
+    if world == 1 and args.steps > 0 and args.full:
         # How many of a frame's primary rays belong to waves that march at all: 4 out of 5 waves of the frame lie outside the
         # host's cull rectangle (or miss the volume's active box) and go straight to the sky.  From the per-wave records of the
         # batch's middle frame.  And the same frames with the rectangle switched off (every wave looks at the scene).
@@ -912,7 +989,7 @@ def main() -> None:
         busy = (rec[:, 3] + rec[:, 4]) > 0
         marching = {"primary_rays_in_marching_waves": int(rec[busy, 0].sum()), "primary_rays": int(rec[:, 0].sum()),
                     "waves_marching": int(busy.sum()), "waves": int((rec[:, 0] > 0).sum())}
-        if not args.no_extra_legs:
+        if extra_legs:
             pn = params(W, H)
             pn.flags |= _abi.FLAG_NO_CULL_RECT
             pipen = pipeline(pn, W, H, K, False)
@@ -923,7 +1000,7 @@ def main() -> None:
             del pipen
 
     texel_leg = None
-    if not args.no_extra_legs and args.steps > 0 and world == 1 and fmt == _abi.FORMAT_F32 and args.path == "auto":
+    if extra_legs and args.steps > 0 and world == 1 and fmt == _abi.FORMAT_F32 and args.path == "auto":
         # the same frames with the volume kept as the reference's own 16-bit texel (RDXVoxelVolume.cpp:399-421), cell records
         for vol in sc.volumes():
             vol.set_device_format(_abi.FORMAT_TEXEL16)
@@ -942,7 +1019,7 @@ def main() -> None:
             vol.set_device_format(fmt)
 
     full_leg = None
-    if not args.no_extra_legs and args.steps > 0 and world == 1 and args.workload == "c3":
+    if extra_legs and args.steps > 0 and world == 1 and args.workload == "c3":
         # the same frames with ONE point light in the scene: the full closest hit (the reference's default render mode as soon as a
         # scene has a point / spot light, a mirroring material or a texture, SH/Raytracing_NoTex.hlsl:41-139) instead of the
         # directional-light kernel.  A block of frames runs it in passes (camera-ray march / light shadow rays + shading / mirror
@@ -967,7 +1044,7 @@ def main() -> None:
         r.SyncWithScene()
 
     dropin_leg = None
-    if not args.no_extra_legs and args.steps > 0 and world == 1 and args.workload == "c3":
+    if extra_legs and args.steps > 0 and world == 1 and args.workload == "c3":
         # What a drop-in user gets: the C++ adaptor's DEFAULTS — render mode Interp (the reference's default),
         # the volume as the reference's 16-bit texel, its 1x1 default normal texel on the material, B8G8R8A8 frames, the two reference-artefact
         # flags, MaxBounces 2 — on the benchmark's frames, as a block (one launch per 96 frames) and as a lone frame (one frame per launch, one
@@ -1024,7 +1101,7 @@ def main() -> None:
         dropin_leg = leg(lambda: None, run_dropin)
 
     dynamic_leg = None
-    if not args.no_extra_legs and args.steps > 0 and world == 1 and args.workload == "c3":
+    if extra_legs and args.steps > 0 and world == 1 and args.workload == "c3":
         # Per-frame scene state (vrt_block::scenes): BASELINE config 5's 8 instances ALL moving from frame to frame — the reference moves
         # objects every frame and rebuilds its TLAS every frame (RendererEngineInstance.cpp:111-130, DXRenderer.cpp:809-825) — still
         # ONE march launch per batch (instances, BVH, lights, cull rectangle packed per frame on the host, one copy ahead of the
@@ -1074,7 +1151,7 @@ def main() -> None:
         r.SyncWithScene()
 
     coverage_leg = None
-    if not args.no_extra_legs and args.steps > 0 and world == 1 and args.workload == "c3":
+    if extra_legs and args.steps > 0 and world == 1 and args.workload == "c3":
         # Every pixel marches: the same 256^3 volume with the camera INSIDE its box, 0.6 extents from the centre,
         # looking at it — no sky wave, no wave outside the cull rectangle; the case that stresses the texture path hardest.
         def run_coverage(_):
@@ -1138,9 +1215,9 @@ def main() -> None:
         pmc = measured_counters(key)
         traffic = pmc.get("hbm_bytes_per_launch") if pmc else None
         cpu = None
-        if world == 1 and not args.no_cpu_baseline:
+        if world == 1 and args.full and not args.no_cpu_baseline:
             cpu = cpu_baseline(sc, p, args.cpu_seconds)
-        coherent_key = "l1_int16_coherent_lanes" if (fmt == _abi.FORMAT_TEXEL16 and "l1_int16_coherent_lanes" in ceilings) else "l1_coherent_lanes"
+        coherent_key = "l1_int16_coherent_lanes" if (fmt == _abi.FORMAT_TEXEL16 and "l1_int16_coherent_lanes" in (ceilings or {})) else "l1_coherent_lanes"
         roofline = {
             # The contract's fields are what the contract defines: ALGORITHMIC bytes (32 B per trilinear sample + 192 B per hit +
             # the pixel store) of one launch / its mean event-timed duration / the HBM peak.  Everything in `measured_in_run` was measured by
@@ -1169,14 +1246,14 @@ def main() -> None:
                 "gevaluations_per_s": round(evals / (k_ms * 1e-3) / 1e9, 2) if kms else None,
                 # the march's inner operation in isolation, on this box, right before the timed region (vrt_debug_gather_ceiling):
                 # independent cells per lane (by where the bricks live; fp32 and int16 bricks) and the 64 lanes of a wave on the 3x3 cells
-                # of an 8x8-pixel tile
+                # of an 8x8-pixel tile (--full only: null in a plain run, and so is every limiter_* figure)
                 "gather_ceiling_gsamples_per_s": ceilings, "gather_ceiling_measured_in_run": ceilings_measured,
                 "limiter": "L1-served trilinear gather (the texture path)",
-                "limiter_ceiling_gsamples_per_s": ceilings[gather_key],
-                "limiter_frac": round(evals / (k_ms * 1e-3) / 1e9 / ceilings[gather_key], 4) if kms else None,
+                "limiter_ceiling_gsamples_per_s": ceilings[gather_key] if ceilings else None,
+                "limiter_frac": round(evals / (k_ms * 1e-3) / 1e9 / ceilings[gather_key], 4) if kms and ceilings else None,
                 # ... and against a gather whose 64 lanes are tile-coherent (the march's lanes lie between the two)
-                "limiter_ceiling_coherent_lanes_gsamples_per_s": ceilings[coherent_key],
-                "limiter_frac_coherent_lanes": round(evals / (k_ms * 1e-3) / 1e9 / ceilings[coherent_key], 4) if kms else None,
+                "limiter_ceiling_coherent_lanes_gsamples_per_s": ceilings[coherent_key] if ceilings else None,
+                "limiter_frac_coherent_lanes": round(evals / (k_ms * 1e-3) / 1e9 / ceilings[coherent_key], 4) if kms and ceilings else None,
                 # measured in rounds 4 and 5 (profiles/r04_ab_cell_activity_mask.txt, r05_data_paths.txt, r05_ab_placement.txt): the evaluation
                 # RATE is the march's speed against the gather microbenchmark, not what its time is made of — a third fewer samples for
                 # bit-identical frames: +3.4 %; half the loads per sample: +1.5 %; no re-placement of lanes or bricks changes the 19 lines per load

@@ -1,15 +1,16 @@
 """What the march's speed stands on besides its arithmetic, checked on the build's own ISA listing (no GPU): the register budgets
 that decide how many waves a SIMD holds, no scratch memory in the lean kernels, and no packed fp32 instruction anywhere (round 5
 measured v_pk_fma_f32 / v_pk_add_f32 2-5 % slower than the scalar instructions they replace: profiles/r05_ab_step_asm.txt).
-The listing is what csrc/build.sh keeps from -save-temps in $VRT_BUILD_TMP (/tmp/vrtbuild); where the library was built
-elsewhere (the GPU box gets the .so, not the listing) the tests skip."""
+The listing is what csrc/build.sh keeps from -save-temps in $VRT_BUILD_TMP (default: build/hip inside the checkout); where the
+library was built elsewhere and the listing did not come with it the tests skip."""
 import os
 import re
 
 import pytest
 
-LISTING = os.path.join(os.environ.get("VRT_BUILD_TMP", "/tmp/vrtbuild"), "vrt_kernels-hip-amdgcn-amd-amdhsa-gfx950.s")
-LIB = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "volumetricraytracer_amd", "lib", "libvrt_hip.so")
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+LISTING = os.path.join(os.environ.get("VRT_BUILD_TMP", os.path.join(ROOT, "build", "hip")), "vrt_kernels-hip-amdgcn-amd-amdhsa-gfx950.s")
+LIB = os.path.join(ROOT, "volumetricraytracer_amd", "lib", "libvrt_hip.so")
 
 
 def _listing():

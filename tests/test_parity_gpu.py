@@ -1068,7 +1068,7 @@ def test_bench_two_rank_rehearsal(oracle_lib):
     env.update(VRT_BENCH_BACKEND="gloo", VRT_BENCH_VERIFY="1", HSA_ENABLE_IPC_MODE_LEGACY="0", VRT_BENCH_NATIVE_PROBE="1",
                VRT_BENCH_NATIVE_PROBE_DEADLINE_S="45")
     cmd = [sys.executable, os.path.join(root, "bench.py"), "--gpus", "2", "--steps", "3", "--warmup", "1", "--workload", "c2",
-           "--no-cpu-baseline"]
+           "--full", "--no-cpu-baseline"]
     res = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=900, cwd=root)
     assert res.returncode == 0, res.stderr[-2000:]
     line = [ln for ln in res.stdout.splitlines() if ln.startswith("{")][-1]
@@ -1099,7 +1099,7 @@ def test_bench_two_rank_rehearsal(oracle_lib):
 
 
 def test_bench_one_gpu_line_has_the_contract_fields(oracle_lib):
-    """`python bench.py` on one GPU (a short run): ONE JSON line with the driver contract's fields, the `roofline` and
+    """`python bench.py --full` on one GPU (a short run): ONE JSON line with the driver contract's fields, the `roofline` and
     `cpu_baseline` objects, one stream x 48 frames per launch, launch durations that add up to the timed region (nothing
     overlaps: kernel time x launches per step ~ ms_per_step), and the legs (latency, scale anchor, end to end, config 4)."""
     import json
@@ -1108,8 +1108,8 @@ def test_bench_one_gpu_line_has_the_contract_fields(oracle_lib):
 
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     env = {k: val for k, val in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT")}
-    res = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--steps", "3", "--warmup", "1", "--cpu-seconds", "1"], env=env,
-                         capture_output=True, text=True, timeout=900, cwd=root)
+    res = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--steps", "3", "--warmup", "1", "--full", "--cpu-seconds", "1"],
+                         env=env, capture_output=True, text=True, timeout=900, cwd=root)
     assert res.returncode == 0, res.stderr[-2000:]
     lines = [ln for ln in res.stdout.splitlines() if ln.startswith("{")]
     assert len(lines) == 1
@@ -1156,6 +1156,54 @@ def test_bench_one_gpu_line_has_the_contract_fields(oracle_lib):
     assert dd["round4_form"]["block"]["kernel_form"]["full_closest_hit"] and dd["round4_form"]["block"]["kernel_form"]["passes"]
     assert dd["block_over_lean"] > 0.85 and dd["block_over_round4_form"] > 1.15 and dd["lone_frame_over_lean"] > 0.8
     assert 0 < o["config"]["marching"]["primary_rays_in_marching_waves"] < o["config"]["marching"]["primary_rays"] == 1920 * 1080
+
+
+def test_bench_plain_run_is_lean_and_dumps_its_outputs(tmp_path):
+    """`python bench.py --steps N --warmup W` without --full: the contract's line and nothing measured besides it (no CPU baseline,
+    no gather ceilings, no legs), a step of the same 30 launches whatever --steps is, and --dump-outputs: what the timed region's
+    last launch rendered, within 64 MB, the same from run to run."""
+    import json
+    import subprocess
+    import sys
+
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    env = {k: val for k, val in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT")}
+    lines, dumps = [], []
+    for steps, warmup in ((3, 1), (1, 1)):
+        d = tmp_path / f"out{steps}"
+        res = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--steps", str(steps), "--warmup", str(warmup),
+                              "--dump-outputs", str(d)], env=env, capture_output=True, text=True, timeout=600, cwd=root)
+        assert res.returncode == 0, res.stderr[-2000:]
+        js = [ln for ln in res.stdout.splitlines() if ln.startswith("{")]
+        assert len(js) == 1
+        lines.append(json.loads(js[0]))
+        dumps.append({f.name[:-4]: np.load(f) for f in sorted(d.iterdir())})
+        assert sum(f.stat().st_size for f in d.iterdir()) <= 64_000_000
+    for o, steps in zip(lines, (3, 1)):
+        assert o["steps"] == steps and o["unit"] == "Mrays/s" and o["higher_is_better"] is True and o["dtype"] == "f32"
+        assert o["config"]["launches_per_step"] == 30 and o["ms_per_step"] > 60.0
+        assert abs(o["value"] - o["config"]["rays_per_step"] / (o["ms_per_step"] * 1e-3) / 1e6) / o["value"] < 0.01
+        for k in ("cpu_baseline", "latency", "scale_anchor", "end_to_end", "config4", "reference_texel_format", "full_closest_hit",
+                  "no_cull_rect", "dynamic_scene", "full_coverage", "drop_in_defaults"):
+            assert o[k] is None, k
+        assert o["config"]["marching"] is None and o["roofline"]["measured_in_run"]["gather_ceiling_measured_in_run"] is False
+        assert o["roofline"]["frac"] > 0
+    # one step is one step: a 1-step run times the same 30 launches as a 3-step run
+    assert 0.7 < lines[1]["ms_per_step"] / lines[0]["ms_per_step"] < 1.4
+    a, b = dumps
+    assert set(a) == {"last_frame", "frames_sample", "frames_sample_index", "last_frame_counters"} == set(b)
+    assert a["last_frame"].shape == (1080, 1920, 4) and a["last_frame"].dtype == np.float32
+    assert a["frames_sample"].dtype == np.float32 and a["last_frame_counters"].dtype == np.float64
+    for k in a:
+        assert np.array_equal(a[k], b[k]), k  # same arguments, same inputs, same outputs
+    c = dict(zip(("primary_rays", "shadow_rays", "bounce_rays", "primary_steps", "shadow_steps", "hits", "exhausted_rays"), a["last_frame_counters"]))
+    assert c["primary_rays"] == 1920 * 1080 and c["hits"] > 0 and c["shadow_rays"] > 0
+    # the sample is drawn from the launch's frames: its pixels of the last camera are the last frame's
+    idx = a["frames_sample_index"].astype(np.int64)
+    last_cam = idx[:, 0].max()
+    mine = idx[:, 0] == last_cam
+    assert mine.sum() > 1000 and len(np.unique(idx[:, 0])) == 96
+    assert np.array_equal(a["frames_sample"][mine], a["last_frame"][idx[mine, 1], idx[mine, 2]])
 
 
 def test_native_tile_gather_with_one_rank(oracle_lib):

@@ -326,6 +326,44 @@ def test_bench_cli_parses_and_prints_help():
     assert (a.gpus, a.frames_per_step, a.strip_rows, a.scaling, a.workload) == (1, 96, 8, "strong", "c3")
     a = bench.parse_args(["--gpus", "8", "--steps", "20", "--warmup", "5"])
     assert (a.gpus, a.steps, a.warmup) == (8, 20, 5)
+    # a plain run measures the headline only; the rest is behind --full, and nothing is written unless asked for
+    assert (a.full, a.dump_outputs) == (False, None)
+    a = bench.parse_args(["--full", "--dump-outputs", "out"])
+    assert (a.full, a.dump_outputs) == (True, "out")
+
+
+def test_bench_dump_outputs_are_seeded_and_bounded(tmp_path):
+    """bench.py --dump-outputs on frames as the timed path leaves them: float32 / float64 arrays of at most 64 MB, the sample drawn
+    at the same positions in every run, its pixels those of the frames, R8G8B8A8 frames written as float32 0..255, and a frame too
+    large to keep whole left to the sample."""
+    import numpy as np
+    import torch
+
+    sys.path.insert(0, ROOT)
+    import bench
+
+    g = torch.Generator().manual_seed(3)
+    frames = [(c, torch.rand((1080, 1920, 4), generator=g)) for c in (40, 41, 42)]
+    counters = {k: float(i + 1) for i, k in enumerate(bench.COUNTER_KEYS)}
+    runs = []
+    for name in ("a", "b"):
+        bench.dump_outputs(str(tmp_path / name), frames, counters)
+        runs.append({f.name[:-4]: np.load(f) for f in (tmp_path / name).iterdir()})
+        assert sum(f.stat().st_size for f in (tmp_path / name).iterdir()) <= 64_000_000
+    a, b = runs
+    assert set(a) == {"last_frame", "frames_sample", "frames_sample_index", "last_frame_counters"}
+    assert all(np.array_equal(a[k], b[k]) for k in a)
+    assert all(x.dtype in (np.float32, np.float64) for x in a.values())
+    assert np.array_equal(a["last_frame"], frames[-1][1].numpy())
+    assert list(a["last_frame_counters"]) == [1.0, 2.0, 3.0, 4.0, 5.0, 6.0, 7.0]
+    idx = a["frames_sample_index"].astype(np.int64)
+    assert set(np.unique(idx[:, 0])) == {40, 41, 42} and idx[:, 1].max() < 1080 and idx[:, 2].max() < 1920
+    want = np.stack([frames[c - 40][1][y, x].numpy() for c, y, x in idx[:2000]])
+    assert np.array_equal(a["frames_sample"][:2000], want)
+    big = [(0, torch.full((2160, 3840, 4), 200, dtype=torch.uint8))]
+    out = bench.dump_outputs(str(tmp_path / "c"), big, counters)
+    assert "last_frame" not in out and out["frames_sample"].dtype == np.float32 and (out["frames_sample"] == 200.0).all()
+    assert sum(f.stat().st_size for f in (tmp_path / "c").iterdir()) <= 64_000_000
 
 
 def test_bench_block_plan_issues_exactly_the_frames_asked_for():

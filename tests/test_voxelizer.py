@@ -742,12 +742,11 @@ def test_skybox_from_a_block_compressed_dds_cube_map(tmp_path, bc, dx10):
             vx.load_skybox_faces(bad)
 
 
-@pytest.mark.skipif(not os.path.isdir("/root/reference/VolumetricRaytracer/VolumetricRaytracer/Resources/Skybox"),
-                    reason="the reference checkout (with its Resources/Skybox PNGs) is only present on the build machine")
 def test_reference_skybox_pngs_decode():
-    """The reference's own six sky box faces (data files, Resources/Skybox/*.png) through this build's PNG reader: 1024^2
-    RGBA each, identical to what PIL decodes."""
-    d = "/root/reference/VolumetricRaytracer/VolumetricRaytracer/Resources/Skybox"
+    """The reference's own six sky box faces (data files, Resources/Skybox/*.png; stored under tests/golden/skybox with their
+    image data re-deflated, every chunk and filtered scanline as it was: tests/golden/make_skybox_fixtures.py) through this
+    build's PNG reader: 1024^2 RGBA each, identical to what PIL decodes."""
+    d = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "skybox")
     cube = vx.load_skybox_faces(d)
     assert cube.shape == (6, 1024, 1024, 4)
     try:

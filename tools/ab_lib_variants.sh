@@ -18,7 +18,7 @@ out="$root/gpurun_out/ab"; mkdir -p "$out"; : > "$out/ab.txt"
 for round in 1 2; do
   for v in "${variants[@]}"; do
     name="${v%%:*}"
-    VRT_LIB="$root/volumetricraytracer_amd/lib/ab_$name.so" python3 "$root/bench.py" --no-cpu-baseline --steps 10 "$@" > "$out/$name.$round.json" 2> "$out/$name.$round.err" || echo "$name failed"
+    VRT_LIB="$root/volumetricraytracer_amd/lib/ab_$name.so" python3 "$root/bench.py" --full --no-cpu-baseline --steps 10 "$@" > "$out/$name.$round.json" 2> "$out/$name.$round.err" || echo "$name failed"
     python3 - "$name" "$round" "$out/$name.$round.json" >> "$out/ab.txt" <<'PY'
 import json, sys
 name, rnd, path = sys.argv[1:4]

@@ -1,11 +1,12 @@
 #!/usr/bin/env python3
 """Per-kernel register / LDS / scratch use from the -save-temps ISA of the HIP build (amdhsa.kernels metadata).
-Usage: python tools/kernel_resources.py [/tmp/vrtbuild/vrt_kernels-hip-amdgcn-amd-amdhsa-gfx950.s] [name filter]"""
+Usage: python tools/kernel_resources.py [build/hip/vrt_kernels-hip-amdgcn-amd-amdhsa-gfx950.s] [name filter]"""
+import os
 import re
 import subprocess
 import sys
 
-path = sys.argv[1] if len(sys.argv) > 1 else "/tmp/vrtbuild/vrt_kernels-hip-amdgcn-amd-amdhsa-gfx950.s"
+path = sys.argv[1] if len(sys.argv) > 1 else os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "build", "hip", "vrt_kernels-hip-amdgcn-amd-amdhsa-gfx950.s")
 flt = sys.argv[2] if len(sys.argv) > 2 else "march"
 text = open(path).read()
 meta = text[text.index("amdhsa.kernels:"):]

@@ -3,14 +3,14 @@
 set -uo pipefail
 out=gpurun_out/r02p; mkdir -p $out
 export TMPDIR=/tmp
-python3 bench.py > $out/bench_default.json 2> $out/bench_default.err
+python3 bench.py --full > $out/bench_default.json 2> $out/bench_default.err
 tools/profile_bench.sh r02 > $out/profile.log 2>&1
 tools/pmc_sq.sh r02 --no-extra-legs > $out/pmc.log 2>&1
 python3 tools/timeline.py c3 > $out/timeline_c3.txt 2>&1
 for k in 1 2 3 4; do python3 bench.py --no-cpu-baseline --no-extra-legs --frames-in-flight $k > $out/k$k.json 2>/dev/null; done
 for cfg in "f32:--format f32" "texel16_bricks:--format texel16" "texel16_cells:--format texel16 --path cells" "f32_dense:--path dense" "f32_lds:--path lds"; do
   name="${cfg%%:*}"; args="${cfg#*:}"
-  python3 bench.py --no-cpu-baseline $args > $out/fmt_$name.json 2>/dev/null
+  python3 bench.py --full --no-cpu-baseline $args > $out/fmt_$name.json 2>/dev/null
 done
 for w in c2 c3sdf c5; do python3 bench.py --no-cpu-baseline --no-extra-legs --workload $w > $out/wl_$w.json 2>/dev/null; done
 (cd tools/microbench && { [ -x gather16 ] || hipcc --offload-arch=gfx950 -O3 -ffp-contract=off -o gather16 gather16.hip; } && ./gather16 > ../../$out/gather16.txt 2>&1)

@@ -4,7 +4,8 @@
 set -euo pipefail
 here="$(cd "$(dirname "${BASH_SOURCE[0]}")" && pwd)"
 out="$here/../lib"
-tmp="${VRT_BUILD_TMP:-/tmp/vrtbuild}"
+# temporaries and the kept ISA listing stay inside the checkout (build/hip, ignored by git): tests/test_kernel_resources.py reads it
+tmp="${VRT_BUILD_TMP:-$here/../../build/hip}"
 mkdir -p "$out" "$tmp"
 cd "$tmp"
 # VRT_LIB_NAME / VRT_EXTRA_DEFS: A/B builds of kernel variants next to the product library (tools/ab_lib_variants.sh)
