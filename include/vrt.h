@@ -15,6 +15,9 @@
  *   vrt_set_volume_format,          VDXVoxelVolume::EncodeVoxel  RDXVoxelVolume.cpp:399-421 (the 4-byte volume texel,
  *   vrt_volume_upload_texels        DecodeDensity Shaders/Include/Voxel.hlsli:254-266)
  *   vrt_volume_set_material         VDXVoxelVolume::UpdateGeometryConstantBuffer  :368-397
+ *   vrt_volume_update_region,       VVoxelVolume::SetVoxel / MakeDirty / IsDirty  Voxel/Private/VoxelVolume.cpp:59-137, and
+ *   vrt_volume_update_voxels        VDXVoxelVolume::UpdateFromVoxelVolume  RDXVoxelVolume.cpp:33-60 (re-upload of a dirty volume),
+ *                                   for a box of voxels instead of the whole volume
  *   vrt_volume_free                 VRDXScene::RemoveVoxelVolume  Renderer/DX/Private/RDXScene.cpp:663-701
  *   vrt_env_upload                  VRDXScene::InitEnvironmentMap RDXScene.cpp:181-199
  *   vrt_scene_set                   VRDXScene::SyncWithScene + PrepareForRendering
@@ -281,6 +284,37 @@ int vrt_voxelize_mesh(vrt_ctx* ctx, int slot, uint8_t resolution, float extent, 
 int vrt_volume_download(vrt_ctx* ctx, int slot, vrt_voxel* out);
 
 int vrt_volume_free(vrt_ctx* ctx, int slot);
+
+/* Incremental edits — what VVoxelVolume::SetVoxel + MakeDirty (Voxel/Private/VoxelVolume.cpp:59-137) followed by the renderer's
+ * re-upload of a dirty volume (IsDirty -> VDXVoxelVolume::UpdateFromVoxelVolume, RDXVoxelVolume.cpp:33-60) do, for a box of voxels
+ * instead of the whole volume.  Replaces the voxels of the box [x0, x0+sx) x [y0, y0+sy) x [z0, z0+sz) of a resident slot, in place,
+ * on every device.  Box data in the volume's own order: x slowest, then z, then y — element (ix, iz, iy) at (ix*sz + iz)*sy + iy.
+ * Densities in the caller's units (a VRT_FORMAT_TEXEL16 slot quantises them on the device like the full upload);
+ * material_or_null == NULL leaves the box's material ids as they are.  Waits for work already enqueued on the context's devices
+ * (a frame begun before the call renders the old volume, one begun after renders the new one); device pointers of the slot do
+ * not change.  Afterwards every device buffer of the slot equals what a full upload of the edited volume holds, so frames and
+ * counters are those of the full upload.  A launch captured into a graph before the edit keeps the cull rectangle it was captured
+ * with (capture with VRT_FLAG_NO_CULL_RECT where an edit may grow the active box).
+ * Errors, all checked before any device state is touched: VRT_ERR_SLOT for an unused slot; VRT_ERR_INVALID for a NULL pointer, a
+ * size below 1 or a box reaching outside [0, N). */
+int vrt_volume_update_region(vrt_ctx* ctx, int slot, const int origin_xyz[3], const int size_xyz[3],
+                             const float* density, const uint8_t* material_or_null);
+/* Same from VVoxel records (VVoxelVolume's storage, the adaptor's), same box order. */
+int vrt_volume_update_voxels(vrt_ctx* ctx, int slot, const int origin_xyz[3], const int size_xyz[3], const vrt_voxel* voxels);
+
+/* Tests: the raw bytes of one device buffer of a slot on device `device_index` of the context.  *size_out (when not NULL) = the
+ * buffer's size; out == NULL only asks for it; a capacity below the size is VRT_ERR_INVALID.  The tables are the first nb^3
+ * entries (without their build scratch); SKIP and NIB are empty while the slot has no empty-space table (step_max <= 0);
+ * ACTIVE_BOX is the six ints {min x, z, y, max x, z, y} of the near bricks (the same on every device). */
+#define VRT_VOLUME_BYTES_DENSE 0      /* N^3 floats (VRT_FORMAT_TEXEL16: the integer field +-q) */
+#define VRT_VOLUME_BYTES_MATERIAL 1   /* N^3 bytes */
+#define VRT_VOLUME_BYTES_BRICKS 2     /* nb^3 brick records */
+#define VRT_VOLUME_BYTES_CELLS 3      /* nb^3 x 64 cell records of 16 B (VRT_FORMAT_TEXEL16 only) */
+#define VRT_VOLUME_BYTES_SKIP 4       /* level-1 table: nb^3 leap counts */
+#define VRT_VOLUME_BYTES_NIB 5        /* level-2 table: nb^3 words */
+#define VRT_VOLUME_BYTES_CUBE_SKIP 6  /* Cube modes' table: nb^3 distances */
+#define VRT_VOLUME_BYTES_ACTIVE_BOX 7
+int vrt_debug_volume_bytes(vrt_ctx* ctx, int slot, int device_index, int which, void* out, size_t capacity, size_t* size_out);
 
 /* 2D material textures — VRenderer::InitializeTexture / UploadToGPU(VTexture) (Renderer/Public/Renderer.h:54-57)
  * and the scene's geometry-texture table (VRDXScene, RDXScene.cpp:771-800, 905-925).  R8G8B8A8_UNORM, mip 0,

@@ -54,6 +54,10 @@ HIT_POLISH_SAMPLES = 2
 MAX_BLOCK_FRAMES = 48  # frames one march launch covers with their cameras in the kernarg segment (csrc/vrt_device.h kMaxBlockFrames)
 MAX_LAUNCH_FRAMES = 256  # ... with their cameras copied to device memory ahead of the launch: vrt_block.n_frames' upper bound
 
+# vrt_debug_volume_bytes: which device buffer of a slot
+VOLUME_BYTES_DENSE, VOLUME_BYTES_MATERIAL, VOLUME_BYTES_BRICKS, VOLUME_BYTES_CELLS = 0, 1, 2, 3
+VOLUME_BYTES_SKIP, VOLUME_BYTES_NIB, VOLUME_BYTES_CUBE_SKIP, VOLUME_BYTES_ACTIVE_BOX = 4, 5, 6, 7
+
 FORMAT_F32 = 0
 FORMAT_TEXEL16 = 1
 
@@ -194,6 +198,9 @@ SYMBOLS = {
                                     C.POINTER(C.c_size_t)]),
     "vrt_volume_download": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p]),
     "vrt_volume_free": (C.c_int, [C.c_void_p, C.c_int]),
+    "vrt_volume_update_region": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int), C.c_void_p, C.c_void_p]),
+    "vrt_volume_update_voxels": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int), C.c_void_p]),
+    "vrt_debug_volume_bytes": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_size_t, C.POINTER(C.c_size_t)]),
     "vrt_env_upload": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p]),
     "vrt_scene_set": (C.c_int, [C.c_void_p, C.POINTER(vrt_scene)]),
     "vrt_render": (C.c_int, [C.c_void_p, C.POINTER(vrt_params), C.c_void_p]),

@@ -503,6 +503,27 @@ bool VHipRenderer::SyncWithScene(Scene::VScene& scene) {
                                              reinterpret_cast<const vrt_voxel*>(v.GetVoxels().data())), "vrt_volume_upload_voxels"))
                 return false;
             Uploaded[slot] = &v;
+        } else if (v.IsRegionDirty() && RegionUploads) {
+            /* only a box changed (VVoxelVolume::MakeDirtyRegion): update it in place; the box's records in the volume's own order */
+            const VIntVector lo = v.GetDirtyRegionMin(), hi = v.GetDirtyRegionMax();
+            const int size[3] = {hi.X - lo.X + 1, hi.Y - lo.Y + 1, hi.Z - lo.Z + 1}, origin[3] = {lo.X, lo.Y, lo.Z};
+            const size_t n = v.GetSize();
+            const std::vector<Voxel::VVoxel>& all = v.GetVoxels();
+            RegionStaging.resize((size_t)size[0] * size[1] * size[2]);
+            size_t k = 0;
+            for (int x = lo.X; x <= hi.X; x++)
+                for (int z = lo.Z; z <= hi.Z; z++) {
+                    const size_t row = ((size_t)x * n + (size_t)z) * n + (size_t)lo.Y;
+                    std::copy(all.begin() + (ptrdiff_t)row, all.begin() + (ptrdiff_t)(row + (size_t)size[1]), RegionStaging.begin() + (ptrdiff_t)k);
+                    k += (size_t)size[1];
+                }
+            if (!ok(vrt_volume_update_voxels(Ctx, (int)slot, origin, size, reinterpret_cast<const vrt_voxel*>(RegionStaging.data())),
+                    "vrt_volume_update_voxels"))
+                return false;
+        } else if (v.IsRegionDirty()) { /* RegionUploads off: the whole volume, as for MakeDirty() */
+            if (!ok(vrt_volume_upload_voxels(Ctx, (int)slot, v.GetResolution(), v.GetVolumeExtends(),
+                                             reinterpret_cast<const vrt_voxel*>(v.GetVoxels().data())), "vrt_volume_upload_voxels"))
+                return false;
         }
         const VMaterial& m = v.GetMaterial();
         vrt_material mat = {{m.AlbedoColor.R, m.AlbedoColor.G, m.AlbedoColor.B, m.AlbedoColor.A}, m.Roughness, m.Metallic};

@@ -67,6 +67,10 @@ public:
        surface's pixels by more than one 8-bit step: the texel's 0.01 quantum).  VRT_FORMAT_F32 keeps the caller's
        floats (3 % faster, bench.py's format). */
     int VolumeFormat = VRT_FORMAT_TEXEL16;
+    /* A volume already on the device whose only change is a box (VVoxelVolume::MakeDirtyRegion) is updated in place
+       (vrt_volume_update_voxels: the box's voxels and what depends on them).  false: uploaded whole, like a MakeDirty() volume
+       (A/B runs; the same frames). */
+    bool RegionUploads = true;
     /* The reference binds 1x1 DEFAULT textures to every material slot that names no image (VRDXScene::AllocateDefaultTextures,
        RDXScene.cpp:241-260): albedo white and RM (1, 1, 0) are exact identities, but the default normal texel, VColor(0.5, 0.5, 1)
        stored as 8 bits, is (127, 127, 255) and decodes to (-0.0039, -0.0039, 1): in the textured render modes (Interp — the
@@ -112,6 +116,7 @@ private:
     const void* FramePixels = nullptr;
     size_t FrameBytes = 0;
     std::vector<const Voxel::VVoxelVolume*> Uploaded; /* per slot */
+    std::vector<Voxel::VVoxel> RegionStaging;          /* the box of a region update, packed */
     const VTextureCube* UploadedEnv = nullptr;
     struct TextureEntry {
         VObjectPtr<VTexture2D> Texture; /* null: lookup failed, do not retry */

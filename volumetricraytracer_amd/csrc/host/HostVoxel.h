@@ -5,6 +5,7 @@
  * out-of-range ignored), :139-176 (index <-> position), :129-137 (dirty flag).
  */
 #pragma once
+#include <algorithm>
 #include <cstdint>
 #include <memory>
 #include <vector>
@@ -29,6 +30,7 @@ public:
         CellSize = (volumeExtends * 2) / ((float)VoxelCountAlongAxis - 1.f);
         Voxels.assign(GetVoxelCount(), VVoxel());
         DirtyFlag = true;
+        RegionDirty = false;
     }
     unsigned GetSize() const { return VoxelCountAlongAxis; }
     size_t GetVoxelCount() const { return (size_t)VoxelCountAlongAxis * VoxelCountAlongAxis * VoxelCountAlongAxis; }
@@ -66,7 +68,31 @@ public:
     const VMaterial& GetMaterial() const { return GeometryMaterial; }
     void MakeDirty() { DirtyFlag = true; }
     bool IsDirty() const { return DirtyFlag; }
-    void PostRender() { DirtyFlag = false; } /* VoxelVolume.cpp:114-117 */
+    void PostRender() { /* VoxelVolume.cpp:114-117 */
+        DirtyFlag = false;
+        RegionDirty = false;
+    }
+    /* Not part of the reference type (an extension like DensityScale): only the voxels lo..hi (inclusive indices, clamped to the
+     * volume) changed since the last render; successive calls union their boxes.  A renderer that keeps the volume resident
+     * updates just this box (vrt_volume_update_voxels); MakeDirty() still means the whole volume and wins. */
+    void MakeDirtyRegion(const VIntVector& lo, const VIntVector& hi) {
+        const int n = (int)VoxelCountAlongAxis - 1;
+        const VIntVector a(std::max(lo.X, 0), std::max(lo.Y, 0), std::max(lo.Z, 0));
+        const VIntVector b(std::min(hi.X, n), std::min(hi.Y, n), std::min(hi.Z, n));
+        if (a.X > b.X || a.Y > b.Y || a.Z > b.Z) return; /* nothing of the box inside the volume */
+        if (!RegionDirty) {
+            DirtyLo = a;
+            DirtyHi = b;
+        } else {
+            DirtyLo = VIntVector(std::min(DirtyLo.X, a.X), std::min(DirtyLo.Y, a.Y), std::min(DirtyLo.Z, a.Z));
+            DirtyHi = VIntVector(std::max(DirtyHi.X, b.X), std::max(DirtyHi.Y, b.Y), std::max(DirtyHi.Z, b.Z));
+        }
+        RegionDirty = true;
+    }
+    bool IsRegionDirty() const { return RegionDirty; }
+    /* the union of the MakeDirtyRegion boxes (inclusive), valid while IsRegionDirty() */
+    VIntVector GetDirtyRegionMin() const { return DirtyLo; }
+    VIntVector GetDirtyRegionMax() const { return DirtyHi; }
     const std::vector<VVoxel>& GetVoxels() const { return Voxels; }
     std::vector<VVoxel>& GetVoxels() { return Voxels; }
 
@@ -84,6 +110,8 @@ private:
     unsigned VoxelCountAlongAxis = 0;
     VMaterial GeometryMaterial;
     bool DirtyFlag = true;
+    bool RegionDirty = false;
+    VIntVector DirtyLo, DirtyHi;
 };
 
 }  // namespace Voxel

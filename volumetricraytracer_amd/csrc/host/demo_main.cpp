@@ -12,6 +12,9 @@
  *            [--volumes texel16|f32]        device format of the volumes; default texel16, the reference's own 16-bit volume texel
  *            [--identity-defaults]          none of the reference's artefacts: unbound material slots are exact identities instead of its 1x1 default texels (its normal texel tilts by 0.3 degrees), unit view vector, clamped normal taps
  *            [--block N]                    N frames of the animation per RenderBlock call (ONE march launch per N frames) instead of one Render() per frame
+ *            [--edit-brush R]               every frame carves a sphere of radius R cells out of the red sphere's volume along a circle (SetVoxel +
+ *                                           MakeDirtyRegion): the renderer updates the edited box in place (vrt_volume_update_voxels)
+ *            [--edit-full]                  ... and uploads the whole volume after every edit instead (the same frames)
  */
 #include <chrono>
 #include <cmath>
@@ -64,6 +67,8 @@ int main(int argc, char** argv) {
     unsigned W = 1024, H = 576;
     std::string scenePath, skyboxDir, outPath = "vrt_demo.ppm";
     bool identityDefaults = false;
+    int editBrush = 0;
+    bool editFull = false;
     int mode = 0, inFlight = 3, block = 0; /* three frames in flight: the reference's swap chain (FrameCount, DXConstants.cpp:23) */
     std::string format = "bgra8", volumes = "texel16";
     for (int i = 1; i < argc; i++) {
@@ -78,6 +83,8 @@ int main(int argc, char** argv) {
         else if (!strcmp(argv[i], "--block") && i + 1 < argc) block = atoi(argv[++i]);
         else if (!strcmp(argv[i], "--volumes") && i + 1 < argc) volumes = argv[++i];
         else if (!strcmp(argv[i], "--identity-defaults")) identityDefaults = true;
+        else if (!strcmp(argv[i], "--edit-brush") && i + 1 < argc) editBrush = atoi(argv[++i]);
+        else if (!strcmp(argv[i], "--edit-full")) editFull = true;
     }
 
     std::shared_ptr<Renderer::VRenderer> renderer = Renderer::VRendererFactory::NewRenderer();
@@ -126,11 +133,41 @@ int main(int argc, char** argv) {
     if (hip) hip->FrameFormat = format == "float" ? Fmt::Float4 : (format == "rgba8" ? Fmt::RGBA8 : Fmt::BGRA8);
     if (hip) hip->VolumeFormat = volumes == "f32" ? VRT_FORMAT_F32 : VRT_FORMAT_TEXEL16;
     if (hip) hip->ReferenceDefaultTextures = hip->ReferenceViewVector = hip->ReferenceBoundaryTexels = !identityDefaults;
+    if (hip) hip->RegionUploads = !editFull;
+    if (editBrush > 0 && block > 0) {
+        fprintf(stderr, "--edit-brush edits the volume every frame: RenderBlock refuses that; drop --block\n");
+        return 1;
+    }
     double kernel_ms = 0.0;
+    /* the brush: a sphere of editBrush cells around a point that circles the red sphere's centre 12 cells out, 4 cells above it;
+       union (CSG difference) with the field, the box it can change marked dirty */
+    auto carve = [&](int f) {
+        Voxel::VVoxelVolume& vol = *sphere1->GetVoxelVolume();
+        const int n = (int)vol.GetSize(), r = editBrush;
+        const float a = (float)f * 0.15f, cell = vol.GetCellSize();
+        const VIntVector c(n / 2 + (int)std::lround(12.f * std::cos(a)), n / 2 + 4, n / 2 + (int)std::lround(12.f * std::sin(a)));
+        const VIntVector lo(c.X - r, c.Y - r, c.Z - r), hi(c.X + r, c.Y + r, c.Z + r);
+        for (int x = lo.X; x <= hi.X; x++)
+            for (int y = lo.Y; y <= hi.Y; y++)
+                for (int z = lo.Z; z <= hi.Z; z++) {
+                    const VIntVector idx(x, y, z);
+                    if (!vol.IsValidVoxelIndex(idx)) continue;
+                    const float dx = (float)(x - c.X), dy = (float)(y - c.Y), dz = (float)(z - c.Z);
+                    Voxel::VVoxel v = vol.GetVoxel(idx);
+                    const float carved = ((float)r - std::sqrt(dx * dx + dy * dy + dz * dz)) * cell;
+                    if (carved > v.Density) {
+                        v.Density = carved;
+                        v.Material = 0;
+                        vol.SetVoxel(idx, v);
+                    }
+                }
+        vol.MakeDirtyRegion(lo, hi);
+    };
     auto tick = [&](int f) {                                                     /* TickEngineInstance */
         const float dt = 1.f / 60.f, angle = (float)f * dt * 0.5f;
         sphere1->Position = VQuat::FromAxisAngle(VVector::UP, angle) * rel1;
         sphere2->Position = VQuat::FromAxisAngle(VVector::RIGHT, angle) * rel2;
+        if (editBrush > 0) carve(f);
         scene->Touch();
     };
     /* one untimed frame / block first: the pinned frame buffers and the device buffers of this size are allocated by the first call */
@@ -163,6 +200,7 @@ int main(int argc, char** argv) {
         if (hip) hip->Flush(); /* collect the frames still in flight: GetFrameData() is the last frame again */
     }
     const double wall = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
+    if (editBrush > 0) printf("brush of %d cells, %s; ", editBrush, editFull ? "full uploads" : "region updates");
     printf("%d frames %ux%u %s%s: %.3f ms/frame wall (%.0f frames/s)", frames, W, H, format.c_str(),
            block > 0 ? (", RenderBlock of " + std::to_string(block)).c_str() : (", " + std::to_string(inFlight) + " in flight").c_str(), wall / frames * 1e3, frames / wall);
     if (kernel_ms > 0.0) printf(", march kernel %.3f ms/%s", kernel_ms / (block > 0 ? (frames + block - 1) / block : frames), block > 0 ? "block" : "frame");

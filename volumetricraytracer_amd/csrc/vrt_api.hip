@@ -120,6 +120,10 @@ struct DeviceVolume {
     unsigned* nib = nullptr;      /* nb^3 words: the empty-space table, level 2 (sub-block nibbles) */
     bool skip_valid = false;      /* tables built for the current metric (only when step_max > 0) */
     uint8_t* cube_skip = nullptr; /* 2 x nb^3 bytes: the Cube modes' distance-to-solid table and its build scratch */
+    /* vrt_volume_update_region: 2 x nb^3 bytes, the seeds (0 / 255) of the level-1 table and of the Cube table — the tables keep
+       distances, from which the seeds cannot be recovered.  Built by the first update after an upload or a metric change. */
+    uint8_t* seeds = nullptr;
+    bool seeds_valid = false;
 };
 
 /* The small read-only arrays a launch dereferences, in ONE device allocation so that a frame in flight can keep its
@@ -198,6 +202,13 @@ struct DeviceState {
     bool peer_to_first = false;  /* this device maps device 0's memory (hipDeviceEnablePeerAccess succeeded): the strided 2D gather copy may be used */
     int last_slot = 0;
     unsigned* d_diag = nullptr;  /* allocated on first use of VRT_FLAG_DIAG_TIMELINE (never in a capture) */
+    /* vrt_volume_update_region: the box's staging copy and the level-2 table's region scratch (grown on demand, shared by the
+       slots), and the near bricks' box of the level-1 table */
+    void* edit_staging = nullptr;
+    size_t edit_staging_cap = 0;
+    void* edit_scratch = nullptr;
+    size_t edit_scratch_cap = 0;
+    int* d_box6 = nullptr;
     int last_blocks = 0;         /* workgroups per frame of the last launch */
     int last_frames = 1;         /* frames of the last launch: vrt_last_timing / vrt_debug_wave_records read its LAST frame's records */
     bool last_diag = false;
@@ -519,6 +530,7 @@ int free_device_volume(DeviceState& D, int slot) {
     if (v.skip) HIP_TRY(hipFree(v.skip));
     if (v.nib) HIP_TRY(hipFree(v.nib));
     if (v.cube_skip) HIP_TRY(hipFree(v.cube_skip));
+    if (v.seeds) HIP_TRY(hipFree(v.seeds));
     v = DeviceVolume();
     return VRT_OK;
 }
@@ -551,7 +563,11 @@ void destroy_device(DeviceState& D) {
         if (D.vol[i].skip) (void)hipFree(D.vol[i].skip);
         if (D.vol[i].nib) (void)hipFree(D.vol[i].nib);
         if (D.vol[i].cube_skip) (void)hipFree(D.vol[i].cube_skip);
+        if (D.vol[i].seeds) (void)hipFree(D.vol[i].seeds);
     }
+    if (D.edit_staging) (void)hipFree(D.edit_staging);
+    if (D.edit_scratch) (void)hipFree(D.edit_scratch);
+    if (D.d_box6) (void)hipFree(D.d_box6);
     if (D.d_vols) (void)hipFree(D.d_vols);
     if (D.d_inst) (void)hipFree(D.d_inst);
     if (D.d_nodes) (void)hipFree(D.d_nodes);
@@ -695,6 +711,89 @@ int upload_volume(vrt_ctx* ctx, int slot, uint8_t resolution, float extent, cons
     ctx->scene_stale = true;
     int rc = rebuild_skip(ctx, slot);
     if (rc != VRT_OK) return rc;
+    return sync_volume_table(ctx);
+}
+
+/* Grows a per-device cache buffer to at least `bytes` (its contents are not kept). */
+int ensure_buffer(void*& p, size_t& cap, size_t bytes) {
+    if (cap >= bytes) return VRT_OK;
+    if (p) HIP_TRY(hipFree(p));
+    p = nullptr;
+    cap = 0;
+    HIP_TRY(hipMalloc(&p, bytes));
+    cap = bytes;
+    return VRT_OK;
+}
+
+/* vrt_volume_update_region / _update_voxels: the box's samples in place on every device, then every structure the full upload derives
+ * from them, only where the box can change it: bricks and cell records of the bricks whose samples meet the box, the seeds
+ * of the bricks it touches, both brick-distance tables from their seeds (three passes each), and the level-2 table around the cells
+ * whose flags may change (launch_nibble_region).  Afterwards every buffer equals what upload_volume builds from the edited volume. */
+int update_region(vrt_ctx* ctx, int slot, const int origin[3], const int size[3], const float* density, const uint8_t* material,
+                  const vrt_voxel* voxels) {
+    if (!ctx || !origin || !size || (!density && !voxels)) return VRT_ERR_INVALID;
+    if (!valid_slot(slot) || !ctx->vol[slot].used) return VRT_ERR_SLOT;
+    HostVolume& h = ctx->vol[slot];
+    const int N = h.N, C = N - 1, nb = h.nb;
+    for (int a = 0; a < 3; a++)
+        if (size[a] < 1 || origin[a] < 0 || (long long)origin[a] + size[a] > N) return VRT_ERR_INVALID;
+    EditBox samples, cells, bricks; /* in the grid's axis order {x, z, y} */
+    for (int a = 0; a < 3; a++) {
+        const int ax = a == 0 ? 0 : (a == 1 ? 2 : 1);
+        const int lo = origin[ax], hi = origin[ax] + size[ax] - 1;
+        samples.lo[a] = lo;
+        samples.n[a] = size[ax];
+        cells.lo[a] = std::max(lo - 1, 0); /* cells with a corner in the box */
+        cells.n[a] = std::min(hi, C - 1) - cells.lo[a] + 1;
+        /* bricks whose 5^3 (clamped) samples meet the box, [ceil((lo - 4) / 4), floor(hi / 4)]: the same range holds the cell records of
+           cells lo-1..hi and the Cube seeds of samples lo..hi */
+        bricks.lo[a] = lo > 0 ? (lo - 1) / kBrickCells : 0;
+        bricks.n[a] = std::min(hi / kBrickCells, nb - 1) - bricks.lo[a] + 1;
+    }
+    const size_t count = (size_t)size[0] * size[1] * size[2];
+    const size_t staged = voxels ? count * sizeof(vrt_voxel) : count * (sizeof(float) + (material ? 1 : 0));
+    const bool texel16 = h.format == VRT_FORMAT_TEXEL16;
+    const float scale = texel16 ? h.density_scale * 0.01f : h.density_scale;
+    const size_t n = (size_t)nb * nb * nb;
+    const EditBox all = {{0, 0, 0}, {nb, nb, nb}};
+    for (auto& D : ctx->dev) { /* frames already enqueued render the old volume */
+        HIP_TRY(hipSetDevice(D.ordinal));
+        HIP_TRY(hipDeviceSynchronize());
+    }
+    int box[6];
+    memcpy(box, h.abox, sizeof box);
+    for (auto& D : ctx->dev) {
+        HIP_TRY(hipSetDevice(D.ordinal));
+        DeviceVolume& v = D.vol[slot];
+        int rc = ensure_buffer(D.edit_staging, D.edit_staging_cap, staged);
+        if (rc != VRT_OK) return rc;
+        if (voxels) {
+            HIP_TRY(hipMemcpyAsync(D.edit_staging, voxels, staged, hipMemcpyHostToDevice, D.stream));
+        } else {
+            HIP_TRY(hipMemcpyAsync(D.edit_staging, density, count * sizeof(float), hipMemcpyHostToDevice, D.stream));
+            if (material)
+                HIP_TRY(hipMemcpyAsync(static_cast<char*>(D.edit_staging) + count * sizeof(float), material, count, hipMemcpyHostToDevice, D.stream));
+        }
+        HIP_TRY(launch_scatter_region(D.edit_staging, voxels != nullptr, material != nullptr, texel16, v.dense, v.material, N, samples, D.stream));
+        HIP_TRY(launch_retile_region(v.dense, v.bricks, texel16 ? v.cells : nullptr, h.format, N, nb, bricks, D.stream));
+        const bool tables = v.skip_valid; /* the two-level empty-space table is live (step_max > 0) */
+        if (!v.seeds) HIP_TRY(hipMalloc(&v.seeds, 2 * n));
+        HIP_TRY(launch_seeds_region(v.dense, tables ? v.seeds : nullptr, v.seeds + n, N, nb, scale, h.step_max, v.seeds_valid ? bricks : all,
+                                    D.stream));
+        v.seeds_valid = true;
+        HIP_TRY(launch_seed_distance(v.seeds + n, v.cube_skip, v.cube_skip + n, nb, false, nullptr, D.stream));
+        if (tables) {
+            if (!D.d_box6) HIP_TRY(hipMalloc(&D.d_box6, sizeof box));
+            HIP_TRY(launch_seed_distance(v.seeds, v.skip, v.skip + n, nb, true, D.d_box6, D.stream));
+            rc = ensure_buffer(D.edit_scratch, D.edit_scratch_cap, nibble_region_scratch_bytes(N, cells));
+            if (rc != VRT_OK) return rc;
+            HIP_TRY(launch_nibble_region(v.dense, v.nib, D.edit_scratch, N, nb, scale, h.step_max, cells, D.stream));
+            HIP_TRY(hipMemcpyAsync(box, D.d_box6, sizeof box, hipMemcpyDeviceToHost, D.stream));
+        }
+        HIP_TRY(hipStreamSynchronize(D.stream));
+    }
+    memcpy(h.abox, box, sizeof box); /* unchanged without the tables, as upload_volume leaves it */
+    ctx->scene_stale = true;
     return sync_volume_table(ctx);
 }
 
@@ -1307,6 +1406,51 @@ int vrt_volume_download(vrt_ctx* ctx, int slot, vrt_voxel* out) {
     return VRT_OK;
 }
 
+int vrt_volume_update_region(vrt_ctx* ctx, int slot, const int origin_xyz[3], const int size_xyz[3], const float* density,
+                             const uint8_t* material_or_null) {
+    return update_region(ctx, slot, origin_xyz, size_xyz, density, material_or_null, nullptr);
+}
+
+int vrt_volume_update_voxels(vrt_ctx* ctx, int slot, const int origin_xyz[3], const int size_xyz[3], const vrt_voxel* voxels) {
+    return update_region(ctx, slot, origin_xyz, size_xyz, nullptr, nullptr, voxels);
+}
+
+int vrt_debug_volume_bytes(vrt_ctx* ctx, int slot, int device_index, int which, void* out, size_t capacity, size_t* size_out) {
+    if (!ctx) return VRT_ERR_INVALID;
+    if (!valid_slot(slot) || !ctx->vol[slot].used) return VRT_ERR_SLOT;
+    if (device_index < 0 || device_index >= (int)ctx->dev.size()) return VRT_ERR_INVALID;
+    DeviceState& D = ctx->dev[(size_t)device_index];
+    const HostVolume& h = ctx->vol[slot];
+    const DeviceVolume& v = D.vol[slot];
+    const size_t count = (size_t)h.N * h.N * h.N, n = (size_t)h.nb * h.nb * h.nb;
+    const bool texel16 = h.format == VRT_FORMAT_TEXEL16;
+    const void* src = nullptr;
+    size_t bytes = 0;
+    switch (which) {
+        case VRT_VOLUME_BYTES_DENSE: src = v.dense; bytes = count * sizeof(float); break;
+        case VRT_VOLUME_BYTES_MATERIAL: src = v.material; bytes = count; break;
+        case VRT_VOLUME_BYTES_BRICKS: src = v.bricks; bytes = n * kBrickFloats * (texel16 ? sizeof(short) : sizeof(float)); break;
+        case VRT_VOLUME_BYTES_CELLS: src = v.cells; bytes = texel16 ? n * 64 * 16 : 0; break;
+        case VRT_VOLUME_BYTES_SKIP: src = v.skip; bytes = v.skip_valid ? n : 0; break;
+        case VRT_VOLUME_BYTES_NIB: src = v.nib; bytes = v.skip_valid ? n * sizeof(unsigned) : 0; break;
+        case VRT_VOLUME_BYTES_CUBE_SKIP: src = v.cube_skip; bytes = n; break;
+        case VRT_VOLUME_BYTES_ACTIVE_BOX: bytes = sizeof h.abox; break;
+        default: return VRT_ERR_INVALID;
+    }
+    if (size_out) *size_out = bytes;
+    if (!out) return VRT_OK;
+    if (capacity < bytes) return VRT_ERR_INVALID;
+    if (which == VRT_VOLUME_BYTES_ACTIVE_BOX) {
+        memcpy(out, h.abox, bytes);
+        return VRT_OK;
+    }
+    if (bytes == 0) return VRT_OK;
+    HIP_TRY(hipSetDevice(D.ordinal));
+    HIP_TRY(hipDeviceSynchronize());
+    HIP_TRY(hipMemcpy(out, src, bytes, hipMemcpyDeviceToHost));
+    return VRT_OK;
+}
+
 int vrt_volume_set_material(vrt_ctx* ctx, int slot, const vrt_material* material) {
     if (!ctx || !material) return VRT_ERR_INVALID;
     if (!valid_slot(slot) || !ctx->vol[slot].used) return VRT_ERR_SLOT;
@@ -1325,6 +1469,7 @@ int vrt_volume_set_metric(vrt_ctx* ctx, int slot, float density_scale, float ste
     }
     ctx->vol[slot].density_scale = density_scale;
     ctx->vol[slot].step_max = step_max;
+    for (auto& D : ctx->dev) D.vol[slot].seeds_valid = false; /* the level-1 seeds depend on the metric */
     ctx->scene_stale = true;
     int rc = rebuild_skip(ctx, slot);
     if (rc != VRT_OK) return rc;

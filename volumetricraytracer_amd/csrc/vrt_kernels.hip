@@ -2230,12 +2230,8 @@ __global__ __launch_bounds__(kBlockThreads) void march_kernel_coop(const DBlock 
 }
 
 /* dense N^3 grid → 4^3-cell bricks with a one-sample apron (5^3 samples, padded to 128 floats). */
-__global__ __launch_bounds__(128) void retile_bricks_kernel(const float* __restrict__ dense, float* __restrict__ bricks,
-                                                            int N, int nb) {
-    const int brick = (int)blockIdx.x; /* (bx*nb + bz)*nb + by */
-    const int by = brick % nb;
-    const int bz = (brick / nb) % nb;
-    const int bx = brick / (nb * nb);
+__device__ __forceinline__ void retile_brick(const float* __restrict__ dense, float* __restrict__ bricks, int N, int brick, int bx, int by,
+                                             int bz) {
     const int l = (int)threadIdx.x;
     float v = 0.0f;
     if (l < 125) {
@@ -2248,13 +2244,15 @@ __global__ __launch_bounds__(128) void retile_bricks_kernel(const float* __restr
     }
     bricks[(size_t)brick * kBrickFloats + l] = v;
 }
+__global__ __launch_bounds__(128) void retile_bricks_kernel(const float* __restrict__ dense, float* __restrict__ bricks,
+                                                            int N, int nb) {
+    const int brick = (int)blockIdx.x; /* (bx*nb + bz)*nb + by */
+    retile_brick(dense, bricks, N, brick, brick / (nb * nb), brick % nb, (brick / nb) % nb);
+}
 
 /* The same for VRT_FORMAT_TEXEL16 volumes: the dense grid holds the integer field +-q as floats; bricks of 128 int16. */
-__global__ __launch_bounds__(128) void retile_bricks16_kernel(const float* __restrict__ dense, short* __restrict__ bricks, int N, int nb) {
-    const int brick = (int)blockIdx.x;
-    const int by = brick % nb;
-    const int bz = (brick / nb) % nb;
-    const int bx = brick / (nb * nb);
+__device__ __forceinline__ void retile_brick16(const float* __restrict__ dense, short* __restrict__ bricks, int N, int brick, int bx, int by,
+                                               int bz) {
     const int l = (int)threadIdx.x;
     short v = 0;
     if (l < 125) {
@@ -2267,12 +2265,15 @@ __global__ __launch_bounds__(128) void retile_bricks16_kernel(const float* __res
     }
     bricks[(size_t)brick * kBrickFloats + l] = v;
 }
+__global__ __launch_bounds__(128) void retile_bricks16_kernel(const float* __restrict__ dense, short* __restrict__ bricks, int N, int nb) {
+    const int brick = (int)blockIdx.x;
+    retile_brick16(dense, bricks, N, brick, brick / (nb * nb), brick % nb, (brick / nb) % nb);
+}
 
 /* VRT_PATH_CELLS: the 8 corner texels of every cell as one 16-byte record (cells beyond the grid repeat the last sample,
  * like the bricks' apron). */
-__global__ __launch_bounds__(64) void retile_cells16_kernel(const float* __restrict__ dense, short* __restrict__ cells, int N, int nb) {
-    const int brick = (int)blockIdx.x;
-    const int by = brick % nb, bz = (brick / nb) % nb, bx = brick / (nb * nb);
+__device__ __forceinline__ void retile_cells16(const float* __restrict__ dense, short* __restrict__ cells, int N, int brick, int bx, int by,
+                                               int bz) {
     const int l = (int)threadIdx.x; /* record lx*16 + lz*4 + ly */
     const int lx = l >> 4, lz = (l >> 2) & 3, ly = l & 3;
     short v[8];
@@ -2289,6 +2290,10 @@ __global__ __launch_bounds__(64) void retile_cells16_kernel(const float* __restr
     w.z = (unsigned)(unsigned short)v[4] | ((unsigned)(unsigned short)v[5] << 16);
     w.w = (unsigned)(unsigned short)v[6] | ((unsigned)(unsigned short)v[7] << 16);
     reinterpret_cast<uint4v*>(cells)[(size_t)brick * 64 + l] = w;
+}
+__global__ __launch_bounds__(64) void retile_cells16_kernel(const float* __restrict__ dense, short* __restrict__ cells, int N, int nb) {
+    const int brick = (int)blockIdx.x;
+    retile_cells16(dense, cells, N, brick, brick / (nb * nb), brick % nb, (brick / nb) % nb);
 }
 
 /* VRT_FORMAT_TEXEL16: a density as the reference's volume texel keeps it — sign + 15-bit trunc(|d| * 100)
@@ -2326,6 +2331,15 @@ __global__ void texels_to_field_kernel(const uchar4* __restrict__ texels, float*
 
 /* Empty-space table, level 2 (oracle: build_nibble_table).  Step 1: a cell is ACTIVE when one of its 8 corners holds a
  * trustworthy distance below the clamp. */
+__device__ __forceinline__ uint8_t cell_active(const float* __restrict__ dense, int N, size_t x, size_t z, size_t y, float density_scale,
+                                               float step_max) {
+    bool a = false;
+    for (int k = 0; k < 8; k++) {
+        const size_t xx = x + (k >> 2), zz = z + ((k >> 1) & 1), yy = y + (k & 1);
+        a = a || dense[(xx * N + zz) * N + yy] * density_scale < step_max;
+    }
+    return a ? 1 : 0;
+}
 __global__ void active_cells_kernel(const float* __restrict__ dense, uint8_t* __restrict__ act, int N, float density_scale, float step_max) {
     const int C = N - 1;
     const size_t count = (size_t)C * C * C;
@@ -2333,12 +2347,7 @@ __global__ void active_cells_kernel(const float* __restrict__ dense, uint8_t* __
     const size_t stride = (size_t)gridDim.x * blockDim.x;
     for (; i < count; i += stride) {
         const size_t x = i / ((size_t)C * C), z = (i / C) % C, y = i % C;
-        bool a = false;
-        for (int k = 0; k < 8; k++) {
-            const size_t xx = x + (k >> 2), zz = z + ((k >> 1) & 1), yy = y + (k & 1);
-            a = a || dense[(xx * N + zz) * N + yy] * density_scale < step_max;
-        }
-        act[i] = a ? 1 : 0;
+        act[i] = cell_active(dense, N, x, z, y, density_scale, step_max);
     }
 }
 
@@ -2370,19 +2379,13 @@ __global__ void edt_pass_kernel(const uint8_t* __restrict__ act, const uint16_t*
     }
 }
 
-/* Step 5: per brick the eight sub-block nibbles: min over the sub-block's cells of floor(sqrt(d2)), capped at 15. */
-__global__ __launch_bounds__(64) void nibble_kernel(const uint16_t* __restrict__ d2, unsigned* __restrict__ nib, int C, int nb) {
-    const int brick = (int)blockIdx.x;
-    const int by = brick % nb, bz = (brick / nb) % nb, bx = brick / (nb * nb);
-    const int l = (int)threadIdx.x; /* one lane per cell */
-    const int lx = l >> 4, lz = (l >> 2) & 3, ly = l & 3;
-    const int x = bx * 4 + lx, y = by * 4 + ly, z = bz * 4 + lz;
-    int r = 15;
-    if (x < C && y < C && z < C) {
-        const int v = d2[((size_t)x * C + z) * C + y];
-        r = 0;
-        while (r < 15 && (r + 1) * (r + 1) <= v) r++;
-    }
+/* floor(sqrt(d2)) capped at 15, and the eight sub-block nibbles of a brick from its 64 lanes' values (lane = cell lx*16 + lz*4 + ly). */
+__device__ __forceinline__ int capped_root(int v) {
+    int r = 0;
+    while (r < 15 && (r + 1) * (r + 1) <= v) r++;
+    return r;
+}
+__device__ __forceinline__ unsigned nibble_word(int r, int lx, int lz, int ly) {
     unsigned w = 0;
     for (int k = 0; k < 8; k++) {
         const bool mine = ((lx >> 1) * 4 + (lz >> 1) * 2 + (ly >> 1)) == k;
@@ -2394,17 +2397,28 @@ __global__ __launch_bounds__(64) void nibble_kernel(const uint16_t* __restrict__
         }
         w |= (unsigned)m << (4 * k);
     }
+    return w;
+}
+
+/* Step 5: per brick the eight sub-block nibbles: min over the sub-block's cells of floor(sqrt(d2)), capped at 15. */
+__global__ __launch_bounds__(64) void nibble_kernel(const uint16_t* __restrict__ d2, unsigned* __restrict__ nib, int C, int nb) {
+    const int brick = (int)blockIdx.x;
+    const int by = brick % nb, bz = (brick / nb) % nb, bx = brick / (nb * nb);
+    const int l = (int)threadIdx.x; /* one lane per cell */
+    const int lx = l >> 4, lz = (l >> 2) & 3, ly = l & 3;
+    const int x = bx * 4 + lx, y = by * 4 + ly, z = bz * 4 + lz;
+    int r = 15;
+    if (x < C && y < C && z < C) r = capped_root(d2[((size_t)x * C + z) * C + y]);
+    const unsigned w = nibble_word(r, lx, lz, ly);
     if (l == 0) nib[brick] = w;
 }
 
 /* Empty-space table, level 1, step 1: a brick is "near" (0) when any of its 5^3 samples holds a trustworthy
  * distance below the clamp, density*density_scale < step_max (equivalently: when it holds an active cell); everything
  * else starts at 255.  Samples come from the dense grid (whatever the brick format). */
-__global__ __launch_bounds__(128) void skip_seed_kernel(const float* __restrict__ dense, uint8_t* __restrict__ table, int N, int nb,
-                                                        float density_scale, float step_max) {
-    const int brick = (int)blockIdx.x;
+__device__ __forceinline__ void skip_seed(const float* __restrict__ dense, uint8_t* __restrict__ table, int N, int brick, int bx, int by, int bz,
+                                          float density_scale, float step_max) {
     const int l = (int)threadIdx.x;
-    const int by = brick % nb, bz = (brick / nb) % nb, bx = brick / (nb * nb);
     bool near = false;
     if (l < 125) {
         const int lx = l / 25, lz = (l / 5) % 5, ly = l % 5;
@@ -2419,6 +2433,11 @@ __global__ __launch_bounds__(128) void skip_seed_kernel(const float* __restrict_
     if ((l & 63) == 0) flag[l >> 6] = any0 != 0ull;
     __syncthreads();
     if (l == 0) table[brick] = (flag[0] || flag[1]) ? 0 : 255;
+}
+__global__ __launch_bounds__(128) void skip_seed_kernel(const float* __restrict__ dense, uint8_t* __restrict__ table, int N, int nb,
+                                                        float density_scale, float step_max) {
+    const int brick = (int)blockIdx.x;
+    skip_seed(dense, table, N, brick, brick / (nb * nb), brick % nb, (brick / nb) % nb, density_scale, step_max);
 }
 
 /* Bounding box, in bricks, of the near bricks (distance 0): box = {min x, z, y, max x, z, y}, preset to {nb.., -1..}. */
@@ -2446,16 +2465,18 @@ __global__ void skip_to_leap_kernel(uint8_t* __restrict__ table, int n) {
 /* Cube modes' table, step 1: a brick is a seed (0) when one of its 4^3 cell-origin voxels is solid
  * (density <= 0); voxels beyond cell N-2 do not exist (only at resolutions < 2, where one brick covers
  * the volume). */
-__global__ __launch_bounds__(64) void cube_seed_kernel(const float* __restrict__ dense, uint8_t* __restrict__ table, int N, int nb) {
-    const int brick = (int)blockIdx.x;
+__device__ __forceinline__ void cube_seed(const float* __restrict__ dense, uint8_t* __restrict__ table, int N, int brick, int bx, int by, int bz) {
     const int l = (int)threadIdx.x;
-    const int by = brick % nb, bz = (brick / nb) % nb, bx = brick / (nb * nb);
     const int lx = l >> 4, lz = (l >> 2) & 3, ly = l & 3;
     const int x = bx * 4 + lx, y = by * 4 + ly, z = bz * 4 + lz;
     bool solid = false;
     if (x <= N - 2 && y <= N - 2 && z <= N - 2) solid = dense[((size_t)x * N + z) * N + y] <= 0.0f;
     const unsigned long long any0 = __ballot(solid);
     if (l == 0) table[brick] = any0 != 0ull ? 0 : 255;
+}
+__global__ __launch_bounds__(64) void cube_seed_kernel(const float* __restrict__ dense, uint8_t* __restrict__ table, int N, int nb) {
+    const int brick = (int)blockIdx.x;
+    cube_seed(dense, table, N, brick, brick / (nb * nb), brick % nb, (brick / nb) % nb);
 }
 
 /* Step k of the exact Chebyshev distance transform: bricks still at 255 that touch (3x3x3) a brick at
@@ -2477,6 +2498,151 @@ __global__ void skip_dilate_kernel(const uint8_t* __restrict__ cur, uint8_t* __r
         if (hit) d = (uint8_t)k;
     }
     nxt[i] = d;
+}
+
+/* ---- incremental volume edits (vrt_volume_update_region) ---------------------------------------------------------------
+ * Every kernel below recomputes one region of a structure the full upload builds, with the same per-element arithmetic as the
+ * full build's kernel (shared through the helpers above), so that the edited slot ends byte-identical to a full upload. */
+
+__device__ __forceinline__ size_t box_count(const EditBox& b) { return (size_t)b.n[0] * b.n[1] * b.n[2]; }
+/* local index (x slowest, then z, then y) -> global coordinates */
+__device__ __forceinline__ void box_coords(const EditBox& b, size_t i, int& x, int& z, int& y) {
+    y = b.lo[2] + (int)(i % (size_t)b.n[2]);
+    z = b.lo[1] + (int)((i / (size_t)b.n[2]) % (size_t)b.n[1]);
+    x = b.lo[0] + (int)(i / ((size_t)b.n[1] * b.n[2]));
+}
+__device__ __forceinline__ size_t box_index(const EditBox& b, int x, int z, int y) {
+    return ((size_t)(x - b.lo[0]) * b.n[1] + (size_t)(z - b.lo[1])) * b.n[2] + (size_t)(y - b.lo[2]);
+}
+
+/* The staged box -> dense grid + materials.  VOXELS: 8-byte VVoxel records (split_voxels_kernel); otherwise box floats followed,
+ * when has_material, by box bytes.  texel16: quantised like quantize_field_kernel. */
+template <bool VOXELS>
+__global__ void scatter_region_kernel(const void* __restrict__ staging, float* __restrict__ dense, uint8_t* __restrict__ material, int N,
+                                      EditBox b, int texel16, int has_material) {
+    const size_t count = box_count(b);
+    size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    const size_t stride = (size_t)gridDim.x * blockDim.x;
+    for (; i < count; i += stride) {
+        int x, z, y;
+        box_coords(b, i, x, z, y);
+        const size_t g = ((size_t)x * N + z) * N + y;
+        float d;
+        if constexpr (VOXELS) {
+            const uint2 r = static_cast<const uint2*>(staging)[i];
+            d = __uint_as_float(r.y);
+            material[g] = (uint8_t)(r.x & 0xffu);
+        } else {
+            d = static_cast<const float*>(staging)[i];
+            if (has_material) material[g] = static_cast<const uint8_t*>(staging)[count * sizeof(float) + i];
+        }
+        dense[g] = texel16 ? texel16_value(d) : d;
+    }
+}
+
+/* One workgroup per brick of a brick box. */
+__device__ __forceinline__ int region_brick(const EditBox& b, int nb, int& bx, int& by, int& bz) {
+    box_coords(b, blockIdx.x, bx, bz, by);
+    return (bx * nb + bz) * nb + by;
+}
+__global__ __launch_bounds__(128) void retile_region_kernel(const float* __restrict__ dense, float* __restrict__ bricks, int N, int nb, EditBox b) {
+    int bx, by, bz;
+    const int brick = region_brick(b, nb, bx, by, bz);
+    retile_brick(dense, bricks, N, brick, bx, by, bz);
+}
+__global__ __launch_bounds__(128) void retile_region16_kernel(const float* __restrict__ dense, short* __restrict__ bricks, int N, int nb, EditBox b) {
+    int bx, by, bz;
+    const int brick = region_brick(b, nb, bx, by, bz);
+    retile_brick16(dense, bricks, N, brick, bx, by, bz);
+}
+__global__ __launch_bounds__(64) void retile_cells16_region_kernel(const float* __restrict__ dense, short* __restrict__ cells, int N, int nb, EditBox b) {
+    int bx, by, bz;
+    const int brick = region_brick(b, nb, bx, by, bz);
+    retile_cells16(dense, cells, N, brick, bx, by, bz);
+}
+__global__ __launch_bounds__(128) void skip_seed_region_kernel(const float* __restrict__ dense, uint8_t* __restrict__ seeds, int N, int nb, EditBox b,
+                                                               float density_scale, float step_max) {
+    int bx, by, bz;
+    const int brick = region_brick(b, nb, bx, by, bz);
+    skip_seed(dense, seeds, N, brick, bx, by, bz, density_scale, step_max);
+}
+__global__ __launch_bounds__(64) void cube_seed_region_kernel(const float* __restrict__ dense, uint8_t* __restrict__ seeds, int N, int nb, EditBox b) {
+    int bx, by, bz;
+    const int brick = region_brick(b, nb, bx, by, bz);
+    cube_seed(dense, seeds, N, brick, bx, by, bz);
+}
+
+/* The exact Chebyshev distance (bricks) to the nearest seed (0) that dilate_table computes in nb launches, as three separable passes
+ * (the L-infinity distance nests per axis): out(p) = min over q on p's line along AXIS (0: y, 1: z, 2: x) of max(|p - q|, in(q)), in(q) = 255
+ * (no seed) skipped; no seed on any line stays 255.  LEAP: the pass stores the leap count of skip_to_leap_kernel instead. */
+template <int AXIS, bool LEAP>
+__global__ void seed_distance_pass_kernel(const uint8_t* __restrict__ in, uint8_t* __restrict__ out, int nb) {
+    const int i = (int)(blockIdx.x * blockDim.x + threadIdx.x);
+    if (i >= nb * nb * nb) return;
+    const int pitch = AXIS == 0 ? 1 : (AXIS == 1 ? nb : nb * nb);
+    const int pos = AXIS == 0 ? i % nb : (AXIS == 1 ? (i / nb) % nb : i / (nb * nb));
+    const uint8_t* line = in + (i - pos * pitch);
+    int best = 255;
+    for (int q = 0; q < nb; q++) {
+        const int v = line[q * pitch];
+        const int d = q > pos ? q - pos : pos - q;
+        const int m = d > v ? d : v;
+        best = (v != 255 && m < best) ? m : best;
+    }
+    if constexpr (LEAP) best = best > 1 ? best - 1 : 0;
+    out[i] = (uint8_t)best;
+}
+
+/* Level-2 table over a cell box: active flags (active_cells_kernel), the three windowed passes (edt_pass_kernel) from an input box
+ * `ib` that holds the output box `ob` grown by kNibWindow along AXIS, and the nibbles of a brick box (nibble_kernel). */
+__global__ void active_cells_region_kernel(const float* __restrict__ dense, uint8_t* __restrict__ act, int N, EditBox b, float density_scale,
+                                           float step_max) {
+    const size_t count = box_count(b);
+    size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    const size_t stride = (size_t)gridDim.x * blockDim.x;
+    for (; i < count; i += stride) {
+        int x, z, y;
+        box_coords(b, i, x, z, y);
+        act[i] = cell_active(dense, N, (size_t)x, (size_t)z, (size_t)y, density_scale, step_max);
+    }
+}
+template <int AXIS>
+__global__ void edt_region_pass_kernel(const uint8_t* __restrict__ act, const uint16_t* __restrict__ in, uint16_t* __restrict__ out, int C,
+                                       EditBox ib, EditBox ob) {
+    const size_t count = box_count(ob);
+    size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    const size_t stride = (size_t)gridDim.x * blockDim.x;
+    for (; i < count; i += stride) {
+        int x, z, y;
+        box_coords(ob, i, x, z, y);
+        const int pos = AXIS == 0 ? y : (AXIS == 1 ? z : x);
+        int best = 0xffff;
+        for (int d = -kNibWindow; d <= kNibWindow; d++) {
+            const int q = pos + d;
+            if (q < 0 || q >= C) continue;
+            const size_t j = AXIS == 0 ? box_index(ib, x, z, q) : (AXIS == 1 ? box_index(ib, x, q, y) : box_index(ib, q, z, y));
+            int g = (d < 0 ? -d : d);
+            g = g > 0 ? g - 1 : 0;
+            g *= g;
+            int v;
+            if constexpr (AXIS == 0) v = act[j] ? g : 0xffff;
+            else v = g + (int)in[j];
+            best = v < best ? v : best;
+        }
+        out[i] = (uint16_t)(best > 0xffff ? 0xffff : best);
+    }
+}
+__global__ __launch_bounds__(64) void nibble_region_kernel(const uint16_t* __restrict__ d2, unsigned* __restrict__ nib, int C, int nb, EditBox bricks,
+                                                           EditBox cells) {
+    int bx, by, bz;
+    const int brick = region_brick(bricks, nb, bx, by, bz);
+    const int l = (int)threadIdx.x;
+    const int lx = l >> 4, lz = (l >> 2) & 3, ly = l & 3;
+    const int x = bx * 4 + lx, y = by * 4 + ly, z = bz * 4 + lz;
+    int r = 15;
+    if (x < C && y < C && z < C) r = capped_root(d2[box_index(cells, x, z, y)]);
+    const unsigned w = nibble_word(r, lx, lz, ly);
+    if (l == 0) nib[brick] = w;
 }
 
 /* ---- device Voxelizer (Voxelizer/Private/VolumeConverter.cpp:161-252; arithmetic in voxelize_core.h) ------
@@ -2764,6 +2930,113 @@ static hipError_t dilate_table(uint8_t* table, uint8_t* scratch, int nb, hipStre
         hipError_t e = hipMemcpyAsync(table, cur, (size_t)n, hipMemcpyDeviceToDevice, stream);
         if (e != hipSuccess) return e;
     }
+    return hipGetLastError();
+}
+
+/* ---- vrt_volume_update_region ---- */
+static unsigned stride_grid(size_t count) { return (unsigned)std::max<size_t>(1, std::min<size_t>((count + 255) / 256, 1u << 16)); }
+static unsigned box_blocks(const EditBox& b) { return (unsigned)((size_t)b.n[0] * b.n[1] * b.n[2]); }
+
+hipError_t launch_scatter_region(const void* staging, bool voxels, bool has_material, bool texel16, float* dense, uint8_t* material, int N,
+                                 const EditBox& box, hipStream_t stream) {
+    const unsigned grid = stride_grid((size_t)box.n[0] * box.n[1] * box.n[2]);
+    if (voxels)
+        hipLaunchKernelGGL(scatter_region_kernel<true>, dim3(grid), dim3(256), 0, stream, staging, dense, material, N, box, (int)texel16, 1);
+    else
+        hipLaunchKernelGGL(scatter_region_kernel<false>, dim3(grid), dim3(256), 0, stream, staging, dense, material, N, box, (int)texel16,
+                           (int)has_material);
+    return hipGetLastError();
+}
+
+hipError_t launch_retile_region(const float* dense, void* bricks, void* cells_or_null, int format, int N, int nb, const EditBox& bricks_box,
+                                hipStream_t stream) {
+    const unsigned n = box_blocks(bricks_box);
+    if (format == VRT_FORMAT_TEXEL16)
+        hipLaunchKernelGGL(retile_region16_kernel, dim3(n), dim3(128), 0, stream, dense, static_cast<short*>(bricks), N, nb, bricks_box);
+    else
+        hipLaunchKernelGGL(retile_region_kernel, dim3(n), dim3(128), 0, stream, dense, static_cast<float*>(bricks), N, nb, bricks_box);
+    if (cells_or_null)
+        hipLaunchKernelGGL(retile_cells16_region_kernel, dim3(n), dim3(64), 0, stream, dense, static_cast<short*>(cells_or_null), N, nb, bricks_box);
+    return hipGetLastError();
+}
+
+hipError_t launch_seeds_region(const float* dense, uint8_t* skip_seeds_or_null, uint8_t* cube_seeds, int N, int nb, float density_scale,
+                               float step_max, const EditBox& bricks_box, hipStream_t stream) {
+    const unsigned n = box_blocks(bricks_box);
+    if (skip_seeds_or_null)
+        hipLaunchKernelGGL(skip_seed_region_kernel, dim3(n), dim3(128), 0, stream, dense, skip_seeds_or_null, N, nb, bricks_box, density_scale,
+                           step_max);
+    hipLaunchKernelGGL(cube_seed_region_kernel, dim3(n), dim3(64), 0, stream, dense, cube_seeds, N, nb, bricks_box);
+    return hipGetLastError();
+}
+
+hipError_t launch_seed_distance(const uint8_t* seeds, uint8_t* table, uint8_t* scratch, int nb, bool leap, int* box6_or_null, hipStream_t stream) {
+    const int n = nb * nb * nb;
+    const unsigned grid = (unsigned)((n + 255) / 256);
+    hipLaunchKernelGGL((seed_distance_pass_kernel<0, false>), dim3(grid), dim3(256), 0, stream, seeds, table, nb);
+    hipLaunchKernelGGL((seed_distance_pass_kernel<1, false>), dim3(grid), dim3(256), 0, stream, table, scratch, nb);
+    if (leap)
+        hipLaunchKernelGGL((seed_distance_pass_kernel<2, true>), dim3(grid), dim3(256), 0, stream, scratch, table, nb);
+    else
+        hipLaunchKernelGGL((seed_distance_pass_kernel<2, false>), dim3(grid), dim3(256), 0, stream, scratch, table, nb);
+    if (box6_or_null) {
+        const int preset[6] = {nb, nb, nb, -1, -1, -1};
+        hipError_t e = hipMemcpyAsync(box6_or_null, preset, sizeof preset, hipMemcpyHostToDevice, stream); /* pageable source: staged before return */
+        if (e != hipSuccess) return e;
+        hipLaunchKernelGGL(active_box_kernel, dim3(grid), dim3(256), 0, stream, seeds, nb, box6_or_null);
+    }
+    return hipGetLastError();
+}
+
+/* The boxes of a level-2 update whose active flags may change in the cell box `changed`: the windowed distance changes within
+   kNibWindow of it (final, rounded out to whole bricks: a nibble is a minimum over its brick's cells), and the passes read the flags
+   another kNibWindow further out (grown). */
+static void nibble_region_boxes(int C, const EditBox& changed, EditBox& bricks, EditBox& final_cells, EditBox& grown) {
+    for (int a = 0; a < 3; a++) {
+        const int f0 = std::max(changed.lo[a] - kNibWindow, 0);
+        const int f1 = std::min(changed.lo[a] + changed.n[a] - 1 + kNibWindow, C - 1);
+        const int b0 = f0 / kBrickCells, b1 = f1 / kBrickCells;
+        bricks.lo[a] = b0;
+        bricks.n[a] = b1 - b0 + 1;
+        final_cells.lo[a] = b0 * kBrickCells;
+        final_cells.n[a] = std::min(b1 * kBrickCells + kBrickCells - 1, C - 1) - final_cells.lo[a] + 1;
+        grown.lo[a] = std::max(final_cells.lo[a] - kNibWindow, 0);
+        grown.n[a] = std::min(final_cells.lo[a] + final_cells.n[a] - 1 + kNibWindow, C - 1) - grown.lo[a] + 1;
+    }
+}
+
+/* act: grown box; g: grown x, grown z, final y; h: grown x, final z, final y; the final distances go back into g */
+size_t nibble_region_scratch_bytes(int N, const EditBox& changed) {
+    EditBox bricks, fin, grown;
+    nibble_region_boxes(N - 1, changed, bricks, fin, grown);
+    const size_t act = (size_t)grown.n[0] * grown.n[1] * grown.n[2];
+    const size_t g = (size_t)grown.n[0] * grown.n[1] * fin.n[2];
+    const size_t h = (size_t)grown.n[0] * fin.n[1] * fin.n[2];
+    return ((act + 63) & ~(size_t)63) + 2 * (g + h);
+}
+
+hipError_t launch_nibble_region(const float* dense, unsigned* nib, void* scratch, int N, int nb, float density_scale, float step_max,
+                                const EditBox& changed, hipStream_t stream) {
+    const int C = N - 1;
+    EditBox bricks, fin, grown;
+    nibble_region_boxes(C, changed, bricks, fin, grown);
+    const size_t act_n = (size_t)grown.n[0] * grown.n[1] * grown.n[2];
+    EditBox gb = grown, hb = grown; /* outputs of the y and z passes */
+    gb.lo[2] = fin.lo[2];
+    gb.n[2] = fin.n[2];
+    hb.lo[1] = fin.lo[1];
+    hb.n[1] = fin.n[1];
+    hb.lo[2] = fin.lo[2];
+    hb.n[2] = fin.n[2];
+    uint8_t* act = static_cast<uint8_t*>(scratch);
+    uint16_t* g = reinterpret_cast<uint16_t*>(act + ((act_n + 63) & ~(size_t)63));
+    uint16_t* h = g + (size_t)gb.n[0] * gb.n[1] * gb.n[2];
+    auto cnt = [](const EditBox& b) { return (size_t)b.n[0] * b.n[1] * b.n[2]; };
+    hipLaunchKernelGGL(active_cells_region_kernel, dim3(stride_grid(act_n)), dim3(256), 0, stream, dense, act, N, grown, density_scale, step_max);
+    hipLaunchKernelGGL((edt_region_pass_kernel<0>), dim3(stride_grid(cnt(gb))), dim3(256), 0, stream, act, (const uint16_t*)nullptr, g, C, grown, gb);
+    hipLaunchKernelGGL((edt_region_pass_kernel<1>), dim3(stride_grid(cnt(hb))), dim3(256), 0, stream, act, g, h, C, gb, hb);
+    hipLaunchKernelGGL((edt_region_pass_kernel<2>), dim3(stride_grid(cnt(fin))), dim3(256), 0, stream, act, h, g, C, hb, fin);
+    hipLaunchKernelGGL(nibble_region_kernel, dim3(box_blocks(bricks)), dim3(64), 0, stream, g, nib, C, nb, bricks, fin);
     return hipGetLastError();
 }
 

@@ -39,4 +39,27 @@ hipError_t launch_gather_ceiling(const void* pool, unsigned n_bricks, int format
 hipError_t launch_split_voxels(const void* voxels, float* density, uint8_t* material, size_t count,
                                hipStream_t stream);
 
+/* vrt_volume_update_region: a box of samples, cells or bricks in the grid's own axis order {x, z, y}: [lo, lo + n) per axis. */
+struct EditBox {
+    int lo[3];
+    int n[3];
+};
+/* The staged box (VVoxel records, or floats followed by bytes when has_material; x slowest, then z, then y) -> dense + material,
+   quantised like launch_quantize_field when texel16. */
+hipError_t launch_scatter_region(const void* staging, bool voxels, bool has_material, bool texel16, float* dense, uint8_t* material, int N,
+                                 const EditBox& box, hipStream_t stream);
+/* launch_retile (and launch_retile_cells16 when cells_or_null) over the bricks of a brick box. */
+hipError_t launch_retile_region(const float* dense, void* bricks, void* cells_or_null, int format, int N, int nb, const EditBox& bricks_box,
+                                hipStream_t stream);
+/* The seeds (0 / 255) of the level-1 table (when skip_seeds_or_null) and of the Cube table over the bricks of a brick box. */
+hipError_t launch_seeds_region(const float* dense, uint8_t* skip_seeds_or_null, uint8_t* cube_seeds, int N, int nb, float density_scale,
+                               float step_max, const EditBox& bricks_box, hipStream_t stream);
+/* nb^3 seeds -> the table launch_skip_table (leap) / launch_cube_table (distance) builds, and the near bricks' box (box6_or_null);
+   scratch: nb^3 bytes. */
+hipError_t launch_seed_distance(const uint8_t* seeds, uint8_t* table, uint8_t* scratch, int nb, bool leap, int* box6_or_null, hipStream_t stream);
+/* Level-2 table where the active flags of the cell box `changed` may have changed. */
+size_t nibble_region_scratch_bytes(int N, const EditBox& changed);
+hipError_t launch_nibble_region(const float* dense, unsigned* nib, void* scratch, int N, int nb, float density_scale, float step_max,
+                                const EditBox& changed, hipStream_t stream);
+
 }  // namespace vrt

@@ -110,6 +110,8 @@ class VHipRenderer:
             if self._uploaded.get(slot) != id(vol) or vol.dirty:
                 self.upload_volume(slot, vol)
             else:
+                if vol.dirty_box is not None:  # only a box of the resident volume changed
+                    self.update_volume_region(slot, vol, *vol.dirty_box)
                 # the volume's voxels are unchanged, but its material may name other images or scalars than at the last sync
                 # (VMaterial is edited in place; VDXVoxelVolume::UpdateGeometryConstantBuffer, RDXVoxelVolume.cpp:368-397, runs
                 # every frame): re-send them — the C-ABI returns at once when nothing differs
@@ -155,6 +157,20 @@ class VHipRenderer:
         self._bind_material(slot, vol)
         self._uploaded[slot] = id(vol)
         vol.dirty = False
+        vol.dirty_box = None
+
+    def update_volume_region(self, slot: int, vol: VVoxelVolume, lo, hi) -> None:
+        """vrt_volume_update_region: the voxels lo..hi (inclusive xyz corners) of the volume resident in `slot`, from the host
+        arrays, in place on the device; every device structure ends as a full upload of the volume would leave it."""
+        self._require()
+        (x0, y0, z0), (x1, y1, z1) = lo, hi
+        d = np.ascontiguousarray(vol.density[x0:x1 + 1, z0:z1 + 1, y0:y1 + 1], dtype=np.float32)
+        m = np.ascontiguousarray(vol.material_id[x0:x1 + 1, z0:z1 + 1, y0:y1 + 1], dtype=np.uint8)
+        origin = (C.c_int * 3)(x0, y0, z0)
+        size = (C.c_int * 3)(x1 - x0 + 1, y1 - y0 + 1, z1 - z0 + 1)
+        _abi.check(self._lib.vrt_volume_update_region(self._ctx, slot, origin, size, d.ctypes.data_as(C.c_void_p),
+                                                      m.ctypes.data_as(C.c_void_p)), "vrt_volume_update_region")
+        vol.dirty_box = None
 
     def _bind_material(self, slot: int, vol: VVoxelVolume) -> None:
         """The slot's material scalars and texture bindings as the volume's VMaterial holds them NOW (images uploaded on first

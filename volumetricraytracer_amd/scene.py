@@ -139,6 +139,37 @@ class VVoxelVolume:
         # own 16-bit volume texel (RDXVoxelVolume.cpp:399-421)
         self.device_format = _abi.FORMAT_F32
         self.dirty = True
+        # voxels edited by set_region since the last sync, as inclusive xyz corners (lo, hi), or None: the renderer updates just
+        # this box of a volume already on the device (vrt_volume_update_region) instead of uploading all of it again
+        self.dirty_box = None
+
+    def set_region(self, origin_xyz, density_xzy, material_xzy=None) -> "VVoxelVolume":
+        """Writes a box of voxels (VVoxelVolume::SetVoxel for many at once, VoxelVolume.cpp:59-112): density_xzy is indexed
+        [x, z, y] like `density`, its box starts at voxel origin_xyz; material_xzy (same shape) or None to keep the materials.
+        Unions the box into `dirty_box`; `dirty` (the whole volume) stays as it is."""
+        d = np.asarray(density_xzy, dtype=np.float32)
+        if d.ndim != 3:
+            raise ValueError("density_xzy must be [sx, sz, sy]")
+        x0, y0, z0 = (int(v) for v in origin_xyz)
+        sx, sz, sy = d.shape
+        if min(sx, sy, sz) < 1 or min(x0, y0, z0) < 0 or max(x0 + sx, y0 + sy, z0 + sz) > self.N:
+            raise ValueError("the box reaches outside the volume")
+        if not self.density.flags.writeable:  # (fill() may leave a read-only array)
+            self.density = np.array(self.density, dtype=np.float32)
+        self.density[x0:x0 + sx, z0:z0 + sz, y0:y0 + sy] = d
+        if material_xzy is not None:
+            if not self.material_id.flags.writeable:
+                self.material_id = np.array(self.material_id, dtype=np.uint8)
+            m = np.asarray(material_xzy, dtype=np.uint8)
+            if m.shape != d.shape:
+                raise ValueError("material_xzy must have the shape of density_xzy")
+            self.material_id[x0:x0 + sx, z0:z0 + sz, y0:y0 + sy] = m
+        lo, hi = (x0, y0, z0), (x0 + sx - 1, y0 + sy - 1, z0 + sz - 1)
+        if self.dirty_box is not None:
+            lo = tuple(min(a, b) for a, b in zip(lo, self.dirty_box[0]))
+            hi = tuple(max(a, b) for a, b in zip(hi, self.dirty_box[1]))
+        self.dirty_box = (lo, hi)
+        return self
 
     def GetSize(self) -> int:
         return self.N
