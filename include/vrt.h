@@ -27,6 +27,7 @@
  *                                   DXRenderer.cpp:37-66, 827-867 (+ the HLSL entry points
  *                                   Renderer/DX/Resources/Shaders/Raytracing.hlsl:26-455)
  *   vrt_last_timing                 (no reference analogue; FPS counter Engine.cpp:250-262)
+ *   vrt_trace_rays*, vrt_camera_rays (no reference analogue: its DXR TraceRay calls live only inside its shaders)
  *
  * Error convention: 0 = OK, negative = error.  The reference logs and returns early
  * (DXRenderer.cpp:220-225); the adaptor maps negative codes onto that behaviour.
@@ -461,6 +462,61 @@ int vrt_exchange_tiles(vrt_ctx* ctx, const void* device_tiles, void* device_recv
  * drain every frame in flight first. */
 int vrt_render_begin(vrt_ctx* ctx, const vrt_params* params, int slot);
 int vrt_render_end(vrt_ctx* ctx, int slot, const void** host_pixels);
+
+/* Ray queries (no reference analogue): what the resident scene's surfaces are along caller-supplied world-space rays — picking,
+ * line of sight, probe distances — marched on the GPU by the render's own march.
+ *
+ * March contract: these vrt_params fields apply as in a render: eps_hit, eps_in, step_min, k_relax, cone_eps, max_steps, mode
+ * (Interp or Cube geometry) and path.  Of the flags only VRT_FLAG_NO_HIT_POLISH and VRT_FLAG_REFERENCE_BOUNDARY_TEXELS have an
+ * effect.  width and height must pass the render's checks but are otherwise unused.  A caller who wants the hits a render
+ * shows passes the render's cone_eps (the threshold grows with t as in a frame whose camera sits at the ray's origin);
+ * cone_eps = 0 gives a constant threshold.  VRT_PATH_BRICK_LDS marches as VRT_PATH_BRICK (the LDS cache is a render
+ * experiment); VRT_PATH_AUTO resolves as in a render.  Every ray is the oracle's vrto_trace of it: t_base 0, the direction
+ * normalised (1 / sqrt of its squared length), the same hit flag, t, normal and instance (steps: see vrt_hit). */
+typedef struct vrt_ray {
+    float origin[3];
+    float t_max;          /* hits at t > t_max do not count */
+    float direction[3];   /* need not be unit; t is measured along the normalised direction (the oracle's convention) */
+    float reserved_;      /* 0 */
+} vrt_ray;                /* 32 B */
+
+typedef struct vrt_hit {
+    float t;              /* world-space distance along the normalised direction; -1 for a miss */
+    float normal[3];      /* world-space unit geometric normal (exact length; material normal maps are not applied); 0 for a miss */
+    int32_t instance;     /* index into vrt_scene::instances; -1 for a miss */
+    int32_t voxel[3];     /* nearest grid sample of the hit instance's volume, (x, y, z) as vrt_volume_update_region takes them:
+                             voxel[a] = clamp(floor((p[a] + extent) * inv_cell + 0.5), 0, N-1), p = the object-space hit point
+                             (object axes x, y, z = the grid's x, y, z; the grid is stored density[x*N*N + z*N + y]); -1 for a miss */
+    uint32_t material;    /* material id of that sample; 0 for a miss */
+    uint32_t steps;       /* march positions the ray visited (VRT_QUERY_ANY: of the any-hit march).  One instance: what vrto_trace reports
+                             in steps_out.  Several: the BVH walk's count, as in a render's counters — an instance whose box lies
+                             beyond the closest hit found so far is not marched, so the count can be below the oracle's, which
+                             marches every instance the ray meets */
+    uint32_t reserved_[2];
+} vrt_hit;                /* 48 B */
+
+#define VRT_QUERY_CLOSEST 0
+#define VRT_QUERY_ANY     1  /* occlusion: instance = 0 when some surface lies within [0, t_max], every other field as for a miss
+                                but steps */
+
+/* n rays from device memory into n hit records in device memory, asynchronous on hip_stream, on the first device of the
+ * context.  A zero-length or non-finite direction, a non-finite origin or a NaN / negative t_max yields a miss record (steps 0),
+ * not an error.  Argument errors are checked before anything is enqueued: a NULL context, params or buffer (n > 0), n < 0 or an
+ * unknown query is VRT_ERR_INVALID; no scene is VRT_ERR_NOT_READY; n == 0 is OK and launches nothing.  Allocates nothing, so it
+ * can be captured into a hipGraph (the material grids' and the scene arrays' addresses are baked in: a region edit shows in a
+ * replay, a full re-upload or a new scene does not).  Like vrt_render_rows, a vrt_scene_set that was deferred while frames were
+ * in flight is applied ahead of the query; on a capturing stream that is VRT_ERR_NOT_READY.  Queries leave the render's
+ * bookkeeping alone: vrt_last_timing, the timing and launch histories, the kernel form and the per-wave records read the same
+ * before and after any number of them. */
+int vrt_trace_rays(vrt_ctx* ctx, const vrt_params* params, int query, int n, const vrt_ray* device_rays, vrt_hit* device_hits,
+                   void* hip_stream);
+/* The same from and into host arrays, synchronous: staged through a context-owned device buffer, reallocated only when a larger
+ * n arrives. */
+int vrt_trace_rays_host(vrt_ctx* ctx, const vrt_params* params, int query, int n, const vrt_ray* rays, vrt_hit* hits);
+/* Host only, no context, no GPU: the camera rays the march kernel casts for the n pixels (x, y) of a width x height frame of
+ * scene's camera, bit for bit (origin, normalised direction), t_max = 10000 (the kernel's primary t_max).  VRT_ERR_INVALID for a
+ * NULL pointer (n > 0), n < 0, a frame size outside 1..16384 or a pixel outside the frame, before anything is written. */
+int vrt_camera_rays(const vrt_scene* scene, int width, int height, int n, const int32_t* pixels_xy, vrt_ray* rays_out);
 
 int vrt_last_timing(vrt_ctx* ctx, vrt_timing* out);
 /* Kernel durations (ms) of the last n vrt_render_rows/vrt_render launches, oldest first;

@@ -1,0 +1,153 @@
+"""Ray queries (vrt_trace_rays / _host, vrt_camera_rays) without a GPU: the record layouts of C and ctypes agree, the host camera
+rays are bit-equal to the oracle's (and so to the march kernel's, which the render parity tests pin to the oracle), argument errors
+come back before any device work, and the build's ISA listing holds the query kernel within the lean kernels' budget."""
+import ctypes as C
+import math
+import os
+import re
+import subprocess
+
+import numpy as np
+import pytest
+
+import volumetricraytracer_amd as v
+from volumetricraytracer_amd import _abi
+from volumetricraytracer_amd import workloads as scenes
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+LISTING = os.path.join(os.environ.get("VRT_BUILD_TMP", os.path.join(ROOT, "build", "hip")), "vrt_kernels-hip-amdgcn-amd-amdhsa-gfx950.s")
+LIB = os.path.join(ROOT, "volumetricraytracer_amd", "lib", "libvrt_hip.so")
+
+
+def test_ray_and_hit_records_have_the_c_layout(tmp_path):
+    fields = ["sizeof(vrt_ray)", "offsetof(vrt_ray, origin)", "offsetof(vrt_ray, t_max)", "offsetof(vrt_ray, direction)",
+              "offsetof(vrt_ray, reserved_)", "sizeof(vrt_hit)", "offsetof(vrt_hit, t)", "offsetof(vrt_hit, normal)",
+              "offsetof(vrt_hit, instance)", "offsetof(vrt_hit, voxel)", "offsetof(vrt_hit, material)", "offsetof(vrt_hit, steps)",
+              "VRT_QUERY_CLOSEST", "VRT_QUERY_ANY"]
+    prog = tmp_path / "q.c"
+    prog.write_text('#include <stdio.h>\n#include <stddef.h>\n#include "vrt.h"\nint main(void){\n' +
+                    "".join(f'printf("%ld\\n", (long)({f}));\n' for f in fields) + "return 0;}\n")
+    exe = tmp_path / "q"
+    subprocess.run(["gcc", "-std=c99", "-I", os.path.join(ROOT, "include"), str(prog), "-o", str(exe)], check=True)
+    got = [int(x) for x in subprocess.run([str(exe)], check=True, capture_output=True, text=True).stdout.split()]
+    R, H = _abi.vrt_ray, _abi.vrt_hit
+    want = [C.sizeof(R), R.origin.offset, R.t_max.offset, R.direction.offset, R.reserved_.offset, C.sizeof(H), H.t.offset,
+            H.normal.offset, H.instance.offset, H.voxel.offset, H.material.offset, H.steps.offset, _abi.QUERY_CLOSEST, _abi.QUERY_ANY]
+    assert got == want
+    assert got[0] == 32 and got[5] == 48
+    assert v.RAY_DTYPE.itemsize == 32 and v.HIT_DTYPE.itemsize == 48
+    assert [v.HIT_DTYPE.fields[n][1] for n in ("t", "normal", "instance", "voxel", "material", "steps")] == got[6:12]
+
+
+def _cameras():
+    """Scene cameras of the configs plus a few placed by hand (roll, pitch, a camera looking straight down)."""
+    out = []
+    for sc in (scenes.config2_sphere(4, 8), scenes.config3_torus(4, 8), scenes.config5_instances(4, 8)):
+        out.append(sc)
+    base = scenes.config2_sphere(4, 8)
+    for k, (axis, deg, fov) in enumerate([(v.UP, 17.0, 30.0), (v.RIGHT, -40.0, 90.0), (v.FORWARD, 33.0, 120.0), (v.RIGHT, 90.0, 75.0)]):
+        sc = scenes.config2_sphere(4, 8)
+        sc.Camera = v.VCamera(Position=(120.0 - 37.0 * k, 15.5 * k, -60.0 + 11.0 * k),
+                              Rotation=tuple(v.quat_mul(v.quat_from_axis_angle(axis, math.radians(deg)), base.Camera.Rotation)),
+                              FOVAngle=fov)
+        out.append(sc)
+    return out
+
+
+@pytest.mark.parametrize("size", [(1920, 1080), (256, 144), (333, 777), (1, 1), (64, 64), (4096, 17)])
+def test_camera_rays_are_the_oracles_bit_for_bit(oracle_lib, size):
+    from oracle.binding import OracleScene
+
+    w, h = size
+    rng = np.random.default_rng(w * 7 + h)
+    corners = [(0, 0), (w - 1, 0), (0, h - 1), (w - 1, h - 1), (w // 2, h // 2)]
+    pixels = np.array(corners + [(int(x), int(y)) for x, y in zip(rng.integers(0, w, 40), rng.integers(0, h, 40))], np.int32)
+    lib = _abi.load()
+    for sc in _cameras():
+        rays = np.zeros(len(pixels), v.RAY_DTYPE)
+        abi = sc.to_abi()
+        assert lib.vrt_camera_rays(C.byref(abi), w, h, len(pixels), pixels.ctypes.data_as(C.c_void_p), rays.ctypes.data_as(C.c_void_p)) == 0
+        o, d = OracleScene(sc).camera_rays(w, h, pixels)
+        assert np.array_equal(rays["origin"].view(np.uint32), o.view(np.uint32))
+        assert np.array_equal(rays["direction"].view(np.uint32), d.view(np.uint32)), (size, sc.Camera)
+        assert np.all(rays["t_max"] == 10000.0) and np.all(rays["reserved_"] == 0.0)
+
+
+def test_camera_rays_through_the_renderer_mirror(oracle_lib):
+    from oracle.binding import OracleScene
+
+    sc = scenes.config3_torus(4, 8)
+    r = v.VHipRenderer()  # no context needed: vrt_camera_rays is host only
+    r.SetSceneToRender(sc)
+    r.ResizeRenderOutput(640, 360)
+    rays = r.camera_rays([(0, 0), (639, 359), (320, 180)])
+    o, d = OracleScene(sc).camera_rays(640, 360, [(0, 0), (639, 359), (320, 180)])
+    assert np.array_equal(rays["direction"], d) and np.array_equal(rays["origin"], o)
+
+
+def test_argument_errors_without_a_gpu():
+    lib = _abi.load()
+    p = v.default_params(64, 64, 1.0)
+    rays = np.zeros(4, v.RAY_DTYPE)
+    hits = np.zeros(4, v.HIT_DTYPE)
+    rp, hp = rays.ctypes.data_as(C.c_void_p), hits.ctypes.data_as(C.c_void_p)
+    INVALID = _abi.VRT_ERR_INVALID
+    # NULL context, n < 0, an unknown query, NULL buffers
+    assert lib.vrt_trace_rays(None, C.byref(p), _abi.QUERY_CLOSEST, 4, rp, hp, None) == INVALID
+    assert lib.vrt_trace_rays(None, C.byref(p), _abi.QUERY_CLOSEST, -1, rp, hp, None) == INVALID
+    assert lib.vrt_trace_rays(None, C.byref(p), 2, 4, rp, hp, None) == INVALID
+    assert lib.vrt_trace_rays(None, None, _abi.QUERY_ANY, 0, None, None, None) == INVALID
+    assert lib.vrt_trace_rays_host(None, C.byref(p), _abi.QUERY_ANY, 4, rp, hp) == INVALID
+    assert lib.vrt_trace_rays_host(None, C.byref(p), -1, 4, rp, hp) == INVALID
+    assert lib.vrt_trace_rays_host(None, C.byref(p), _abi.QUERY_CLOSEST, -5, rp, hp) == INVALID
+    assert np.all(hits["t"] == 0.0)  # nothing written
+    # vrt_camera_rays: no scene, n < 0, NULL arrays, a frame size or a pixel outside the range; nothing written
+    abi = scenes.config2_sphere(4, 8).to_abi()
+    px = np.array([[0, 0], [63, 63], [64, 0]], np.int32)
+    pp = px.ctypes.data_as(C.c_void_p)
+    assert lib.vrt_camera_rays(None, 64, 64, 1, pp, rp) == INVALID
+    assert lib.vrt_camera_rays(C.byref(abi), 64, 64, -1, pp, rp) == INVALID
+    assert lib.vrt_camera_rays(C.byref(abi), 64, 64, 1, None, rp) == INVALID
+    assert lib.vrt_camera_rays(C.byref(abi), 64, 64, 1, pp, None) == INVALID
+    assert lib.vrt_camera_rays(C.byref(abi), 0, 64, 1, pp, rp) == INVALID
+    assert lib.vrt_camera_rays(C.byref(abi), 64, 16385, 1, pp, rp) == INVALID
+    assert lib.vrt_camera_rays(C.byref(abi), 64, 64, 3, pp, rp) == INVALID  # (64, 0) lies outside a 64-wide frame
+    assert np.all(rays["t_max"] == 0.0)
+    assert lib.vrt_camera_rays(C.byref(abi), 64, 64, 0, None, None) == 0
+    assert lib.vrt_camera_rays(C.byref(abi), 64, 64, 2, pp, rp) == 0
+
+
+def _listing():
+    if not os.path.exists(LISTING) or not os.path.exists(LIB) or os.path.getmtime(LISTING) + 600 < os.path.getmtime(LIB):
+        pytest.skip("no ISA listing of this build here (it is written by csrc/build.sh next to the build's temporaries)")
+    return open(LISTING).read()
+
+
+def _query_kernels(text):
+    """{(PATH, SINGLE, ANY, REF): resources} of the query_kernel<PATH, SINGLE, ANY, REF> instantiations (Itanium names)."""
+    meta = text[text.index("amdhsa.kernels:"):]
+    out = {}
+    for block in re.split(r"\n  - \.agpr_count:", meta)[1:]:
+        f = dict(re.findall(r"\.(name|vgpr_count|private_segment_fixed_size|vgpr_spill_count|group_segment_fixed_size):\s+(\S+)", block))
+        m = re.fullmatch(r"_ZN3vrt12query_kernelILi(\d+)ELb([01])ELb([01])ELb([01])EEEvNS_6DQueryE", f["name"])
+        if m:
+            out[(int(m.group(1)),) + tuple(x == "1" for x in m.groups()[1:])] = {k: int(x) for k, x in f.items() if k != "name"}
+    return out
+
+
+def test_the_query_kernel_is_built_within_the_lean_budget():
+    text = _listing()
+    qk = _query_kernels(text)
+    # every internal path: dense, bricks, int16 bricks, cell records, both Cube paths
+    assert {t[0] for t in qk} == {1, 2, 8, 9, 10, 11}, sorted(qk)
+    single_closest = {t: r for t, r in qk.items() if t[1] and not t[2]}
+    assert len(single_closest) >= 10, sorted(qk)
+    for t, r in qk.items():
+        assert r["private_segment_fixed_size"] == 0 and r["vgpr_spill_count"] == 0, (t, r)
+        assert r["group_segment_fixed_size"] == 0, (t, r)  # no LDS
+    for t, r in single_closest.items():
+        assert r["vgpr_count"] <= 64, (t, r)  # 8 waves per SIMD
+    for name in re.findall(r"^(_ZN3vrt12query_kernel\S+):", text, flags=re.M):
+        body = re.search(rf"^{re.escape(name)}:[^\n]*\n(.*?)\n\.Lfunc_end", text, flags=re.S | re.M).group(1)
+        assert not re.search(r"^\s+v_pk_(?:fma|add|mul)_f32\b", body, flags=re.M), name
+        assert body.count("global_store_dwordx4") >= 3 and "global_load_dwordx4" in body, name  # 2 x 16-B loads, 3 x 16-B stores

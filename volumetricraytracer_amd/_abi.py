@@ -67,6 +67,9 @@ PATH_BRICK = 2
 PATH_BRICK_LDS = 3
 PATH_CELLS = 4
 
+QUERY_CLOSEST = 0
+QUERY_ANY = 1  # occlusion: instance 0 when some surface lies within [0, t_max]
+
 
 class vrt_voxel(C.Structure):
     _fields_ = [("material", C.c_uint8), ("pad_", C.c_uint8 * 3), ("density", C.c_float)]
@@ -182,6 +185,22 @@ class vrt_block(C.Structure):
     ]
 
 
+class vrt_ray(C.Structure):
+    _fields_ = [("origin", C.c_float * 3), ("t_max", C.c_float), ("direction", C.c_float * 3), ("reserved_", C.c_float)]
+
+
+class vrt_hit(C.Structure):
+    _fields_ = [
+        ("t", C.c_float),
+        ("normal", C.c_float * 3),
+        ("instance", C.c_int32),
+        ("voxel", C.c_int32 * 3),
+        ("material", C.c_uint32),
+        ("steps", C.c_uint32),
+        ("reserved_", C.c_uint32 * 2),
+    ]
+
+
 SYMBOLS = {
     "vrt_create": (C.c_int, [C.POINTER(C.c_void_p), C.c_int, C.POINTER(C.c_int)]),
     "vrt_destroy": (C.c_int, [C.c_void_p]),
@@ -216,6 +235,9 @@ SYMBOLS = {
     "vrt_exchange_tiles": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
     "vrt_render_begin": (C.c_int, [C.c_void_p, C.POINTER(vrt_params), C.c_int]),
     "vrt_render_end": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(C.c_void_p)]),
+    "vrt_trace_rays": (C.c_int, [C.c_void_p, C.POINTER(vrt_params), C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "vrt_trace_rays_host": (C.c_int, [C.c_void_p, C.POINTER(vrt_params), C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
+    "vrt_camera_rays": (C.c_int, [C.POINTER(vrt_scene), C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
     "vrt_last_timing": (C.c_int, [C.c_void_p, C.POINTER(vrt_timing)]),
     "vrt_timing_history": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(C.c_float)]),
     "vrt_launch_history": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(C.c_float), C.POINTER(C.c_int)]),

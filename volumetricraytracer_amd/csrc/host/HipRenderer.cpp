@@ -559,9 +559,10 @@ bool VHipRenderer::SyncWithScene(Scene::VScene& scene) {
 /* The scene's constants, lights and instance list as the C-ABI takes them (UpdateSceneConstantBuffer, UpdateLights,
    BuildTopLevelAccelerationStructures: RDXScene.cpp:703-755, 454-545) — for vrt_scene_set, or as one frame of vrt_block::scenes.
    Volume slots are the indices of scene.GetAllRegisteredVolumes(), which SyncWithScene uploaded. */
-bool VHipRenderer::FillSceneStruct(Scene::VScene& scene, vrt_scene& s) {
+bool VHipRenderer::FillSceneStruct(Scene::VScene& scene, vrt_scene& s, std::vector<const Scene::VVoxelObject*>* objects) {
     const auto volumes = scene.GetAllRegisteredVolumes();
     memset(&s, 0, sizeof s);
+    if (objects) objects->clear();
     const VObjectPtr<Scene::VCamera> cam = scene.GetActiveCamera();
     if (!cam) {
         V_LOG_ERROR("scene has no active camera");
@@ -607,6 +608,7 @@ bool VHipRenderer::FillSceneStruct(Scene::VScene& scene, vrt_scene& s) {
                 continue;
             }
             vrt_instance& I = s.instances[s.n_instances++];
+            if (objects) objects->push_back(vo.get());
             for (size_t slot = 0; slot < volumes.size(); slot++)
                 if (volumes[slot] == vo->GetVoxelVolume()) I.volume_slot = (int)slot;
             I.position[0] = vo->Position.X; I.position[1] = vo->Position.Y; I.position[2] = vo->Position.Z;
@@ -735,6 +737,36 @@ void VHipRenderer::Flush() {
 }
 
 bool VHipRenderer::GetLastTiming(vrt_timing& out) const { return Ctx && vrt_last_timing(Ctx, &out) == VRT_OK; }
+
+bool VHipRenderer::TraceRays(const std::vector<vrt_ray>& rays, std::vector<vrt_hit>& hits, bool anyHit) {
+    if (!IsActive()) {
+        V_LOG_WARNING("TraceRays() on an inactive renderer");
+        return false;
+    }
+    const VObjectPtr<Scene::VScene> scene = SceneRef.lock();
+    if (!scene || rays.size() > (size_t)INT32_MAX) return false;
+    if (!SyncWithScene(*scene)) return false;
+    vrt_scene s;
+    if (!FillSceneStruct(*scene, s, &QueryObjects)) return false;
+    const vrt_params p = MakeParams(*scene);
+    hits.resize(rays.size());
+    return ok(vrt_trace_rays_host(Ctx, &p, anyHit ? VRT_QUERY_ANY : VRT_QUERY_CLOSEST, (int)rays.size(), rays.data(), hits.data()),
+              "vrt_trace_rays_host");
+}
+
+bool VHipRenderer::Pick(int px, int py, vrt_hit& out) {
+    const VObjectPtr<Scene::VScene> scene = SceneRef.lock();
+    if (!IsActive() || !scene || px < 0 || py < 0 || (unsigned)px >= Width || (unsigned)py >= Height) return false;
+    vrt_scene s;
+    if (!FillSceneStruct(*scene, s)) return false;
+    const int32_t xy[2] = {px, py};
+    std::vector<vrt_ray> ray(1);
+    if (!ok(vrt_camera_rays(&s, (int)Width, (int)Height, 1, xy, ray.data()), "vrt_camera_rays")) return false;
+    std::vector<vrt_hit> hit;
+    if (!TraceRays(ray, hit, false)) return false;
+    out = hit[0];
+    return true;
+}
 
 }  // namespace Hip
 }  // namespace Renderer

@@ -100,10 +100,24 @@ public:
        memory.  GetBlockFrame(f): frame f in FrameFormat, valid until the next RenderBlock / Stop.  n_frames <= 256. */
     bool RenderBlock(int n_frames, const std::function<void(int)>& tick);
     const void* GetBlockFrame(int f) const { return (BlockFrames && f >= 0 && f < BlockFrameCount) ? BlockFrames + (size_t)f * BlockFrameBytes : nullptr; }
+    /* Ray queries on the GPU (vrt_trace_rays_host) against the scene Render() would draw now (synced first), with the march
+       parameters of its frames (MakeParams: the frame's cone_eps, so a camera ray gets the hit its pixel shows): world-space rays
+       in, one vrt_hit per ray out.  anyHit: occlusion within each ray's t_max (instance 0 when blocked, -1 when clear).  False
+       (after logging) on failure. */
+    bool TraceRays(const std::vector<vrt_ray>& rays, std::vector<vrt_hit>& hits, bool anyHit = false);
+    /* The closest hit under pixel (px, py) of the current output size: the camera ray the march kernel casts for it
+       (vrt_camera_rays), traced as TraceRays does.  False when the pixel lies outside the frame or the query fails; a miss is
+       true with out.instance = -1. */
+    bool Pick(int px, int py, vrt_hit& out);
+    /* The placed object a hit record of the last TraceRays / Pick names (null for a miss). */
+    const Scene::VVoxelObject* HitObject(const vrt_hit& hit) const {
+        return hit.instance >= 0 && (size_t)hit.instance < QueryObjects.size() ? QueryObjects[(size_t)hit.instance] : nullptr;
+    }
 
 private:
     bool SyncWithScene(Scene::VScene& scene);
-    bool FillSceneStruct(Scene::VScene& scene, vrt_scene& out);
+    bool FillSceneStruct(Scene::VScene& scene, vrt_scene& out, std::vector<const Scene::VVoxelObject*>* objects = nullptr);
+    std::vector<const Scene::VVoxelObject*> QueryObjects; /* instance -> placed object of the last query's scene */
     vrt_params MakeParams(Scene::VScene& scene) const;
     std::vector<vrt_scene> BlockScenes;
     const unsigned char* BlockFrames = nullptr;

@@ -15,6 +15,9 @@
  *            [--edit-brush R]               every frame carves a sphere of radius R cells out of the red sphere's volume along a circle (SetVoxel +
  *                                           MakeDirtyRegion): the renderer updates the edited box in place (vrt_volume_update_voxels)
  *            [--edit-full]                  ... and uploads the whole volume after every edit instead (the same frames)
+ *            [--pick X Y]                   every frame asks what lies under pixel (X, Y) (VHipRenderer::Pick: a GPU ray query) and prints the
+ *                                           hit record; with --edit-brush the brush is centred on the picked voxel when the pick hits the red
+ *                                           sphere, and a frame whose pick misses it edits nothing
  */
 #include <chrono>
 #include <cmath>
@@ -69,6 +72,8 @@ int main(int argc, char** argv) {
     bool identityDefaults = false;
     int editBrush = 0;
     bool editFull = false;
+    bool pick = false;
+    int pickX = 0, pickY = 0;
     int mode = 0, inFlight = 3, block = 0; /* three frames in flight: the reference's swap chain (FrameCount, DXConstants.cpp:23) */
     std::string format = "bgra8", volumes = "texel16";
     for (int i = 1; i < argc; i++) {
@@ -85,6 +90,11 @@ int main(int argc, char** argv) {
         else if (!strcmp(argv[i], "--identity-defaults")) identityDefaults = true;
         else if (!strcmp(argv[i], "--edit-brush") && i + 1 < argc) editBrush = atoi(argv[++i]);
         else if (!strcmp(argv[i], "--edit-full")) editFull = true;
+        else if (!strcmp(argv[i], "--pick") && i + 2 < argc) {
+            pick = true;
+            pickX = atoi(argv[++i]);
+            pickY = atoi(argv[++i]);
+        }
     }
 
     std::shared_ptr<Renderer::VRenderer> renderer = Renderer::VRendererFactory::NewRenderer();
@@ -138,14 +148,18 @@ int main(int argc, char** argv) {
         fprintf(stderr, "--edit-brush edits the volume every frame: RenderBlock refuses that; drop --block\n");
         return 1;
     }
+    if (pick && (!hip || block > 0)) {
+        fprintf(stderr, "--pick asks the HIP renderer once per frame: drop --block\n");
+        return 1;
+    }
     double kernel_ms = 0.0;
-    /* the brush: a sphere of editBrush cells around a point that circles the red sphere's centre 12 cells out, 4 cells above it;
-       union (CSG difference) with the field, the box it can change marked dirty */
-    auto carve = [&](int f) {
+    bool warmUp = true; /* the untimed first frame prints no pick record */
+    /* the brush: a sphere of editBrush cells around voxel c — a point that circles the red sphere's centre 12 cells out, 4 cells above
+       it, or (--pick) the voxel under the picked pixel; union (CSG difference) with the field, the box it can change marked dirty */
+    auto carve = [&](const VIntVector& c) {
         Voxel::VVoxelVolume& vol = *sphere1->GetVoxelVolume();
-        const int n = (int)vol.GetSize(), r = editBrush;
-        const float a = (float)f * 0.15f, cell = vol.GetCellSize();
-        const VIntVector c(n / 2 + (int)std::lround(12.f * std::cos(a)), n / 2 + 4, n / 2 + (int)std::lround(12.f * std::sin(a)));
+        const int r = editBrush;
+        const float cell = vol.GetCellSize();
         const VIntVector lo(c.X - r, c.Y - r, c.Z - r), hi(c.X + r, c.Y + r, c.Z + r);
         for (int x = lo.X; x <= hi.X; x++)
             for (int y = lo.Y; y <= hi.Y; y++)
@@ -167,8 +181,21 @@ int main(int argc, char** argv) {
         const float dt = 1.f / 60.f, angle = (float)f * dt * 0.5f;
         sphere1->Position = VQuat::FromAxisAngle(VVector::UP, angle) * rel1;
         sphere2->Position = VQuat::FromAxisAngle(VVector::RIGHT, angle) * rel2;
-        if (editBrush > 0) carve(f);
         scene->Touch();
+        if (pick) { /* what lies under the pixel now, before this frame's edit */
+            vrt_hit h;
+            if (!hip->Pick(pickX, pickY, h)) {
+                if (!warmUp) printf("frame %d pick (%d, %d): failed\n", f, pickX, pickY);
+            } else {
+                if (!warmUp) printf("frame %d pick (%d, %d): instance %d t %.4f normal (%.4f, %.4f, %.4f) voxel (%d, %d, %d) material %u steps %u\n", f, pickX,
+                       pickY, h.instance, h.t, h.normal[0], h.normal[1], h.normal[2], h.voxel[0], h.voxel[1], h.voxel[2], h.material, h.steps);
+                if (editBrush > 0 && hip->HitObject(h) == sphere1.get()) carve(VIntVector(h.voxel[0], h.voxel[1], h.voxel[2]));
+            }
+        } else if (editBrush > 0) {
+            const int n = (int)sphere1->GetVoxelVolume()->GetSize();
+            const float a = (float)f * 0.15f;
+            carve(VIntVector(n / 2 + (int)std::lround(12.f * std::cos(a)), n / 2 + 4, n / 2 + (int)std::lround(12.f * std::sin(a))));
+        }
     };
     /* one untimed frame / block first: the pinned frame buffers and the device buffers of this size are allocated by the first call */
     if (hip && block > 0) {
@@ -179,6 +206,7 @@ int main(int argc, char** argv) {
         if (hip) hip->Flush();
     }
     scene->PostRender();
+    warmUp = false;
     const auto t0 = std::chrono::steady_clock::now();
     if (hip && block > 0) {
         /* the same animation, `block` frames per call: per-frame scene state, ONE march launch per block */

@@ -88,6 +88,7 @@ RcclApi* rccl() {
 /* the per-frame scene sections (vrt_device.h, DDyn) hold what the C-ABI's limits allow */
 static_assert(kDynMaxInstances == VRT_MAX_INSTANCES && kMaxBvhNodes == 2 * VRT_MAX_INSTANCES - 1, "section capacity = VRT_MAX_INSTANCES");
 static_assert(kDynMaxPointLights == VRT_MAX_POINT_LIGHTS && kDynMaxSpotLights == VRT_MAX_SPOT_LIGHTS, "section capacity = VRT_MAX_*_LIGHTS");
+static_assert(sizeof(vrt_ray) == 32 && sizeof(vrt_hit) == 48, "query_kernel reads two and writes three 16-B words per ray");
 
 constexpr int kStatSlots = 16; /* streams that may have launches in flight at once without sharing a counter buffer */
 constexpr int kRing = 256; /* per-launch event pairs + stat slots kept for vrt_timing_history */
@@ -209,6 +210,9 @@ struct DeviceState {
     void* edit_scratch = nullptr;
     size_t edit_scratch_cap = 0;
     int* d_box6 = nullptr;
+    /* vrt_trace_rays_host: the rays and then the hit records of a batch (grown on demand) */
+    void* query_buf = nullptr;
+    size_t query_cap = 0;
     int last_blocks = 0;         /* workgroups per frame of the last launch */
     int last_frames = 1;         /* frames of the last launch: vrt_last_timing / vrt_debug_wave_records read its LAST frame's records */
     bool last_diag = false;
@@ -568,6 +572,7 @@ void destroy_device(DeviceState& D) {
     if (D.edit_staging) (void)hipFree(D.edit_staging);
     if (D.edit_scratch) (void)hipFree(D.edit_scratch);
     if (D.d_box6) (void)hipFree(D.d_box6);
+    if (D.query_buf) (void)hipFree(D.query_buf);
     if (D.d_vols) (void)hipFree(D.d_vols);
     if (D.d_inst) (void)hipFree(D.d_inst);
     if (D.d_nodes) (void)hipFree(D.d_nodes);
@@ -1282,6 +1287,37 @@ int enqueue_rows(vrt_ctx* ctx, DeviceState& D, const vrt_params* p, const RowSet
     return VRT_OK;
 }
 
+/* What vrt_trace_rays and vrt_trace_rays_host refuse, checked before anything is enqueued. */
+int check_query(const vrt_ctx* ctx, const vrt_params* p, int query, int n, const void* rays, const void* hits) {
+    if (!ctx || !p || n < 0 || (query != VRT_QUERY_CLOSEST && query != VRT_QUERY_ANY) || (n > 0 && (!rays || !hits))) return VRT_ERR_INVALID;
+    return check_params(ctx, p);
+}
+
+/* One query launch of n rays on the first device (vrt_trace_rays).  Touches none of the render's bookkeeping (launch count, timing
+   ring, per-wave records, kernel form); allocates nothing. */
+int enqueue_query(vrt_ctx* ctx, const vrt_params* p, int query, int n, const void* rays, void* hits, hipStream_t stream) {
+    DeviceState& D = ctx->dev[0];
+    const bool single = ctx->scene.n_instances == 1;
+    const int path = resolve_path(ctx, p->path, single, p->mode);
+    if (path < 0) return path;
+    HIP_TRY(hipSetDevice(D.ordinal));
+    if (!ctx->arrays_uploaded) { /* deferred by pack_scene (frames were in flight): now, as enqueue_rows does */
+        hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
+        if (stream != nullptr && hipStreamIsCapturing(stream, &cs) == hipSuccess && cs != hipStreamCaptureStatusNone) return VRT_ERR_NOT_READY;
+        const int rc = upload_scene_arrays(ctx);
+        if (rc != VRT_OK) return rc;
+    }
+    DQuery Q;
+    memset(&Q, 0, sizeof Q); /* (the whole struct travels as the kernarg) */
+    build_frame(ctx, D, p, RowSet{}, nullptr, nullptr, Q.f);
+    Q.rays = rays;
+    Q.hits = hits;
+    Q.n = n;
+    for (int s = 0; s < VRT_MAX_VOLUMES; s++) Q.material[s] = D.vol[s].material;
+    HIP_TRY(launch_query(Q, path, single, query == VRT_QUERY_ANY, stream));
+    return VRT_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -1605,6 +1641,61 @@ int vrt_render_rows(vrt_ctx* ctx, const vrt_params* params, int row0, int rows, 
     ctx->last_h = (uint32_t)rows;
     ctx->last_gather_ms = 0.f;
     ctx->last_total_ms = 0.f;
+    return VRT_OK;
+}
+
+int vrt_trace_rays(vrt_ctx* ctx, const vrt_params* params, int query, int n, const vrt_ray* device_rays, vrt_hit* device_hits,
+                   void* hip_stream) {
+    const int rc = check_query(ctx, params, query, n, device_rays, device_hits);
+    if (rc != VRT_OK || n == 0) return rc;
+    return enqueue_query(ctx, params, query, n, device_rays, device_hits, static_cast<hipStream_t>(hip_stream));
+}
+
+int vrt_trace_rays_host(vrt_ctx* ctx, const vrt_params* params, int query, int n, const vrt_ray* rays, vrt_hit* hits) {
+    int rc = check_query(ctx, params, query, n, rays, hits);
+    if (rc != VRT_OK || n == 0) return rc;
+    DeviceState& D = ctx->dev[0];
+    HIP_TRY(hipSetDevice(D.ordinal));
+    const size_t ray_bytes = sizeof(vrt_ray) * (size_t)n, hit_bytes = sizeof(vrt_hit) * (size_t)n;
+    rc = ensure_buffer(D.query_buf, D.query_cap, ray_bytes + hit_bytes);
+    if (rc != VRT_OK) return rc;
+    char* base = static_cast<char*>(D.query_buf);
+    HIP_TRY(hipMemcpyAsync(base, rays, ray_bytes, hipMemcpyHostToDevice, D.stream));
+    rc = enqueue_query(ctx, params, query, n, base, base + ray_bytes, D.stream);
+    if (rc != VRT_OK) {
+        (void)hipStreamSynchronize(D.stream);
+        return rc;
+    }
+    HIP_TRY(hipMemcpyAsync(hits, base + ray_bytes, hit_bytes, hipMemcpyDeviceToHost, D.stream));
+    HIP_TRY(hipStreamSynchronize(D.stream));
+    return VRT_OK;
+}
+
+int vrt_camera_rays(const vrt_scene* scene, int width, int height, int n, const int32_t* pixels_xy, vrt_ray* rays_out) {
+    if (!scene || n < 0 || (n > 0 && (!pixels_xy || !rays_out)) || width < 1 || height < 1 || width > 16384 || height > 16384)
+        return VRT_ERR_INVALID;
+    for (int i = 0; i < n; i++)
+        if (pixels_xy[2 * i] < 0 || pixels_xy[2 * i] >= width || pixels_xy[2 * i + 1] < 0 || pixels_xy[2 * i + 1] >= height) return VRT_ERR_INVALID;
+    DCam C;
+    pack_camera(scene_camera(*scene), width, height, C);
+    /* the march kernel's camera_ray, operation by operation (this file is compiled with -ffp-contract=off as the kernels are) */
+    const float inv_w = 1.0f / (float)width, inv_h = 1.0f / (float)height;
+    for (int i = 0; i < n; i++) {
+        const float sx = (((float)pixels_xy[2 * i] + 0.5f) * inv_w) * 2.0f - 1.0f;
+        const float sy = (((float)pixels_xy[2 * i + 1] + 0.5f) * inv_h) * 2.0f - 1.0f;
+        const float tx = sx * C.cx, ty = (-sy) * C.cy;
+        const H3 d = hnormalize(h3((tx * C.r0[0] + ty * C.r1[0]) - C.r2[0], (tx * C.r0[1] + ty * C.r1[1]) - C.r2[1],
+                                   (tx * C.r0[2] + ty * C.r1[2]) - C.r2[2]));
+        vrt_ray& r = rays_out[i];
+        r.origin[0] = C.cam_o[0];
+        r.origin[1] = C.cam_o[1];
+        r.origin[2] = C.cam_o[2];
+        r.t_max = 10000.0f;
+        r.direction[0] = d.x;
+        r.direction[1] = d.y;
+        r.direction[2] = d.z;
+        r.reserved_ = 0.0f;
+    }
     return VRT_OK;
 }
 

@@ -2849,6 +2849,98 @@ hipError_t launch_march(const DBlock& B, int path, bool single, hipStream_t stre
     }
 }
 
+/*
+ * Ray queries (vrt_trace_rays): one lane per caller-supplied ray, 256-lane workgroups, no LDS.  The march is the render's own
+ * trace_closest / trace_any (same contract, t_base 0, the exact-length normal of a camera ray's hit), without the diagnostic
+ * stamps, the per-wave counters, the cull rectangle or the wave-level reach test: a query batch has no screen.  The ray record is
+ * two 16-B loads, the hit record three 16-B stores.
+ */
+constexpr int kQueryThreads = 256;
+typedef float qf4 __attribute__((ext_vector_type(4)));
+typedef unsigned qu4 __attribute__((ext_vector_type(4)));
+
+template <int PATH, bool SINGLE, bool ANY, bool REF>
+__global__ __launch_bounds__(kQueryThreads) __attribute__((amdgpu_waves_per_eu(SINGLE ? 8 : 1))) void query_kernel(const DQuery Q) {
+    const DFrame& F = Q.f;
+    const unsigned i = blockIdx.x * (unsigned)kQueryThreads + threadIdx.x;
+    if (i >= (unsigned)Q.n) return;
+    const qf4* rec = reinterpret_cast<const qf4*>(Q.rays) + 2 * (size_t)i;
+    const qf4 r0 = rec[0], r1 = rec[1]; /* origin, t_max; direction, reserved */
+    const F3 o = f3(r0.x, r0.y, r0.z), draw = f3(r1.x, r1.y, r1.z);
+    const float t_max = r0.w;
+    const float l2 = dot3(draw, draw);
+    /* a zero-length or non-finite direction, a non-finite origin or a t_max that is NaN or negative: a miss, nothing marched */
+    const bool ok = l2 > 0.0f && l2 < __builtin_inff() && __builtin_isfinite(o.x) && __builtin_isfinite(o.y) && __builtin_isfinite(o.z) &&
+                    t_max >= 0.0f;
+    qu4 w0 = {__float_as_uint(-1.0f), 0u, 0u, 0u}; /* t, normal */
+    qu4 w1 = {0xffffffffu, 0xffffffffu, 0xffffffffu, 0xffffffffu}; /* instance, voxel */
+    qu4 w2 = {0u, 0u, 0u, 0u}; /* material, steps, reserved */
+    if (ok) {
+        const F3 d = normalize3(draw); /* as the oracle's vrto_trace */
+        unsigned steps = 0, ex = 0;
+        if constexpr (ANY) {
+            if (trace_any<PATH, SINGLE>(F, o, d, t_max, 0.0f, steps, ex)) w1.x = 0u;
+        } else {
+            float t = 0.0f;
+            int inst = 0;
+            F3 n = f3(0.0f, 0.0f, 0.0f);
+            if (trace_closest<PATH, SINGLE, false, 2, REF>(F, o, d, t_max, 0.0f, t, inst, n, steps, ex)) {
+                w0 = qu4{__float_as_uint(t), __float_as_uint(n.x), __float_as_uint(n.y), __float_as_uint(n.z)};
+                /* the nearest grid sample of the hit point, in the instance's object space (setup_ray's transform) */
+                const DInstance* I = SINGLE ? F.inst : F.inst + inst;
+                const int slot = I->slot;
+                const DVolume* V = SINGLE ? F.vol0 : F.vols + slot;
+                const F3 oo = mul33(I->w2o, f3(o.x - I->pos[0], o.y - I->pos[1], o.z - I->pos[2]));
+                const F3 od = mul33(I->w2o, d);
+                const float nmax = (float)(V->N - 1), ext = V->extent, ic = V->inv_cell;
+                const float px = __builtin_fmaf(od.x, t, oo.x), py = __builtin_fmaf(od.y, t, oo.y), pz = __builtin_fmaf(od.z, t, oo.z);
+                const int vx = (int)__builtin_amdgcn_fmed3f(floorf((px + ext) * ic + 0.5f), 0.0f, nmax);
+                const int vy = (int)__builtin_amdgcn_fmed3f(floorf((py + ext) * ic + 0.5f), 0.0f, nmax);
+                const int vz = (int)__builtin_amdgcn_fmed3f(floorf((pz + ext) * ic + 0.5f), 0.0f, nmax);
+                const uint8_t* mat = Q.material[slot];
+                const size_t N = (size_t)V->N;
+                w1 = qu4{(unsigned)inst, (unsigned)vx, (unsigned)vy, (unsigned)vz};
+                w2.x = mat != nullptr ? (unsigned)mat[((size_t)vx * N + (size_t)vz) * N + (size_t)vy] : 0u; /* grid order x, z, y */
+            }
+        }
+        w2.y = steps;
+    }
+    qu4* out = reinterpret_cast<qu4*>(Q.hits) + 3 * (size_t)i;
+    out[0] = w0;
+    out[1] = w1;
+    out[2] = w2;
+}
+
+template <int PATH>
+static hipError_t launch_query_t(const DQuery& Q, bool single, bool any, bool ref, hipStream_t stream) {
+    const dim3 g(((unsigned)Q.n + (unsigned)kQueryThreads - 1u) / (unsigned)kQueryThreads), t(kQueryThreads);
+    constexpr bool kCube = PATH == kPathCube || PATH == kPathCube16; /* (the cell walk's normal has no boundary-texel variant) */
+    if (any) {
+        if (single) hipLaunchKernelGGL((query_kernel<PATH, true, true, false>), g, t, 0, stream, Q);
+        else hipLaunchKernelGGL((query_kernel<PATH, false, true, false>), g, t, 0, stream, Q);
+    } else if (ref && !kCube) {
+        if (single) hipLaunchKernelGGL((query_kernel<PATH, true, false, !kCube>), g, t, 0, stream, Q);
+        else hipLaunchKernelGGL((query_kernel<PATH, false, false, !kCube>), g, t, 0, stream, Q);
+    } else {
+        if (single) hipLaunchKernelGGL((query_kernel<PATH, true, false, false>), g, t, 0, stream, Q);
+        else hipLaunchKernelGGL((query_kernel<PATH, false, false, false>), g, t, 0, stream, Q);
+    }
+    return hipGetLastError();
+}
+
+hipError_t launch_query(const DQuery& Q, int path, bool single, bool any, hipStream_t stream) {
+    if (Q.n <= 0) return hipSuccess;
+    const bool ref = Q.f.zero_outside != 0;
+    switch (path) {
+        case kPathCube: return launch_query_t<kPathCube>(Q, single, any, false, stream);
+        case kPathCube16: return launch_query_t<kPathCube16>(Q, single, any, false, stream);
+        case kPathBrick16: return launch_query_t<kPathBrick16>(Q, single, any, ref, stream);
+        case kPathCells16: return launch_query_t<kPathCells16>(Q, single, any, ref, stream);
+        case VRT_PATH_DENSE: return launch_query_t<VRT_PATH_DENSE>(Q, single, any, ref, stream);
+        default: return launch_query_t<VRT_PATH_BRICK>(Q, single, any, ref, stream); /* VRT_PATH_BRICK_LDS marches as VRT_PATH_BRICK */
+    }
+}
+
 hipError_t launch_retile(const float* dense, void* bricks, int format, int N, int nb, hipStream_t stream) {
     if (format == VRT_FORMAT_TEXEL16)
         hipLaunchKernelGGL(retile_bricks16_kernel, dim3((unsigned)(nb * nb * nb)), dim3(128), 0, stream, dense, static_cast<short*>(bricks), N, nb);

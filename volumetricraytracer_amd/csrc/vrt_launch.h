@@ -12,6 +12,18 @@ namespace vrt {
    never AUTO).
    block.f.n_frames frames (grid.y) in ONE launch, frame f with camera block.cam[f]. */
 hipError_t launch_march(const DBlock& block, int path, bool single_instance, hipStream_t stream);
+/* vrt_trace_rays: the kernarg of a query launch.  f: the scene and the march contract as build_frame fills them (no frame);
+   material: the slots' N^3 material grids (the hit record's material id). */
+struct DQuery {
+    DFrame f;
+    const void* rays; /* n vrt_ray records (32 B) */
+    void* hits;       /* n vrt_hit records (48 B) */
+    int32_t n;
+    int32_t pad_;
+    const uint8_t* material[VRT_MAX_VOLUMES];
+};
+/* n rays, one lane each: closest hit, or (any) occlusion.  path as launch_march takes it (VRT_PATH_BRICK_LDS marches as VRT_PATH_BRICK). */
+hipError_t launch_query(const DQuery& q, int path, bool single_instance, bool any, hipStream_t stream);
 /* dense grid -> brick records of `format` (fp32: 512 B, VRT_FORMAT_TEXEL16: 256 B of int16). */
 hipError_t launch_retile(const float* dense, void* bricks, int format, int N, int nb, hipStream_t stream);
 /* VRT_PATH_CELLS: integer field -> nb^3 x 64 cell records of 8 int16. */

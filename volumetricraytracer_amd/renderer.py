@@ -16,6 +16,31 @@ from . import _abi
 from .scene import VScene, VVoxelVolume, default_params, march_budget
 
 
+# numpy views of vrt_ray / vrt_hit (include/vrt.h)
+RAY_DTYPE = np.dtype([("origin", "<f4", 3), ("t_max", "<f4"), ("direction", "<f4", 3), ("reserved_", "<f4")])
+HIT_DTYPE = np.dtype([("t", "<f4"), ("normal", "<f4", 3), ("instance", "<i4"), ("voxel", "<i4", 3), ("material", "<u4"),
+                      ("steps", "<u4"), ("reserved_", "<u4", 2)])
+assert RAY_DTYPE.itemsize == C.sizeof(_abi.vrt_ray) and HIT_DTYPE.itemsize == C.sizeof(_abi.vrt_hit)
+
+
+def make_rays(origins, directions, t_max=10000.0) -> np.ndarray:
+    """A vrt_ray array from [n, 3] origins and directions and a scalar or per-ray t_max."""
+    o = np.asarray(origins, dtype=np.float32).reshape(-1, 3)
+    d = np.asarray(directions, dtype=np.float32).reshape(-1, 3)
+    if len(o) != len(d):
+        raise ValueError("origins and directions differ in length")
+    rays = np.zeros(len(o), RAY_DTYPE)
+    rays["origin"], rays["direction"] = o, d
+    rays["t_max"] = np.broadcast_to(np.asarray(t_max, dtype=np.float32), (len(o),))
+    return rays
+
+
+def hits_to_dict(hits: np.ndarray) -> dict:
+    """The fields of a vrt_hit array as separate numpy arrays; hit = instance >= 0."""
+    return {"hit": hits["instance"] >= 0, "t": hits["t"].copy(), "normal": hits["normal"].copy(), "instance": hits["instance"].copy(),
+            "voxel": hits["voxel"].copy(), "material": hits["material"].copy(), "steps": hits["steps"].copy()}
+
+
 class VHipRenderer:
     def __init__(self, devices: Sequence[int] = (0,)):
         self._lib = _abi.load()
@@ -337,6 +362,47 @@ class VHipRenderer:
             return np.frombuffer(buf, dtype=np.uint8).reshape(params.height, params.width, 4).copy()
         buf = (C.c_float * (params.width * params.height * 4)).from_address(ptr.value)
         return np.frombuffer(buf, dtype=np.float32).reshape(params.height, params.width, 4).copy()
+
+    # -- ray queries (vrt_trace_rays*, vrt_camera_rays) ----------------------------------------------------------------------------
+    def trace_rays(self, origins, directions, t_max=10000.0, any_hit: bool = False, params: Optional[_abi.vrt_params] = None) -> dict:
+        """Closest hit (or, any_hit, occlusion within t_max) of world-space rays against the synced scene, on the GPU
+        (vrt_trace_rays_host): a dict of numpy arrays hit, t, normal, instance, voxel, material, steps.  Syncs the scene first;
+        params defaults to make_params() (the render's march contract).  t_max: a scalar or one value per ray."""
+        self._require()
+        self.SyncWithScene()
+        p = params if params is not None else self.make_params()
+        rays = make_rays(origins, directions, t_max)
+        hits = np.zeros(len(rays), HIT_DTYPE)
+        query = _abi.QUERY_ANY if any_hit else _abi.QUERY_CLOSEST
+        _abi.check(self._lib.vrt_trace_rays_host(self._ctx, C.byref(p), query, len(rays), rays.ctypes.data_as(C.c_void_p),
+                                                 hits.ctypes.data_as(C.c_void_p)), "vrt_trace_rays_host")
+        return hits_to_dict(hits)
+
+    def trace_rays_device(self, params: _abi.vrt_params, query: int, n: int, rays_ptr: int, hits_ptr: int, stream: int = 0) -> None:
+        """Asynchronous query of n vrt_ray records in device memory into n vrt_hit records (vrt_trace_rays); allocates
+        nothing, so it can be captured into a graph.  Does not sync the scene."""
+        self._require()
+        _abi.check(self._lib.vrt_trace_rays(self._ctx, C.byref(params), int(query), int(n), C.c_void_p(rays_ptr), C.c_void_p(hits_ptr),
+                                            C.c_void_p(stream)), "vrt_trace_rays")
+
+    def camera_rays(self, pixels, width: Optional[int] = None, height: Optional[int] = None) -> np.ndarray:
+        """The march kernel's camera rays of (x, y) pixels of the scene's camera, bit for bit, as a vrt_ray array
+        (vrt_camera_rays; host only).  Default frame size: the current output size."""
+        if self._scene is None:
+            raise RuntimeError("SetSceneToRender was not called")
+        px = np.ascontiguousarray(pixels, dtype=np.int32).reshape(-1, 2)
+        rays = np.zeros(len(px), RAY_DTYPE)
+        sc = self._scene.to_abi()
+        _abi.check(self._lib.vrt_camera_rays(C.byref(sc), int(width or self.Width), int(height or self.Height), len(px),
+                                             px.ctypes.data_as(C.c_void_p), rays.ctypes.data_as(C.c_void_p)), "vrt_camera_rays")
+        return rays
+
+    def pick(self, px: int, py: int, params: Optional[_abi.vrt_params] = None) -> dict:
+        """What lies under pixel (px, py) of the current output size: the closest hit of its camera ray with make_params()
+        (the render's cone_eps), as trace_rays returns it for one ray, with scalar fields."""
+        r = self.camera_rays([(px, py)])
+        out = self.trace_rays(r["origin"], r["direction"], r["t_max"], params=params)
+        return {k: (v[0] if v.ndim == 1 else v[0].copy()) for k, v in out.items()}
 
     # -- multi-GPU exchange, one process per GPU (vrt_comm_* / vrt_gather_tiles: RCCL ncclGather) --------------------
     @staticmethod
