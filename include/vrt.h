@@ -260,7 +260,12 @@ int vrt_volume_upload_voxels(vrt_ctx* ctx, int slot, uint8_t resolution, float e
                              const vrt_voxel* voxels);
 /* Device format of the volumes uploaded FROM NOW ON (vrt_volume_upload, _upload_voxels, vrt_voxelize_mesh); default
  * VRT_FORMAT_F32.  With VRT_FORMAT_TEXEL16 the upload quantises every density on the device the way
- * VDXVoxelVolume::UpdateVolumeTexture does on the host (RDXVoxelVolume.cpp:294-327).  Volumes already resident keep theirs. */
+ * VDXVoxelVolume::UpdateVolumeTexture does on the host (RDXVoxelVolume.cpp:294-327).  Volumes already resident keep theirs.
+ * The texel rule, for every density d (the reference's (uint16_t)(abs(d) * 100.f) leaves out-of-range values undefined):
+ * a = |d| * 100 in fp32; q = 0xffffffff when a >= 4294967040 (+-inf included), 0 when d is NaN, else trunc(a); q &= 0x7fff;
+ * the texel holds -q when d < 0 (so a small negative d keeps its sign as -0.0), else q.  The Python encoders
+ * (VVoxelVolume.reference_texels / quantize_like_reference_texels) follow the same rule, so vrt_volume_upload_texels of
+ * their texture holds what this upload holds. */
 int vrt_set_volume_format(vrt_ctx* ctx, int format);
 /* The reference's volume texture itself: N^3 R8G8B8A8_UINT texels, texel (x,y,z) at byte 4*(z*N*N + y*N + x)
  * (UpdateVolumeTexture, RDXVoxelVolume.cpp:294-327 with Core/Private/MathHelpers (2).cpp:26-46): R = sign<<7 | q>>8,

@@ -102,6 +102,8 @@ def load() -> C.CDLL:
         lib.vrto_literal_octree_info.argtypes = [C.POINTER(vrto_volume), C.POINTER(vrto_octree_info)]
         lib.vrto_debug_tables.restype = C.c_int
         lib.vrto_debug_tables.argtypes = [C.POINTER(vrto_volume), C.c_void_p, C.c_void_p, C.c_void_p]
+        lib.vrto_debug_cube_table.restype = C.c_int
+        lib.vrto_debug_cube_table.argtypes = [C.POINTER(vrto_volume), C.c_void_p, C.c_void_p]
         lib.vrto_env_lookup.restype = None
         lib.vrto_env_lookup.argtypes = [C.c_void_p, C.c_int, C.POINTER(C.c_float), C.POINTER(C.c_float)]
         _lib = lib
@@ -253,6 +255,18 @@ class OracleScene:
         if rc != 0:
             raise RuntimeError(f"vrto_debug_tables failed: {rc}")
         return skip, nib, field
+
+    def cube_table(self, slot: int):
+        """(cube_skip [nb,nb,nb] uint8 Chebyshev brick distances of the Cube modes, active box [6] int32 {min x, z, y, max x, z, y}
+        of the near bricks, or None without a bounded step) of the volume in `slot`."""
+        vol = self.scene.volumes()[slot]
+        nb = (vol.N - 1 + 3) // 4
+        cube = np.zeros((nb, nb, nb), np.uint8)
+        box = np.zeros(6, np.int32) if vol.step_max > 0 else None
+        rc = load().vrto_debug_cube_table(C.byref(self.vols[slot]), cube.ctypes.data, None if box is None else box.ctypes.data)
+        if rc != 0:
+            raise RuntimeError(f"vrto_debug_cube_table failed: {rc}")
+        return cube, box
 
     def sample(self, slot: int, p) -> float:
         return float(load().vrto_sample(C.byref(self.vols[slot]), _f3(p)))

@@ -1519,6 +1519,16 @@ int vrto_debug_tables(const vrto_volume* vol, uint8_t* skip_out, uint32_t* nib_o
     return VRT_OK;
 }
 
+int vrto_debug_cube_table(const vrto_volume* vol, uint8_t* cube_skip_out, int32_t* box_out) {
+    if (!vol || !vol->density || (box_out && !(vol->step_max > 0.0f))) return VRT_ERR_INVALID;
+    const int N = (1 << vol->resolution) + 1, nb = (N - 1 + 3) / 4;
+    std::shared_ptr<const Derived> d = derive(*vol, N, nb, true);
+    if (cube_skip_out) memcpy(cube_skip_out, d->cube_skip.data(), (size_t)nb * nb * nb);
+    if (box_out)
+        for (int i = 0; i < 6; i++) box_out[i] = d->abox[i];
+    return VRT_OK;
+}
+
 void vrto_env_lookup(const uint8_t* env_rgba8, int face_size, const float dir[3], float rgb_out[3]) {
     env_lookup(env_rgba8, face_size, v3(dir[0], dir[1], dir[2]), rgb_out);
 }

@@ -146,6 +146,10 @@ int vrto_literal_octree_info(const vrto_volume* vol, vrto_octree_info* out);
  * Chebyshev brick distances D, nib_out: nb^3 words of sub-block nibbles — and (field_out, N^3 floats) the field the march
  * samples (the integer field +-q for VRT_FORMAT_TEXEL16).  Any pointer may be NULL. */
 int vrto_debug_tables(const vrto_volume* vol, uint8_t* skip_out, uint32_t* nib_out, float* field_out);
+/* Debug: the Cube modes' table of `vol` (cube_skip_out: nb^3 Chebyshev brick distances to the nearest brick with a solid
+ * cell-origin voxel) and, for a bounded-step volume (step_max > 0), the active box {min x, z, y, max x, z, y} of the near bricks
+ * (box_out: 6 ints; VRT_ERR_INVALID when asked for without a bounded step).  Either pointer may be NULL. */
+int vrto_debug_cube_table(const vrto_volume* vol, uint8_t* cube_skip_out, int32_t* box_out);
 
 /* Cube-map lookup used by the miss path (dir is a world direction; returns rgb). */
 void vrto_env_lookup(const uint8_t* env_rgba8, int face_size, const float dir[3], float rgb_out[3]);

@@ -114,6 +114,23 @@ class VMaterial:
         return m
 
 
+def texel16_q(density) -> np.ndarray:
+    """q of the reference's 16-bit volume texel (VRT_FORMAT_TEXEL16), uint32 of the shape of `density`: a = |d| * 100 in fp32;
+    q = trunc(a), except 0xffffffff when a >= 4294967040 (the largest fp32 below 2^32, +-inf included) and 0 when d is NaN;
+    then q &= 0x7fff.  The texel's sign is d < 0, so a small negative density keeps it (-0.0) while NaN does not.  The
+    reference's own (uint16_t)(abs(d) * 100.f) leaves out-of-range values undefined; this is the rule of the device quantiser
+    (texel16_value, vrt_kernels.hip, and vrt_set_volume_format in vrt.h), which every encoder here follows."""
+    d = np.asarray(density, dtype=np.float32)
+    with np.errstate(over="ignore", invalid="ignore"):  # inf / NaN in, by design
+        a = np.abs(d) * np.float32(100.0)
+    sat = a >= np.float32(4294967040.0)
+    fin = (a >= np.float32(0.0)) & ~sat  # NaN: neither
+    q = np.zeros(d.shape, dtype=np.uint64)
+    q[fin] = a[fin].astype(np.uint64)
+    q[sat] = 0xFFFFFFFF
+    return (q & 0x7FFF).astype(np.uint32)
+
+
 class VVoxelVolume:
     """Dense voxel grid.  N = 2^resolution + 1 voxels per axis, cube [-extent, extent]^3.
 
@@ -195,10 +212,12 @@ class VVoxelVolume:
 
     def reference_texels(self) -> np.ndarray:
         """The reference's volume texture for this volume: uint8 [N, N, N, 4] indexed [z, y, x] with
-        R = sign<<7 | q>>8, G = q & 0xff, B = A = material, q = trunc(|d| * 100) & 0x7fff
-        (VDXVoxelVolume::UpdateVolumeTexture / EncodeVoxel, Renderer/DX/Private/RDXVoxelVolume.cpp:294-327, 399-421)."""
+        R = sign<<7 | q>>8, G = q & 0xff, B = A = material (VDXVoxelVolume::UpdateVolumeTexture / EncodeVoxel,
+        Renderer/DX/Private/RDXVoxelVolume.cpp:294-327, 399-421), q and the sign by the texel rule of texel16_q —
+        the rule the device quantiser applies, so that vrt_volume_upload_texels of this texture holds what
+        vrt_volume_upload of the densities holds in VRT_FORMAT_TEXEL16, non-finite and huge densities included."""
         d = np.asarray(self.density, dtype=np.float32)               # [x, z, y]
-        q = ((np.abs(d) * np.float32(100.0)).astype(np.int64) & 0x7FFF).astype(np.uint16)
+        q = texel16_q(d).astype(np.uint16)
         tex = np.zeros((self.N, self.N, self.N, 4), dtype=np.uint8)  # [z, y, x, rgba]
         r = ((q >> 8).astype(np.uint8) | np.where(d < 0, 0x80, 0).astype(np.uint8))
         for ch, a in ((0, r), (1, (q & 0xFF).astype(np.uint8)), (2, self.material_id), (3, self.material_id)):
@@ -206,12 +225,12 @@ class VVoxelVolume:
         return tex
 
     def quantize_like_reference_texels(self) -> "VVoxelVolume":
-        """Rounds the densities the way the reference's GPU texture does: sign bit + 15-bit trunc(|d| * 100)
-        (VDXVoxelVolume::EncodeVoxel, Renderer/DX/Private/RDXVoxelVolume.cpp:399-421; DecodeDensity,
+        """Rounds the densities the way the reference's GPU texture does: sign bit + 15-bit q of texel16_q, decoded as
+        (+-q) * 0.01 (VDXVoxelVolume::EncodeVoxel, Renderer/DX/Private/RDXVoxelVolume.cpp:399-421; DecodeDensity,
         Shaders/Include/Voxel.hlsli:254-266).  This build keeps fp32 on the device; apply this before the
         upload to march exactly the field the DXR backend sees (0.01 quantum, magnitudes wrap at 327.68)."""
         d = np.asarray(self.density, dtype=np.float32)
-        q = ((np.abs(d) * np.float32(100.0)).astype(np.int64) & 0xFFFF & 0x7FFF).astype(np.float32) * np.float32(0.01)
+        q = texel16_q(d).astype(np.float32) * np.float32(0.01)
         self.density = np.where(d < 0, -q, q).astype(np.float32)
         self.dirty = True
         return self
