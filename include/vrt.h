@@ -18,6 +18,8 @@
  *   vrt_volume_update_region,       VVoxelVolume::SetVoxel / MakeDirty / IsDirty  Voxel/Private/VoxelVolume.cpp:59-137, and
  *   vrt_volume_update_voxels        VDXVoxelVolume::UpdateFromVoxelVolume  RDXVoxelVolume.cpp:33-60 (re-upload of a dirty volume),
  *                                   for a box of voxels instead of the whole volume
+ *   vrt_volume_apply_brushes,       (no reference analogue beyond VVoxelVolume::SetVoxel, VoxelVolume.cpp:59-77, in a host loop: CSG
+ *   vrt_volume_download_region      sphere / box / capsule brushes evaluated on the resident volume, and the read-back of a box)
  *   vrt_volume_free                 VRDXScene::RemoveVoxelVolume  Renderer/DX/Private/RDXScene.cpp:663-701
  *   vrt_env_upload                  VRDXScene::InitEnvironmentMap RDXScene.cpp:181-199
  *   vrt_scene_set                   VRDXScene::SyncWithScene + PrepareForRendering
@@ -307,6 +309,75 @@ int vrt_volume_update_region(vrt_ctx* ctx, int slot, const int origin_xyz[3], co
                              const float* density, const uint8_t* material_or_null);
 /* Same from VVoxel records (VVoxelVolume's storage, the adaptor's), same box order. */
 int vrt_volume_update_voxels(vrt_ctx* ctx, int slot, const int origin_xyz[3], const int size_xyz[3], const vrt_voxel* voxels);
+
+/* CSG sculpt brushes, evaluated on the device (no reference analogue beyond VVoxelVolume::SetVoxel in a host loop): the caller hands
+ * over 64-byte records instead of a box of voxels. */
+#define VRT_MAX_BRUSHES 32           /* records per call */
+enum { VRT_BRUSH_SPHERE = 0, VRT_BRUSH_BOX = 1, VRT_BRUSH_CAPSULE = 2 };
+enum { VRT_BRUSH_ADD = 0, VRT_BRUSH_SUBTRACT = 1, VRT_BRUSH_PAINT = 2 };
+
+typedef struct vrt_brush {            /* 64 B; all lengths in CELLS of the slot's grid, positions in grid coordinates */
+    int32_t shape, op;
+    float a[3];        /* (x, y, z) as vrt_volume_update_region and vrt_hit::voxel number them, fractions allowed:
+                          sphere / box: centre; capsule: first end */
+    float b[3];        /* box: half sizes (> 0); capsule: second end (!= a); sphere: ignored */
+    float radius;      /* sphere, capsule: radius > 0; box: corner rounding >= 0 */
+    float blend;       /* smooth-min / smooth-max width, >= 0; 0 = hard CSG */
+    float reach;       /* > 0: only samples whose brush distance s is < reach are looked at (ADD, SUBTRACT) */
+    int32_t material;  /* 0..255, or -1 = leave material ids alone (PAINT: must be 0..255) */
+    uint32_t reserved_[4];            /* 0 */
+} vrt_brush;
+
+typedef struct vrt_brush_result {     /* 32 B */
+    int32_t lo[3], hi[3];             /* xyz, inclusive: bounding box of the samples written; lo > hi when none */
+    uint64_t written;                 /* samples written at least once (density or material) */
+} vrt_brush_result;
+
+/* Applies the n records, in order, to the resident slot, in place, on every device.  Waits for work already enqueued on the
+ * context's devices (a frame begun before the call renders the old volume, one begun after renders the new one); device pointers
+ * of the slot do not change.  Afterwards every device buffer of the slot equals what a full upload of the edited volume holds, so
+ * frames and counters are those of the full upload.  A launch captured into a graph before the edit keeps the cull rectangle it
+ * was captured with (capture with VRT_FLAG_NO_CULL_RECT where an edit may grow the active box).
+ * Errors, all checked before any device state is touched: VRT_ERR_SLOT for an unused slot; VRT_ERR_INVALID for a NULL context, or
+ * NULL records with n > 0; n < 0 or n > VRT_MAX_BRUSHES; an unknown shape or op; a non-finite field; a radius, half size or reach
+ * that is not positive (a sphere's b and a PAINT record's reach and blend are only checked for being finite); a negative blend or
+ * a negative rounding radius; a capsule with a == b; a material outside -1..255, or PAINT with material -1; non-zero reserved
+ * words.  n == 0 is OK and changes nothing.  A brush that lies wholly outside the grid is not an error: it writes nothing.
+ * result_or_null: the written samples' count and box, from device 0 (all devices compute the same bytes).
+ *
+ * The arithmetic is part of the contract.  It is all fp32, evaluated exactly as parenthesised (no fused multiply-add; square
+ * root and division correctly rounded).  dot(u,v) = (u.x*v.x + u.y*v.y) + u.z*v.z, len(u) = sqrtf(dot(u,u)), and
+ * p = ((float)ix, (float)iy, (float)iz) for the sample (ix, iy, iz).
+ *   Sphere:  s = len(p - a) - radius.
+ *   Capsule: with pa = p - a and ba = b - a: h = fminf(fmaxf(dot(pa,ba) / dot(ba,ba), 0), 1); s = len(pa - ba*h) - radius.
+ *   Box:     q = fabsf(p - a) - b + radius (per component);
+ *            s = (len(fmaxf(q, 0)) + fminf(fmaxf(q.x, fmaxf(q.y, q.z)), 0)) - radius.
+ *   Units:   cell = (extent * 2.0f) / (float)(N - 1); unit = cell / density_scale — the caller's density_scale
+ *            (vrt_volume_set_metric), without the 0.01 of VRT_FORMAT_TEXEL16; both computed once on the host.
+ *            Brush value v = s * unit; blend width k = blend * unit.
+ *   d is the sample's current density in the caller's units: the stored float (VRT_FORMAT_F32), or stored * 0.01f
+ *   (VRT_FORMAT_TEXEL16, as vrt_volume_download decodes it).
+ *   ADD:      m = fminf(d, v); when k > 0: g = fmaxf(k - fabsf(d - v), 0) / k and m = m - ((g*g)*k)*0.25f.
+ *             The sample is written iff s < reach && m < d.
+ *   SUBTRACT: c = -v and m = fmaxf(d, c); when k > 0: g = fmaxf(k - fabsf(d - c), 0) / k and m = m + ((g*g)*k)*0.25f.
+ *             The sample is written iff s < reach && m > d.
+ *   A written sample stores m (F32) or the texel of m (TEXEL16: the rule at vrt_set_volume_format).  With material >= 0 its
+ *   material id becomes m <= 0 ? material : 0 — the Voxelizer's rule, material = (density <= 0).
+ *   A sample that is not written keeps its stored bits (a TEXEL16 value need not survive decode + encode: trunc(q*0.01f*100.f) != q
+ *   for q = 5, 10, 15, 20, 23, ...).  NaN densities are never written: both comparisons are false for them.
+ *   PAINT:    a sample with s <= 0 && d <= 0 whose material id differs from `material` gets it.  Densities do not change; reach
+ *             and blend are ignored.
+ *   Order:    record i+1 sees what record i left, per sample, re-decoded from the stored value (so a TEXEL16 slot quantises
+ *             between records): one call with n records leaves what n calls with one record each leave.
+ * Choosing reach: it states how far from the brush surface the field must be corrected.  A cell or two suffices for carving
+ * (SUBTRACT only raises values near the new surface).  For adding into a true SDF it is as far as the old field over-estimates the
+ * distance to the new solid.  A slot with step_max > 0 never steps further than step_max, so step_max/cell + 1 is enough there. */
+int vrt_volume_apply_brushes(vrt_ctx* ctx, int slot, int n, const vrt_brush* brushes, vrt_brush_result* result_or_null);
+/* Reads the box [origin, origin+size) of device 0's slot as VVoxel records: box order as vrt_volume_update_voxels takes it, decode
+ * as vrt_volume_download's.  Only the box's bytes cross the bus, so a host mirror can follow a device-side edit without a full
+ * download.  Argument checks as vrt_volume_update_region's.  On a VRT_FORMAT_TEXEL16 slot the decoded values (q * 0.01f) re-quantise
+ * when uploaded again and need not give q back — as with vrt_volume_download. */
+int vrt_volume_download_region(vrt_ctx* ctx, int slot, const int origin_xyz[3], const int size_xyz[3], vrt_voxel* out);
 
 /* Tests: the raw bytes of one device buffer of a slot on device `device_index` of the context.  *size_out (when not NULL) = the
  * buffer's size; out == NULL only asks for it; a capacity below the size is VRT_ERR_INVALID.  The tables are the first nb^3

@@ -67,6 +67,11 @@ PATH_BRICK = 2
 PATH_BRICK_LDS = 3
 PATH_CELLS = 4
 
+# vrt_volume_apply_brushes
+MAX_BRUSHES = 32
+BRUSH_SPHERE, BRUSH_BOX, BRUSH_CAPSULE = 0, 1, 2
+BRUSH_ADD, BRUSH_SUBTRACT, BRUSH_PAINT = 0, 1, 2
+
 QUERY_CLOSEST = 0
 QUERY_ANY = 1  # occlusion: instance 0 when some surface lies within [0, t_max]
 
@@ -201,6 +206,24 @@ class vrt_hit(C.Structure):
     ]
 
 
+class vrt_brush(C.Structure):
+    _fields_ = [
+        ("shape", C.c_int32),
+        ("op", C.c_int32),
+        ("a", C.c_float * 3),
+        ("b", C.c_float * 3),
+        ("radius", C.c_float),
+        ("blend", C.c_float),
+        ("reach", C.c_float),
+        ("material", C.c_int32),
+        ("reserved_", C.c_uint32 * 4),
+    ]
+
+
+class vrt_brush_result(C.Structure):
+    _fields_ = [("lo", C.c_int32 * 3), ("hi", C.c_int32 * 3), ("written", C.c_uint64)]
+
+
 SYMBOLS = {
     "vrt_create": (C.c_int, [C.POINTER(C.c_void_p), C.c_int, C.POINTER(C.c_int)]),
     "vrt_destroy": (C.c_int, [C.c_void_p]),
@@ -219,6 +242,8 @@ SYMBOLS = {
     "vrt_volume_free": (C.c_int, [C.c_void_p, C.c_int]),
     "vrt_volume_update_region": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int), C.c_void_p, C.c_void_p]),
     "vrt_volume_update_voxels": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int), C.c_void_p]),
+    "vrt_volume_apply_brushes": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.POINTER(vrt_brush), C.POINTER(vrt_brush_result)]),
+    "vrt_volume_download_region": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int), C.c_void_p]),
     "vrt_debug_volume_bytes": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_size_t, C.POINTER(C.c_size_t)]),
     "vrt_env_upload": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p]),
     "vrt_scene_set": (C.c_int, [C.c_void_p, C.POINTER(vrt_scene)]),

@@ -114,6 +114,13 @@ public:
         return hit.instance >= 0 && (size_t)hit.instance < QueryObjects.size() ? QueryObjects[(size_t)hit.instance] : nullptr;
     }
 
+    /* CSG sculpt brushes evaluated on the device (vrt_volume_apply_brushes; the records and their arithmetic: vrt.h) on the volume of
+       a placed object of the scene Render() would draw now (synced first).  The box of written voxels is then read back into the
+       host VVoxelVolume (vrt_volume_download_region) without marking it dirty: the device is already current.  With VolumeFormat
+       VRT_FORMAT_TEXEL16 the mirror receives the decoded texels (q * 0.01), which quantise again — and need not give q back — should
+       the volume be uploaded whole later.  False (after logging) on failure or when the object's volume is not in the scene. */
+    bool ApplyBrushes(const Scene::VVoxelObject& object, const std::vector<vrt_brush>& brushes, vrt_brush_result* result = nullptr);
+
 private:
     bool SyncWithScene(Scene::VScene& scene);
     bool FillSceneStruct(Scene::VScene& scene, vrt_scene& out, std::vector<const Scene::VVoxelObject*>* objects = nullptr);

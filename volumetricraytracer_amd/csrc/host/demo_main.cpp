@@ -15,6 +15,8 @@
  *            [--edit-brush R]               every frame carves a sphere of radius R cells out of the red sphere's volume along a circle (SetVoxel +
  *                                           MakeDirtyRegion): the renderer updates the edited box in place (vrt_volume_update_voxels)
  *            [--edit-full]                  ... and uploads the whole volume after every edit instead (the same frames)
+ *            [--edit-device]                with --edit-brush: the carve is one SUBTRACT sphere record evaluated on the device
+ *                                           (VHipRenderer::ApplyBrushes, vrt_volume_apply_brushes); no host loop, no box upload
  *            [--pick X Y]                   every frame asks what lies under pixel (X, Y) (VHipRenderer::Pick: a GPU ray query) and prints the
  *                                           hit record; with --edit-brush the brush is centred on the picked voxel when the pick hits the red
  *                                           sphere, and a frame whose pick misses it edits nothing
@@ -71,7 +73,7 @@ int main(int argc, char** argv) {
     std::string scenePath, skyboxDir, outPath = "vrt_demo.ppm";
     bool identityDefaults = false;
     int editBrush = 0;
-    bool editFull = false;
+    bool editFull = false, editDevice = false;
     bool pick = false;
     int pickX = 0, pickY = 0;
     int mode = 0, inFlight = 3, block = 0; /* three frames in flight: the reference's swap chain (FrameCount, DXConstants.cpp:23) */
@@ -90,6 +92,7 @@ int main(int argc, char** argv) {
         else if (!strcmp(argv[i], "--identity-defaults")) identityDefaults = true;
         else if (!strcmp(argv[i], "--edit-brush") && i + 1 < argc) editBrush = atoi(argv[++i]);
         else if (!strcmp(argv[i], "--edit-full")) editFull = true;
+        else if (!strcmp(argv[i], "--edit-device")) editDevice = true;
         else if (!strcmp(argv[i], "--pick") && i + 2 < argc) {
             pick = true;
             pickX = atoi(argv[++i]);
@@ -148,6 +151,7 @@ int main(int argc, char** argv) {
         fprintf(stderr, "--edit-brush edits the volume every frame: RenderBlock refuses that; drop --block\n");
         return 1;
     }
+    if (editDevice && !hip) editDevice = false;
     if (pick && (!hip || block > 0)) {
         fprintf(stderr, "--pick asks the HIP renderer once per frame: drop --block\n");
         return 1;
@@ -157,6 +161,18 @@ int main(int argc, char** argv) {
     /* the brush: a sphere of editBrush cells around voxel c — a point that circles the red sphere's centre 12 cells out, 4 cells above
        it, or (--pick) the voxel under the picked pixel; union (CSG difference) with the field, the box it can change marked dirty */
     auto carve = [&](const VIntVector& c) {
+        if (editDevice) { /* the same sphere as one brush record: hard SUBTRACT, corrected two cells beyond its surface, material 0 */
+            vrt_brush b;
+            memset(&b, 0, sizeof b);
+            b.shape = VRT_BRUSH_SPHERE;
+            b.op = VRT_BRUSH_SUBTRACT;
+            b.a[0] = (float)c.X, b.a[1] = (float)c.Y, b.a[2] = (float)c.Z;
+            b.radius = (float)editBrush;
+            b.reach = 2.f;
+            b.material = 0;
+            hip->ApplyBrushes(*sphere1, {b});
+            return;
+        }
         Voxel::VVoxelVolume& vol = *sphere1->GetVoxelVolume();
         const int r = editBrush;
         const float cell = vol.GetCellSize();
@@ -228,7 +244,7 @@ int main(int argc, char** argv) {
         if (hip) hip->Flush(); /* collect the frames still in flight: GetFrameData() is the last frame again */
     }
     const double wall = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
-    if (editBrush > 0) printf("brush of %d cells, %s; ", editBrush, editFull ? "full uploads" : "region updates");
+    if (editBrush > 0) printf("brush of %d cells, %s; ", editBrush, editDevice ? "device brushes" : (editFull ? "full uploads" : "region updates"));
     printf("%d frames %ux%u %s%s: %.3f ms/frame wall (%.0f frames/s)", frames, W, H, format.c_str(),
            block > 0 ? (", RenderBlock of " + std::to_string(block)).c_str() : (", " + std::to_string(inFlight) + " in flight").c_str(), wall / frames * 1e3, frames / wall);
     if (kernel_ms > 0.0) printf(", march kernel %.3f ms/%s", kernel_ms / (block > 0 ? (frames + block - 1) / block : frames), block > 0 ? "block" : "frame");

@@ -89,6 +89,8 @@ RcclApi* rccl() {
 static_assert(kDynMaxInstances == VRT_MAX_INSTANCES && kMaxBvhNodes == 2 * VRT_MAX_INSTANCES - 1, "section capacity = VRT_MAX_INSTANCES");
 static_assert(kDynMaxPointLights == VRT_MAX_POINT_LIGHTS && kDynMaxSpotLights == VRT_MAX_SPOT_LIGHTS, "section capacity = VRT_MAX_*_LIGHTS");
 static_assert(sizeof(vrt_ray) == 32 && sizeof(vrt_hit) == 48, "query_kernel reads two and writes three 16-B words per ray");
+static_assert(sizeof(vrt_brush) == 64 && sizeof(vrt_brush_result) == 32, "vrt.h states these sizes");
+static_assert(sizeof(DBrushList) <= 3072, "the brush records travel in the kernel-argument block");
 
 constexpr int kStatSlots = 16; /* streams that may have launches in flight at once without sharing a counter buffer */
 constexpr int kRing = 256; /* per-launch event pairs + stat slots kept for vrt_timing_history */
@@ -210,6 +212,7 @@ struct DeviceState {
     void* edit_scratch = nullptr;
     size_t edit_scratch_cap = 0;
     int* d_box6 = nullptr;
+    DBrushSlot* d_brush = nullptr; /* vrt_volume_apply_brushes: what the brush launch wrote (kBrushSlots partial records) */
     /* vrt_trace_rays_host: the rays and then the hit records of a batch (grown on demand) */
     void* query_buf = nullptr;
     size_t query_cap = 0;
@@ -572,6 +575,7 @@ void destroy_device(DeviceState& D) {
     if (D.edit_staging) (void)hipFree(D.edit_staging);
     if (D.edit_scratch) (void)hipFree(D.edit_scratch);
     if (D.d_box6) (void)hipFree(D.d_box6);
+    if (D.d_brush) (void)hipFree(D.d_brush);
     if (D.query_buf) (void)hipFree(D.query_buf);
     if (D.d_vols) (void)hipFree(D.d_vols);
     if (D.d_inst) (void)hipFree(D.d_inst);
@@ -800,6 +804,174 @@ int update_region(vrt_ctx* ctx, int slot, const int origin[3], const int size[3]
     memcpy(h.abox, box, sizeof box); /* unchanged without the tables, as upload_volume leaves it */
     ctx->scene_stale = true;
     return sync_volume_table(ctx);
+}
+
+/* vrt_volume_apply_brushes: the argument rules of vrt.h for one record. */
+bool valid_brush(const vrt_brush& r) {
+    if (r.shape != VRT_BRUSH_SPHERE && r.shape != VRT_BRUSH_BOX && r.shape != VRT_BRUSH_CAPSULE) return false;
+    if (r.op != VRT_BRUSH_ADD && r.op != VRT_BRUSH_SUBTRACT && r.op != VRT_BRUSH_PAINT) return false;
+    for (int a = 0; a < 3; a++)
+        if (!std::isfinite(r.a[a]) || !std::isfinite(r.b[a])) return false;
+    for (uint32_t w : r.reserved_)
+        if (w != 0u) return false;
+    if (!std::isfinite(r.radius) || !std::isfinite(r.blend) || !std::isfinite(r.reach)) return false;
+    if (r.shape == VRT_BRUSH_BOX) {
+        if (!(r.b[0] > 0.f && r.b[1] > 0.f && r.b[2] > 0.f) || r.radius < 0.f) return false;
+    } else if (!(r.radius > 0.f)) {
+        return false;
+    }
+    if (r.shape == VRT_BRUSH_CAPSULE && r.a[0] == r.b[0] && r.a[1] == r.b[1] && r.a[2] == r.b[2]) return false;
+    if (r.material < -1 || r.material > 255) return false;
+    if (r.op == VRT_BRUSH_PAINT) return r.material >= 0;
+    return r.reach > 0.f && r.blend >= 0.f;
+}
+
+/* The samples a record can write, xyz, inclusive: the shape's bounds grown by reach (PAINT: by nothing), by one sample and by the
+ * rounding of the fp32 distance at that magnitude, clipped to the grid.  False when no sample is left. */
+bool brush_box(const vrt_brush& r, int N, int lo[3], int hi[3]) {
+    for (int a = 0; a < 3; a++) {
+        double c0 = r.a[a], c1 = r.a[a], ext = r.shape == VRT_BRUSH_BOX ? r.b[a] : r.radius;
+        if (r.shape == VRT_BRUSH_CAPSULE) {
+            c0 = std::min(r.a[a], r.b[a]);
+            c1 = std::max(r.a[a], r.b[a]);
+        }
+        if (r.op != VRT_BRUSH_PAINT) ext += r.reach;
+        const double pad = 1.0 + 1e-5 * (std::max(std::fabs(c0), std::fabs(c1)) + ext + N);
+        const double l = std::max(std::floor(c0 - ext - pad), 0.0), h = std::min(std::ceil(c1 + ext + pad), (double)(N - 1));
+        if (l > h) return false;
+        lo[a] = (int)l;
+        hi[a] = (int)h;
+    }
+    return true;
+}
+
+/* vrt_volume_apply_brushes: the records are evaluated on the device over the union of their boxes (launch_brush_region), which
+ * reports the box of the samples it wrote; what the full upload derives from the samples is then recomputed over that box, by the
+ * kernels and in the order of update_region — or not at all when no density changed.  Afterwards every buffer equals what
+ * upload_volume builds from the edited volume. */
+int apply_brushes(vrt_ctx* ctx, int slot, int n_rec, const vrt_brush* rec, vrt_brush_result* result) {
+    if (!ctx || n_rec < 0 || n_rec > VRT_MAX_BRUSHES || (!rec && n_rec > 0)) return VRT_ERR_INVALID;
+    if (!valid_slot(slot) || !ctx->vol[slot].used) return VRT_ERR_SLOT;
+    for (int i = 0; i < n_rec; i++)
+        if (!valid_brush(rec[i])) return VRT_ERR_INVALID;
+    HostVolume& h = ctx->vol[slot];
+    const int N = h.N, C = N - 1, nb = h.nb;
+    if (result) *result = vrt_brush_result{{N, N, N}, {-1, -1, -1}, 0};
+    const float cell = (h.extent * 2.0f) / (float)(N - 1);
+    DBrushList list;
+    memset(&list, 0, sizeof list);
+    list.unit = cell / h.density_scale;
+    int ulo[3] = {N, N, N}, uhi[3] = {-1, -1, -1}; /* union of the records' boxes, xyz */
+    for (int i = 0; i < n_rec; i++) {
+        int lo[3], hi[3];
+        if (!brush_box(rec[i], N, lo, hi)) continue; /* wholly outside the grid */
+        DBrush& b = list.rec[list.n++];
+        b.shape = rec[i].shape;
+        b.op = rec[i].op;
+        memcpy(b.a, rec[i].a, sizeof b.a);
+        memcpy(b.b, rec[i].b, sizeof b.b);
+        b.radius = rec[i].radius;
+        b.k = rec[i].blend * list.unit;
+        b.reach = rec[i].reach;
+        b.material = rec[i].material;
+        for (int a = 0; a < 3; a++) {
+            const int ax = a == 0 ? 0 : (a == 1 ? 2 : 1); /* the grid's axis order {x, z, y} */
+            b.lo[a] = lo[ax];
+            b.hi[a] = hi[ax];
+            ulo[a] = std::min(ulo[a], lo[a]);
+            uhi[a] = std::max(uhi[a], hi[a]);
+        }
+    }
+    if (list.n == 0) return VRT_OK;
+    EditBox foot;
+    for (int a = 0; a < 3; a++) {
+        const int ax = a == 0 ? 0 : (a == 1 ? 2 : 1);
+        foot.lo[a] = ulo[ax];
+        foot.n[a] = uhi[ax] - ulo[ax] + 1;
+    }
+    const bool texel16 = h.format == VRT_FORMAT_TEXEL16;
+    const float scale = texel16 ? h.density_scale * 0.01f : h.density_scale;
+    const size_t n = (size_t)nb * nb * nb;
+    const EditBox all = {{0, 0, 0}, {nb, nb, nb}};
+    for (auto& D : ctx->dev) { /* frames already enqueued render the old volume */
+        HIP_TRY(hipSetDevice(D.ordinal));
+        HIP_TRY(hipDeviceSynchronize());
+    }
+    int box[6];
+    memcpy(box, h.abox, sizeof box);
+    bool density_changed = false;
+    for (size_t di = 0; di < ctx->dev.size(); di++) {
+        DeviceState& D = ctx->dev[di];
+        HIP_TRY(hipSetDevice(D.ordinal));
+        DeviceVolume& v = D.vol[slot];
+        if (!D.d_brush) HIP_TRY(hipMalloc(&D.d_brush, kBrushSlots * sizeof(DBrushSlot)));
+        HIP_TRY(launch_brush_region(list, texel16, v.dense, v.material, N, foot, D.d_brush, D.stream));
+        DBrushSlot part[kBrushSlots];
+        HIP_TRY(hipMemcpyAsync(part, D.d_brush, sizeof part, hipMemcpyDeviceToHost, D.stream));
+        HIP_TRY(hipStreamSynchronize(D.stream));
+        vrt_brush_result got = {{N, N, N}, {-1, -1, -1}, 0}; /* the partial records merged */
+        unsigned long long density_written = 0;
+        for (const DBrushSlot& p : part) {
+            for (int a = 0; a < 3; a++) {
+                got.lo[a] = std::min(got.lo[a], N - (int)p.inv_lo[a]);
+                got.hi[a] = std::max(got.hi[a], (int)p.hi1[a] - 1);
+            }
+            got.written += p.counts & 0xffffffffull;
+            density_written += p.counts >> 32;
+        }
+        if (di == 0 && result) *result = got;
+        if (density_written == 0) continue; /* nothing written, or only material ids: no derived structure changes */
+        density_changed = true;
+        EditBox cells, bricks; /* of the written samples' box, as update_region derives them from its box */
+        for (int a = 0; a < 3; a++) {
+            const int ax = a == 0 ? 0 : (a == 1 ? 2 : 1);
+            const int lo = got.lo[ax], hi = got.hi[ax];
+            cells.lo[a] = std::max(lo - 1, 0);
+            cells.n[a] = std::min(hi, C - 1) - cells.lo[a] + 1;
+            bricks.lo[a] = lo > 0 ? (lo - 1) / kBrickCells : 0;
+            bricks.n[a] = std::min(hi / kBrickCells, nb - 1) - bricks.lo[a] + 1;
+        }
+        HIP_TRY(launch_retile_region(v.dense, v.bricks, texel16 ? v.cells : nullptr, h.format, N, nb, bricks, D.stream));
+        const bool tables = v.skip_valid;
+        if (!v.seeds) HIP_TRY(hipMalloc(&v.seeds, 2 * n));
+        HIP_TRY(launch_seeds_region(v.dense, tables ? v.seeds : nullptr, v.seeds + n, N, nb, scale, h.step_max, v.seeds_valid ? bricks : all,
+                                    D.stream));
+        v.seeds_valid = true;
+        HIP_TRY(launch_seed_distance(v.seeds + n, v.cube_skip, v.cube_skip + n, nb, false, nullptr, D.stream));
+        if (tables) {
+            if (!D.d_box6) HIP_TRY(hipMalloc(&D.d_box6, sizeof box));
+            HIP_TRY(launch_seed_distance(v.seeds, v.skip, v.skip + n, nb, true, D.d_box6, D.stream));
+            int rc = ensure_buffer(D.edit_scratch, D.edit_scratch_cap, nibble_region_scratch_bytes(N, cells));
+            if (rc != VRT_OK) return rc;
+            HIP_TRY(launch_nibble_region(v.dense, v.nib, D.edit_scratch, N, nb, scale, h.step_max, cells, D.stream));
+            HIP_TRY(hipMemcpyAsync(box, D.d_box6, sizeof box, hipMemcpyDeviceToHost, D.stream));
+        }
+        HIP_TRY(hipStreamSynchronize(D.stream));
+    }
+    if (!density_changed) return VRT_OK;
+    memcpy(h.abox, box, sizeof box); /* unchanged without the tables, as upload_volume leaves it */
+    ctx->scene_stale = true;
+    return sync_volume_table(ctx);
+}
+
+/* vrt_volume_download_region: the box through the cached staging buffer of device 0 (gather_region_kernel), then one copy. */
+int download_region(vrt_ctx* ctx, int slot, const int origin[3], const int size[3], vrt_voxel* out) {
+    if (!ctx || !origin || !size || !out) return VRT_ERR_INVALID;
+    if (!valid_slot(slot) || !ctx->vol[slot].used) return VRT_ERR_SLOT;
+    const HostVolume& h = ctx->vol[slot];
+    for (int a = 0; a < 3; a++)
+        if (size[a] < 1 || origin[a] < 0 || (long long)origin[a] + size[a] > h.N) return VRT_ERR_INVALID;
+    const EditBox box = {{origin[0], origin[2], origin[1]}, {size[0], size[2], size[1]}};
+    const size_t bytes = (size_t)size[0] * size[1] * size[2] * sizeof(vrt_voxel);
+    DeviceState& D = ctx->dev[0];
+    HIP_TRY(hipSetDevice(D.ordinal));
+    int rc = ensure_buffer(D.edit_staging, D.edit_staging_cap, bytes);
+    if (rc != VRT_OK) return rc;
+    const DeviceVolume& v = D.vol[slot];
+    HIP_TRY(launch_gather_region(v.dense, v.material, h.format == VRT_FORMAT_TEXEL16, h.N, box, D.edit_staging, D.stream));
+    HIP_TRY(hipMemcpyAsync(out, D.edit_staging, bytes, hipMemcpyDeviceToHost, D.stream));
+    HIP_TRY(hipStreamSynchronize(D.stream));
+    return VRT_OK;
 }
 
 /* A scene's small arrays as the kernels read them: instances (with the directional light's shadow-ray constants), the threaded
@@ -1449,6 +1621,14 @@ int vrt_volume_update_region(vrt_ctx* ctx, int slot, const int origin_xyz[3], co
 
 int vrt_volume_update_voxels(vrt_ctx* ctx, int slot, const int origin_xyz[3], const int size_xyz[3], const vrt_voxel* voxels) {
     return update_region(ctx, slot, origin_xyz, size_xyz, nullptr, nullptr, voxels);
+}
+
+int vrt_volume_apply_brushes(vrt_ctx* ctx, int slot, int n, const vrt_brush* brushes, vrt_brush_result* result_or_null) {
+    return apply_brushes(ctx, slot, n, brushes, result_or_null);
+}
+
+int vrt_volume_download_region(vrt_ctx* ctx, int slot, const int origin_xyz[3], const int size_xyz[3], vrt_voxel* out) {
+    return download_region(ctx, slot, origin_xyz, size_xyz, out);
 }
 
 int vrt_debug_volume_bytes(vrt_ctx* ctx, int slot, int device_index, int which, void* out, size_t capacity, size_t* size_out) {

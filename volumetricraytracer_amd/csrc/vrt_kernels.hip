@@ -2540,6 +2540,124 @@ __global__ void scatter_region_kernel(const void* __restrict__ staging, float* _
     }
 }
 
+/* ---- CSG brushes (vrt_volume_apply_brushes) ----
+ * The arithmetic is the contract written out in vrt.h, fp32 and parenthesised as there (the build keeps -ffp-contract=off). */
+__device__ __forceinline__ float brush_dot(float ux, float uy, float uz, float vx, float vy, float vz) { return (ux * vx + uy * vy) + uz * vz; }
+__device__ __forceinline__ float brush_len(float ux, float uy, float uz) { return sqrtf(brush_dot(ux, uy, uz, ux, uy, uz)); }
+/* s: the brush's distance at sample p, in cells */
+__device__ __forceinline__ float brush_distance(const DBrush& B, float px, float py, float pz) {
+    const float ax = px - B.a[0], ay = py - B.a[1], az = pz - B.a[2]; /* p - a */
+    if (B.shape == VRT_BRUSH_SPHERE) return brush_len(ax, ay, az) - B.radius;
+    if (B.shape == VRT_BRUSH_CAPSULE) {
+        const float bx = B.b[0] - B.a[0], by = B.b[1] - B.a[1], bz = B.b[2] - B.a[2];
+        const float h = fminf(fmaxf(brush_dot(ax, ay, az, bx, by, bz) / brush_dot(bx, by, bz, bx, by, bz), 0.0f), 1.0f);
+        return brush_len(ax - bx * h, ay - by * h, az - bz * h) - B.radius;
+    }
+    const float qx = (fabsf(ax) - B.b[0]) + B.radius, qy = (fabsf(ay) - B.b[1]) + B.radius, qz = (fabsf(az) - B.b[2]) + B.radius;
+    return (brush_len(fmaxf(qx, 0.0f), fmaxf(qy, 0.0f), fmaxf(qz, 0.0f)) + fminf(fmaxf(qx, fmaxf(qy, qz)), 0.0f)) - B.radius;
+}
+
+/* One lane per sample of the records' union box, y fastest like the dense grid.  Every lane of a wave walks the same record list (the
+ * records sit in the kernel-argument block: wave-uniform loads); a sample outside a record's own box skips its distance.  A sample
+ * no record writes keeps its stored bits — a TEXEL16 value does not survive decode + encode.  The written samples' counts and box are
+ * reduced across the wave first; a wave that wrote then reports with one atomic per word to one of kBrushSlots partial records. */
+template <bool TEXEL16>
+__global__ __launch_bounds__(256) void brush_region_kernel(DBrushList L, float* __restrict__ dense, uint8_t* __restrict__ material, int N,
+                                                           EditBox b, DBrushSlot* __restrict__ slots) {
+    const size_t count = box_count(b);
+    size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    const size_t stride = (size_t)gridDim.x * blockDim.x;
+    unsigned inv_lo_x = 0u, inv_lo_y = 0u, inv_lo_z = 0u, hi1_x = 0u, hi1_y = 0u, hi1_z = 0u; /* N - lowest, 1 + highest: 0 = none */
+    unsigned n_written = 0u, n_density = 0u;
+    for (; i < count; i += stride) {
+        int x, z, y;
+        box_coords(b, i, x, z, y);
+        const size_t g = ((size_t)x * N + z) * N + y;
+        float stored = dense[g];
+        float d = TEXEL16 ? stored * 0.01f : stored;
+        unsigned mat = material[g];
+        bool wrote_d = false, wrote_m = false;
+        const float px = (float)x, py = (float)y, pz = (float)z;
+        for (int r = 0; r < L.n; r++) {
+            const DBrush& B = L.rec[r];
+            if (x < B.lo[0] || x > B.hi[0] || z < B.lo[1] || z > B.hi[1] || y < B.lo[2] || y > B.hi[2]) continue;
+            const float s = brush_distance(B, px, py, pz);
+            if (B.op == VRT_BRUSH_PAINT) {
+                if (s <= 0.0f && d <= 0.0f && mat != (unsigned)B.material) {
+                    mat = (unsigned)B.material;
+                    wrote_m = true;
+                }
+                continue;
+            }
+            if (!(s < B.reach)) continue;
+            const float v = s * L.unit, k = B.k;
+            float m;
+            bool write;
+            if (B.op == VRT_BRUSH_ADD) {
+                m = fminf(d, v);
+                if (k > 0.0f) {
+                    const float gk = fmaxf(k - fabsf(d - v), 0.0f) / k;
+                    m = m - ((gk * gk) * k) * 0.25f;
+                }
+                write = m < d;
+            } else {
+                const float c = -v;
+                m = fmaxf(d, c);
+                if (k > 0.0f) {
+                    const float gk = fmaxf(k - fabsf(d - c), 0.0f) / k;
+                    m = m + ((gk * gk) * k) * 0.25f;
+                }
+                write = m > d;
+            }
+            if (write) {
+                stored = TEXEL16 ? texel16_value(m) : m;
+                d = TEXEL16 ? stored * 0.01f : stored; /* the next record sees the stored value */
+                wrote_d = true;
+                if (B.material >= 0) {
+                    mat = m <= 0.0f ? (unsigned)B.material : 0u;
+                    wrote_m = true;
+                }
+            }
+        }
+        if (wrote_d) dense[g] = stored;
+        if (wrote_m) material[g] = (uint8_t)mat;
+        if (wrote_d || wrote_m) {
+            n_written++;
+            n_density += wrote_d ? 1u : 0u;
+            inv_lo_x = max(inv_lo_x, (unsigned)(N - x)), inv_lo_y = max(inv_lo_y, (unsigned)(N - y)), inv_lo_z = max(inv_lo_z, (unsigned)(N - z));
+            hi1_x = max(hi1_x, (unsigned)(x + 1)), hi1_y = max(hi1_y, (unsigned)(y + 1)), hi1_z = max(hi1_z, (unsigned)(z + 1));
+        }
+    }
+    for (int o = 32; o > 0; o >>= 1) {
+        n_written += __shfl_xor(n_written, o);
+        n_density += __shfl_xor(n_density, o);
+        inv_lo_x = max(inv_lo_x, __shfl_xor(inv_lo_x, o)), inv_lo_y = max(inv_lo_y, __shfl_xor(inv_lo_y, o));
+        inv_lo_z = max(inv_lo_z, __shfl_xor(inv_lo_z, o));
+        hi1_x = max(hi1_x, __shfl_xor(hi1_x, o)), hi1_y = max(hi1_y, __shfl_xor(hi1_y, o)), hi1_z = max(hi1_z, __shfl_xor(hi1_z, o));
+    }
+    if ((threadIdx.x & 63u) == 0u && n_written != 0u) {
+        DBrushSlot* slot = slots + ((blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6)) & (unsigned)(kBrushSlots - 1));
+        atomicAdd(&slot->counts, ((unsigned long long)n_density << 32) | (unsigned long long)n_written);
+        atomicMax(&slot->inv_lo[0], inv_lo_x), atomicMax(&slot->inv_lo[1], inv_lo_y), atomicMax(&slot->inv_lo[2], inv_lo_z);
+        atomicMax(&slot->hi1[0], hi1_x), atomicMax(&slot->hi1[1], hi1_y), atomicMax(&slot->hi1[2], hi1_z);
+    }
+}
+
+/* vrt_volume_download_region: the box's samples as VVoxel records, decoded like vrt_volume_download. */
+__global__ void gather_region_kernel(const float* __restrict__ dense, const uint8_t* __restrict__ material, uint2* __restrict__ out, int N,
+                                     EditBox b, int texel16) {
+    const size_t count = box_count(b);
+    size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    const size_t stride = (size_t)gridDim.x * blockDim.x;
+    for (; i < count; i += stride) {
+        int x, z, y;
+        box_coords(b, i, x, z, y);
+        const size_t g = ((size_t)x * N + z) * N + y;
+        const float d = dense[g];
+        out[i] = make_uint2((unsigned)material[g], __float_as_uint(texel16 ? d * 0.01f : d));
+    }
+}
+
 /* One workgroup per brick of a brick box. */
 __device__ __forceinline__ int region_brick(const EditBox& b, int nb, int& bx, int& by, int& bz) {
     box_coords(b, blockIdx.x, bx, bz, by);
@@ -3037,6 +3155,28 @@ hipError_t launch_scatter_region(const void* staging, bool voxels, bool has_mate
     else
         hipLaunchKernelGGL(scatter_region_kernel<false>, dim3(grid), dim3(256), 0, stream, staging, dense, material, N, box, (int)texel16,
                            (int)has_material);
+    return hipGetLastError();
+}
+
+hipError_t launch_brush_region(const DBrushList& list, bool texel16, float* dense, uint8_t* material, int N, const EditBox& box,
+                               DBrushSlot* slots, hipStream_t stream) {
+    static_assert(sizeof(DBrushSlot) == 128 && (kBrushSlots & (kBrushSlots - 1)) == 0, "one line per slot, a power of two of them");
+    hipError_t e = hipMemsetAsync(slots, 0, kBrushSlots * sizeof(DBrushSlot), stream);
+    if (e != hipSuccess) return e;
+    const size_t count = (size_t)box.n[0] * box.n[1] * box.n[2];
+    if (list.n == 0 || count == 0) return hipSuccess;
+    const unsigned grid = stride_grid(count);
+    if (texel16)
+        hipLaunchKernelGGL(brush_region_kernel<true>, dim3(grid), dim3(256), 0, stream, list, dense, material, N, box, slots);
+    else
+        hipLaunchKernelGGL(brush_region_kernel<false>, dim3(grid), dim3(256), 0, stream, list, dense, material, N, box, slots);
+    return hipGetLastError();
+}
+
+hipError_t launch_gather_region(const float* dense, const uint8_t* material, bool texel16, int N, const EditBox& box, void* voxels_out,
+                                hipStream_t stream) {
+    const unsigned grid = stride_grid((size_t)box.n[0] * box.n[1] * box.n[2]);
+    hipLaunchKernelGGL(gather_region_kernel, dim3(grid), dim3(256), 0, stream, dense, material, static_cast<uint2*>(voxels_out), N, box, (int)texel16);
     return hipGetLastError();
 }
 

@@ -74,4 +74,36 @@ size_t nibble_region_scratch_bytes(int N, const EditBox& changed);
 hipError_t launch_nibble_region(const float* dense, unsigned* nib, void* scratch, int N, int nb, float density_scale, float step_max,
                                 const EditBox& changed, hipStream_t stream);
 
+/* vrt_volume_apply_brushes: one record as the kernel reads it — the caller's vrt_brush with the blend width already in density
+   units (k = blend * unit) and the sample box outside which the record writes nothing, in the grid's own axis order {x, z, y}. */
+struct DBrush {
+    int32_t shape, op;
+    float a[3], b[3];
+    float radius, k, reach;
+    int32_t material;
+    int32_t lo[3], hi[3]; /* inclusive, clipped to the grid */
+};
+struct DBrushList {
+    int32_t n;
+    float unit; /* density units per cell: cell / density_scale */
+    DBrush rec[VRT_MAX_BRUSHES];
+};
+/* What a brush launch reports (device memory, zeroed by launch_brush_region): the written samples' box and counts, kept in
+   kBrushSlots partial records that the host merges — thousands of waves report at once, and atomics on one word take their turns
+   (a single record made the launch 25 times longer than the scatter of the same box).  Every field grows from 0 = nothing written. */
+constexpr int kBrushSlots = 64;
+struct DBrushSlot {
+    uint32_t inv_lo[3];        /* N - lowest written x, y, z */
+    uint32_t hi1[3];           /* 1 + highest written x, y, z */
+    unsigned long long counts; /* samples written (low half; N^3 < 2^32) and, of those, samples whose density was written (high half;
+                                  0: only material ids changed, no derived structure to rebuild) */
+    uint32_t pad_[24];         /* one 128-byte line per slot */
+};
+/* The records of `list`, in order, over the samples of `box` (the union of the records' boxes), in place. */
+hipError_t launch_brush_region(const DBrushList& list, bool texel16, float* dense, uint8_t* material, int N, const EditBox& box,
+                               DBrushSlot* slots, hipStream_t stream);
+/* vrt_volume_download_region: the samples of `box` as VVoxel records (x slowest, then z, then y), a TEXEL16 field decoded (* 0.01f). */
+hipError_t launch_gather_region(const float* dense, const uint8_t* material, bool texel16, int N, const EditBox& box, void* voxels_out,
+                                hipStream_t stream);
+
 }  // namespace vrt

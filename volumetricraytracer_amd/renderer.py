@@ -41,6 +41,31 @@ def hits_to_dict(hits: np.ndarray) -> dict:
             "voxel": hits["voxel"].copy(), "material": hits["material"].copy(), "steps": hits["steps"].copy()}
 
 
+def _brush(shape, op, a, b, radius, blend, reach, material) -> _abi.vrt_brush:
+    r = _abi.vrt_brush()
+    r.shape, r.op = int(shape), int(op)
+    for i in range(3):
+        r.a[i], r.b[i] = float(a[i]), float(b[i])
+    r.radius, r.blend, r.reach, r.material = float(radius), float(blend), float(reach), int(material)
+    return r
+
+
+def sphere_brush(op: int, center, radius: float, blend: float = 0.0, reach: float = 2.0, material: int = -1) -> _abi.vrt_brush:
+    """A vrt_brush record: a sphere at `center` (grid coordinates xyz, fractions allowed), lengths in cells (vrt.h)."""
+    return _brush(_abi.BRUSH_SPHERE, op, center, (0.0, 0.0, 0.0), radius, blend, reach, material)
+
+
+def box_brush(op: int, center, half_sizes, rounding: float = 0.0, blend: float = 0.0, reach: float = 2.0,
+              material: int = -1) -> _abi.vrt_brush:
+    """A vrt_brush record: an axis-aligned box of `half_sizes` (xyz, cells) at `center`, its corners rounded by `rounding`."""
+    return _brush(_abi.BRUSH_BOX, op, center, half_sizes, rounding, blend, reach, material)
+
+
+def capsule_brush(op: int, end_a, end_b, radius: float, blend: float = 0.0, reach: float = 2.0, material: int = -1) -> _abi.vrt_brush:
+    """A vrt_brush record: the capsule of `radius` around the segment end_a..end_b (grid coordinates xyz)."""
+    return _brush(_abi.BRUSH_CAPSULE, op, end_a, end_b, radius, blend, reach, material)
+
+
 class VHipRenderer:
     def __init__(self, devices: Sequence[int] = (0,)):
         self._lib = _abi.load()
@@ -196,6 +221,40 @@ class VHipRenderer:
         _abi.check(self._lib.vrt_volume_update_region(self._ctx, slot, origin, size, d.ctypes.data_as(C.c_void_p),
                                                       m.ctypes.data_as(C.c_void_p)), "vrt_volume_update_region")
         vol.dirty_box = None
+
+    def apply_brushes(self, slot: int, vol: VVoxelVolume, brushes) -> dict:
+        """vrt_volume_apply_brushes: the CSG brush records (sphere_brush / box_brush / capsule_brush, at most _abi.MAX_BRUSHES),
+        in order, on the volume resident in `slot`, evaluated on the device.  The written box of the host mirror `vol` is then
+        read back (download_region) — without touching dirty / dirty_box: the device is already current.  On a TEXEL16 volume the
+        mirror receives decoded values (q * 0.01), which quantise again should the volume be uploaded whole later.
+        Returns {"written", "lo", "hi"} (xyz, inclusive; lo > hi when nothing was written)."""
+        self._require()
+        brushes = list(brushes)
+        arr = (_abi.vrt_brush * max(1, len(brushes)))(*brushes)
+        res = _abi.vrt_brush_result()
+        _abi.check(self._lib.vrt_volume_apply_brushes(self._ctx, slot, len(brushes), arr, C.byref(res)), "vrt_volume_apply_brushes")
+        lo, hi = tuple(res.lo), tuple(res.hi)
+        if res.written and vol is not None:
+            d, m = self.download_region(slot, lo, hi)
+            (x0, y0, z0), (x1, y1, z1) = lo, hi
+            for name in ("density", "material_id"):
+                if not getattr(vol, name).flags.writeable:
+                    setattr(vol, name, np.array(getattr(vol, name)))
+            vol.density[x0:x1 + 1, z0:z1 + 1, y0:y1 + 1] = d
+            vol.material_id[x0:x1 + 1, z0:z1 + 1, y0:y1 + 1] = m
+        return {"written": int(res.written), "lo": lo, "hi": hi}
+
+    def download_region(self, slot: int, lo, hi):
+        """vrt_volume_download_region: the voxels lo..hi (inclusive xyz corners) of the slot on device 0 as (density float32,
+        material uint8), both indexed [x, z, y] like VVoxelVolume.density; a TEXEL16 slot decodes like download_volume."""
+        self._require()
+        (x0, y0, z0), (x1, y1, z1) = lo, hi
+        sx, sy, sz = x1 - x0 + 1, y1 - y0 + 1, z1 - z0 + 1
+        rec = np.zeros(max(0, sx) * max(0, sy) * max(0, sz), dtype=np.dtype([("material", "u1"), ("pad", "u1", 3), ("density", "<f4")]))
+        _abi.check(self._lib.vrt_volume_download_region(self._ctx, slot, (C.c_int * 3)(x0, y0, z0), (C.c_int * 3)(sx, sy, sz),
+                                                        rec.ctypes.data_as(C.c_void_p)), "vrt_volume_download_region")
+        shape = (sx, sz, sy)
+        return np.ascontiguousarray(rec["density"].reshape(shape)), np.ascontiguousarray(rec["material"].reshape(shape))
 
     def _bind_material(self, slot: int, vol: VVoxelVolume) -> None:
         """The slot's material scalars and texture bindings as the volume's VMaterial holds them NOW (images uploaded on first
