@@ -90,7 +90,7 @@ def main():
             times = {k: [] for k in variants}
             for block in range(args.blocks):
                 t = {k: [] for k in variants}
-                for rep in range(args.reps + (1 if block == 0 else 0)):  # round 0 builds the seed grids and grows the buffers
+                for rep in range(args.reps + (1 if block == 0 else 0)):  # round 0 grows the buffers
                     for k, fn in variants.items():
                         t[k].append(timed(fn))
                         if isinstance(fn, Brushes):

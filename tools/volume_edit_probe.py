@@ -43,7 +43,7 @@ def main():
                 m = np.ascontiguousarray(vol.material_id[o[0]:o[0] + b, o[2]:o[2] + b, o[1]:o[1] + b])
                 oo, ss = (C.c_int * 3)(*o), (C.c_int * 3)(b, b, b)
                 t = []
-                for _ in range(args.reps + 1):  # the first call builds the seed grids and grows the staging / scratch buffers
+                for _ in range(args.reps + 1):  # the first call grows the staging / scratch buffers
                     t0 = time.perf_counter()
                     _abi.check(r._lib.vrt_volume_update_region(r._ctx, 0, oo, ss, d.ctypes.data_as(C.c_void_p), m.ctypes.data_as(C.c_void_p)),
                                "vrt_volume_update_region")

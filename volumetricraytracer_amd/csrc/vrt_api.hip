@@ -123,11 +123,13 @@ struct DeviceVolume {
     unsigned* nib = nullptr;      /* nb^3 words: the empty-space table, level 2 (sub-block nibbles) */
     bool skip_valid = false;      /* tables built for the current metric (only when step_max > 0) */
     uint8_t* cube_skip = nullptr; /* 2 x nb^3 bytes: the Cube modes' distance-to-solid table and its build scratch */
-    /* vrt_volume_update_region: 2 x nb^3 bytes, the seeds (0 / 255) of the level-1 table and of the Cube table — the tables keep
-       distances, from which the seeds cannot be recovered.  Built by the first update after an upload or a metric change. */
+    /* 2 x nb^3 bytes, the seeds (0 / 255) of the level-1 table (valid while skip_valid) and of the Cube table (always valid) — the tables
+       keep distances, from which an edit could not recover the seeds. */
     uint8_t* seeds = nullptr;
-    bool seeds_valid = false;
 };
+
+/* The grid's axis order is {x, z, y}: grid axis a is xyz axis grid_axis(a), and the other way round. */
+constexpr int grid_axis(int a) { return a == 0 ? 0 : (a == 1 ? 2 : 1); }
 
 /* The small read-only arrays a launch dereferences, in ONE device allocation so that a frame in flight can keep its
    own snapshot while the application already edits the scene for the next frame. */
@@ -479,42 +481,13 @@ void fill_dvolume(const vrt_ctx* ctx, const DeviceState& D, const HostVolume& h,
     out.skip = (h.step_max > 0.0f && d.skip_valid) ? d.skip : nullptr;
     out.nib = out.skip ? d.nib : nullptr;
     for (int a = 0; a < 3; a++) { /* brick box {x, z, y} -> object-space box per axis x, y, z */
-        const int ax = a == 0 ? 0 : (a == 1 ? 2 : 1);
+        const int ax = grid_axis(a);
         const int lo_cell = h.abox[ax] * kBrickCells;
         const int hi_cell = std::min((h.abox[3 + ax] + 1) * kBrickCells, h.N - 1);
         out.abox_lo[a] = (float)lo_cell * cell - h.extent;
         out.abox_hi[a] = (float)hi_cell * cell - h.extent;
     }
     out.cube_skip = d.cube_skip;
-}
-
-/* (Re)builds the two-level empty-space table of a slot on every device for its current metric. */
-int rebuild_skip(vrt_ctx* ctx, int slot) {
-    HostVolume& h = ctx->vol[slot];
-    const float scale = h.format == VRT_FORMAT_TEXEL16 ? h.density_scale * 0.01f : h.density_scale;
-    for (auto& D : ctx->dev) {
-        DeviceVolume& v = D.vol[slot];
-        v.skip_valid = false;
-        if (!h.used || !(h.step_max > 0.0f) || !v.dense) continue;
-        HIP_TRY(hipSetDevice(D.ordinal));
-        const size_t n = (size_t)h.nb * h.nb * h.nb;
-        if (!v.skip) HIP_TRY(hipMalloc(&v.skip, 2 * n));
-        if (!v.nib) HIP_TRY(hipMalloc(&v.nib, n * sizeof(unsigned)));
-        void* scratch = nullptr;
-        HIP_TRY(hipMalloc(&scratch, nibble_scratch_bytes(h.N)));
-        int* d_box = static_cast<int*>(scratch); /* the first 24 bytes of the scratch: read back before the nibble pass reuses them */
-        int box[6] = {h.nb, h.nb, h.nb, -1, -1, -1};
-        hipError_t e = launch_skip_table(v.dense, v.skip, v.skip + n, d_box, h.N, h.nb, scale, h.step_max, D.stream);
-        if (e == hipSuccess) e = hipMemcpyAsync(box, d_box, sizeof box, hipMemcpyDeviceToHost, D.stream);
-        if (e == hipSuccess) e = hipStreamSynchronize(D.stream);
-        if (e == hipSuccess) e = launch_nibble_table(v.dense, v.nib, scratch, h.N, h.nb, scale, h.step_max, D.stream);
-        if (e == hipSuccess) e = hipStreamSynchronize(D.stream);
-        (void)hipFree(scratch);
-        HIP_TRY(e);
-        memcpy(ctx->vol[slot].abox, box, sizeof box);
-        v.skip_valid = true;
-    }
-    return VRT_OK;
 }
 
 int sync_volume_table(vrt_ctx* ctx) {
@@ -562,16 +535,7 @@ int init_device(DeviceState& D, int ordinal) {
 
 void destroy_device(DeviceState& D) {
     if (hipSetDevice(D.ordinal) != hipSuccess) return;
-    for (int i = 0; i < VRT_MAX_VOLUMES; i++) {
-        if (D.vol[i].dense) (void)hipFree(D.vol[i].dense);
-        if (D.vol[i].bricks) (void)hipFree(D.vol[i].bricks);
-        if (D.vol[i].cells) (void)hipFree(D.vol[i].cells);
-        if (D.vol[i].material) (void)hipFree(D.vol[i].material);
-        if (D.vol[i].skip) (void)hipFree(D.vol[i].skip);
-        if (D.vol[i].nib) (void)hipFree(D.vol[i].nib);
-        if (D.vol[i].cube_skip) (void)hipFree(D.vol[i].cube_skip);
-        if (D.vol[i].seeds) (void)hipFree(D.vol[i].seeds);
-    }
+    for (int i = 0; i < VRT_MAX_VOLUMES; i++) (void)free_device_volume(D, i);
     if (D.edit_staging) (void)hipFree(D.edit_staging);
     if (D.edit_scratch) (void)hipFree(D.edit_scratch);
     if (D.d_box6) (void)hipFree(D.d_box6);
@@ -620,6 +584,97 @@ void destroy_device(DeviceState& D) {
             (void)hipEventDestroy(D.ev1[i]);
         }
     if (D.stream) (void)hipStreamDestroy(D.stream);
+}
+
+/* Grows a per-device cache buffer to at least `bytes` (its contents are not kept). */
+int ensure_buffer(void*& p, size_t& cap, size_t bytes) {
+    if (cap >= bytes) return VRT_OK;
+    if (p) HIP_TRY(hipFree(p));
+    p = nullptr;
+    cap = 0;
+    HIP_TRY(hipMalloc(&p, bytes));
+    cap = bytes;
+    return VRT_OK;
+}
+
+/* The {x, z, y} boxes an edit of the samples lo..hi (xyz, inclusive) touches: the samples themselves; the cells with a corner among
+ * them; and the bricks whose 5^3 (clamped) samples meet them, [ceil((lo - 4) / 4), floor(hi / 4)] — the same range holds the cell records
+ * of cells lo-1..hi and the Cube seeds of samples lo..hi.  All of the grid gives all of its cells and bricks. */
+struct DerivedBoxes {
+    EditBox samples, cells, bricks;
+};
+DerivedBoxes derived_boxes(const HostVolume& h, const int lo_xyz[3], const int hi_xyz[3]) {
+    DerivedBoxes b;
+    for (int a = 0; a < 3; a++) {
+        const int lo = lo_xyz[grid_axis(a)], hi = hi_xyz[grid_axis(a)];
+        b.samples.lo[a] = lo;
+        b.samples.n[a] = hi - lo + 1;
+        b.cells.lo[a] = std::max(lo - 1, 0);
+        b.cells.n[a] = std::min(hi, h.N - 2) - b.cells.lo[a] + 1;
+        b.bricks.lo[a] = lo > 0 ? (lo - 1) / kBrickCells : 0;
+        b.bricks.n[a] = std::min(hi / kBrickCells, h.nb - 1) - b.bricks.lo[a] + 1;
+    }
+    return b;
+}
+
+/* Every structure a slot derives from its dense grid, on one device and in one order, only where the written samples can change it
+ * (DESIGN §2): bricks and cell records of the bricks whose samples meet the box, the seeds of those bricks, both brick-distance tables
+ * from their seeds (three passes each), and the level-2 table around the cells whose flags may change.  written_or_null == nullptr: the
+ * whole grid for the slot's current metric (an upload; metric_only: a metric change, which bricks, cell records and the Cube table do not
+ * depend on), which also decides whether the slot has the two-level empty-space table.  box6: the near bricks' box, written when it has. */
+int rebuild_derived(vrt_ctx* ctx, DeviceState& D, int slot, const DerivedBoxes* written_or_null, bool metric_only, int box6[6]) {
+    const HostVolume& h = ctx->vol[slot];
+    DeviceVolume& v = D.vol[slot];
+    const int N = h.N, nb = h.nb;
+    const size_t n = (size_t)nb * nb * nb;
+    const bool texel16 = h.format == VRT_FORMAT_TEXEL16;
+    const float scale = texel16 ? h.density_scale * 0.01f : h.density_scale;
+    const int zero[3] = {0, 0, 0}, last[3] = {N - 1, N - 1, N - 1};
+    const DerivedBoxes B = written_or_null ? *written_or_null : derived_boxes(h, zero, last);
+    HIP_TRY(hipSetDevice(D.ordinal));
+    if (!written_or_null) {
+        v.skip_valid = h.step_max > 0.0f; /* otherwise no tables: buffers of an earlier metric are kept, and read as 0 bytes */
+        if (v.skip_valid && !v.skip) HIP_TRY(hipMalloc(&v.skip, 2 * n));
+        if (v.skip_valid && !v.nib) HIP_TRY(hipMalloc(&v.nib, n * sizeof(unsigned)));
+    }
+    const bool tables = v.skip_valid;
+    if (!metric_only) HIP_TRY(launch_retile_region(v.dense, v.bricks, texel16 ? v.cells : nullptr, h.format, N, nb, B.bricks, D.stream));
+    HIP_TRY(launch_seeds_region(v.dense, tables ? v.seeds : nullptr, metric_only ? nullptr : v.seeds + n, N, nb, scale, h.step_max, B.bricks,
+                                D.stream));
+    if (!metric_only) HIP_TRY(launch_seed_distance(v.seeds + n, v.cube_skip, v.cube_skip + n, nb, false, nullptr, D.stream));
+    if (!tables) {
+        HIP_TRY(hipStreamSynchronize(D.stream));
+        return VRT_OK;
+    }
+    if (!D.d_box6) HIP_TRY(hipMalloc(&D.d_box6, 6 * sizeof(int)));
+    HIP_TRY(launch_seed_distance(v.seeds, v.skip, v.skip + n, nb, true, D.d_box6, D.stream));
+    /* level-2 scratch: an edit's is cached; the whole grid's (5 bytes per cell: 671 MB at resolution 9) is freed after the build */
+    const size_t scratch_bytes = nibble_region_scratch_bytes(N, B.cells);
+    void* scratch = nullptr;
+    if (written_or_null) {
+        int rc = ensure_buffer(D.edit_scratch, D.edit_scratch_cap, scratch_bytes);
+        if (rc != VRT_OK) return rc;
+        scratch = D.edit_scratch;
+    } else {
+        HIP_TRY(hipMalloc(&scratch, scratch_bytes));
+    }
+    hipError_t e = launch_nibble_region(v.dense, v.nib, scratch, N, nb, scale, h.step_max, B.cells, D.stream);
+    if (e == hipSuccess) e = hipMemcpyAsync(box6, D.d_box6, 6 * sizeof(int), hipMemcpyDeviceToHost, D.stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(D.stream);
+    if (!written_or_null) (void)hipFree(scratch);
+    HIP_TRY(e);
+    return VRT_OK;
+}
+
+/* rebuild_derived over the whole grid of a slot on every device: after an upload, or (metric_only) a metric change. */
+int rebuild_slot(vrt_ctx* ctx, int slot, bool metric_only) {
+    HostVolume& h = ctx->vol[slot];
+    for (auto& D : ctx->dev) {
+        if (!D.vol[slot].dense) continue;
+        int rc = rebuild_derived(ctx, D, slot, nullptr, metric_only, h.abox); /* abox: unchanged without the tables */
+        if (rc != VRT_OK) return rc;
+    }
+    return VRT_OK;
 }
 
 bool valid_slot(int slot) { return slot >= 0 && slot < VRT_MAX_VOLUMES; }
@@ -692,15 +747,10 @@ int upload_volume(vrt_ctx* ctx, int slot, uint8_t resolution, float extent, cons
         /* VRT_FORMAT_TEXEL16: quantise like VDXVoxelVolume::EncodeVoxel; the dense grid then holds the integer field too,
            so that every data path and every table sees the same values */
         if (format == VRT_FORMAT_TEXEL16 && !texels) HIP_TRY(launch_quantize_field(v.dense, count, D.stream));
-        HIP_TRY(launch_retile(v.dense, v.bricks, format, N, nb, D.stream));
-        if (format == VRT_FORMAT_TEXEL16) {
-            HIP_TRY(hipMalloc(&v.cells, (size_t)nb * nb * nb * 64 * 16));
-            HIP_TRY(launch_retile_cells16(v.dense, v.cells, N, nb, D.stream));
-        }
         const size_t nbricks = (size_t)nb * nb * nb;
+        if (format == VRT_FORMAT_TEXEL16) HIP_TRY(hipMalloc(&v.cells, nbricks * 64 * 16));
         HIP_TRY(hipMalloc(&v.cube_skip, 2 * nbricks));
-        HIP_TRY(launch_cube_table(v.dense, v.cube_skip, v.cube_skip + nbricks, N, nb, D.stream));
-        HIP_TRY(hipStreamSynchronize(D.stream));
+        HIP_TRY(hipMalloc(&v.seeds, 2 * nbricks));
     }
     HostVolume& h = ctx->vol[slot];
     const bool was_used = h.used;
@@ -718,59 +768,30 @@ int upload_volume(vrt_ctx* ctx, int slot, uint8_t resolution, float extent, cons
         h.tex_scale[0] = h.tex_scale[1] = 100.f;
     }
     ctx->scene_stale = true;
-    int rc = rebuild_skip(ctx, slot);
+    int rc = rebuild_slot(ctx, slot, false);
     if (rc != VRT_OK) return rc;
     return sync_volume_table(ctx);
 }
 
-/* Grows a per-device cache buffer to at least `bytes` (its contents are not kept). */
-int ensure_buffer(void*& p, size_t& cap, size_t bytes) {
-    if (cap >= bytes) return VRT_OK;
-    if (p) HIP_TRY(hipFree(p));
-    p = nullptr;
-    cap = 0;
-    HIP_TRY(hipMalloc(&p, bytes));
-    cap = bytes;
-    return VRT_OK;
-}
-
-/* vrt_volume_update_region / _update_voxels: the box's samples in place on every device, then every structure the full upload derives
- * from them, only where the box can change it: bricks and cell records of the bricks whose samples meet the box, the seeds
- * of the bricks it touches, both brick-distance tables from their seeds (three passes each), and the level-2 table around the cells
- * whose flags may change (launch_nibble_region).  Afterwards every buffer equals what upload_volume builds from the edited volume. */
+/* vrt_volume_update_region / _update_voxels: the box's samples in place on every device, then what the slot derives from them, where
+ * the box can change it (rebuild_derived).  Afterwards every buffer equals what upload_volume builds from the edited volume. */
 int update_region(vrt_ctx* ctx, int slot, const int origin[3], const int size[3], const float* density, const uint8_t* material,
                   const vrt_voxel* voxels) {
     if (!ctx || !origin || !size || (!density && !voxels)) return VRT_ERR_INVALID;
     if (!valid_slot(slot) || !ctx->vol[slot].used) return VRT_ERR_SLOT;
     HostVolume& h = ctx->vol[slot];
-    const int N = h.N, C = N - 1, nb = h.nb;
+    const int N = h.N;
     for (int a = 0; a < 3; a++)
         if (size[a] < 1 || origin[a] < 0 || (long long)origin[a] + size[a] > N) return VRT_ERR_INVALID;
-    EditBox samples, cells, bricks; /* in the grid's axis order {x, z, y} */
-    for (int a = 0; a < 3; a++) {
-        const int ax = a == 0 ? 0 : (a == 1 ? 2 : 1);
-        const int lo = origin[ax], hi = origin[ax] + size[ax] - 1;
-        samples.lo[a] = lo;
-        samples.n[a] = size[ax];
-        cells.lo[a] = std::max(lo - 1, 0); /* cells with a corner in the box */
-        cells.n[a] = std::min(hi, C - 1) - cells.lo[a] + 1;
-        /* bricks whose 5^3 (clamped) samples meet the box, [ceil((lo - 4) / 4), floor(hi / 4)]: the same range holds the cell records of
-           cells lo-1..hi and the Cube seeds of samples lo..hi */
-        bricks.lo[a] = lo > 0 ? (lo - 1) / kBrickCells : 0;
-        bricks.n[a] = std::min(hi / kBrickCells, nb - 1) - bricks.lo[a] + 1;
-    }
+    const int last[3] = {origin[0] + size[0] - 1, origin[1] + size[1] - 1, origin[2] + size[2] - 1};
+    const DerivedBoxes written = derived_boxes(h, origin, last);
     const size_t count = (size_t)size[0] * size[1] * size[2];
     const size_t staged = voxels ? count * sizeof(vrt_voxel) : count * (sizeof(float) + (material ? 1 : 0));
     const bool texel16 = h.format == VRT_FORMAT_TEXEL16;
-    const float scale = texel16 ? h.density_scale * 0.01f : h.density_scale;
-    const size_t n = (size_t)nb * nb * nb;
-    const EditBox all = {{0, 0, 0}, {nb, nb, nb}};
     for (auto& D : ctx->dev) { /* frames already enqueued render the old volume */
         HIP_TRY(hipSetDevice(D.ordinal));
         HIP_TRY(hipDeviceSynchronize());
     }
-    int box[6];
-    memcpy(box, h.abox, sizeof box);
     for (auto& D : ctx->dev) {
         HIP_TRY(hipSetDevice(D.ordinal));
         DeviceVolume& v = D.vol[slot];
@@ -783,25 +804,11 @@ int update_region(vrt_ctx* ctx, int slot, const int origin[3], const int size[3]
             if (material)
                 HIP_TRY(hipMemcpyAsync(static_cast<char*>(D.edit_staging) + count * sizeof(float), material, count, hipMemcpyHostToDevice, D.stream));
         }
-        HIP_TRY(launch_scatter_region(D.edit_staging, voxels != nullptr, material != nullptr, texel16, v.dense, v.material, N, samples, D.stream));
-        HIP_TRY(launch_retile_region(v.dense, v.bricks, texel16 ? v.cells : nullptr, h.format, N, nb, bricks, D.stream));
-        const bool tables = v.skip_valid; /* the two-level empty-space table is live (step_max > 0) */
-        if (!v.seeds) HIP_TRY(hipMalloc(&v.seeds, 2 * n));
-        HIP_TRY(launch_seeds_region(v.dense, tables ? v.seeds : nullptr, v.seeds + n, N, nb, scale, h.step_max, v.seeds_valid ? bricks : all,
-                                    D.stream));
-        v.seeds_valid = true;
-        HIP_TRY(launch_seed_distance(v.seeds + n, v.cube_skip, v.cube_skip + n, nb, false, nullptr, D.stream));
-        if (tables) {
-            if (!D.d_box6) HIP_TRY(hipMalloc(&D.d_box6, sizeof box));
-            HIP_TRY(launch_seed_distance(v.seeds, v.skip, v.skip + n, nb, true, D.d_box6, D.stream));
-            rc = ensure_buffer(D.edit_scratch, D.edit_scratch_cap, nibble_region_scratch_bytes(N, cells));
-            if (rc != VRT_OK) return rc;
-            HIP_TRY(launch_nibble_region(v.dense, v.nib, D.edit_scratch, N, nb, scale, h.step_max, cells, D.stream));
-            HIP_TRY(hipMemcpyAsync(box, D.d_box6, sizeof box, hipMemcpyDeviceToHost, D.stream));
-        }
-        HIP_TRY(hipStreamSynchronize(D.stream));
+        HIP_TRY(launch_scatter_region(D.edit_staging, voxels != nullptr, material != nullptr, texel16, v.dense, v.material, N, written.samples,
+                                      D.stream));
+        rc = rebuild_derived(ctx, D, slot, &written, false, h.abox);
+        if (rc != VRT_OK) return rc;
     }
-    memcpy(h.abox, box, sizeof box); /* unchanged without the tables, as upload_volume leaves it */
     ctx->scene_stale = true;
     return sync_volume_table(ctx);
 }
@@ -846,16 +853,15 @@ bool brush_box(const vrt_brush& r, int N, int lo[3], int hi[3]) {
 }
 
 /* vrt_volume_apply_brushes: the records are evaluated on the device over the union of their boxes (launch_brush_region), which
- * reports the box of the samples it wrote; what the full upload derives from the samples is then recomputed over that box, by the
- * kernels and in the order of update_region — or not at all when no density changed.  Afterwards every buffer equals what
- * upload_volume builds from the edited volume. */
+ * reports the box of the samples it wrote; what the slot derives from the samples is then recomputed over that box (rebuild_derived) —
+ * or not at all when no density changed.  Afterwards every buffer equals what upload_volume builds from the edited volume. */
 int apply_brushes(vrt_ctx* ctx, int slot, int n_rec, const vrt_brush* rec, vrt_brush_result* result) {
     if (!ctx || n_rec < 0 || n_rec > VRT_MAX_BRUSHES || (!rec && n_rec > 0)) return VRT_ERR_INVALID;
     if (!valid_slot(slot) || !ctx->vol[slot].used) return VRT_ERR_SLOT;
     for (int i = 0; i < n_rec; i++)
         if (!valid_brush(rec[i])) return VRT_ERR_INVALID;
     HostVolume& h = ctx->vol[slot];
-    const int N = h.N, C = N - 1, nb = h.nb;
+    const int N = h.N;
     if (result) *result = vrt_brush_result{{N, N, N}, {-1, -1, -1}, 0};
     const float cell = (h.extent * 2.0f) / (float)(N - 1);
     DBrushList list;
@@ -875,30 +881,19 @@ int apply_brushes(vrt_ctx* ctx, int slot, int n_rec, const vrt_brush* rec, vrt_b
         b.reach = rec[i].reach;
         b.material = rec[i].material;
         for (int a = 0; a < 3; a++) {
-            const int ax = a == 0 ? 0 : (a == 1 ? 2 : 1); /* the grid's axis order {x, z, y} */
-            b.lo[a] = lo[ax];
-            b.hi[a] = hi[ax];
+            b.lo[a] = lo[grid_axis(a)];
+            b.hi[a] = hi[grid_axis(a)];
             ulo[a] = std::min(ulo[a], lo[a]);
             uhi[a] = std::max(uhi[a], hi[a]);
         }
     }
     if (list.n == 0) return VRT_OK;
-    EditBox foot;
-    for (int a = 0; a < 3; a++) {
-        const int ax = a == 0 ? 0 : (a == 1 ? 2 : 1);
-        foot.lo[a] = ulo[ax];
-        foot.n[a] = uhi[ax] - ulo[ax] + 1;
-    }
+    const EditBox foot = derived_boxes(h, ulo, uhi).samples;
     const bool texel16 = h.format == VRT_FORMAT_TEXEL16;
-    const float scale = texel16 ? h.density_scale * 0.01f : h.density_scale;
-    const size_t n = (size_t)nb * nb * nb;
-    const EditBox all = {{0, 0, 0}, {nb, nb, nb}};
     for (auto& D : ctx->dev) { /* frames already enqueued render the old volume */
         HIP_TRY(hipSetDevice(D.ordinal));
         HIP_TRY(hipDeviceSynchronize());
     }
-    int box[6];
-    memcpy(box, h.abox, sizeof box);
     bool density_changed = false;
     for (size_t di = 0; di < ctx->dev.size(); di++) {
         DeviceState& D = ctx->dev[di];
@@ -922,34 +917,11 @@ int apply_brushes(vrt_ctx* ctx, int slot, int n_rec, const vrt_brush* rec, vrt_b
         if (di == 0 && result) *result = got;
         if (density_written == 0) continue; /* nothing written, or only material ids: no derived structure changes */
         density_changed = true;
-        EditBox cells, bricks; /* of the written samples' box, as update_region derives them from its box */
-        for (int a = 0; a < 3; a++) {
-            const int ax = a == 0 ? 0 : (a == 1 ? 2 : 1);
-            const int lo = got.lo[ax], hi = got.hi[ax];
-            cells.lo[a] = std::max(lo - 1, 0);
-            cells.n[a] = std::min(hi, C - 1) - cells.lo[a] + 1;
-            bricks.lo[a] = lo > 0 ? (lo - 1) / kBrickCells : 0;
-            bricks.n[a] = std::min(hi / kBrickCells, nb - 1) - bricks.lo[a] + 1;
-        }
-        HIP_TRY(launch_retile_region(v.dense, v.bricks, texel16 ? v.cells : nullptr, h.format, N, nb, bricks, D.stream));
-        const bool tables = v.skip_valid;
-        if (!v.seeds) HIP_TRY(hipMalloc(&v.seeds, 2 * n));
-        HIP_TRY(launch_seeds_region(v.dense, tables ? v.seeds : nullptr, v.seeds + n, N, nb, scale, h.step_max, v.seeds_valid ? bricks : all,
-                                    D.stream));
-        v.seeds_valid = true;
-        HIP_TRY(launch_seed_distance(v.seeds + n, v.cube_skip, v.cube_skip + n, nb, false, nullptr, D.stream));
-        if (tables) {
-            if (!D.d_box6) HIP_TRY(hipMalloc(&D.d_box6, sizeof box));
-            HIP_TRY(launch_seed_distance(v.seeds, v.skip, v.skip + n, nb, true, D.d_box6, D.stream));
-            int rc = ensure_buffer(D.edit_scratch, D.edit_scratch_cap, nibble_region_scratch_bytes(N, cells));
-            if (rc != VRT_OK) return rc;
-            HIP_TRY(launch_nibble_region(v.dense, v.nib, D.edit_scratch, N, nb, scale, h.step_max, cells, D.stream));
-            HIP_TRY(hipMemcpyAsync(box, D.d_box6, sizeof box, hipMemcpyDeviceToHost, D.stream));
-        }
-        HIP_TRY(hipStreamSynchronize(D.stream));
+        const DerivedBoxes written = derived_boxes(h, got.lo, got.hi);
+        int rc = rebuild_derived(ctx, D, slot, &written, false, h.abox);
+        if (rc != VRT_OK) return rc;
     }
     if (!density_changed) return VRT_OK;
-    memcpy(h.abox, box, sizeof box); /* unchanged without the tables, as upload_volume leaves it */
     ctx->scene_stale = true;
     return sync_volume_table(ctx);
 }
@@ -1158,7 +1130,7 @@ void cull_rect(const vrt_ctx* ctx, const vrt_params* p, DCam& F, const vrt_scene
             hi[a] = (double)h.extent;
             if (h.step_max > 0.0f && p->mode < VRT_MODE_CUBE && clip_everywhere) { /* the sphere-trace is clipped to the active box (a little
                                                                    slack for its float rounding); the Cube modes visit the whole volume box */
-                const int ax = a == 0 ? 0 : (a == 1 ? 2 : 1);
+                const int ax = grid_axis(a);
                 lo[a] = std::max(lo[a], (double)(h.abox[ax] * kBrickCells) * cell - (double)h.extent - 0.01 * cell);
                 hi[a] = std::min(hi[a], (double)std::min((h.abox[3 + ax] + 1) * kBrickCells, h.N - 1) * cell - (double)h.extent + 0.01 * cell);
             }
@@ -1685,9 +1657,8 @@ int vrt_volume_set_metric(vrt_ctx* ctx, int slot, float density_scale, float ste
     }
     ctx->vol[slot].density_scale = density_scale;
     ctx->vol[slot].step_max = step_max;
-    for (auto& D : ctx->dev) D.vol[slot].seeds_valid = false; /* the level-1 seeds depend on the metric */
     ctx->scene_stale = true;
-    int rc = rebuild_skip(ctx, slot);
+    int rc = rebuild_slot(ctx, slot, true);
     if (rc != VRT_OK) return rc;
     return sync_volume_table(ctx);
 }

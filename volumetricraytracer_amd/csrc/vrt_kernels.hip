@@ -2244,11 +2244,6 @@ __device__ __forceinline__ void retile_brick(const float* __restrict__ dense, fl
     }
     bricks[(size_t)brick * kBrickFloats + l] = v;
 }
-__global__ __launch_bounds__(128) void retile_bricks_kernel(const float* __restrict__ dense, float* __restrict__ bricks,
-                                                            int N, int nb) {
-    const int brick = (int)blockIdx.x; /* (bx*nb + bz)*nb + by */
-    retile_brick(dense, bricks, N, brick, brick / (nb * nb), brick % nb, (brick / nb) % nb);
-}
 
 /* The same for VRT_FORMAT_TEXEL16 volumes: the dense grid holds the integer field +-q as floats; bricks of 128 int16. */
 __device__ __forceinline__ void retile_brick16(const float* __restrict__ dense, short* __restrict__ bricks, int N, int brick, int bx, int by,
@@ -2264,10 +2259,6 @@ __device__ __forceinline__ void retile_brick16(const float* __restrict__ dense, 
         v = (short)(int)dense[((size_t)x * N + z) * N + y]; /* |value| <= 32767, integer: exact */
     }
     bricks[(size_t)brick * kBrickFloats + l] = v;
-}
-__global__ __launch_bounds__(128) void retile_bricks16_kernel(const float* __restrict__ dense, short* __restrict__ bricks, int N, int nb) {
-    const int brick = (int)blockIdx.x;
-    retile_brick16(dense, bricks, N, brick, brick / (nb * nb), brick % nb, (brick / nb) % nb);
 }
 
 /* VRT_PATH_CELLS: the 8 corner texels of every cell as one 16-byte record (cells beyond the grid repeat the last sample,
@@ -2290,10 +2281,6 @@ __device__ __forceinline__ void retile_cells16(const float* __restrict__ dense, 
     w.z = (unsigned)(unsigned short)v[4] | ((unsigned)(unsigned short)v[5] << 16);
     w.w = (unsigned)(unsigned short)v[6] | ((unsigned)(unsigned short)v[7] << 16);
     reinterpret_cast<uint4v*>(cells)[(size_t)brick * 64 + l] = w;
-}
-__global__ __launch_bounds__(64) void retile_cells16_kernel(const float* __restrict__ dense, short* __restrict__ cells, int N, int nb) {
-    const int brick = (int)blockIdx.x;
-    retile_cells16(dense, cells, N, brick, brick / (nb * nb), brick % nb, (brick / nb) % nb);
 }
 
 /* VRT_FORMAT_TEXEL16: a density as the reference's volume texel keeps it — sign + 15-bit trunc(|d| * 100)
@@ -2340,44 +2327,6 @@ __device__ __forceinline__ uint8_t cell_active(const float* __restrict__ dense, 
     }
     return a ? 1 : 0;
 }
-__global__ void active_cells_kernel(const float* __restrict__ dense, uint8_t* __restrict__ act, int N, float density_scale, float step_max) {
-    const int C = N - 1;
-    const size_t count = (size_t)C * C * C;
-    size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-    const size_t stride = (size_t)gridDim.x * blockDim.x;
-    for (; i < count; i += stride) {
-        const size_t x = i / ((size_t)C * C), z = (i / C) % C, y = i % C;
-        act[i] = cell_active(dense, N, x, z, y, density_scale, step_max);
-    }
-}
-
-/* Steps 2-4: separable min-plus passes of the windowed squared Euclidean distance transform between cells (cube-to-cube
- * distance: per axis max(|d|-1, 0)), along y (AXIS 0, from the active flags), z (AXIS 1) and x (AXIS 2).  0xffff = none
- * within the window. */
-template <int AXIS>
-__global__ void edt_pass_kernel(const uint8_t* __restrict__ act, const uint16_t* __restrict__ in, uint16_t* __restrict__ out, int C) {
-    const size_t count = (size_t)C * C * C;
-    size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-    const size_t stride = (size_t)gridDim.x * blockDim.x;
-    const size_t pitch = AXIS == 0 ? 1 : (AXIS == 1 ? (size_t)C : (size_t)C * C);
-    for (; i < count; i += stride) {
-        const int pos = AXIS == 0 ? (int)(i % C) : (AXIS == 1 ? (int)((i / C) % C) : (int)(i / ((size_t)C * C)));
-        int best = 0xffff;
-        for (int d = -kNibWindow; d <= kNibWindow; d++) {
-            const int q = pos + d;
-            if (q < 0 || q >= C) continue;
-            const size_t j = (size_t)((long long)i + (long long)d * (long long)pitch);
-            int g = (d < 0 ? -d : d);
-            g = g > 0 ? g - 1 : 0;
-            g *= g;
-            int v;
-            if constexpr (AXIS == 0) v = act[j] ? g : 0xffff;
-            else v = g + (int)in[j];
-            best = v < best ? v : best;
-        }
-        out[i] = (uint16_t)(best > 0xffff ? 0xffff : best);
-    }
-}
 
 /* floor(sqrt(d2)) capped at 15, and the eight sub-block nibbles of a brick from its 64 lanes' values (lane = cell lx*16 + lz*4 + ly). */
 __device__ __forceinline__ int capped_root(int v) {
@@ -2398,19 +2347,6 @@ __device__ __forceinline__ unsigned nibble_word(int r, int lx, int lz, int ly) {
         w |= (unsigned)m << (4 * k);
     }
     return w;
-}
-
-/* Step 5: per brick the eight sub-block nibbles: min over the sub-block's cells of floor(sqrt(d2)), capped at 15. */
-__global__ __launch_bounds__(64) void nibble_kernel(const uint16_t* __restrict__ d2, unsigned* __restrict__ nib, int C, int nb) {
-    const int brick = (int)blockIdx.x;
-    const int by = brick % nb, bz = (brick / nb) % nb, bx = brick / (nb * nb);
-    const int l = (int)threadIdx.x; /* one lane per cell */
-    const int lx = l >> 4, lz = (l >> 2) & 3, ly = l & 3;
-    const int x = bx * 4 + lx, y = by * 4 + ly, z = bz * 4 + lz;
-    int r = 15;
-    if (x < C && y < C && z < C) r = capped_root(d2[((size_t)x * C + z) * C + y]);
-    const unsigned w = nibble_word(r, lx, lz, ly);
-    if (l == 0) nib[brick] = w;
 }
 
 /* Empty-space table, level 1, step 1: a brick is "near" (0) when any of its 5^3 samples holds a trustworthy
@@ -2434,11 +2370,6 @@ __device__ __forceinline__ void skip_seed(const float* __restrict__ dense, uint8
     __syncthreads();
     if (l == 0) table[brick] = (flag[0] || flag[1]) ? 0 : 255;
 }
-__global__ __launch_bounds__(128) void skip_seed_kernel(const float* __restrict__ dense, uint8_t* __restrict__ table, int N, int nb,
-                                                        float density_scale, float step_max) {
-    const int brick = (int)blockIdx.x;
-    skip_seed(dense, table, N, brick, brick / (nb * nb), brick % nb, (brick / nb) % nb, density_scale, step_max);
-}
 
 /* Bounding box, in bricks, of the near bricks (distance 0): box = {min x, z, y, max x, z, y}, preset to {nb.., -1..}. */
 __global__ void active_box_kernel(const uint8_t* __restrict__ table, int nb, int* __restrict__ box) {
@@ -2453,15 +2384,6 @@ __global__ void active_box_kernel(const uint8_t* __restrict__ table, int nb, int
     atomicMax(&box[5], by);
 }
 
-/* The march wants the leap count, not the distance: L = max(D-1, 0) (one convert + one multiply per sample). */
-__global__ void skip_to_leap_kernel(uint8_t* __restrict__ table, int n) {
-    const int i = (int)(blockIdx.x * blockDim.x + threadIdx.x);
-    if (i < n) {
-        const uint8_t d = table[i];
-        table[i] = d > 1 ? (uint8_t)(d - 1) : (uint8_t)0;
-    }
-}
-
 /* Cube modes' table, step 1: a brick is a seed (0) when one of its 4^3 cell-origin voxels is solid
  * (density <= 0); voxels beyond cell N-2 do not exist (only at resolutions < 2, where one brick covers
  * the volume). */
@@ -2474,35 +2396,11 @@ __device__ __forceinline__ void cube_seed(const float* __restrict__ dense, uint8
     const unsigned long long any0 = __ballot(solid);
     if (l == 0) table[brick] = any0 != 0ull ? 0 : 255;
 }
-__global__ __launch_bounds__(64) void cube_seed_kernel(const float* __restrict__ dense, uint8_t* __restrict__ table, int N, int nb) {
-    const int brick = (int)blockIdx.x;
-    cube_seed(dense, table, N, brick, brick / (nb * nb), brick % nb, (brick / nb) % nb);
-}
 
-/* Step k of the exact Chebyshev distance transform: bricks still at 255 that touch (3x3x3) a brick at
- * distance k-1 get distance k.  Launched for k = 1..nb on ping-pong buffers. */
-__global__ void skip_dilate_kernel(const uint8_t* __restrict__ cur, uint8_t* __restrict__ nxt, int nb, int k) {
-    const int i = (int)(blockIdx.x * blockDim.x + threadIdx.x);
-    if (i >= nb * nb * nb) return;
-    const int by = i % nb, bz = (i / nb) % nb, bx = i / (nb * nb);
-    uint8_t d = cur[i];
-    if (d == 255) {
-        bool hit = false;
-        for (int dx = -1; dx <= 1; dx++)
-            for (int dz = -1; dz <= 1; dz++)
-                for (int dy = -1; dy <= 1; dy++) {
-                    const int x = bx + dx, y = by + dy, z = bz + dz;
-                    if (x < 0 || y < 0 || z < 0 || x >= nb || y >= nb || z >= nb) continue;
-                    hit = hit || cur[(x * nb + z) * nb + y] == (uint8_t)(k - 1);
-                }
-        if (hit) d = (uint8_t)k;
-    }
-    nxt[i] = d;
-}
-
-/* ---- incremental volume edits (vrt_volume_update_region) ---------------------------------------------------------------
- * Every kernel below recomputes one region of a structure the full upload builds, with the same per-element arithmetic as the
- * full build's kernel (shared through the helpers above), so that the edited slot ends byte-identical to a full upload. */
+/* ---- what a slot derives from its dense grid, over a box ----------------------------------------------------------------
+ * Every kernel below computes one region of a derived structure (bricks, cell records, seeds, level-2 table) from the dense grid,
+ * element by element through the helpers above.  An upload runs them over the whole grid, an edit (vrt_volume_update_region,
+ * vrt_volume_apply_brushes) over the box it can change: the same code, so an edited slot ends byte-identical to a full upload. */
 
 __device__ __forceinline__ size_t box_count(const EditBox& b) { return (size_t)b.n[0] * b.n[1] * b.n[2]; }
 /* local index (x slowest, then z, then y) -> global coordinates */
@@ -2515,7 +2413,7 @@ __device__ __forceinline__ size_t box_index(const EditBox& b, int x, int z, int 
     return ((size_t)(x - b.lo[0]) * b.n[1] + (size_t)(z - b.lo[1])) * b.n[2] + (size_t)(y - b.lo[2]);
 }
 
-/* The staged box -> dense grid + materials.  VOXELS: 8-byte VVoxel records (split_voxels_kernel); otherwise box floats followed,
+/* The staged box -> dense grid + materials.  VOXELS: 8-byte VVoxel records (u8 material, pad, f32 density); otherwise box floats followed,
  * when has_material, by box bytes.  texel16: quantised like quantize_field_kernel. */
 template <bool VOXELS>
 __global__ void scatter_region_kernel(const void* __restrict__ staging, float* __restrict__ dense, uint8_t* __restrict__ material, int N,
@@ -2690,9 +2588,10 @@ __global__ __launch_bounds__(64) void cube_seed_region_kernel(const float* __res
     cube_seed(dense, seeds, N, brick, bx, by, bz);
 }
 
-/* The exact Chebyshev distance (bricks) to the nearest seed (0) that dilate_table computes in nb launches, as three separable passes
- * (the L-infinity distance nests per axis): out(p) = min over q on p's line along AXIS (0: y, 1: z, 2: x) of max(|p - q|, in(q)), in(q) = 255
- * (no seed) skipped; no seed on any line stays 255.  LEAP: the pass stores the leap count of skip_to_leap_kernel instead. */
+/* The exact Chebyshev distance D (bricks) to the nearest seed (0) of all nb^3 bricks, as three separable passes (the L-infinity distance
+ * nests per axis): out(p) = min over q on p's line along AXIS (0: y, 1: z, 2: x) of max(|p - q|, in(q)), in(q) = 255 (no seed) skipped; no
+ * seed on any line stays 255 (nb <= 128: a distance never reaches it).  LEAP: the pass stores the leap count L = max(D - 1, 0) the march
+ * wants instead (one convert + one multiply per sample). */
 template <int AXIS, bool LEAP>
 __global__ void seed_distance_pass_kernel(const uint8_t* __restrict__ in, uint8_t* __restrict__ out, int nb) {
     const int i = (int)(blockIdx.x * blockDim.x + threadIdx.x);
@@ -2711,8 +2610,7 @@ __global__ void seed_distance_pass_kernel(const uint8_t* __restrict__ in, uint8_
     out[i] = (uint8_t)best;
 }
 
-/* Level-2 table over a cell box: active flags (active_cells_kernel), the three windowed passes (edt_pass_kernel) from an input box
- * `ib` that holds the output box `ob` grown by kNibWindow along AXIS, and the nibbles of a brick box (nibble_kernel). */
+/* Level-2 table over a cell box.  Step 1: the active flags (cell_active) of a cell box. */
 __global__ void active_cells_region_kernel(const float* __restrict__ dense, uint8_t* __restrict__ act, int N, EditBox b, float density_scale,
                                            float step_max) {
     const size_t count = box_count(b);
@@ -2724,6 +2622,9 @@ __global__ void active_cells_region_kernel(const float* __restrict__ dense, uint
         act[i] = cell_active(dense, N, (size_t)x, (size_t)z, (size_t)y, density_scale, step_max);
     }
 }
+/* Steps 2-4: separable min-plus passes of the windowed squared Euclidean distance transform between cells (cube-to-cube
+ * distance: per axis max(|d|-1, 0)), along y (AXIS 0, from the active flags), z (AXIS 1) and x (AXIS 2), from an input box `ib` that
+ * holds the output box `ob` grown by kNibWindow along AXIS (clipped to the grid).  0xffff = none within the window. */
 template <int AXIS>
 __global__ void edt_region_pass_kernel(const uint8_t* __restrict__ act, const uint16_t* __restrict__ in, uint16_t* __restrict__ out, int C,
                                        EditBox ib, EditBox ob) {
@@ -2750,6 +2651,7 @@ __global__ void edt_region_pass_kernel(const uint8_t* __restrict__ act, const ui
         out[i] = (uint16_t)(best > 0xffff ? 0xffff : best);
     }
 }
+/* Step 5: per brick of a brick box the eight sub-block nibbles: min over the sub-block's cells of floor(sqrt(d2)), capped at 15. */
 __global__ __launch_bounds__(64) void nibble_region_kernel(const uint16_t* __restrict__ d2, unsigned* __restrict__ nib, int C, int nb, EditBox bricks,
                                                            EditBox cells) {
     int bx, by, bz;
@@ -3059,19 +2961,6 @@ hipError_t launch_query(const DQuery& Q, int path, bool single, bool any, hipStr
     }
 }
 
-hipError_t launch_retile(const float* dense, void* bricks, int format, int N, int nb, hipStream_t stream) {
-    if (format == VRT_FORMAT_TEXEL16)
-        hipLaunchKernelGGL(retile_bricks16_kernel, dim3((unsigned)(nb * nb * nb)), dim3(128), 0, stream, dense, static_cast<short*>(bricks), N, nb);
-    else
-        hipLaunchKernelGGL(retile_bricks_kernel, dim3((unsigned)(nb * nb * nb)), dim3(128), 0, stream, dense, static_cast<float*>(bricks), N, nb);
-    return hipGetLastError();
-}
-
-hipError_t launch_retile_cells16(const float* dense, void* cells, int N, int nb, hipStream_t stream) {
-    hipLaunchKernelGGL(retile_cells16_kernel, dim3((unsigned)(nb * nb * nb)), dim3(64), 0, stream, dense, static_cast<short*>(cells), N, nb);
-    return hipGetLastError();
-}
-
 hipError_t launch_quantize_field(float* density, size_t count, hipStream_t stream) {
     hipLaunchKernelGGL(quantize_field_kernel, dim3(2048), dim3(256), 0, stream, density, count);
     return hipGetLastError();
@@ -3082,68 +2971,7 @@ hipError_t launch_texels_to_field(const void* texels, float* density, uint8_t* m
     return hipGetLastError();
 }
 
-static hipError_t dilate_table(uint8_t* table, uint8_t* scratch, int nb, hipStream_t stream);
-
-hipError_t launch_skip_table(const float* dense, uint8_t* table, uint8_t* scratch, int* box6, int N, int nb, float density_scale,
-                             float step_max, hipStream_t stream) {
-    const int n = nb * nb * nb;
-    hipLaunchKernelGGL(skip_seed_kernel, dim3((unsigned)n), dim3(128), 0, stream, dense, table, N, nb, density_scale, step_max);
-    hipError_t e = dilate_table(table, scratch, nb, stream);
-    if (e != hipSuccess) return e;
-    const int preset[6] = {nb, nb, nb, -1, -1, -1};
-    e = hipMemcpyAsync(box6, preset, sizeof preset, hipMemcpyHostToDevice, stream); /* pageable source: staged before return */
-    if (e != hipSuccess) return e;
-    hipLaunchKernelGGL(active_box_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, stream, table, nb, box6);
-    hipLaunchKernelGGL(skip_to_leap_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, stream, table, n);
-    return hipGetLastError();
-}
-
-size_t nibble_scratch_bytes(int N) {
-    const size_t C = (size_t)(N - 1);
-    return C * C * C * 5 + 64; /* active flags (1 B) + two ping-pong squared-distance grids (2 B each) per cell */
-}
-
-hipError_t launch_nibble_table(const float* dense, unsigned* nib, void* scratch, int N, int nb, float density_scale, float step_max,
-                               hipStream_t stream) {
-    const int C = N - 1;
-    const size_t cells = (size_t)C * C * C;
-    uint8_t* act = static_cast<uint8_t*>(scratch);
-    uint16_t* g = reinterpret_cast<uint16_t*>(act + ((cells + 63) & ~(size_t)63));
-    uint16_t* h = g + cells;
-    const unsigned grid = (unsigned)std::min<size_t>((cells + 255) / 256, 1u << 16);
-    hipLaunchKernelGGL(active_cells_kernel, dim3(grid), dim3(256), 0, stream, dense, act, N, density_scale, step_max);
-    hipLaunchKernelGGL((edt_pass_kernel<0>), dim3(grid), dim3(256), 0, stream, act, (const uint16_t*)nullptr, g, C);
-    hipLaunchKernelGGL((edt_pass_kernel<1>), dim3(grid), dim3(256), 0, stream, act, g, h, C);
-    hipLaunchKernelGGL((edt_pass_kernel<2>), dim3(grid), dim3(256), 0, stream, act, h, g, C);
-    hipLaunchKernelGGL(nibble_kernel, dim3((unsigned)(nb * nb * nb)), dim3(64), 0, stream, g, nib, C, nb);
-    return hipGetLastError();
-}
-
-hipError_t launch_cube_table(const float* dense, uint8_t* table, uint8_t* scratch, int N, int nb, hipStream_t stream) {
-    const int n = nb * nb * nb;
-    hipLaunchKernelGGL(cube_seed_kernel, dim3((unsigned)n), dim3(64), 0, stream, dense, table, N, nb);
-    return dilate_table(table, scratch, nb, stream);
-}
-
-static hipError_t dilate_table(uint8_t* table, uint8_t* scratch, int nb, hipStream_t stream) {
-    const int n = nb * nb * nb;
-    uint8_t* cur = table;
-    uint8_t* nxt = scratch;
-    const int rounds = nb < 254 ? nb : 254;
-    for (int k = 1; k <= rounds; k++) {
-        hipLaunchKernelGGL(skip_dilate_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, stream, cur, nxt, nb, k);
-        uint8_t* t = cur;
-        cur = nxt;
-        nxt = t;
-    }
-    if (cur != table) {
-        hipError_t e = hipMemcpyAsync(table, cur, (size_t)n, hipMemcpyDeviceToDevice, stream);
-        if (e != hipSuccess) return e;
-    }
-    return hipGetLastError();
-}
-
-/* ---- vrt_volume_update_region ---- */
+/* ---- uploads and edits: launches over a box ---- */
 static unsigned stride_grid(size_t count) { return (unsigned)std::max<size_t>(1, std::min<size_t>((count + 255) / 256, 1u << 16)); }
 static unsigned box_blocks(const EditBox& b) { return (unsigned)((size_t)b.n[0] * b.n[1] * b.n[2]); }
 
@@ -3192,13 +3020,14 @@ hipError_t launch_retile_region(const float* dense, void* bricks, void* cells_or
     return hipGetLastError();
 }
 
-hipError_t launch_seeds_region(const float* dense, uint8_t* skip_seeds_or_null, uint8_t* cube_seeds, int N, int nb, float density_scale,
+hipError_t launch_seeds_region(const float* dense, uint8_t* skip_seeds_or_null, uint8_t* cube_seeds_or_null, int N, int nb, float density_scale,
                                float step_max, const EditBox& bricks_box, hipStream_t stream) {
     const unsigned n = box_blocks(bricks_box);
     if (skip_seeds_or_null)
         hipLaunchKernelGGL(skip_seed_region_kernel, dim3(n), dim3(128), 0, stream, dense, skip_seeds_or_null, N, nb, bricks_box, density_scale,
                            step_max);
-    hipLaunchKernelGGL(cube_seed_region_kernel, dim3(n), dim3(64), 0, stream, dense, cube_seeds, N, nb, bricks_box);
+    if (cube_seeds_or_null)
+        hipLaunchKernelGGL(cube_seed_region_kernel, dim3(n), dim3(64), 0, stream, dense, cube_seeds_or_null, N, nb, bricks_box);
     return hipGetLastError();
 }
 

@@ -24,34 +24,22 @@ struct DQuery {
 };
 /* n rays, one lane each: closest hit, or (any) occlusion.  path as launch_march takes it (VRT_PATH_BRICK_LDS marches as VRT_PATH_BRICK). */
 hipError_t launch_query(const DQuery& q, int path, bool single_instance, bool any, hipStream_t stream);
-/* dense grid -> brick records of `format` (fp32: 512 B, VRT_FORMAT_TEXEL16: 256 B of int16). */
-hipError_t launch_retile(const float* dense, void* bricks, int format, int N, int nb, hipStream_t stream);
-/* VRT_PATH_CELLS: integer field -> nb^3 x 64 cell records of 8 int16. */
-hipError_t launch_retile_cells16(const float* dense, void* cells, int N, int nb, hipStream_t stream);
 /* VRT_FORMAT_TEXEL16: densities -> the integer field +-q of the reference's volume texel, in place. */
 hipError_t launch_quantize_field(float* density, size_t count, hipStream_t stream);
 /* The reference's RGBA8 volume texture (device copy) -> integer field + materials in the grid's own order. */
 hipError_t launch_texels_to_field(const void* texels, float* density, uint8_t* material, int N, hipStream_t stream);
-/* Empty-space table, level 1: nb^3 leap-count bytes from the dense grid (scratch: another nb^3 bytes), and (box6, six
-   device ints) the bounding box of the near bricks in brick coordinates {min x, z, y, max x, z, y} ({nb.., -1..}: none). */
-hipError_t launch_skip_table(const float* dense, uint8_t* table, uint8_t* scratch, int* box6, int N, int nb, float density_scale,
-                             float step_max, hipStream_t stream);
-/* Empty-space table, level 2: nb^3 words of sub-block nibbles (scratch: nibble_scratch_bytes(N)). */
-size_t nibble_scratch_bytes(int N);
-hipError_t launch_nibble_table(const float* dense, unsigned* nib, void* scratch, int N, int nb, float density_scale, float step_max,
-                               hipStream_t stream);
-/* Cube modes: nb^3-byte Chebyshev distance (bricks) to the nearest brick holding a solid voxel. */
-hipError_t launch_cube_table(const float* dense, uint8_t* table, uint8_t* scratch, int N, int nb, hipStream_t stream);
 /* Device Voxelizer: frames = n_frames vrt_vox::TriangleFrame records (device memory); writes N^3 densities + materials. */
 hipError_t launch_voxelize(const void* frames, size_t n_frames, float* density, uint8_t* material, int N, float cell, float extent,
                            float threshold, hipStream_t stream);
 /* vrt_debug_gather_ceiling: `blocks` workgroups of 256 lanes, `iters` trilinear samples per lane from a pool of n_bricks (a power of two)
    brick records of `format`; out: blocks * 256 floats. */
 hipError_t launch_gather_ceiling(const void* pool, unsigned n_bricks, int format, bool coherent, int iters, float* out, int blocks, hipStream_t stream);
-hipError_t launch_split_voxels(const void* voxels, float* density, uint8_t* material, size_t count,
-                               hipStream_t stream);
+/* VVoxel records (8 B) -> densities + materials, in the grid's own order. */
+hipError_t launch_split_voxels(const void* voxels, float* density, uint8_t* material, size_t count, hipStream_t stream);
 
-/* vrt_volume_update_region: a box of samples, cells or bricks in the grid's own axis order {x, z, y}: [lo, lo + n) per axis. */
+/* What a slot derives from its dense grid is built by the launches below over a box: the whole grid by an upload, the part an edit
+   (vrt_volume_update_region, vrt_volume_apply_brushes) can change otherwise.
+   A box of samples, cells or bricks in the grid's own axis order {x, z, y}: [lo, lo + n) per axis. */
 struct EditBox {
     int lo[3];
     int n[3];
@@ -60,16 +48,20 @@ struct EditBox {
    quantised like launch_quantize_field when texel16. */
 hipError_t launch_scatter_region(const void* staging, bool voxels, bool has_material, bool texel16, float* dense, uint8_t* material, int N,
                                  const EditBox& box, hipStream_t stream);
-/* launch_retile (and launch_retile_cells16 when cells_or_null) over the bricks of a brick box. */
+/* dense grid -> the brick records of `format` (fp32: 512 B, VRT_FORMAT_TEXEL16: 256 B of int16) and, when cells_or_null (VRT_PATH_CELLS),
+   the 64 cell records of 8 int16 of every brick of a brick box. */
 hipError_t launch_retile_region(const float* dense, void* bricks, void* cells_or_null, int format, int N, int nb, const EditBox& bricks_box,
                                 hipStream_t stream);
-/* The seeds (0 / 255) of the level-1 table (when skip_seeds_or_null) and of the Cube table over the bricks of a brick box. */
-hipError_t launch_seeds_region(const float* dense, uint8_t* skip_seeds_or_null, uint8_t* cube_seeds, int N, int nb, float density_scale,
+/* The seeds (0 / 255) of the level-1 table (a brick with a sample below the clamp) and of the Cube table (a brick holding a solid voxel)
+   over the bricks of a brick box, each into its nb^3-byte grid when given. */
+hipError_t launch_seeds_region(const float* dense, uint8_t* skip_seeds_or_null, uint8_t* cube_seeds_or_null, int N, int nb, float density_scale,
                                float step_max, const EditBox& bricks_box, hipStream_t stream);
-/* nb^3 seeds -> the table launch_skip_table (leap) / launch_cube_table (distance) builds, and the near bricks' box (box6_or_null);
-   scratch: nb^3 bytes. */
+/* nb^3 seeds -> nb^3 bytes of the Chebyshev distance (bricks) to the nearest seed (the Cube modes' table) or, leap, of the leap count
+   max(distance - 1, 0) (the empty-space table, level 1), and (box6_or_null, six device ints) the bounding box of the seeds in brick
+   coordinates {min x, z, y, max x, z, y} ({nb.., -1..}: none); scratch: nb^3 bytes. */
 hipError_t launch_seed_distance(const uint8_t* seeds, uint8_t* table, uint8_t* scratch, int nb, bool leap, int* box6_or_null, hipStream_t stream);
-/* Level-2 table where the active flags of the cell box `changed` may have changed. */
+/* Empty-space table, level 2 (nb^3 words of sub-block nibbles) where the active flags of the cell box `changed` may have changed;
+   scratch: nibble_region_scratch_bytes (all cells: 5 bytes per cell). */
 size_t nibble_region_scratch_bytes(int N, const EditBox& changed);
 hipError_t launch_nibble_region(const float* dense, unsigned* nib, void* scratch, int N, int nb, float density_scale, float step_max,
                                 const EditBox& changed, hipStream_t stream);
