@@ -20,6 +20,8 @@
  *                                   for a box of voxels instead of the whole volume
  *   vrt_volume_apply_brushes,       (no reference analogue beyond VVoxelVolume::SetVoxel, VoxelVolume.cpp:59-77, in a host loop: CSG
  *   vrt_volume_download_region      sphere / box / capsule brushes evaluated on the resident volume, and the read-back of a box)
+ *   vrt_volume_fill_enclosed        (no reference analogue: its Voxelizer stops at the unsigned shell, Voxelizer/Private/VolumeConverter.cpp:30-84 —
+ *                                   the shell of a closed mesh made solid on the resident volume, so that a SUBTRACT brush carves a solid)
  *   vrt_volume_free                 VRDXScene::RemoveVoxelVolume  Renderer/DX/Private/RDXScene.cpp:663-701
  *   vrt_env_upload                  VRDXScene::InitEnvironmentMap RDXScene.cpp:181-199
  *   vrt_scene_set                   VRDXScene::SyncWithScene + PrepareForRendering
@@ -373,6 +375,46 @@ typedef struct vrt_brush_result {     /* 32 B */
  * (SUBTRACT only raises values near the new surface).  For adding into a true SDF it is as far as the old field over-estimates the
  * distance to the new solid.  A slot with step_max > 0 never steps further than step_max, so step_max/cell + 1 is enough there. */
 int vrt_volume_apply_brushes(vrt_ctx* ctx, int slot, int n, const vrt_brush* brushes, vrt_brush_result* result_or_null);
+
+/* Solid volumes from shells (no reference analogue: its Voxelizer stops at the shell).  vrt_voxelize_mesh and the CPU converter leave the
+ * reference's UNSIGNED shell field, density = dist/thr - 0.5: inside a closed mesh the field is positive again, so a VRT_BRUSH_SUBTRACT dab
+ * (max(d, -v)) opens a hole into an empty cavity behind a wall about 1.7 cells thick.  This call turns every enclosed cavity solid, on the
+ * device, in place. */
+typedef struct vrt_fill_result {      /* 40 B */
+    int32_t lo[3], hi[3];             /* xyz, inclusive: bounding box of the samples written; lo > hi when none */
+    uint64_t filled;                  /* samples written */
+    uint32_t sweeps;                  /* propagation rounds the device ran (informative; implementation-defined) */
+    uint32_t reserved_;
+} vrt_fill_result;
+
+/* Fills the enclosed cavities of the resident slot, in place, on every device.  Waits for work already enqueued on the context's devices
+ * (a frame begun before the call renders the old volume, one begun after renders the new one); device pointers of the slot do not
+ * change.  Afterwards every device buffer of the slot equals what a full upload of the filled volume holds (what the slot derives from
+ * its samples is rebuilt over the written box; nothing is rebuilt when filled == 0), so frames and counters are those of the full
+ * upload.  A launch captured into a graph before the call keeps the cull rectangle it was captured with, as for the other edits.
+ * Errors, all checked before any device state is touched: VRT_ERR_INVALID for a NULL context; VRT_ERR_SLOT for an unused slot;
+ * VRT_ERR_INVALID for a wall that is not finite or is negative, or a material outside -1..255.  A volume without an enclosed sample
+ * is OK: filled == 0 and lo > hi.  A second call on a filled volume fills nothing.
+ * result_or_null: the written samples' count and box, from device 0 (all devices compute the same bytes).
+ *
+ * The rule is part of the contract.
+ *   d is the sample's current density in the caller's units: the stored float (VRT_FORMAT_F32), or stored * 0.01f
+ *   (VRT_FORMAT_TEXEL16, as vrt_volume_download decodes it).
+ *   Passable: a sample with d > 0.  NaN, +-0 and negative samples are walls.
+ *   Exterior: every passable sample with an index 0 or N - 1 on some axis, and every passable sample that can be reached from one of
+ *             those by steps to a 6-neighbour (one index +-1) over passable samples.  Diagonal contact does not connect.  The set is
+ *             unique: the result does not depend on the order in which the device visits the grid.
+ *   Enclosed: passable and not exterior.  Every enclosed sample stores m = -(d + wall): one fp32 add, then a negation — m itself
+ *             (F32) or the texel of m (TEXEL16: the rule at vrt_set_volume_format).  With material >= 0 its material id becomes
+ *             `material` (the Voxelizer's rule, material = (density <= 0), is material = 1); -1 leaves the ids alone.
+ *   Every other sample keeps its stored bits; walls are never touched, so the outer surface is the one the shell had.
+ * Choosing wall: the wall's thickness in density units; 1 for Voxelizer shells.  Their wall runs from -0.5 at the mesh to 0 at both
+ * crossings; a cavity point at distance s from the mesh holds f = s/thr - 0.5 and lies (f + 1) * thr below the OUTER crossing.
+ * What the call does not do: the wall's own samples on the inner side of the mesh keep their shell values -0.5..0 where a signed
+ * field would hold -1..-0.5.  All of the interior is negative afterwards — nothing renders inside and a carve shows a solid — but
+ * where a brush surface meets the former inner crossing the carved surface can sit a fraction of a cell off.  Redistancing the wall
+ * is a separate pass. */
+int vrt_volume_fill_enclosed(vrt_ctx* ctx, int slot, float wall, int material, vrt_fill_result* result_or_null);
 /* Reads the box [origin, origin+size) of device 0's slot as VVoxel records: box order as vrt_volume_update_voxels takes it, decode
  * as vrt_volume_download's.  Only the box's bytes cross the bus, so a host mirror can follow a device-side edit without a full
  * download.  Argument checks as vrt_volume_update_region's.  On a VRT_FORMAT_TEXEL16 slot the decoded values (q * 0.01f) re-quantise

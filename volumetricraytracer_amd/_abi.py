@@ -224,6 +224,10 @@ class vrt_brush_result(C.Structure):
     _fields_ = [("lo", C.c_int32 * 3), ("hi", C.c_int32 * 3), ("written", C.c_uint64)]
 
 
+class vrt_fill_result(C.Structure):
+    _fields_ = [("lo", C.c_int32 * 3), ("hi", C.c_int32 * 3), ("filled", C.c_uint64), ("sweeps", C.c_uint32), ("reserved_", C.c_uint32)]
+
+
 SYMBOLS = {
     "vrt_create": (C.c_int, [C.POINTER(C.c_void_p), C.c_int, C.POINTER(C.c_int)]),
     "vrt_destroy": (C.c_int, [C.c_void_p]),
@@ -243,6 +247,7 @@ SYMBOLS = {
     "vrt_volume_update_region": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int), C.c_void_p, C.c_void_p]),
     "vrt_volume_update_voxels": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int), C.c_void_p]),
     "vrt_volume_apply_brushes": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.POINTER(vrt_brush), C.POINTER(vrt_brush_result)]),
+    "vrt_volume_fill_enclosed": (C.c_int, [C.c_void_p, C.c_int, C.c_float, C.c_int, C.POINTER(vrt_fill_result)]),
     "vrt_volume_download_region": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int), C.c_void_p]),
     "vrt_debug_volume_bytes": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_size_t, C.POINTER(C.c_size_t)]),
     "vrt_env_upload": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p]),

@@ -754,6 +754,31 @@ bool VHipRenderer::TraceRays(const std::vector<vrt_ray>& rays, std::vector<vrt_h
               "vrt_trace_rays_host");
 }
 
+int VHipRenderer::SlotOf(const Voxel::VVoxelVolume* volume) const {
+    int slot = -1;
+    for (size_t i = 0; i < Uploaded.size(); i++)
+        if (Uploaded[i] == volume) slot = (int)i;
+    return slot;
+}
+
+/* the host mirror follows a device-side edit: the written box, row by row of the volume's own order (x slowest, then z, then y) */
+bool VHipRenderer::MirrorBox(int slot, Voxel::VVoxelVolume& volume, const int lo[3], const int hi[3]) {
+    const int size[3] = {hi[0] - lo[0] + 1, hi[1] - lo[1] + 1, hi[2] - lo[2] + 1};
+    RegionStaging.resize((size_t)size[0] * size[1] * size[2]);
+    if (!ok(vrt_volume_download_region(Ctx, slot, lo, size, reinterpret_cast<vrt_voxel*>(RegionStaging.data())), "vrt_volume_download_region"))
+        return false;
+    const size_t n = volume.GetSize();
+    std::vector<Voxel::VVoxel>& all = volume.GetVoxels();
+    size_t k = 0;
+    for (int x = lo[0]; x <= hi[0]; x++)
+        for (int z = lo[2]; z <= hi[2]; z++) {
+            const size_t row = ((size_t)x * n + (size_t)z) * n + (size_t)lo[1];
+            std::copy(RegionStaging.begin() + (ptrdiff_t)k, RegionStaging.begin() + (ptrdiff_t)(k + (size_t)size[1]), all.begin() + (ptrdiff_t)row);
+            k += (size_t)size[1];
+        }
+    return true;
+}
+
 bool VHipRenderer::ApplyBrushes(const Scene::VVoxelObject& object, const std::vector<vrt_brush>& brushes, vrt_brush_result* result) {
     if (!IsActive()) {
         V_LOG_WARNING("ApplyBrushes() on an inactive renderer");
@@ -763,9 +788,7 @@ bool VHipRenderer::ApplyBrushes(const Scene::VVoxelObject& object, const std::ve
     const VObjectPtr<Voxel::VVoxelVolume> volume = object.GetVoxelVolume();
     if (!scene || !volume || brushes.size() > (size_t)VRT_MAX_BRUSHES) return false;
     if (!SyncWithScene(*scene)) return false;
-    int slot = -1;
-    for (size_t i = 0; i < Uploaded.size(); i++)
-        if (Uploaded[i] == volume.get()) slot = (int)i;
+    const int slot = SlotOf(volume.get());
     if (slot < 0) {
         V_LOG_ERROR("ApplyBrushes(): the object's volume is not part of the rendered scene");
         return false;
@@ -774,21 +797,28 @@ bool VHipRenderer::ApplyBrushes(const Scene::VVoxelObject& object, const std::ve
     if (!ok(vrt_volume_apply_brushes(Ctx, slot, (int)brushes.size(), brushes.data(), &res), "vrt_volume_apply_brushes")) return false;
     if (result) *result = res;
     if (res.written == 0) return true;
-    /* the host mirror follows: the written box, row by row of the volume's own order (x slowest, then z, then y) */
-    const int size[3] = {res.hi[0] - res.lo[0] + 1, res.hi[1] - res.lo[1] + 1, res.hi[2] - res.lo[2] + 1};
-    RegionStaging.resize((size_t)size[0] * size[1] * size[2]);
-    if (!ok(vrt_volume_download_region(Ctx, slot, res.lo, size, reinterpret_cast<vrt_voxel*>(RegionStaging.data())), "vrt_volume_download_region"))
+    return MirrorBox(slot, *volume, res.lo, res.hi);
+}
+
+bool VHipRenderer::FillEnclosed(const Scene::VVoxelObject& object, float wall, int material, vrt_fill_result* result) {
+    if (!IsActive()) {
+        V_LOG_WARNING("FillEnclosed() on an inactive renderer");
         return false;
-    const size_t n = volume->GetSize();
-    std::vector<Voxel::VVoxel>& all = volume->GetVoxels();
-    size_t k = 0;
-    for (int x = res.lo[0]; x <= res.hi[0]; x++)
-        for (int z = res.lo[2]; z <= res.hi[2]; z++) {
-            const size_t row = ((size_t)x * n + (size_t)z) * n + (size_t)res.lo[1];
-            std::copy(RegionStaging.begin() + (ptrdiff_t)k, RegionStaging.begin() + (ptrdiff_t)(k + (size_t)size[1]), all.begin() + (ptrdiff_t)row);
-            k += (size_t)size[1];
-        }
-    return true;
+    }
+    const VObjectPtr<Scene::VScene> scene = SceneRef.lock();
+    const VObjectPtr<Voxel::VVoxelVolume> volume = object.GetVoxelVolume();
+    if (!scene || !volume) return false;
+    if (!SyncWithScene(*scene)) return false;
+    const int slot = SlotOf(volume.get());
+    if (slot < 0) {
+        V_LOG_ERROR("FillEnclosed(): the object's volume is not part of the rendered scene");
+        return false;
+    }
+    vrt_fill_result res;
+    if (!ok(vrt_volume_fill_enclosed(Ctx, slot, wall, material, &res), "vrt_volume_fill_enclosed")) return false;
+    if (result) *result = res;
+    if (res.filled == 0) return true;
+    return MirrorBox(slot, *volume, res.lo, res.hi);
 }
 
 bool VHipRenderer::Pick(int px, int py, vrt_hit& out) {

@@ -120,9 +120,17 @@ public:
        VRT_FORMAT_TEXEL16 the mirror receives the decoded texels (q * 0.01), which quantise again — and need not give q back — should
        the volume be uploaded whole later.  False (after logging) on failure or when the object's volume is not in the scene. */
     bool ApplyBrushes(const Scene::VVoxelObject& object, const std::vector<vrt_brush>& brushes, vrt_brush_result* result = nullptr);
+    /* The cavities a shell volume encloses made solid on the device (vrt_volume_fill_enclosed; the rule: vrt.h), on the volume of a
+       placed object of the scene Render() would draw now (synced first): Voxelizer output, whose unsigned shell a SUBTRACT brush would
+       otherwise open into an empty inside.  wall: the wall's thickness in density units (1 for Voxelizer shells); material: the id the
+       filled voxels get, or -1.  The written box is read back into the host VVoxelVolume like ApplyBrushes does.  False (after
+       logging) on failure or when the object's volume is not in the scene. */
+    bool FillEnclosed(const Scene::VVoxelObject& object, float wall = 1.f, int material = -1, vrt_fill_result* result = nullptr);
 
 private:
     bool SyncWithScene(Scene::VScene& scene);
+    int SlotOf(const Voxel::VVoxelVolume* volume) const; /* -1: not uploaded */
+    bool MirrorBox(int slot, Voxel::VVoxelVolume& volume, const int lo[3], const int hi[3]); /* device box -> host volume */
     bool FillSceneStruct(Scene::VScene& scene, vrt_scene& out, std::vector<const Scene::VVoxelObject*>* objects = nullptr);
     std::vector<const Scene::VVoxelObject*> QueryObjects; /* instance -> placed object of the last query's scene */
     vrt_params MakeParams(Scene::VScene& scene) const;

@@ -1,8 +1,10 @@
 #include "VolumeConverter.h"
 
 #include "../../../include/vrt.h"
+#include "../fill_core.h"
 #include "../voxelize_core.h"
 
+#include <algorithm>
 #include <cmath>
 #include <iostream>
 #include <vector>
@@ -40,6 +42,55 @@ void voxelize_face(Voxel::VVoxelVolume& volume, const TriangleFrame& t, float th
 
 static vrt_ctx* g_device_ctx = nullptr;
 void VVolumeConverter::UseDevice(vrt_ctx* ctx) { g_device_ctx = ctx; }
+static bool g_solid = false;
+void VVolumeConverter::MakeSolid(bool solid) { g_solid = solid; }
+
+VVolumeConverter::VFillResult VVolumeConverter::FillEnclosed(Voxel::VVoxel* voxels, size_t n, float wall, int material) {
+    const size_t count = n * n * n;
+    const ptrdiff_t step[3] = {(ptrdiff_t)(n * n), 1, (ptrdiff_t)n}; /* x, y, z */
+    std::vector<uint8_t> exterior(count, 0);
+    std::vector<uint32_t> queue; /* sample indices: 513^3 < 2^32 */
+    const auto visit = [&](size_t i) {
+        if (!exterior[i] && vrt_fill::passable(voxels[i].Density)) {
+            exterior[i] = 1;
+            queue.push_back((uint32_t)i);
+        }
+    };
+    for (size_t a = 0; a < n; a++) /* the six faces */
+        for (size_t b = 0; b < n; b++)
+            for (size_t face : {(size_t)0, n - 1}) {
+                visit((face * n + a) * n + b);
+                visit((a * n + face) * n + b);
+                visit((a * n + b) * n + face);
+            }
+    for (size_t head = 0; head < queue.size(); head++) {
+        const size_t i = queue[head];
+        const size_t at[3] = {i / (n * n), i % n, (i / n) % n};
+        for (int a = 0; a < 3; a++) {
+            if (at[a] > 0) visit((size_t)((ptrdiff_t)i - step[a]));
+            if (at[a] + 1 < n) visit((size_t)((ptrdiff_t)i + step[a]));
+        }
+    }
+    VFillResult out;
+    out.Lo = VIntVector((int)n, (int)n, (int)n);
+    out.Hi = VIntVector(-1, -1, -1);
+    for (size_t i = 0; i < count; i++) {
+        if (exterior[i] || !vrt_fill::passable(voxels[i].Density)) continue;
+        voxels[i].Density = vrt_fill::filled_density(voxels[i].Density, wall);
+        if (material >= 0) voxels[i].Material = (uint8_t)material;
+        const int x = (int)(i / (n * n)), y = (int)(i % n), z = (int)((i / n) % n);
+        out.Lo = VIntVector(std::min(out.Lo.X, x), std::min(out.Lo.Y, y), std::min(out.Lo.Z, z));
+        out.Hi = VIntVector(std::max(out.Hi.X, x), std::max(out.Hi.Y, y), std::max(out.Hi.Z, z));
+        out.Filled++;
+    }
+    return out;
+}
+
+VVolumeConverter::VFillResult VVolumeConverter::FillEnclosed(Voxel::VVoxelVolume& volume, float wall, int material) {
+    const VFillResult out = FillEnclosed(volume.GetVoxels().data(), volume.GetSize(), wall, material);
+    if (out.Filled) volume.MakeDirty();
+    return out;
+}
 
 bool VVolumeConverter::ExtractResolutionFromName(const std::string& name, uint8_t& outResolution) {
     const size_t at = name.rfind('_');
@@ -91,6 +142,7 @@ std::shared_ptr<Voxel::VVoxelVolume> VVolumeConverter::ConvertMeshInfoToVoxelVol
         for (size_t i = 0; i < idx.size(); i++) idx[i] = meshInfo.Indices[i] > 0xfffffffeull ? 0xffffffffu : (uint32_t)meshInfo.Indices[i];
         static_assert(sizeof(Voxel::VVoxel) == sizeof(vrt_voxel), "VVoxel must match the wire record");
         int rc = vrt_voxelize_mesh(g_device_ctx, kScratchSlot, resolution, extends, pos.data(), meshInfo.Vertices.size(), idx.data(), idx.size(), &skipped);
+        if (rc == VRT_OK && g_solid) rc = vrt_volume_fill_enclosed(g_device_ctx, kScratchSlot, 1.f, 1, nullptr);
         if (rc == VRT_OK) rc = vrt_volume_download(g_device_ctx, kScratchSlot, reinterpret_cast<vrt_voxel*>(volume->GetVoxels().data()));
         if (rc == VRT_OK) {
             (void)vrt_volume_free(g_device_ctx, kScratchSlot);
@@ -115,6 +167,7 @@ std::shared_ptr<Voxel::VVoxelVolume> VVolumeConverter::ConvertMeshInfoToVoxelVol
         vrt_vox::index_box(t, threshold, volume->GetVolumeExtends(), volume->GetCellSize(), (int)volume->GetSize());
         voxelize_face(*volume, t, threshold);
     }
+    if (g_solid && !on_device) FillEnclosed(*volume, 1.f, 1);
     if (skipped) std::cout << "[WARNING] Skipped " << skipped << " degenerate or out-of-range triangle(s) of " << meshInfo.MeshName << std::endl;
 
     VMaterial material = meshInfo.Material;

@@ -26,6 +26,22 @@ public:
        volume, bit for bit (both builds compile csrc/voxelize_core.h).  ctx = a live vrt_ctx, or nullptr to go
        back to the CPU loop.  The converter uses (and overwrites) volume slot 19 of that context. */
     static void UseDevice(::vrt_ctx* ctx);
+    /* What FillEnclosed wrote: the samples' count and their inclusive xyz box (Lo > Hi when none). */
+    struct VFillResult {
+        VIntVector Lo, Hi;
+        size_t Filled = 0;
+    };
+    /* The shell of a closed mesh made solid, in place (the rule of vrt_volume_fill_enclosed, include/vrt.h; its arithmetic is
+       csrc/fill_core.h, shared with the HIP kernels): a breadth-first flood from the grid's faces over the samples with density > 0,
+       6-connected; every sample with density > 0 it does not reach gets -(density + wall) and, material >= 0, that material id.
+       wall: the wall's thickness in density units, 1 for this converter's shells; material: 0..255 (1 = the converter's own rule for
+       density <= 0) or -1 to leave the ids alone.  Marks the volume dirty when it wrote. */
+    static VFillResult FillEnclosed(Voxel::VVoxelVolume& volume, float wall, int material);
+    /* The same on n^3 VVoxel records (index x*n*n + z*n + y). */
+    static VFillResult FillEnclosed(Voxel::VVoxel* voxels, size_t n, float wall, int material);
+    /* true: every converted volume is filled (wall 1, material 1) before it is returned — on the device (vrt_volume_fill_enclosed)
+       while UseDevice names a context, on the host otherwise; the same volume, bit for bit. */
+    static void MakeSolid(bool solid);
     static bool ExtractResolutionFromName(const std::string& name, uint8_t& outResolution);
     /* extraction threshold of a volume: cell size · √3 (VolumeConverter.cpp:57) */
     static float ExtractionThreshold(const Voxel::VVoxelVolume& volume);

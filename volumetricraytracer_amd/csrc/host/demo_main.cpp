@@ -17,6 +17,10 @@
  *            [--edit-full]                  ... and uploads the whole volume after every edit instead (the same frames)
  *            [--edit-device]                with --edit-brush: the carve is one SUBTRACT sphere record evaluated on the device
  *                                           (VHipRenderer::ApplyBrushes, vrt_volume_apply_brushes); no host loop, no box upload
+ *            [--solid]                      the red sphere is built as the Voxelizer builds a mesh — an unsigned shell, density = |distance to its surface| / thr - 0.5
+ *                                           with thr = cell * sqrt 3, positive again inside — and, after the upload, every volume of the scene has its enclosed
+ *                                           cavities filled on the device (VHipRenderer::FillEnclosed, vrt_volume_fill_enclosed; wall 1, material 1): --edit-brush
+ *                                           then carves a solid, in the red sphere and in the models of a --scene file, instead of opening a hollow shell
  *            [--pick X Y]                   every frame asks what lies under pixel (X, Y) (VHipRenderer::Pick: a GPU ray query) and prints the
  *                                           hit record; with --edit-brush the brush is centred on the picked voxel when the pick hits the red
  *                                           sphere, and a frame whose pick misses it edits nothing
@@ -33,19 +37,25 @@
 
 using namespace VolumeRaytracer;
 
-static VObjectPtr<Scene::VVoxelObject> InitSphere(Scene::VScene& scene, float radius, const VMaterial& material) {
+static VObjectPtr<Scene::VVoxelObject> InitSphere(Scene::VScene& scene, float radius, const VMaterial& material, bool shell = false) {
     auto volume = std::make_shared<Voxel::VVoxelVolume>(6, 100.f);
     const int n = (int)volume->GetSize();
+    const float thr = volume->GetCellSize() * std::sqrt(3.f); /* the Voxelizer's extraction threshold, VolumeConverter.cpp:57 */
     for (int x = 0; x < n; x++)
         for (int y = 0; y < n; y++)
             for (int z = 0; z < n; z++) {
                 const VIntVector idx(x, y, z);
-                const float density = volume->VoxelIndexToRelativePosition(idx).Length() - radius; /* VSphere, DensityGenerator.cpp:33-36 */
+                float density = volume->VoxelIndexToRelativePosition(idx).Length() - radius; /* VSphere, DensityGenerator.cpp:33-36 */
+                if (shell) density = std::fabs(density) / thr - 0.5f;                          /* VoxelizeFace, VolumeConverter.cpp:200-202 */
                 Voxel::VVoxel v;
                 v.Material = density <= 0 ? 1 : 0;
                 v.Density = density;
                 volume->SetVoxel(idx, v);
             }
+    if (shell) { /* the metric of Voxelizer output */
+        volume->DensityScale = thr;
+        volume->StepMax = 0.5f * thr;
+    }
     volume->SetMaterial(material);
     auto obj = scene.SpawnObject<Scene::VVoxelObject>(VVector::ZERO, VQuat::IDENTITY, VVector::ONE);
     obj->SetVoxelVolume(volume);
@@ -73,7 +83,7 @@ int main(int argc, char** argv) {
     std::string scenePath, skyboxDir, outPath = "vrt_demo.ppm";
     bool identityDefaults = false;
     int editBrush = 0;
-    bool editFull = false, editDevice = false;
+    bool editFull = false, editDevice = false, solid = false;
     bool pick = false;
     int pickX = 0, pickY = 0;
     int mode = 0, inFlight = 3, block = 0; /* three frames in flight: the reference's swap chain (FrameCount, DXConstants.cpp:23) */
@@ -93,6 +103,7 @@ int main(int argc, char** argv) {
         else if (!strcmp(argv[i], "--edit-brush") && i + 1 < argc) editBrush = atoi(argv[++i]);
         else if (!strcmp(argv[i], "--edit-full")) editFull = true;
         else if (!strcmp(argv[i], "--edit-device")) editDevice = true;
+        else if (!strcmp(argv[i], "--solid")) solid = true;
         else if (!strcmp(argv[i], "--pick") && i + 2 < argc) {
             pick = true;
             pickX = atoi(argv[++i]);
@@ -134,7 +145,7 @@ int main(int argc, char** argv) {
     material.AlbedoColor = VColor::RED;
     material.Roughness = 0.1f;
     material.Metallic = 0.6f;
-    auto sphere1 = InitSphere(*scene, 40.f, material);
+    auto sphere1 = InitSphere(*scene, 40.f, material, solid);
     material.AlbedoColor = VColor::BLUE;
     auto sphere2 = InitSphere(*scene, 20.f, material);
     const VVector rel1(200.f, 0.f, 100.f), rel2(100.f, 0.f, 200.f);
@@ -155,6 +166,22 @@ int main(int argc, char** argv) {
     if (pick && (!hip || block > 0)) {
         fprintf(stderr, "--pick asks the HIP renderer once per frame: drop --block\n");
         return 1;
+    }
+    if (solid && !hip) {
+        fprintf(stderr, "--solid fills on the device: it needs the HIP renderer\n");
+        return 1;
+    }
+    if (solid) { /* uploads the scene, fills every volume's cavities in place; the host mirrors follow, so nothing is left dirty */
+        unsigned long long filled = 0;
+        for (const auto& placed : scene->GetAllPlacedObjects()) {
+            auto object = std::dynamic_pointer_cast<Scene::VVoxelObject>(placed);
+            if (!object || !object->GetVoxelVolume()) continue;
+            vrt_fill_result res;
+            if (!hip->FillEnclosed(*object, 1.f, 1, &res)) return 1;
+            filled += res.filled;
+        }
+        scene->PostRender();
+        printf("solid: %llu enclosed voxels filled on the device\n", filled);
     }
     double kernel_ms = 0.0;
     bool warmUp = true; /* the untimed first frame prints no pick record */

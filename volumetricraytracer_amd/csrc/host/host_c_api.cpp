@@ -84,6 +84,23 @@ int vrh_voxelize_file(const char* gltf_path, const char* texlib_or_null, const c
     }
 }
 
+/* VVolumeConverter::FillEnclosed on caller records: n^3 VVoxel records (index x*n*n + z*n + y), edited in place; result_or_null as
+   vrt_volume_fill_enclosed reports (sweeps 0).  0 / -1. */
+int vrh_fill_enclosed(vrt_voxel* voxels, int n, float wall, int material, vrt_fill_result* result_or_null) {
+    static_assert(sizeof(Voxel::VVoxel) == sizeof(vrt_voxel), "VVoxel must match the wire record");
+    if (!voxels || n < 1 || !(wall >= 0.f) || wall > 3.402823466e38f || material < -1 || material > 255) {
+        g_error = "vrh_fill_enclosed: bad argument";
+        return -1;
+    }
+    const auto r = Voxelizer::VVolumeConverter::FillEnclosed(reinterpret_cast<Voxel::VVoxel*>(voxels), (size_t)n, wall, material);
+    if (result_or_null)
+        *result_or_null = vrt_fill_result{{r.Lo.X, r.Lo.Y, r.Lo.Z}, {r.Hi.X, r.Hi.Y, r.Hi.Z}, (uint64_t)r.Filled, 0, 0};
+    return 0;
+}
+
+/* The converter's switch behind `voxelizer --solid`: volumes converted from now on are filled (wall 1, material 1). */
+void vrh_make_solid(int solid) { Voxelizer::VVolumeConverter::MakeSolid(solid != 0); }
+
 /* Load a .vox scene with the C++ reader and write it back with the C++ writer. */
 int vrh_vox_rewrite(const char* in_path, const char* out_path) {
     try {

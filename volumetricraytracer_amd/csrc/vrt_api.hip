@@ -90,6 +90,7 @@ static_assert(kDynMaxInstances == VRT_MAX_INSTANCES && kMaxBvhNodes == 2 * VRT_M
 static_assert(kDynMaxPointLights == VRT_MAX_POINT_LIGHTS && kDynMaxSpotLights == VRT_MAX_SPOT_LIGHTS, "section capacity = VRT_MAX_*_LIGHTS");
 static_assert(sizeof(vrt_ray) == 32 && sizeof(vrt_hit) == 48, "query_kernel reads two and writes three 16-B words per ray");
 static_assert(sizeof(vrt_brush) == 64 && sizeof(vrt_brush_result) == 32, "vrt.h states these sizes");
+static_assert(sizeof(vrt_fill_result) == 40, "vrt.h states this size");
 static_assert(sizeof(DBrushList) <= 3072, "the brush records travel in the kernel-argument block");
 
 constexpr int kStatSlots = 16; /* streams that may have launches in flight at once without sharing a counter buffer */
@@ -214,7 +215,10 @@ struct DeviceState {
     void* edit_scratch = nullptr;
     size_t edit_scratch_cap = 0;
     int* d_box6 = nullptr;
-    DBrushSlot* d_brush = nullptr; /* vrt_volume_apply_brushes: what the brush launch wrote (kBrushSlots partial records) */
+    DBrushSlot* d_brush = nullptr; /* vrt_volume_apply_brushes, vrt_volume_fill_enclosed: what the launch wrote (kBrushSlots partial records) */
+    /* vrt_volume_fill_enclosed: the rounds' flags, the passable mask and the exterior labels (grown on demand, shared by the slots) */
+    void* fill_scratch = nullptr;
+    size_t fill_scratch_cap = 0;
     /* vrt_trace_rays_host: the rays and then the hit records of a batch (grown on demand) */
     void* query_buf = nullptr;
     size_t query_cap = 0;
@@ -540,6 +544,7 @@ void destroy_device(DeviceState& D) {
     if (D.edit_scratch) (void)hipFree(D.edit_scratch);
     if (D.d_box6) (void)hipFree(D.d_box6);
     if (D.d_brush) (void)hipFree(D.d_brush);
+    if (D.fill_scratch) (void)hipFree(D.fill_scratch);
     if (D.query_buf) (void)hipFree(D.query_buf);
     if (D.d_vols) (void)hipFree(D.d_vols);
     if (D.d_inst) (void)hipFree(D.d_inst);
@@ -922,6 +927,70 @@ int apply_brushes(vrt_ctx* ctx, int slot, int n_rec, const vrt_brush* rec, vrt_b
         if (rc != VRT_OK) return rc;
     }
     if (!density_changed) return VRT_OK;
+    ctx->scene_stale = true;
+    return sync_volume_table(ctx);
+}
+
+/* vrt_volume_fill_enclosed: per device, the passable mask and the face seeds (launch_fill_mask), propagation rounds in batches of
+ * kFillRoundsPerRead with one read of their flags per batch until a round labels nothing, then the edit of the samples left without a
+ * label (launch_fill_apply), which reports like a brush launch; what the slot derives from the samples is recomputed over the written
+ * box (rebuild_derived).  Afterwards every buffer equals what upload_volume builds from the filled volume. */
+int fill_enclosed(vrt_ctx* ctx, int slot, float wall, int material, vrt_fill_result* result) {
+    if (!ctx) return VRT_ERR_INVALID;
+    if (!valid_slot(slot) || !ctx->vol[slot].used) return VRT_ERR_SLOT;
+    if (!std::isfinite(wall) || wall < 0.f || material < -1 || material > 255) return VRT_ERR_INVALID;
+    HostVolume& h = ctx->vol[slot];
+    const int N = h.N;
+    if (result) *result = vrt_fill_result{{N, N, N}, {-1, -1, -1}, 0, 0, 0};
+    const bool texel16 = h.format == VRT_FORMAT_TEXEL16;
+    /* a round that changes something labels at least one sample, so no run needs more rounds than the grid has samples */
+    const unsigned long long round_cap = (unsigned long long)N * N * N + 1ull;
+    for (auto& D : ctx->dev) { /* frames already enqueued render the old volume */
+        HIP_TRY(hipSetDevice(D.ordinal));
+        HIP_TRY(hipDeviceSynchronize());
+    }
+    bool any_filled = false;
+    for (size_t di = 0; di < ctx->dev.size(); di++) {
+        DeviceState& D = ctx->dev[di];
+        HIP_TRY(hipSetDevice(D.ordinal));
+        DeviceVolume& v = D.vol[slot];
+        int rc = ensure_buffer(D.fill_scratch, D.fill_scratch_cap, fill_scratch_bytes(N));
+        if (rc != VRT_OK) return rc;
+        if (!D.d_brush) HIP_TRY(hipMalloc(&D.d_brush, kBrushSlots * sizeof(DBrushSlot)));
+        HIP_TRY(launch_fill_mask(v.dense, texel16, N, D.fill_scratch, D.stream));
+        unsigned long long rounds = 0;
+        for (bool settled = false; !settled;) {
+            if (rounds >= round_cap) {
+                fprintf(stderr, "[vrt] vrt_volume_fill_enclosed: %llu rounds without settling on a grid of %d^3\n", rounds, N);
+                return VRT_ERR_HIP;
+            }
+            int flags[kFillRoundsPerRead];
+            HIP_TRY(launch_fill_rounds(N, D.fill_scratch, kFillRoundsPerRead, D.stream));
+            HIP_TRY(hipMemcpyAsync(flags, fill_round_flags(D.fill_scratch), sizeof flags, hipMemcpyDeviceToHost, D.stream));
+            HIP_TRY(hipStreamSynchronize(D.stream));
+            rounds += kFillRoundsPerRead;
+            for (int f : flags) settled = settled || f == 0;
+        }
+        HIP_TRY(launch_fill_apply(texel16, v.dense, v.material, N, D.fill_scratch, wall, material, D.d_brush, D.stream));
+        DBrushSlot part[kBrushSlots];
+        HIP_TRY(hipMemcpyAsync(part, D.d_brush, sizeof part, hipMemcpyDeviceToHost, D.stream));
+        HIP_TRY(hipStreamSynchronize(D.stream));
+        vrt_fill_result got = {{N, N, N}, {-1, -1, -1}, 0, (uint32_t)std::min<unsigned long long>(rounds, 0xffffffffull), 0}; /* the partial records merged */
+        for (const DBrushSlot& p : part) {
+            for (int a = 0; a < 3; a++) {
+                got.lo[a] = std::min(got.lo[a], N - (int)p.inv_lo[a]);
+                got.hi[a] = std::max(got.hi[a], (int)p.hi1[a] - 1);
+            }
+            got.filled += p.counts & 0xffffffffull;
+        }
+        if (di == 0 && result) *result = got;
+        if (got.filled == 0) continue;
+        any_filled = true;
+        const DerivedBoxes written = derived_boxes(h, got.lo, got.hi);
+        rc = rebuild_derived(ctx, D, slot, &written, false, h.abox);
+        if (rc != VRT_OK) return rc;
+    }
+    if (!any_filled) return VRT_OK;
     ctx->scene_stale = true;
     return sync_volume_table(ctx);
 }
@@ -1597,6 +1666,10 @@ int vrt_volume_update_voxels(vrt_ctx* ctx, int slot, const int origin_xyz[3], co
 
 int vrt_volume_apply_brushes(vrt_ctx* ctx, int slot, int n, const vrt_brush* brushes, vrt_brush_result* result_or_null) {
     return apply_brushes(ctx, slot, n, brushes, result_or_null);
+}
+
+int vrt_volume_fill_enclosed(vrt_ctx* ctx, int slot, float wall, int material, vrt_fill_result* result_or_null) {
+    return fill_enclosed(ctx, slot, wall, material, result_or_null);
 }
 
 int vrt_volume_download_region(vrt_ctx* ctx, int slot, const int origin_xyz[3], const int size_xyz[3], vrt_voxel* out) {

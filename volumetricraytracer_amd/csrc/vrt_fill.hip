@@ -1,0 +1,183 @@
+/* vrt_fill.hip — the kernels of vrt_volume_fill_enclosed (include/vrt.h): which passable samples (d > 0) of a resident volume the
+ * grid's faces cannot reach through 6-neighbour steps over passable samples, and the edit that turns them solid.
+ *
+ * Labels ("exterior") live in a scratch buffer next to the passable mask, both as bits: a row of samples along y is row_bytes(N)
+ * bytes, sample y at bit y & 7 of byte y >> 3 — an 8^3 tile owns one byte of each of its 64 rows.  Labels only ever go from 0 to 1 and
+ * a byte is written by its tile alone, so a tile that reads a neighbour's byte while that neighbour runs sees an older or a newer
+ * state of a set that only grows towards the same fixed point: every order of the workgroups gives the same labels.  There is no wait
+ * on another workgroup anywhere: convergence comes from the host launching rounds until one changes nothing. */
+#include <hip/hip_runtime.h>
+
+#include <algorithm>
+
+#include "fill_core.h"
+#include "vrt_launch.h"
+
+namespace vrt {
+
+namespace {
+
+using vrt_fill::kTile;
+
+constexpr size_t kFlagBytes = 256; /* the rounds' flags, ahead of the two bit grids */
+static_assert(kFillRoundsPerRead * sizeof(int) <= kFlagBytes, "one flag per round of a batch");
+
+/* Passable mask of every row byte, and the seeds: the passable samples with an index 0 or N - 1 on some axis.  One lane per byte:
+ * 8 consecutive samples along y. */
+__global__ __launch_bounds__(256) void fill_mask_kernel(const float* __restrict__ dense, int texel16, int N, uint8_t* __restrict__ pas,
+                                                        uint8_t* __restrict__ lab) {
+    const int T = vrt_fill::row_bytes(N);
+    const size_t count = (size_t)N * N * T;
+    size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    const size_t stride = (size_t)gridDim.x * blockDim.x;
+    for (; i < count; i += stride) {
+        const size_t row = i / (size_t)T; /* x * N + z */
+        const int t = (int)(i % (size_t)T);
+        const int x = (int)(row / (size_t)N), z = (int)(row % (size_t)N);
+        unsigned p = 0u;
+        for (int k = 0; k < kTile; k++) {
+            const int y = t * kTile + k;
+            if (y >= N) break;
+            const float s = dense[row * N + y];
+            p |= vrt_fill::passable(texel16 ? s * 0.01f : s) ? 1u << k : 0u;
+        }
+        unsigned face = 0xffu;
+        if (x > 0 && x < N - 1 && z > 0 && z < N - 1) face = (t == 0 ? 1u : 0u) | (t == (N - 1) / kTile ? 1u << ((N - 1) % kTile) : 0u);
+        pas[i] = (uint8_t)p;
+        lab[i] = (uint8_t)(p & face);
+    }
+}
+
+/* One round: one workgroup (one wave) per 8^3 tile.  The tile's 64 rows and the rows one sample around them come into LDS as 10-bit
+ * columns — bit 0 the sample below the tile, bits 1..8 the tile's, bit 9 the one above —, lane lx * 8 + lz owns row (lx, lz); the tile
+ * then propagates labels over its own passable samples until nothing changes, writes the rows that changed and raises the round's flag.
+ * A tile without an unlabelled passable sample leaves at once. */
+constexpr int kHalo = kTile + 2;
+__global__ __launch_bounds__(64) void fill_round_kernel(int N, const uint8_t* __restrict__ pas, uint8_t* lab, int* __restrict__ flag) {
+    const int T = vrt_fill::row_bytes(N);
+    const int ty = (int)blockIdx.x, tz = (int)blockIdx.y, tx = (int)blockIdx.z;
+    const int l = (int)threadIdx.x, lx = l >> 3, lz = l & 7;
+    const int x = tx * kTile + lx, z = tz * kTile + lz;
+    const bool inside = x < N && z < N;
+    const size_t mine_at = ((size_t)x * N + z) * T + ty;
+    const unsigned passm = inside ? (unsigned)pas[mine_at] << 1 : 0u;
+    const unsigned loaded = inside ? (unsigned)lab[mine_at] << 1 : 0u;
+    if (!__any((passm & ~loaded) != 0u)) return;
+
+    __shared__ unsigned col[kHalo * kHalo];
+    for (int c = l; c < kHalo * kHalo; c += 64) {
+        const int cx = tx * kTile + c / kHalo - 1, cz = tz * kTile + c % kHalo - 1;
+        unsigned w = 0u;
+        if (cx >= 0 && cx < N && cz >= 0 && cz < N) {
+            const uint8_t* row = lab + ((size_t)cx * N + cz) * T;
+            w = (unsigned)row[ty] << 1;
+            if (ty > 0) w |= (unsigned)row[ty - 1] >> 7;
+            if (ty + 1 < T) w |= ((unsigned)row[ty + 1] & 1u) << 9;
+        }
+        col[c] = w;
+    }
+    __syncthreads();
+    const int own = (lx + 1) * kHalo + (lz + 1);
+    unsigned mine = col[own];
+    bool tile_changed = false;
+    for (int it = 0; it <= kTile * kTile * kTile; it++) { /* every pass but the last labels a sample: at most 8^3 of them */
+        const unsigned around = col[own - kHalo] | col[own + kHalo] | col[own - 1] | col[own + 1];
+        unsigned cur = mine | (around & passm);
+#pragma unroll
+        for (int k = 0; k < kTile; k++) cur |= ((cur << 1) | (cur >> 1)) & passm; /* along y, from the tile's and the halo's bits */
+        const bool changed = cur != mine;
+        if (!__any(changed)) break;
+        __syncthreads(); /* every lane has read this pass's columns */
+        if (changed) col[own] = mine = cur;
+        tile_changed = true;
+        __syncthreads();
+    }
+    if (!tile_changed) return;
+    if (((mine ^ loaded) & 0x1feu) != 0u) lab[mine_at] = (uint8_t)(mine >> 1); /* never outside the grid: passm is 0 there */
+    if (l == 0) *flag = 1;
+}
+
+/* One lane per sample, y fastest like the dense grid: an enclosed sample (passable, not labelled) stores m = -(d + wall) — its texel in
+ * a TEXEL16 slot — and, with material_id >= 0, that id.  Counts and box are reduced across the wave and reported like the brushes'. */
+template <bool TEXEL16>
+__global__ __launch_bounds__(256) void fill_apply_kernel(float* __restrict__ dense, uint8_t* __restrict__ material, int N,
+                                                         const uint8_t* __restrict__ pas, const uint8_t* __restrict__ lab, float wall,
+                                                         int material_id, DBrushSlot* __restrict__ slots) {
+    const int T = vrt_fill::row_bytes(N);
+    const size_t count = (size_t)N * N * N;
+    size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    const size_t stride = (size_t)gridDim.x * blockDim.x;
+    unsigned inv_lo_x = 0u, inv_lo_y = 0u, inv_lo_z = 0u, hi1_x = 0u, hi1_y = 0u, hi1_z = 0u; /* N - lowest, 1 + highest: 0 = none */
+    unsigned n_written = 0u;
+    for (; i < count; i += stride) {
+        const size_t row = i / (size_t)N;
+        const int y = (int)(i % (size_t)N);
+        const size_t at = row * T + (size_t)(y / kTile);
+        if ((((unsigned)pas[at] & ~(unsigned)lab[at]) >> (y % kTile) & 1u) == 0u) continue;
+        const int x = (int)(row / (size_t)N), z = (int)(row % (size_t)N);
+        const float stored = dense[i];
+        const float m = vrt_fill::filled_density(TEXEL16 ? stored * 0.01f : stored, wall);
+        dense[i] = TEXEL16 ? vrt_fill::texel16_value(m) : m;
+        if (material_id >= 0) material[i] = (uint8_t)material_id;
+        n_written++;
+        inv_lo_x = max(inv_lo_x, (unsigned)(N - x)), inv_lo_y = max(inv_lo_y, (unsigned)(N - y)), inv_lo_z = max(inv_lo_z, (unsigned)(N - z));
+        hi1_x = max(hi1_x, (unsigned)(x + 1)), hi1_y = max(hi1_y, (unsigned)(y + 1)), hi1_z = max(hi1_z, (unsigned)(z + 1));
+    }
+    for (int o = 32; o > 0; o >>= 1) {
+        n_written += __shfl_xor(n_written, o);
+        inv_lo_x = max(inv_lo_x, __shfl_xor(inv_lo_x, o)), inv_lo_y = max(inv_lo_y, __shfl_xor(inv_lo_y, o));
+        inv_lo_z = max(inv_lo_z, __shfl_xor(inv_lo_z, o));
+        hi1_x = max(hi1_x, __shfl_xor(hi1_x, o)), hi1_y = max(hi1_y, __shfl_xor(hi1_y, o)), hi1_z = max(hi1_z, __shfl_xor(hi1_z, o));
+    }
+    if ((threadIdx.x & 63u) == 0u && n_written != 0u) {
+        DBrushSlot* slot = slots + ((blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6)) & (unsigned)(kBrushSlots - 1));
+        atomicAdd(&slot->counts, ((unsigned long long)n_written << 32) | (unsigned long long)n_written); /* every write is a density write */
+        atomicMax(&slot->inv_lo[0], inv_lo_x), atomicMax(&slot->inv_lo[1], inv_lo_y), atomicMax(&slot->inv_lo[2], inv_lo_z);
+        atomicMax(&slot->hi1[0], hi1_x), atomicMax(&slot->hi1[1], hi1_y), atomicMax(&slot->hi1[2], hi1_z);
+    }
+}
+
+size_t bits_bytes(int N) { return (size_t)N * N * vrt_fill::row_bytes(N); }
+uint8_t* pas_of(void* scratch) { return static_cast<uint8_t*>(scratch) + kFlagBytes; }
+uint8_t* lab_of(void* scratch, int N) { return pas_of(scratch) + bits_bytes(N); }
+unsigned stride_grid(size_t count) { return (unsigned)std::max<size_t>(1, std::min<size_t>((count + 255) / 256, 1u << 16)); }
+
+}  // namespace
+
+size_t fill_scratch_bytes(int N) { return kFlagBytes + 2 * bits_bytes(N); }
+
+const int* fill_round_flags(const void* scratch) { return static_cast<const int*>(scratch); }
+
+hipError_t launch_fill_mask(const float* dense, bool texel16, int N, void* scratch, hipStream_t stream) {
+    hipLaunchKernelGGL(fill_mask_kernel, dim3(stride_grid(bits_bytes(N))), dim3(256), 0, stream, dense, (int)texel16, N, pas_of(scratch),
+                       lab_of(scratch, N));
+    return hipGetLastError();
+}
+
+hipError_t launch_fill_rounds(int N, void* scratch, int rounds, hipStream_t stream) {
+    if (rounds < 1 || rounds > kFillRoundsPerRead) return hipErrorInvalidValue;
+    hipError_t e = hipMemsetAsync(scratch, 0, kFlagBytes, stream);
+    if (e != hipSuccess) return e;
+    const unsigned T = (unsigned)vrt_fill::row_bytes(N);
+    for (int r = 0; r < rounds; r++)
+        hipLaunchKernelGGL(fill_round_kernel, dim3(T, T, T), dim3(64), 0, stream, N, pas_of(scratch), lab_of(scratch, N),
+                           static_cast<int*>(scratch) + r);
+    return hipGetLastError();
+}
+
+hipError_t launch_fill_apply(bool texel16, float* dense, uint8_t* material, int N, const void* scratch, float wall, int material_id,
+                             DBrushSlot* slots, hipStream_t stream) {
+    hipError_t e = hipMemsetAsync(slots, 0, kBrushSlots * sizeof(DBrushSlot), stream);
+    if (e != hipSuccess) return e;
+    void* s = const_cast<void*>(scratch);
+    const unsigned grid = stride_grid((size_t)N * N * N);
+    if (texel16)
+        hipLaunchKernelGGL(fill_apply_kernel<true>, dim3(grid), dim3(256), 0, stream, dense, material, N, pas_of(s), lab_of(s, N), wall,
+                           material_id, slots);
+    else
+        hipLaunchKernelGGL(fill_apply_kernel<false>, dim3(grid), dim3(256), 0, stream, dense, material, N, pas_of(s), lab_of(s, N), wall,
+                           material_id, slots);
+    return hipGetLastError();
+}
+
+}  // namespace vrt

@@ -98,4 +98,20 @@ hipError_t launch_brush_region(const DBrushList& list, bool texel16, float* dens
 hipError_t launch_gather_region(const float* dense, const uint8_t* material, bool texel16, int N, const EditBox& box, void* voxels_out,
                                 hipStream_t stream);
 
+
+/* vrt_volume_fill_enclosed (vrt_fill.hip).  scratch: fill_scratch_bytes(N) of device memory holding the flags of a batch of rounds, the
+   passable mask and the exterior labels (one bit per sample each), valid from launch_fill_mask to launch_fill_apply. */
+constexpr int kFillRoundsPerRead = 8; /* propagation rounds enqueued between two reads of their flags: one stream sync per batch */
+size_t fill_scratch_bytes(int N);
+/* The mask of the samples with d > 0 (a TEXEL16 field decoded) and the seeds: those of them on a face of the grid. */
+hipError_t launch_fill_mask(const float* dense, bool texel16, int N, void* scratch, hipStream_t stream);
+/* `rounds` (1 .. kFillRoundsPerRead) propagation rounds, one workgroup per 8^3 tile each; round r sets fill_round_flags(scratch)[r]
+   (device memory, zeroed first) when it labelled a sample.  A round that labelled none has reached the exterior set. */
+hipError_t launch_fill_rounds(int N, void* scratch, int rounds, hipStream_t stream);
+const int* fill_round_flags(const void* scratch);
+/* Every passable sample without a label stores -(d + wall) (its texel when texel16) and, material_id >= 0, that id; slots: zeroed, then
+   the written samples' counts and box as launch_brush_region reports them. */
+hipError_t launch_fill_apply(bool texel16, float* dense, uint8_t* material, int N, const void* scratch, float wall, int material_id,
+                             DBrushSlot* slots, hipStream_t stream);
+
 }  // namespace vrt

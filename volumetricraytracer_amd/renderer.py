@@ -235,14 +235,32 @@ class VHipRenderer:
         _abi.check(self._lib.vrt_volume_apply_brushes(self._ctx, slot, len(brushes), arr, C.byref(res)), "vrt_volume_apply_brushes")
         lo, hi = tuple(res.lo), tuple(res.hi)
         if res.written and vol is not None:
-            d, m = self.download_region(slot, lo, hi)
-            (x0, y0, z0), (x1, y1, z1) = lo, hi
-            for name in ("density", "material_id"):
-                if not getattr(vol, name).flags.writeable:
-                    setattr(vol, name, np.array(getattr(vol, name)))
-            vol.density[x0:x1 + 1, z0:z1 + 1, y0:y1 + 1] = d
-            vol.material_id[x0:x1 + 1, z0:z1 + 1, y0:y1 + 1] = m
+            self._mirror_box(slot, vol, lo, hi)
         return {"written": int(res.written), "lo": lo, "hi": hi}
+
+    def _mirror_box(self, slot: int, vol: VVoxelVolume, lo, hi) -> None:
+        """The voxels lo..hi of the slot on device 0 into the host mirror `vol` (download_region), dirty / dirty_box untouched."""
+        d, m = self.download_region(slot, lo, hi)
+        (x0, y0, z0), (x1, y1, z1) = lo, hi
+        for name in ("density", "material_id"):
+            if not getattr(vol, name).flags.writeable:
+                setattr(vol, name, np.array(getattr(vol, name)))
+        vol.density[x0:x1 + 1, z0:z1 + 1, y0:y1 + 1] = d
+        vol.material_id[x0:x1 + 1, z0:z1 + 1, y0:y1 + 1] = m
+
+    def fill_enclosed(self, slot: int, vol: Optional[VVoxelVolume], wall: float = 1.0, material: int = -1) -> dict:
+        """vrt_volume_fill_enclosed: every cavity the volume resident in `slot` encloses (samples with density > 0 that the grid's
+        faces cannot reach through 6-neighbour steps over such samples) made solid on the device: -(density + wall), and `material`
+        as material id unless it is -1.  wall = 1 and material = 1 suit Voxelizer shells.  Given a host mirror `vol`, its written box
+        is then read back as apply_brushes does.  Returns {"filled", "lo", "hi", "sweeps"} (xyz, inclusive; lo > hi when nothing was
+        filled)."""
+        self._require()
+        res = _abi.vrt_fill_result()
+        _abi.check(self._lib.vrt_volume_fill_enclosed(self._ctx, slot, float(wall), int(material), C.byref(res)), "vrt_volume_fill_enclosed")
+        lo, hi = tuple(res.lo), tuple(res.hi)
+        if res.filled and vol is not None:
+            self._mirror_box(slot, vol, lo, hi)
+        return {"filled": int(res.filled), "lo": lo, "hi": hi, "sweeps": int(res.sweeps)}
 
     def download_region(self, slot: int, lo, hi):
         """vrt_volume_download_region: the voxels lo..hi (inclusive xyz corners) of the slot on device 0 as (density float32,

@@ -39,6 +39,8 @@ def load_host() -> C.CDLL:
         lib.vrh_volume_free.argtypes = [C.c_void_p]
         lib.vrh_voxelize_file.restype = C.c_int
         lib.vrh_voxelize_file.argtypes = [C.c_char_p, C.c_char_p, C.c_char_p, C.c_char_p, C.c_size_t]
+        lib.vrh_fill_enclosed.restype = C.c_int
+        lib.vrh_fill_enclosed.argtypes = [C.c_void_p, C.c_int, C.c_float, C.c_int, C.POINTER(_abi.vrt_fill_result)]
         lib.vrh_vox_rewrite.restype = C.c_int
         lib.vrh_vox_rewrite.argtypes = [C.c_char_p, C.c_char_p]
         _host = lib
@@ -72,6 +74,25 @@ def convert_mesh(positions: np.ndarray, indices: np.ndarray, bounds_extends, mes
         return vol
     finally:
         lib.vrh_volume_free(h)
+
+
+def fill_enclosed_host(vol: VVoxelVolume, wall: float = 1.0, material: int = -1) -> dict:
+    """VVolumeConverter::FillEnclosed (the host build of vrt_volume_fill_enclosed's rule) on a volume's densities and material ids, in
+    place: every sample with density > 0 that a 6-connected flood from the grid's faces over such samples does not reach gets
+    -(density + wall) and, unless material is -1, that material id.  Returns {"filled", "lo", "hi"} (xyz, inclusive; lo > hi when
+    nothing was filled)."""
+    lib = load_host()
+    rec = np.zeros(vol.N ** 3, dtype=np.dtype([("material", "u1"), ("pad", "u1", 3), ("density", "<f4")]))
+    rec["density"] = np.asarray(vol.density, np.float32).reshape(-1)
+    rec["material"] = np.asarray(vol.material_id, np.uint8).reshape(-1)
+    res = _abi.vrt_fill_result()
+    if lib.vrh_fill_enclosed(rec.ctypes.data, vol.N, float(wall), int(material), C.byref(res)) != 0:
+        raise RuntimeError("vrh_fill_enclosed: " + lib.vrh_last_error().decode(errors="replace"))
+    if res.filled:
+        vol.density = np.ascontiguousarray(rec["density"].reshape(vol.N, vol.N, vol.N))
+        vol.material_id = np.ascontiguousarray(rec["material"].reshape(vol.N, vol.N, vol.N))
+        vol.dirty = True
+    return {"filled": int(res.filled), "lo": tuple(res.lo), "hi": tuple(res.hi)}
 
 
 def voxelize_file(gltf_path: str, out_path: str | None = None, texlib: str | None = None) -> str:
