@@ -22,6 +22,8 @@
  *   vrt_volume_download_region      sphere / box / capsule brushes evaluated on the resident volume, and the read-back of a box)
  *   vrt_volume_fill_enclosed        (no reference analogue: its Voxelizer stops at the unsigned shell, Voxelizer/Private/VolumeConverter.cpp:30-84 —
  *                                   the shell of a closed mesh made solid on the resident volume, so that a SUBTRACT brush carves a solid)
+ *   vrt_volume_redistance           (no reference analogue: whatever field the resident volume holds rewritten, within a band, as the
+ *                                   signed distance to its own zero surface — what ADD brushes, blends and offsets assume)
  *   vrt_volume_free                 VRDXScene::RemoveVoxelVolume  Renderer/DX/Private/RDXScene.cpp:663-701
  *   vrt_env_upload                  VRDXScene::InitEnvironmentMap RDXScene.cpp:181-199
  *   vrt_scene_set                   VRDXScene::SyncWithScene + PrepareForRendering
@@ -412,9 +414,80 @@ typedef struct vrt_fill_result {      /* 40 B */
  * crossings; a cavity point at distance s from the mesh holds f = s/thr - 0.5 and lies (f + 1) * thr below the OUTER crossing.
  * What the call does not do: the wall's own samples on the inner side of the mesh keep their shell values -0.5..0 where a signed
  * field would hold -1..-0.5.  All of the interior is negative afterwards — nothing renders inside and a carve shows a solid — but
- * where a brush surface meets the former inner crossing the carved surface can sit a fraction of a cell off.  Redistancing the wall
- * is a separate pass. */
+ * where a brush surface meets the former inner crossing the carved surface can sit a fraction of a cell off.
+ * vrt_volume_redistance(band, VRT_REDISTANCE_FROM_OUTSIDE) afterwards turns wall and interior into a signed distance. */
 int vrt_volume_fill_enclosed(vrt_ctx* ctx, int slot, float wall, int material, vrt_fill_result* result_or_null);
+
+/* True signed distances (no reference analogue).  The Voxelizer's field is a scaled unsigned shell, valid some two cells around the
+ * mesh and a background constant elsewhere; vrt_volume_fill_enclosed leaves a jump at the former inner crossing and a wall that runs
+ * the wrong way; a sequence of min / max brushes leaves no distance field either.  An ADD brush, any blend > 0 and any offset (d - r)
+ * are only right on a true signed distance field.  This call turns whatever the slot holds into the signed distance to its own zero
+ * surface, within a band, in place. */
+enum { VRT_REDISTANCE_FROM_BOTH = 0, VRT_REDISTANCE_FROM_OUTSIDE = 1, VRT_REDISTANCE_FROM_INSIDE = 2 };
+typedef struct vrt_redistance_result { /* 48 B */
+    int32_t lo[3], hi[3];             /* xyz, inclusive: the samples written (the clipped box); lo > hi when none */
+    uint64_t written;                 /* samples written */
+    uint64_t near;                    /* of those, samples whose distance came out below the band */
+    uint32_t surfels;                 /* surfels among the samples of the box grown by band + 1, clipped to the grid */
+    uint32_t reserved_;
+} vrt_redistance_result;
+
+/* Redistances the samples of a box of the resident slot, in place, on every device.  Both box pointers NULL: the whole grid;
+ * otherwise [origin, origin + size) as vrt_volume_update_region takes it.  Waits for work already enqueued on the context's devices
+ * (a frame begun before the call renders the old volume, one begun after renders the new one); device pointers of the slot do not
+ * change.  Afterwards every device buffer of the slot equals what a full upload of the edited volume holds (what the slot derives
+ * from its samples is rebuilt over the written box), so frames and counters are those of the full upload.  A launch captured into a
+ * graph before the call keeps the cull rectangle it was captured with, as for the other edits.  Material ids are never touched and
+ * the slot's metric (vrt_volume_set_metric) is left alone.
+ * Errors, all checked before any device state is touched: VRT_ERR_INVALID for a NULL context; VRT_ERR_SLOT for an unused slot;
+ * VRT_ERR_INVALID for a band outside 1..15, an unknown `from`, one box pointer NULL and the other not, or a box that
+ * vrt_volume_update_region would refuse.  VRT_ERR_OOM when the scratch memory (the surfels) cannot be allocated: the volume is
+ * untouched then.
+ * result_or_null: from device 0 (all devices compute the same bytes).
+ *
+ * The rule is part of the contract.  All arithmetic is fp32, evaluated as parenthesised, no fused multiply-add; sqrtf and / are
+ * correctly rounded; dot(u,v) = (u.x*v.x + u.y*v.y) + u.z*v.z.  Coordinates are grid coordinates, ((float)ix, (float)iy, (float)iz);
+ * lengths are in cells.
+ *   1. Decode and class.  d is the sample's density as for the brushes: the stored float, or stored * 0.01f (VRT_FORMAT_TEXEL16).
+ *      e = -0.0f when d is NaN, else fminf(fmaxf(d, -1e18f), 1e18f).  A sample is OUTSIDE when e > 0, else INSIDE; sigma = +1
+ *      outside, -1 inside; phi = sigma * e (>= 0).
+ *   2. Interface samples and surfels.  An interface sample has a 6-neighbour (one index +-1) inside the grid of the other class.
+ *      With from = VRT_REDISTANCE_FROM_OUTSIDE only outside interface samples make a surfel, with _FROM_INSIDE only inside ones,
+ *      with _FROM_BOTH all of them.
+ *   3. The surfel of an interface sample q.  Per axis a, with n+ / n- the neighbours at index +1 / -1 (one beyond the grid does not
+ *      count): w+ = phi - sigma*e(n+), w- = phi - sigma*e(n-); s_a = fmaxf(fmaxf(w+, w-), 0) over the neighbours that exist;
+ *      dir_a = -1 when w- exists and w- > w+ (or w+ does not exist), else +1.  G = dot(s, s) (> 0 for an interface sample).
+ *      Centre c_a = (float)q_a + dir_a * ((phi * s_a) / G); normal n_a = dir_a * (s_a / sqrtf(G)).  This is a Godunov upwind
+ *      gradient: exact for a linear field away from the grid's faces (below), and it never looks at a neighbour whose value is further from zero than q's own.
+ *   4. Distance of a box sample p to the surfel (c, n): the distance to a disc of radius 0.75 around c.  v = p - c; h = dot(v, n);
+ *      vv = dot(v, v); r = sqrtf(fmaxf(vv - h*h, 0)); u = fmaxf(r - 0.75f, 0); D2 = h*h + u*u.
+ *   5. Value.  D = fminf(sqrtf(min over ALL surfels of the grid of D2), (float)band); with no surfel at all D = (float)band.
+ *      unit = cell / density_scale as for the brushes, computed once on the host.  m = D * unit for an outside sample,
+ *      -(D * unit) for an inside one.  Every sample of the box stores m (F32) or the texel of m (TEXEL16: the rule at
+ *      vrt_set_volume_format).  The sign follows the sample's class before the call: in F32 the sign bit never changes.  The class
+ *      itself can: D is 0 for a sample that lies on a disc (an outside sample next to a -1e18 neighbour is its own surfel's
+ *      centre) and stores +0, and a TEXEL16 slot stores the texel 0 for every outside sample nearer than one texel step
+ *      (m < 0.01); by rule 1 such a sample counts as inside on the next call.
+ *   (An implementation may skip any surfel whose sample lies more than band + 1 indices from p on some axis: |c - q| <= 1 per axis
+ *   and the disc's radius is 0.75, so that surfel is at least band + 0.25 cells from p and loses against the clamp.)
+ * Why `from` exists: in a Voxelizer shell only the outside of the wall is monotone.  Past the mesh the value rises again, so inside
+ * interface samples deeper than 0.87 cells below the crossing see a wrong gradient.  FROM_OUTSIDE is right for shells, filled or
+ * not; FROM_BOTH is right for true signed distance fields (it halves the error of the crossing's position).
+ * What moves: the zero surface moves by a first-order amount — on a sphere of 20.7 cells under-estimates of up to 0.040 cells and
+ * over-estimates of up to 0.019, crossings on grid edges by up to 0.046 cells (0.002 on average); DESIGN.md section 2 has the figures.
+ * Where the zero surface meets a face of the grid the result is NOT a distance: a neighbour beyond the grid does not count, so the
+ * gradient of a sample on a face lacks a component, its surfel is wrong, and samples around it can be off by more than a cell
+ * (measured on a plane oblique to all axes through a 33^3 grid, over all samples within band - 1 of it: 0.48 cells at band 3, 1.61 at
+ * band 8, 1.94 at band 15).  The "exact for a linear field" of step 3 holds for samples nearer to the surface than to a face sample's
+ * disc, |distance| < (index distance to the nearest face) - 3: there FROM_BOTH is exact to 1.2e-6 cells on that plane, and a one-sided
+ * `from`, which keeps half of the discs, is off by up to 0.0099 cells.  Keep surfaces that matter a few cells inside the grid.
+ * Under-estimates are the safe side for sphere tracing.  A second call is not a no-op in bits.
+ * Afterwards the field is a distance up to band cells from the surface, so a caller may raise the step limit:
+ * vrt_volume_set_metric(scale, step_max up to band * cell).  The call does not choose step_max for the caller.
+ * The box: samples outside it keep their bits but still make surfels, so a box around an edit (the edit's box grown by the band)
+ * repairs the field there against the surface as it is now. */
+int vrt_volume_redistance(vrt_ctx* ctx, int slot, int band, int from, const int origin_xyz_or_null[3], const int size_xyz_or_null[3],
+                          vrt_redistance_result* result_or_null);
 /* Reads the box [origin, origin+size) of device 0's slot as VVoxel records: box order as vrt_volume_update_voxels takes it, decode
  * as vrt_volume_download's.  Only the box's bytes cross the bus, so a host mirror can follow a device-side edit without a full
  * download.  Argument checks as vrt_volume_update_region's.  On a VRT_FORMAT_TEXEL16 slot the decoded values (q * 0.01f) re-quantise

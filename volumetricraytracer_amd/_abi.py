@@ -228,6 +228,13 @@ class vrt_fill_result(C.Structure):
     _fields_ = [("lo", C.c_int32 * 3), ("hi", C.c_int32 * 3), ("filled", C.c_uint64), ("sweeps", C.c_uint32), ("reserved_", C.c_uint32)]
 
 
+class vrt_redistance_result(C.Structure):
+    _fields_ = [("lo", C.c_int32 * 3), ("hi", C.c_int32 * 3), ("written", C.c_uint64), ("near", C.c_uint64), ("surfels", C.c_uint32),
+                ("reserved_", C.c_uint32)]
+
+
+REDISTANCE_FROM_BOTH, REDISTANCE_FROM_OUTSIDE, REDISTANCE_FROM_INSIDE = 0, 1, 2
+
 SYMBOLS = {
     "vrt_create": (C.c_int, [C.POINTER(C.c_void_p), C.c_int, C.POINTER(C.c_int)]),
     "vrt_destroy": (C.c_int, [C.c_void_p]),
@@ -248,6 +255,8 @@ SYMBOLS = {
     "vrt_volume_update_voxels": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int), C.c_void_p]),
     "vrt_volume_apply_brushes": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.POINTER(vrt_brush), C.POINTER(vrt_brush_result)]),
     "vrt_volume_fill_enclosed": (C.c_int, [C.c_void_p, C.c_int, C.c_float, C.c_int, C.POINTER(vrt_fill_result)]),
+    "vrt_volume_redistance": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int),
+                                        C.POINTER(vrt_redistance_result)]),
     "vrt_volume_download_region": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int), C.c_void_p]),
     "vrt_debug_volume_bytes": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_size_t, C.POINTER(C.c_size_t)]),
     "vrt_env_upload": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p]),

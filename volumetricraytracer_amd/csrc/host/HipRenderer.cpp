@@ -821,6 +821,36 @@ bool VHipRenderer::FillEnclosed(const Scene::VVoxelObject& object, float wall, i
     return MirrorBox(slot, *volume, res.lo, res.hi);
 }
 
+bool VHipRenderer::Redistance(const Scene::VVoxelObject& object, int band, int from, const VIntVector* boxLo, const VIntVector* boxHi,
+                              vrt_redistance_result* result) {
+    if (!IsActive()) {
+        V_LOG_WARNING("Redistance() on an inactive renderer");
+        return false;
+    }
+    const VObjectPtr<Scene::VScene> scene = SceneRef.lock();
+    const VObjectPtr<Voxel::VVoxelVolume> volume = object.GetVoxelVolume();
+    if (!scene || !volume || (boxLo == nullptr) != (boxHi == nullptr)) return false;
+    if (!SyncWithScene(*scene)) return false;
+    const int slot = SlotOf(volume.get());
+    if (slot < 0) {
+        V_LOG_ERROR("Redistance(): the object's volume is not part of the rendered scene");
+        return false;
+    }
+    vrt_redistance_result res;
+    if (boxLo) {
+        const int last = (int)volume->GetSize() - 1;
+        const int lo[3] = {std::max(boxLo->X, 0), std::max(boxLo->Y, 0), std::max(boxLo->Z, 0)};
+        const int size[3] = {std::min(boxHi->X, last) - lo[0] + 1, std::min(boxHi->Y, last) - lo[1] + 1, std::min(boxHi->Z, last) - lo[2] + 1};
+        if (size[0] < 1 || size[1] < 1 || size[2] < 1) return false;
+        if (!ok(vrt_volume_redistance(Ctx, slot, band, from, lo, size, &res), "vrt_volume_redistance")) return false;
+    } else if (!ok(vrt_volume_redistance(Ctx, slot, band, from, nullptr, nullptr, &res), "vrt_volume_redistance")) {
+        return false;
+    }
+    if (result) *result = res;
+    if (res.written == 0) return true;
+    return MirrorBox(slot, *volume, res.lo, res.hi);
+}
+
 bool VHipRenderer::Pick(int px, int py, vrt_hit& out) {
     const VObjectPtr<Scene::VScene> scene = SceneRef.lock();
     if (!IsActive() || !scene || px < 0 || py < 0 || (unsigned)px >= Width || (unsigned)py >= Height) return false;

@@ -126,6 +126,13 @@ public:
        filled voxels get, or -1.  The written box is read back into the host VVoxelVolume like ApplyBrushes does.  False (after
        logging) on failure or when the object's volume is not in the scene. */
     bool FillEnclosed(const Scene::VVoxelObject& object, float wall = 1.f, int material = -1, vrt_fill_result* result = nullptr);
+    /* The volume of a placed object rewritten on the device as the signed distance, within `band` cells, to its own zero surface
+       (vrt_volume_redistance; the rule: vrt.h), over the samples boxLo..boxHi (inclusive xyz indices, clamped to the grid) or the
+       whole grid without a box.  from: VRT_REDISTANCE_FROM_OUTSIDE for Voxelizer shells, filled or not, _FROM_BOTH for true distance
+       fields.  The written box is read back into the host VVoxelVolume like ApplyBrushes does.  False (after logging) on failure or
+       when the object's volume is not in the scene. */
+    bool Redistance(const Scene::VVoxelObject& object, int band, int from, const VIntVector* boxLo = nullptr, const VIntVector* boxHi = nullptr,
+                    vrt_redistance_result* result = nullptr);
 
 private:
     bool SyncWithScene(Scene::VScene& scene);

@@ -2,6 +2,7 @@
 
 #include "../../../include/vrt.h"
 #include "../fill_core.h"
+#include "../redistance_core.h"
 #include "../voxelize_core.h"
 
 #include <algorithm>
@@ -92,6 +93,81 @@ VVolumeConverter::VFillResult VVolumeConverter::FillEnclosed(Voxel::VVoxelVolume
     return out;
 }
 
+static int g_sdf_band = 0;
+void VVolumeConverter::MakeSdf(int band) { g_sdf_band = band; }
+
+VVolumeConverter::VRedistanceResult VVolumeConverter::Redistance(Voxel::VVoxel* voxels, size_t n, float unit, bool texel16, int band, int from,
+                                                                 const int lo[3], const int hi[3]) {
+    namespace R = vrt_redist;
+    const int N = (int)n, reach = R::cull_reach(band);
+    int glo[3], ghi[3]; /* the box grown by band + 1, clipped: the only samples whose surfels can reach into the box */
+    for (int a = 0; a < 3; a++) {
+        glo[a] = std::max(lo[a] - reach, 0);
+        ghi[a] = std::min(hi[a] + reach, N - 1);
+    }
+    const auto at = [&](int x, int y, int z) { return ((size_t)x * n + (size_t)z) * n + (size_t)y; };
+    const auto value = [&](int x, int y, int z) {
+        const float d = voxels[at(x, y, z)].Density;
+        return R::clamped(texel16 ? d * 0.01f : d);
+    };
+    /* the surfels, kept per row (x, z) of the grown box with their y */
+    struct Entry {
+        int y;
+        R::Surfel s;
+    };
+    const int rows_z = ghi[2] - glo[2] + 1;
+    std::vector<std::vector<Entry>> rows((size_t)(ghi[0] - glo[0] + 1) * (size_t)rows_z);
+    VRedistanceResult out;
+    for (int x = glo[0]; x <= ghi[0]; x++)
+        for (int z = glo[2]; z <= ghi[2]; z++)
+            for (int y = glo[1]; y <= ghi[1]; y++) {
+                const float e = value(x, y, z);
+                const bool is_out = R::outside(e);
+                if (from != VRT_REDISTANCE_FROM_BOTH && (from == VRT_REDISTANCE_FROM_OUTSIDE) != is_out) continue;
+                const int q[3] = {x, y, z};
+                const bool hp[3] = {x + 1 < N, y + 1 < N, z + 1 < N}, hm[3] = {x > 0, y > 0, z > 0};
+                const float ep[3] = {hp[0] ? value(x + 1, y, z) : e, hp[1] ? value(x, y + 1, z) : e, hp[2] ? value(x, y, z + 1) : e};
+                const float em[3] = {hm[0] ? value(x - 1, y, z) : e, hm[1] ? value(x, y - 1, z) : e, hm[2] ? value(x, y, z - 1) : e};
+                bool other = false;
+                for (int a = 0; a < 3; a++) other = other || R::outside(ep[a]) != is_out || R::outside(em[a]) != is_out;
+                if (!other) continue;
+                rows[(size_t)(x - glo[0]) * (size_t)rows_z + (size_t)(z - glo[2])].push_back(Entry{y, R::surfel_of(q, e, ep, em, hp, hm)});
+                out.Surfels++;
+            }
+    /* every surfel is known: the samples can be overwritten one by one, each after its own class has been read */
+    out.Lo = VIntVector(lo[0], lo[1], lo[2]);
+    out.Hi = VIntVector(hi[0], hi[1], hi[2]);
+    for (int x = lo[0]; x <= hi[0]; x++)
+        for (int z = lo[2]; z <= hi[2]; z++)
+            for (int y = lo[1]; y <= hi[1]; y++) {
+                float best = INFINITY;
+                for (int sx = std::max(x - reach, glo[0]); sx <= std::min(x + reach, ghi[0]); sx++)
+                    for (int sz = std::max(z - reach, glo[2]); sz <= std::min(z + reach, ghi[2]); sz++)
+                        for (const Entry& s : rows[(size_t)(sx - glo[0]) * (size_t)rows_z + (size_t)(sz - glo[2])]) {
+                            if (s.y < y - reach || s.y > y + reach) continue;
+                            best = fminf(best, R::disc_d2((float)x, (float)y, (float)z, s.s.c[0], s.s.c[1], s.s.c[2], s.s.n[0], s.s.n[1], s.s.n[2]));
+                        }
+                const bool is_out = R::outside(value(x, y, z));
+                const float D = R::banded(best, band);
+                const float m = R::signed_value(D, unit, is_out);
+                voxels[at(x, y, z)].Density = texel16 ? vrt_fill::texel16_value(m) : m;
+                out.Written++;
+                if (D < (float)band) out.Near++;
+            }
+    return out;
+}
+
+VVolumeConverter::VRedistanceResult VVolumeConverter::Redistance(Voxel::VVoxelVolume& volume, int band, int from, const VIntVector* boxLo,
+                                                                 const VIntVector* boxHi) {
+    const int last = (int)volume.GetSize() - 1;
+    const int lo[3] = {boxLo ? boxLo->X : 0, boxLo ? boxLo->Y : 0, boxLo ? boxLo->Z : 0};
+    const int hi[3] = {boxHi ? boxHi->X : last, boxHi ? boxHi->Y : last, boxHi ? boxHi->Z : last};
+    const float unit = volume.GetCellSize() / volume.DensityScale;
+    const VRedistanceResult out = Redistance(volume.GetVoxels().data(), volume.GetSize(), unit, false, band, from, lo, hi);
+    volume.MakeDirty();
+    return out;
+}
+
 bool VVolumeConverter::ExtractResolutionFromName(const std::string& name, uint8_t& outResolution) {
     const size_t at = name.rfind('_');
     if (at == std::string::npos) return false;
@@ -143,6 +219,10 @@ std::shared_ptr<Voxel::VVoxelVolume> VVolumeConverter::ConvertMeshInfoToVoxelVol
         static_assert(sizeof(Voxel::VVoxel) == sizeof(vrt_voxel), "VVoxel must match the wire record");
         int rc = vrt_voxelize_mesh(g_device_ctx, kScratchSlot, resolution, extends, pos.data(), meshInfo.Vertices.size(), idx.data(), idx.size(), &skipped);
         if (rc == VRT_OK && g_solid) rc = vrt_volume_fill_enclosed(g_device_ctx, kScratchSlot, 1.f, 1, nullptr);
+        if (rc == VRT_OK && g_sdf_band > 0) { /* lengths in the shell's own metric, density * thr */
+            rc = vrt_volume_set_metric(g_device_ctx, kScratchSlot, threshold, 0.5f * threshold);
+            if (rc == VRT_OK) rc = vrt_volume_redistance(g_device_ctx, kScratchSlot, g_sdf_band, VRT_REDISTANCE_FROM_OUTSIDE, nullptr, nullptr, nullptr);
+        }
         if (rc == VRT_OK) rc = vrt_volume_download(g_device_ctx, kScratchSlot, reinterpret_cast<vrt_voxel*>(volume->GetVoxels().data()));
         if (rc == VRT_OK) {
             (void)vrt_volume_free(g_device_ctx, kScratchSlot);
@@ -168,6 +248,10 @@ std::shared_ptr<Voxel::VVoxelVolume> VVolumeConverter::ConvertMeshInfoToVoxelVol
         voxelize_face(*volume, t, threshold);
     }
     if (g_solid && !on_device) FillEnclosed(*volume, 1.f, 1);
+    if (g_sdf_band > 0 && !on_device) {
+        volume->DensityScale = threshold;
+        Redistance(*volume, g_sdf_band, VRT_REDISTANCE_FROM_OUTSIDE);
+    }
     if (skipped) std::cout << "[WARNING] Skipped " << skipped << " degenerate or out-of-range triangle(s) of " << meshInfo.MeshName << std::endl;
 
     VMaterial material = meshInfo.Material;

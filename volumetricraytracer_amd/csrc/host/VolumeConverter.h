@@ -42,6 +42,26 @@ public:
     /* true: every converted volume is filled (wall 1, material 1) before it is returned — on the device (vrt_volume_fill_enclosed)
        while UseDevice names a context, on the host otherwise; the same volume, bit for bit. */
     static void MakeSolid(bool solid);
+    /* What Redistance wrote: the box (inclusive xyz), its sample count, how many of them came out nearer than the band, and the surfels
+       among the samples of the box grown by band + 1. */
+    struct VRedistanceResult {
+        VIntVector Lo, Hi;
+        size_t Written = 0, Near = 0, Surfels = 0;
+    };
+    /* The samples of a box (the whole grid without one) rewritten as the signed distance, within `band` cells, to the zero surface of
+       the field the volume holds — the rule of vrt_volume_redistance (include/vrt.h; its arithmetic is csrc/redistance_core.h, shared
+       with the HIP kernels), as a plain windowed loop.  band: 1..15; from: VRT_REDISTANCE_FROM_*, FROM_OUTSIDE for this converter's
+       shells, filled or not.  Lengths become density units through the volume's DensityScale.  Material ids stay.  Marks the volume dirty. */
+    static VRedistanceResult Redistance(Voxel::VVoxelVolume& volume, int band, int from, const VIntVector* boxLo = nullptr,
+                                        const VIntVector* boxHi = nullptr);
+    /* The same on n^3 VVoxel records (index x*n*n + z*n + y) over the samples lo..hi (xyz, inclusive, inside the grid); unit: density
+       units per cell; texel16: the records hold the integer field +-q of a VRT_FORMAT_TEXEL16 slot. */
+    static VRedistanceResult Redistance(Voxel::VVoxel* voxels, size_t n, float unit, bool texel16, int band, int from, const int lo[3],
+                                        const int hi[3]);
+    /* band > 0: every converted volume is redistanced over the whole grid (FROM_OUTSIDE) before it is returned, after the fill of
+       MakeSolid — on the device (vrt_volume_redistance) while UseDevice names a context, on the host otherwise; the same volume, bit
+       for bit.  0 switches it off. */
+    static void MakeSdf(int band);
     static bool ExtractResolutionFromName(const std::string& name, uint8_t& outResolution);
     /* extraction threshold of a volume: cell size · √3 (VolumeConverter.cpp:57) */
     static float ExtractionThreshold(const Voxel::VVoxelVolume& volume);

@@ -21,6 +21,9 @@
  *                                           with thr = cell * sqrt 3, positive again inside — and, after the upload, every volume of the scene has its enclosed
  *                                           cavities filled on the device (VHipRenderer::FillEnclosed, vrt_volume_fill_enclosed; wall 1, material 1): --edit-brush
  *                                           then carves a solid, in the red sphere and in the models of a --scene file, instead of opening a hollow shell
+ *            [--sdf BAND]                   with --solid: after the fill every volume is redistanced on the device (VHipRenderer::Redistance, vrt_volume_redistance,
+ *                                           FROM_OUTSIDE, BAND cells, 1..15) into a true signed distance; under --edit-device the box each dab wrote, grown by
+ *                                           BAND, is redistanced again after the dab
  *            [--pick X Y]                   every frame asks what lies under pixel (X, Y) (VHipRenderer::Pick: a GPU ray query) and prints the
  *                                           hit record; with --edit-brush the brush is centred on the picked voxel when the pick hits the red
  *                                           sphere, and a frame whose pick misses it edits nothing
@@ -82,7 +85,7 @@ int main(int argc, char** argv) {
     unsigned W = 1024, H = 576;
     std::string scenePath, skyboxDir, outPath = "vrt_demo.ppm";
     bool identityDefaults = false;
-    int editBrush = 0;
+    int editBrush = 0, sdf = 0;
     bool editFull = false, editDevice = false, solid = false;
     bool pick = false;
     int pickX = 0, pickY = 0;
@@ -104,6 +107,7 @@ int main(int argc, char** argv) {
         else if (!strcmp(argv[i], "--edit-full")) editFull = true;
         else if (!strcmp(argv[i], "--edit-device")) editDevice = true;
         else if (!strcmp(argv[i], "--solid")) solid = true;
+        else if (!strcmp(argv[i], "--sdf") && i + 1 < argc) sdf = atoi(argv[++i]);
         else if (!strcmp(argv[i], "--pick") && i + 2 < argc) {
             pick = true;
             pickX = atoi(argv[++i]);
@@ -171,6 +175,10 @@ int main(int argc, char** argv) {
         fprintf(stderr, "--solid fills on the device: it needs the HIP renderer\n");
         return 1;
     }
+    if (sdf != 0 && (!solid || sdf < 1 || sdf > 15)) {
+        fprintf(stderr, "--sdf BAND (1..15) redistances what --solid filled: give both\n");
+        return 1;
+    }
     if (solid) { /* uploads the scene, fills every volume's cavities in place; the host mirrors follow, so nothing is left dirty */
         unsigned long long filled = 0;
         for (const auto& placed : scene->GetAllPlacedObjects()) {
@@ -182,6 +190,20 @@ int main(int argc, char** argv) {
         }
         scene->PostRender();
         printf("solid: %llu enclosed voxels filled on the device\n", filled);
+    }
+    unsigned long long dabSurfels = 0, dabSamples = 0;
+    if (sdf > 0) { /* ... and every volume becomes a signed distance to its outer surface */
+        unsigned long long surfels = 0, near = 0;
+        for (const auto& placed : scene->GetAllPlacedObjects()) {
+            auto object = std::dynamic_pointer_cast<Scene::VVoxelObject>(placed);
+            if (!object || !object->GetVoxelVolume()) continue;
+            vrt_redistance_result res;
+            if (!hip->Redistance(*object, sdf, VRT_REDISTANCE_FROM_OUTSIDE, nullptr, nullptr, &res)) return 1;
+            surfels += res.surfels;
+            near += res.near;
+        }
+        scene->PostRender();
+        printf("sdf: band %d, %llu surfels, %llu voxels nearer than the band, redistanced on the device\n", sdf, surfels, near);
     }
     double kernel_ms = 0.0;
     bool warmUp = true; /* the untimed first frame prints no pick record */
@@ -197,7 +219,12 @@ int main(int argc, char** argv) {
             b.radius = (float)editBrush;
             b.reach = 2.f;
             b.material = 0;
-            hip->ApplyBrushes(*sphere1, {b});
+            vrt_brush_result wrote;
+            if (hip->ApplyBrushes(*sphere1, {b}, &wrote) && sdf > 0 && wrote.written > 0) { /* the dab's box grown by the band, a distance again */
+                const VIntVector lo(wrote.lo[0] - sdf, wrote.lo[1] - sdf, wrote.lo[2] - sdf), hi(wrote.hi[0] + sdf, wrote.hi[1] + sdf, wrote.hi[2] + sdf);
+                vrt_redistance_result res;
+                if (hip->Redistance(*sphere1, sdf, VRT_REDISTANCE_FROM_OUTSIDE, &lo, &hi, &res)) dabSurfels += res.surfels, dabSamples += res.written;
+            }
             return;
         }
         Voxel::VVoxelVolume& vol = *sphere1->GetVoxelVolume();
@@ -271,6 +298,7 @@ int main(int argc, char** argv) {
         if (hip) hip->Flush(); /* collect the frames still in flight: GetFrameData() is the last frame again */
     }
     const double wall = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
+    if (sdf > 0 && editDevice && editBrush > 0) printf("sdf: %llu voxels redistanced around the dabs from %llu surfels\n", dabSamples, dabSurfels);
     if (editBrush > 0) printf("brush of %d cells, %s; ", editBrush, editDevice ? "device brushes" : (editFull ? "full uploads" : "region updates"));
     printf("%d frames %ux%u %s%s: %.3f ms/frame wall (%.0f frames/s)", frames, W, H, format.c_str(),
            block > 0 ? (", RenderBlock of " + std::to_string(block)).c_str() : (", " + std::to_string(inFlight) + " in flight").c_str(), wall / frames * 1e3, frames / wall);

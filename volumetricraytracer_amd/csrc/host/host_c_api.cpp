@@ -98,6 +98,30 @@ int vrh_fill_enclosed(vrt_voxel* voxels, int n, float wall, int material, vrt_fi
     return 0;
 }
 
+/* VVolumeConverter::Redistance on caller records: n^3 VVoxel records (index x*n*n + z*n + y), the densities of the box edited in place;
+   unit: density units per cell; texel16 != 0: the densities are the integer field +-q; both box pointers NULL: the whole grid;
+   result_or_null as vrt_volume_redistance reports.  0 / -1. */
+int vrh_redistance(vrt_voxel* voxels, int n, float unit, int texel16, int band, int from, const int* origin_xyz_or_null,
+                   const int* size_xyz_or_null, vrt_redistance_result* result_or_null) {
+    bool good = voxels && n >= 2 && band >= 1 && band <= 15 && from >= VRT_REDISTANCE_FROM_BOTH && from <= VRT_REDISTANCE_FROM_INSIDE &&
+                (origin_xyz_or_null == nullptr) == (size_xyz_or_null == nullptr);
+    int lo[3] = {0, 0, 0}, hi[3] = {n - 1, n - 1, n - 1};
+    for (int a = 0; good && origin_xyz_or_null && a < 3; a++) {
+        good = size_xyz_or_null[a] >= 1 && origin_xyz_or_null[a] >= 0 && (long long)origin_xyz_or_null[a] + size_xyz_or_null[a] <= n;
+        lo[a] = origin_xyz_or_null[a];
+        hi[a] = origin_xyz_or_null[a] + size_xyz_or_null[a] - 1;
+    }
+    if (!good) {
+        g_error = "vrh_redistance: bad argument";
+        return -1;
+    }
+    const auto r = Voxelizer::VVolumeConverter::Redistance(reinterpret_cast<Voxel::VVoxel*>(voxels), (size_t)n, unit, texel16 != 0, band, from, lo, hi);
+    if (result_or_null)
+        *result_or_null = vrt_redistance_result{{r.Lo.X, r.Lo.Y, r.Lo.Z}, {r.Hi.X, r.Hi.Y, r.Hi.Z}, (uint64_t)r.Written, (uint64_t)r.Near,
+                                                (uint32_t)r.Surfels, 0};
+    return 0;
+}
+
 /* The converter's switch behind `voxelizer --solid`: volumes converted from now on are filled (wall 1, material 1). */
 void vrh_make_solid(int solid) { Voxelizer::VVolumeConverter::MakeSolid(solid != 0); }
 

@@ -1,8 +1,10 @@
-/* Voxelizer executable: `voxelizer [--gpu] [--solid] [--out file.vox] path.gltf [texlib.json]` writes `<stem>.vox`
+/* Voxelizer executable: `voxelizer [--gpu] [--solid] [--sdf BAND] [--out file.vox] path.gltf [texlib.json]` writes `<stem>.vox`
  * (Voxelizer/Private/Voxelizer.cpp:36-117).  --gpu runs the per-triangle loop on the first HIP device
  * (vrt_voxelize_mesh); the file is the same, byte for byte.  --solid fills the cavities a closed mesh's shell encloses (wall 1,
  * material 1: VVolumeConverter::FillEnclosed, or vrt_volume_fill_enclosed with --gpu; again the same file), so that the model can
- * be carved as a solid. */
+ * be carved as a solid.  --sdf BAND (1..15) then rewrites every volume as the signed distance, within BAND cells, to its outer surface
+ * (VVolumeConverter::Redistance, or vrt_volume_redistance with --gpu, FROM_OUTSIDE; after the fill when both are given; the same file
+ * again): what ADD brushes, blends and offsets need. */
 #include <chrono>
 #include <cstring>
 #include <iostream>
@@ -15,12 +17,19 @@
 
 int main(int argc, char** argv) {
     bool gpu = false, solid = false;
+    int sdf = 0;
     std::string out;
     std::vector<std::string> args;
     for (int i = 1; i < argc; i++) {
         if (!strcmp(argv[i], "--gpu")) gpu = true;
         else if (!strcmp(argv[i], "--solid")) solid = true;
-        else if (!strcmp(argv[i], "--out") && i + 1 < argc) out = argv[++i];
+        else if (!strcmp(argv[i], "--sdf") && i + 1 < argc) {
+            sdf = atoi(argv[++i]);
+            if (sdf < 1 || sdf > 15) {
+                std::cerr << "[ERROR] --sdf takes a band of 1..15 cells" << std::endl;
+                return 1;
+            }
+        } else if (!strcmp(argv[i], "--out") && i + 1 < argc) out = argv[++i];
         else args.push_back(argv[i]);
     }
     if (args.empty()) {
@@ -37,12 +46,13 @@ int main(int argc, char** argv) {
         VolumeRaytracer::Voxelizer::VVolumeConverter::UseDevice(ctx);
     }
     VolumeRaytracer::Voxelizer::VVolumeConverter::MakeSolid(solid);
+    VolumeRaytracer::Voxelizer::VVolumeConverter::MakeSdf(sdf);
     int status = 0;
     try {
         const auto t0 = std::chrono::steady_clock::now();
         const std::string path = VolumeRaytracer::Voxelizer::VoxelizeFile(args[0], args.size() > 1 ? args[1] : "", out);
         const double s = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
-        std::cout << "Exported voxelized scene to: " << path << " (" << (gpu ? "device" : "host") << " voxelizer, " << (solid ? "solid, " : "") << s << " s)" << std::endl;
+        std::cout << "Exported voxelized scene to: " << path << " (" << (gpu ? "device" : "host") << " voxelizer, " << (solid ? "solid, " : "") << (sdf ? "sdf band " + std::to_string(sdf) + ", " : "") << s << " s)" << std::endl;
     } catch (const std::exception& e) {
         std::cerr << "[ERROR] " << e.what() << std::endl;
         status = 1;

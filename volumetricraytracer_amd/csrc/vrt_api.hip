@@ -26,6 +26,7 @@
 #include "vrt_device.h"
 #include "vrt_launch.h"
 #include "voxelize_core.h"
+#include "redistance_core.h"
 
 using namespace vrt;
 
@@ -91,6 +92,7 @@ static_assert(kDynMaxPointLights == VRT_MAX_POINT_LIGHTS && kDynMaxSpotLights ==
 static_assert(sizeof(vrt_ray) == 32 && sizeof(vrt_hit) == 48, "query_kernel reads two and writes three 16-B words per ray");
 static_assert(sizeof(vrt_brush) == 64 && sizeof(vrt_brush_result) == 32, "vrt.h states these sizes");
 static_assert(sizeof(vrt_fill_result) == 40, "vrt.h states this size");
+static_assert(sizeof(vrt_redistance_result) == 48, "vrt.h states this size");
 static_assert(sizeof(DBrushList) <= 3072, "the brush records travel in the kernel-argument block");
 
 constexpr int kStatSlots = 16; /* streams that may have launches in flight at once without sharing a counter buffer */
@@ -219,6 +221,11 @@ struct DeviceState {
     /* vrt_volume_fill_enclosed: the rounds' flags, the passable mask and the exterior labels (grown on demand, shared by the slots) */
     void* fill_scratch = nullptr;
     size_t fill_scratch_cap = 0;
+    /* vrt_volume_redistance: the tile table and the compact surfels (grown on demand, shared by the slots) */
+    void* redist_table = nullptr;
+    size_t redist_table_cap = 0;
+    void* redist_surfels = nullptr;
+    size_t redist_surfels_cap = 0;
     /* vrt_trace_rays_host: the rays and then the hit records of a batch (grown on demand) */
     void* query_buf = nullptr;
     size_t query_cap = 0;
@@ -545,6 +552,8 @@ void destroy_device(DeviceState& D) {
     if (D.d_box6) (void)hipFree(D.d_box6);
     if (D.d_brush) (void)hipFree(D.d_brush);
     if (D.fill_scratch) (void)hipFree(D.fill_scratch);
+    if (D.redist_table) (void)hipFree(D.redist_table);
+    if (D.redist_surfels) (void)hipFree(D.redist_surfels);
     if (D.query_buf) (void)hipFree(D.query_buf);
     if (D.d_vols) (void)hipFree(D.d_vols);
     if (D.d_inst) (void)hipFree(D.d_inst);
@@ -991,6 +1000,78 @@ int fill_enclosed(vrt_ctx* ctx, int slot, float wall, int material, vrt_fill_res
         if (rc != VRT_OK) return rc;
     }
     if (!any_filled) return VRT_OK;
+    ctx->scene_stale = true;
+    return sync_volume_table(ctx);
+}
+
+/* vrt_volume_redistance: first, on every device, the surfels of the box grown by band + 1 are counted (launch_redistance_count) and the
+ * buffer that holds them is grown — nothing of the volume has been written when that fails —; then per device the surfels are written,
+ * the box's samples become banded signed distances in place (launch_redistance_distance, which reports like a brush launch), and what
+ * the slot derives from the samples is recomputed over the box (rebuild_derived).  Afterwards every buffer equals what upload_volume
+ * builds from the redistanced volume. */
+int redistance(vrt_ctx* ctx, int slot, int band, int from, const int* origin, const int* size, vrt_redistance_result* result) {
+    if (!ctx) return VRT_ERR_INVALID;
+    if (!valid_slot(slot) || !ctx->vol[slot].used) return VRT_ERR_SLOT;
+    if (band < 1 || band > vrt_redist::kMaxBand) return VRT_ERR_INVALID;
+    if (from != VRT_REDISTANCE_FROM_BOTH && from != VRT_REDISTANCE_FROM_OUTSIDE && from != VRT_REDISTANCE_FROM_INSIDE) return VRT_ERR_INVALID;
+    if ((origin == nullptr) != (size == nullptr)) return VRT_ERR_INVALID;
+    HostVolume& h = ctx->vol[slot];
+    const int N = h.N;
+    int lo[3] = {0, 0, 0}, hi[3] = {N - 1, N - 1, N - 1}, glo[3], ghi[3];
+    for (int a = 0; a < 3 && origin; a++) {
+        if (size[a] < 1 || origin[a] < 0 || (long long)origin[a] + size[a] > N) return VRT_ERR_INVALID;
+        lo[a] = origin[a];
+        hi[a] = origin[a] + size[a] - 1;
+    }
+    for (int a = 0; a < 3; a++) {
+        glo[a] = std::max(lo[a] - vrt_redist::cull_reach(band), 0);
+        ghi[a] = std::min(hi[a] + vrt_redist::cull_reach(band), N - 1);
+    }
+    const DerivedBoxes written = derived_boxes(h, lo, hi);
+    const EditBox grown = derived_boxes(h, glo, ghi).samples;
+    const bool texel16 = h.format == VRT_FORMAT_TEXEL16;
+    const float cell = (h.extent * 2.0f) / (float)(N - 1);
+    const float unit = cell / h.density_scale;
+    for (auto& D : ctx->dev) { /* frames already enqueued render the old volume */
+        HIP_TRY(hipSetDevice(D.ordinal));
+        HIP_TRY(hipDeviceSynchronize());
+    }
+    std::vector<unsigned> surfels(ctx->dev.size(), 0u);
+    for (size_t di = 0; di < ctx->dev.size(); di++) { /* everything that can run out of memory, before any sample is written */
+        DeviceState& D = ctx->dev[di];
+        HIP_TRY(hipSetDevice(D.ordinal));
+        int rc = ensure_buffer(D.redist_table, D.redist_table_cap, redistance_table_bytes(N));
+        if (rc != VRT_OK) return rc;
+        if (!D.d_brush) HIP_TRY(hipMalloc(&D.d_brush, kBrushSlots * sizeof(DBrushSlot)));
+        HIP_TRY(launch_redistance_count(D.vol[slot].dense, texel16, N, from, grown, D.redist_table, D.stream));
+        HIP_TRY(hipMemcpyAsync(&surfels[di], redistance_surfel_count(D.redist_table), sizeof(unsigned), hipMemcpyDeviceToHost, D.stream));
+        HIP_TRY(hipStreamSynchronize(D.stream));
+        rc = ensure_buffer(D.redist_surfels, D.redist_surfels_cap, redistance_surfel_bytes(surfels[di]));
+        if (rc != VRT_OK) return rc;
+    }
+    for (size_t di = 0; di < ctx->dev.size(); di++) {
+        DeviceState& D = ctx->dev[di];
+        HIP_TRY(hipSetDevice(D.ordinal));
+        DeviceVolume& v = D.vol[slot];
+        if (surfels[di] > 0u)
+            HIP_TRY(launch_redistance_surfels(v.dense, texel16, N, from, grown, D.redist_table, D.redist_surfels, surfels[di], D.stream));
+        HIP_TRY(launch_redistance_distance(texel16, v.dense, N, band, unit, written.samples, D.redist_table, D.redist_surfels, D.d_brush, D.stream));
+        DBrushSlot part[kBrushSlots];
+        HIP_TRY(hipMemcpyAsync(part, D.d_brush, sizeof part, hipMemcpyDeviceToHost, D.stream));
+        HIP_TRY(hipStreamSynchronize(D.stream));
+        vrt_redistance_result got = {{N, N, N}, {-1, -1, -1}, 0, 0, surfels[di], 0}; /* the partial records merged */
+        for (const DBrushSlot& p : part) {
+            for (int a = 0; a < 3; a++) {
+                got.lo[a] = std::min(got.lo[a], N - (int)p.inv_lo[a]);
+                got.hi[a] = std::max(got.hi[a], (int)p.hi1[a] - 1);
+            }
+            got.written += p.counts & 0xffffffffull;
+            got.near += p.counts >> 32;
+        }
+        if (di == 0 && result) *result = got;
+        int rc = rebuild_derived(ctx, D, slot, &written, false, h.abox);
+        if (rc != VRT_OK) return rc;
+    }
     ctx->scene_stale = true;
     return sync_volume_table(ctx);
 }
@@ -1670,6 +1751,11 @@ int vrt_volume_apply_brushes(vrt_ctx* ctx, int slot, int n, const vrt_brush* bru
 
 int vrt_volume_fill_enclosed(vrt_ctx* ctx, int slot, float wall, int material, vrt_fill_result* result_or_null) {
     return fill_enclosed(ctx, slot, wall, material, result_or_null);
+}
+
+int vrt_volume_redistance(vrt_ctx* ctx, int slot, int band, int from, const int origin_xyz_or_null[3], const int size_xyz_or_null[3],
+                          vrt_redistance_result* result_or_null) {
+    return redistance(ctx, slot, band, from, origin_xyz_or_null, size_xyz_or_null, result_or_null);
 }
 
 int vrt_volume_download_region(vrt_ctx* ctx, int slot, const int origin_xyz[3], const int size_xyz[3], vrt_voxel* out) {

@@ -114,4 +114,20 @@ const int* fill_round_flags(const void* scratch);
 hipError_t launch_fill_apply(bool texel16, float* dense, uint8_t* material, int N, const void* scratch, float wall, int material_id,
                              DBrushSlot* slots, hipStream_t stream);
 
+/* vrt_volume_redistance (vrt_redistance.hip).  table: redistance_table_bytes(N) of device memory — the surfel counter and one
+   {start, count} range per 8^3 tile of the grid —, valid from launch_redistance_count to launch_redistance_distance.  grown: the box
+   grown by band + 1 and clipped to the grid; boxes are in the grid's own axis order like every EditBox. */
+size_t redistance_table_bytes(int N);
+size_t redistance_surfel_bytes(unsigned surfels);
+const unsigned* redistance_surfel_count(const void* table); /* device memory: the total after launch_redistance_count */
+/* Zeroes the table, then counts the surfels of every tile of `grown` and reserves their ranges. */
+hipError_t launch_redistance_count(const float* dense, bool texel16, int N, int from, const EditBox& grown, void* table, hipStream_t stream);
+/* Writes the surfels (centre xyz, normal xyz: 24 B) into their tiles' ranges; `capacity` surfels fit. */
+hipError_t launch_redistance_surfels(const float* dense, bool texel16, int N, int from, const EditBox& grown, void* table, void* surfels,
+                                     unsigned capacity, hipStream_t stream);
+/* Every sample of `box` stores its banded signed distance (its texel when texel16), in place; slots: zeroed, then the written samples'
+   box and count as launch_brush_region reports them, with the count of samples nearer than the band in the high half of `counts`. */
+hipError_t launch_redistance_distance(bool texel16, float* dense, int N, int band, float unit, const EditBox& box, const void* table,
+                                      const void* surfels, DBrushSlot* slots, hipStream_t stream);
+
 }  // namespace vrt

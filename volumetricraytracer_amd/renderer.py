@@ -262,6 +262,26 @@ class VHipRenderer:
             self._mirror_box(slot, vol, lo, hi)
         return {"filled": int(res.filled), "lo": lo, "hi": hi, "sweeps": int(res.sweeps)}
 
+    def redistance(self, slot: int, vol: Optional[VVoxelVolume], band: int, from_: int = _abi.REDISTANCE_FROM_BOTH, lo=None, hi=None) -> dict:
+        """vrt_volume_redistance: the samples lo..hi (inclusive xyz corners; both None: the whole grid) of the volume resident in
+        `slot` rewritten on the device as the signed distance, within `band` cells (1..15), to the zero surface of the field the slot
+        holds.  from_: _abi.REDISTANCE_FROM_OUTSIDE for Voxelizer shells, filled or not; _FROM_BOTH for true distance fields.  Given a
+        host mirror `vol`, the written box is then read back as apply_brushes does.  Returns {"written", "near", "surfels", "lo",
+        "hi"}."""
+        self._require()
+        if (lo is None) != (hi is None):
+            raise ValueError("redistance: give both corners of the box or neither")
+        res = _abi.vrt_redistance_result()
+        origin = size = None
+        if lo is not None:
+            origin = (C.c_int * 3)(*[int(a) for a in lo])
+            size = (C.c_int * 3)(*[int(b) - int(a) + 1 for a, b in zip(lo, hi)])
+        _abi.check(self._lib.vrt_volume_redistance(self._ctx, slot, int(band), int(from_), origin, size, C.byref(res)), "vrt_volume_redistance")
+        wlo, whi = tuple(res.lo), tuple(res.hi)
+        if res.written and vol is not None:
+            self._mirror_box(slot, vol, wlo, whi)
+        return {"written": int(res.written), "near": int(res.near), "surfels": int(res.surfels), "lo": wlo, "hi": whi}
+
     def download_region(self, slot: int, lo, hi):
         """vrt_volume_download_region: the voxels lo..hi (inclusive xyz corners) of the slot on device 0 as (density float32,
         material uint8), both indexed [x, z, y] like VVoxelVolume.density; a TEXEL16 slot decodes like download_volume."""

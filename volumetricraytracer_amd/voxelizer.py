@@ -41,6 +41,9 @@ def load_host() -> C.CDLL:
         lib.vrh_voxelize_file.argtypes = [C.c_char_p, C.c_char_p, C.c_char_p, C.c_char_p, C.c_size_t]
         lib.vrh_fill_enclosed.restype = C.c_int
         lib.vrh_fill_enclosed.argtypes = [C.c_void_p, C.c_int, C.c_float, C.c_int, C.POINTER(_abi.vrt_fill_result)]
+        lib.vrh_redistance.restype = C.c_int
+        lib.vrh_redistance.argtypes = [C.c_void_p, C.c_int, C.c_float, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int),
+                                       C.POINTER(_abi.vrt_redistance_result)]
         lib.vrh_vox_rewrite.restype = C.c_int
         lib.vrh_vox_rewrite.argtypes = [C.c_char_p, C.c_char_p]
         _host = lib
@@ -93,6 +96,30 @@ def fill_enclosed_host(vol: VVoxelVolume, wall: float = 1.0, material: int = -1)
         vol.material_id = np.ascontiguousarray(rec["material"].reshape(vol.N, vol.N, vol.N))
         vol.dirty = True
     return {"filled": int(res.filled), "lo": tuple(res.lo), "hi": tuple(res.hi)}
+
+
+def redistance_host(vol: VVoxelVolume, band: int, from_: int = _abi.REDISTANCE_FROM_BOTH, lo=None, hi=None, unit=None, texel16: bool = False) -> dict:
+    """VVolumeConverter::Redistance (the host build of vrt_volume_redistance's rule) on a volume's densities, in place: the samples
+    lo..hi (inclusive xyz corners; both None: the whole grid) become the signed distance, within `band` cells, to the zero surface of
+    the field.  unit: density units per cell, by default cell / density_scale in float32 as the device computes it; texel16: the
+    densities are the integer field +-q of a TEXEL16 slot.  Material ids stay.  Returns {"written", "near", "surfels", "lo", "hi"}."""
+    lib = load_host()
+    if (lo is None) != (hi is None):
+        raise ValueError("redistance_host: give both corners of the box or neither")
+    rec = np.zeros(vol.N ** 3, dtype=np.dtype([("material", "u1"), ("pad", "u1", 3), ("density", "<f4")]))
+    rec["density"] = np.asarray(vol.density, np.float32).reshape(-1)
+    if unit is None:
+        unit = np.float32(vol.GetCellSize()) / np.float32(vol.density_scale)
+    origin = size = None
+    if lo is not None:
+        origin = (C.c_int * 3)(*[int(a) for a in lo])
+        size = (C.c_int * 3)(*[int(b) - int(a) + 1 for a, b in zip(lo, hi)])
+    res = _abi.vrt_redistance_result()
+    if lib.vrh_redistance(rec.ctypes.data, vol.N, float(unit), int(bool(texel16)), int(band), int(from_), origin, size, C.byref(res)) != 0:
+        raise RuntimeError("vrh_redistance: " + lib.vrh_last_error().decode(errors="replace"))
+    vol.density = np.ascontiguousarray(rec["density"].reshape(vol.N, vol.N, vol.N))
+    vol.dirty = True
+    return {"written": int(res.written), "near": int(res.near), "surfels": int(res.surfels), "lo": tuple(res.lo), "hi": tuple(res.hi)}
 
 
 def voxelize_file(gltf_path: str, out_path: str | None = None, texlib: str | None = None) -> str:
