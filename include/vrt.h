@@ -24,6 +24,8 @@
  *                                   the shell of a closed mesh made solid on the resident volume, so that a SUBTRACT brush carves a solid)
  *   vrt_volume_redistance           (no reference analogue: whatever field the resident volume holds rewritten, within a band, as the
  *                                   signed distance to its own zero surface — what ADD brushes, blends and offsets assume)
+ *   vrt_volume_extract_mesh         (no reference analogue: its Voxelizer goes one way, glTF -> .vox; the resident volume's surface
+ *                                   back out as an indexed triangle mesh, by surface nets)
  *   vrt_volume_free                 VRDXScene::RemoveVoxelVolume  Renderer/DX/Private/RDXScene.cpp:663-701
  *   vrt_env_upload                  VRDXScene::InitEnvironmentMap RDXScene.cpp:181-199
  *   vrt_scene_set                   VRDXScene::SyncWithScene + PrepareForRendering
@@ -488,6 +490,64 @@ typedef struct vrt_redistance_result { /* 48 B */
  * repairs the field there against the surface as it is now. */
 int vrt_volume_redistance(vrt_ctx* ctx, int slot, int band, int from, const int origin_xyz_or_null[3], const int size_xyz_or_null[3],
                           vrt_redistance_result* result_or_null);
+
+/* The surface of a resident volume as triangles (no reference analogue): the level set d = iso of the field the slot holds, over a
+ * box of samples, as an indexed mesh for whatever consumes geometry — a DCC tool, a collider, a printer, the Voxelizer again. */
+typedef struct vrt_mesh_result {      /* 40 B */
+    int32_t lo[3], hi[3];             /* xyz, inclusive: the cells that made a vertex; lo > hi when none */
+    uint64_t vertices;
+    uint64_t quads;                   /* triangles = 2 * quads, indices = 6 * quads */
+} vrt_mesh_result;
+
+/* Synchronous.  Reads the dense grid and the material grid of device 0 (all devices hold the same bytes) after waiting for work
+ * already enqueued on the context's devices, as the edit calls do; writes nothing to the slot: every vrt_debug_volume_bytes buffer
+ * reads the same before and after.  Both box pointers NULL: the whole grid; otherwise the samples [origin, origin + size) as
+ * vrt_volume_update_region takes them.  positions / normals / materials hold 3 floats / 3 floats / 1 byte per vertex and
+ * vertex_capacity vertices each; each may be NULL on its own and is then not written.  indices holds index_capacity 32-bit indices.
+ * With all four output pointers NULL the call only counts and fills the result: count, allocate, call again.
+ * Errors, all checked before any output is written: VRT_ERR_INVALID for a NULL context, a non-finite iso, one box pointer NULL and the
+ * other not, or a box that vrt_volume_update_region would refuse; VRT_ERR_SLOT for an unused slot; VRT_ERR_INVALID, with the result
+ * filled in and no output byte touched, when an output pointer was given and vertex_capacity < vertices or index_capacity < 6 * quads;
+ * VRT_ERR_OOM when scratch memory cannot be allocated.  A field without a surface is VRT_OK with zeros; so is a box one sample thick
+ * on some axis, which has no cells.
+ *
+ * The rule — naive surface nets: one vertex per cell the surface passes through, one quad per grid edge it crosses; no case table,
+ * watertight by construction — is part of the contract.  All arithmetic is fp32, evaluated as parenthesised, no fused multiply-add;
+ * sqrtf and / are correctly rounded; dot(u,v) = (u.x*v.x + u.y*v.y) + u.z*v.z.
+ *   1. Decode and class.  d is the sample's density as for the brushes: the stored float, or stored * 0.01f (VRT_FORMAT_TEXEL16).
+ *      f = -0.0f when d is NaN, else fminf(fmaxf(d - iso, -1e18f), 1e18f).  A sample is OUTSIDE when f > 0, else INSIDE.
+ *   2. Cells.  Cell (cx,cy,cz) has the corner samples (cx+dx, cy+dy, cz+dz), dx,dy,dz in {0,1}; corner number j = dx + 2*dy + 4*dz.
+ *      The cell box is the cells whose eight corners all lie in the sample box.  An active cell is a cell of the cell box whose
+ *      corners are not all of one class.
+ *   3. The vertex of an active cell.  Walk its 12 edges in this order: axis a = x, y, z; with (b, c) the other two axes in cyclic
+ *      order (x: (y,z), y: (z,x), z: (x,y)), ob = 0, 1 outer and oc = 0, 1 inner.  The edge runs from corner A (offset 0 on a, ob
+ *      on b, oc on c) to corner B (offset 1 on a).  Every edge adds f(B) - f(A) to g_a (g starts at 0.0f).  An edge whose ends
+ *      differ in class is a crossing: t = f(A) / (f(A) - f(B)) (the denominator is never 0 and t lies in [0, 1]); it adds t to s_a,
+ *      (float)ob to s_b and (float)oc to s_c (s starts at 0.0f) and counts into k.  Grid position p_a = (float)c_a + (s_a / (float)k);
+ *      object-space position (p_a * cell) - extent with cell = (extent * 2.0f) / (float)(N - 1) computed once on the host, as for the
+ *      brushes.  Object axes x, y, z are the grid's x, y, z: the frame of vrt_hit::voxel.  Normal: G = dot(g, g); (0,0,0) when
+ *      G == 0, else n_a = g_a / sqrtf(G) — the trilinear gradient at the cell's centre, pointing from inside to outside; the clamp of
+ *      step 1 keeps G finite.  Material: the material id of the lowest-numbered INSIDE corner.
+ *   4. Quads.  Every grid edge from a sample A to B = A + 1 on axis a whose ends differ in class and whose four neighbouring cells all
+ *      lie in the cell box makes one.  With (b, c) as above those cells have index A_a on axis a and, on (b, c), q0 = (A_b-1, A_c-1),
+ *      q1 = (A_b, A_c-1), q2 = (A_b, A_c), q3 = (A_b-1, A_c); all four are active by construction.  Vertex order q0 q1 q2 q3 when A
+ *      is INSIDE, q3 q2 q1 q0 when A is OUTSIDE; triangles (v0, v1, v2) and (v0, v2, v3).  For a triangle (p0, p1, p2),
+ *      cross(p1 - p0, p2 - p0) then points to the outside in the output's x, y, z.  The mesh is open where the surface leaves the
+ *      cell box and closed everywhere else.
+ *   5. Order.  Vertices are numbered in the order of their cells' keys (cx*N + cz)*N + cy — the grid's storage order, x slowest and y
+ *      fastest; quads in the order of the same key of their sample A and, within a sample, axis x, y, z.  The output does not depend
+ *      on how the device schedules its work.
+ * What the rule is worth: on a sphere of 10.4 cells vertices lie between 0.035 cells inside and 0.0000 outside the analytic surface
+ * (the mean of chord points never leaves a convex body), the enclosed volume is 0.9895 of the analytic one and vertex normals are
+ * within 3.2 degrees of the radial direction; DESIGN.md section 2 has the figures.  Sharp features are rounded to the cell. */
+int vrt_volume_extract_mesh(vrt_ctx* ctx, int slot, float iso,
+                            const int origin_xyz_or_null[3], const int size_xyz_or_null[3],
+                            float* positions_or_null,    /* 3 floats per vertex, object space */
+                            float* normals_or_null,      /* 3 floats per vertex */
+                            uint8_t* materials_or_null,  /* 1 byte per vertex */
+                            size_t vertex_capacity,
+                            uint32_t* indices_or_null, size_t index_capacity,
+                            vrt_mesh_result* result_or_null);
 /* Reads the box [origin, origin+size) of device 0's slot as VVoxel records: box order as vrt_volume_update_voxels takes it, decode
  * as vrt_volume_download's.  Only the box's bytes cross the bus, so a host mirror can follow a device-side edit without a full
  * download.  Argument checks as vrt_volume_update_region's.  On a VRT_FORMAT_TEXEL16 slot the decoded values (q * 0.01f) re-quantise

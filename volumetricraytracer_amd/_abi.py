@@ -233,6 +233,10 @@ class vrt_redistance_result(C.Structure):
                 ("reserved_", C.c_uint32)]
 
 
+class vrt_mesh_result(C.Structure):
+    _fields_ = [("lo", C.c_int32 * 3), ("hi", C.c_int32 * 3), ("vertices", C.c_uint64), ("quads", C.c_uint64)]
+
+
 REDISTANCE_FROM_BOTH, REDISTANCE_FROM_OUTSIDE, REDISTANCE_FROM_INSIDE = 0, 1, 2
 
 SYMBOLS = {
@@ -257,6 +261,8 @@ SYMBOLS = {
     "vrt_volume_fill_enclosed": (C.c_int, [C.c_void_p, C.c_int, C.c_float, C.c_int, C.POINTER(vrt_fill_result)]),
     "vrt_volume_redistance": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int),
                                         C.POINTER(vrt_redistance_result)]),
+    "vrt_volume_extract_mesh": (C.c_int, [C.c_void_p, C.c_int, C.c_float, C.POINTER(C.c_int), C.POINTER(C.c_int), C.c_void_p, C.c_void_p,
+                                          C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.POINTER(vrt_mesh_result)]),
     "vrt_volume_download_region": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int), C.c_void_p]),
     "vrt_debug_volume_bytes": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_size_t, C.POINTER(C.c_size_t)]),
     "vrt_env_upload": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p]),

@@ -851,6 +851,44 @@ bool VHipRenderer::Redistance(const Scene::VVoxelObject& object, int band, int f
     return MirrorBox(slot, *volume, res.lo, res.hi);
 }
 
+bool VHipRenderer::ExtractMesh(const Scene::VVoxelObject& object, Voxelizer::VVolumeConverter::VSurfaceMesh& out, float iso, const VIntVector* boxLo,
+                               const VIntVector* boxHi) {
+    if (!IsActive()) {
+        V_LOG_WARNING("ExtractMesh() on an inactive renderer");
+        return false;
+    }
+    const VObjectPtr<Scene::VScene> scene = SceneRef.lock();
+    const VObjectPtr<Voxel::VVoxelVolume> volume = object.GetVoxelVolume();
+    if (!scene || !volume || (boxLo == nullptr) != (boxHi == nullptr)) return false;
+    if (!SyncWithScene(*scene)) return false;
+    const int slot = SlotOf(volume.get());
+    if (slot < 0) {
+        V_LOG_ERROR("ExtractMesh(): the object's volume is not part of the rendered scene");
+        return false;
+    }
+    int lo[3], size[3];
+    if (boxLo) {
+        const int last = (int)volume->GetSize() - 1;
+        lo[0] = std::max(boxLo->X, 0), lo[1] = std::max(boxLo->Y, 0), lo[2] = std::max(boxLo->Z, 0);
+        size[0] = std::min(boxHi->X, last) - lo[0] + 1, size[1] = std::min(boxHi->Y, last) - lo[1] + 1, size[2] = std::min(boxHi->Z, last) - lo[2] + 1;
+        if (size[0] < 1 || size[1] < 1 || size[2] < 1) return false;
+    }
+    const int* origin = boxLo ? lo : nullptr;
+    const int* extent = boxLo ? size : nullptr;
+    vrt_mesh_result res; /* count, size the arrays, fetch */
+    if (!ok(vrt_volume_extract_mesh(Ctx, slot, iso, origin, extent, nullptr, nullptr, nullptr, 0, nullptr, 0, &res), "vrt_volume_extract_mesh")) return false;
+    out.Positions.assign(res.vertices * 3, 0.f);
+    out.Normals.assign(res.vertices * 3, 0.f);
+    out.Materials.assign(res.vertices, 0);
+    out.Indices.assign(res.quads * 6, 0u);
+    out.Lo = VIntVector(res.lo[0], res.lo[1], res.lo[2]);
+    out.Hi = VIntVector(res.hi[0], res.hi[1], res.hi[2]);
+    if (res.vertices == 0) return true;
+    return ok(vrt_volume_extract_mesh(Ctx, slot, iso, origin, extent, out.Positions.data(), out.Normals.data(), out.Materials.data(), out.Materials.size(),
+                                      out.Indices.data(), out.Indices.size(), &res),
+              "vrt_volume_extract_mesh");
+}
+
 bool VHipRenderer::Pick(int px, int py, vrt_hit& out) {
     const VObjectPtr<Scene::VScene> scene = SceneRef.lock();
     if (!IsActive() || !scene || px < 0 || py < 0 || (unsigned)px >= Width || (unsigned)py >= Height) return false;

@@ -15,6 +15,7 @@
 #include <vector>
 #include "../../../include/vrt.h"
 #include "HostRenderer.h"
+#include "VolumeConverter.h"
 
 namespace VolumeRaytracer {
 namespace Renderer {
@@ -133,6 +134,13 @@ public:
        when the object's volume is not in the scene. */
     bool Redistance(const Scene::VVoxelObject& object, int band, int from, const VIntVector* boxLo = nullptr, const VIntVector* boxHi = nullptr,
                     vrt_redistance_result* result = nullptr);
+    /* The surface density = iso of the volume of a placed object as it is on the device now — sculpted, filled, redistanced —, as an
+       indexed triangle mesh in the volume's object space (vrt_volume_extract_mesh: surface nets on the device; the rule: vrt.h), over
+       the samples boxLo..boxHi (inclusive xyz indices, clamped to the grid) or the whole grid without a box.  The scene is synced
+       first; the volume is only read.  With VolumeFormat VRT_FORMAT_TEXEL16 the surface is that of the 16-bit field.  False (after
+       logging) on failure or when the object's volume is not in the scene. */
+    bool ExtractMesh(const Scene::VVoxelObject& object, Voxelizer::VVolumeConverter::VSurfaceMesh& out, float iso = 0.f,
+                     const VIntVector* boxLo = nullptr, const VIntVector* boxHi = nullptr);
 
 private:
     bool SyncWithScene(Scene::VScene& scene);

@@ -2,6 +2,7 @@
 
 #include "../../../include/vrt.h"
 #include "../fill_core.h"
+#include "../mesh_core.h"
 #include "../redistance_core.h"
 #include "../voxelize_core.h"
 
@@ -166,6 +167,75 @@ VVolumeConverter::VRedistanceResult VVolumeConverter::Redistance(Voxel::VVoxelVo
     const VRedistanceResult out = Redistance(volume.GetVoxels().data(), volume.GetSize(), unit, false, band, from, lo, hi);
     volume.MakeDirty();
     return out;
+}
+
+VVolumeConverter::VSurfaceMesh VVolumeConverter::ExtractMesh(const Voxel::VVoxel* voxels, size_t n, float extent, bool texel16, float iso,
+                                                             const int lo[3], const int hi[3]) {
+    namespace M = vrt_mesh;
+    const int N = (int)n;
+    const float cell = (extent * 2.0f) / (float)(N - 1);
+    const int cells[3] = {hi[0] - lo[0], hi[1] - lo[1], hi[2] - lo[2]}; /* a row of s samples has s - 1 cells */
+    VSurfaceMesh out;
+    out.Lo = VIntVector(N, N, N);
+    out.Hi = VIntVector(-1, -1, -1);
+    if (cells[0] < 1 || cells[1] < 1 || cells[2] < 1) return out;
+    const auto at = [&](int x, int y, int z) { return ((size_t)x * n + (size_t)z) * n + (size_t)y; };
+    const auto corners = [&](const int c[3], float f[8]) {
+        for (int j = 0; j < 8; j++) {
+            const float d = voxels[at(c[0] + (j & 1), c[1] + ((j >> 1) & 1), c[2] + (j >> 2))].Density;
+            f[j] = M::field(texel16 ? d * 0.01f : d, iso);
+        }
+    };
+    /* first pass, in the order of the cells' keys: the vertices, and every active cell's number */
+    constexpr uint32_t kNone = 0xffffffffu;
+    std::vector<uint32_t> number((size_t)cells[0] * cells[1] * cells[2], kNone);
+    const auto slot = [&](const int c[3]) { return ((size_t)(c[0] - lo[0]) * cells[2] + (size_t)(c[2] - lo[2])) * cells[1] + (size_t)(c[1] - lo[1]); };
+    for (int x = lo[0]; x < hi[0]; x++)
+        for (int z = lo[2]; z < hi[2]; z++)
+            for (int y = lo[1]; y < hi[1]; y++) {
+                const int c[3] = {x, y, z};
+                float f[8];
+                corners(c, f);
+                const unsigned classes = M::corner_classes(f);
+                if (!M::active(classes)) continue;
+                number[slot(c)] = (uint32_t)out.Materials.size();
+                const M::Vertex v = M::cell_vertex(c, f);
+                for (int a = 0; a < 3; a++) out.Positions.push_back(M::object_coordinate(v.p[a], cell, extent));
+                for (int a = 0; a < 3; a++) out.Normals.push_back(v.n[a]);
+                const int j = M::material_corner(classes);
+                out.Materials.push_back(voxels[at(x + (j & 1), y + ((j >> 1) & 1), z + (j >> 2))].Material);
+                out.Lo = VIntVector(std::min(out.Lo.X, x), std::min(out.Lo.Y, y), std::min(out.Lo.Z, z));
+                out.Hi = VIntVector(std::max(out.Hi.X, x), std::max(out.Hi.Y, y), std::max(out.Hi.Z, z));
+            }
+    /* second pass, in the same order: the quads of every cell's corner 0 */
+    for (int x = lo[0]; x < hi[0]; x++)
+        for (int z = lo[2]; z < hi[2]; z++)
+            for (int y = lo[1]; y < hi[1]; y++) {
+                const int c[3] = {x, y, z};
+                if (number[slot(c)] == kNone) continue;
+                float f[8];
+                corners(c, f);
+                const unsigned classes = M::corner_classes(f);
+                const unsigned quads = M::owned_quads(classes, c, lo);
+                for (int a = 0; a < 3; a++) {
+                    if (!((quads >> a) & 1u)) continue;
+                    int q_cells[4][3];
+                    M::quad_cells(a, c, q_cells);
+                    uint32_t q[4], six[6];
+                    for (int i = 0; i < 4; i++) q[i] = number[slot(q_cells[i])];
+                    M::quad_indices(q, (classes & 1u) != 0u, six);
+                    out.Indices.insert(out.Indices.end(), six, six + 6);
+                }
+            }
+    return out;
+}
+
+VVolumeConverter::VSurfaceMesh VVolumeConverter::ExtractMesh(const Voxel::VVoxelVolume& volume, float iso, const VIntVector* boxLo,
+                                                             const VIntVector* boxHi) {
+    const int last = (int)volume.GetSize() - 1;
+    const int lo[3] = {boxLo ? boxLo->X : 0, boxLo ? boxLo->Y : 0, boxLo ? boxLo->Z : 0};
+    const int hi[3] = {boxHi ? boxHi->X : last, boxHi ? boxHi->Y : last, boxHi ? boxHi->Z : last};
+    return ExtractMesh(volume.GetVoxels().data(), volume.GetSize(), volume.GetVolumeExtends(), false, iso, lo, hi);
 }
 
 bool VVolumeConverter::ExtractResolutionFromName(const std::string& name, uint8_t& outResolution) {

@@ -10,7 +10,9 @@
  * UNSIGNED shell: |surface distance| < thr/2 ⇔ density < 0.
  */
 #pragma once
+#include <cstdint>
 #include <memory>
+#include <vector>
 #include "HostVoxel.h"
 #include "VoxelizerTypes.h"
 
@@ -62,6 +64,25 @@ public:
        MakeSolid — on the device (vrt_volume_redistance) while UseDevice names a context, on the host otherwise; the same volume, bit
        for bit.  0 switches it off. */
     static void MakeSdf(int band);
+    /* What ExtractMesh returns: an indexed triangle mesh in the volume's object space (the frame of vrt_hit::voxel), one vertex per
+       active cell with its normal and material id, two triangles (six indices) per quad, and the active cells' box (inclusive xyz;
+       Lo > Hi when there is no vertex). */
+    struct VSurfaceMesh {
+        std::vector<float> Positions, Normals; /* 3 floats per vertex */
+        std::vector<uint8_t> Materials;
+        std::vector<uint32_t> Indices;
+        VIntVector Lo, Hi;
+        size_t Vertices() const { return Materials.size(); }
+        size_t Quads() const { return Indices.size() / 6; }
+    };
+    /* The surface density = iso of a volume over a box of samples (the whole grid without one) by naive surface nets — the rule of
+       vrt_volume_extract_mesh (include/vrt.h; its arithmetic is csrc/mesh_core.h, shared with the HIP kernels), as plain loops in the
+       contract's order.  The volume is only read. */
+    static VSurfaceMesh ExtractMesh(const Voxel::VVoxelVolume& volume, float iso = 0.f, const VIntVector* boxLo = nullptr,
+                                    const VIntVector* boxHi = nullptr);
+    /* The same on n^3 VVoxel records (index x*n*n + z*n + y) over the samples lo..hi (xyz, inclusive, inside the grid); extent: the
+       volume's half size; texel16: the records hold the integer field +-q of a VRT_FORMAT_TEXEL16 slot. */
+    static VSurfaceMesh ExtractMesh(const Voxel::VVoxel* voxels, size_t n, float extent, bool texel16, float iso, const int lo[3], const int hi[3]);
     static bool ExtractResolutionFromName(const std::string& name, uint8_t& outResolution);
     /* extraction threshold of a volume: cell size · √3 (VolumeConverter.cpp:57) */
     static float ExtractionThreshold(const Voxel::VVoxelVolume& volume);

@@ -24,6 +24,8 @@
  *            [--sdf BAND]                   with --solid: after the fill every volume is redistanced on the device (VHipRenderer::Redistance, vrt_volume_redistance,
  *                                           FROM_OUTSIDE, BAND cells, 1..15) into a true signed distance; under --edit-device the box each dab wrote, grown by
  *                                           BAND, is redistanced again after the dab
+ *            [--mesh-out FILE]              after the last frame the first object's volume, as sculpted on the device, leaves as triangles: surface nets on the
+ *                                           device (VHipRenderer::ExtractMesh, vrt_volume_extract_mesh) written as glTF (.gltf + .bin, or .glb); `voxelizer` reads it back
  *            [--pick X Y]                   every frame asks what lies under pixel (X, Y) (VHipRenderer::Pick: a GPU ray query) and prints the
  *                                           hit record; with --edit-brush the brush is centred on the picked voxel when the pick hits the red
  *                                           sphere, and a frame whose pick misses it edits nothing
@@ -35,6 +37,7 @@
 #include <cstring>
 #include <string>
 
+#include "GltfExporter.h"
 #include "HipRenderer.h"
 #include "HostSerialization.h"
 
@@ -83,7 +86,7 @@ static VObjectPtr<VTextureCube> ProceduralSky(size_t S) {
 int main(int argc, char** argv) {
     int frames = 60;
     unsigned W = 1024, H = 576;
-    std::string scenePath, skyboxDir, outPath = "vrt_demo.ppm";
+    std::string scenePath, skyboxDir, outPath = "vrt_demo.ppm", meshOut;
     bool identityDefaults = false;
     int editBrush = 0, sdf = 0;
     bool editFull = false, editDevice = false, solid = false;
@@ -108,6 +111,7 @@ int main(int argc, char** argv) {
         else if (!strcmp(argv[i], "--edit-device")) editDevice = true;
         else if (!strcmp(argv[i], "--solid")) solid = true;
         else if (!strcmp(argv[i], "--sdf") && i + 1 < argc) sdf = atoi(argv[++i]);
+        else if (!strcmp(argv[i], "--mesh-out") && i + 1 < argc) meshOut = argv[++i];
         else if (!strcmp(argv[i], "--pick") && i + 2 < argc) {
             pick = true;
             pickX = atoi(argv[++i]);
@@ -173,6 +177,10 @@ int main(int argc, char** argv) {
     }
     if (solid && !hip) {
         fprintf(stderr, "--solid fills on the device: it needs the HIP renderer\n");
+        return 1;
+    }
+    if (!meshOut.empty() && !hip) {
+        fprintf(stderr, "--mesh-out extracts on the device: it needs the HIP renderer\n");
         return 1;
     }
     if (sdf != 0 && (!solid || sdf < 1 || sdf > 15)) {
@@ -321,6 +329,24 @@ int main(int argc, char** argv) {
             fclose(fp);
             printf("wrote %s\n", outPath.c_str());
         }
+    }
+    if (!meshOut.empty()) { /* the first object's volume as it is on the device now */
+        VObjectPtr<Scene::VVoxelObject> first;
+        for (const auto& placed : scene->GetAllPlacedObjects()) {
+            const auto object = std::dynamic_pointer_cast<Scene::VVoxelObject>(placed);
+            if (object && object->GetVoxelVolume()) {
+                first = object;
+                break;
+            }
+        }
+        Voxelizer::VGLTFExporter::VEntry e;
+        if (!first || !hip->ExtractMesh(*first, e.Mesh)) return 1;
+        const Voxel::VVoxelVolume& volume = *first->GetVoxelVolume();
+        e.Name = "Object0_" + std::to_string((int)volume.GetResolution());
+        e.Position = first->Position, e.Rotation = first->Rotation, e.Scale = first->Scale;
+        e.Material = volume.GetMaterial();
+        if (!Voxelizer::VGLTFExporter::Export(meshOut, {e})) return 1;
+        printf("mesh: %zu vertices %zu triangles, wrote %s\n", e.Mesh.Vertices(), 2 * e.Mesh.Quads(), meshOut.c_str());
     }
     renderer->Stop();
     return 0;

@@ -1,12 +1,14 @@
 /* host_c_api.cpp — C entry points of libvrt_host.so for the Python tests / bench (ctypes): the
  * Voxelizer on in-memory meshes and on .gltf files, and a .vox rewrite through the C++ reader and
  * writer.  Not part of the renderer boundary (that is include/vrt.h). */
+#include <cmath>
 #include <cstring>
 #include <exception>
 #include <string>
 
 #include "../../../include/vrt.h"
 #include "HostRenderer.h"
+#include "GltfImporter.h"
 #include "HostSerialization.h"
 #include "SceneConverter.h"
 #include "VolumeConverter.h"
@@ -120,6 +122,73 @@ int vrh_redistance(vrt_voxel* voxels, int n, float unit, int texel16, int band, 
         *result_or_null = vrt_redistance_result{{r.Lo.X, r.Lo.Y, r.Lo.Z}, {r.Hi.X, r.Hi.Y, r.Hi.Z}, (uint64_t)r.Written, (uint64_t)r.Near,
                                                 (uint32_t)r.Surfels, 0};
     return 0;
+}
+
+/* VVolumeConverter::ExtractMesh on caller records: n^3 VVoxel records (index x*n*n + z*n + y), only read; extent: the volume's half size;
+   texel16 != 0: the densities are the integer field +-q; the box, the outputs, their capacities and result_or_null as
+   vrt_volume_extract_mesh takes them (all four outputs NULL: count only).  0 / -1; -2 with the result filled in: a capacity too small. */
+int vrh_extract_mesh(const vrt_voxel* voxels, int n, float extent, int texel16, float iso, const int* origin_xyz_or_null,
+                     const int* size_xyz_or_null, float* positions_or_null, float* normals_or_null, uint8_t* materials_or_null,
+                     size_t vertex_capacity, uint32_t* indices_or_null, size_t index_capacity, vrt_mesh_result* result_or_null) {
+    bool good = voxels && n >= 2 && std::isfinite(iso) && (origin_xyz_or_null == nullptr) == (size_xyz_or_null == nullptr);
+    int lo[3] = {0, 0, 0}, hi[3] = {n - 1, n - 1, n - 1};
+    for (int a = 0; good && origin_xyz_or_null && a < 3; a++) {
+        good = size_xyz_or_null[a] >= 1 && origin_xyz_or_null[a] >= 0 && (long long)origin_xyz_or_null[a] + size_xyz_or_null[a] <= n;
+        lo[a] = origin_xyz_or_null[a];
+        hi[a] = origin_xyz_or_null[a] + size_xyz_or_null[a] - 1;
+    }
+    if (!good) {
+        g_error = "vrh_extract_mesh: bad argument";
+        return -1;
+    }
+    const auto m = Voxelizer::VVolumeConverter::ExtractMesh(reinterpret_cast<const Voxel::VVoxel*>(voxels), (size_t)n, extent, texel16 != 0, iso, lo, hi);
+    if (result_or_null)
+        *result_or_null = vrt_mesh_result{{m.Lo.X, m.Lo.Y, m.Lo.Z}, {m.Hi.X, m.Hi.Y, m.Hi.Z}, (uint64_t)m.Vertices(), (uint64_t)m.Quads()};
+    if (!positions_or_null && !normals_or_null && !materials_or_null && !indices_or_null) return 0;
+    if (vertex_capacity < m.Vertices() || index_capacity < m.Indices.size()) {
+        g_error = "vrh_extract_mesh: capacity too small";
+        return -2;
+    }
+    if (positions_or_null && m.Vertices()) memcpy(positions_or_null, m.Positions.data(), m.Positions.size() * sizeof(float));
+    if (normals_or_null && m.Vertices()) memcpy(normals_or_null, m.Normals.data(), m.Normals.size() * sizeof(float));
+    if (materials_or_null && m.Vertices()) memcpy(materials_or_null, m.Materials.data(), m.Materials.size());
+    if (indices_or_null && !m.Indices.empty()) memcpy(indices_or_null, m.Indices.data(), m.Indices.size() * sizeof(uint32_t));
+    return 0;
+}
+
+/* VGLTFImporter::ImportScene on a .gltf / .glb file, mesh `mesh` (its index in the file): counts_out[2] = vertices, indices; the
+   positions as the importer hands them to the converter (x100, re-centred on the bounds' middle; 3 floats per vertex) and the indices
+   are copied when their pointer is given and the capacity suffices; name_out receives the mesh's name.  0 / -1. */
+int vrh_gltf_mesh(const char* path, int mesh, size_t* counts_out, float* positions_or_null, size_t vertex_capacity, uint32_t* indices_or_null,
+                  size_t index_capacity, char* name_out, size_t name_len) {
+    try {
+        const std::shared_ptr<Voxelizer::VSceneInfo> scene = Voxelizer::VGLTFImporter::ImportScene(path ? path : "");
+        const auto found = scene->Meshes.find(std::to_string(mesh));
+        if (found == scene->Meshes.end()) {
+            g_error = "vrh_gltf_mesh: no such mesh";
+            return -1;
+        }
+        const Voxelizer::VMeshInfo& info = found->second;
+        if (counts_out) counts_out[0] = info.Vertices.size(), counts_out[1] = info.Indices.size();
+        if ((positions_or_null && vertex_capacity < info.Vertices.size()) || (indices_or_null && index_capacity < info.Indices.size())) {
+            g_error = "buffer too small";
+            return -1;
+        }
+        for (size_t i = 0; positions_or_null && i < info.Vertices.size(); i++) {
+            positions_or_null[3 * i] = info.Vertices[i].Position.X;
+            positions_or_null[3 * i + 1] = info.Vertices[i].Position.Y;
+            positions_or_null[3 * i + 2] = info.Vertices[i].Position.Z;
+        }
+        for (size_t i = 0; indices_or_null && i < info.Indices.size(); i++) indices_or_null[i] = (uint32_t)info.Indices[i];
+        if (name_out && name_len) {
+            strncpy(name_out, info.MeshName.c_str(), name_len - 1);
+            name_out[name_len - 1] = '\0';
+        }
+        return 0;
+    } catch (const std::exception& e) {
+        g_error = e.what();
+        return -1;
+    }
 }
 
 /* The converter's switch behind `voxelizer --solid`: volumes converted from now on are filled (wall 1, material 1). */

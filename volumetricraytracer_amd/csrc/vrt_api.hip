@@ -93,6 +93,7 @@ static_assert(sizeof(vrt_ray) == 32 && sizeof(vrt_hit) == 48, "query_kernel read
 static_assert(sizeof(vrt_brush) == 64 && sizeof(vrt_brush_result) == 32, "vrt.h states these sizes");
 static_assert(sizeof(vrt_fill_result) == 40, "vrt.h states this size");
 static_assert(sizeof(vrt_redistance_result) == 48, "vrt.h states this size");
+static_assert(sizeof(vrt_mesh_result) == 40, "vrt.h states this size");
 static_assert(sizeof(DBrushList) <= 3072, "the brush records travel in the kernel-argument block");
 
 constexpr int kStatSlots = 16; /* streams that may have launches in flight at once without sharing a counter buffer */
@@ -226,6 +227,11 @@ struct DeviceState {
     size_t redist_table_cap = 0;
     void* redist_surfels = nullptr;
     size_t redist_surfels_cap = 0;
+    /* vrt_volume_extract_mesh: the runs' records with their scan, and the staged mesh (grown on demand, shared by the slots) */
+    void* mesh_scratch = nullptr;
+    size_t mesh_scratch_cap = 0;
+    void* mesh_out = nullptr;
+    size_t mesh_out_cap = 0;
     /* vrt_trace_rays_host: the rays and then the hit records of a batch (grown on demand) */
     void* query_buf = nullptr;
     size_t query_cap = 0;
@@ -554,6 +560,8 @@ void destroy_device(DeviceState& D) {
     if (D.fill_scratch) (void)hipFree(D.fill_scratch);
     if (D.redist_table) (void)hipFree(D.redist_table);
     if (D.redist_surfels) (void)hipFree(D.redist_surfels);
+    if (D.mesh_scratch) (void)hipFree(D.mesh_scratch);
+    if (D.mesh_out) (void)hipFree(D.mesh_out);
     if (D.query_buf) (void)hipFree(D.query_buf);
     if (D.d_vols) (void)hipFree(D.d_vols);
     if (D.d_inst) (void)hipFree(D.d_inst);
@@ -1074,6 +1082,75 @@ int redistance(vrt_ctx* ctx, int slot, int band, int from, const int* origin, co
     }
     ctx->scene_stale = true;
     return sync_volume_table(ctx);
+}
+
+/* vrt_volume_extract_mesh, on device 0: the runs of the cell box are counted and scanned (launch_mesh_count), the host reads the two
+ * totals and the active cells' box, checks the caller's capacities and sizes the staged mesh, the runs write it (launch_mesh_emit) and
+ * the arrays the caller asked for are copied out.  The slot is only read. */
+int extract_mesh(vrt_ctx* ctx, int slot, float iso, const int* origin, const int* size, float* positions, float* normals, uint8_t* materials,
+                 size_t vertex_capacity, uint32_t* indices, size_t index_capacity, vrt_mesh_result* result) {
+    if (!ctx || !std::isfinite(iso)) return VRT_ERR_INVALID;
+    if ((origin == nullptr) != (size == nullptr)) return VRT_ERR_INVALID;
+    if (!valid_slot(slot) || !ctx->vol[slot].used) return VRT_ERR_SLOT;
+    const HostVolume& h = ctx->vol[slot];
+    const int N = h.N;
+    int lo[3] = {0, 0, 0}, hi[3] = {N - 1, N - 1, N - 1};
+    for (int a = 0; a < 3 && origin; a++) {
+        if (size[a] < 1 || origin[a] < 0 || (long long)origin[a] + size[a] > N) return VRT_ERR_INVALID;
+        lo[a] = origin[a];
+        hi[a] = origin[a] + size[a] - 1;
+    }
+    const bool wanted = positions || normals || materials || indices;
+    const bool texel16 = h.format == VRT_FORMAT_TEXEL16;
+    const float cell = (h.extent * 2.0f) / (float)(N - 1);
+    for (auto& D : ctx->dev) { /* edits already enqueued come first */
+        HIP_TRY(hipSetDevice(D.ordinal));
+        HIP_TRY(hipDeviceSynchronize());
+    }
+    vrt_mesh_result got = {{N, N, N}, {-1, -1, -1}, 0, 0};
+    const MeshGrid grid = mesh_grid(N, lo, hi);
+    DeviceState& D = ctx->dev[0];
+    if (!mesh_grid_empty(grid)) {
+        HIP_TRY(hipSetDevice(D.ordinal));
+        int rc = ensure_buffer(D.mesh_scratch, D.mesh_scratch_cap, mesh_scratch_bytes(grid));
+        if (rc != VRT_OK) return rc;
+        if (!D.d_brush) HIP_TRY(hipMalloc(&D.d_brush, kBrushSlots * sizeof(DBrushSlot)));
+        HIP_TRY(launch_mesh_count(D.vol[slot].dense, texel16, grid, iso, D.mesh_scratch, D.d_brush, D.stream));
+        unsigned long long totals = 0;
+        DBrushSlot part[kBrushSlots];
+        HIP_TRY(hipMemcpyAsync(&totals, mesh_totals(D.mesh_scratch), sizeof totals, hipMemcpyDeviceToHost, D.stream));
+        HIP_TRY(hipMemcpyAsync(part, D.d_brush, sizeof part, hipMemcpyDeviceToHost, D.stream));
+        HIP_TRY(hipStreamSynchronize(D.stream));
+        got.vertices = totals & 0xffffffffull;
+        got.quads = totals >> 32;
+        for (const DBrushSlot& p : part)
+            for (int a = 0; a < 3; a++) {
+                got.lo[a] = std::min(got.lo[a], N - (int)p.inv_lo[a]);
+                got.hi[a] = std::max(got.hi[a], (int)p.hi1[a] - 1);
+            }
+    }
+    if (result) *result = got;
+    if (!wanted) return VRT_OK;
+    if (vertex_capacity < got.vertices || index_capacity < 6 * got.quads) return VRT_ERR_INVALID;
+    if (got.vertices == 0) return VRT_OK;
+    /* the staged mesh: positions, normals, indices, materials, each where the one before ends (all but the last a multiple of 4 bytes) */
+    const size_t V = (size_t)got.vertices, Q = (size_t)got.quads;
+    const size_t at_normals = V * 3 * sizeof(float), at_indices = at_normals * 2, at_materials = at_indices + Q * 6 * sizeof(uint32_t);
+    int rc = ensure_buffer(D.mesh_out, D.mesh_out_cap, at_materials + V);
+    if (rc != VRT_OK) return rc;
+    char* out = static_cast<char*>(D.mesh_out);
+    float* d_positions = positions ? reinterpret_cast<float*>(out) : nullptr;
+    float* d_normals = normals ? reinterpret_cast<float*>(out + at_normals) : nullptr;
+    uint32_t* d_indices = indices && Q ? reinterpret_cast<uint32_t*>(out + at_indices) : nullptr;
+    uint8_t* d_materials = materials ? reinterpret_cast<uint8_t*>(out + at_materials) : nullptr;
+    HIP_TRY(launch_mesh_emit(D.vol[slot].dense, D.vol[slot].material, texel16, grid, iso, cell, h.extent, D.mesh_scratch, d_positions, d_normals,
+                             d_materials, d_indices, (unsigned)V, (unsigned)Q, D.stream));
+    if (d_positions) HIP_TRY(hipMemcpyAsync(positions, d_positions, at_normals, hipMemcpyDeviceToHost, D.stream));
+    if (d_normals) HIP_TRY(hipMemcpyAsync(normals, d_normals, at_normals, hipMemcpyDeviceToHost, D.stream));
+    if (d_indices) HIP_TRY(hipMemcpyAsync(indices, d_indices, Q * 6 * sizeof(uint32_t), hipMemcpyDeviceToHost, D.stream));
+    if (d_materials) HIP_TRY(hipMemcpyAsync(materials, d_materials, V, hipMemcpyDeviceToHost, D.stream));
+    HIP_TRY(hipStreamSynchronize(D.stream));
+    return VRT_OK;
 }
 
 /* vrt_volume_download_region: the box through the cached staging buffer of device 0 (gather_region_kernel), then one copy. */
@@ -1756,6 +1833,13 @@ int vrt_volume_fill_enclosed(vrt_ctx* ctx, int slot, float wall, int material, v
 int vrt_volume_redistance(vrt_ctx* ctx, int slot, int band, int from, const int origin_xyz_or_null[3], const int size_xyz_or_null[3],
                           vrt_redistance_result* result_or_null) {
     return redistance(ctx, slot, band, from, origin_xyz_or_null, size_xyz_or_null, result_or_null);
+}
+
+int vrt_volume_extract_mesh(vrt_ctx* ctx, int slot, float iso, const int origin_xyz_or_null[3], const int size_xyz_or_null[3],
+                            float* positions_or_null, float* normals_or_null, uint8_t* materials_or_null, size_t vertex_capacity,
+                            uint32_t* indices_or_null, size_t index_capacity, vrt_mesh_result* result_or_null) {
+    return extract_mesh(ctx, slot, iso, origin_xyz_or_null, size_xyz_or_null, positions_or_null, normals_or_null, materials_or_null, vertex_capacity,
+                        indices_or_null, index_capacity, result_or_null);
 }
 
 int vrt_volume_download_region(vrt_ctx* ctx, int slot, const int origin_xyz[3], const int size_xyz[3], vrt_voxel* out) {

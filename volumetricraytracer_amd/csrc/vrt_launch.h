@@ -130,4 +130,29 @@ hipError_t launch_redistance_surfels(const float* dense, bool texel16, int N, in
 hipError_t launch_redistance_distance(bool texel16, float* dense, int N, int band, float unit, const EditBox& box, const void* table,
                                       const void* surfels, DBrushSlot* slots, hipStream_t stream);
 
+/* vrt_volume_extract_mesh (vrt_mesh.hip).  The cell box of a sample box, in xyz order (the mesh rule's own): its first cell, its cells
+   per axis (one less than the samples; none when the box is one sample thick somewhere) and how many runs of 64 cells a row along y has. */
+struct MeshGrid {
+    int N;
+    int lo[3];
+    int n[3];
+    int runs_y;
+};
+MeshGrid mesh_grid(int N, const int lo_xyz[3], const int hi_xyz[3]); /* the samples lo..hi, inclusive */
+bool mesh_grid_empty(const MeshGrid& grid);
+/* scratch: mesh_scratch_bytes(grid) of device memory — the totals, the scan's block sums and one 16-byte record per run —, valid from
+   launch_mesh_count to launch_mesh_emit. */
+size_t mesh_scratch_bytes(const MeshGrid& grid);
+/* device memory: vertices (low half) and quads (high half) of the whole mesh after launch_mesh_count */
+const unsigned long long* mesh_totals(const void* scratch);
+/* Counts every run's vertices and quads and turns the counts into the runs' first vertex and first quad (a prefix sum in run order);
+   slots: zeroed, then the active cells' box in inv_lo / hi1 as launch_brush_region reports a written box.  Not for an empty grid. */
+hipError_t launch_mesh_count(const float* dense, bool texel16, const MeshGrid& grid, float iso, void* scratch, DBrushSlot* slots,
+                             hipStream_t stream);
+/* Writes the vertices (3 floats of object space, 3 floats of normal, 1 material byte each) and the quads (6 indices each) at their
+   numbers; any output may be NULL and is skipped.  vertex_cap / quad_cap: what the outputs hold. */
+hipError_t launch_mesh_emit(const float* dense, const uint8_t* material, bool texel16, const MeshGrid& grid, float iso, float cell, float extent,
+                            void* scratch, float* positions, float* normals, uint8_t* materials, uint32_t* indices, unsigned vertex_cap,
+                            unsigned quad_cap, hipStream_t stream);
+
 }  // namespace vrt

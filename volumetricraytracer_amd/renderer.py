@@ -282,6 +282,31 @@ class VHipRenderer:
             self._mirror_box(slot, vol, wlo, whi)
         return {"written": int(res.written), "near": int(res.near), "surfels": int(res.surfels), "lo": wlo, "hi": whi}
 
+    def extract_mesh(self, slot: int, iso: float = 0.0, lo=None, hi=None):
+        """vrt_volume_extract_mesh: the surface density = iso of the volume resident in `slot`, over the samples lo..hi (inclusive xyz
+        corners; both None: the whole grid), as an indexed triangle mesh built on the device by surface nets: one call that counts,
+        one that fetches.  The slot is only read.  Returns (positions (V, 3) float32 in the volume's object space, normals (V, 3)
+        float32 pointing outwards, materials (V,) uint8, indices (T, 3) uint32, {"vertices", "quads", "lo", "hi"}) — T = 2 * quads;
+        lo / hi: the cells that made a vertex (xyz, inclusive; lo > hi when none)."""
+        self._require()
+        if (lo is None) != (hi is None):
+            raise ValueError("extract_mesh: give both corners of the box or neither")
+        origin = size = None
+        if lo is not None:
+            origin = (C.c_int * 3)(*[int(a) for a in lo])
+            size = (C.c_int * 3)(*[int(b) - int(a) + 1 for a, b in zip(lo, hi)])
+        res = _abi.vrt_mesh_result()
+        call = self._lib.vrt_volume_extract_mesh
+        _abi.check(call(self._ctx, slot, float(iso), origin, size, None, None, None, 0, None, 0, C.byref(res)), "vrt_volume_extract_mesh")
+        V, Q = int(res.vertices), int(res.quads)
+        positions, normals = np.zeros((V, 3), np.float32), np.zeros((V, 3), np.float32)
+        materials, indices = np.zeros(V, np.uint8), np.zeros((2 * Q, 3), np.uint32)
+        if V:
+            _abi.check(call(self._ctx, slot, float(iso), origin, size, positions.ctypes.data_as(C.c_void_p), normals.ctypes.data_as(C.c_void_p),
+                            materials.ctypes.data_as(C.c_void_p), V, indices.ctypes.data_as(C.c_void_p), 6 * Q, C.byref(res)),
+                       "vrt_volume_extract_mesh")
+        return positions, normals, materials, indices, {"vertices": V, "quads": Q, "lo": tuple(res.lo), "hi": tuple(res.hi)}
+
     def download_region(self, slot: int, lo, hi):
         """vrt_volume_download_region: the voxels lo..hi (inclusive xyz corners) of the slot on device 0 as (density float32,
         material uint8), both indexed [x, z, y] like VVoxelVolume.density; a TEXEL16 slot decodes like download_volume."""

@@ -44,6 +44,11 @@ def load_host() -> C.CDLL:
         lib.vrh_redistance.restype = C.c_int
         lib.vrh_redistance.argtypes = [C.c_void_p, C.c_int, C.c_float, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int),
                                        C.POINTER(_abi.vrt_redistance_result)]
+        lib.vrh_extract_mesh.restype = C.c_int
+        lib.vrh_extract_mesh.argtypes = [C.c_void_p, C.c_int, C.c_float, C.c_int, C.c_float, C.POINTER(C.c_int), C.POINTER(C.c_int), C.c_void_p,
+                                         C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.POINTER(_abi.vrt_mesh_result)]
+        lib.vrh_gltf_mesh.restype = C.c_int
+        lib.vrh_gltf_mesh.argtypes = [C.c_char_p, C.c_int, C.POINTER(C.c_size_t), C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_char_p, C.c_size_t]
         lib.vrh_vox_rewrite.restype = C.c_int
         lib.vrh_vox_rewrite.argtypes = [C.c_char_p, C.c_char_p]
         _host = lib
@@ -120,6 +125,48 @@ def redistance_host(vol: VVoxelVolume, band: int, from_: int = _abi.REDISTANCE_F
     vol.density = np.ascontiguousarray(rec["density"].reshape(vol.N, vol.N, vol.N))
     vol.dirty = True
     return {"written": int(res.written), "near": int(res.near), "surfels": int(res.surfels), "lo": tuple(res.lo), "hi": tuple(res.hi)}
+
+
+def extract_mesh_host(vol: VVoxelVolume, iso: float = 0.0, lo=None, hi=None, texel16: bool = False):
+    """VVolumeConverter::ExtractMesh (the host build of vrt_volume_extract_mesh's rule) on a volume's densities and material ids: the
+    surface density = iso over the samples lo..hi (inclusive xyz corners; both None: the whole grid) by surface nets.  texel16: the
+    densities are the integer field +-q of a TEXEL16 slot.  The volume is only read.  Returns (positions (V, 3) float32 in object space,
+    normals (V, 3) float32, materials (V,) uint8, indices (T, 3) uint32, {"vertices", "quads", "lo", "hi"})."""
+    lib = load_host()
+    if (lo is None) != (hi is None):
+        raise ValueError("extract_mesh_host: give both corners of the box or neither")
+    rec = np.zeros(vol.N ** 3, dtype=np.dtype([("material", "u1"), ("pad", "u1", 3), ("density", "<f4")]))
+    rec["density"] = np.asarray(vol.density, np.float32).reshape(-1)
+    rec["material"] = np.asarray(vol.material_id, np.uint8).reshape(-1)
+    origin = size = None
+    if lo is not None:
+        origin = (C.c_int * 3)(*[int(a) for a in lo])
+        size = (C.c_int * 3)(*[int(b) - int(a) + 1 for a, b in zip(lo, hi)])
+    res = _abi.vrt_mesh_result()
+    head = (rec.ctypes.data, vol.N, float(vol.VolumeExtends), int(bool(texel16)), float(iso), origin, size)
+    if lib.vrh_extract_mesh(*head, None, None, None, 0, None, 0, C.byref(res)) != 0:
+        raise RuntimeError("vrh_extract_mesh: " + lib.vrh_last_error().decode(errors="replace"))
+    V, Q = int(res.vertices), int(res.quads)
+    positions, normals = np.zeros((V, 3), np.float32), np.zeros((V, 3), np.float32)
+    materials, indices = np.zeros(V, np.uint8), np.zeros((2 * Q, 3), np.uint32)
+    if V and lib.vrh_extract_mesh(*head, positions.ctypes.data, normals.ctypes.data, materials.ctypes.data, V, indices.ctypes.data, 6 * Q,
+                                  C.byref(res)) != 0:
+        raise RuntimeError("vrh_extract_mesh: " + lib.vrh_last_error().decode(errors="replace"))
+    return positions, normals, materials, indices, {"vertices": V, "quads": Q, "lo": tuple(res.lo), "hi": tuple(res.hi)}
+
+
+def import_gltf_mesh(path: str, mesh: int = 0):
+    """VGLTFImporter::ImportScene on a .gltf / .glb file: (name, positions (V, 3) float32 as the importer hands them to the converter
+    — times 100 and re-centred on the middle of the bounds —, indices uint32) of mesh number `mesh` of the file."""
+    lib = load_host()
+    counts = (C.c_size_t * 2)()
+    name = C.create_string_buffer(256)
+    if lib.vrh_gltf_mesh(path.encode(), int(mesh), counts, None, 0, None, 0, name, 256) != 0:
+        raise RuntimeError("vrh_gltf_mesh: " + lib.vrh_last_error().decode(errors="replace"))
+    positions, indices = np.zeros((counts[0], 3), np.float32), np.zeros(counts[1], np.uint32)
+    if lib.vrh_gltf_mesh(path.encode(), int(mesh), counts, positions.ctypes.data, counts[0], indices.ctypes.data, counts[1], name, 256) != 0:
+        raise RuntimeError("vrh_gltf_mesh: " + lib.vrh_last_error().decode(errors="replace"))
+    return name.value.decode(), positions, indices
 
 
 def voxelize_file(gltf_path: str, out_path: str | None = None, texlib: str | None = None) -> str:
