@@ -20,6 +20,8 @@
  *                                   for a box of voxels instead of the whole volume
  *   vrt_volume_apply_brushes,       (no reference analogue beyond VVoxelVolume::SetVoxel, VoxelVolume.cpp:59-77, in a host loop: CSG
  *   vrt_volume_download_region      sphere / box / capsule brushes evaluated on the resident volume, and the read-back of a box)
+ *   vrt_volume_stamp                (no reference analogue beyond VVoxelVolume::SetVoxel, VoxelVolume.cpp:59-77, in a host loop over two
+ *                                   volumes: CSG of one resident volume, placed by a matrix, into another)
  *   vrt_volume_fill_enclosed        (no reference analogue: its Voxelizer stops at the unsigned shell, Voxelizer/Private/VolumeConverter.cpp:30-84 —
  *                                   the shell of a closed mesh made solid on the resident volume, so that a SUBTRACT brush carves a solid)
  *   vrt_volume_redistance           (no reference analogue: whatever field the resident volume holds rewritten, within a band, as the
@@ -379,6 +381,71 @@ typedef struct vrt_brush_result {     /* 32 B */
  * (SUBTRACT only raises values near the new surface).  For adding into a true SDF it is as far as the old field over-estimates the
  * distance to the new solid.  A slot with step_max > 0 never steps further than step_max, so step_max/cell + 1 is enough there. */
 int vrt_volume_apply_brushes(vrt_ctx* ctx, int slot, int n, const vrt_brush* brushes, vrt_brush_result* result_or_null);
+
+/* CSG with an arbitrary shape (no reference analogue beyond VVoxelVolume::SetVoxel in a host loop over two volumes): the shape is a
+ * second resident volume, sampled trilinearly where the destination's samples land in it.  Stamps a voxelized mesh into a volume,
+ * unites or cuts two objects before vrt_volume_extract_mesh, resamples a volume to another resolution, copies or crops between slots. */
+enum { VRT_STAMP_ADD = 0, VRT_STAMP_SUBTRACT = 1, VRT_STAMP_REPLACE = 2 };
+#define VRT_STAMP_MATERIAL_KEEP   (-1) /* leave material ids alone */
+#define VRT_STAMP_MATERIAL_SOURCE (-2) /* take the id of the nearest source sample */
+typedef struct vrt_stamp {            /* 96 B */
+    int32_t op, material;             /* material: 0..255, VRT_STAMP_MATERIAL_KEEP or VRT_STAMP_MATERIAL_SOURCE */
+    float dst_to_src[12];             /* row-major 3x4: destination grid coordinates (x, y, z) -> source grid coordinates */
+    float length_scale;               /* > 0: destination cells per source cell (how source lengths grow); 1/|row| for a similarity */
+    float offset;                     /* cells of the destination: the stamped shape is grown (> 0) or shrunk (< 0) by it */
+    float blend, reach;               /* as vrt_brush, in cells of the destination; REPLACE ignores both (finite only) */
+    uint32_t reserved_[6];            /* 0 */
+} vrt_stamp;
+
+/* Applies the volume resident in src_slot to the one resident in dst_slot, in place, on every device (both slots are replicated on
+ * all of them).  Waits for work already enqueued on the context's devices (a frame begun before the call renders the old volume, one
+ * begun after renders the new one); device pointers of neither slot change.  Afterwards every device buffer of dst_slot equals what
+ * a full upload of the edited volume holds (what the slot derives from its samples is rebuilt over the written box; nothing is rebuilt
+ * when no density changed), so frames and counters are those of the full upload; every buffer of src_slot reads the same before and
+ * after.  A launch captured into a graph before the edit keeps the cull rectangle it was captured with (capture with
+ * VRT_FLAG_NO_CULL_RECT where an edit may grow the active box).  The two slots may differ in resolution, extent, metric and format.
+ * The caller passes the matrix itself, not position / rotation / scale, so that no trigonometry sits inside the contract; the
+ * adaptors build it from a placement (VHipRenderer::StampVolume, stamp_from_placement).
+ * Errors, all checked before any device state is touched: VRT_ERR_INVALID for a NULL context or record; dst_slot == src_slot; an
+ * unknown op; a material outside -2..255; a non-finite field; length_scale <= 0; blend < 0; reach <= 0 (ADD and SUBTRACT only);
+ * non-zero reserved words; a singular 3x3 part (its determinant evaluated in double precision is 0, or its double-precision
+ * inverse has a non-finite entry).  VRT_ERR_SLOT when either slot is unused.  VRT_ERR_OOM when scratch memory cannot be allocated.
+ * A source that lands wholly outside the destination grid is VRT_OK and writes nothing (lo > hi).
+ * result_or_null: the written samples' count and box, from device 0 (all devices compute the same bytes).
+ *
+ * The rule is part of the contract.  All arithmetic is fp32, evaluated as parenthesised, no fused multiply-add.  Ns is the source's
+ * N, M = dst_to_src, p = ((float)ix, (float)iy, (float)iz) a destination sample; the rule applies to every sample of the destination.
+ *   1. Source coordinate.  u_a = ((M[a][0]*p.x + M[a][1]*p.y) + M[a][2]*p.z) + M[a][3].  The sample is OUTSIDE THE SOURCE unless
+ *      u_a >= 0 && u_a <= (float)(Ns-1) on all three axes; outside samples keep their stored bits.
+ *   2. Cell and fraction.  i_a = min(max((int)floorf(u_a), 0), Ns-2); f_a = u_a - (float)i_a (0..1, 1 only on the last sample).
+ *   3. Decode.  The eight corner samples (i.x+dx, i.y+dy, i.z+dz) of the source cell, decoded as for the brushes: the stored float,
+ *      or stored * 0.01f for a VRT_FORMAT_TEXEL16 source.
+ *   4. Trilinear, on x, then y, then z; every lerp is (s0 * (1.0f - f)) + (s1 * f), which is exact at both ends.  Result t.
+ *   5. Units.  unit = cell / density_scale per slot, as for the brushes.  gain = (length_scale * unit_dst) / unit_src,
+ *      off = offset * unit_dst, k = blend * unit_dst and rv = reach * unit_dst are each computed once on the host.
+ *      v = (t * gain) - off: the source's value in the destination's density units.
+ *   6. Ops.  d is the destination sample's decoded density.
+ *      ADD:      m = fminf(d, v); when k > 0: g = fmaxf(k - fabsf(d - v), 0) / k and m = m - ((g*g)*k)*0.25f.
+ *                Written iff v < rv && m < d.
+ *      SUBTRACT: c = -v and m = fmaxf(d, c); when k > 0: g = fmaxf(k - fabsf(d - c), 0) / k and m = m + ((g*g)*k)*0.25f.
+ *                Written iff v < rv && m > d.
+ *      REPLACE:  m = v.  Written iff v == v.
+ *      NaN is never written.  A written sample stores m (F32) or the texel of m (TEXEL16: the rule at vrt_set_volume_format);
+ *      everything else keeps its bits.
+ *   7. Material of a written sample.  material >= 0: m <= 0 ? material : 0.  VRT_STAMP_MATERIAL_KEEP: untouched.
+ *      VRT_STAMP_MATERIAL_SOURCE: with j_a = i_a + (f_a >= 0.5f ? 1 : 0), the source's id at j when m <= 0, else 0; REPLACE takes the
+ *      source's id unconditionally (a copy copies).
+ *   (An implementation may skip any sample for which step 1 says "outside"; the host derives a conservative box from the
+ *   double-precision inverse of M.)
+ * There is no INTERSECT: outside the source's box it would have to invent a value.
+ * ADD and SUBTRACT assume what the brushes assume: a source that is a signed distance near its surface, and reach as at
+ * vrt_volume_apply_brushes.  Past the source's box nothing is written, so keep reach (times 1/length_scale, in source cells) within
+ * the margin the source leaves around its shape.
+ * What the rule is worth: an analytic sphere SDF of 10.4 cells on 33^3 stamped by ADD into an empty 65^3 field at an oblique placement
+ * leaves a zero crossing within 0.033 destination cells of the analytic sphere at scale 0.5, 0.032 at scale 1 and 0.043 at scale 1.7
+ * (0.017, 0.020 and 0.030 on average): the trilinear interpolant of a convex distance sags between samples by a fraction of a SOURCE
+ * cell; DESIGN.md section 2 has the figures. */
+int vrt_volume_stamp(vrt_ctx* ctx, int dst_slot, int src_slot, const vrt_stamp* stamp, vrt_brush_result* result_or_null);
 
 /* Solid volumes from shells (no reference analogue: its Voxelizer stops at the shell).  vrt_voxelize_mesh and the CPU converter leave the
  * reference's UNSIGNED shell field, density = dist/thr - 0.5: inside a closed mesh the field is positive again, so a VRT_BRUSH_SUBTRACT dab

@@ -1,0 +1,144 @@
+"""The volumes, placements and records that the stamp tests share (tests/test_volume_stamp.py on the host pass,
+tests/test_volume_stamp_gpu.py on the device): each is built once and never written to afterwards."""
+from __future__ import annotations
+
+import functools
+import itertools
+import math
+
+import numpy as np
+
+import stamp_ref as S
+import volume_ref as R
+import volumetricraytracer_amd as v
+from volumetricraytracer_amd import workloads as scenes
+
+RES = {9: 3, 17: 4, 33: 5, 65: 6}
+FORMATS = (R.F32, R.TEXEL16)
+FIELDS = ("sphere", "shell", "hand")
+OPS = (S.ADD, S.SUBTRACT, S.REPLACE)
+BLENDS = (0.0, 1.5)
+MATERIALS = (7, S.KEEP, S.SOURCE)
+OFFSETS = (0.0, 0.75, -0.75)
+TEXEL_EDGES = (5, 10, 15, 20, 23)  # q for which trunc(q * 0.01f * 100.f) != q
+
+
+def hand_made(N: int, seed: int) -> np.ndarray:
+    """Densities of a few cells' size with both signs, and sprinkled over them NaN, +-inf, +-0 and values whose texel is one of
+    TEXEL_EDGES (with both signs)."""
+    rng = np.random.default_rng(seed)
+    d = (rng.standard_normal((N, N, N)) * 2.0).astype(np.float32)
+    special = [np.nan, np.inf, -np.inf, 0.0, -0.0] + [s * (q + 0.5) * 0.01 for q in TEXEL_EDGES for s in (1.0, -1.0)]
+    flat = d.reshape(-1)
+    where = rng.choice(flat.size, size=flat.size // 6, replace=False)
+    flat[where] = np.asarray(special, np.float32)[np.arange(where.size) % len(special)]
+    return d
+
+
+@functools.lru_cache(maxsize=None)
+def volume(kind: str, N: int, role: str) -> v.VVoxelVolume:
+    """A volume of N^3 samples; role "src" / "dst" only varies extent, metric and seed so that the two sides of a stamp differ."""
+    res = RES[N]
+    src = role == "src"
+    if kind == "shell":
+        vol = scenes.voxelized_torus(res)
+    elif kind == "sphere":
+        extent = 40.0 if src else 100.0
+        vol = v.sphere_volume(res, extent, 0.62 * extent)
+        vol.density_scale = 0.8 if src else 1.0
+    elif kind == "torus":
+        vol = v.torus_volume(res, 100.0, 55.0, 22.0)
+    else:
+        assert kind == "hand"
+        vol = v.VVoxelVolume(res, 6.0 if src else 9.0)
+        vol.density = hand_made(N, 11 if src else 12)
+        vol.density_scale = 0.5 if src else 1.0
+    vol.density = np.array(vol.density, np.float32)
+    i = np.arange(N)
+    ids = (1 + (i[:, None, None] + 2 * i[None, :, None] + 3 * i[None, None, :]) % 5).astype(np.uint8)
+    with np.errstate(invalid="ignore"):
+        vol.material_id = np.where(vol.density <= 0, ids, np.uint8(0)).astype(np.uint8)
+    vol.density.setflags(write=False)
+    vol.material_id.setflags(write=False)
+    return vol
+
+
+@functools.lru_cache(maxsize=None)
+def stored(kind: str, N: int, role: str, fmt: int) -> np.ndarray:
+    a = R.dense_field(volume(kind, N, role).density, fmt)
+    a.setflags(write=False)
+    return a
+
+
+def quat(axis, degrees: float):
+    a = np.asarray(axis, np.float64)
+    a = a / np.linalg.norm(a)
+    h = math.radians(degrees) / 2.0
+    return tuple(a * math.sin(h)) + (math.cos(h),)
+
+
+def axis_turns():
+    """Six of the 48 signed axis permutations, one per permutation, with the sign patterns cycling: 90 degree turns and mirrors."""
+    signs = list(itertools.product((1.0, -1.0), repeat=3))
+    out = []
+    for n, perm in enumerate(itertools.permutations(range(3))):
+        m = np.zeros((3, 3))
+        for a in range(3):
+            m[a, perm[a]] = signs[(3 * n + 1) % 8][a]
+        out.append(m)
+    return out
+
+
+def placements(Nd: int, Ns: int):
+    """[(name, dst_to_src as 12 floats, length_scale)]"""
+    cd, cs = (Nd - 1) / 2.0, (Ns - 1) / 2.0
+    eye = np.eye(3)
+    rigid = lambda lin, t: [float(x) for x in np.hstack([lin, np.asarray(t, np.float64).reshape(3, 1)]).reshape(-1)]
+    out = [("identity", rigid(eye, (0, 0, 0)), 1.0),
+           ("shift, half of the source off the grid", rigid(eye, (-(Nd - 1 - (Ns - 1) // 2), -2, 1)), 1.0)]
+    for n, m in enumerate(axis_turns()):
+        out.append((f"axis turn {n}", rigid(m, cs - m @ np.full(3, cd)), 1.0))
+    for n, (axis, deg, scale, shift) in enumerate((((1, 2, 3), 37.0, 0.5, (0.3, -0.4, 0.2)), ((-2, 1, 0.5), 112.0, 1.7, (-1.25, 0.6, 2.1)))):
+        rec = v.stamp_from_placement(Ns, np.full(3, cd) + shift, quat(axis, deg), scale)
+        out.append((f"oblique {n}, scale {scale}", list(rec.dst_to_src), float(rec.length_scale)))
+    big = 2.5 * Nd / Ns
+    rec = v.stamp_from_placement(Ns, np.full(3, cd) + (0.5, 0.25, -0.5), quat((3, -1, 2), 61.0), big)
+    out.append(("a source larger than the destination", list(rec.dst_to_src), float(rec.length_scale)))
+    rec = v.stamp_from_placement(Ns, (3.0 * Nd, cd, cd), quat((0, 0, 1), 20.0), 1.0)
+    out.append(("wholly outside", list(rec.dst_to_src), 1.0))
+    out.append(("u lands on Ns - 1", rigid(0.5 * eye, (0, 0, 0)), 2.0))
+    return out
+
+
+def record(op, matrix, length_scale, blend, material, offset, reach=3.0):
+    return v.stamp_record(op, matrix, length_scale, offset, blend, reach, material)
+
+
+def sweep(Nd: int, Ns: int):
+    """Every placement with every op; blend, material, offset and the source field cycle so that each value meets each op and each
+    placement somewhere in the sweep.  Yields (what, source field, destination field, record)."""
+    n = 0
+    for name, matrix, scale in placements(Nd, Ns):
+        for op in OPS:
+            blend, material, offset = BLENDS[n % 2], MATERIALS[(n // 2 + n) % 3], OFFSETS[(n // 3 + n) % 3]
+            field = FIELDS[(2 * n + n // 3) % 3]
+            yield (f"{name}, op {op}, blend {blend}, material {material}, offset {offset}, {field}", field,
+                   "hand" if field == "hand" else "torus", record(op, matrix, scale, blend, material, offset))
+            n += 1
+
+
+def parameter_cross(Nd: int, Ns: int):
+    """Ops x blend x material x offset at one oblique placement, sphere into torus."""
+    name, matrix, scale = placements(Nd, Ns)[8]
+    assert name.startswith("oblique 0")
+    for op, blend, material, offset in itertools.product(OPS, BLENDS, MATERIALS, OFFSETS):
+        yield f"op {op}, blend {blend}, material {material}, offset {offset}", "sphere", "torus", record(op, matrix, scale, blend, material, offset)
+
+
+def reference(src_kind, dst_kind, Nd, Ns, dfmt, sfmt, rec):
+    """(stored, material, result) of the destination after the record, by stamp_ref; fresh arrays."""
+    dst, src = volume(dst_kind, Nd, "dst"), volume(src_kind, Ns, "src")
+    d, m = np.array(stored(dst_kind, Nd, "dst", dfmt)), np.array(dst.material_id)
+    res = S.apply(d, m, dfmt, dst.VolumeExtends, dst.density_scale, stored(src_kind, Ns, "src", sfmt), src.material_id, sfmt,
+                  src.VolumeExtends, src.density_scale, rec)
+    return d, m, res

@@ -72,6 +72,10 @@ MAX_BRUSHES = 32
 BRUSH_SPHERE, BRUSH_BOX, BRUSH_CAPSULE = 0, 1, 2
 BRUSH_ADD, BRUSH_SUBTRACT, BRUSH_PAINT = 0, 1, 2
 
+# vrt_volume_stamp
+STAMP_ADD, STAMP_SUBTRACT, STAMP_REPLACE = 0, 1, 2
+STAMP_MATERIAL_KEEP, STAMP_MATERIAL_SOURCE = -1, -2
+
 QUERY_CLOSEST = 0
 QUERY_ANY = 1  # occlusion: instance 0 when some surface lies within [0, t_max]
 
@@ -224,6 +228,19 @@ class vrt_brush_result(C.Structure):
     _fields_ = [("lo", C.c_int32 * 3), ("hi", C.c_int32 * 3), ("written", C.c_uint64)]
 
 
+class vrt_stamp(C.Structure):
+    _fields_ = [
+        ("op", C.c_int32),
+        ("material", C.c_int32),
+        ("dst_to_src", C.c_float * 12),
+        ("length_scale", C.c_float),
+        ("offset", C.c_float),
+        ("blend", C.c_float),
+        ("reach", C.c_float),
+        ("reserved_", C.c_uint32 * 6),
+    ]
+
+
 class vrt_fill_result(C.Structure):
     _fields_ = [("lo", C.c_int32 * 3), ("hi", C.c_int32 * 3), ("filled", C.c_uint64), ("sweeps", C.c_uint32), ("reserved_", C.c_uint32)]
 
@@ -258,6 +275,7 @@ SYMBOLS = {
     "vrt_volume_update_region": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int), C.c_void_p, C.c_void_p]),
     "vrt_volume_update_voxels": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int), C.c_void_p]),
     "vrt_volume_apply_brushes": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.POINTER(vrt_brush), C.POINTER(vrt_brush_result)]),
+    "vrt_volume_stamp": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.POINTER(vrt_stamp), C.POINTER(vrt_brush_result)]),
     "vrt_volume_fill_enclosed": (C.c_int, [C.c_void_p, C.c_int, C.c_float, C.c_int, C.POINTER(vrt_fill_result)]),
     "vrt_volume_redistance": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int),
                                         C.POINTER(vrt_redistance_result)]),

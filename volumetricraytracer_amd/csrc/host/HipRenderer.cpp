@@ -396,6 +396,7 @@ void VHipRenderer::Stop() {
     vrt_destroy(Ctx);
     Ctx = nullptr;
     Uploaded.clear();
+    StampSource = nullptr;
     UploadedEnv = nullptr;
     for (bool& b : SlotBusy) b = false;
     FramePixels = nullptr;
@@ -503,6 +504,7 @@ bool VHipRenderer::SyncWithScene(Scene::VScene& scene) {
                                              reinterpret_cast<const vrt_voxel*>(v.GetVoxels().data())), "vrt_volume_upload_voxels"))
                 return false;
             Uploaded[slot] = &v;
+            if ((int)slot == StampSlot) StampSource = nullptr; /* the scene took the slot StampVolume keeps its source in */
         } else if (v.IsRegionDirty() && RegionUploads) {
             /* only a box changed (VVoxelVolume::MakeDirtyRegion): update it in place; the box's records in the volume's own order */
             const VIntVector lo = v.GetDirtyRegionMin(), hi = v.GetDirtyRegionMax();
@@ -795,6 +797,72 @@ bool VHipRenderer::ApplyBrushes(const Scene::VVoxelObject& object, const std::ve
     }
     vrt_brush_result res;
     if (!ok(vrt_volume_apply_brushes(Ctx, slot, (int)brushes.size(), brushes.data(), &res), "vrt_volume_apply_brushes")) return false;
+    if (result) *result = res;
+    if (res.written == 0) return true;
+    return MirrorBox(slot, *volume, res.lo, res.hi);
+}
+
+vrt_stamp VHipRenderer::StampFromPlacement(unsigned srcSize, const VVector& position, const VQuat& rotation, float scale, int op, int material,
+                                           float offset, float blend, float reach) {
+    vrt_stamp rec;
+    memset(&rec, 0, sizeof rec);
+    rec.op = op;
+    rec.material = material;
+    double x = rotation.x, y = rotation.y, z = rotation.z, w = rotation.w;
+    const double n = std::sqrt(x * x + y * y + z * z + w * w);
+    if (n > 0.0) x /= n, y /= n, z /= n, w /= n;
+    const double rot[3][3] = {{1 - 2 * (y * y + z * z), 2 * (x * y - z * w), 2 * (x * z + y * w)},
+                              {2 * (x * y + z * w), 1 - 2 * (x * x + z * z), 2 * (y * z - x * w)},
+                              {2 * (x * z - y * w), 2 * (y * z + x * w), 1 - 2 * (x * x + y * y)}};
+    const double pos[3] = {position.X, position.Y, position.Z}, centre = ((double)srcSize - 1.0) / 2.0;
+    for (int a = 0; a < 3; a++) {
+        double t = centre;
+        for (int b = 0; b < 3; b++) {
+            const double lin = rot[b][a] / (double)scale; /* R^T / scale */
+            rec.dst_to_src[4 * a + b] = (float)lin;
+            t -= lin * pos[b];
+        }
+        rec.dst_to_src[4 * a + 3] = (float)t;
+    }
+    rec.length_scale = scale;
+    rec.offset = offset;
+    rec.blend = blend;
+    rec.reach = reach;
+    return rec;
+}
+
+bool VHipRenderer::StampVolume(const Scene::VVoxelObject& dstObject, const Voxel::VVoxelVolume& srcVolume, const VVector& position,
+                               const VQuat& rotation, float scale, int op, int material, float offset, float blend, float reach,
+                               vrt_brush_result* result) {
+    if (!IsActive()) {
+        V_LOG_WARNING("StampVolume() on an inactive renderer");
+        return false;
+    }
+    const VObjectPtr<Scene::VScene> scene = SceneRef.lock();
+    const VObjectPtr<Voxel::VVoxelVolume> volume = dstObject.GetVoxelVolume();
+    if (!scene || !volume || volume.get() == &srcVolume || !(scale > 0.f)) return false;
+    if (!SyncWithScene(*scene)) return false;
+    const int slot = SlotOf(volume.get());
+    if (slot < 0 || SlotOf(&srcVolume) >= 0) {
+        V_LOG_ERROR("StampVolume(): the object's volume is not part of the rendered scene, or the source is");
+        return false;
+    }
+    if (scene->GetAllRegisteredVolumes().size() > (size_t)StampSlot) {
+        V_LOG_ERROR("StampVolume(): the scene uses the slot the stamped volume needs");
+        return false;
+    }
+    if (StampSource != &srcVolume || srcVolume.IsDirty() || StampSourceFormat != VolumeFormat) {
+        StampSource = nullptr;
+        if (!ok(vrt_volume_upload_voxels(Ctx, StampSlot, srcVolume.GetResolution(), srcVolume.GetVolumeExtends(),
+                                         reinterpret_cast<const vrt_voxel*>(srcVolume.GetVoxels().data())), "vrt_volume_upload_voxels"))
+            return false;
+        if (!ok(vrt_volume_set_metric(Ctx, StampSlot, srcVolume.DensityScale, 0.f), "vrt_volume_set_metric")) return false;
+        StampSource = &srcVolume;
+        StampSourceFormat = VolumeFormat;
+    }
+    const vrt_stamp rec = StampFromPlacement(srcVolume.GetSize(), position, rotation, scale, op, material, offset, blend, reach);
+    vrt_brush_result res;
+    if (!ok(vrt_volume_stamp(Ctx, slot, StampSlot, &rec, &res), "vrt_volume_stamp")) return false;
     if (result) *result = res;
     if (res.written == 0) return true;
     return MirrorBox(slot, *volume, res.lo, res.hi);

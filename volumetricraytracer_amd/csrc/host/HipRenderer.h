@@ -121,6 +121,23 @@ public:
        VRT_FORMAT_TEXEL16 the mirror receives the decoded texels (q * 0.01), which quantise again — and need not give q back — should
        the volume be uploaded whole later.  False (after logging) on failure or when the object's volume is not in the scene. */
     bool ApplyBrushes(const Scene::VVoxelObject& object, const std::vector<vrt_brush>& brushes, vrt_brush_result* result = nullptr);
+    /* CSG with an arbitrary shape on the device (vrt_volume_stamp; the rule: vrt.h): srcVolume — any volume, of any resolution, not one
+       of the rendered scene — merged into the volume of a placed object of the scene Render() would draw now (synced first).  The
+       source's centre sample is put at `position` (grid coordinates of the object's volume, xyz, fractions allowed), turned by
+       `rotation` about it, and one source cell covers `scale` cells of the object's volume; op: VRT_STAMP_ADD / _SUBTRACT / _REPLACE;
+       material: 0..255, VRT_STAMP_MATERIAL_KEEP or _SOURCE; offset, blend, reach: cells of the object's volume, as vrt_stamp takes
+       them.  The source lives in the spare slot StampSlot of the context: it is uploaded when it is another volume than at the last
+       call, when it IsDirty() (a new volume is: call its PostRender() once it is final to keep it resident) or when VolumeFormat
+       changed.  The written box is read back into the host VVoxelVolume like ApplyBrushes does.  False (after logging) on failure,
+       when the object's volume is not in the scene or when the scene itself needs StampSlot. */
+    static constexpr int StampSlot = VRT_MAX_VOLUMES - 2; /* the Voxelizer on the device keeps the last slot */
+    bool StampVolume(const Scene::VVoxelObject& dstObject, const Voxel::VVoxelVolume& srcVolume, const VVector& position, const VQuat& rotation,
+                     float scale, int op, int material = VRT_STAMP_MATERIAL_KEEP, float offset = 0.f, float blend = 0.f, float reach = 2.f,
+                     vrt_brush_result* result = nullptr);
+    /* The record StampVolume hands to vrt_volume_stamp: u = R^T (p - position) / scale + (srcSize - 1) / 2, built in double and
+       rounded once; length_scale = scale. */
+    static vrt_stamp StampFromPlacement(unsigned srcSize, const VVector& position, const VQuat& rotation, float scale, int op, int material,
+                                        float offset, float blend, float reach);
     /* The cavities a shell volume encloses made solid on the device (vrt_volume_fill_enclosed; the rule: vrt.h), on the volume of a
        placed object of the scene Render() would draw now (synced first): Voxelizer output, whose unsigned shell a SUBTRACT brush would
        otherwise open into an empty inside.  wall: the wall's thickness in density units (1 for Voxelizer shells); material: the id the
@@ -161,6 +178,8 @@ private:
     size_t FrameBytes = 0;
     std::vector<const Voxel::VVoxelVolume*> Uploaded; /* per slot */
     std::vector<Voxel::VVoxel> RegionStaging;          /* the box of a region update, packed */
+    const Voxel::VVoxelVolume* StampSource = nullptr;  /* what StampSlot holds */
+    int StampSourceFormat = -1;
     const VTextureCube* UploadedEnv = nullptr;
     struct TextureEntry {
         VObjectPtr<VTexture2D> Texture; /* null: lookup failed, do not retry */

@@ -4,6 +4,7 @@
 #include "../fill_core.h"
 #include "../mesh_core.h"
 #include "../redistance_core.h"
+#include "../stamp_core.h"
 #include "../voxelize_core.h"
 
 #include <algorithm>
@@ -236,6 +237,56 @@ VVolumeConverter::VSurfaceMesh VVolumeConverter::ExtractMesh(const Voxel::VVoxel
     const int lo[3] = {boxLo ? boxLo->X : 0, boxLo ? boxLo->Y : 0, boxLo ? boxLo->Z : 0};
     const int hi[3] = {boxHi ? boxHi->X : last, boxHi ? boxHi->Y : last, boxHi ? boxHi->Z : last};
     return ExtractMesh(volume.GetVoxels().data(), volume.GetSize(), volume.GetVolumeExtends(), false, iso, lo, hi);
+}
+
+VVolumeConverter::VStampResult VVolumeConverter::Stamp(Voxel::VVoxel* dst, size_t nd, float unitDst, bool dstTexel16, const Voxel::VVoxel* src,
+                                                       size_t ns, float unitSrc, bool srcTexel16, const ::vrt_stamp& stamp) {
+    namespace S = vrt_stamp_core;
+    const int N = (int)nd, Ns = (int)ns;
+    VStampResult out;
+    out.Lo = VIntVector(N, N, N);
+    out.Hi = VIntVector(-1, -1, -1);
+    int lo[3], hi[3];
+    if (!S::valid(stamp) || !S::footprint(stamp, Ns, N, lo, hi)) return out;
+    const S::Rule R = S::rule_of(stamp, Ns, unitDst, unitSrc);
+    const auto source_at = [&](int x, int y, int z) { return ((size_t)x * ns + (size_t)z) * ns + (size_t)y; };
+    for (int x = lo[0]; x <= hi[0]; x++)
+        for (int z = lo[2]; z <= hi[2]; z++)
+            for (int y = lo[1]; y <= hi[1]; y++) {
+                const float px = (float)x, py = (float)y, pz = (float)z;
+                const float u[3] = {S::source_coord(R.m, 0, px, py, pz), S::source_coord(R.m, 1, px, py, pz), S::source_coord(R.m, 2, px, py, pz)};
+                if (!S::inside(u[0], Ns) || !S::inside(u[1], Ns) || !S::inside(u[2], Ns)) continue;
+                const int c[3] = {S::cell_of(u[0], Ns), S::cell_of(u[1], Ns), S::cell_of(u[2], Ns)};
+                const float f[3] = {u[0] - (float)c[0], u[1] - (float)c[1], u[2] - (float)c[2]};
+                float s[8];
+                for (int j = 0; j < 8; j++) {
+                    const float raw = src[source_at(c[0] + (j & 1), c[1] + ((j >> 1) & 1), c[2] + (j >> 2))].Density;
+                    s[j] = srcTexel16 ? raw * 0.01f : raw;
+                }
+                Voxel::VVoxel& voxel = dst[((size_t)x * nd + (size_t)z) * nd + (size_t)y];
+                const float d = dstTexel16 ? voxel.Density * 0.01f : voxel.Density;
+                const float v = S::value(S::trilinear(s, f[0], f[1], f[2]), R.gain, R.off);
+                float m;
+                if (!S::merge(R.op, d, v, R.k, R.rv, m)) continue;
+                voxel.Density = dstTexel16 ? vrt_fill::texel16_value(m) : m;
+                if (R.material != VRT_STAMP_MATERIAL_KEEP) {
+                    unsigned id = 0u;
+                    if (R.material == VRT_STAMP_MATERIAL_SOURCE) id = src[source_at(S::nearest(c[0], f[0]), S::nearest(c[1], f[1]), S::nearest(c[2], f[2]))].Material;
+                    voxel.Material = (uint8_t)S::written_material(R.op, R.material, m, id);
+                }
+                out.Lo = VIntVector(std::min(out.Lo.X, x), std::min(out.Lo.Y, y), std::min(out.Lo.Z, z));
+                out.Hi = VIntVector(std::max(out.Hi.X, x), std::max(out.Hi.Y, y), std::max(out.Hi.Z, z));
+                out.Written++;
+            }
+    return out;
+}
+
+VVolumeConverter::VStampResult VVolumeConverter::Stamp(Voxel::VVoxelVolume& dst, const Voxel::VVoxelVolume& src, const ::vrt_stamp& stamp) {
+    const float unitDst = vrt_stamp_core::unit_of((int)dst.GetSize(), dst.GetVolumeExtends(), dst.DensityScale);
+    const float unitSrc = vrt_stamp_core::unit_of((int)src.GetSize(), src.GetVolumeExtends(), src.DensityScale);
+    const VStampResult out = Stamp(dst.GetVoxels().data(), dst.GetSize(), unitDst, false, src.GetVoxels().data(), src.GetSize(), unitSrc, false, stamp);
+    if (out.Written) dst.MakeDirty();
+    return out;
 }
 
 bool VVolumeConverter::ExtractResolutionFromName(const std::string& name, uint8_t& outResolution) {

@@ -17,6 +17,7 @@
 #include "VoxelizerTypes.h"
 
 struct vrt_ctx; /* include/vrt.h */
+struct vrt_stamp;
 
 namespace VolumeRaytracer {
 namespace Voxelizer {
@@ -83,6 +84,21 @@ public:
     /* The same on n^3 VVoxel records (index x*n*n + z*n + y) over the samples lo..hi (xyz, inclusive, inside the grid); extent: the
        volume's half size; texel16: the records hold the integer field +-q of a VRT_FORMAT_TEXEL16 slot. */
     static VSurfaceMesh ExtractMesh(const Voxel::VVoxel* voxels, size_t n, float extent, bool texel16, float iso, const int lo[3], const int hi[3]);
+    /* What Stamp wrote: the samples' count and their inclusive xyz box (Lo > Hi when none). */
+    struct VStampResult {
+        VIntVector Lo, Hi;
+        size_t Written = 0;
+    };
+    /* CSG of one volume into another, in place — the rule of vrt_volume_stamp (include/vrt.h; its arithmetic is csrc/stamp_core.h,
+       shared with the HIP kernel), as a plain loop over the footprint of the source's box: every sample of `dst` that the record's
+       matrix takes into `src` merges the trilinear sample of `src` there (ADD / SUBTRACT / REPLACE).  Lengths become density units
+       through the two volumes' DensityScale.  Marks `dst` dirty when it wrote.  The record must be one vrt_volume_stamp accepts
+       (vrt_stamp_core::valid); otherwise nothing is written. */
+    static VStampResult Stamp(Voxel::VVoxelVolume& dst, const Voxel::VVoxelVolume& src, const ::vrt_stamp& stamp);
+    /* The same on nd^3 and ns^3 VVoxel records (index x*n*n + z*n + y); unit: density units per cell of each grid; texel16: that
+       grid's records hold the integer field +-q of a VRT_FORMAT_TEXEL16 slot. */
+    static VStampResult Stamp(Voxel::VVoxel* dst, size_t nd, float unitDst, bool dstTexel16, const Voxel::VVoxel* src, size_t ns, float unitSrc,
+                              bool srcTexel16, const ::vrt_stamp& stamp);
     static bool ExtractResolutionFromName(const std::string& name, uint8_t& outResolution);
     /* extraction threshold of a volume: cell size · √3 (VolumeConverter.cpp:57) */
     static float ExtractionThreshold(const Voxel::VVoxelVolume& volume);

@@ -17,6 +17,9 @@
  *            [--edit-full]                  ... and uploads the whole volume after every edit instead (the same frames)
  *            [--edit-device]                with --edit-brush: the carve is one SUBTRACT sphere record evaluated on the device
  *                                           (VHipRenderer::ApplyBrushes, vrt_volume_apply_brushes); no host loop, no box upload
+ *            [--edit-stamp]                 with --edit-brush: instead of the analytic sphere a 33^3 torus SDF, uploaded once into a spare slot, is stamped
+ *                                           with SUBTRACT at the brush or pick position, R cells across its outer radius and turned a little further every
+ *                                           frame (VHipRenderer::StampVolume, vrt_volume_stamp): an arbitrary shape carved on the device; implies --edit-device
  *            [--solid]                      the red sphere is built as the Voxelizer builds a mesh — an unsigned shell, density = |distance to its surface| / thr - 0.5
  *                                           with thr = cell * sqrt 3, positive again inside — and, after the upload, every volume of the scene has its enclosed
  *                                           cavities filled on the device (VHipRenderer::FillEnclosed, vrt_volume_fill_enclosed; wall 1, material 1): --edit-brush
@@ -68,6 +71,25 @@ static VObjectPtr<Scene::VVoxelObject> InitSphere(Scene::VScene& scene, float ra
     return obj;
 }
 
+/* The shape --edit-stamp carves with: a torus around z, ring 9 cells out, tube 3.5 cells, as a true distance in cells on 33^3 samples
+   (cell 1, so one density unit is one cell); 3.5 cells of margin around it for the stamp's reach. */
+constexpr float kStampOuter = 12.5f;
+static std::shared_ptr<Voxel::VVoxelVolume> InitStampTorus() {
+    auto volume = std::make_shared<Voxel::VVoxelVolume>(5, 16.f);
+    const int n = (int)volume->GetSize();
+    for (int x = 0; x < n; x++)
+        for (int y = 0; y < n; y++)
+            for (int z = 0; z < n; z++) {
+                const VVector p = volume->VoxelIndexToRelativePosition(VIntVector(x, y, z));
+                const float ring = std::sqrt(p.X * p.X + p.Y * p.Y) - 9.f;
+                Voxel::VVoxel v;
+                v.Density = std::sqrt(ring * ring + p.Z * p.Z) - 3.5f;
+                v.Material = v.Density <= 0 ? 1 : 0;
+                volume->SetVoxel(VIntVector(x, y, z), v);
+            }
+    return volume;
+}
+
 static VObjectPtr<VTextureCube> ProceduralSky(size_t S) {
     std::vector<uint8_t> px(6 * S * S * 4);
     const float tint[6][3] = {{1.f, .85f, .8f}, {.8f, .85f, 1.f}, {.85f, 1.f, .8f}, {1.f, .8f, 1.f}, {.6f, .75f, 1.f}, {.55f, .5f, .45f}};
@@ -89,7 +111,7 @@ int main(int argc, char** argv) {
     std::string scenePath, skyboxDir, outPath = "vrt_demo.ppm", meshOut;
     bool identityDefaults = false;
     int editBrush = 0, sdf = 0;
-    bool editFull = false, editDevice = false, solid = false;
+    bool editFull = false, editDevice = false, editStamp = false, solid = false;
     bool pick = false;
     int pickX = 0, pickY = 0;
     int mode = 0, inFlight = 3, block = 0; /* three frames in flight: the reference's swap chain (FrameCount, DXConstants.cpp:23) */
@@ -109,6 +131,7 @@ int main(int argc, char** argv) {
         else if (!strcmp(argv[i], "--edit-brush") && i + 1 < argc) editBrush = atoi(argv[++i]);
         else if (!strcmp(argv[i], "--edit-full")) editFull = true;
         else if (!strcmp(argv[i], "--edit-device")) editDevice = true;
+        else if (!strcmp(argv[i], "--edit-stamp")) editStamp = editDevice = true;
         else if (!strcmp(argv[i], "--solid")) solid = true;
         else if (!strcmp(argv[i], "--sdf") && i + 1 < argc) sdf = atoi(argv[++i]);
         else if (!strcmp(argv[i], "--mesh-out") && i + 1 < argc) meshOut = argv[++i];
@@ -170,6 +193,10 @@ int main(int argc, char** argv) {
         fprintf(stderr, "--edit-brush edits the volume every frame: RenderBlock refuses that; drop --block\n");
         return 1;
     }
+    if (editStamp && (!hip || editBrush <= 0)) {
+        fprintf(stderr, "--edit-stamp stamps on the device where --edit-brush R would dab: it needs the HIP renderer and --edit-brush\n");
+        return 1;
+    }
     if (editDevice && !hip) editDevice = false;
     if (pick && (!hip || block > 0)) {
         fprintf(stderr, "--pick asks the HIP renderer once per frame: drop --block\n");
@@ -213,22 +240,34 @@ int main(int argc, char** argv) {
         scene->PostRender();
         printf("sdf: band %d, %llu surfels, %llu voxels nearer than the band, redistanced on the device\n", sdf, surfels, near);
     }
+    const std::shared_ptr<Voxel::VVoxelVolume> stampTorus = editStamp ? InitStampTorus() : nullptr;
+    int stampTurns = 0;
+    unsigned long long stampedVoxels = 0;
     double kernel_ms = 0.0;
     bool warmUp = true; /* the untimed first frame prints no pick record */
     /* the brush: a sphere of editBrush cells around voxel c — a point that circles the red sphere's centre 12 cells out, 4 cells above
        it, or (--pick) the voxel under the picked pixel; union (CSG difference) with the field, the box it can change marked dirty */
     auto carve = [&](const VIntVector& c) {
-        if (editDevice) { /* the same sphere as one brush record: hard SUBTRACT, corrected two cells beyond its surface, material 0 */
-            vrt_brush b;
-            memset(&b, 0, sizeof b);
-            b.shape = VRT_BRUSH_SPHERE;
-            b.op = VRT_BRUSH_SUBTRACT;
-            b.a[0] = (float)c.X, b.a[1] = (float)c.Y, b.a[2] = (float)c.Z;
-            b.radius = (float)editBrush;
-            b.reach = 2.f;
-            b.material = 0;
+        if (editDevice) {
             vrt_brush_result wrote;
-            if (hip->ApplyBrushes(*sphere1, {b}, &wrote) && sdf > 0 && wrote.written > 0) { /* the dab's box grown by the band, a distance again */
+            bool done;
+            if (editStamp) { /* the torus, editBrush cells across its outer radius, a third of a radian further round every time: hard SUBTRACT */
+                const VQuat turn = VQuat::FromAxisAngle(VVector::UP, 0.35f * (float)stampTurns++) * VQuat::FromAxisAngle(VVector::RIGHT, 0.5f);
+                done = hip->StampVolume(*sphere1, *stampTorus, VVector((float)c.X, (float)c.Y, (float)c.Z), turn, (float)editBrush / kStampOuter,
+                                        VRT_STAMP_SUBTRACT, 0, 0.f, 0.f, 2.f, &wrote);
+                if (done) stampTorus->PostRender(), stampedVoxels += wrote.written; /* final: it stays resident in its slot */
+            } else { /* the same sphere as one brush record: hard SUBTRACT, corrected two cells beyond its surface, material 0 */
+                vrt_brush b;
+                memset(&b, 0, sizeof b);
+                b.shape = VRT_BRUSH_SPHERE;
+                b.op = VRT_BRUSH_SUBTRACT;
+                b.a[0] = (float)c.X, b.a[1] = (float)c.Y, b.a[2] = (float)c.Z;
+                b.radius = (float)editBrush;
+                b.reach = 2.f;
+                b.material = 0;
+                done = hip->ApplyBrushes(*sphere1, {b}, &wrote);
+            }
+            if (done && sdf > 0 && wrote.written > 0) { /* the dab's box grown by the band, a distance again */
                 const VIntVector lo(wrote.lo[0] - sdf, wrote.lo[1] - sdf, wrote.lo[2] - sdf), hi(wrote.hi[0] + sdf, wrote.hi[1] + sdf, wrote.hi[2] + sdf);
                 vrt_redistance_result res;
                 if (hip->Redistance(*sphere1, sdf, VRT_REDISTANCE_FROM_OUTSIDE, &lo, &hi, &res)) dabSurfels += res.surfels, dabSamples += res.written;
@@ -307,7 +346,9 @@ int main(int argc, char** argv) {
     }
     const double wall = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
     if (sdf > 0 && editDevice && editBrush > 0) printf("sdf: %llu voxels redistanced around the dabs from %llu surfels\n", dabSamples, dabSurfels);
-    if (editBrush > 0) printf("brush of %d cells, %s; ", editBrush, editDevice ? "device brushes" : (editFull ? "full uploads" : "region updates"));
+    if (editStamp) printf("stamp: %d torus stamps wrote %llu voxels on the device\n", stampTurns, stampedVoxels);
+    if (editBrush > 0)
+        printf("brush of %d cells, %s; ", editBrush, editStamp ? "device stamps" : (editDevice ? "device brushes" : (editFull ? "full uploads" : "region updates")));
     printf("%d frames %ux%u %s%s: %.3f ms/frame wall (%.0f frames/s)", frames, W, H, format.c_str(),
            block > 0 ? (", RenderBlock of " + std::to_string(block)).c_str() : (", " + std::to_string(inFlight) + " in flight").c_str(), wall / frames * 1e3, frames / wall);
     if (kernel_ms > 0.0) printf(", march kernel %.3f ms/%s", kernel_ms / (block > 0 ? (frames + block - 1) / block : frames), block > 0 ? "block" : "frame");

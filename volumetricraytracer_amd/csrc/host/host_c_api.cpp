@@ -12,6 +12,7 @@
 #include "HostSerialization.h"
 #include "SceneConverter.h"
 #include "VolumeConverter.h"
+#include "../stamp_core.h"
 
 using namespace VolumeRaytracer;
 
@@ -154,6 +155,23 @@ int vrh_extract_mesh(const vrt_voxel* voxels, int n, float extent, int texel16, 
     if (materials_or_null && m.Vertices()) memcpy(materials_or_null, m.Materials.data(), m.Materials.size());
     if (indices_or_null && !m.Indices.empty()) memcpy(indices_or_null, m.Indices.data(), m.Indices.size() * sizeof(uint32_t));
     return 0;
+}
+
+/* VVolumeConverter::Stamp on caller records: nd^3 destination records edited in place and ns^3 source records only read (index
+   x*n*n + z*n + y); extent and density_scale of each grid give its density units per cell as vrt_volume_stamp derives them; texel16 != 0:
+   that grid's densities are the integer field +-q; result_or_null as vrt_volume_stamp reports.  The record passes the argument rules of
+   vrt_volume_stamp: VRT_OK, or VRT_ERR_INVALID as that call returns it (a NULL pointer or a grid below 2 samples likewise). */
+int vrh_stamp(vrt_voxel* dst, int nd, float dst_extent, float dst_density_scale, int dst_texel16, const vrt_voxel* src, int ns, float src_extent,
+              float src_density_scale, int src_texel16, const vrt_stamp* stamp, vrt_brush_result* result_or_null) {
+    if (!dst || !src || !stamp || nd < 2 || ns < 2 || dst == src || !vrt_stamp_core::valid(*stamp)) {
+        g_error = "vrh_stamp: bad argument";
+        return VRT_ERR_INVALID;
+    }
+    const auto r = Voxelizer::VVolumeConverter::Stamp(reinterpret_cast<Voxel::VVoxel*>(dst), (size_t)nd, vrt_stamp_core::unit_of(nd, dst_extent, dst_density_scale),
+                                                      dst_texel16 != 0, reinterpret_cast<const Voxel::VVoxel*>(src), (size_t)ns,
+                                                      vrt_stamp_core::unit_of(ns, src_extent, src_density_scale), src_texel16 != 0, *stamp);
+    if (result_or_null) *result_or_null = vrt_brush_result{{r.Lo.X, r.Lo.Y, r.Lo.Z}, {r.Hi.X, r.Hi.Y, r.Hi.Z}, (uint64_t)r.Written};
+    return VRT_OK;
 }
 
 /* VGLTFImporter::ImportScene on a .gltf / .glb file, mesh `mesh` (its index in the file): counts_out[2] = vertices, indices; the

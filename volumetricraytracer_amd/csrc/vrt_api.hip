@@ -27,6 +27,7 @@
 #include "vrt_launch.h"
 #include "voxelize_core.h"
 #include "redistance_core.h"
+#include "stamp_core.h"
 
 using namespace vrt;
 
@@ -91,6 +92,7 @@ static_assert(kDynMaxInstances == VRT_MAX_INSTANCES && kMaxBvhNodes == 2 * VRT_M
 static_assert(kDynMaxPointLights == VRT_MAX_POINT_LIGHTS && kDynMaxSpotLights == VRT_MAX_SPOT_LIGHTS, "section capacity = VRT_MAX_*_LIGHTS");
 static_assert(sizeof(vrt_ray) == 32 && sizeof(vrt_hit) == 48, "query_kernel reads two and writes three 16-B words per ray");
 static_assert(sizeof(vrt_brush) == 64 && sizeof(vrt_brush_result) == 32, "vrt.h states these sizes");
+static_assert(sizeof(vrt_stamp) == 96, "vrt.h states this size");
 static_assert(sizeof(vrt_fill_result) == 40, "vrt.h states this size");
 static_assert(sizeof(vrt_redistance_result) == 48, "vrt.h states this size");
 static_assert(sizeof(vrt_mesh_result) == 40, "vrt.h states this size");
@@ -944,6 +946,58 @@ int apply_brushes(vrt_ctx* ctx, int slot, int n_rec, const vrt_brush* rec, vrt_b
         if (rc != VRT_OK) return rc;
     }
     if (!density_changed) return VRT_OK;
+    ctx->scene_stale = true;
+    return sync_volume_table(ctx);
+}
+
+/* vrt_volume_stamp: the source slot's dense grid gathered into the destination's over the footprint of the source's box
+ * (launch_stamp_region), which reports the box of the samples it wrote; what the destination derives from its samples is then
+ * recomputed over that box (rebuild_derived) — or not at all when nothing was written.  The source slot is only read.  Afterwards
+ * every buffer of the destination equals what upload_volume builds from the edited volume. */
+int stamp_volume(vrt_ctx* ctx, int dst_slot, int src_slot, const vrt_stamp* rec, vrt_brush_result* result) {
+    if (!ctx || !rec || dst_slot == src_slot || !vrt_stamp_core::valid(*rec)) return VRT_ERR_INVALID;
+    if (!valid_slot(dst_slot) || !valid_slot(src_slot) || !ctx->vol[dst_slot].used || !ctx->vol[src_slot].used) return VRT_ERR_SLOT;
+    HostVolume& h = ctx->vol[dst_slot];
+    const HostVolume& hs = ctx->vol[src_slot];
+    const int N = h.N;
+    if (result) *result = vrt_brush_result{{N, N, N}, {-1, -1, -1}, 0};
+    int lo[3], hi[3];
+    if (!vrt_stamp_core::footprint(*rec, hs.N, N, lo, hi)) return VRT_OK; /* wholly outside the grid */
+    const vrt_stamp_core::Rule rule = vrt_stamp_core::rule_of(*rec, hs.N, vrt_stamp_core::unit_of(N, h.extent, h.density_scale),
+                                                    vrt_stamp_core::unit_of(hs.N, hs.extent, hs.density_scale));
+    const EditBox foot = derived_boxes(h, lo, hi).samples;
+    for (auto& D : ctx->dev) { /* frames already enqueued render the old volume; the only allocation comes before any write */
+        HIP_TRY(hipSetDevice(D.ordinal));
+        HIP_TRY(hipDeviceSynchronize());
+        if (!D.d_brush) HIP_TRY(hipMalloc(&D.d_brush, kBrushSlots * sizeof(DBrushSlot)));
+    }
+    bool any_written = false;
+    for (size_t di = 0; di < ctx->dev.size(); di++) {
+        DeviceState& D = ctx->dev[di];
+        HIP_TRY(hipSetDevice(D.ordinal));
+        DeviceVolume& v = D.vol[dst_slot];
+        const DeviceVolume& vs = D.vol[src_slot];
+        HIP_TRY(launch_stamp_region(rule, hs.format == VRT_FORMAT_TEXEL16, vs.dense, vs.material, h.format == VRT_FORMAT_TEXEL16, v.dense,
+                                    v.material, N, foot, D.d_brush, D.stream));
+        DBrushSlot part[kBrushSlots];
+        HIP_TRY(hipMemcpyAsync(part, D.d_brush, sizeof part, hipMemcpyDeviceToHost, D.stream));
+        HIP_TRY(hipStreamSynchronize(D.stream));
+        vrt_brush_result got = {{N, N, N}, {-1, -1, -1}, 0}; /* the partial records merged */
+        for (const DBrushSlot& p : part) {
+            for (int a = 0; a < 3; a++) {
+                got.lo[a] = std::min(got.lo[a], N - (int)p.inv_lo[a]);
+                got.hi[a] = std::max(got.hi[a], (int)p.hi1[a] - 1);
+            }
+            got.written += p.counts & 0xffffffffull;
+        }
+        if (di == 0 && result) *result = got;
+        if (got.written == 0) continue; /* every written sample is a density write: nothing written, nothing derived changes */
+        any_written = true;
+        const DerivedBoxes written = derived_boxes(h, got.lo, got.hi);
+        int rc = rebuild_derived(ctx, D, dst_slot, &written, false, h.abox);
+        if (rc != VRT_OK) return rc;
+    }
+    if (!any_written) return VRT_OK;
     ctx->scene_stale = true;
     return sync_volume_table(ctx);
 }
@@ -1824,6 +1878,10 @@ int vrt_volume_update_voxels(vrt_ctx* ctx, int slot, const int origin_xyz[3], co
 
 int vrt_volume_apply_brushes(vrt_ctx* ctx, int slot, int n, const vrt_brush* brushes, vrt_brush_result* result_or_null) {
     return apply_brushes(ctx, slot, n, brushes, result_or_null);
+}
+
+int vrt_volume_stamp(vrt_ctx* ctx, int dst_slot, int src_slot, const vrt_stamp* stamp, vrt_brush_result* result_or_null) {
+    return stamp_volume(ctx, dst_slot, src_slot, stamp, result_or_null);
 }
 
 int vrt_volume_fill_enclosed(vrt_ctx* ctx, int slot, float wall, int material, vrt_fill_result* result_or_null) {

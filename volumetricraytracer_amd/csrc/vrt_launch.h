@@ -6,6 +6,10 @@
 #include "../../include/vrt.h"
 #include "vrt_device.h"
 
+namespace vrt_stamp_core {
+struct Rule; /* stamp_core.h */
+}
+
 namespace vrt {
 
 /* path: VRT_PATH_DENSE / VRT_PATH_BRICK / VRT_PATH_BRICK_LDS / kPathCube / kPathBrick16 / kPathCube16 (already resolved,
@@ -129,6 +133,13 @@ hipError_t launch_redistance_surfels(const float* dense, bool texel16, int N, in
    box and count as launch_brush_region reports them, with the count of samples nearer than the band in the high half of `counts`. */
 hipError_t launch_redistance_distance(bool texel16, float* dense, int N, int band, float unit, const EditBox& box, const void* table,
                                       const void* surfels, DBrushSlot* slots, hipStream_t stream);
+
+/* vrt_volume_stamp (vrt_stamp.hip): the rule of stamp_core.h over the destination samples of `box` (the footprint: outside it the
+   source's box cannot be hit), in place; the source's dense and material grids are only read and must not be the destination's.
+   slots: zeroed, then the written samples' counts and box as launch_brush_region reports them. */
+hipError_t launch_stamp_region(const vrt_stamp_core::Rule& rule, bool src_texel16, const float* src_dense, const uint8_t* src_material,
+                               bool dst_texel16, float* dense, uint8_t* material, int N, const EditBox& box, DBrushSlot* slots,
+                               hipStream_t stream);
 
 /* vrt_volume_extract_mesh (vrt_mesh.hip).  The cell box of a sample box, in xyz order (the mesh rule's own): its first cell, its cells
    per axis (one less than the samples; none when the box is one sample thick somewhere) and how many runs of 64 cells a row along y has. */

@@ -1,0 +1,105 @@
+/* vrt_stamp.hip — the kernel of vrt_volume_stamp (include/vrt.h): CSG of one resident volume into another.  Every sample of the
+ * footprint box of the destination is taken through the caller's matrix into the source's grid, the source's dense grid is sampled
+ * trilinearly there, and the value is merged into the destination by the rule of stamp_core.h (shared with the host pass).
+ *
+ * The eight taps of a lane depend on its own address and share nothing with its neighbours' under a rotation, so there is no tile to
+ * stage: the kernel keeps few registers and lets occupancy hide the gather.  Lanes run along y, the dense grid's fastest axis, so the
+ * destination's loads and stores coalesce whatever the matrix is. */
+#include <hip/hip_runtime.h>
+
+#include <algorithm>
+
+#include "stamp_core.h"
+#include "vrt_launch.h"
+
+namespace vrt {
+
+namespace {
+
+/* One lane per sample of the footprint box, y fastest: blockIdx.y walks the box's x slabs, blockIdx.x and the lanes a slab's z rows of
+ * y, so the index arithmetic stays in 32 bits (a slab holds fewer than 2^32 samples).  A lane outside the source goes on before it
+ * touches the destination, and so does a wave of them.  A sample that is not written keeps its stored bits.  The written samples'
+ * count and box are reduced across the wave first; a wave that wrote then reports with one atomic per word to one of kBrushSlots
+ * partial records, as the brushes do. */
+template <bool SRC16, bool DST16>
+__global__ __launch_bounds__(256) void stamp_region_kernel(vrt_stamp_core::Rule R, const float* __restrict__ src, const uint8_t* __restrict__ src_material,
+                                                           float* __restrict__ dense, uint8_t* __restrict__ material, int N, EditBox b,
+                                                           DBrushSlot* __restrict__ slots) {
+    namespace S = vrt_stamp_core;
+    const unsigned ny = (unsigned)b.n[2], slab = (unsigned)b.n[1] * ny;
+    const unsigned stride = gridDim.x * blockDim.x;
+    const int ns = R.ns;
+    unsigned inv_lo_x = 0u, inv_lo_y = 0u, inv_lo_z = 0u, hi1_x = 0u, hi1_y = 0u, hi1_z = 0u; /* N - lowest, 1 + highest: 0 = none */
+    unsigned n_written = 0u;
+    for (unsigned sx = blockIdx.y; sx < (unsigned)b.n[0]; sx += gridDim.y)
+        for (unsigned i = blockIdx.x * blockDim.x + threadIdx.x; i < slab; i += stride) {
+            const unsigned row = i / ny;
+            const int y = b.lo[2] + (int)(i - row * ny);
+            const int z = b.lo[1] + (int)row;
+            const int x = b.lo[0] + (int)sx;
+            const float px = (float)x, py = (float)y, pz = (float)z;
+            const float ux = S::source_coord(R.m, 0, px, py, pz), uy = S::source_coord(R.m, 1, px, py, pz), uz = S::source_coord(R.m, 2, px, py, pz);
+            if (!(S::inside(ux, ns) && S::inside(uy, ns) && S::inside(uz, ns))) continue;
+            const int cx = S::cell_of(ux, ns), cy = S::cell_of(uy, ns), cz = S::cell_of(uz, ns);
+            const float fx = ux - (float)cx, fy = uy - (float)cy, fz = uz - (float)cz;
+            /* the source's grid is [x][z][y] like every dense grid: 0 <= c <= ns - 2 on every axis, so all eight taps lie inside it */
+            const size_t at = ((size_t)cx * ns + (size_t)cz) * ns + (size_t)cy;
+            const size_t tx = (size_t)ns * ns, tz = (size_t)ns;
+            float s[8];
+#pragma unroll
+            for (int j = 0; j < 8; j++) {
+                const float raw = src[at + (j & 1 ? tx : 0) + (j & 2 ? 1 : 0) + (j & 4 ? tz : 0)];
+                s[j] = SRC16 ? raw * 0.01f : raw;
+            }
+            const size_t g = ((size_t)x * N + z) * N + y;
+            const float stored = dense[g];
+            const float d = DST16 ? stored * 0.01f : stored;
+            const float v = S::value(S::trilinear(s, fx, fy, fz), R.gain, R.off);
+            float m;
+            if (!S::merge(R.op, d, v, R.k, R.rv, m)) continue;
+            dense[g] = DST16 ? vrt_fill::texel16_value(m) : m;
+            if (R.material != VRT_STAMP_MATERIAL_KEEP) {
+                unsigned id = 0u;
+                if (R.material == VRT_STAMP_MATERIAL_SOURCE)
+                    id = src_material[((size_t)S::nearest(cx, fx) * ns + (size_t)S::nearest(cz, fz)) * ns + (size_t)S::nearest(cy, fy)];
+                material[g] = (uint8_t)S::written_material(R.op, R.material, m, id);
+            }
+            n_written++;
+            inv_lo_x = max(inv_lo_x, (unsigned)(N - x)), inv_lo_y = max(inv_lo_y, (unsigned)(N - y)), inv_lo_z = max(inv_lo_z, (unsigned)(N - z));
+            hi1_x = max(hi1_x, (unsigned)(x + 1)), hi1_y = max(hi1_y, (unsigned)(y + 1)), hi1_z = max(hi1_z, (unsigned)(z + 1));
+        }
+    for (int o = 32; o > 0; o >>= 1) {
+        n_written += __shfl_xor(n_written, o);
+        inv_lo_x = max(inv_lo_x, __shfl_xor(inv_lo_x, o)), inv_lo_y = max(inv_lo_y, __shfl_xor(inv_lo_y, o));
+        inv_lo_z = max(inv_lo_z, __shfl_xor(inv_lo_z, o));
+        hi1_x = max(hi1_x, __shfl_xor(hi1_x, o)), hi1_y = max(hi1_y, __shfl_xor(hi1_y, o)), hi1_z = max(hi1_z, __shfl_xor(hi1_z, o));
+    }
+    if ((threadIdx.x & 63u) == 0u && n_written != 0u) {
+        DBrushSlot* slot = slots + (((blockIdx.y * gridDim.x + blockIdx.x) * (blockDim.x >> 6) + (threadIdx.x >> 6)) & (unsigned)(kBrushSlots - 1));
+        atomicAdd(&slot->counts, ((unsigned long long)n_written << 32) | (unsigned long long)n_written); /* every write is a density write */
+        atomicMax(&slot->inv_lo[0], inv_lo_x), atomicMax(&slot->inv_lo[1], inv_lo_y), atomicMax(&slot->inv_lo[2], inv_lo_z);
+        atomicMax(&slot->hi1[0], hi1_x), atomicMax(&slot->hi1[1], hi1_y), atomicMax(&slot->hi1[2], hi1_z);
+    }
+}
+
+}  // namespace
+
+hipError_t launch_stamp_region(const vrt_stamp_core::Rule& rule, bool src_texel16, const float* src_dense, const uint8_t* src_material,
+                               bool dst_texel16, float* dense, uint8_t* material, int N, const EditBox& box, DBrushSlot* slots,
+                               hipStream_t stream) {
+    hipError_t e = hipMemsetAsync(slots, 0, kBrushSlots * sizeof(DBrushSlot), stream);
+    if (e != hipSuccess) return e;
+    const size_t slab = (size_t)box.n[1] * box.n[2];
+    const dim3 g((unsigned)std::max<size_t>(1, std::min<size_t>((slab + 255) / 256, 1u << 12)), (unsigned)std::max(1, std::min(box.n[0], 1 << 12))), t(256);
+    if (src_texel16 && dst_texel16)
+        hipLaunchKernelGGL((stamp_region_kernel<true, true>), g, t, 0, stream, rule, src_dense, src_material, dense, material, N, box, slots);
+    else if (src_texel16)
+        hipLaunchKernelGGL((stamp_region_kernel<true, false>), g, t, 0, stream, rule, src_dense, src_material, dense, material, N, box, slots);
+    else if (dst_texel16)
+        hipLaunchKernelGGL((stamp_region_kernel<false, true>), g, t, 0, stream, rule, src_dense, src_material, dense, material, N, box, slots);
+    else
+        hipLaunchKernelGGL((stamp_region_kernel<false, false>), g, t, 0, stream, rule, src_dense, src_material, dense, material, N, box, slots);
+    return hipGetLastError();
+}
+
+}  // namespace vrt

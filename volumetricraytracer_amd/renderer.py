@@ -66,6 +66,40 @@ def capsule_brush(op: int, end_a, end_b, radius: float, blend: float = 0.0, reac
     return _brush(_abi.BRUSH_CAPSULE, op, end_a, end_b, radius, blend, reach, material)
 
 
+def stamp_record(op: int, dst_to_src, length_scale: float = 1.0, offset: float = 0.0, blend: float = 0.0, reach: float = 2.0,
+                 material: int = _abi.STAMP_MATERIAL_KEEP) -> _abi.vrt_stamp:
+    """A vrt_stamp record from the matrix itself: dst_to_src is the row-major 3x4 matrix (12 values, or a [3, 4] array) that takes
+    destination grid coordinates (x, y, z) to source grid coordinates; lengths in cells of the destination (vrt.h)."""
+    m = np.asarray(dst_to_src, dtype=np.float64).reshape(12)
+    r = _abi.vrt_stamp()
+    r.op, r.material = int(op), int(material)
+    for i in range(12):
+        r.dst_to_src[i] = float(m[i])
+    r.length_scale, r.offset, r.blend, r.reach = float(length_scale), float(offset), float(blend), float(reach)
+    return r
+
+
+def stamp_from_placement(src_N: int, position, rotation_xyzw=(0.0, 0.0, 0.0, 1.0), scale: float = 1.0, op: int = _abi.STAMP_ADD,
+                         offset: float = 0.0, blend: float = 0.0, reach: float = 2.0, material: int = _abi.STAMP_MATERIAL_KEEP) -> _abi.vrt_stamp:
+    """A vrt_stamp record that places a source of src_N^3 samples in the destination's grid: the source's centre sample sits at
+    `position` (destination grid coordinates xyz, fractions allowed), turned by the quaternion `rotation_xyzw` about it, and one
+    source cell covers `scale` destination cells.  The matrix u = R^T (p - position) / scale + (src_N - 1) / 2 is built in double
+    and rounded to fp32 once; length_scale = scale."""
+    x, y, z, w = (float(c) for c in rotation_xyzw)
+    n = (x * x + y * y + z * z + w * w) ** 0.5
+    if not n > 0.0 or not float(scale) > 0.0:
+        raise ValueError("stamp_from_placement: a zero quaternion or a scale that is not positive")
+    x, y, z, w = x / n, y / n, z / n, w / n
+    rot = np.array([[1 - 2 * (y * y + z * z), 2 * (x * y - z * w), 2 * (x * z + y * w)],
+                    [2 * (x * y + z * w), 1 - 2 * (x * x + z * z), 2 * (y * z - x * w)],
+                    [2 * (x * z - y * w), 2 * (y * z + x * w), 1 - 2 * (x * x + y * y)]], np.float64)
+    lin = rot.T / float(scale)
+    m = np.zeros((3, 4), np.float64)
+    m[:, :3] = lin
+    m[:, 3] = -lin @ np.asarray(position, np.float64).reshape(3) + (int(src_N) - 1) / 2.0
+    return stamp_record(op, m, scale, offset, blend, reach, material)
+
+
 class VHipRenderer:
     def __init__(self, devices: Sequence[int] = (0,)):
         self._lib = _abi.load()
@@ -236,6 +270,20 @@ class VHipRenderer:
         lo, hi = tuple(res.lo), tuple(res.hi)
         if res.written and vol is not None:
             self._mirror_box(slot, vol, lo, hi)
+        return {"written": int(res.written), "lo": lo, "hi": hi}
+
+    def stamp_volume(self, dst_slot: int, src_slot: int, stamp: _abi.vrt_stamp, vol: Optional[VVoxelVolume] = None) -> dict:
+        """vrt_volume_stamp: the volume resident in `src_slot` merged into the one resident in `dst_slot` on the device, as the record
+        says (stamp_record / stamp_from_placement): ADD, SUBTRACT or REPLACE of the source's trilinear samples wherever the
+        destination's samples land inside the source.  The source slot is only read.  Given the destination's host mirror `vol`, its
+        written box is then read back as apply_brushes does.  Returns {"written", "lo", "hi"} (xyz, inclusive; lo > hi when nothing
+        was written)."""
+        self._require()
+        res = _abi.vrt_brush_result()
+        _abi.check(self._lib.vrt_volume_stamp(self._ctx, int(dst_slot), int(src_slot), C.byref(stamp), C.byref(res)), "vrt_volume_stamp")
+        lo, hi = tuple(res.lo), tuple(res.hi)
+        if res.written and vol is not None:
+            self._mirror_box(dst_slot, vol, lo, hi)
         return {"written": int(res.written), "lo": lo, "hi": hi}
 
     def _mirror_box(self, slot: int, vol: VVoxelVolume, lo, hi) -> None:

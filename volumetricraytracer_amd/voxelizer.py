@@ -44,6 +44,9 @@ def load_host() -> C.CDLL:
         lib.vrh_redistance.restype = C.c_int
         lib.vrh_redistance.argtypes = [C.c_void_p, C.c_int, C.c_float, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int),
                                        C.POINTER(_abi.vrt_redistance_result)]
+        lib.vrh_stamp.restype = C.c_int
+        lib.vrh_stamp.argtypes = [C.c_void_p, C.c_int, C.c_float, C.c_float, C.c_int, C.c_void_p, C.c_int, C.c_float, C.c_float, C.c_int,
+                                  C.POINTER(_abi.vrt_stamp), C.POINTER(_abi.vrt_brush_result)]
         lib.vrh_extract_mesh.restype = C.c_int
         lib.vrh_extract_mesh.argtypes = [C.c_void_p, C.c_int, C.c_float, C.c_int, C.c_float, C.POINTER(C.c_int), C.POINTER(C.c_int), C.c_void_p,
                                          C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.POINTER(_abi.vrt_mesh_result)]
@@ -125,6 +128,31 @@ def redistance_host(vol: VVoxelVolume, band: int, from_: int = _abi.REDISTANCE_F
     vol.density = np.ascontiguousarray(rec["density"].reshape(vol.N, vol.N, vol.N))
     vol.dirty = True
     return {"written": int(res.written), "near": int(res.near), "surfels": int(res.surfels), "lo": tuple(res.lo), "hi": tuple(res.hi)}
+
+
+def stamp_host(dst: VVoxelVolume, src: VVoxelVolume, stamp: _abi.vrt_stamp, dst_texel16: bool = False, src_texel16: bool = False) -> dict:
+    """VVolumeConverter::Stamp (the host build of vrt_volume_stamp's rule) on two volumes' densities and material ids: `src` merged
+    into `dst` in place as the record says; each volume's extent and density_scale give its density units.  texel16: that volume's
+    densities are the integer field +-q of a TEXEL16 slot.  Raises _abi.VrtError with the code vrt_volume_stamp returns for a record
+    it refuses.  Returns {"written", "lo", "hi"} (xyz, inclusive; lo > hi when nothing was written)."""
+    lib = load_host()
+    dtype = np.dtype([("material", "u1"), ("pad", "u1", 3), ("density", "<f4")])
+    recs = []
+    for vol in (dst, src):
+        rec = np.zeros(vol.N ** 3, dtype=dtype)
+        rec["density"] = np.asarray(vol.density, np.float32).reshape(-1)
+        rec["material"] = np.asarray(vol.material_id, np.uint8).reshape(-1)
+        recs.append(rec)
+    res = _abi.vrt_brush_result()
+    rc = lib.vrh_stamp(recs[0].ctypes.data, dst.N, float(dst.VolumeExtends), float(dst.density_scale), int(bool(dst_texel16)),
+                       recs[1].ctypes.data, src.N, float(src.VolumeExtends), float(src.density_scale), int(bool(src_texel16)),
+                       C.byref(stamp), C.byref(res))
+    _abi.check(rc, "vrh_stamp")
+    if res.written:
+        dst.density = np.ascontiguousarray(recs[0]["density"].reshape(dst.N, dst.N, dst.N))
+        dst.material_id = np.ascontiguousarray(recs[0]["material"].reshape(dst.N, dst.N, dst.N))
+        dst.dirty = True
+    return {"written": int(res.written), "lo": tuple(res.lo), "hi": tuple(res.hi)}
 
 
 def extract_mesh_host(vol: VVoxelVolume, iso: float = 0.0, lo=None, hi=None, texel16: bool = False):
