@@ -13,7 +13,7 @@ import volume_ref as R
 import volumetricraytracer_amd as v
 from volumetricraytracer_amd import workloads as scenes
 
-RES = {9: 3, 17: 4, 33: 5, 65: 6}
+RES = {2: 0, 3: 1, 5: 2, 9: 3, 17: 4, 33: 5, 65: 6, 257: 8}
 FORMATS = (R.F32, R.TEXEL16)
 FIELDS = ("sphere", "shell", "hand")
 OPS = (S.ADD, S.SUBTRACT, S.REPLACE)
@@ -23,11 +23,13 @@ OFFSETS = (0.0, 0.75, -0.75)
 TEXEL_EDGES = (5, 10, 15, 20, 23)  # q for which trunc(q * 0.01f * 100.f) != q
 
 
-def hand_made(N: int, seed: int) -> np.ndarray:
-    """Densities of a few cells' size with both signs, and sprinkled over them NaN, +-inf, +-0 and values whose texel is one of
-    TEXEL_EDGES (with both signs)."""
+def hand_made(N: int, seed: int, special: bool = True) -> np.ndarray:
+    """Densities of a few cells' size with both signs, and (special) sprinkled over them NaN, +-inf, +-0 and values whose texel is one
+    of TEXEL_EDGES (with both signs)."""
     rng = np.random.default_rng(seed)
     d = (rng.standard_normal((N, N, N)) * 2.0).astype(np.float32)
+    if not special:
+        return d
     special = [np.nan, np.inf, -np.inf, 0.0, -0.0] + [s * (q + 0.5) * 0.01 for q in TEXEL_EDGES for s in (1.0, -1.0)]
     flat = d.reshape(-1)
     where = rng.choice(flat.size, size=flat.size // 6, replace=False)
@@ -49,9 +51,9 @@ def volume(kind: str, N: int, role: str) -> v.VVoxelVolume:
     elif kind == "torus":
         vol = v.torus_volume(res, 100.0, 55.0, 22.0)
     else:
-        assert kind == "hand"
+        assert kind in ("hand", "normal")
         vol = v.VVoxelVolume(res, 6.0 if src else 9.0)
-        vol.density = hand_made(N, 11 if src else 12)
+        vol.density = hand_made(N, 11 if src else 12, special=kind == "hand")
         vol.density_scale = 0.5 if src else 1.0
     vol.density = np.array(vol.density, np.float32)
     i = np.arange(N)

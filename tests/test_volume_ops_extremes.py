@@ -1,0 +1,124 @@
+"""The host passes of the volume calls at resolutions 0, 1 and 2 (N = 2, 3, 5) — vrh_stamp, vrh_redistance, vrh_extract_mesh and the
+host fill, which compile the same *_core.h as the HIP kernels — against the numpy references, on the case tables that
+tests/test_volume_ops_extremes_gpu.py puts through the device (tests/extreme_cases.py).  Tolerance 0."""
+import numpy as np
+import pytest
+
+import extreme_cases as X
+import fill_ref as F
+import mesh_ref as MR
+import redistance_ref as RR
+import volume_ref as R
+import volumetricraytracer_amd as v
+from volumetricraytracer_amd import voxelizer as vx
+from test_volume_mesh import assert_same_mesh
+from test_volume_stamp import check as check_host_stamp, same_bits
+
+
+@pytest.mark.parametrize("N", X.SMALL)
+def test_host_fill_on_the_smallest_grids(N):
+    """The host fill has no TEXEL16 form: the fp32 rule only."""
+    for name, (d, filled, lo, hi) in X.fill_fields(N).items():
+        material = F.hand_made_material(d)
+        want_d, want_m, info = F.fill(d, material, R.F32, 1.0, 9)
+        assert info["filled"] == filled and (not filled or (info["lo"], info["hi"]) == (lo, hi)), (N, name, info)  # the reference itself
+        vol = X.volume(N, R.F32, False)
+        vol.density, vol.material_id = d.copy(), material.copy()
+        got = vx.fill_enclosed_host(vol, 1.0, 9)
+        assert got["filled"] == filled, (N, name, got)
+        if filled:
+            assert (got["lo"], got["hi"]) == (lo, hi), (N, name, got)
+        else:
+            assert all(l > h for l, h in zip(got["lo"], got["hi"])), (N, name, got)
+        assert same_bits(vol.density, want_d) and np.array_equal(vol.material_id, want_m), (N, name)
+        again = vx.fill_enclosed_host(vol, 1.0, 9)
+        assert again["filled"] == 0 and same_bits(vol.density, want_d), (N, name)
+
+
+@pytest.mark.parametrize("fmt", X.FORMATS)
+@pytest.mark.parametrize("N", X.SMALL)
+def test_host_redistance_on_the_smallest_grids(N, fmt):
+    stored, material = X.small_field(N, fmt)
+    unit = X.unit_of(N)
+    for band, from_, box in X.redistance_runs(N):
+        lo, hi = X.redistance_boxes(N)[box]
+        want, info = RR.redistance(stored, fmt, band, from_, unit, lo, hi)
+        vol = X.volume(N, fmt, False)
+        vol.density, vol.material_id = stored.copy(), material.copy()
+        got = vx.redistance_host(vol, band, from_, lo, hi, texel16=fmt == R.TEXEL16)
+        what = f"N {N}, format {fmt}, band {band}, from {from_}, box {box}"
+        assert got == info, (what, got, info)
+        assert same_bits(vol.density, want), what
+        assert np.array_equal(vol.material_id, material), what
+        assert info["written"] == (N ** 3 if box == "whole grid" else 1), what
+        if band == 15 and info["surfels"]:  # wider than the grid: no sample is as far as the band from a surfel
+            assert info["near"] == info["written"], what
+
+
+@pytest.mark.parametrize("fmt", X.FORMATS)
+@pytest.mark.parametrize("N", X.SMALL)
+def test_host_mesh_on_the_smallest_grids(N, fmt):
+    stored, material = X.small_field(N, fmt)
+    vol = X.volume(N, fmt, False)
+    vol.density, vol.material_id = stored, material
+    for box, (lo, hi) in X.mesh_boxes(N).items():
+        for iso in X.MESH_ISOS:
+            want = MR.extract(stored, material, fmt, iso, X.EXTENT, lo, hi)
+            got = vx.extract_mesh_host(vol, iso, lo, hi, texel16=fmt == R.TEXEL16)
+            assert_same_mesh(got, want, f"N {N}, format {fmt}, iso {iso}, box {box}")
+            assert want[4]["vertices"] > 0, (N, fmt, iso, box)
+            if N == 2:  # a single cell: one vertex, and no edge with four cells around it
+                assert (want[4]["vertices"], want[4]["quads"]) == (1, 0) and want[4]["lo"] == want[4]["hi"] == (0, 0, 0)
+            if N == 5 and box == "whole grid":
+                assert want[4]["quads"] > 0
+
+
+@pytest.mark.parametrize("sfmt", X.FORMATS)
+@pytest.mark.parametrize("dfmt", X.FORMATS)
+@pytest.mark.parametrize("Nd,Ns", X.STAMP_SIZES)
+def test_host_stamp_on_the_smallest_grids(Nd, Ns, dfmt, sfmt):
+    written = {}
+    for case in X.stamp_cases(Nd, Ns):
+        written[case[0]] = check_host_stamp(case, Nd, Ns, dfmt, sfmt)["written"]
+    assert len(written) == 12
+    for name in ("identity", "axis turn 0", "u lands on"):
+        assert any(n > 0 for what, n in written.items() if what.startswith(name)), (name, written)
+
+
+@pytest.mark.parametrize("op", X.EDIT_OPS)
+def test_the_oracle_sees_each_edit(oracle_lib, op):
+    """The GPU tests hold a frame begun before a stamp, a fill or a redistance to the old volume and one begun after it to the new:
+    that says something only if the two differ.  Here the oracle marches each scene before and after the host pass of its edit, at
+    both frame sizes those tests use.  (A fill shows from outside: the shell is thin enough for a hit's normal to reach the cavity.)"""
+    from volumetricraytracer_amd import _abi
+    from volumetricraytracer_amd import workloads as scenes
+    from oracle.binding import OracleScene
+
+    frames = {}
+    for edited in (False, True):
+        sc, vol = X.edit_scene(op)
+        X.host_edit(op, vol, prepare_only=not edited)
+        for w, h, flags in ((256, 144, 0), (200, 120, _abi.FLAG_NO_CULL_RECT)):
+            p = v.default_params(w, h, scenes.min_cell(sc), 255, shadow=True)
+            p.flags |= flags
+            frames[(edited, w)], st = OracleScene(sc).render(p, threads=8)
+            assert st["hits"] > 1000
+    for w in (256, 200):
+        differing = int((frames[(False, w)] != frames[(True, w)]).any(axis=2).sum())
+        print(f"{op}, width {w}: {differing} pixels differ")
+        assert differing > 100, (op, w, differing)
+
+
+def test_the_case_tables_reach_what_they_are_for():
+    assert [X.resolution(N) for N in X.SMALL + (17, 257, 513)] == [0, 1, 2, 4, 8, 9]
+    assert [v.VVoxelVolume(r, 1.0).N for r in (0, 1, 2)] == list(X.SMALL)
+    assert any(Ns == 2 for _, Ns in X.STAMP_SIZES)
+    for N in X.SMALL:
+        d = X.random_field(N)
+        assert (d > 0).any() and (d < 0).any()
+        if N >= 3:
+            assert np.isnan(d).sum() == 1 and (d == 0).sum() == 2 and np.signbit(d[d == 0]).sum() == 1
+            t = X.small_field(N, R.TEXEL16)[0]
+            assert not np.isnan(t).any() and (t == np.round(t)).all()
+    assert X.fill_fields(3)["sealed"][1:] == (1, (1, 1, 1), (1, 1, 1)) and X.fill_fields(5)["sealed"][1:] == (27, (1, 1, 1), (3, 3, 3))
+    assert X.fill_fields(2)["sealed"][1] == 0

@@ -1,0 +1,579 @@
+"""The device-side volume calls — vrt_volume_update_region / _update_voxels / _download_region, _apply_brushes, _stamp, _fill_enclosed,
+_redistance and _extract_mesh — at the two ends of the resolutions they accept, and two promises of vrt.h that the newer calls were
+never held to.
+
+A. Resolutions 0, 1, 2 (N = 2, 3, 5: one brick, one 8^3 tile, one partial run of cells) for stamp, fill, redistance and mesh, in
+   both formats, with and without the empty-space tables.  The same case tables (tests/extreme_cases.py) go through the host passes in
+   tests/test_volume_ops_extremes.py.
+B. The code paths that only a grid of 257^3 or 513^3 reaches: the second iteration of the capped grid-stride loops, the face seeds of
+   the fill beyond lane 2^24, the second chunk of the mesh's prefix sum.  Each test asserts on the CPU, from the reference alone, that
+   its input takes that path, before it looks at the device.
+C. A frame begun before a stamp, a fill or a redistance renders the old volume and a captured launch replays over the new one; a
+   context over two devices stamps both.
+
+Tolerance 0 on every buffer; frames against the oracle within TOL."""
+import ctypes as C
+import functools
+
+import numpy as np
+import pytest
+
+import brush_ref as B
+import extreme_cases as X
+import fill_ref as F
+import mesh_ref as MR
+import redistance_ref as RR
+import stamp_cases as K
+import stamp_ref as S
+import volume_ref as R
+import volumetricraytracer_amd as v
+from volumetricraytracer_amd import _abi
+from volumetricraytracer_amd import workloads as scenes
+from oracle.binding import OracleScene
+from test_volume_brush_gpu import check_result as check_brush_result
+from test_volume_buffers_gpu import assert_bytes, read
+from test_volume_edit_gpu import update
+from test_volume_fill_gpu import EDITED, FULL, TOL, Case, assert_same_buffers, buffers, fill_and_check, upload_field
+from test_volume_fill_gpu import check_result as check_fill_result
+from test_volume_mesh import assert_same_mesh, same_bits
+from test_volume_mesh_gpu import raw_call
+from test_volume_stamp_gpu import SOURCE, SPARE, stamp_and_check, with_table
+from test_volume_stamp_gpu import _fresh_slots  # noqa: F401 -- the autouse fixture: these four slots start unused and are freed after
+from test_volume_stamp_gpu import upload as upload_stamp_volume
+
+pytestmark = pytest.mark.gpu
+SLOTS = (EDITED, FULL, SOURCE, SPARE)
+
+
+def free_slots(r):
+    """Between the cases of one test: what _fresh_slots does around it."""
+    for slot in SLOTS:
+        r._uploaded.pop(slot, None)
+        r._lib.vrt_volume_free(r._ctx, slot)  # VRT_ERR_SLOT when unused
+
+
+def same_dense(have, stored, material, what):
+    assert_bytes(have["dense"], np.ascontiguousarray(stored).reshape(-1).view(np.uint8), what + ": dense grid")
+    assert_bytes(have["material"], np.ascontiguousarray(material).reshape(-1), what + ": material ids")
+
+
+def box_args(lo, hi):
+    if lo is None:
+        return None, None
+    return (C.c_int * 3)(*lo), (C.c_int * 3)(*[h - l + 1 for l, h in zip(lo, hi)])
+
+
+# ---- A. resolutions 0, 1, 2 ----------------------------------------------------------------------------------------------------------
+
+@pytest.mark.parametrize("fmt", X.FORMATS)
+@pytest.mark.parametrize("N", X.SMALL)
+def test_fill_on_the_smallest_grids(renderer, N, fmt):
+    """N = 2 has no sample off the faces, N = 3 one, N = 5 the 3^3 block; one opened face sample turns all of them exterior."""
+    for table in (True, False):
+        for name, (d, filled, lo, hi) in X.fill_fields(N).items():
+            vol = X.volume(N, fmt, table)
+            vol.density, vol.material_id = d, F.hand_made_material(d)
+            case = Case(vol, 1.0, 9)
+            assert case.info["filled"] == filled and (not filled or (case.info["lo"], case.info["hi"]) == (lo, hi))  # the reference itself
+            free_slots(renderer)
+            got = fill_and_check(renderer, case, f"N {N}, format {fmt}, tables {table}, {name}")  # every buffer, and a second call
+            assert got["filled"] == filled
+
+
+@functools.lru_cache(maxsize=None)
+def small_redistance(N, fmt, band, from_, box):
+    lo, hi = X.redistance_boxes(N)[box]
+    want, info = RR.redistance(X.small_field(N, fmt)[0], fmt, band, from_, X.unit_of(N), lo, hi)
+    return X.read_only(want), info
+
+
+@pytest.mark.parametrize("fmt", X.FORMATS)
+@pytest.mark.parametrize("N", X.SMALL)
+def test_redistance_on_the_smallest_grids(renderer, N, fmt):
+    """Bands 1, 7, 8 and 15 — one and two rings of tiles, all but the first wider than the grid — with every `from`, on the whole grid
+    and on a one-sample box, over a field with NaN and +-0 samples."""
+    stored, material = X.small_field(N, fmt)
+    for table in (True, False):
+        vol = X.volume(N, fmt, table)
+        for band, from_, box in X.redistance_runs(N):
+            lo, hi = X.redistance_boxes(N)[box]
+            want, info = small_redistance(N, fmt, band, from_, box)
+            what = f"N {N}, format {fmt}, tables {table}, band {band}, from {from_}, box {box}"
+            free_slots(renderer)
+            upload_field(renderer, EDITED, vol, fmt, stored, material)
+            got = renderer.redistance(EDITED, None, band, from_, lo, hi)
+            assert got == info, (what, got, info)
+            have = buffers(renderer, EDITED)
+            assert_same_buffers(have, R.device_bytes(want, material, fmt, vol.density_scale, vol.step_max), what + " against the reference")
+            upload_field(renderer, FULL, vol, fmt, want, material)
+            assert_same_buffers(have, buffers(renderer, FULL), what + " against a full upload")
+
+
+@functools.lru_cache(maxsize=None)
+def small_mesh(N, fmt, iso, box):
+    stored, material = X.small_field(N, fmt)
+    lo, hi = X.mesh_boxes(N)[box]
+    return MR.extract(stored, material, fmt, iso, X.EXTENT, lo, hi)
+
+
+@pytest.mark.parametrize("fmt", X.FORMATS)
+@pytest.mark.parametrize("N", X.SMALL)
+def test_mesh_on_the_smallest_grids(renderer, N, fmt):
+    """The counting call, the filling call and a call with the positions alone, at two levels; N = 2 is a single cell: one vertex, no
+    quad.  Vertex and quad order are compared exactly, and the slot's buffers stay as they were."""
+    stored, material = X.small_field(N, fmt)
+    for table in (True, False):
+        free_slots(renderer)
+        upload_field(renderer, EDITED, X.volume(N, fmt, table), fmt, stored, material)
+        before = buffers(renderer, EDITED)
+        for box, (lo, hi) in X.mesh_boxes(N).items():
+            for iso in X.MESH_ISOS:
+                want = small_mesh(N, fmt, iso, box)
+                what = f"N {N}, format {fmt}, tables {table}, iso {iso}, box {box}"
+                V, Q = want[4]["vertices"], want[4]["quads"]
+                assert V > 0 and (N > 2 or (V, Q) == (1, 0)), (what, want[4])
+                o, s = box_args(lo, hi)
+                rc, counted = raw_call(renderer, EDITED, iso, o, s)
+                assert rc == _abi.VRT_OK and counted == (want[4]["lo"], want[4]["hi"], V, Q), (what, counted)
+                assert_same_mesh(renderer.extract_mesh(EDITED, iso, lo, hi), want, what)
+                pos = np.full((V, 3), 7.5, np.float32)
+                rc, rec = raw_call(renderer, EDITED, iso, o, s, pos=pos, vcap=V, icap=6 * Q)
+                assert rc == _abi.VRT_OK and rec == counted and same_bits(pos, want[0]), what + ": positions alone"
+        assert_same_buffers(buffers(renderer, EDITED), before, f"N {N}, format {fmt}, tables {table}: after the extractions")
+
+
+@pytest.mark.parametrize("sfmt", X.FORMATS)
+@pytest.mark.parametrize("dfmt", X.FORMATS)
+@pytest.mark.parametrize("Nd,Ns", X.STAMP_SIZES)
+def test_stamp_on_the_smallest_grids(renderer, Nd, Ns, dfmt, sfmt):
+    """A source of Ns = 2 has cell Ns - 2 = 0 as its only one, and with "u lands on Ns - 1" its last sample is reached with fraction 1."""
+    written = {}
+    for case in X.stamp_cases(Nd, Ns):
+        for table in (True, False):
+            written[case[0]] = stamp_and_check(renderer, case, Nd, Ns, dfmt, sfmt, table)["written"]  # the reference's result, a full upload
+            want_d, want_m, _ = K.reference(case[1], case[2], Nd, Ns, dfmt, sfmt, case[3])
+            dst = with_table(K.volume(case[2], Nd, "dst"), table)
+            assert_same_buffers(buffers(renderer, EDITED), R.device_bytes(want_d, want_m, dfmt, dst.density_scale, dst.step_max),
+                                f"{case[0]} ({Ns}^3 fmt {sfmt} into {Nd}^3 fmt {dfmt}, tables {table}) against the reference")
+    assert len(written) == 12
+    for name in ("identity", "axis turn 0", "u lands on"):
+        assert any(n > 0 for what, n in written.items() if what.startswith(name)), (name, written)
+
+
+# ---- B. the paths that only large grids reach ---------------------------------------------------------------------------------------
+
+def big_volume(N, fmt, table=True):
+    return X.volume(N, fmt, table, extent=100.0, scale=1.0)
+
+
+@functools.lru_cache(maxsize=None)
+def brushed_257(fmt):
+    """(stored, material) before the brushes and [(records, result, stored, material)] after each call, by brush_ref."""
+    d, m = X.torus_257()
+    first = X.read_only(R.dense_field(d, fmt), np.array(m))
+    stored, material = first[0].copy(), first[1].copy()
+    steps = []
+    for recs in X.brush_calls_257():
+        info = B.apply(stored, material, fmt, recs, 100.0, 1.0)
+        steps.append((recs, info) + X.read_only(stored.copy(), material.copy()))
+    return first, steps
+
+
+@pytest.mark.parametrize("fmt", X.FORMATS)
+def test_whole_grid_brushes_at_257(renderer, fmt):
+    """brush_region_kernel runs one lane per sample of the records' union box, at most 65 536 workgroups of 256 = 2^24 lanes, and
+    loops with its written count and bounding box carried along.  The whole 257^3 grid has 16 974 593 samples, 197 377 more than 2^24:
+    the first box for which the loop runs a second time, over the samples with (x * N + z) * N + y >= 2^24 (part of x = 254, all of
+    x = 255 and 256)."""
+    N = 257
+    assert N ** 3 - X.CAP == 197377
+    (stored, material), steps = brushed_257(fmt)
+    before_d, before_m = stored, material
+    for n, (recs, info, want_d, want_m) in enumerate(steps):  # the conditions, from the reference alone
+        for rec in recs[:1]:  # the record that spans the grid: its shape grown by its reach covers every axis
+            assert all(c - (rec.radius + rec.reach) <= 0 and c + (rec.radius + rec.reach) >= N - 1 for c in rec.a)
+        density = want_d.view(np.uint32) != before_d.view(np.uint32)
+        ids = want_m != before_m
+        for what, mask in (("density", density), ("material ids", ids)):
+            below, beyond = X.split_by_cap(mask)
+            assert below > 0 and beyond > 0, (n, what, below, beyond)
+        assert 0 < info["written"] < N ** 3 and not (density | ids).all(), (n, info)
+        before_d, before_m = want_d, want_m
+    assert steps[0][1]["lo"] == (0, 0, 0) and steps[0][1]["hi"] == (N - 1,) * 3 and steps[1][1]["written"] < 10000
+    vol = big_volume(N, fmt)
+    upload_field(renderer, EDITED, vol, fmt, stored, material)
+    for n, (recs, info, want_d, want_m) in enumerate(steps):
+        what = f"257^3, format {fmt}, call {n}"
+        got = renderer.apply_brushes(EDITED, None, recs)
+        print(f"{what}: {got}")
+        check_brush_result(got, info, what)
+        have = buffers(renderer, EDITED)
+        same_dense(have, want_d, want_m, what)
+        upload_field(renderer, FULL, vol, fmt, want_d, want_m)
+        assert_same_buffers(have, buffers(renderer, FULL), what + " against a full upload")
+
+
+@pytest.mark.parametrize("fmt", X.FORMATS)
+def test_whole_grid_updates_and_downloads_at_257(renderer, fmt):
+    """scatter_region_kernel<false> (vrt_volume_update_region), scatter_region_kernel<true> (_update_voxels) and gather_region_kernel
+    (_download_region) loop like the brushes: a whole-volume box of 257^3 = 2^24 + 197 377 samples is the first whose second iteration
+    runs.  The new values differ from the old ones in the last three x-planes only, so a box that stopped at lane 2^24 would leave
+    old samples behind."""
+    N = 257
+    d, m = X.torus_257()
+    vol = big_volume(N, fmt)
+    vol.density, vol.material_id = np.array(d), np.array(m)
+    renderer.upload_volume(EDITED, vol)
+    rng = np.random.default_rng(57 + fmt)
+    for k, records in enumerate((False, True)):
+        old = R.dense_field(vol.density, fmt)
+        new = rng.uniform(-2.0, 4.0, (3, N, N)).astype(np.float32)
+        vol.density[N - 3:], vol.material_id[N - 3:] = new, (new <= 0).astype(np.uint8) * (3 + k)
+        changed = R.dense_field(vol.density, fmt).view(np.uint32) != old.view(np.uint32)
+        below, beyond = X.split_by_cap(changed)
+        assert beyond > 190000 and not changed[:N - 3].any(), (below, beyond)  # the condition: new values beyond lane 2^24, and only there
+        update(renderer, EDITED, vol, (0, 0, 0), (N, N, N), records=records)
+        renderer.upload_volume(FULL, vol)
+        assert_same_buffers(buffers(renderer, EDITED), buffers(renderer, FULL), f"257^3, format {fmt}, whole-volume box, records {records}")
+    whole = renderer.download_volume(EDITED, vol.Resolution, vol.VolumeExtends)
+    density, material = renderer.download_region(EDITED, (0, 0, 0), (N - 1,) * 3)
+    assert np.array_equal(density.view(np.uint32), whole.density.view(np.uint32)) and np.array_equal(material, whole.material_id)
+    want = B.decode(R.dense_field(vol.density, fmt), fmt)
+    assert np.array_equal(density.view(np.uint32), want.view(np.uint32)) and np.array_equal(material, vol.material_id)
+
+
+def fill_against_a_full_upload(r, case, what):
+    """fill_and_check without the reference of the upload, which takes minutes on these grids: the result record, the dense grid and
+    the ids against fill_ref, every buffer against a full upload of its field, and a second call that fills nothing."""
+    upload_field(r, EDITED, case.vol, case.fmt, case.stored, case.material)
+    got = r.fill_enclosed(EDITED, None, case.wall, case.material_id)
+    print(f"{what}: {got}, reference {case.info}")
+    check_fill_result(got, case.info, what)
+    have = buffers(r, EDITED)
+    same_dense(have, case.want_d, case.want_m, what)
+    upload_field(r, FULL, case.vol, case.fmt, case.want_d, case.want_m)
+    assert_same_buffers(have, buffers(r, FULL), what + " against a full upload")
+    again = r.fill_enclosed(EDITED, None, case.wall, case.material_id)
+    assert again["filled"] == 0 and all(l > h for l, h in zip(again["lo"], again["hi"])), (what, again)
+    assert_same_buffers(buffers(r, EDITED), have, what + " after a second call")
+
+
+def cavity_conditions(case, cavities, channel, N):
+    """From the reference alone: exactly the cavities are filled, on both sides of lane 2^24 of fill_apply_kernel (one lane per sample),
+    and the channel — passable samples at or beyond that lane among it — is not."""
+    filled = case.want_d.view(np.uint32) != case.stored.view(np.uint32)
+    want = np.zeros(filled.shape, bool)
+    for lo, hi in cavities:
+        want[lo[0]:hi[0] + 1, lo[2]:hi[2] + 1, lo[1]:hi[1] + 1] = True
+    assert np.array_equal(filled, want) and case.info["filled"] == int(want.sum())
+    below, beyond = X.split_by_cap(filled)
+    left_below, left_beyond = X.split_by_cap(F.passable(F.decode(case.stored, case.fmt)) & ~filled)
+    assert below > 0 and beyond > 0 and left_beyond > 0, (below, beyond, left_below, left_beyond)
+    lo, hi = channel
+    assert hi[0] == N - 1 and not filled[lo[0]:hi[0] + 1, lo[2]:hi[2] + 1, lo[1]:hi[1] + 1].any()
+    return filled
+
+
+@pytest.mark.parametrize("fmt", X.FORMATS)
+def test_fill_at_257(renderer, fmt):
+    """fill_apply_kernel runs one lane per sample under the same cap of 2^24 lanes and carries its filled count and box through the
+    loop: 257^3 = 2^24 + 197 377 samples is the first grid with a second iteration.  Sealed cavities lie across x = 253 .. 255 (lane
+    2^24 falls in x = 254), in x = 255 alone and near the origin; a channel that opens on the face x = 256 must stay as it is."""
+    N = 257
+    d, cavities, channel = X.cavity_field(N, 253, 255)
+    vol = big_volume(N, fmt)
+    vol.density, vol.material_id = d, F.hand_made_material(d)
+    case = Case(vol, 1.0, 9)
+    cavity_conditions(case, cavities, channel, N)
+    fill_against_a_full_upload(renderer, case, f"257^3 cavities, format {fmt}")
+
+
+def test_fill_of_the_benched_shell(renderer):
+    """The voxelized torus at resolution 8, the size the product renders: filled count, box and dense grid against fill_ref."""
+    vol = scenes.voxelized_torus(8)
+    case = Case(vol, 1.0, 1)
+    assert case.info["filled"] > 900000
+    upload_field(renderer, EDITED, vol, R.F32, case.stored, case.material)
+    got = renderer.fill_enclosed(EDITED, None, 1.0, 1)
+    print(f"voxelized torus 8: {got}, reference {case.info}")
+    check_fill_result(got, case.info, "voxelized torus 8")
+    assert_bytes(read(renderer, EDITED, "dense"), case.want_d.reshape(-1).view(np.uint8), "voxelized torus 8: dense grid")
+
+
+def bricks_meeting(boxes, N):
+    """The ids of the bricks that hold a sample of one of the boxes (lo, hi xyz inclusive): brick b of an axis holds samples 4b .. 4b + 4."""
+    nb = R.n_bricks(N)
+    ids = []
+    for lo, hi in boxes:
+        ax = [np.arange(max(0, -(-(l - 4) // 4)), min(nb - 1, h // 4) + 1) for l, h in zip(lo, hi)]  # x, y, z
+        bx, bz, by = np.meshgrid(ax[0], ax[2], ax[1], indexing="ij")
+        ids.append(((bx * nb + bz) * nb + by).reshape(-1))
+    return np.concatenate(ids)
+
+
+def test_fill_at_513_texel16():
+    """fill_mask_kernel runs one lane per row byte — N^2 * ceil(N / 8) of them — under the cap of 2^24 lanes.  513^2 * 65 = 17 105 985
+    is the first count beyond it: the bytes of its second iteration are rows with x >= 503, the whole face x = 512 with its seeds among
+    them.  The cavities lie at x = 504 .. 508 and the open channel enters from the face x = 512: without that face's seeds it would be
+    taken for a cavity.  fill_apply_kernel loops nine times over the 513^3 = 8 * 2^24 + 787 969 samples; the cavities fall into its
+    iterations 0 and 7, the last one (x >= 510) holds the channel and fills nothing.  Both levels of the empty-space table and the Cube
+    table are left to test_fill_at_257: a second 513^3 slot to compare them with takes this test past the suite's slowest one."""
+    N, fmt = 513, R.TEXEL16
+    T = -(-N // 8)
+    assert N * N * T == 17105985 and N * N * T > X.CAP >= 257 * 257 * -(-257 // 8)
+    assert list(R.dense_field(np.float32([-1.0, 0.5]), fmt)) == [-100.0, 50.0]  # the texels of cavity_field's two values, written directly
+    stored, cavities, channel = X.cavity_field(N, 504, 508, -100.0, 50.0)
+    material = (stored <= 0).astype(np.uint8)
+    want_d, want_m, info = F.fill(stored, material, fmt, 1.0, 9)
+    # the conditions, from the reference alone
+    filled = want_d.view(np.uint32) != stored.view(np.uint32)
+    assert info["filled"] == int(filled.sum()) == sum(int(np.prod([h - l + 1 for l, h in zip(lo, hi)])) for lo, hi in cavities)
+    rounds = np.unique(np.flatnonzero(filled.reshape(-1)) // X.CAP)
+    assert N ** 3 // X.CAP == 8 and rounds[0] == 0 and rounds[-1] == 7, rounds  # iterations 0 and 7 of fill_apply_kernel's nine fill
+    seed = channel[1]  # the channel's sample on the face x = N - 1, xyz
+    assert seed[0] == N - 1 and stored[seed[0], seed[2], seed[1]] > 0 and ((seed[0] * N + seed[2]) * T + seed[1] // 8) >= X.CAP
+    (x0, y0, z0), (x1, y1, z1) = channel
+    assert not filled[x0:x1 + 1, z0:z1 + 1, y0:y1 + 1].any() and (stored[x0:x1 + 1, z0:z1 + 1, y0:y1 + 1] > 0).all()
+    del filled
+    nb = R.n_bricks(N)
+    rng = np.random.default_rng(13)
+    which = np.unique(np.concatenate([bricks_meeting(cavities + [channel], N), rng.integers(0, nb ** 3, 4096)]))
+    vol = big_volume(N, fmt)
+    with v.VHipRenderer() as r:
+        upload_field(r, EDITED, vol, fmt, stored, material)
+        got = r.fill_enclosed(EDITED, None, 1.0, 9)
+        print(f"513^3: {got}, reference {info}")
+        check_fill_result(got, info, "513^3")
+        assert_bytes(read(r, EDITED, "dense"), want_d.reshape(-1).view(np.uint8), "513^3 dense")
+        assert_bytes(read(r, EDITED, "material"), want_m.reshape(-1), "513^3 material")
+        have = read(r, EDITED, "bricks").view(np.int16).reshape(nb ** 3, 128)
+        assert np.array_equal(have[which], R.bricks(want_d, fmt, which)), "513^3 bricks"
+        del have
+        have = read(r, EDITED, "cells").view(np.int16).reshape(nb ** 3, 64, 8)
+        assert np.array_equal(have[which], R.cells(want_d, which)), "513^3 cells"
+        del have
+
+
+MESH_513_BOX = ((0, 200, 0), (512, 329, 512))  # 513 x 130 x 513 samples
+
+
+def test_mesh_on_513():
+    """mesh_scan_sums_kernel scans the sums of blocks of 256 * 8 = 2048 runs, 256 sums at a time, and carries a running total from one
+    chunk of sums to the next: the second chunk exists from 256 * 2048 = 524 288 runs on.  A run is 64 cells along y of one (x, z) row,
+    runs are numbered x slowest: 257^3 has 256 * 256 * 4 = 262 144 of them.  A box of 513 x 130 x 513 samples on 513^3 has 512 * 512 rows
+    of ceil(129 / 64) = 3 runs, 786 432, and run 524 288 lies in x = 341 (524 288 / (512 * 3) = 341.33).  The sphere of 40 cells is
+    centred there: the vertices of the cells with x >= 342 get their numbers through the carry."""
+    N = 513
+    lo, hi = MESH_513_BOX
+    rows, runs_y = (hi[0] - lo[0]) * (hi[2] - lo[2]), -(-(hi[1] - lo[1]) // 64)
+    assert rows * runs_y == 786432 > 256 * 2048 and 256 * 256 * 4 < 256 * 2048
+    assert (256 * 2048) // ((hi[2] - lo[2]) * runs_y) == 341
+    cell, _ = B.units(N, 100.0, 1.0)
+    density, material = X.sphere_in_constant(N, (341.3, 264.2, 255.8), 40.4, float(cell))
+    want = MR.extract(density, material, R.F32, 0.0, 100.0, lo, hi)
+    cells_x = np.floor((want[0][:, 0].astype(np.float64) + 100.0) / float(cell)).astype(np.int64)  # the cell a vertex lies in
+    assert (cells_x < 341).sum() > 5000 and (cells_x > 342).sum() > 5000, want[4]  # the condition: runs on both sides of run 524 288
+    assert want[4]["lo"][0] < 341 and want[4]["hi"][0] > 342 and want[4]["lo"][1] > lo[1] and want[4]["hi"][1] < hi[1] - 1
+    with v.VHipRenderer() as r:
+        upload_field(r, EDITED, big_volume(N, R.F32, table=False), R.F32, density, material)
+        got = r.extract_mesh(EDITED, 0.0, lo, hi)
+    assert_same_mesh(got, want, "513^3, box 513 x 130 x 513")
+    most, unpaired, E = MR.edge_census(got[3], len(got[0]))
+    assert most == 1 and len(unpaired) == 0 and len(got[0]) - E + len(got[3]) == 2  # a closed sphere
+
+
+@pytest.mark.parametrize("fmt", X.FORMATS)
+def test_mesh_of_the_whole_257_grid(renderer, fmt):
+    """The size the product renders: 256 * 256 rows of four runs, a sphere of 80 cells across all of them."""
+    N = 257
+    cell, _ = B.units(N, 100.0, 1.0)
+    density = RR.sphere_field(N, (128.3, 127.8, 128.1), 80.4, float(cell))
+    stored, material = R.dense_field(density, fmt), F.hand_made_material(density)
+    want = MR.extract(stored, material, fmt, 0.0, 100.0)
+    assert want[4]["vertices"] > 100000
+    upload_field(renderer, EDITED, big_volume(N, fmt, table=False), fmt, stored, material)
+    assert_same_mesh(renderer.extract_mesh(EDITED), want, f"257^3, format {fmt}")
+
+
+@pytest.mark.parametrize("fmt", X.FORMATS)
+def test_stamp_into_the_far_corner_at_257(renderer, fmt):
+    """No large-grid path of its own (the stamp's launch caps lie beyond N = 1025): addressing at the size the product renders.  An
+    oblique ADD of the 65^3 sphere (19.84 cells) about (245.3, 244.6, 245.2): the grid's far corner lies 19.5 cells from there, inside
+    the sphere, so the footprint is clipped by the faces x, y, z = 256 and the written box ends on all three."""
+    Nd, Ns = 257, 65
+    rec = v.stamp_from_placement(Ns, (245.3, 244.6, 245.2), K.quat((1, 2, 3), 37.0), 1.0, op=S.ADD, material=7)
+    rec.blend, rec.reach = 1.5, 3.0
+    m = np.asarray(list(rec.dst_to_src), np.float64).reshape(3, 4)
+    corners = np.array([[a, b, c] for a in (0, Ns - 1) for b in (0, Ns - 1) for c in (0, Ns - 1)], np.float64)
+    placed = (np.linalg.inv(m[:, :3]) @ (corners - m[:, 3]).T).T  # the source's corners in destination coordinates
+    assert (placed.max(0) > Nd - 1).all() and (placed.min(0) > 0).all(), placed  # clipped by the three far faces only
+    want = stamp_and_check(renderer, ("oblique ADD into the far corner", "sphere", "torus", rec), Nd, Ns, fmt, fmt, table=True)
+    assert want["written"] > 20000 and want["hi"] == (Nd - 1,) * 3 and min(want["lo"]) > 200, want
+
+
+@pytest.mark.parametrize("fmt", X.FORMATS)
+def test_redistance_in_the_far_corner_at_257(renderer, fmt):
+    """No large-grid path of its own either: a box of 40^3 samples that ends on the faces x, y, z = 256, band 8, FROM_BOTH, around a
+    sphere of 8.7 cells; the reference is evaluated over the box with the header's band + 1 culling rule."""
+    N = 257
+    cell, unit = B.units(N, 100.0, 1.0)
+    density = RR.sphere_field(N, (236.3, 238.8, 240.1), 8.7, float(cell))
+    stored, material = R.dense_field(density, fmt), F.hand_made_material(density)
+    lo, hi = (N - 40,) * 3, (N - 1,) * 3
+    want, info = RR.redistance(stored, fmt, 8, RR.BOTH, unit, lo, hi, cull=True)
+    assert info["written"] == 40 ** 3 and 1000 < info["surfels"] and 0 < info["near"] < info["written"], info
+    vol = big_volume(N, fmt)
+    upload_field(renderer, EDITED, vol, fmt, stored, material)
+    got = renderer.redistance(EDITED, None, 8, RR.BOTH, lo, hi)
+    assert got == info, (got, info)
+    have = buffers(renderer, EDITED)
+    same_dense(have, want, material, f"257^3 far corner, format {fmt}")
+    upload_field(renderer, FULL, vol, fmt, want, material)
+    assert_same_buffers(have, buffers(renderer, FULL), f"257^3 far corner, format {fmt}, against a full upload")
+
+
+# ---- C. frames around a stamp, a fill and a redistance; two devices -----------------------------------------------------------------
+
+def prepare_edit(r, op, vol):
+    """What the edit needs on the device beforehand, the scene's volume being resident in slot 0: the stamp's source in a spare slot;
+    the fill that makes the shell a solid to redistance."""
+    if op == "stamp":
+        src = X.stamp_source()
+        upload_field(r, SPARE, src, R.F32, K.stored("sphere", 17, "src", R.F32), src.material_id)
+    elif op == "redistance":
+        assert r.fill_enclosed(0, vol, 1.0, 1)["filled"] > 1000
+
+
+def device_edit(r, op, vol):
+    """The edit on slot 0 with the host mirror following, as extreme_cases.host_edit does it on the host."""
+    if op == "stamp":
+        got = r.stamp_volume(0, SPARE, X.frame_stamp(vol), vol)
+        assert got["written"] > 100, got
+    elif op == "fill":
+        got = r.fill_enclosed(0, vol, 1.0, 1)
+        assert got["filled"] > 1000, got
+    else:
+        got = r.redistance(0, vol, 3, RR.OUTSIDE)
+        assert got["near"] > 1000, got
+    assert vol.dirty_box is None and not vol.dirty  # the mirror follows without being dirtied
+
+
+def frame_renderer(r, sc, p):
+    r.SetSceneToRender(sc)
+    r.ResizeRenderOutput(p.width, p.height)
+    r.params_override = p
+    r.SetRendererMode(p.mode)
+
+
+@pytest.mark.parametrize("op", X.EDIT_OPS)
+def test_a_frame_begun_before_the_edit_renders_the_old_volume(oracle_lib, op):
+    """(That the oracle's frames before and after each edit differ is a test of its own, on the host passes:
+    tests/test_volume_ops_extremes.py.)"""
+    sc, vol = X.edit_scene(op)
+    p = v.default_params(256, 144, scenes.min_cell(sc), 255, shadow=True)
+    with v.VHipRenderer() as r:
+        frame_renderer(r, sc, p)
+        r.Render()  # the scene's volume is resident in slot 0 now
+        prepare_edit(r, op, vol)
+        before = r.Render()
+        r.render_begin(0, p)
+        device_edit(r, op, vol)  # waits for the frame on slot 0
+        r.render_begin(1, p)
+        first, second = r.render_end(0, p), r.render_end(1, p)
+        after = r.Render()
+    assert np.array_equal(first, before)
+    assert np.array_equal(second, after)
+    assert not np.array_equal(before, after)
+    ref, _ = OracleScene(sc).render(p, threads=8)  # the oracle marches the mirror
+    assert np.abs(after - ref).max() <= TOL
+
+
+@pytest.mark.parametrize("op", X.EDIT_OPS)
+def test_a_captured_frame_replays_over_the_edited_volume(renderer, oracle_lib, op):
+    """Device pointers survive the call: a render_rows launch captured before it replays the edited volume."""
+    import torch
+
+    sc, vol = X.edit_scene(op)
+    p = v.default_params(200, 120, scenes.min_cell(sc), 255, shadow=True)
+    p.flags |= _abi.FLAG_NO_CULL_RECT  # a captured launch keeps its cull rectangle, and an edit may grow the active box
+    renderer.SetSceneToRender(sc)
+    renderer.SyncWithScene()
+    prepare_edit(renderer, op, vol)
+    side = torch.cuda.Stream()
+    out = torch.zeros((120, 200, 4), dtype=torch.float32, device="cuda:0")
+    with torch.cuda.stream(side):
+        renderer.render_rows(p, 0, 120, out.data_ptr(), side.cuda_stream)
+    torch.cuda.synchronize()
+    old = out.clone()
+    g = torch.cuda.CUDAGraph()
+    with torch.cuda.graph(g, stream=side):
+        renderer.render_rows(p, 0, 120, out.data_ptr(), side.cuda_stream)
+    device_edit(renderer, op, vol)
+    out.zero_()
+    g.replay()
+    torch.cuda.synchronize()
+    fresh = torch.zeros_like(out)
+    renderer.render_rows(p, 0, 120, fresh.data_ptr(), torch.cuda.current_stream().cuda_stream)
+    torch.cuda.synchronize()
+    assert torch.equal(out, fresh) and not torch.equal(out, old)
+    ref, _ = OracleScene(sc).render(p, threads=8)
+    assert np.abs(out.cpu().numpy() - ref).max() <= TOL
+    got = renderer.download_volume(0, vol.Resolution, vol.VolumeExtends)
+    assert np.array_equal(got.density.view(np.uint32), vol.density.view(np.uint32)) and np.array_equal(got.material_id, vol.material_id)
+
+
+def test_a_captured_ray_query_replays_over_the_stamped_volume(renderer):
+    """vrt.h: a region edit shows in the replay of a captured vrt_trace_rays launch.  The rays are a frame's camera rays."""
+    import torch
+
+    sc, vol = X.edit_scene("stamp")
+    w, h = 200, 120
+    p = v.default_params(w, h, scenes.min_cell(sc), 255, shadow=False)
+    renderer.SetSceneToRender(sc)
+    renderer.SyncWithScene()
+    prepare_edit(renderer, "stamp", vol)
+    pixels = np.stack(np.meshgrid(np.arange(w), np.arange(h), indexing="xy"), -1).reshape(-1, 2)
+    host_rays = renderer.camera_rays(pixels, w, h)
+    n = len(host_rays)
+    rays = torch.from_numpy(host_rays.view(np.float32).reshape(n, 8).copy()).to("cuda:0")
+    hits = torch.zeros((n, 12), dtype=torch.int32, device="cuda:0")
+    as_dict = lambda t: v.hits_to_dict(np.ascontiguousarray(t.cpu().numpy()).view(v.HIT_DTYPE).reshape(-1))
+    side = torch.cuda.Stream()
+    with torch.cuda.stream(side):
+        renderer.trace_rays_device(p, _abi.QUERY_CLOSEST, n, rays.data_ptr(), hits.data_ptr(), side.cuda_stream)
+    torch.cuda.synchronize()
+    old = as_dict(hits)
+    g = torch.cuda.CUDAGraph()
+    with torch.cuda.graph(g, stream=side):
+        renderer.trace_rays_device(p, _abi.QUERY_CLOSEST, n, rays.data_ptr(), hits.data_ptr(), side.cuda_stream)
+    device_edit(renderer, "stamp", vol)
+    hits.zero_()
+    g.replay()
+    torch.cuda.synchronize()
+    got = as_dict(hits)
+    want = renderer.trace_rays(host_rays["origin"], host_rays["direction"], host_rays["t_max"], params=p)
+    for k in want:
+        assert np.array_equal(got[k], want[k]), k
+    assert int(old["hit"].sum()) > 1000 and int((got["t"] != old["t"]).sum()) > 50
+
+
+def test_a_context_over_two_devices_stamps_both():
+    Nd, Ns = 33, 17
+    name, matrix, scale = K.placements(Nd, Ns)[9]
+    assert name.startswith("oblique 1")
+    rec = K.record(S.ADD, matrix, scale, 1.5, S.SOURCE, 0.0)
+    _, _, want = K.reference("sphere", "torus", Nd, Ns, R.TEXEL16, R.F32, rec)
+    results = {}
+    for devices in ((0, 0), (0,)):
+        with v.VHipRenderer(devices=devices) as r:
+            upload_stamp_volume(r, EDITED, "torus", Nd, "dst", R.TEXEL16, table=True)
+            upload_stamp_volume(r, SOURCE, "sphere", Ns, "src", R.F32)
+            devs = range(len(devices))
+            src_before = [buffers(r, SOURCE, dev) for dev in devs]
+            res = r.stamp_volume(EDITED, SOURCE, rec)
+            results[devices] = (res, [buffers(r, EDITED, dev) for dev in devs], src_before, [buffers(r, SOURCE, dev) for dev in devs])
+    (res2, dst2, src_before2, src2), (res1, dst1, _, _) = results[(0, 0)], results[(0,)]
+    assert res2 == res1 == want and want["written"] > 500
+    for dev in (0, 1):
+        assert_same_buffers(dst2[dev], dst1[0], f"device {dev} of two against the single device")
+        assert_same_buffers(src2[dev], src_before2[dev], f"the source on device {dev}")
