@@ -22,6 +22,8 @@
  *   vrt_volume_download_region      sphere / box / capsule brushes evaluated on the resident volume, and the read-back of a box)
  *   vrt_volume_stamp                (no reference analogue beyond VVoxelVolume::SetVoxel, VoxelVolume.cpp:59-77, in a host loop over two
  *                                   volumes: CSG of one resident volume, placed by a matrix, into another)
+ *   vrt_volume_smooth               (no reference analogue beyond VVoxelVolume::SetVoxel, VoxelVolume.cpp:59-77, in a host loop: the
+ *                                   relaxing brush — a weighted 7-point stencil inside a sphere / box / capsule region)
  *   vrt_volume_fill_enclosed        (no reference analogue: its Voxelizer stops at the unsigned shell, Voxelizer/Private/VolumeConverter.cpp:30-84 —
  *                                   the shell of a closed mesh made solid on the resident volume, so that a SUBTRACT brush carves a solid)
  *   vrt_volume_redistance           (no reference analogue: whatever field the resident volume holds rewritten, within a band, as the
@@ -446,6 +448,69 @@ typedef struct vrt_stamp {            /* 96 B */
  * (0.017, 0.020 and 0.030 on average): the trilinear interpolant of a convex distance sags between samples by a fraction of a SOURCE
  * cell; DESIGN.md section 2 has the figures. */
 int vrt_volume_stamp(vrt_ctx* ctx, int dst_slot, int src_slot, const vrt_stamp* stamp, vrt_brush_result* result_or_null);
+
+/* The relaxing sculpt brush (no reference analogue beyond VVoxelVolume::SetVoxel in a host loop): inside a brush shape every sample
+ * moves towards the mean of its six neighbours.  Takes out the staircase a hard SUBTRACT leaves, the seam between two stamps, the
+ * texel noise of a VRT_FORMAT_TEXEL16 slot and the noise of a Voxelizer shell before vrt_volume_extract_mesh, which adds no smoothing
+ * of its own.  Unlike the brushes and the stamp it is a stencil: a sample's new value depends on its neighbours' old values. */
+#define VRT_MAX_SMOOTH_ITERATIONS 16
+typedef struct vrt_smooth {           /* 64 B */
+    int32_t shape;                    /* VRT_BRUSH_SPHERE / _BOX / _CAPSULE: the region, as vrt_brush */
+    int32_t iterations;               /* 1 .. VRT_MAX_SMOOTH_ITERATIONS */
+    float a[3], b[3], radius;         /* as vrt_brush: cells, grid coordinates */
+    float strength;                   /* 0 < strength <= 1 (<= 0.5 when rebound > 0) */
+    float falloff;                    /* > 0, cells: the weight rises from 0 at the brush surface to strength at falloff cells inside */
+    float rebound;                    /* 0 .. 1: 0 = plain relaxation; > 0 = every iteration is followed by an inflating pass (Taubin) */
+    int32_t material;                 /* 0..255, or -1 = leave material ids alone */
+    uint32_t reserved_[3];            /* 0 */
+} vrt_smooth;
+
+/* Relaxes the resident slot inside the record's shape, in place, on every device.  Waits for work already enqueued on the context's
+ * devices (a frame begun before the call renders the old volume, one begun after renders the new one); device pointers of the slot do
+ * not change.  Afterwards every device buffer of the slot equals what a full upload of the edited volume holds (what the slot derives
+ * from its samples is rebuilt over the written box; nothing is rebuilt when nothing was written), so frames and counters are those of
+ * the full upload.  A launch captured into a graph before the edit keeps the cull rectangle it was captured with (capture with
+ * VRT_FLAG_NO_CULL_RECT where an edit may grow the active box).
+ * Errors, all checked before any device state is touched: VRT_ERR_INVALID for a NULL context or record; an unknown shape; a
+ * non-finite field; iterations outside 1..VRT_MAX_SMOOTH_ITERATIONS; strength outside (0, 1]; falloff <= 0; rebound outside [0, 1];
+ * rebound > 0 with strength > 0.5; the shape rules of vrt_volume_apply_brushes (a radius or half size that is not positive, a negative
+ * rounding radius, a capsule with a == b; a sphere's b is only checked for being finite); a material outside -1..255; non-zero
+ * reserved words.  VRT_ERR_SLOT for an unused slot.  VRT_ERR_OOM when the scratch memory (three floats per sample of the region's box)
+ * cannot be allocated: it is allocated on every device before any sample is written, so the volume is untouched then.  A region that
+ * lies wholly outside the grid is VRT_OK and writes nothing (lo > hi).
+ * result_or_null: the written samples' count and box, from device 0 (all devices compute the same bytes).
+ *
+ * The rule is part of the contract.  All arithmetic is fp32, evaluated as parenthesised, no fused multiply-add; sqrtf and / are
+ * correctly rounded.  p = ((float)ix, (float)iy, (float)iz).
+ *   1. Region and weight.  s is the brush distance of the sample, exactly as at vrt_volume_apply_brushes (Sphere, Capsule, Box).
+ *      A sample is IN THE REGION iff s < 0; its weight is w = strength * fminf((-s) / falloff, 1.0f).
+ *   2. Decode.  f0 is the sample's density as for the brushes: the stored float, or stored * 0.01f (VRT_FORMAT_TEXEL16) — for every
+ *      sample of the grid.
+ *   3. One pass with the weight field u.  For a region sample: L = ((f(x-1) + f(x+1)) + (f(y-1) + f(y+1))) + (f(z-1) + f(z+1)), a
+ *      neighbour beyond the grid being the sample itself; avg = L * 0.16666667f (the float nearest to 1/6, bits 0x3E2AAAAB);
+ *      f' = f + (u * (avg - f)).  Samples outside the region keep f.  Every read of a pass sees the field BEFORE that pass (Jacobi):
+ *      the result does not depend on how the device schedules its work.
+ *   4. Iterations.  Each of the `iterations` rounds is one pass with u = w and, when rebound > 0, one more with u = -(rebound * w).
+ *      Values stay fp32 between passes: a TEXEL16 slot is NOT re-quantised in between, unlike between two brush records — the
+ *      texel rule truncates towards zero, and many small moves would each be cut back.
+ *   5. Write.  m is the region sample's value after the last pass; the value to store is m (F32) or the texel of m (TEXEL16: the rule
+ *      at vrt_set_volume_format).  The sample is written iff m == m and the value to store differs IN BITS from the stored value: a
+ *      TEXEL16 sample whose texel did not move keeps its bits and is not counted.  (The comparison is between texels: a stored
+ *      q = 5, 10, 15, 20, 23, ... decodes to a value whose texel is q - 1, so such a region sample is written unless the passes lift
+ *      it back over that boundary.)  Everything else keeps its bits.  NaN is never written; a NaN or inf - inf among the neighbours simply
+ *      propagates by the arithmetic above.
+ *   6. Material of a written sample.  material >= 0: m <= 0 ? material : 0.  material -1: untouched.
+ * Choosing values.  A pass multiplies the grid's checkerboard mode by 1 - 2u: strength 0.5 annihilates it, strength 1 flips its sign.
+ * That is why a rebound pass needs strength <= 0.5: then every mode's factor per round, (1 + u*l)(1 - rebound*u*l) with l in
+ * [-2, 0], stays within [0, 1].  Plain relaxation is mean-curvature flow: a convex surface of radius R retreats by about w/(3R)
+ * cells per iteration; the rebound removes that first-order retreat.  The rule is linear, so the call works on any field, shells
+ * included; it does not leave a distance field — vrt_volume_redistance over the written box grown by the band repairs that, as it
+ * does after a brush.
+ * What the rule is worth: an analytic sphere SDF of 10.4 cells on 33^3 with uniform noise of +-0.3 cells per sample has zero
+ * crossings (on grid edges) with an RMS radial error of 0.140 cells; whole-grid smoothing at strength 0.5 leaves 0.066 after two
+ * plain iterations, the surface having retreated by 0.033 cells on average, and 0.056 after eight iterations with rebound 1, the
+ * surface within 0.001 cells of where it was (eight plain iterations: a retreat of 0.131 cells).  DESIGN.md section 2 has the table. */
+int vrt_volume_smooth(vrt_ctx* ctx, int slot, const vrt_smooth* smooth, vrt_brush_result* result_or_null);
 
 /* Solid volumes from shells (no reference analogue: its Voxelizer stops at the shell).  vrt_voxelize_mesh and the CPU converter leave the
  * reference's UNSIGNED shell field, density = dist/thr - 0.5: inside a closed mesh the field is positive again, so a VRT_BRUSH_SUBTRACT dab

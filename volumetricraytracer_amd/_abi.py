@@ -76,6 +76,9 @@ BRUSH_ADD, BRUSH_SUBTRACT, BRUSH_PAINT = 0, 1, 2
 STAMP_ADD, STAMP_SUBTRACT, STAMP_REPLACE = 0, 1, 2
 STAMP_MATERIAL_KEEP, STAMP_MATERIAL_SOURCE = -1, -2
 
+# vrt_volume_smooth
+MAX_SMOOTH_ITERATIONS = 16
+
 QUERY_CLOSEST = 0
 QUERY_ANY = 1  # occlusion: instance 0 when some surface lies within [0, t_max]
 
@@ -241,6 +244,21 @@ class vrt_stamp(C.Structure):
     ]
 
 
+class vrt_smooth(C.Structure):
+    _fields_ = [
+        ("shape", C.c_int32),
+        ("iterations", C.c_int32),
+        ("a", C.c_float * 3),
+        ("b", C.c_float * 3),
+        ("radius", C.c_float),
+        ("strength", C.c_float),
+        ("falloff", C.c_float),
+        ("rebound", C.c_float),
+        ("material", C.c_int32),
+        ("reserved_", C.c_uint32 * 3),
+    ]
+
+
 class vrt_fill_result(C.Structure):
     _fields_ = [("lo", C.c_int32 * 3), ("hi", C.c_int32 * 3), ("filled", C.c_uint64), ("sweeps", C.c_uint32), ("reserved_", C.c_uint32)]
 
@@ -276,6 +294,7 @@ SYMBOLS = {
     "vrt_volume_update_voxels": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int), C.c_void_p]),
     "vrt_volume_apply_brushes": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.POINTER(vrt_brush), C.POINTER(vrt_brush_result)]),
     "vrt_volume_stamp": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.POINTER(vrt_stamp), C.POINTER(vrt_brush_result)]),
+    "vrt_volume_smooth": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(vrt_smooth), C.POINTER(vrt_brush_result)]),
     "vrt_volume_fill_enclosed": (C.c_int, [C.c_void_p, C.c_int, C.c_float, C.c_int, C.POINTER(vrt_fill_result)]),
     "vrt_volume_redistance": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int),
                                         C.POINTER(vrt_redistance_result)]),

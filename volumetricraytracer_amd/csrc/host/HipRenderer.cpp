@@ -802,6 +802,27 @@ bool VHipRenderer::ApplyBrushes(const Scene::VVoxelObject& object, const std::ve
     return MirrorBox(slot, *volume, res.lo, res.hi);
 }
 
+bool VHipRenderer::SmoothVolume(const Scene::VVoxelObject& object, const vrt_smooth& smooth, vrt_brush_result* result) {
+    if (!IsActive()) {
+        V_LOG_WARNING("SmoothVolume() on an inactive renderer");
+        return false;
+    }
+    const VObjectPtr<Scene::VScene> scene = SceneRef.lock();
+    const VObjectPtr<Voxel::VVoxelVolume> volume = object.GetVoxelVolume();
+    if (!scene || !volume) return false;
+    if (!SyncWithScene(*scene)) return false;
+    const int slot = SlotOf(volume.get());
+    if (slot < 0) {
+        V_LOG_ERROR("SmoothVolume(): the object's volume is not part of the rendered scene");
+        return false;
+    }
+    vrt_brush_result res;
+    if (!ok(vrt_volume_smooth(Ctx, slot, &smooth, &res), "vrt_volume_smooth")) return false;
+    if (result) *result = res;
+    if (res.written == 0) return true;
+    return MirrorBox(slot, *volume, res.lo, res.hi);
+}
+
 vrt_stamp VHipRenderer::StampFromPlacement(unsigned srcSize, const VVector& position, const VQuat& rotation, float scale, int op, int material,
                                            float offset, float blend, float reach) {
     vrt_stamp rec;

@@ -121,6 +121,11 @@ public:
        VRT_FORMAT_TEXEL16 the mirror receives the decoded texels (q * 0.01), which quantise again — and need not give q back — should
        the volume be uploaded whole later.  False (after logging) on failure or when the object's volume is not in the scene. */
     bool ApplyBrushes(const Scene::VVoxelObject& object, const std::vector<vrt_brush>& brushes, vrt_brush_result* result = nullptr);
+    /* The relaxing brush on the device (vrt_volume_smooth; the rule: vrt.h): inside the record's shape every sample of the volume of a
+       placed object of the scene Render() would draw now (synced first) moves towards the mean of its six neighbours.  The written box
+       is read back into the host VVoxelVolume like ApplyBrushes does.  False (after logging) on failure or when the object's volume is
+       not in the scene. */
+    bool SmoothVolume(const Scene::VVoxelObject& object, const vrt_smooth& smooth, vrt_brush_result* result = nullptr);
     /* CSG with an arbitrary shape on the device (vrt_volume_stamp; the rule: vrt.h): srcVolume — any volume, of any resolution, not one
        of the rendered scene — merged into the volume of a placed object of the scene Render() would draw now (synced first).  The
        source's centre sample is put at `position` (grid coordinates of the object's volume, xyz, fractions allowed), turned by

@@ -4,6 +4,7 @@
 #include "../fill_core.h"
 #include "../mesh_core.h"
 #include "../redistance_core.h"
+#include "../smooth_core.h"
 #include "../stamp_core.h"
 #include "../voxelize_core.h"
 
@@ -286,6 +287,72 @@ VVolumeConverter::VStampResult VVolumeConverter::Stamp(Voxel::VVoxelVolume& dst,
     const float unitSrc = vrt_stamp_core::unit_of((int)src.GetSize(), src.GetVolumeExtends(), src.DensityScale);
     const VStampResult out = Stamp(dst.GetVoxels().data(), dst.GetSize(), unitDst, false, src.GetVoxels().data(), src.GetSize(), unitSrc, false, stamp);
     if (out.Written) dst.MakeDirty();
+    return out;
+}
+
+VVolumeConverter::VStampResult VVolumeConverter::Smooth(Voxel::VVoxel* voxels, size_t n, bool texel16, const ::vrt_smooth& smooth) {
+    namespace S = vrt_smooth_core;
+    const int N = (int)n;
+    VStampResult out;
+    out.Lo = VIntVector(N, N, N);
+    out.Hi = VIntVector(-1, -1, -1);
+    int lo[3], hi[3], wlo[3], whi[3];
+    if (!S::valid(smooth) || !S::boxes(smooth, N, lo, hi, wlo, whi)) return out;
+    /* the work box, [x][z][y] like the grid: two copies of the decoded field and the weights */
+    const int nx = whi[0] - wlo[0] + 1, ny = whi[1] - wlo[1] + 1, nz = whi[2] - wlo[2] + 1;
+    const size_t count = (size_t)nx * nz * ny;
+    const auto at = [&](int x, int y, int z) { return ((size_t)x * nz + (size_t)z) * ny + (size_t)y; }; /* box coordinates */
+    const auto voxel_at = [&](int x, int y, int z) -> Voxel::VVoxel& {
+        return voxels[((size_t)(wlo[0] + x) * n + (size_t)(wlo[2] + z)) * n + (size_t)(wlo[1] + y)];
+    };
+    std::vector<float> copy[2] = {std::vector<float>(count), std::vector<float>(count)}, weights(count);
+    for (int x = 0; x < nx; x++)
+        for (int z = 0; z < nz; z++)
+            for (int y = 0; y < ny; y++) {
+                const int gx = wlo[0] + x, gy = wlo[1] + y, gz = wlo[2] + z;
+                copy[0][at(x, y, z)] = S::decode(voxel_at(x, y, z).Density, texel16);
+                const bool boxed = gx >= lo[0] && gx <= hi[0] && gy >= lo[1] && gy <= hi[1] && gz >= lo[2] && gz <= hi[2];
+                weights[at(x, y, z)] = boxed ? S::weight(smooth, (float)gx, (float)gy, (float)gz) : S::kOutside;
+            }
+    const int passes = S::passes(smooth);
+    for (int p = 0; p < passes; p++) {
+        const std::vector<float>& src = copy[p & 1];
+        std::vector<float>& dst = copy[(p + 1) & 1];
+        for (int x = 0; x < nx; x++)
+            for (int z = 0; z < nz; z++)
+                for (int y = 0; y < ny; y++) {
+                    const size_t i = at(x, y, z);
+                    const float f = src[i], w = weights[i];
+                    /* a region sample's neighbour lies in the work box unless the grid ends there: then it is the sample itself */
+                    dst[i] = !S::in_region(w) ? f
+                                              : S::relax(f, src[at(std::max(x - 1, 0), y, z)], src[at(std::min(x + 1, nx - 1), y, z)],
+                                                         src[at(x, std::max(y - 1, 0), z)], src[at(x, std::min(y + 1, ny - 1), z)],
+                                                         src[at(x, y, std::max(z - 1, 0))], src[at(x, y, std::min(z + 1, nz - 1))],
+                                                         S::pass_weight(smooth, p, w));
+                }
+    }
+    const std::vector<float>& last = copy[passes & 1];
+    for (int x = 0; x < nx; x++)
+        for (int z = 0; z < nz; z++)
+            for (int y = 0; y < ny; y++) {
+                const size_t i = at(x, y, z);
+                if (!S::in_region(weights[i])) continue;
+                Voxel::VVoxel& voxel = voxel_at(x, y, z);
+                float value;
+                if (!S::stores(last[i], voxel.Density, texel16, value)) continue;
+                voxel.Density = value;
+                if (smooth.material >= 0) voxel.Material = (uint8_t)S::written_material(smooth.material, last[i]);
+                const int gx = wlo[0] + x, gy = wlo[1] + y, gz = wlo[2] + z;
+                out.Lo = VIntVector(std::min(out.Lo.X, gx), std::min(out.Lo.Y, gy), std::min(out.Lo.Z, gz));
+                out.Hi = VIntVector(std::max(out.Hi.X, gx), std::max(out.Hi.Y, gy), std::max(out.Hi.Z, gz));
+                out.Written++;
+            }
+    return out;
+}
+
+VVolumeConverter::VStampResult VVolumeConverter::Smooth(Voxel::VVoxelVolume& volume, const ::vrt_smooth& smooth) {
+    const VStampResult out = Smooth(volume.GetVoxels().data(), volume.GetSize(), false, smooth);
+    if (out.Written) volume.MakeDirty();
     return out;
 }
 

@@ -18,6 +18,7 @@
 
 struct vrt_ctx; /* include/vrt.h */
 struct vrt_stamp;
+struct vrt_smooth;
 
 namespace VolumeRaytracer {
 namespace Voxelizer {
@@ -99,6 +100,14 @@ public:
        grid's records hold the integer field +-q of a VRT_FORMAT_TEXEL16 slot. */
     static VStampResult Stamp(Voxel::VVoxel* dst, size_t nd, float unitDst, bool dstTexel16, const Voxel::VVoxel* src, size_t ns, float unitSrc,
                               bool srcTexel16, const ::vrt_stamp& stamp);
+    /* The relaxing brush, in place — the rule of vrt_volume_smooth (include/vrt.h; its arithmetic is csrc/smooth_core.h, shared with the
+       HIP kernels), as a plain loop with two buffers over the region's box grown by one sample: inside the record's shape every
+       sample moves towards the mean of its six neighbours, `iterations` times, each followed by an inflating pass when rebound > 0.
+       Marks the volume dirty when it wrote.  The record must be one vrt_volume_smooth accepts (vrt_smooth_core::valid); otherwise
+       nothing is written.  The result is reported like Stamp's. */
+    static VStampResult Smooth(Voxel::VVoxelVolume& volume, const ::vrt_smooth& smooth);
+    /* The same on n^3 VVoxel records (index x*n*n + z*n + y); texel16: the records hold the integer field +-q of a VRT_FORMAT_TEXEL16 slot. */
+    static VStampResult Smooth(Voxel::VVoxel* voxels, size_t n, bool texel16, const ::vrt_smooth& smooth);
     static bool ExtractResolutionFromName(const std::string& name, uint8_t& outResolution);
     /* extraction threshold of a volume: cell size · √3 (VolumeConverter.cpp:57) */
     static float ExtractionThreshold(const Voxel::VVoxelVolume& volume);

@@ -20,6 +20,9 @@
  *            [--edit-stamp]                 with --edit-brush: instead of the analytic sphere a 33^3 torus SDF, uploaded once into a spare slot, is stamped
  *                                           with SUBTRACT at the brush or pick position, R cells across its outer radius and turned a little further every
  *                                           frame (VHipRenderer::StampVolume, vrt_volume_stamp): an arbitrary shape carved on the device; implies --edit-device
+ *            [--edit-smooth S]              with --edit-device or --edit-stamp: after every dab one smooth record runs at the dab's position — a sphere of 1.5 R
+ *                                           cells, strength S, two iterations, no rebound (VHipRenderer::SmoothVolume, vrt_volume_smooth): the carve's
+ *                                           staircase relaxed on the device; with --sdf BAND it runs before the redistance of the dab's box
  *            [--solid]                      the red sphere is built as the Voxelizer builds a mesh — an unsigned shell, density = |distance to its surface| / thr - 0.5
  *                                           with thr = cell * sqrt 3, positive again inside — and, after the upload, every volume of the scene has its enclosed
  *                                           cavities filled on the device (VHipRenderer::FillEnclosed, vrt_volume_fill_enclosed; wall 1, material 1): --edit-brush
@@ -112,6 +115,7 @@ int main(int argc, char** argv) {
     bool identityDefaults = false;
     int editBrush = 0, sdf = 0;
     bool editFull = false, editDevice = false, editStamp = false, solid = false;
+    float editSmooth = 0.f;
     bool pick = false;
     int pickX = 0, pickY = 0;
     int mode = 0, inFlight = 3, block = 0; /* three frames in flight: the reference's swap chain (FrameCount, DXConstants.cpp:23) */
@@ -132,6 +136,7 @@ int main(int argc, char** argv) {
         else if (!strcmp(argv[i], "--edit-full")) editFull = true;
         else if (!strcmp(argv[i], "--edit-device")) editDevice = true;
         else if (!strcmp(argv[i], "--edit-stamp")) editStamp = editDevice = true;
+        else if (!strcmp(argv[i], "--edit-smooth") && i + 1 < argc) editSmooth = (float)atof(argv[++i]);
         else if (!strcmp(argv[i], "--solid")) solid = true;
         else if (!strcmp(argv[i], "--sdf") && i + 1 < argc) sdf = atoi(argv[++i]);
         else if (!strcmp(argv[i], "--mesh-out") && i + 1 < argc) meshOut = argv[++i];
@@ -197,6 +202,10 @@ int main(int argc, char** argv) {
         fprintf(stderr, "--edit-stamp stamps on the device where --edit-brush R would dab: it needs the HIP renderer and --edit-brush\n");
         return 1;
     }
+    if (editSmooth != 0.f && (!hip || !editDevice || editBrush <= 0 || !(editSmooth > 0.f && editSmooth <= 1.f))) {
+        fprintf(stderr, "--edit-smooth S relaxes every dab on the device: it needs --edit-brush with --edit-device or --edit-stamp, and 0 < S <= 1\n");
+        return 1;
+    }
     if (editDevice && !hip) editDevice = false;
     if (pick && (!hip || block > 0)) {
         fprintf(stderr, "--pick asks the HIP renderer once per frame: drop --block\n");
@@ -242,7 +251,7 @@ int main(int argc, char** argv) {
     }
     const std::shared_ptr<Voxel::VVoxelVolume> stampTorus = editStamp ? InitStampTorus() : nullptr;
     int stampTurns = 0;
-    unsigned long long stampedVoxels = 0;
+    unsigned long long stampedVoxels = 0, smoothedVoxels = 0;
     double kernel_ms = 0.0;
     bool warmUp = true; /* the untimed first frame prints no pick record */
     /* the brush: a sphere of editBrush cells around voxel c — a point that circles the red sphere's centre 12 cells out, 4 cells above
@@ -266,6 +275,26 @@ int main(int argc, char** argv) {
                 b.reach = 2.f;
                 b.material = 0;
                 done = hip->ApplyBrushes(*sphere1, {b}, &wrote);
+            }
+            if (done && editSmooth > 0.f) { /* the dab relaxed: a sphere half as large again, two plain iterations */
+                vrt_smooth s;
+                memset(&s, 0, sizeof s);
+                s.shape = VRT_BRUSH_SPHERE;
+                s.iterations = 2;
+                s.a[0] = (float)c.X, s.a[1] = (float)c.Y, s.a[2] = (float)c.Z;
+                s.radius = 1.5f * (float)editBrush;
+                s.strength = editSmooth;
+                s.falloff = 0.5f * (float)editBrush;
+                s.material = 0;
+                vrt_brush_result smoothed;
+                if (hip->SmoothVolume(*sphere1, s, &smoothed) && smoothed.written > 0) {
+                    smoothedVoxels += smoothed.written;
+                    for (int a = 0; a < 3; a++) { /* the redistance below covers both edits */
+                        wrote.lo[a] = wrote.written ? std::min(wrote.lo[a], smoothed.lo[a]) : smoothed.lo[a];
+                        wrote.hi[a] = wrote.written ? std::max(wrote.hi[a], smoothed.hi[a]) : smoothed.hi[a];
+                    }
+                    wrote.written += smoothed.written;
+                }
             }
             if (done && sdf > 0 && wrote.written > 0) { /* the dab's box grown by the band, a distance again */
                 const VIntVector lo(wrote.lo[0] - sdf, wrote.lo[1] - sdf, wrote.lo[2] - sdf), hi(wrote.hi[0] + sdf, wrote.hi[1] + sdf, wrote.hi[2] + sdf);
@@ -347,6 +376,7 @@ int main(int argc, char** argv) {
     const double wall = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
     if (sdf > 0 && editDevice && editBrush > 0) printf("sdf: %llu voxels redistanced around the dabs from %llu surfels\n", dabSamples, dabSurfels);
     if (editStamp) printf("stamp: %d torus stamps wrote %llu voxels on the device\n", stampTurns, stampedVoxels);
+    if (editSmooth > 0.f) printf("smooth: strength %g relaxed %llu voxels around the dabs on the device\n", editSmooth, smoothedVoxels);
     if (editBrush > 0)
         printf("brush of %d cells, %s; ", editBrush, editStamp ? "device stamps" : (editDevice ? "device brushes" : (editFull ? "full uploads" : "region updates")));
     printf("%d frames %ux%u %s%s: %.3f ms/frame wall (%.0f frames/s)", frames, W, H, format.c_str(),

@@ -12,6 +12,7 @@
 #include "HostSerialization.h"
 #include "SceneConverter.h"
 #include "VolumeConverter.h"
+#include "../smooth_core.h"
 #include "../stamp_core.h"
 
 using namespace VolumeRaytracer;
@@ -170,6 +171,21 @@ int vrh_stamp(vrt_voxel* dst, int nd, float dst_extent, float dst_density_scale,
     const auto r = Voxelizer::VVolumeConverter::Stamp(reinterpret_cast<Voxel::VVoxel*>(dst), (size_t)nd, vrt_stamp_core::unit_of(nd, dst_extent, dst_density_scale),
                                                       dst_texel16 != 0, reinterpret_cast<const Voxel::VVoxel*>(src), (size_t)ns,
                                                       vrt_stamp_core::unit_of(ns, src_extent, src_density_scale), src_texel16 != 0, *stamp);
+    if (result_or_null) *result_or_null = vrt_brush_result{{r.Lo.X, r.Lo.Y, r.Lo.Z}, {r.Hi.X, r.Hi.Y, r.Hi.Z}, (uint64_t)r.Written};
+    return VRT_OK;
+}
+
+/* VVolumeConverter::Smooth on caller records: n^3 records edited in place (index x*n*n + z*n + y); extent and density_scale are the
+   grid's metric as vrh_stamp takes it (the rule works in cells and in the stored units: neither enters it); texel16 != 0: the densities
+   are the integer field +-q; result_or_null as vrt_volume_smooth reports.  The record passes the argument rules of vrt_volume_smooth:
+   VRT_OK, or VRT_ERR_INVALID as that call returns it (a NULL pointer or a grid below 2 samples likewise). */
+int vrh_smooth(vrt_voxel* voxels, int n, float extent, float density_scale, int texel16, const vrt_smooth* smooth, vrt_brush_result* result_or_null) {
+    (void)extent, (void)density_scale;
+    if (!voxels || !smooth || n < 2 || !vrt_smooth_core::valid(*smooth)) {
+        g_error = "vrh_smooth: bad argument";
+        return VRT_ERR_INVALID;
+    }
+    const auto r = Voxelizer::VVolumeConverter::Smooth(reinterpret_cast<Voxel::VVoxel*>(voxels), (size_t)n, texel16 != 0, *smooth);
     if (result_or_null) *result_or_null = vrt_brush_result{{r.Lo.X, r.Lo.Y, r.Lo.Z}, {r.Hi.X, r.Hi.Y, r.Hi.Z}, (uint64_t)r.Written};
     return VRT_OK;
 }

@@ -28,6 +28,8 @@
 #include "voxelize_core.h"
 #include "redistance_core.h"
 #include "stamp_core.h"
+#include "brush_core.h"
+#include "smooth_core.h"
 
 using namespace vrt;
 
@@ -93,6 +95,7 @@ static_assert(kDynMaxPointLights == VRT_MAX_POINT_LIGHTS && kDynMaxSpotLights ==
 static_assert(sizeof(vrt_ray) == 32 && sizeof(vrt_hit) == 48, "query_kernel reads two and writes three 16-B words per ray");
 static_assert(sizeof(vrt_brush) == 64 && sizeof(vrt_brush_result) == 32, "vrt.h states these sizes");
 static_assert(sizeof(vrt_stamp) == 96, "vrt.h states this size");
+static_assert(sizeof(vrt_smooth) == 64, "vrt.h states this size");
 static_assert(sizeof(vrt_fill_result) == 40, "vrt.h states this size");
 static_assert(sizeof(vrt_redistance_result) == 48, "vrt.h states this size");
 static_assert(sizeof(vrt_mesh_result) == 40, "vrt.h states this size");
@@ -234,6 +237,9 @@ struct DeviceState {
     size_t mesh_scratch_cap = 0;
     void* mesh_out = nullptr;
     size_t mesh_out_cap = 0;
+    /* vrt_volume_smooth: two fp32 copies of the work box and its weights (grown on demand, shared by the slots) */
+    void* smooth_scratch = nullptr;
+    size_t smooth_scratch_cap = 0;
     /* vrt_trace_rays_host: the rays and then the hit records of a batch (grown on demand) */
     void* query_buf = nullptr;
     size_t query_cap = 0;
@@ -564,6 +570,7 @@ void destroy_device(DeviceState& D) {
     if (D.redist_surfels) (void)hipFree(D.redist_surfels);
     if (D.mesh_scratch) (void)hipFree(D.mesh_scratch);
     if (D.mesh_out) (void)hipFree(D.mesh_out);
+    if (D.smooth_scratch) (void)hipFree(D.smooth_scratch);
     if (D.query_buf) (void)hipFree(D.query_buf);
     if (D.d_vols) (void)hipFree(D.d_vols);
     if (D.d_inst) (void)hipFree(D.d_inst);
@@ -837,44 +844,10 @@ int update_region(vrt_ctx* ctx, int slot, const int origin[3], const int size[3]
     return sync_volume_table(ctx);
 }
 
-/* vrt_volume_apply_brushes: the argument rules of vrt.h for one record. */
-bool valid_brush(const vrt_brush& r) {
-    if (r.shape != VRT_BRUSH_SPHERE && r.shape != VRT_BRUSH_BOX && r.shape != VRT_BRUSH_CAPSULE) return false;
-    if (r.op != VRT_BRUSH_ADD && r.op != VRT_BRUSH_SUBTRACT && r.op != VRT_BRUSH_PAINT) return false;
-    for (int a = 0; a < 3; a++)
-        if (!std::isfinite(r.a[a]) || !std::isfinite(r.b[a])) return false;
-    for (uint32_t w : r.reserved_)
-        if (w != 0u) return false;
-    if (!std::isfinite(r.radius) || !std::isfinite(r.blend) || !std::isfinite(r.reach)) return false;
-    if (r.shape == VRT_BRUSH_BOX) {
-        if (!(r.b[0] > 0.f && r.b[1] > 0.f && r.b[2] > 0.f) || r.radius < 0.f) return false;
-    } else if (!(r.radius > 0.f)) {
-        return false;
-    }
-    if (r.shape == VRT_BRUSH_CAPSULE && r.a[0] == r.b[0] && r.a[1] == r.b[1] && r.a[2] == r.b[2]) return false;
-    if (r.material < -1 || r.material > 255) return false;
-    if (r.op == VRT_BRUSH_PAINT) return r.material >= 0;
-    return r.reach > 0.f && r.blend >= 0.f;
-}
-
-/* The samples a record can write, xyz, inclusive: the shape's bounds grown by reach (PAINT: by nothing), by one sample and by the
- * rounding of the fp32 distance at that magnitude, clipped to the grid.  False when no sample is left. */
-bool brush_box(const vrt_brush& r, int N, int lo[3], int hi[3]) {
-    for (int a = 0; a < 3; a++) {
-        double c0 = r.a[a], c1 = r.a[a], ext = r.shape == VRT_BRUSH_BOX ? r.b[a] : r.radius;
-        if (r.shape == VRT_BRUSH_CAPSULE) {
-            c0 = std::min(r.a[a], r.b[a]);
-            c1 = std::max(r.a[a], r.b[a]);
-        }
-        if (r.op != VRT_BRUSH_PAINT) ext += r.reach;
-        const double pad = 1.0 + 1e-5 * (std::max(std::fabs(c0), std::fabs(c1)) + ext + N);
-        const double l = std::max(std::floor(c0 - ext - pad), 0.0), h = std::min(std::ceil(c1 + ext + pad), (double)(N - 1));
-        if (l > h) return false;
-        lo[a] = (int)l;
-        hi[a] = (int)h;
-    }
-    return true;
-}
+/* vrt_volume_apply_brushes: the argument rules of vrt.h for one record and the samples it can write (brush_core.h, shared with the
+ * host pass of vrt_volume_smooth). */
+using vrt_brush_core::brush_box;
+using vrt_brush_core::valid_brush;
 
 /* vrt_volume_apply_brushes: the records are evaluated on the device over the union of their boxes (launch_brush_region), which
  * reports the box of the samples it wrote; what the slot derives from the samples is then recomputed over that box (rebuild_derived) —
@@ -995,6 +968,55 @@ int stamp_volume(vrt_ctx* ctx, int dst_slot, int src_slot, const vrt_stamp* rec,
         any_written = true;
         const DerivedBoxes written = derived_boxes(h, got.lo, got.hi);
         int rc = rebuild_derived(ctx, D, dst_slot, &written, false, h.abox);
+        if (rc != VRT_OK) return rc;
+    }
+    if (!any_written) return VRT_OK;
+    ctx->scene_stale = true;
+    return sync_volume_table(ctx);
+}
+
+/* vrt_volume_smooth: the work box (the region's box grown by one sample) is relaxed in scratch memory and the region samples whose
+ * bits changed are stored (launch_smooth), which reports their box; what the slot derives from its samples is then recomputed over
+ * that box (rebuild_derived) — or not at all when nothing was written.  The scratch memory of every device is there before the first
+ * sample is written.  Afterwards every buffer of the slot equals what upload_volume builds from the edited volume. */
+int smooth_volume(vrt_ctx* ctx, int slot, const vrt_smooth* rec, vrt_brush_result* result) {
+    if (!ctx || !rec || !vrt_smooth_core::valid(*rec)) return VRT_ERR_INVALID;
+    if (!valid_slot(slot) || !ctx->vol[slot].used) return VRT_ERR_SLOT;
+    HostVolume& h = ctx->vol[slot];
+    const int N = h.N;
+    if (result) *result = vrt_brush_result{{N, N, N}, {-1, -1, -1}, 0};
+    int lo[3], hi[3], work_lo[3], work_hi[3];
+    if (!vrt_smooth_core::boxes(*rec, N, lo, hi, work_lo, work_hi)) return VRT_OK; /* wholly outside the grid */
+    const EditBox region = derived_boxes(h, lo, hi).samples, work = derived_boxes(h, work_lo, work_hi).samples;
+    for (auto& D : ctx->dev) { /* frames already enqueued render the old volume; every allocation comes before any write */
+        HIP_TRY(hipSetDevice(D.ordinal));
+        HIP_TRY(hipDeviceSynchronize());
+        if (!D.d_brush) HIP_TRY(hipMalloc(&D.d_brush, kBrushSlots * sizeof(DBrushSlot)));
+        int rc = ensure_buffer(D.smooth_scratch, D.smooth_scratch_cap, smooth_scratch_bytes(work));
+        if (rc != VRT_OK) return rc;
+    }
+    bool any_written = false;
+    for (size_t di = 0; di < ctx->dev.size(); di++) {
+        DeviceState& D = ctx->dev[di];
+        HIP_TRY(hipSetDevice(D.ordinal));
+        DeviceVolume& v = D.vol[slot];
+        HIP_TRY(launch_smooth(*rec, h.format == VRT_FORMAT_TEXEL16, v.dense, v.material, N, work, region, D.smooth_scratch, D.d_brush, D.stream));
+        DBrushSlot part[kBrushSlots];
+        HIP_TRY(hipMemcpyAsync(part, D.d_brush, sizeof part, hipMemcpyDeviceToHost, D.stream));
+        HIP_TRY(hipStreamSynchronize(D.stream));
+        vrt_brush_result got = {{N, N, N}, {-1, -1, -1}, 0}; /* the partial records merged */
+        for (const DBrushSlot& p : part) {
+            for (int a = 0; a < 3; a++) {
+                got.lo[a] = std::min(got.lo[a], N - (int)p.inv_lo[a]);
+                got.hi[a] = std::max(got.hi[a], (int)p.hi1[a] - 1);
+            }
+            got.written += p.counts & 0xffffffffull;
+        }
+        if (di == 0 && result) *result = got;
+        if (got.written == 0) continue; /* every written sample is a density write: nothing written, nothing derived changes */
+        any_written = true;
+        const DerivedBoxes written = derived_boxes(h, got.lo, got.hi);
+        int rc = rebuild_derived(ctx, D, slot, &written, false, h.abox);
         if (rc != VRT_OK) return rc;
     }
     if (!any_written) return VRT_OK;
@@ -1882,6 +1904,10 @@ int vrt_volume_apply_brushes(vrt_ctx* ctx, int slot, int n, const vrt_brush* bru
 
 int vrt_volume_stamp(vrt_ctx* ctx, int dst_slot, int src_slot, const vrt_stamp* stamp, vrt_brush_result* result_or_null) {
     return stamp_volume(ctx, dst_slot, src_slot, stamp, result_or_null);
+}
+
+int vrt_volume_smooth(vrt_ctx* ctx, int slot, const vrt_smooth* smooth, vrt_brush_result* result_or_null) {
+    return smooth_volume(ctx, slot, smooth, result_or_null);
 }
 
 int vrt_volume_fill_enclosed(vrt_ctx* ctx, int slot, float wall, int material, vrt_fill_result* result_or_null) {

@@ -26,6 +26,7 @@
 #include "vrt_device.h"
 #include "vrt_launch.h"
 #include "voxelize_core.h"
+#include "brush_core.h"
 
 namespace vrt {
 
@@ -2439,21 +2440,9 @@ __global__ void scatter_region_kernel(const void* __restrict__ staging, float* _
 }
 
 /* ---- CSG brushes (vrt_volume_apply_brushes) ----
- * The arithmetic is the contract written out in vrt.h, fp32 and parenthesised as there (the build keeps -ffp-contract=off). */
-__device__ __forceinline__ float brush_dot(float ux, float uy, float uz, float vx, float vy, float vz) { return (ux * vx + uy * vy) + uz * vz; }
-__device__ __forceinline__ float brush_len(float ux, float uy, float uz) { return sqrtf(brush_dot(ux, uy, uz, ux, uy, uz)); }
-/* s: the brush's distance at sample p, in cells */
-__device__ __forceinline__ float brush_distance(const DBrush& B, float px, float py, float pz) {
-    const float ax = px - B.a[0], ay = py - B.a[1], az = pz - B.a[2]; /* p - a */
-    if (B.shape == VRT_BRUSH_SPHERE) return brush_len(ax, ay, az) - B.radius;
-    if (B.shape == VRT_BRUSH_CAPSULE) {
-        const float bx = B.b[0] - B.a[0], by = B.b[1] - B.a[1], bz = B.b[2] - B.a[2];
-        const float h = fminf(fmaxf(brush_dot(ax, ay, az, bx, by, bz) / brush_dot(bx, by, bz, bx, by, bz), 0.0f), 1.0f);
-        return brush_len(ax - bx * h, ay - by * h, az - bz * h) - B.radius;
-    }
-    const float qx = (fabsf(ax) - B.b[0]) + B.radius, qy = (fabsf(ay) - B.b[1]) + B.radius, qz = (fabsf(az) - B.b[2]) + B.radius;
-    return (brush_len(fmaxf(qx, 0.0f), fmaxf(qy, 0.0f), fmaxf(qz, 0.0f)) + fminf(fmaxf(qx, fmaxf(qy, qz)), 0.0f)) - B.radius;
-}
+ * The arithmetic is the contract written out in vrt.h, fp32 and parenthesised as there (the build keeps -ffp-contract=off); the
+ * brush's distance s at sample p, in cells, is brush_core.h's, which vrt_volume_smooth shares. */
+__device__ __forceinline__ float brush_distance(const DBrush& B, float px, float py, float pz) { return vrt_brush_core::distance(B, px, py, pz); }
 
 /* One lane per sample of the records' union box, y fastest like the dense grid.  Every lane of a wave walks the same record list (the
  * records sit in the kernel-argument block: wave-uniform loads); a sample outside a record's own box skips its distance.  A sample

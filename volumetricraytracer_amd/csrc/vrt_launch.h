@@ -141,6 +141,15 @@ hipError_t launch_stamp_region(const vrt_stamp_core::Rule& rule, bool src_texel1
                                bool dst_texel16, float* dense, uint8_t* material, int N, const EditBox& box, DBrushSlot* slots,
                                hipStream_t stream);
 
+/* vrt_volume_smooth (vrt_smooth.hip): the rule of smooth_core.h.  work: the region's box grown by one sample and clipped to the grid;
+   region: the box outside which no sample is in the region.  scratch: smooth_scratch_bytes(work) of device memory — two fp32 copies
+   of the work box and its weights.  Gathers the work box, runs the record's passes from one copy to the other (one launch each), then
+   stores the region samples whose bits changed; slots: zeroed, then the written samples' counts and box as launch_brush_region
+   reports them. */
+size_t smooth_scratch_bytes(const EditBox& work);
+hipError_t launch_smooth(const vrt_smooth& rule, bool texel16, float* dense, uint8_t* material, int N, const EditBox& work,
+                         const EditBox& region, void* scratch, DBrushSlot* slots, hipStream_t stream);
+
 /* vrt_volume_extract_mesh (vrt_mesh.hip).  The cell box of a sample box, in xyz order (the mesh rule's own): its first cell, its cells
    per axis (one less than the samples; none when the box is one sample thick somewhere) and how many runs of 64 cells a row along y has. */
 struct MeshGrid {

@@ -66,6 +66,18 @@ def capsule_brush(op: int, end_a, end_b, radius: float, blend: float = 0.0, reac
     return _brush(_abi.BRUSH_CAPSULE, op, end_a, end_b, radius, blend, reach, material)
 
 
+def smooth_record(shape: int, a, b, radius: float, strength: float = 0.5, iterations: int = 1, falloff: float = 1.0, rebound: float = 0.0,
+                  material: int = -1) -> _abi.vrt_smooth:
+    """A vrt_smooth record: the region is the shape of a brush record (BRUSH_SPHERE: centre a, b ignored; BRUSH_BOX: centre a, half
+    sizes b, rounding `radius`; BRUSH_CAPSULE: ends a and b), lengths in cells, positions in grid coordinates xyz (vrt.h)."""
+    r = _abi.vrt_smooth()
+    r.shape, r.iterations, r.material = int(shape), int(iterations), int(material)
+    for i in range(3):
+        r.a[i], r.b[i] = float(a[i]), float(b[i])
+    r.radius, r.strength, r.falloff, r.rebound = float(radius), float(strength), float(falloff), float(rebound)
+    return r
+
+
 def stamp_record(op: int, dst_to_src, length_scale: float = 1.0, offset: float = 0.0, blend: float = 0.0, reach: float = 2.0,
                  material: int = _abi.STAMP_MATERIAL_KEEP) -> _abi.vrt_stamp:
     """A vrt_stamp record from the matrix itself: dst_to_src is the row-major 3x4 matrix (12 values, or a [3, 4] array) that takes
@@ -284,6 +296,19 @@ class VHipRenderer:
         lo, hi = tuple(res.lo), tuple(res.hi)
         if res.written and vol is not None:
             self._mirror_box(dst_slot, vol, lo, hi)
+        return {"written": int(res.written), "lo": lo, "hi": hi}
+
+    def smooth_volume(self, slot: int, smooth: _abi.vrt_smooth, vol: Optional[VVoxelVolume] = None) -> dict:
+        """vrt_volume_smooth: the volume resident in `slot` relaxed on the device inside the record's shape (smooth_record): every
+        sample there moves towards the mean of its six neighbours, `iterations` times.  Given the slot's host mirror `vol`, the written
+        box is then read back as apply_brushes does.  Returns {"written", "lo", "hi"} (xyz, inclusive; lo > hi when nothing was
+        written)."""
+        self._require()
+        res = _abi.vrt_brush_result()
+        _abi.check(self._lib.vrt_volume_smooth(self._ctx, int(slot), C.byref(smooth), C.byref(res)), "vrt_volume_smooth")
+        lo, hi = tuple(res.lo), tuple(res.hi)
+        if res.written and vol is not None:
+            self._mirror_box(slot, vol, lo, hi)
         return {"written": int(res.written), "lo": lo, "hi": hi}
 
     def _mirror_box(self, slot: int, vol: VVoxelVolume, lo, hi) -> None:

@@ -47,6 +47,8 @@ def load_host() -> C.CDLL:
         lib.vrh_stamp.restype = C.c_int
         lib.vrh_stamp.argtypes = [C.c_void_p, C.c_int, C.c_float, C.c_float, C.c_int, C.c_void_p, C.c_int, C.c_float, C.c_float, C.c_int,
                                   C.POINTER(_abi.vrt_stamp), C.POINTER(_abi.vrt_brush_result)]
+        lib.vrh_smooth.restype = C.c_int
+        lib.vrh_smooth.argtypes = [C.c_void_p, C.c_int, C.c_float, C.c_float, C.c_int, C.POINTER(_abi.vrt_smooth), C.POINTER(_abi.vrt_brush_result)]
         lib.vrh_extract_mesh.restype = C.c_int
         lib.vrh_extract_mesh.argtypes = [C.c_void_p, C.c_int, C.c_float, C.c_int, C.c_float, C.POINTER(C.c_int), C.POINTER(C.c_int), C.c_void_p,
                                          C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.POINTER(_abi.vrt_mesh_result)]
@@ -152,6 +154,26 @@ def stamp_host(dst: VVoxelVolume, src: VVoxelVolume, stamp: _abi.vrt_stamp, dst_
         dst.density = np.ascontiguousarray(recs[0]["density"].reshape(dst.N, dst.N, dst.N))
         dst.material_id = np.ascontiguousarray(recs[0]["material"].reshape(dst.N, dst.N, dst.N))
         dst.dirty = True
+    return {"written": int(res.written), "lo": tuple(res.lo), "hi": tuple(res.hi)}
+
+
+def smooth_host(vol: VVoxelVolume, smooth: _abi.vrt_smooth, texel16: bool = False) -> dict:
+    """VVolumeConverter::Smooth (the host build of vrt_volume_smooth's rule) on a volume's densities and material ids, in place.
+    texel16: the densities are the integer field +-q of a TEXEL16 slot.  Raises _abi.VrtError with the code vrt_volume_smooth returns
+    for a record it refuses.  Returns {"written", "lo", "hi"} (xyz, inclusive; lo > hi when nothing was written)."""
+    lib = load_host()
+    dtype = np.dtype([("material", "u1"), ("pad", "u1", 3), ("density", "<f4")])
+    rec = np.zeros(vol.N ** 3, dtype=dtype)
+    rec["density"] = np.asarray(vol.density, np.float32).reshape(-1)
+    rec["material"] = np.asarray(vol.material_id, np.uint8).reshape(-1)
+    res = _abi.vrt_brush_result()
+    rc = lib.vrh_smooth(rec.ctypes.data, vol.N, float(vol.VolumeExtends), float(vol.density_scale), int(bool(texel16)), C.byref(smooth),
+                        C.byref(res))
+    _abi.check(rc, "vrh_smooth")
+    if res.written:
+        vol.density = np.ascontiguousarray(rec["density"].reshape(vol.N, vol.N, vol.N))
+        vol.material_id = np.ascontiguousarray(rec["material"].reshape(vol.N, vol.N, vol.N))
+        vol.dirty = True
     return {"written": int(res.written), "lo": tuple(res.lo), "hi": tuple(res.hi)}
 
 
