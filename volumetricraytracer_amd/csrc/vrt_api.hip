@@ -1729,6 +1729,7 @@ int enqueue_rows(vrt_ctx* ctx, DeviceState& D, const vrt_params* p, const RowSet
     D.timed[ring] = cap == hipStreamCaptureStatusNone && !(p->flags & VRT_FLAG_NO_TIMING);
     D.ring_frames[ring] = n_frames;
     if (D.timed[ring]) HIP_TRY(hipEventRecord(D.ev0[ring], stream));
+    fill_header(B.h, F); /* (last: F is complete) */
     HIP_TRY(launch_march(B, path, single, stream));
     if (D.timed[ring]) HIP_TRY(hipEventRecord(D.ev1[ring], stream));
     return VRT_OK;

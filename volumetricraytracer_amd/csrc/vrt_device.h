@@ -5,6 +5,7 @@
  * scalar (SGPR) loads from the kernarg segment and small read-only global arrays.
  */
 #pragma once
+#include <stddef.h>
 #include <stdint.h>
 
 namespace vrt {
@@ -39,7 +40,9 @@ constexpr int kMapLinear = 2;
 
 /* Workgroups launched for a tiles_x x tiles_y frame under a tile map. */
 inline int grid_blocks(int tiles_x, int tiles_y, int tile_map) {
-    if (tile_map != kMapSupertile) return tiles_x * tiles_y;
+    /* (whole groups of 8: block_and_wave in vrt_kernels.hip deals the four waves of 8 consecutive blocks over 32 workgroups; a frame of
+       fewer tiles than the last group holds would lose the waves whose workgroup index lies beyond the grid) */
+    if (tile_map != kMapSupertile) return ((tiles_x * tiles_y + 7) / 8) * 8;
     const int st = ((tiles_x + 3) / 4) * ((tiles_y + 3) / 4);
     return ((st + 7) / 8) * 8 * 16; /* whole supertiles, a multiple of 8 of them */
 }
@@ -213,6 +216,62 @@ struct DFrame {
                                   launch renders the scene in this struct.  Read by the DYN instantiations of the march kernels only */
 };
 
+/* The header of a march launch's kernarg: a copy of everything a wave that does NOT march reads (four out of five waves of the
+ * benchmark frame), so that the per-lane primary-ray kernels fetch it with two s_load_dwordx16 behind one wait at their entry
+ * (load_header in vrt_kernels.hip) instead of field by field through DFrame, each field behind a wait of its own where the compiler
+ * first meets a use.  A copy, in front of DFrame, rather than a regrouping of DFrame itself: the order of DFrame's fields decides how
+ * the compiler merges the marching path's kernarg loads, and a regrouped DFrame cost the kernels that never read the header (the full
+ * closest hit's, the light pass) scalar spills, a vector register and scratch.  fill_header writes it from the finished DFrame. */
+struct DHeader {
+    float inv_w, inv_h;
+    int32_t width, height;
+    int32_t row0, rows;
+    int32_t tiles_x, tiles_y;
+    int32_t tile_map;
+    int32_t rgba8;
+    int32_t strip_rows, strip_first, strip_stride;
+    int32_t env_size;
+    uint32_t stats_stride;
+    uint32_t tile_div_m;       /* the tile maps' row length ((tiles_x + 3) / 4 supertiles, or tiles_x) as a multiply-shift: magic_div */
+    const uint8_t* env;
+    float* out;
+    unsigned* stats;
+    const DCam* cams;
+    uint64_t frame_stride;
+    uint32_t tile_div_sh;
+    uint32_t strip_div_m, strip_div_sh; /* strip_rows as a multiply-shift (strip_rows > 0) */
+    int32_t diag;
+    unsigned* diag_buf;
+};
+constexpr int kFrameHeaderBytes = 128;
+static_assert(sizeof(DHeader) == kFrameHeaderBytes && offsetof(DHeader, env) == 64, "the header is two 64-byte scalar loads");
+
+/* Division by a launch constant without a division: for 0 <= n < 2^kDivBits and d >= 1,  n / d == (n * m) >> sh  with
+ * s = ceil(log2 d), sh = kDivBits + s, m = ceil(2^sh / d)  (m < 2^(kDivBits + 1), the product < 2^49).  Exact: m d = 2^sh + e with
+ * 0 <= e < d <= 2^s, so n m / 2^sh = n / d + n e / (d 2^sh), and the second term is below 1 / d — too little to carry n / d's
+ * fraction (at most (d - 1) / d) over the next integer.  Every numerator the kernels divide is a tile index or a local row of a
+ * launch of at most kMaxBlocks / 2 tiles (enqueue_rows refuses larger ones): tile indices (whole supertiles, a multiple of 8 of them,
+ * included) stay below 2^20 + 2^8, local rows below 16 * (2^19 + 32) — all below 2^24. */
+constexpr int kDivBits = 24;
+inline void magic_div(uint32_t d, uint32_t& m, uint32_t& sh) {
+    uint32_t s = 0;
+    while (s < 32 && (1ull << s) < (uint64_t)d) s++;
+    sh = (uint32_t)kDivBits + s;
+    m = (uint32_t)(((1ull << sh) + d - 1) / d);
+}
+inline void fill_header(DHeader& H, const DFrame& F) {
+    H.inv_w = F.inv_w; H.inv_h = F.inv_h;
+    H.width = F.width; H.height = F.height; H.row0 = F.row0; H.rows = F.rows;
+    H.tiles_x = F.tiles_x; H.tiles_y = F.tiles_y; H.tile_map = F.tile_map; H.rgba8 = F.rgba8;
+    H.strip_rows = F.strip_rows; H.strip_first = F.strip_first; H.strip_stride = F.strip_stride;
+    H.env_size = F.env_size; H.stats_stride = F.stats_stride;
+    H.env = F.env; H.out = F.out; H.stats = F.stats; H.cams = F.cams; H.frame_stride = F.frame_stride;
+    H.diag = F.diag; H.diag_buf = F.diag_buf;
+    const int32_t row = F.tile_map == kMapSupertile ? (F.tiles_x + 3) >> 2 : F.tiles_x;
+    magic_div((uint32_t)(row > 0 ? row : 1), H.tile_div_m, H.tile_div_sh);
+    magic_div((uint32_t)(F.strip_rows > 0 ? F.strip_rows : 1), H.strip_div_m, H.strip_div_sh);
+}
+
 /* Per-frame scene state of a launch over a scene that changes from frame to frame — what the reference re-sends every frame: the
  * scene constant buffer's light (RDXScene.cpp:703-724), the light buffers (:726-755) and the TLAS's instance list (:454-545,
  * rebuilt every frame, DXRenderer.cpp:809-825).  One section per frame at dyn + frame * kDynStride: */
@@ -240,6 +299,7 @@ static_assert(sizeof(DDyn) == 64 && kDynStride % 64 == 0, "frame sections stay 6
  * first, so frame f + 1's waves back-fill the wave slots frame f's latency-bound tail leaves empty — what the reference gets from
  * three back buffers in flight (DXConstants.cpp:23, DXRenderer.cpp:974-989), inside ONE launch. */
 struct DBlock {
+    DHeader h;                 /* (first: load_header reads it at the kernarg segment's own address) */
     DFrame f;
     DCam cam[kMaxBlockFrames];
 };

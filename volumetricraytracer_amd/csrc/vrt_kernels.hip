@@ -1128,6 +1128,11 @@ __device__ __forceinline__ unsigned wave_sum(unsigned v) {
  * XCD carries 10 % (config 3) to 18 % (config 5) more marching than the mean, frame after frame (an orbiting camera moves the object
  * slowly); rotated, every XCD has rendered every class after 8 frames.  Config 3: 61.0 -> 64.4 Grays/s (per frame; 63.8 with 8 phases
  * per block, which keeps more of an XCD's L2 warm — balance matters more). */
+/* n / d for a launch constant d as the multiply-shift the host prepared (magic_div in vrt_device.h: exact for n < 2^24).  On a
+ * wave-uniform n: s_mul_i32 + s_mul_hi_u32 + s_lshr_b64 where the division was a v_rcp_iflag_f32 / v_readfirstlane_b32 sequence of
+ * about 30 instructions. */
+__device__ __forceinline__ int div_const(int n, unsigned m, unsigned sh) { return (int)(((unsigned long long)(unsigned)n * m) >> sh); }
+
 __device__ __forceinline__ void tile_of_block(const DFrame& F, int b, int nblk, int& tile_x, int& tile_y) {
     if (F.tile_map == kMapSupertile) {
         const int rot = (int)blockIdx.y;
@@ -1139,13 +1144,36 @@ __device__ __forceinline__ void tile_of_block(const DFrame& F, int b, int nblk, 
         tile_y = (st / st_x) * 4 + (within >> 2);
     } else if (F.tile_map == kMapBand) {
         const int xcd = b & 7, q = b >> 3;
-        const int per = nblk >> 3, rem = nblk & 7;
+        const int per = nblk >> 3, rem = nblk & 7; /* (rem is 0 since grid_blocks launches whole groups of 8; the kernels that read DFrame keep their code) */
         const int L = (xcd < rem) ? xcd * (per + 1) + q : rem * (per + 1) + (xcd - rem) * per + q;
         tile_x = L % F.tiles_x;
         tile_y = L / F.tiles_x;
     } else {
         tile_x = b % F.tiles_x;
         tile_y = b / F.tiles_x;
+    }
+}
+
+/* ... from the header (the per-lane primary-ray kernels): no division. */
+template <class HR /* Header, defined below */>
+__device__ __forceinline__ void tile_of_block_h(const HR& F, int b, int nblk, int& tile_x, int& tile_y) {
+    if (F.tile_map == kMapSupertile) {
+        const int rot = (int)blockIdx.y;
+        const int xcd = (b + rot) & 7, q = b >> 3;
+        const int st = (q >> 4) * 8 + xcd;      /* supertile index, row-major over st_x columns */
+        const int within = q & 15;
+        const int st_x = (F.tiles_x + 3) >> 2;
+        const int st_y = div_const(st, F.tile_div_m, F.tile_div_sh); /* st / st_x */
+        tile_x = (st - st_y * st_x) * 4 + (within & 3);
+        tile_y = st_y * 4 + (within >> 2);
+    } else if (F.tile_map == kMapBand) {
+        const int xcd = b & 7, q = b >> 3;
+        const int L = xcd * (nblk >> 3) + q; /* (the grid is whole groups of 8 blocks: grid_blocks) */
+        tile_y = div_const(L, F.tile_div_m, F.tile_div_sh); /* L / tiles_x */
+        tile_x = L - tile_y * F.tiles_x;
+    } else {
+        tile_y = div_const(b, F.tile_div_m, F.tile_div_sh); /* b / tiles_x */
+        tile_x = b - tile_y * F.tiles_x;
     }
 }
 
@@ -1181,11 +1209,21 @@ __device__ __forceinline__ bool wave_can_reach(const DCam& C, bool valid, int px
 
 /* The frame of the launch this workgroup belongs to (blockIdx.y) and its camera record: one scalar load of 64 bytes at a
  * wave-uniform offset, from the kernarg segment or — launches of more than kMaxBlockFrames frames — from device memory. */
-__device__ __forceinline__ DCam load_cam(const DBlock& B, int frame) {
+template <bool AGAIN = false /* a second read behind the march (camera_again) */>
+__device__ __forceinline__ DCam load_cam(const DBlock& B, const DCam* cams, int frame) {
     typedef unsigned u16v __attribute__((ext_vector_type(16)));
+    /* (written as two loads, compiled as ONE from a selected address: the record's load follows the wait for `cams`, also where the
+       record lives in the kernarg.  Kept apart by force — both in flight with the header — the two 16-register results next to the
+       header's 32 cost scalar spills in every instantiation; see profiles/nonmarching_wave_life.txt) */
     u16v w;
-    if (B.f.cams != nullptr) w = *reinterpret_cast<const u16v __attribute__((address_space(4)))*>((const __attribute__((address_space(4))) DCam*)B.f.cams + frame);
-    else w = *reinterpret_cast<const u16v*>(&B.cam[frame]);
+    if constexpr (AGAIN) {
+        size_t a = cams != nullptr ? (size_t)(cams + frame) : (size_t)__builtin_amdgcn_kernarg_segment_ptr() + offsetof(DBlock, cam) + (size_t)(unsigned)frame * sizeof(DCam);
+        asm("; camera, again" : "+s"(a)); /* (not to be served from the prologue's registers: see load_header) */
+        w = *(const u16v __attribute__((address_space(4)))*)a;
+    } else {
+        w = *reinterpret_cast<const u16v*>(&B.cam[frame < kMaxBlockFrames ? frame : 0]);
+        if (cams != nullptr) w = *reinterpret_cast<const u16v __attribute__((address_space(4)))*>((const __attribute__((address_space(4))) DCam*)cams + frame);
+    }
     DCam C;
     C.cam_o[0] = __uint_as_float(w[0]); C.cam_o[1] = __uint_as_float(w[1]); C.cam_o[2] = __uint_as_float(w[2]);
     C.r0[0] = __uint_as_float(w[3]); C.r0[1] = __uint_as_float(w[4]); C.r0[2] = __uint_as_float(w[5]);
@@ -1195,6 +1233,66 @@ __device__ __forceinline__ DCam load_cam(const DBlock& B, int frame) {
     C.cull_lo = w[14]; C.cull_hi = w[15];
     return C;
 }
+
+__device__ __forceinline__ DCam load_cam(const DBlock& B, int frame) { return load_cam(B, B.f.cams, frame); }
+/* The camera record read again behind the march (the REF instantiations' view-vector length): one scalar load per hit wave instead
+ * of 11 scalar registers held across both marches. */
+__device__ __forceinline__ DCam camera_again(const DBlock& B, int frame) { return load_cam<true>(B, B.f.cams, frame); }
+
+/* The launch's header (DBlock::h, kFrameHeaderBytes: everything a wave that does not march reads) in scalar registers: two 64-byte scalar
+ * loads at the kernel's entry, issued back to back behind one wait.  Read field by field through the kernarg struct, each value is
+ * loaded in the basic block that first uses it, and an in-order wave sat out eleven such round trips, one behind the other, on its
+ * way to a sky pixel.  Now three, on the listing of march_kernel<2,true,false,false,false>: this header, the camera record (load_cam:
+ * its address waits for the header's `cams`), and the sky arm's own second read of the header (sky_wave says why), which travels under
+ * the sky texel's load. */
+struct Header {
+    float inv_w, inv_h;
+    int width, height, row0, rows, tiles_x, tiles_y, tile_map, rgba8, strip_rows, strip_first, strip_stride, env_size;
+    unsigned stats_stride, tile_div_m;
+    const uint8_t* env;
+    float* out;
+    unsigned* stats;
+    const DCam* cams;
+    uint64_t frame_stride;
+    unsigned tile_div_sh, strip_div_m, strip_div_sh;
+    int diag;
+    unsigned* diag_buf;
+};
+template <bool AGAIN = false /* the sky arm's own read (sky_wave) */>
+__device__ __forceinline__ Header load_header(const DBlock& B) {
+    typedef unsigned u16v __attribute__((ext_vector_type(16)));
+    static_assert(offsetof(DBlock, h) == 0, "the header leads the kernarg");
+    (void)B;
+    /* through a pointer the compiler cannot see through (the kernarg segment's own address, B's, behind an asm): it must not serve the
+       marching path's reads of these fields, behind the march, from the registers loaded here — they would stay live across the march
+       (on the listing: up to 50 more scalar registers spilled per instantiation).  Not volatile: a volatile asm counts as a store to
+       anywhere, and behind such a store the compiler no longer fetches the wave-uniform scene records (instance, volume) with scalar
+       loads — the march then holds them in vector registers (57 -> 85) */
+    size_t ka = (size_t)__builtin_amdgcn_kernarg_segment_ptr();
+    if constexpr (AGAIN) asm("; header, again" : "+s"(ka)); /* (a different text: two equal asms of the same input would be merged into one) */
+    else asm("" : "+s"(ka));
+    const u16v __attribute__((address_space(4)))* kp = (const u16v __attribute__((address_space(4)))*)ka;
+    const u16v a = kp[0], c = kp[1]; /* DBlock::h */
+    const auto ptr = [](unsigned lo, unsigned hi) { return (size_t)lo | ((size_t)hi << 32); };
+    Header H;
+    H.inv_w = __uint_as_float(a[0]); H.inv_h = __uint_as_float(a[1]);
+    H.width = (int)a[2]; H.height = (int)a[3]; H.row0 = (int)a[4]; H.rows = (int)a[5];
+    H.tiles_x = (int)a[6]; H.tiles_y = (int)a[7]; H.tile_map = (int)a[8]; H.rgba8 = (int)a[9];
+    H.strip_rows = (int)a[10]; H.strip_first = (int)a[11]; H.strip_stride = (int)a[12]; H.env_size = (int)a[13];
+    H.stats_stride = a[14]; H.tile_div_m = a[15];
+    /* (global pointers, as the kernarg's own are known to be: stores through them are global_store, not flat_store) */
+    H.env = (const uint8_t*)(gbyte_p)ptr(c[0], c[1]);
+    H.out = (float*)(float __attribute__((address_space(1)))*)ptr(c[2], c[3]);
+    H.stats = (unsigned*)(unsigned __attribute__((address_space(1)))*)ptr(c[4], c[5]);
+    H.cams = (const DCam*)(const DCam __attribute__((address_space(1)))*)ptr(c[6], c[7]);
+    H.frame_stride = ptr(c[8], c[9]);
+    H.tile_div_sh = c[10]; H.strip_div_m = c[11]; H.strip_div_sh = c[12];
+    H.diag = (int)c[13];
+    H.diag_buf = (unsigned*)(unsigned __attribute__((address_space(1)))*)ptr(c[14], c[15]);
+    return H;
+}
+static_assert(offsetof(DHeader, tile_div_m) == 60 && offsetof(DHeader, frame_stride) == 96 && offsetof(DHeader, tile_div_sh) == 104 &&
+              offsetof(DHeader, diag) == 116 && offsetof(DHeader, cams) == 88, "load_header's word indices");
 
 /* The scene a frame of the launch renders.  Static launches: the kernarg's own (no copy).  DYN instantiations (vrt_block::scenes —
  * objects and lights that move from frame to frame, as in the reference's demo, RendererEngineInstance.cpp:111-130): the kernarg's
@@ -1229,7 +1327,8 @@ __device__ __forceinline__ const DFrame& frame_view(const DBlock& B, int frame, 
 }
 
 /* Camera ray of pixel (px,py) (Ray.hlsli:36-48, then normalised). */
-__device__ __forceinline__ void camera_ray(const DFrame& F, const DCam& C, int px, int py, F3& o, F3& d) {
+template <class FR>
+__device__ __forceinline__ void camera_ray(const FR& F, const DCam& C, int px, int py, F3& o, F3& d) {
     float sx = (((float)px + 0.5f) * F.inv_w) * 2.0f - 1.0f; /* 1/width, 1/height from the host (oracle: the same two products) */
     float sy = (((float)py + 0.5f) * F.inv_h) * 2.0f - 1.0f;
     float tx = sx * C.cx;
@@ -1262,8 +1361,8 @@ struct Counters {
  */
 /* UNIT: every ray / hit counter of a lane is 0 or 1 (the lean kernels): one ballot + popcount each on the scalar unit instead of
    a 12-instruction shuffle reduction. */
-template <bool DIAG, bool UNIT = false, bool ADD = false /* a later pass of a launch adds to the record an earlier one wrote */>
-__device__ __forceinline__ void write_records(const DFrame& F, int frame, int b, int wave, int lane, Counters k, const DiagAcc& dg,
+template <bool DIAG, bool UNIT = false, bool ADD = false /* a later pass of a launch adds to the record an earlier one wrote */, class FR = DFrame>
+__device__ __forceinline__ void write_records(const FR& F, int frame, int b, int wave, int lane, Counters k, const DiagAcc& dg,
                                               unsigned long long t_start) {
     const size_t frame_words = (size_t)(unsigned)frame * F.stats_stride; /* this frame's records within the launch's buffers */
     const unsigned ex_lane = k.n_hits >> kExhaustedShift;
@@ -1378,7 +1477,8 @@ __device__ __forceinline__ unsigned unorm8(float c) {
     return (unsigned)(fminf(c, 1.0f) * 255.0f + 0.5f);
 }
 
-__device__ __forceinline__ void store_pixel(const DFrame& F, int frame, unsigned pix /* pyl * width + px */, F3 color) {
+template <class FR>
+__device__ __forceinline__ void store_pixel(const FR& F, int frame, unsigned pix /* pyl * width + px */, F3 color) {
     char* const out = reinterpret_cast<char*>(F.out) + (size_t)(unsigned)frame * F.frame_stride;
     const float r = tonemap(color.x), g = tonemap(color.y), b = tonemap(color.z);
     /* streaming stores: a frame writes as many bytes as an XCD's whole L2 holds; they must not push the bricks out */
@@ -1398,6 +1498,14 @@ __device__ __forceinline__ void store_pixel(const DFrame& F, int frame, unsigned
 __device__ __forceinline__ int frame_row(const DFrame& F, int pyl) {
     if (F.strip_rows > 0) {
         const int s = pyl / F.strip_rows;
+        return (s * F.strip_stride + F.strip_first) * F.strip_rows + (pyl - s * F.strip_rows);
+    }
+    return F.row0 + pyl;
+}
+/* ... from the header: no division. */
+__device__ __forceinline__ int frame_row(const Header& F, int pyl) {
+    if (F.strip_rows > 0) {
+        const int s = div_const(pyl, F.strip_div_m, F.strip_div_sh); /* pyl / strip_rows */
         return (s * F.strip_stride + F.strip_first) * F.strip_rows + (pyl - s * F.strip_rows);
     }
     return F.row0 + pyl;
@@ -1498,6 +1606,65 @@ __device__ __forceinline__ void textured_surface(const DVolume* __restrict__ V, 
     }
 }
 
+/* The prologue every per-lane primary-ray kernel shares: header, then the camera record (two scalar-load waits, wherever the cameras
+ * live), the wave's tile and the lane's pixel, and whether any ray of the wave can reach anything. */
+struct WavePixel {
+    int b, wave, lane, px, pyl, py;
+    bool valid, reach;
+};
+__device__ __forceinline__ WavePixel wave_prologue(const Header& H, const DCam& C) {
+    WavePixel w;
+    block_and_wave(w.b, w.wave);
+    int tile_x, tile_y;
+    tile_of_block_h(H, w.b, (int)gridDim.x / kMarchGridMul, tile_x, tile_y);
+    w.lane = (int)threadIdx.x & 63;
+    pixel_of_lane(tile_x, tile_y, w.wave, w.lane, w.px, w.pyl);
+    w.py = frame_row(H, w.pyl);
+    w.valid = tile_x < H.tiles_x && tile_y < H.tiles_y && w.px < H.width && w.pyl < H.rows && w.py < H.height;
+    w.reach = wave_can_reach(C, w.valid, w.px, w.py);
+    return w;
+}
+
+/* The camera ray of the lane's pixel and its sky texel, asked for by EVERY wave ahead of the branch on `reach`: for four out of five
+ * waves of a frame the texel is all they render, and for them it is the last link of a chain of dependent loads; a marching wave carries
+ * it across the march in one register (as it always did). */
+__device__ __forceinline__ unsigned ray_and_sky(const Header& H, const DCam& C, const WavePixel& w, F3& d) {
+    d = f3(0.0f, 0.0f, 0.0f);
+    if (!w.valid) return 0u;
+    F3 o;
+    camera_ray(H, C, w.px, w.py, o, d);
+    return env_fetch(H.env, H.env_size, d);
+}
+
+/* A wave outside the cull rectangle (DCam::cull_*): its record is known as soon as the cull test is — its valid pixels as primary rays,
+ * nothing else — and is stored as soon as the header is back, while the sky texel (requested ahead of the branch, ray_and_sky) is still
+ * on its way, so that the store's acknowledgement (which the wave's end waits for) travels during the rest of the wave's life; the pixel
+ * store is the last thing the wave does.  Four out of five waves of the
+ * benchmark frame; what they cost is the wave slot they hold (profiles/r03_sky_tile_and_occupancy_experiments.txt), i.e. their lifetime.
+ * The diagnostic build's record stamps the wave's end and therefore stays last.
+ *
+ * The arm reads the header AGAIN (one more scalar round trip, under the texel's) instead of using the prologue's registers: the compiler
+ * lays the two arms of the branch on `reach` out one behind the other — the function has divergent control flow inside, so the branch is
+ * linearised although it is uniform — with the march first, and what this arm used of the prologue's header (14 scalar registers, 16 more
+ * of the camera) stayed live across the whole march: up to 90 more scalar spills per instantiation on the listing.  (The other order is no
+ * way out: behind this arm's stores the compiler no longer fetches the instance and volume records with scalar loads, and the march holds them
+ * in vector registers, 57 -> 76.) */
+template <bool DIAG>
+__device__ __forceinline__ void sky_wave(const DBlock& B, int frame, const WavePixel& w, unsigned sky, unsigned long long t_start) {
+    const Header H = load_header<true>(B);
+    if constexpr (!DIAG) {
+        const unsigned n_valid = (unsigned)__builtin_popcountll(__ballot(w.valid));
+        if (H.stats != nullptr && w.lane < 8)
+            H.stats[(size_t)(unsigned)frame * H.stats_stride + ((size_t)w.b * 4 + w.wave) * kStatRecord + w.lane] = w.lane == 0 ? n_valid : 0u;
+    }
+    if (w.valid) store_pixel(H, frame, (unsigned)w.pyl * (unsigned)H.width + (unsigned)w.px, env_decode(sky));
+    if constexpr (DIAG) {
+        Counters k;
+        k.n_primary = w.valid ? 1u : 0u;
+        write_records<DIAG, true>(H, frame, w.b, w.wave, w.lane, k, DiagAcc(), t_start);
+    }
+}
+
 /* (Round 3 experiment, removed: ONE wave rendering a whole 16x16 sky tile — four pixels per lane — while the tile's other three
  * waves end at once.  Letting three out of four sky waves end at once changes nothing (41.1 against 41.0 us per frame: the sky
  * waves only fill wave slots the marching waves leave empty), and the four-pixel sky wave made the frame 20 % slower:
@@ -1516,36 +1683,33 @@ __global__ __launch_bounds__(kMarchThreads) __attribute__((amdgpu_waves_per_eu((
     unsigned long long t_start = 0;
     if constexpr (DIAG) t_start = __builtin_amdgcn_s_memrealtime(); /* 100 MHz; diagnostic build only */
     const int frame = (int)blockIdx.y;
+    const Header H = load_header(B);
+    const DCam C0 = load_cam(B, H.cams, frame);
+    const WavePixel w = wave_prologue(H, C0);
+    F3 d;
+    const unsigned sky = ray_and_sky(H, C0, w, d);
+    if (!w.reach) { /* wave-uniform (a ballot): a scalar branch */
+        sky_wave<DIAG>(B, frame, w, sky, t_start);
+        return;
+    }
+    const DCam& C = C0;
     DFrame Fd;
     const DFrame& F = frame_view<DYN>(B, frame, Fd);
-    const DCam C = load_cam(B, frame);
-    int b, wave;
-    block_and_wave(b, wave);
-    int tile_x, tile_y;
-    tile_of_block(F, b, (int)gridDim.x / kMarchGridMul, tile_x, tile_y);
-    const int lane = (int)threadIdx.x & 63;
-    int px, pyl;
-    pixel_of_lane(tile_x, tile_y, wave, lane, px, pyl);
-    const int py = frame_row(F, pyl);
-    const bool valid = tile_x < F.tiles_x && tile_y < F.tiles_y && px < F.width && pyl < F.rows && py < F.height;
+    const int b = w.b, wave = w.wave, lane = w.lane, px = w.px, pyl = w.pyl;
+    const bool valid = w.valid;
 
     Counters k;
     DiagAcc dg;
-    const bool reach = wave_can_reach(C, valid, px, py);
 
     if (valid) {
-        F3 o, d;
-        camera_ray(F, C, px, py, o, d);
+        const F3 o = f3(C.cam_o[0], C.cam_o[1], C.cam_o[2]); /* (wave-uniform: stays in scalar registers) */
         k.n_primary = 1;
         float t_hit = 0.0f;
         int inst = 0;
         F3 n = f3(0.0f, 0.0f, 0.0f);
         F3 color;
-        /* the sky texel is asked for before the march (one register across it): four out of five waves of a frame see only
-           sky, and for them it is the last link of a chain of dependent loads (kernarg -> instance / volume -> texel -> store) */
-        const unsigned sky = env_fetch(F.env, F.env_size, d);
         /* the normal's length is the correctly rounded one: its dot product with the light decides whether a shadow ray is cast */
-        if (reach && trace_closest<PATH, SINGLE, DIAG, 2, REF>(F, o, d, 10000.0f, 0.0f, t_hit, inst, n, k.s_primary, k.n_hits, &dg)) {
+        if (trace_closest<PATH, SINGLE, DIAG, 2, REF>(F, o, d, 10000.0f, 0.0f, t_hit, inst, n, k.s_primary, k.n_hits, &dg)) {
             k.n_hits += 1; /* (its upper bits count exhausted marches) */
             bool shadowed = false;
             const F3 ld = f3(F.light_dir[0], F.light_dir[1], F.light_dir[2]);
@@ -1560,10 +1724,10 @@ __global__ __launch_bounds__(kMarchThreads) __attribute__((amdgpu_waves_per_eu((
                 }
                 if (F.shadow && !F.unlit && dot3(n, ld) > 0.0f) {
                     k.n_shadow = 1;
-                    const float vs = F.view_vec ? camera_len(F, C, px, py) : 1.0f;
+                    const float vs = F.view_vec ? camera_len(F, camera_again(B, frame), px, w.py) : 1.0f;
                     shadowed = trace_any<PATH, SINGLE, DIAG, true>(F, shadow_origin(F, o, d, t_hit, vs), ld, 5000.0f, t_hit, k.s_shadow, k.n_hits, &dg);
                 }
-                const float vs = F.view_vec ? camera_len(F, C, px, py) : 1.0f;
+                const float vs = F.view_vec ? camera_len(F, camera_again(B, frame), px, w.py) : 1.0f;
                 color = shade_hit_surface(F, V, d, vs, n, albedo, rough, metal, shadowed);
             } else {
             /* A surface facing away from the light gets a contribution <= 0 from it, blocked or not, and this kernel has no
@@ -1837,32 +2001,32 @@ template <int PATH, bool SINGLE, bool DYN = false>
 __global__ __launch_bounds__(kMarchThreads) __attribute__((amdgpu_waves_per_eu((!SINGLE && PATH != VRT_PATH_DENSE) ? VRT_PRIMARY_PASS_WAVES : 1)))
 void primary_pass_kernel(const DBlock B) {
     const int frame = (int)blockIdx.y;
+    const Header H = load_header(B);
+    const DCam C0 = load_cam(B, H.cams, frame);
+    const WavePixel w = wave_prologue(H, C0);
+    F3 d;
+    const unsigned sky = ray_and_sky(H, C0, w, d);
+    if (!w.reach) { /* as in march_kernel; the later passes skip a wave whose mask is 0 */
+        if (w.lane == 0) B.f.hit_mask[pass_wave(B.f, frame, w.b, w.wave)] = 0ull;
+        sky_wave<false>(B, frame, w, sky, 0ull);
+        return;
+    }
+    const DCam& C = C0;
     DFrame Fd;
     const DFrame& F = frame_view<DYN>(B, frame, Fd);
-    const DCam C = load_cam(B, frame);
-    int b, wave;
-    block_and_wave(b, wave);
-    int tile_x, tile_y;
-    tile_of_block(F, b, (int)gridDim.x / kMarchGridMul, tile_x, tile_y);
-    const int lane = (int)threadIdx.x & 63;
-    int px, pyl;
-    pixel_of_lane(tile_x, tile_y, wave, lane, px, pyl);
-    const int py = frame_row(F, pyl);
-    const bool valid = tile_x < F.tiles_x && tile_y < F.tiles_y && px < F.width && pyl < F.rows && py < F.height;
+    const int b = w.b, wave = w.wave, lane = w.lane, px = w.px, pyl = w.pyl;
+    const bool valid = w.valid;
 
     Counters k;
     DiagAcc dg;
-    const bool reach = wave_can_reach(C, valid, px, py);
     bool hit = false;
     if (valid) {
-        F3 o, d;
-        camera_ray(F, C, px, py, o, d);
+        const F3 o = f3(C.cam_o[0], C.cam_o[1], C.cam_o[2]);
         k.n_primary = 1;
         float t_hit = 0.0f;
         int inst = 0;
         F3 n = f3(0.0f, 0.0f, 0.0f);
-        const unsigned sky = env_fetch(F.env, F.env_size, d);
-        if (reach && trace_closest<PATH, SINGLE, false, 2, true>(F, o, d, 10000.0f, 0.0f, t_hit, inst, n, k.s_primary, k.n_hits)) {
+        if (trace_closest<PATH, SINGLE, false, 2, true>(F, o, d, 10000.0f, 0.0f, t_hit, inst, n, k.s_primary, k.n_hits)) {
             k.n_hits += 1;
             hit = true;
             const size_t r = pass_record(F, frame, b, wave, lane);
