@@ -223,7 +223,9 @@ struct DeviceState {
     void* edit_scratch = nullptr;
     size_t edit_scratch_cap = 0;
     int* d_box6 = nullptr;
-    DBrushSlot* d_brush = nullptr; /* vrt_volume_apply_brushes, vrt_volume_fill_enclosed: what the launch wrote (kBrushSlots partial records) */
+    /* the edit report of the brushes, stamp, smooth, fill, redistance and the mesh count: what the launch wrote (kBrushSlots partial
+       records, vrt_launch.h); quiesce allocates them */
+    DBrushSlot* d_brush = nullptr;
     /* vrt_volume_fill_enclosed: the rounds' flags, the passable mask and the exterior labels (grown on demand, shared by the slots) */
     void* fill_scratch = nullptr;
     size_t fill_scratch_cap = 0;
@@ -804,6 +806,70 @@ int upload_volume(vrt_ctx* ctx, int slot, uint8_t resolution, float extent, cons
     return sync_volume_table(ctx);
 }
 
+/* ---- What the volume edit calls share ----
+ * The caller's sample box: origin + size, or (both NULL, where the call allows it) the whole grid, as its first and last sample. */
+int clip_box(int N, const int* origin, const int* size, int lo[3], int hi[3]) {
+    if ((origin == nullptr) != (size == nullptr)) return VRT_ERR_INVALID;
+    for (int a = 0; a < 3; a++) {
+        lo[a] = 0, hi[a] = N - 1;
+        if (!origin) continue;
+        if (size[a] < 1 || origin[a] < 0 || (long long)origin[a] + size[a] > N) return VRT_ERR_INVALID;
+        lo[a] = origin[a], hi[a] = origin[a] + size[a] - 1;
+    }
+    return VRT_OK;
+}
+
+/* Ahead of the first write: what is already enqueued on any device comes first (frames in flight render the old volume), and every
+ * device has its report records.  An edit call's other allocations are its own; none of them follows a write either. */
+int quiesce(vrt_ctx* ctx) {
+    for (auto& D : ctx->dev) {
+        HIP_TRY(hipSetDevice(D.ordinal));
+        HIP_TRY(hipDeviceSynchronize());
+        if (!D.d_brush) HIP_TRY(hipMalloc(&D.d_brush, kBrushSlots * sizeof(DBrushSlot)));
+    }
+    return VRT_OK;
+}
+
+/* What a launch reported on D's stream (and whatever was enqueued there before: one synchronisation), the partial records merged:
+ * the box in xyz and the two halves of `counts`. */
+struct Written {
+    int lo[3], hi[3];
+    unsigned long long low, high;
+};
+int read_report(DeviceState& D, int N, Written& got) {
+    DBrushSlot part[kBrushSlots];
+    HIP_TRY(hipMemcpyAsync(part, D.d_brush, sizeof part, hipMemcpyDeviceToHost, D.stream));
+    HIP_TRY(hipStreamSynchronize(D.stream));
+    got = Written{{N, N, N}, {-1, -1, -1}, 0, 0};
+    for (const DBrushSlot& p : part) {
+        for (int a = 0; a < 3; a++) {
+            got.lo[a] = std::min(got.lo[a], N - (int)p.inv_lo[a]);
+            got.hi[a] = std::max(got.hi[a], (int)p.hi1[a] - 1);
+        }
+        got.low += p.counts & 0xffffffffull;
+        got.high += p.counts >> 32;
+    }
+    return VRT_OK;
+}
+vrt_brush_result brush_result(const Written& got) { /* brushes, stamp, smooth */
+    return vrt_brush_result{{got.lo[0], got.lo[1], got.lo[2]}, {got.hi[0], got.hi[1], got.hi[2]}, got.low};
+}
+
+/* One device's samples are written: what the slot derives from them, recomputed over the xyz box lo..hi (rebuild_derived) — unless
+ * `relevant`, the count of writes that can change a derived structure, is 0.  Then, once: the scene and the volume table follow. */
+int rebuild_written(vrt_ctx* ctx, DeviceState& D, int slot, const int lo[3], const int hi[3], unsigned long long relevant, bool& changed) {
+    if (relevant == 0) return VRT_OK;
+    changed = true;
+    HostVolume& h = ctx->vol[slot];
+    const DerivedBoxes written = derived_boxes(h, lo, hi);
+    return rebuild_derived(ctx, D, slot, &written, false, h.abox);
+}
+int finish_edit(vrt_ctx* ctx, bool changed) {
+    if (!changed) return VRT_OK;
+    ctx->scene_stale = true;
+    return sync_volume_table(ctx);
+}
+
 /* vrt_volume_update_region / _update_voxels: the box's samples in place on every device, then what the slot derives from them, where
  * the box can change it (rebuild_derived).  Afterwards every buffer equals what upload_volume builds from the edited volume. */
 int update_region(vrt_ctx* ctx, int slot, const int origin[3], const int size[3], const float* density, const uint8_t* material,
@@ -812,21 +878,20 @@ int update_region(vrt_ctx* ctx, int slot, const int origin[3], const int size[3]
     if (!valid_slot(slot) || !ctx->vol[slot].used) return VRT_ERR_SLOT;
     HostVolume& h = ctx->vol[slot];
     const int N = h.N;
-    for (int a = 0; a < 3; a++)
-        if (size[a] < 1 || origin[a] < 0 || (long long)origin[a] + size[a] > N) return VRT_ERR_INVALID;
-    const int last[3] = {origin[0] + size[0] - 1, origin[1] + size[1] - 1, origin[2] + size[2] - 1};
-    const DerivedBoxes written = derived_boxes(h, origin, last);
+    int first[3], last[3];
+    int rc = clip_box(N, origin, size, first, last);
+    if (rc != VRT_OK) return rc;
+    const EditBox box = derived_boxes(h, first, last).samples;
     const size_t count = (size_t)size[0] * size[1] * size[2];
     const size_t staged = voxels ? count * sizeof(vrt_voxel) : count * (sizeof(float) + (material ? 1 : 0));
     const bool texel16 = h.format == VRT_FORMAT_TEXEL16;
-    for (auto& D : ctx->dev) { /* frames already enqueued render the old volume */
-        HIP_TRY(hipSetDevice(D.ordinal));
-        HIP_TRY(hipDeviceSynchronize());
-    }
+    rc = quiesce(ctx);
+    if (rc != VRT_OK) return rc;
+    bool changed = false;
     for (auto& D : ctx->dev) {
         HIP_TRY(hipSetDevice(D.ordinal));
         DeviceVolume& v = D.vol[slot];
-        int rc = ensure_buffer(D.edit_staging, D.edit_staging_cap, staged);
+        rc = ensure_buffer(D.edit_staging, D.edit_staging_cap, staged);
         if (rc != VRT_OK) return rc;
         if (voxels) {
             HIP_TRY(hipMemcpyAsync(D.edit_staging, voxels, staged, hipMemcpyHostToDevice, D.stream));
@@ -835,13 +900,11 @@ int update_region(vrt_ctx* ctx, int slot, const int origin[3], const int size[3]
             if (material)
                 HIP_TRY(hipMemcpyAsync(static_cast<char*>(D.edit_staging) + count * sizeof(float), material, count, hipMemcpyHostToDevice, D.stream));
         }
-        HIP_TRY(launch_scatter_region(D.edit_staging, voxels != nullptr, material != nullptr, texel16, v.dense, v.material, N, written.samples,
-                                      D.stream));
-        rc = rebuild_derived(ctx, D, slot, &written, false, h.abox);
+        HIP_TRY(launch_scatter_region(D.edit_staging, voxels != nullptr, material != nullptr, texel16, v.dense, v.material, N, box, D.stream));
+        rc = rebuild_written(ctx, D, slot, first, last, count, changed); /* reads no report: its own box, always */
         if (rc != VRT_OK) return rc;
     }
-    ctx->scene_stale = true;
-    return sync_volume_table(ctx);
+    return finish_edit(ctx, changed);
 }
 
 /* vrt_volume_apply_brushes: the argument rules of vrt.h for one record and the samples it can write (brush_core.h, shared with the
@@ -887,40 +950,23 @@ int apply_brushes(vrt_ctx* ctx, int slot, int n_rec, const vrt_brush* rec, vrt_b
     if (list.n == 0) return VRT_OK;
     const EditBox foot = derived_boxes(h, ulo, uhi).samples;
     const bool texel16 = h.format == VRT_FORMAT_TEXEL16;
-    for (auto& D : ctx->dev) { /* frames already enqueued render the old volume */
-        HIP_TRY(hipSetDevice(D.ordinal));
-        HIP_TRY(hipDeviceSynchronize());
-    }
-    bool density_changed = false;
+    int rc = quiesce(ctx);
+    if (rc != VRT_OK) return rc;
+    bool changed = false;
     for (size_t di = 0; di < ctx->dev.size(); di++) {
         DeviceState& D = ctx->dev[di];
         HIP_TRY(hipSetDevice(D.ordinal));
         DeviceVolume& v = D.vol[slot];
-        if (!D.d_brush) HIP_TRY(hipMalloc(&D.d_brush, kBrushSlots * sizeof(DBrushSlot)));
         HIP_TRY(launch_brush_region(list, texel16, v.dense, v.material, N, foot, D.d_brush, D.stream));
-        DBrushSlot part[kBrushSlots];
-        HIP_TRY(hipMemcpyAsync(part, D.d_brush, sizeof part, hipMemcpyDeviceToHost, D.stream));
-        HIP_TRY(hipStreamSynchronize(D.stream));
-        vrt_brush_result got = {{N, N, N}, {-1, -1, -1}, 0}; /* the partial records merged */
-        unsigned long long density_written = 0;
-        for (const DBrushSlot& p : part) {
-            for (int a = 0; a < 3; a++) {
-                got.lo[a] = std::min(got.lo[a], N - (int)p.inv_lo[a]);
-                got.hi[a] = std::max(got.hi[a], (int)p.hi1[a] - 1);
-            }
-            got.written += p.counts & 0xffffffffull;
-            density_written += p.counts >> 32;
-        }
-        if (di == 0 && result) *result = got;
-        if (density_written == 0) continue; /* nothing written, or only material ids: no derived structure changes */
-        density_changed = true;
-        const DerivedBoxes written = derived_boxes(h, got.lo, got.hi);
-        int rc = rebuild_derived(ctx, D, slot, &written, false, h.abox);
+        Written got;
+        rc = read_report(D, N, got);
+        if (rc != VRT_OK) return rc;
+        if (di == 0 && result) *result = brush_result(got);
+        /* the density writes count: nothing written, or only material ids, and no derived structure changes */
+        rc = rebuild_written(ctx, D, slot, got.lo, got.hi, got.high, changed);
         if (rc != VRT_OK) return rc;
     }
-    if (!density_changed) return VRT_OK;
-    ctx->scene_stale = true;
-    return sync_volume_table(ctx);
+    return finish_edit(ctx, changed);
 }
 
 /* vrt_volume_stamp: the source slot's dense grid gathered into the destination's over the footprint of the source's box
@@ -939,12 +985,9 @@ int stamp_volume(vrt_ctx* ctx, int dst_slot, int src_slot, const vrt_stamp* rec,
     const vrt_stamp_core::Rule rule = vrt_stamp_core::rule_of(*rec, hs.N, vrt_stamp_core::unit_of(N, h.extent, h.density_scale),
                                                     vrt_stamp_core::unit_of(hs.N, hs.extent, hs.density_scale));
     const EditBox foot = derived_boxes(h, lo, hi).samples;
-    for (auto& D : ctx->dev) { /* frames already enqueued render the old volume; the only allocation comes before any write */
-        HIP_TRY(hipSetDevice(D.ordinal));
-        HIP_TRY(hipDeviceSynchronize());
-        if (!D.d_brush) HIP_TRY(hipMalloc(&D.d_brush, kBrushSlots * sizeof(DBrushSlot)));
-    }
-    bool any_written = false;
+    int rc = quiesce(ctx);
+    if (rc != VRT_OK) return rc;
+    bool changed = false;
     for (size_t di = 0; di < ctx->dev.size(); di++) {
         DeviceState& D = ctx->dev[di];
         HIP_TRY(hipSetDevice(D.ordinal));
@@ -952,27 +995,14 @@ int stamp_volume(vrt_ctx* ctx, int dst_slot, int src_slot, const vrt_stamp* rec,
         const DeviceVolume& vs = D.vol[src_slot];
         HIP_TRY(launch_stamp_region(rule, hs.format == VRT_FORMAT_TEXEL16, vs.dense, vs.material, h.format == VRT_FORMAT_TEXEL16, v.dense,
                                     v.material, N, foot, D.d_brush, D.stream));
-        DBrushSlot part[kBrushSlots];
-        HIP_TRY(hipMemcpyAsync(part, D.d_brush, sizeof part, hipMemcpyDeviceToHost, D.stream));
-        HIP_TRY(hipStreamSynchronize(D.stream));
-        vrt_brush_result got = {{N, N, N}, {-1, -1, -1}, 0}; /* the partial records merged */
-        for (const DBrushSlot& p : part) {
-            for (int a = 0; a < 3; a++) {
-                got.lo[a] = std::min(got.lo[a], N - (int)p.inv_lo[a]);
-                got.hi[a] = std::max(got.hi[a], (int)p.hi1[a] - 1);
-            }
-            got.written += p.counts & 0xffffffffull;
-        }
-        if (di == 0 && result) *result = got;
-        if (got.written == 0) continue; /* every written sample is a density write: nothing written, nothing derived changes */
-        any_written = true;
-        const DerivedBoxes written = derived_boxes(h, got.lo, got.hi);
-        int rc = rebuild_derived(ctx, D, dst_slot, &written, false, h.abox);
+        Written got;
+        rc = read_report(D, N, got);
+        if (rc != VRT_OK) return rc;
+        if (di == 0 && result) *result = brush_result(got);
+        rc = rebuild_written(ctx, D, dst_slot, got.lo, got.hi, got.low, changed); /* every written sample is a density write */
         if (rc != VRT_OK) return rc;
     }
-    if (!any_written) return VRT_OK;
-    ctx->scene_stale = true;
-    return sync_volume_table(ctx);
+    return finish_edit(ctx, changed);
 }
 
 /* vrt_volume_smooth: the work box (the region's box grown by one sample) is relaxed in scratch memory and the region samples whose
@@ -988,40 +1018,27 @@ int smooth_volume(vrt_ctx* ctx, int slot, const vrt_smooth* rec, vrt_brush_resul
     int lo[3], hi[3], work_lo[3], work_hi[3];
     if (!vrt_smooth_core::boxes(*rec, N, lo, hi, work_lo, work_hi)) return VRT_OK; /* wholly outside the grid */
     const EditBox region = derived_boxes(h, lo, hi).samples, work = derived_boxes(h, work_lo, work_hi).samples;
-    for (auto& D : ctx->dev) { /* frames already enqueued render the old volume; every allocation comes before any write */
+    int rc = quiesce(ctx);
+    if (rc != VRT_OK) return rc;
+    for (auto& D : ctx->dev) { /* every allocation comes before any write */
         HIP_TRY(hipSetDevice(D.ordinal));
-        HIP_TRY(hipDeviceSynchronize());
-        if (!D.d_brush) HIP_TRY(hipMalloc(&D.d_brush, kBrushSlots * sizeof(DBrushSlot)));
-        int rc = ensure_buffer(D.smooth_scratch, D.smooth_scratch_cap, smooth_scratch_bytes(work));
+        rc = ensure_buffer(D.smooth_scratch, D.smooth_scratch_cap, smooth_scratch_bytes(work));
         if (rc != VRT_OK) return rc;
     }
-    bool any_written = false;
+    bool changed = false;
     for (size_t di = 0; di < ctx->dev.size(); di++) {
         DeviceState& D = ctx->dev[di];
         HIP_TRY(hipSetDevice(D.ordinal));
         DeviceVolume& v = D.vol[slot];
         HIP_TRY(launch_smooth(*rec, h.format == VRT_FORMAT_TEXEL16, v.dense, v.material, N, work, region, D.smooth_scratch, D.d_brush, D.stream));
-        DBrushSlot part[kBrushSlots];
-        HIP_TRY(hipMemcpyAsync(part, D.d_brush, sizeof part, hipMemcpyDeviceToHost, D.stream));
-        HIP_TRY(hipStreamSynchronize(D.stream));
-        vrt_brush_result got = {{N, N, N}, {-1, -1, -1}, 0}; /* the partial records merged */
-        for (const DBrushSlot& p : part) {
-            for (int a = 0; a < 3; a++) {
-                got.lo[a] = std::min(got.lo[a], N - (int)p.inv_lo[a]);
-                got.hi[a] = std::max(got.hi[a], (int)p.hi1[a] - 1);
-            }
-            got.written += p.counts & 0xffffffffull;
-        }
-        if (di == 0 && result) *result = got;
-        if (got.written == 0) continue; /* every written sample is a density write: nothing written, nothing derived changes */
-        any_written = true;
-        const DerivedBoxes written = derived_boxes(h, got.lo, got.hi);
-        int rc = rebuild_derived(ctx, D, slot, &written, false, h.abox);
+        Written got;
+        rc = read_report(D, N, got);
+        if (rc != VRT_OK) return rc;
+        if (di == 0 && result) *result = brush_result(got);
+        rc = rebuild_written(ctx, D, slot, got.lo, got.hi, got.low, changed); /* every written sample is a density write */
         if (rc != VRT_OK) return rc;
     }
-    if (!any_written) return VRT_OK;
-    ctx->scene_stale = true;
-    return sync_volume_table(ctx);
+    return finish_edit(ctx, changed);
 }
 
 /* vrt_volume_fill_enclosed: per device, the passable mask and the face seeds (launch_fill_mask), propagation rounds in batches of
@@ -1038,18 +1055,15 @@ int fill_enclosed(vrt_ctx* ctx, int slot, float wall, int material, vrt_fill_res
     const bool texel16 = h.format == VRT_FORMAT_TEXEL16;
     /* a round that changes something labels at least one sample, so no run needs more rounds than the grid has samples */
     const unsigned long long round_cap = (unsigned long long)N * N * N + 1ull;
-    for (auto& D : ctx->dev) { /* frames already enqueued render the old volume */
-        HIP_TRY(hipSetDevice(D.ordinal));
-        HIP_TRY(hipDeviceSynchronize());
-    }
-    bool any_filled = false;
+    int rc = quiesce(ctx);
+    if (rc != VRT_OK) return rc;
+    bool changed = false;
     for (size_t di = 0; di < ctx->dev.size(); di++) {
         DeviceState& D = ctx->dev[di];
         HIP_TRY(hipSetDevice(D.ordinal));
         DeviceVolume& v = D.vol[slot];
-        int rc = ensure_buffer(D.fill_scratch, D.fill_scratch_cap, fill_scratch_bytes(N));
+        rc = ensure_buffer(D.fill_scratch, D.fill_scratch_cap, fill_scratch_bytes(N));
         if (rc != VRT_OK) return rc;
-        if (!D.d_brush) HIP_TRY(hipMalloc(&D.d_brush, kBrushSlots * sizeof(DBrushSlot)));
         HIP_TRY(launch_fill_mask(v.dense, texel16, N, D.fill_scratch, D.stream));
         unsigned long long rounds = 0;
         for (bool settled = false; !settled;) {
@@ -1065,27 +1079,16 @@ int fill_enclosed(vrt_ctx* ctx, int slot, float wall, int material, vrt_fill_res
             for (int f : flags) settled = settled || f == 0;
         }
         HIP_TRY(launch_fill_apply(texel16, v.dense, v.material, N, D.fill_scratch, wall, material, D.d_brush, D.stream));
-        DBrushSlot part[kBrushSlots];
-        HIP_TRY(hipMemcpyAsync(part, D.d_brush, sizeof part, hipMemcpyDeviceToHost, D.stream));
-        HIP_TRY(hipStreamSynchronize(D.stream));
-        vrt_fill_result got = {{N, N, N}, {-1, -1, -1}, 0, (uint32_t)std::min<unsigned long long>(rounds, 0xffffffffull), 0}; /* the partial records merged */
-        for (const DBrushSlot& p : part) {
-            for (int a = 0; a < 3; a++) {
-                got.lo[a] = std::min(got.lo[a], N - (int)p.inv_lo[a]);
-                got.hi[a] = std::max(got.hi[a], (int)p.hi1[a] - 1);
-            }
-            got.filled += p.counts & 0xffffffffull;
-        }
-        if (di == 0 && result) *result = got;
-        if (got.filled == 0) continue;
-        any_filled = true;
-        const DerivedBoxes written = derived_boxes(h, got.lo, got.hi);
-        rc = rebuild_derived(ctx, D, slot, &written, false, h.abox);
+        Written got;
+        rc = read_report(D, N, got);
+        if (rc != VRT_OK) return rc;
+        if (di == 0 && result)
+            *result = vrt_fill_result{{got.lo[0], got.lo[1], got.lo[2]}, {got.hi[0], got.hi[1], got.hi[2]}, got.low,
+                                      (uint32_t)std::min<unsigned long long>(rounds, 0xffffffffull), 0};
+        rc = rebuild_written(ctx, D, slot, got.lo, got.hi, got.low, changed);
         if (rc != VRT_OK) return rc;
     }
-    if (!any_filled) return VRT_OK;
-    ctx->scene_stale = true;
-    return sync_volume_table(ctx);
+    return finish_edit(ctx, changed);
 }
 
 /* vrt_volume_redistance: first, on every device, the surfels of the box grown by band + 1 are counted (launch_redistance_count) and the
@@ -1098,66 +1101,51 @@ int redistance(vrt_ctx* ctx, int slot, int band, int from, const int* origin, co
     if (!valid_slot(slot) || !ctx->vol[slot].used) return VRT_ERR_SLOT;
     if (band < 1 || band > vrt_redist::kMaxBand) return VRT_ERR_INVALID;
     if (from != VRT_REDISTANCE_FROM_BOTH && from != VRT_REDISTANCE_FROM_OUTSIDE && from != VRT_REDISTANCE_FROM_INSIDE) return VRT_ERR_INVALID;
-    if ((origin == nullptr) != (size == nullptr)) return VRT_ERR_INVALID;
     HostVolume& h = ctx->vol[slot];
     const int N = h.N;
-    int lo[3] = {0, 0, 0}, hi[3] = {N - 1, N - 1, N - 1}, glo[3], ghi[3];
-    for (int a = 0; a < 3 && origin; a++) {
-        if (size[a] < 1 || origin[a] < 0 || (long long)origin[a] + size[a] > N) return VRT_ERR_INVALID;
-        lo[a] = origin[a];
-        hi[a] = origin[a] + size[a] - 1;
-    }
+    int lo[3], hi[3], glo[3], ghi[3];
+    int rc = clip_box(N, origin, size, lo, hi);
+    if (rc != VRT_OK) return rc;
     for (int a = 0; a < 3; a++) {
         glo[a] = std::max(lo[a] - vrt_redist::cull_reach(band), 0);
         ghi[a] = std::min(hi[a] + vrt_redist::cull_reach(band), N - 1);
     }
-    const DerivedBoxes written = derived_boxes(h, lo, hi);
+    const EditBox box = derived_boxes(h, lo, hi).samples;
     const EditBox grown = derived_boxes(h, glo, ghi).samples;
     const bool texel16 = h.format == VRT_FORMAT_TEXEL16;
     const float cell = (h.extent * 2.0f) / (float)(N - 1);
     const float unit = cell / h.density_scale;
-    for (auto& D : ctx->dev) { /* frames already enqueued render the old volume */
-        HIP_TRY(hipSetDevice(D.ordinal));
-        HIP_TRY(hipDeviceSynchronize());
-    }
+    rc = quiesce(ctx);
+    if (rc != VRT_OK) return rc;
     std::vector<unsigned> surfels(ctx->dev.size(), 0u);
     for (size_t di = 0; di < ctx->dev.size(); di++) { /* everything that can run out of memory, before any sample is written */
         DeviceState& D = ctx->dev[di];
         HIP_TRY(hipSetDevice(D.ordinal));
-        int rc = ensure_buffer(D.redist_table, D.redist_table_cap, redistance_table_bytes(N));
+        rc = ensure_buffer(D.redist_table, D.redist_table_cap, redistance_table_bytes(N));
         if (rc != VRT_OK) return rc;
-        if (!D.d_brush) HIP_TRY(hipMalloc(&D.d_brush, kBrushSlots * sizeof(DBrushSlot)));
         HIP_TRY(launch_redistance_count(D.vol[slot].dense, texel16, N, from, grown, D.redist_table, D.stream));
         HIP_TRY(hipMemcpyAsync(&surfels[di], redistance_surfel_count(D.redist_table), sizeof(unsigned), hipMemcpyDeviceToHost, D.stream));
         HIP_TRY(hipStreamSynchronize(D.stream));
         rc = ensure_buffer(D.redist_surfels, D.redist_surfels_cap, redistance_surfel_bytes(surfels[di]));
         if (rc != VRT_OK) return rc;
     }
+    bool changed = false;
     for (size_t di = 0; di < ctx->dev.size(); di++) {
         DeviceState& D = ctx->dev[di];
         HIP_TRY(hipSetDevice(D.ordinal));
         DeviceVolume& v = D.vol[slot];
         if (surfels[di] > 0u)
             HIP_TRY(launch_redistance_surfels(v.dense, texel16, N, from, grown, D.redist_table, D.redist_surfels, surfels[di], D.stream));
-        HIP_TRY(launch_redistance_distance(texel16, v.dense, N, band, unit, written.samples, D.redist_table, D.redist_surfels, D.d_brush, D.stream));
-        DBrushSlot part[kBrushSlots];
-        HIP_TRY(hipMemcpyAsync(part, D.d_brush, sizeof part, hipMemcpyDeviceToHost, D.stream));
-        HIP_TRY(hipStreamSynchronize(D.stream));
-        vrt_redistance_result got = {{N, N, N}, {-1, -1, -1}, 0, 0, surfels[di], 0}; /* the partial records merged */
-        for (const DBrushSlot& p : part) {
-            for (int a = 0; a < 3; a++) {
-                got.lo[a] = std::min(got.lo[a], N - (int)p.inv_lo[a]);
-                got.hi[a] = std::max(got.hi[a], (int)p.hi1[a] - 1);
-            }
-            got.written += p.counts & 0xffffffffull;
-            got.near += p.counts >> 32;
-        }
-        if (di == 0 && result) *result = got;
-        int rc = rebuild_derived(ctx, D, slot, &written, false, h.abox);
+        HIP_TRY(launch_redistance_distance(texel16, v.dense, N, band, unit, box, D.redist_table, D.redist_surfels, D.d_brush, D.stream));
+        Written got;
+        rc = read_report(D, N, got);
+        if (rc != VRT_OK) return rc;
+        if (di == 0 && result)
+            *result = vrt_redistance_result{{got.lo[0], got.lo[1], got.lo[2]}, {got.hi[0], got.hi[1], got.hi[2]}, got.low, got.high, surfels[di], 0};
+        rc = rebuild_written(ctx, D, slot, lo, hi, 1, changed); /* the requested box, whatever was reported */
         if (rc != VRT_OK) return rc;
     }
-    ctx->scene_stale = true;
-    return sync_volume_table(ctx);
+    return finish_edit(ctx, changed);
 }
 
 /* vrt_volume_extract_mesh, on device 0: the runs of the cell box are counted and scanned (launch_mesh_count), the host reads the two
@@ -1166,44 +1154,32 @@ int redistance(vrt_ctx* ctx, int slot, int band, int from, const int* origin, co
 int extract_mesh(vrt_ctx* ctx, int slot, float iso, const int* origin, const int* size, float* positions, float* normals, uint8_t* materials,
                  size_t vertex_capacity, uint32_t* indices, size_t index_capacity, vrt_mesh_result* result) {
     if (!ctx || !std::isfinite(iso)) return VRT_ERR_INVALID;
-    if ((origin == nullptr) != (size == nullptr)) return VRT_ERR_INVALID;
+    if ((origin == nullptr) != (size == nullptr)) return VRT_ERR_INVALID; /* ahead of the slot's check, as ever; clip_box needs the slot's N */
     if (!valid_slot(slot) || !ctx->vol[slot].used) return VRT_ERR_SLOT;
     const HostVolume& h = ctx->vol[slot];
     const int N = h.N;
-    int lo[3] = {0, 0, 0}, hi[3] = {N - 1, N - 1, N - 1};
-    for (int a = 0; a < 3 && origin; a++) {
-        if (size[a] < 1 || origin[a] < 0 || (long long)origin[a] + size[a] > N) return VRT_ERR_INVALID;
-        lo[a] = origin[a];
-        hi[a] = origin[a] + size[a] - 1;
-    }
+    int lo[3], hi[3];
+    int rc = clip_box(N, origin, size, lo, hi);
+    if (rc != VRT_OK) return rc;
     const bool wanted = positions || normals || materials || indices;
     const bool texel16 = h.format == VRT_FORMAT_TEXEL16;
     const float cell = (h.extent * 2.0f) / (float)(N - 1);
-    for (auto& D : ctx->dev) { /* edits already enqueued come first */
-        HIP_TRY(hipSetDevice(D.ordinal));
-        HIP_TRY(hipDeviceSynchronize());
-    }
+    rc = quiesce(ctx);
+    if (rc != VRT_OK) return rc;
     vrt_mesh_result got = {{N, N, N}, {-1, -1, -1}, 0, 0};
     const MeshGrid grid = mesh_grid(N, lo, hi);
     DeviceState& D = ctx->dev[0];
     if (!mesh_grid_empty(grid)) {
         HIP_TRY(hipSetDevice(D.ordinal));
-        int rc = ensure_buffer(D.mesh_scratch, D.mesh_scratch_cap, mesh_scratch_bytes(grid));
+        rc = ensure_buffer(D.mesh_scratch, D.mesh_scratch_cap, mesh_scratch_bytes(grid));
         if (rc != VRT_OK) return rc;
-        if (!D.d_brush) HIP_TRY(hipMalloc(&D.d_brush, kBrushSlots * sizeof(DBrushSlot)));
         HIP_TRY(launch_mesh_count(D.vol[slot].dense, texel16, grid, iso, D.mesh_scratch, D.d_brush, D.stream));
         unsigned long long totals = 0;
-        DBrushSlot part[kBrushSlots];
+        Written cells; /* the active cells' box */
         HIP_TRY(hipMemcpyAsync(&totals, mesh_totals(D.mesh_scratch), sizeof totals, hipMemcpyDeviceToHost, D.stream));
-        HIP_TRY(hipMemcpyAsync(part, D.d_brush, sizeof part, hipMemcpyDeviceToHost, D.stream));
-        HIP_TRY(hipStreamSynchronize(D.stream));
-        got.vertices = totals & 0xffffffffull;
-        got.quads = totals >> 32;
-        for (const DBrushSlot& p : part)
-            for (int a = 0; a < 3; a++) {
-                got.lo[a] = std::min(got.lo[a], N - (int)p.inv_lo[a]);
-                got.hi[a] = std::max(got.hi[a], (int)p.hi1[a] - 1);
-            }
+        rc = read_report(D, N, cells); /* the totals arrive in the same synchronisation */
+        if (rc != VRT_OK) return rc;
+        got = vrt_mesh_result{{cells.lo[0], cells.lo[1], cells.lo[2]}, {cells.hi[0], cells.hi[1], cells.hi[2]}, totals & 0xffffffffull, totals >> 32};
     }
     if (result) *result = got;
     if (!wanted) return VRT_OK;
@@ -1212,7 +1188,7 @@ int extract_mesh(vrt_ctx* ctx, int slot, float iso, const int* origin, const int
     /* the staged mesh: positions, normals, indices, materials, each where the one before ends (all but the last a multiple of 4 bytes) */
     const size_t V = (size_t)got.vertices, Q = (size_t)got.quads;
     const size_t at_normals = V * 3 * sizeof(float), at_indices = at_normals * 2, at_materials = at_indices + Q * 6 * sizeof(uint32_t);
-    int rc = ensure_buffer(D.mesh_out, D.mesh_out_cap, at_materials + V);
+    rc = ensure_buffer(D.mesh_out, D.mesh_out_cap, at_materials + V);
     if (rc != VRT_OK) return rc;
     char* out = static_cast<char*>(D.mesh_out);
     float* d_positions = positions ? reinterpret_cast<float*>(out) : nullptr;
@@ -1234,13 +1210,14 @@ int download_region(vrt_ctx* ctx, int slot, const int origin[3], const int size[
     if (!ctx || !origin || !size || !out) return VRT_ERR_INVALID;
     if (!valid_slot(slot) || !ctx->vol[slot].used) return VRT_ERR_SLOT;
     const HostVolume& h = ctx->vol[slot];
-    for (int a = 0; a < 3; a++)
-        if (size[a] < 1 || origin[a] < 0 || (long long)origin[a] + size[a] > h.N) return VRT_ERR_INVALID;
-    const EditBox box = {{origin[0], origin[2], origin[1]}, {size[0], size[2], size[1]}};
+    int lo[3], hi[3];
+    int rc = clip_box(h.N, origin, size, lo, hi);
+    if (rc != VRT_OK) return rc;
+    const EditBox box = derived_boxes(h, lo, hi).samples;
     const size_t bytes = (size_t)size[0] * size[1] * size[2] * sizeof(vrt_voxel);
     DeviceState& D = ctx->dev[0];
     HIP_TRY(hipSetDevice(D.ordinal));
-    int rc = ensure_buffer(D.edit_staging, D.edit_staging_cap, bytes);
+    rc = ensure_buffer(D.edit_staging, D.edit_staging_cap, bytes);
     if (rc != VRT_OK) return rc;
     const DeviceVolume& v = D.vol[slot];
     HIP_TRY(launch_gather_region(v.dense, v.material, h.format == VRT_FORMAT_TEXEL16, h.N, box, D.edit_staging, D.stream));

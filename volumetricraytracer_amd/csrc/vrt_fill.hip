@@ -11,6 +11,7 @@
 #include <algorithm>
 
 #include "fill_core.h"
+#include "edit_report.h"
 #include "vrt_launch.h"
 
 namespace vrt {
@@ -98,7 +99,7 @@ __global__ __launch_bounds__(64) void fill_round_kernel(int N, const uint8_t* __
 }
 
 /* One lane per sample, y fastest like the dense grid: an enclosed sample (passable, not labelled) stores m = -(d + wall) — its texel in
- * a TEXEL16 slot — and, with material_id >= 0, that id.  Counts and box are reduced across the wave and reported like the brushes'. */
+ * a TEXEL16 slot — and, with material_id >= 0, that id.  Counts and box go into an EditReport (edit_report.h). */
 template <bool TEXEL16>
 __global__ __launch_bounds__(256) void fill_apply_kernel(float* __restrict__ dense, uint8_t* __restrict__ material, int N,
                                                          const uint8_t* __restrict__ pas, const uint8_t* __restrict__ lab, float wall,
@@ -107,8 +108,7 @@ __global__ __launch_bounds__(256) void fill_apply_kernel(float* __restrict__ den
     const size_t count = (size_t)N * N * N;
     size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
     const size_t stride = (size_t)gridDim.x * blockDim.x;
-    unsigned inv_lo_x = 0u, inv_lo_y = 0u, inv_lo_z = 0u, hi1_x = 0u, hi1_y = 0u, hi1_z = 0u; /* N - lowest, 1 + highest: 0 = none */
-    unsigned n_written = 0u;
+    EditReport report;
     for (; i < count; i += stride) {
         const size_t row = i / (size_t)N;
         const int y = (int)(i % (size_t)N);
@@ -119,22 +119,9 @@ __global__ __launch_bounds__(256) void fill_apply_kernel(float* __restrict__ den
         const float m = vrt_fill::filled_density(TEXEL16 ? stored * 0.01f : stored, wall);
         dense[i] = TEXEL16 ? vrt_fill::texel16_value(m) : m;
         if (material_id >= 0) material[i] = (uint8_t)material_id;
-        n_written++;
-        inv_lo_x = max(inv_lo_x, (unsigned)(N - x)), inv_lo_y = max(inv_lo_y, (unsigned)(N - y)), inv_lo_z = max(inv_lo_z, (unsigned)(N - z));
-        hi1_x = max(hi1_x, (unsigned)(x + 1)), hi1_y = max(hi1_y, (unsigned)(y + 1)), hi1_z = max(hi1_z, (unsigned)(z + 1));
+        report.add(N, x, y, z, true); /* every write is a density write */
     }
-    for (int o = 32; o > 0; o >>= 1) {
-        n_written += __shfl_xor(n_written, o);
-        inv_lo_x = max(inv_lo_x, __shfl_xor(inv_lo_x, o)), inv_lo_y = max(inv_lo_y, __shfl_xor(inv_lo_y, o));
-        inv_lo_z = max(inv_lo_z, __shfl_xor(inv_lo_z, o));
-        hi1_x = max(hi1_x, __shfl_xor(hi1_x, o)), hi1_y = max(hi1_y, __shfl_xor(hi1_y, o)), hi1_z = max(hi1_z, __shfl_xor(hi1_z, o));
-    }
-    if ((threadIdx.x & 63u) == 0u && n_written != 0u) {
-        DBrushSlot* slot = slots + ((blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6)) & (unsigned)(kBrushSlots - 1));
-        atomicAdd(&slot->counts, ((unsigned long long)n_written << 32) | (unsigned long long)n_written); /* every write is a density write */
-        atomicMax(&slot->inv_lo[0], inv_lo_x), atomicMax(&slot->inv_lo[1], inv_lo_y), atomicMax(&slot->inv_lo[2], inv_lo_z);
-        atomicMax(&slot->hi1[0], hi1_x), atomicMax(&slot->hi1[1], hi1_y), atomicMax(&slot->hi1[2], hi1_z);
-    }
+    report.commit(slots, blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6));
 }
 
 size_t bits_bytes(int N) { return (size_t)N * N * vrt_fill::row_bytes(N); }
@@ -167,7 +154,7 @@ hipError_t launch_fill_rounds(int N, void* scratch, int rounds, hipStream_t stre
 
 hipError_t launch_fill_apply(bool texel16, float* dense, uint8_t* material, int N, const void* scratch, float wall, int material_id,
                              DBrushSlot* slots, hipStream_t stream) {
-    hipError_t e = hipMemsetAsync(slots, 0, kBrushSlots * sizeof(DBrushSlot), stream);
+    hipError_t e = clear_report(slots, stream);
     if (e != hipSuccess) return e;
     void* s = const_cast<void*>(scratch);
     const unsigned grid = stride_grid((size_t)N * N * N);

@@ -27,6 +27,8 @@
 #include "vrt_launch.h"
 #include "voxelize_core.h"
 #include "brush_core.h"
+#include "edit_report.h"
+#include "fill_core.h"
 
 namespace vrt {
 
@@ -2449,16 +2451,8 @@ __device__ __forceinline__ void retile_cells16(const float* __restrict__ dense, 
 }
 
 /* VRT_FORMAT_TEXEL16: a density as the reference's volume texel keeps it — sign + 15-bit trunc(|d| * 100)
- * (VDXVoxelVolume::EncodeVoxel, RDXVoxelVolume.cpp:399-421) — returned as the integer +-q (oracle: texel16_value). */
-__device__ __forceinline__ float texel16_value(float d) {
-    const float a = fabsf(d) * 100.0f;
-    unsigned q = 0u;
-    if (a >= 4294967040.0f) q = 0xffffffffu;
-    else if (a >= 0.0f) q = (unsigned)a; /* NaN -> 0 */
-    q &= 0x7fffu;
-    const float v = (float)q;
-    return d < 0.0f ? -v : v;
-}
+ * (VDXVoxelVolume::EncodeVoxel, RDXVoxelVolume.cpp:399-421) — returned as the integer +-q: fill_core.h's rule, shared with the host. */
+using vrt_fill::texel16_value;
 
 __global__ void quantize_field_kernel(float* __restrict__ density, size_t count) {
     size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
@@ -2610,16 +2604,15 @@ __device__ __forceinline__ float brush_distance(const DBrush& B, float px, float
 
 /* One lane per sample of the records' union box, y fastest like the dense grid.  Every lane of a wave walks the same record list (the
  * records sit in the kernel-argument block: wave-uniform loads); a sample outside a record's own box skips its distance.  A sample
- * no record writes keeps its stored bits — a TEXEL16 value does not survive decode + encode.  The written samples' counts and box are
- * reduced across the wave first; a wave that wrote then reports with one atomic per word to one of kBrushSlots partial records. */
+ * no record writes keeps its stored bits — a TEXEL16 value does not survive decode + encode.  The written samples' counts and box
+ * go into an EditReport (edit_report.h). */
 template <bool TEXEL16>
 __global__ __launch_bounds__(256) void brush_region_kernel(DBrushList L, float* __restrict__ dense, uint8_t* __restrict__ material, int N,
                                                            EditBox b, DBrushSlot* __restrict__ slots) {
     const size_t count = box_count(b);
     size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
     const size_t stride = (size_t)gridDim.x * blockDim.x;
-    unsigned inv_lo_x = 0u, inv_lo_y = 0u, inv_lo_z = 0u, hi1_x = 0u, hi1_y = 0u, hi1_z = 0u; /* N - lowest, 1 + highest: 0 = none */
-    unsigned n_written = 0u, n_density = 0u;
+    EditReport report;
     for (; i < count; i += stride) {
         int x, z, y;
         box_coords(b, i, x, z, y);
@@ -2672,26 +2665,9 @@ __global__ __launch_bounds__(256) void brush_region_kernel(DBrushList L, float* 
         }
         if (wrote_d) dense[g] = stored;
         if (wrote_m) material[g] = (uint8_t)mat;
-        if (wrote_d || wrote_m) {
-            n_written++;
-            n_density += wrote_d ? 1u : 0u;
-            inv_lo_x = max(inv_lo_x, (unsigned)(N - x)), inv_lo_y = max(inv_lo_y, (unsigned)(N - y)), inv_lo_z = max(inv_lo_z, (unsigned)(N - z));
-            hi1_x = max(hi1_x, (unsigned)(x + 1)), hi1_y = max(hi1_y, (unsigned)(y + 1)), hi1_z = max(hi1_z, (unsigned)(z + 1));
-        }
+        if (wrote_d || wrote_m) report.add(N, x, y, z, wrote_d); /* high half: the density writes */
     }
-    for (int o = 32; o > 0; o >>= 1) {
-        n_written += __shfl_xor(n_written, o);
-        n_density += __shfl_xor(n_density, o);
-        inv_lo_x = max(inv_lo_x, __shfl_xor(inv_lo_x, o)), inv_lo_y = max(inv_lo_y, __shfl_xor(inv_lo_y, o));
-        inv_lo_z = max(inv_lo_z, __shfl_xor(inv_lo_z, o));
-        hi1_x = max(hi1_x, __shfl_xor(hi1_x, o)), hi1_y = max(hi1_y, __shfl_xor(hi1_y, o)), hi1_z = max(hi1_z, __shfl_xor(hi1_z, o));
-    }
-    if ((threadIdx.x & 63u) == 0u && n_written != 0u) {
-        DBrushSlot* slot = slots + ((blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6)) & (unsigned)(kBrushSlots - 1));
-        atomicAdd(&slot->counts, ((unsigned long long)n_density << 32) | (unsigned long long)n_written);
-        atomicMax(&slot->inv_lo[0], inv_lo_x), atomicMax(&slot->inv_lo[1], inv_lo_y), atomicMax(&slot->inv_lo[2], inv_lo_z);
-        atomicMax(&slot->hi1[0], hi1_x), atomicMax(&slot->hi1[1], hi1_y), atomicMax(&slot->hi1[2], hi1_z);
-    }
+    report.commit(slots, blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6));
 }
 
 /* vrt_volume_download_region: the box's samples as VVoxel records, decoded like vrt_volume_download. */
@@ -3141,8 +3117,7 @@ hipError_t launch_scatter_region(const void* staging, bool voxels, bool has_mate
 
 hipError_t launch_brush_region(const DBrushList& list, bool texel16, float* dense, uint8_t* material, int N, const EditBox& box,
                                DBrushSlot* slots, hipStream_t stream) {
-    static_assert(sizeof(DBrushSlot) == 128 && (kBrushSlots & (kBrushSlots - 1)) == 0, "one line per slot, a power of two of them");
-    hipError_t e = hipMemsetAsync(slots, 0, kBrushSlots * sizeof(DBrushSlot), stream);
+    hipError_t e = clear_report(slots, stream);
     if (e != hipSuccess) return e;
     const size_t count = (size_t)box.n[0] * box.n[1] * box.n[2];
     if (list.n == 0 || count == 0) return hipSuccess;

@@ -84,18 +84,21 @@ struct DBrushList {
     float unit; /* density units per cell: cell / density_scale */
     DBrush rec[VRT_MAX_BRUSHES];
 };
-/* What a brush launch reports (device memory, zeroed by launch_brush_region): the written samples' box and counts, kept in
-   kBrushSlots partial records that the host merges — thousands of waves report at once, and atomics on one word take their turns
-   (a single record made the launch 25 times longer than the scatter of the same box).  Every field grows from 0 = nothing written. */
+/* The edit report: what a launch of an edit call (brushes, fill, redistance, stamp, smooth) or of the mesh count reports (device memory,
+   zeroed by the launch; the kernels' side is edit_report.h): the written samples' box and counts, kept in kBrushSlots partial records
+   that the host merges — thousands of waves report at once, and atomics on one word take their turns (a single record made the brush
+   launch 25 times longer than the scatter of the same box).  Every field grows from 0 = nothing written. */
 constexpr int kBrushSlots = 64;
 struct DBrushSlot {
     uint32_t inv_lo[3];        /* N - lowest written x, y, z */
     uint32_t hi1[3];           /* 1 + highest written x, y, z */
-    unsigned long long counts; /* samples written (low half; N^3 < 2^32) and, of those, samples whose density was written (high half;
-                                  0: only material ids changed, no derived structure to rebuild) */
+    unsigned long long counts; /* samples written (low half; N^3 < 2^32) and, of those, the ones the op singles out (high half) — brushes:
+                                  samples whose density was written (0: only material ids changed, no derived structure to rebuild);
+                                  redistance: samples nearer than the band; fill, stamp, smooth: all of them */
     uint32_t pad_[24];         /* one 128-byte line per slot */
 };
-/* The records of `list`, in order, over the samples of `box` (the union of the records' boxes), in place. */
+/* The records of `list`, in order, over the samples of `box` (the union of the records' boxes), in place; slots: zeroed, then the
+   written samples' counts and box (the edit report, above). */
 hipError_t launch_brush_region(const DBrushList& list, bool texel16, float* dense, uint8_t* material, int N, const EditBox& box,
                                DBrushSlot* slots, hipStream_t stream);
 /* vrt_volume_download_region: the samples of `box` as VVoxel records (x slowest, then z, then y), a TEXEL16 field decoded (* 0.01f). */
@@ -114,7 +117,7 @@ hipError_t launch_fill_mask(const float* dense, bool texel16, int N, void* scrat
 hipError_t launch_fill_rounds(int N, void* scratch, int rounds, hipStream_t stream);
 const int* fill_round_flags(const void* scratch);
 /* Every passable sample without a label stores -(d + wall) (its texel when texel16) and, material_id >= 0, that id; slots: zeroed, then
-   the written samples' counts and box as launch_brush_region reports them. */
+   the written samples' counts and box (the edit report, above). */
 hipError_t launch_fill_apply(bool texel16, float* dense, uint8_t* material, int N, const void* scratch, float wall, int material_id,
                              DBrushSlot* slots, hipStream_t stream);
 
@@ -130,13 +133,13 @@ hipError_t launch_redistance_count(const float* dense, bool texel16, int N, int 
 hipError_t launch_redistance_surfels(const float* dense, bool texel16, int N, int from, const EditBox& grown, void* table, void* surfels,
                                      unsigned capacity, hipStream_t stream);
 /* Every sample of `box` stores its banded signed distance (its texel when texel16), in place; slots: zeroed, then the written samples'
-   box and count as launch_brush_region reports them, with the count of samples nearer than the band in the high half of `counts`. */
+   box and count (the edit report, above), with the count of samples nearer than the band in the high half of `counts`. */
 hipError_t launch_redistance_distance(bool texel16, float* dense, int N, int band, float unit, const EditBox& box, const void* table,
                                       const void* surfels, DBrushSlot* slots, hipStream_t stream);
 
 /* vrt_volume_stamp (vrt_stamp.hip): the rule of stamp_core.h over the destination samples of `box` (the footprint: outside it the
    source's box cannot be hit), in place; the source's dense and material grids are only read and must not be the destination's.
-   slots: zeroed, then the written samples' counts and box as launch_brush_region reports them. */
+   slots: zeroed, then the written samples' counts and box (the edit report, above). */
 hipError_t launch_stamp_region(const vrt_stamp_core::Rule& rule, bool src_texel16, const float* src_dense, const uint8_t* src_material,
                                bool dst_texel16, float* dense, uint8_t* material, int N, const EditBox& box, DBrushSlot* slots,
                                hipStream_t stream);
@@ -144,8 +147,7 @@ hipError_t launch_stamp_region(const vrt_stamp_core::Rule& rule, bool src_texel1
 /* vrt_volume_smooth (vrt_smooth.hip): the rule of smooth_core.h.  work: the region's box grown by one sample and clipped to the grid;
    region: the box outside which no sample is in the region.  scratch: smooth_scratch_bytes(work) of device memory — two fp32 copies
    of the work box and its weights.  Gathers the work box, runs the record's passes from one copy to the other (one launch each), then
-   stores the region samples whose bits changed; slots: zeroed, then the written samples' counts and box as launch_brush_region
-   reports them. */
+   stores the region samples whose bits changed; slots: zeroed, then the written samples' counts and box (the edit report, above). */
 size_t smooth_scratch_bytes(const EditBox& work);
 hipError_t launch_smooth(const vrt_smooth& rule, bool texel16, float* dense, uint8_t* material, int N, const EditBox& work,
                          const EditBox& region, void* scratch, DBrushSlot* slots, hipStream_t stream);
@@ -166,7 +168,8 @@ size_t mesh_scratch_bytes(const MeshGrid& grid);
 /* device memory: vertices (low half) and quads (high half) of the whole mesh after launch_mesh_count */
 const unsigned long long* mesh_totals(const void* scratch);
 /* Counts every run's vertices and quads and turns the counts into the runs' first vertex and first quad (a prefix sum in run order);
-   slots: zeroed, then the active cells' box in inv_lo / hi1 as launch_brush_region reports a written box.  Not for an empty grid. */
+   slots: zeroed, then the active cells' box in inv_lo / hi1 (the edit report, above; `counts` stays 0).  Not for an
+   empty grid. */
 hipError_t launch_mesh_count(const float* dense, bool texel16, const MeshGrid& grid, float iso, void* scratch, DBrushSlot* slots,
                              hipStream_t stream);
 /* Writes the vertices (3 floats of object space, 3 floats of normal, 1 material byte each) and the quads (6 indices each) at their

@@ -14,6 +14,7 @@
 #include <hip/hip_runtime.h>
 
 #include "mesh_core.h"
+#include "edit_report.h"
 #include "vrt_launch.h"
 
 namespace vrt {
@@ -77,11 +78,11 @@ __global__ __launch_bounds__(256) void mesh_count_kernel(const float* __restrict
     rec.mask = mask, rec.v = (unsigned)__popcll(mask), rec.q = n_quads;
     runs[r] = rec;
     if (mask != 0ull) { /* lane 0's cell is the run's first: x and z are the run's, y runs from the lowest to the highest set bit */
-        DBrushSlot* slot = slots + (r & (unsigned)(kBrushSlots - 1));
         const int y_lo = c[1] + (int)__ffsll((long long)mask) - 1, y_hi = c[1] + 63 - (int)__clzll((long long)mask);
-        atomicMax(&slot->inv_lo[0], (unsigned)(G.N - c[0])), atomicMax(&slot->inv_lo[1], (unsigned)(G.N - y_lo));
-        atomicMax(&slot->inv_lo[2], (unsigned)(G.N - c[2]));
-        atomicMax(&slot->hi1[0], (unsigned)(c[0] + 1)), atomicMax(&slot->hi1[1], (unsigned)(y_hi + 1)), atomicMax(&slot->hi1[2], (unsigned)(c[2] + 1));
+        EditReport report; /* the ballot has folded the wave already: the run's two end cells say its box */
+        report.bound(G.N, c[0], y_lo, c[2]);
+        report.bound(G.N, c[0], y_hi, c[2]);
+        report.write(slots, r);
     }
 }
 
@@ -255,7 +256,7 @@ const unsigned long long* mesh_totals(const void* scratch) { return static_cast<
 
 hipError_t launch_mesh_count(const float* dense, bool texel16, const MeshGrid& G, float iso, void* scratch, DBrushSlot* slots, hipStream_t stream) {
     if (mesh_grid_empty(G)) return hipErrorInvalidValue;
-    hipError_t e = hipMemsetAsync(slots, 0, kBrushSlots * sizeof(DBrushSlot), stream);
+    hipError_t e = clear_report(slots, stream);
     if (e != hipSuccess) return e;
     const unsigned n_runs = runs_of(G), n_blocks = scan_blocks_of(n_runs);
     Run* runs = records_of(scratch, n_runs);

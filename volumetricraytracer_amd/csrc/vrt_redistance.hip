@@ -12,6 +12,7 @@
 #include <algorithm>
 
 #include "redistance_core.h"
+#include "edit_report.h"
 #include "vrt_launch.h"
 
 namespace vrt {
@@ -165,32 +166,17 @@ __global__ __launch_bounds__(256) void redist_distance_kernel(float* __restrict_
         __syncthreads();
     }
 
-    unsigned n_written = 0u, n_near = 0u;
-    unsigned inv_lo_x = 0u, inv_lo_y = 0u, inv_lo_z = 0u, hi1_x = 0u, hi1_y = 0u, hi1_z = 0u; /* N - lowest, 1 + highest: 0 = none */
+    EditReport report;
     const auto store = [&](size_t i, int x, float best, bool is_out) {
         const float D = vrt_redist::banded(best, band);
         const float m = vrt_redist::signed_value(D, unit, is_out);
         dense[i] = TEXEL16 ? vrt_fill::texel16_value(m) : m;
-        n_written++;
-        n_near += D < (float)band ? 1u : 0u;
-        inv_lo_x = max(inv_lo_x, (unsigned)(N - x)), inv_lo_y = max(inv_lo_y, (unsigned)(N - y)), inv_lo_z = max(inv_lo_z, (unsigned)(N - z));
-        hi1_x = max(hi1_x, (unsigned)(x + 1)), hi1_y = max(hi1_y, (unsigned)(y + 1)), hi1_z = max(hi1_z, (unsigned)(z + 1));
+        report.add(N, x, y, z, D < (float)band); /* high half: the near samples */
     };
     if (in0) store(i0, x0, best0, out0);
     if (in1) store(i1, x1, best1, out1);
-    for (int o = 32; o > 0; o >>= 1) {
-        n_written += __shfl_xor(n_written, o), n_near += __shfl_xor(n_near, o);
-        inv_lo_x = max(inv_lo_x, __shfl_xor(inv_lo_x, o)), inv_lo_y = max(inv_lo_y, __shfl_xor(inv_lo_y, o));
-        inv_lo_z = max(inv_lo_z, __shfl_xor(inv_lo_z, o));
-        hi1_x = max(hi1_x, __shfl_xor(hi1_x, o)), hi1_y = max(hi1_y, __shfl_xor(hi1_y, o)), hi1_z = max(hi1_z, __shfl_xor(hi1_z, o));
-    }
-    if ((tid & 63) == 0 && n_written != 0u) {
-        const unsigned block = (blockIdx.z * gridDim.y + blockIdx.y) * gridDim.x + blockIdx.x;
-        DBrushSlot* slot = slots + ((block * 4u + (unsigned)(tid >> 6)) & (unsigned)(kBrushSlots - 1));
-        atomicAdd(&slot->counts, ((unsigned long long)n_near << 32) | (unsigned long long)n_written); /* high half: the near samples */
-        atomicMax(&slot->inv_lo[0], inv_lo_x), atomicMax(&slot->inv_lo[1], inv_lo_y), atomicMax(&slot->inv_lo[2], inv_lo_z);
-        atomicMax(&slot->hi1[0], hi1_x), atomicMax(&slot->hi1[1], hi1_y), atomicMax(&slot->hi1[2], hi1_z);
-    }
+    const unsigned block = (blockIdx.z * gridDim.y + blockIdx.y) * gridDim.x + blockIdx.x;
+    report.commit(slots, block * 4u + (unsigned)(tid >> 6));
 }
 
 int tiles_of(int N) { return (N + kTile - 1) / kTile; }
@@ -242,7 +228,7 @@ hipError_t launch_redistance_surfels(const float* dense, bool texel16, int N, in
 hipError_t launch_redistance_distance(bool texel16, float* dense, int N, int band, float unit, const EditBox& box, const void* table,
                                       const void* surfels, DBrushSlot* slots, hipStream_t stream) {
     if (band < 1 || band > vrt_redist::kMaxBand) return hipErrorInvalidValue;
-    hipError_t e = hipMemsetAsync(slots, 0, kBrushSlots * sizeof(DBrushSlot), stream);
+    hipError_t e = clear_report(slots, stream);
     if (e != hipSuccess) return e;
     int first[3];
     dim3 grid;

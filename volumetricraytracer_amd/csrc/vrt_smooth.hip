@@ -13,6 +13,7 @@
 #include <hip/hip_runtime.h>
 
 #include "smooth_core.h"
+#include "edit_report.h"
 #include "vrt_launch.h"
 
 namespace vrt {
@@ -78,15 +79,13 @@ __global__ __launch_bounds__(256) void smooth_pass_kernel(vrt_smooth R, int pass
 }
 
 /* One lane per sample of the work box: a region sample whose value to store differs in bits from the stored one is written, with its
- * id.  The written samples' count and box are reduced across the wave first; a wave that wrote then reports with one atomic per word
- * to one of kBrushSlots partial records, as the brushes do. */
+ * id.  The written samples' count and box go into an EditReport (edit_report.h). */
 template <bool TEXEL16>
 __global__ __launch_bounds__(256) void smooth_apply_kernel(int material_id, const float* __restrict__ field, const float* __restrict__ weights,
                                                            float* __restrict__ dense, uint8_t* __restrict__ material, int N, EditBox work,
                                                            DBrushSlot* __restrict__ slots) {
     const unsigned i = blockIdx.x * blockDim.x + threadIdx.x;
-    unsigned inv_lo_x = 0u, inv_lo_y = 0u, inv_lo_z = 0u, hi1_x = 0u, hi1_y = 0u, hi1_z = 0u; /* N - lowest, 1 + highest: 0 = none */
-    unsigned n_written = 0u;
+    EditReport report;
     if (i < box_samples(work) && S::in_region(weights[i])) {
         const unsigned ny = (unsigned)work.n[2], nz = (unsigned)work.n[1];
         const unsigned row = i / ny, sx = row / nz;
@@ -97,23 +96,10 @@ __global__ __launch_bounds__(256) void smooth_apply_kernel(int material_id, cons
         if (S::stores(m, dense[g], TEXEL16, value)) {
             dense[g] = value;
             if (material_id >= 0) material[g] = (uint8_t)S::written_material(material_id, m);
-            n_written = 1u;
-            inv_lo_x = (unsigned)(N - x), inv_lo_y = (unsigned)(N - y), inv_lo_z = (unsigned)(N - z);
-            hi1_x = (unsigned)(x + 1), hi1_y = (unsigned)(y + 1), hi1_z = (unsigned)(z + 1);
+            report.add(N, x, y, z, true); /* every write is a density write */
         }
     }
-    for (int o = 32; o > 0; o >>= 1) {
-        n_written += __shfl_xor(n_written, o);
-        inv_lo_x = max(inv_lo_x, __shfl_xor(inv_lo_x, o)), inv_lo_y = max(inv_lo_y, __shfl_xor(inv_lo_y, o));
-        inv_lo_z = max(inv_lo_z, __shfl_xor(inv_lo_z, o));
-        hi1_x = max(hi1_x, __shfl_xor(hi1_x, o)), hi1_y = max(hi1_y, __shfl_xor(hi1_y, o)), hi1_z = max(hi1_z, __shfl_xor(hi1_z, o));
-    }
-    if ((threadIdx.x & 63u) == 0u && n_written != 0u) {
-        DBrushSlot* slot = slots + ((blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6)) & (unsigned)(kBrushSlots - 1));
-        atomicAdd(&slot->counts, ((unsigned long long)n_written << 32) | (unsigned long long)n_written); /* every write is a density write */
-        atomicMax(&slot->inv_lo[0], inv_lo_x), atomicMax(&slot->inv_lo[1], inv_lo_y), atomicMax(&slot->inv_lo[2], inv_lo_z);
-        atomicMax(&slot->hi1[0], hi1_x), atomicMax(&slot->hi1[1], hi1_y), atomicMax(&slot->hi1[2], hi1_z);
-    }
+    report.commit(slots, blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6));
 }
 
 size_t box_count(const EditBox& b) { return (size_t)b.n[0] * b.n[1] * b.n[2]; }
@@ -124,7 +110,7 @@ size_t smooth_scratch_bytes(const EditBox& work) { return 3 * box_count(work) * 
 
 hipError_t launch_smooth(const vrt_smooth& rule, bool texel16, float* dense, uint8_t* material, int N, const EditBox& work,
                          const EditBox& region, void* scratch, DBrushSlot* slots, hipStream_t stream) {
-    hipError_t e = hipMemsetAsync(slots, 0, kBrushSlots * sizeof(DBrushSlot), stream);
+    hipError_t e = clear_report(slots, stream);
     if (e != hipSuccess) return e;
     const size_t count = box_count(work);
     float* copy[2] = {static_cast<float*>(scratch), static_cast<float*>(scratch) + count};

@@ -10,6 +10,7 @@
 #include <algorithm>
 
 #include "stamp_core.h"
+#include "edit_report.h"
 #include "vrt_launch.h"
 
 namespace vrt {
@@ -19,8 +20,7 @@ namespace {
 /* One lane per sample of the footprint box, y fastest: blockIdx.y walks the box's x slabs, blockIdx.x and the lanes a slab's z rows of
  * y, so the index arithmetic stays in 32 bits (a slab holds fewer than 2^32 samples).  A lane outside the source goes on before it
  * touches the destination, and so does a wave of them.  A sample that is not written keeps its stored bits.  The written samples'
- * count and box are reduced across the wave first; a wave that wrote then reports with one atomic per word to one of kBrushSlots
- * partial records, as the brushes do. */
+ * count and box go into an EditReport (edit_report.h). */
 template <bool SRC16, bool DST16>
 __global__ __launch_bounds__(256) void stamp_region_kernel(vrt_stamp_core::Rule R, const float* __restrict__ src, const uint8_t* __restrict__ src_material,
                                                            float* __restrict__ dense, uint8_t* __restrict__ material, int N, EditBox b,
@@ -29,8 +29,7 @@ __global__ __launch_bounds__(256) void stamp_region_kernel(vrt_stamp_core::Rule 
     const unsigned ny = (unsigned)b.n[2], slab = (unsigned)b.n[1] * ny;
     const unsigned stride = gridDim.x * blockDim.x;
     const int ns = R.ns;
-    unsigned inv_lo_x = 0u, inv_lo_y = 0u, inv_lo_z = 0u, hi1_x = 0u, hi1_y = 0u, hi1_z = 0u; /* N - lowest, 1 + highest: 0 = none */
-    unsigned n_written = 0u;
+    EditReport report;
     for (unsigned sx = blockIdx.y; sx < (unsigned)b.n[0]; sx += gridDim.y)
         for (unsigned i = blockIdx.x * blockDim.x + threadIdx.x; i < slab; i += stride) {
             const unsigned row = i / ny;
@@ -64,22 +63,9 @@ __global__ __launch_bounds__(256) void stamp_region_kernel(vrt_stamp_core::Rule 
                     id = src_material[((size_t)S::nearest(cx, fx) * ns + (size_t)S::nearest(cz, fz)) * ns + (size_t)S::nearest(cy, fy)];
                 material[g] = (uint8_t)S::written_material(R.op, R.material, m, id);
             }
-            n_written++;
-            inv_lo_x = max(inv_lo_x, (unsigned)(N - x)), inv_lo_y = max(inv_lo_y, (unsigned)(N - y)), inv_lo_z = max(inv_lo_z, (unsigned)(N - z));
-            hi1_x = max(hi1_x, (unsigned)(x + 1)), hi1_y = max(hi1_y, (unsigned)(y + 1)), hi1_z = max(hi1_z, (unsigned)(z + 1));
+            report.add(N, x, y, z, true); /* every write is a density write */
         }
-    for (int o = 32; o > 0; o >>= 1) {
-        n_written += __shfl_xor(n_written, o);
-        inv_lo_x = max(inv_lo_x, __shfl_xor(inv_lo_x, o)), inv_lo_y = max(inv_lo_y, __shfl_xor(inv_lo_y, o));
-        inv_lo_z = max(inv_lo_z, __shfl_xor(inv_lo_z, o));
-        hi1_x = max(hi1_x, __shfl_xor(hi1_x, o)), hi1_y = max(hi1_y, __shfl_xor(hi1_y, o)), hi1_z = max(hi1_z, __shfl_xor(hi1_z, o));
-    }
-    if ((threadIdx.x & 63u) == 0u && n_written != 0u) {
-        DBrushSlot* slot = slots + (((blockIdx.y * gridDim.x + blockIdx.x) * (blockDim.x >> 6) + (threadIdx.x >> 6)) & (unsigned)(kBrushSlots - 1));
-        atomicAdd(&slot->counts, ((unsigned long long)n_written << 32) | (unsigned long long)n_written); /* every write is a density write */
-        atomicMax(&slot->inv_lo[0], inv_lo_x), atomicMax(&slot->inv_lo[1], inv_lo_y), atomicMax(&slot->inv_lo[2], inv_lo_z);
-        atomicMax(&slot->hi1[0], hi1_x), atomicMax(&slot->hi1[1], hi1_y), atomicMax(&slot->hi1[2], hi1_z);
-    }
+    report.commit(slots, (blockIdx.y * gridDim.x + blockIdx.x) * (blockDim.x >> 6) + (threadIdx.x >> 6));
 }
 
 }  // namespace
@@ -87,7 +73,7 @@ __global__ __launch_bounds__(256) void stamp_region_kernel(vrt_stamp_core::Rule 
 hipError_t launch_stamp_region(const vrt_stamp_core::Rule& rule, bool src_texel16, const float* src_dense, const uint8_t* src_material,
                                bool dst_texel16, float* dense, uint8_t* material, int N, const EditBox& box, DBrushSlot* slots,
                                hipStream_t stream) {
-    hipError_t e = hipMemsetAsync(slots, 0, kBrushSlots * sizeof(DBrushSlot), stream);
+    hipError_t e = clear_report(slots, stream);
     if (e != hipSuccess) return e;
     const size_t slab = (size_t)box.n[1] * box.n[2];
     const dim3 g((unsigned)std::max<size_t>(1, std::min<size_t>((slab + 255) / 256, 1u << 12)), (unsigned)std::max(1, std::min(box.n[0], 1 << 12))), t(256);
