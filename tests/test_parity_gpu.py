@@ -298,6 +298,17 @@ def test_device_voxelizer_matches_the_cpu_converter(mesh, resolution):
         assert np.array_equal(gpu.density, cpu.density)
         assert np.array_equal(gpu.material_id, cpu.material_id)
         assert (gpu.density <= 0).sum() > 100 and gpu.density.max() == np.float32(cpu.VolumeExtends * 2)
+        if mesh == "cube":
+            # the whole grid, far voxels and background included, against the float64 reference (tests/voxelize_ref.py)
+            import voxelize_ref as V
+
+            tri, none_skipped = V.usable(p, idx)
+            ref = V.reference(tri, resolution, cpu.VolumeExtends)
+            assert none_skipped == 0 and ref.ambiguous == 0 and V.well_conditioned(tri, cpu.GetCellSize()).all()
+            assert (np.abs(gpu.density - ref.density) <= V.tol(gpu.N, ref.density)).all(), V.scaled_error(gpu.N, gpu.density, ref.density)
+            assert (~ref.covered).sum() > 1000 and (gpu.density[~ref.covered] == np.float32(cpu.VolumeExtends * 2)).all()
+            sure = np.abs(ref.density) > V.tol(gpu.N, ref.density)
+            assert (~sure).sum() <= V.LEFT_OUT_SHARE * sure.size and np.array_equal(gpu.material_id[sure], ref.material[sure])
         # the slot renders like an uploaded copy of the CPU volume (metric set by the voxelizer itself)
         if resolution <= 6:
             cpu.Material = v.VMaterial((0.8, 0.6, 0.2, 1.0), 0.8, 0.0)
