@@ -26,6 +26,8 @@
  *                                   relaxing brush — a weighted 7-point stencil inside a sphere / box / capsule region)
  *   vrt_volume_fill_enclosed        (no reference analogue: its Voxelizer stops at the unsigned shell, Voxelizer/Private/VolumeConverter.cpp:30-84 —
  *                                   the shell of a closed mesh made solid on the resident volume, so that a SUBTRACT brush carves a solid)
+ *   vrt_volume_components           (no reference analogue beyond VVoxelVolume::SetVoxel, VoxelVolume.cpp:59-77, in a host loop: the
+ *                                   6-connected pieces of the resident volume labelled, listed, and the unwanted ones removed)
  *   vrt_volume_redistance           (no reference analogue: whatever field the resident volume holds rewritten, within a band, as the
  *                                   signed distance to its own zero surface — what ADD brushes, blends and offsets assume)
  *   vrt_volume_extract_mesh         (no reference analogue: its Voxelizer goes one way, glTF -> .vox; the resident volume's surface
@@ -551,6 +553,89 @@ typedef struct vrt_fill_result {      /* 40 B */
  * where a brush surface meets the former inner crossing the carved surface can sit a fraction of a cell off.
  * vrt_volume_redistance(band, VRT_REDISTANCE_FROM_OUTSIDE) afterwards turns wall and interior into a signed distance. */
 int vrt_volume_fill_enclosed(vrt_ctx* ctx, int slot, float wall, int material, vrt_fill_result* result_or_null);
+
+/* Islands (no reference analogue beyond VVoxelVolume::SetVoxel in a host loop).  A hard VRT_BRUSH_SUBTRACT dab or a SUBTRACT stamp
+ * that cuts through a strut leaves its far end floating, vrt_voxelize_mesh on a noisy or multi-part mesh leaves crumbs, a
+ * VRT_FORMAT_TEXEL16 slot leaves one-texel specks: all of it renders, and all of it reaches vrt_volume_extract_mesh's consumers.  This
+ * call labels the connected pieces of the resident volume's solid samples on the device, lists them, and removes the ones the record
+ * names, in place. */
+enum { VRT_COMPONENTS_REPORT = 0, VRT_COMPONENTS_KEEP_LARGEST = 1, VRT_COMPONENTS_REMOVE_SMALL = 2,
+       VRT_COMPONENTS_KEEP_SEED = 3, VRT_COMPONENTS_REMOVE_SEED = 4 };
+
+typedef struct vrt_components {       /* 64 B */
+    int32_t op;
+    int32_t material;                 /* -1 = leave ids alone, else 0..255: the id every sample of a removed component gets */
+    int32_t seed[3];                  /* xyz, e.g. vrt_hit::voxel; KEEP_SEED / REMOVE_SEED only, otherwise 0 */
+    float gap;                        /* > 0, density units (see the rule); REPORT: ignored, finite */
+    uint64_t min_samples;             /* REMOVE_SMALL: components with fewer samples go; otherwise 0 */
+    uint32_t reserved_[8];            /* 0 */
+} vrt_components;
+
+typedef struct vrt_component {        /* 48 B */
+    int32_t first[3];                 /* xyz of the component's lowest-key sample: its identity, and a valid seed */
+    int32_t lo[3], hi[3];             /* xyz, inclusive */
+    uint32_t removed;                 /* 1: this call removed it */
+    uint64_t samples;
+} vrt_component;
+
+typedef struct vrt_components_result { /* 64 B */
+    int32_t lo[3], hi[3];             /* as vrt_brush_result: box of the samples written; lo > hi when none */
+    uint64_t written;                 /* samples written (removed samples + halo samples) */
+    uint64_t solid;                   /* solid samples of the grid before the call */
+    uint64_t removed_samples;         /* solid samples that were removed */
+    uint32_t components, removed;     /* components before the call; how many of them were removed */
+    uint32_t listed;                  /* records written to the list */
+    uint32_t reserved_;
+} vrt_components_result;
+
+/* Labels the resident slot's components on every device and removes the ones the record names, in place.  Waits for work already
+ * enqueued on the context's devices (a frame begun before the call renders the old volume, one begun after renders the new one);
+ * device pointers of the slot do not change.  Afterwards every device buffer of the slot equals what a full upload of the edited
+ * volume holds (what the slot derives from its samples is rebuilt over the written box; nothing is rebuilt when nothing was written),
+ * so frames and counters are those of the full upload.  A launch captured into a graph before the call keeps the cull rectangle it
+ * was captured with, as for the other edits.
+ * Errors, all checked before any device state is touched: VRT_ERR_INVALID for a NULL context or record; an unknown op; a material
+ * outside -1..255; a gap that is not finite; for the ops that remove, gap <= 0 and, on a VRT_FORMAT_TEXEL16 slot, a gap whose texel is
+ * 0; min_samples != 0 outside REMOVE_SMALL; for the seed ops a seed outside [0, N), for the others a non-zero seed; non-zero reserved
+ * words; list_capacity < 0; a NULL list with list_capacity > 0.  VRT_ERR_SLOT for an unused slot.  VRT_ERR_OOM when the scratch
+ * memory cannot be allocated: 8 bytes per sample of the grid, at most 48 bytes per component and a constant 256 bytes, all of it
+ * allocated on every device before any sample is written, so the volume is untouched then.  VRT_ERR_HIP, also before any write, should
+ * the labelling run into one of its iteration caps (a defect, not an input).  A grid without a solid sample is VRT_OK with zeros and
+ * lo > hi.  One error is found after the device has been read, and never after a write: a seed op whose seed has no solid sample in
+ * its neighbourhood (rule 4) returns VRT_ERR_INVALID and writes nothing.
+ * result_or_null and the list come from device 0 (all devices compute the same bytes).
+ *
+ * The rule is part of the contract.
+ *   1. Class.  d is the sample's density as for the brushes: the stored float, or stored * 0.01f (VRT_FORMAT_TEXEL16).  A sample is
+ *      SOLID iff !(d > 0): NaN, +-0 and negatives are solid — exactly vrt_volume_fill_enclosed's walls and vrt_volume_extract_mesh's
+ *      INSIDE at iso 0.  Every other sample is passable.
+ *   2. Components.  A component is a maximal set of solid samples joined by steps to a 6-neighbour (one index +-1); diagonal contact
+ *      does not connect, as in the fill.  key(x, y, z) = (x*N + z)*N + y, the storage index; a component's identity is the lowest
+ *      key among its samples.  Partition and identities are unique: the result does not depend on how the device schedules its work.
+ *      (6-connectivity only; the reserved words leave room for more.)
+ *   3. The list.  Components are ordered by `samples` descending, ties by identity ascending; the first min(components,
+ *      list_capacity) records are written.  list_or_null == NULL requires list_capacity == 0.
+ *   4. Which components are removed.  REPORT: none.  KEEP_LARGEST: all but the first of the list order.  REMOVE_SMALL: those with
+ *      samples < min_samples.  KEEP_SEED: all but the seed's component.  REMOVE_SEED: the seed's component alone.  The seed's
+ *      component is that of the solid sample, in the seed's 3^3 neighbourhood clipped to the grid, with the smallest squared index
+ *      distance to the seed, ties going to the lowest key: a pick's vrt_hit::voxel is the sample nearest the hit point and may lie
+ *      just outside the surface, but the hit cell always has a solid corner within that neighbourhood.
+ *   5. What a removed sample stores.  m = fmaxf(-d, gap), and m = gap when d is NaN: m itself (F32) or the texel of m (TEXEL16: the
+ *      rule at vrt_set_volume_format).  With material >= 0 the sample's id becomes `material`.  -d is the distance to the surface
+ *      that has just vanished; it never exceeds the distance to anything that remains: the safe side for sphere tracing.
+ *   6. Halo.  A passable sample with d < gap that has a 6-neighbour in a removed component and no 6-neighbour in a kept component
+ *      stores gap (or its texel), and is written only when the value to store differs in bits from the stored value; its material id
+ *      is untouched.  Without it the ring of tiny positive values around a removed piece would still fall under the march's hit
+ *      threshold.  In a distance field every outside sample nearer than 0.577 cells to a removed surface has a removed 6-neighbour,
+ *      so a gap of up to half a cell in density units (0.5 * cell / density_scale) is fully covered.  A sample that also touches a
+ *      kept component keeps its bits: no kept surface moves.
+ *   7. Class, components, removal and halo are all decided from the field as it was before the call (Jacobi).  Everything else keeps
+ *      its stored bits.  A second call with the same record writes nothing, and neither does REPORT.  (REMOVE_SEED resolves its seed
+ *      anew: the second call is VRT_ERR_INVALID, or removes the other component that has a sample in the seed's neighbourhood.)
+ * What the call does not do: around the removed pieces the field is no distance field afterwards (it holds the old magnitudes, at
+ * least gap).  vrt_volume_redistance over the written box grown by the band repairs that, as after a brush. */
+int vrt_volume_components(vrt_ctx* ctx, int slot, const vrt_components* rec,
+                          vrt_component* list_or_null, int list_capacity, vrt_components_result* result_or_null);
 
 /* True signed distances (no reference analogue).  The Voxelizer's field is a scaled unsigned shell, valid some two cells around the
  * mesh and a background constant elsewhere; vrt_volume_fill_enclosed leaves a jump at the former inner crossing and a wall that runs

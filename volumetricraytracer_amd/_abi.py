@@ -79,6 +79,9 @@ STAMP_MATERIAL_KEEP, STAMP_MATERIAL_SOURCE = -1, -2
 # vrt_volume_smooth
 MAX_SMOOTH_ITERATIONS = 16
 
+# vrt_volume_components
+COMPONENTS_REPORT, COMPONENTS_KEEP_LARGEST, COMPONENTS_REMOVE_SMALL, COMPONENTS_KEEP_SEED, COMPONENTS_REMOVE_SEED = 0, 1, 2, 3, 4
+
 QUERY_CLOSEST = 0
 QUERY_ANY = 1  # occlusion: instance 0 when some surface lies within [0, t_max]
 
@@ -259,6 +262,53 @@ class vrt_smooth(C.Structure):
     ]
 
 
+class vrt_components(C.Structure):
+    _fields_ = [
+        ("op", C.c_int32),
+        ("material", C.c_int32),
+        ("seed", C.c_int32 * 3),
+        ("gap", C.c_float),
+        ("min_samples", C.c_uint64),
+        ("reserved_", C.c_uint32 * 8),
+    ]
+
+
+class vrt_component(C.Structure):
+    _fields_ = [("first", C.c_int32 * 3), ("lo", C.c_int32 * 3), ("hi", C.c_int32 * 3), ("removed", C.c_uint32), ("samples", C.c_uint64)]
+
+
+class vrt_components_result(C.Structure):
+    _fields_ = [
+        ("lo", C.c_int32 * 3),
+        ("hi", C.c_int32 * 3),
+        ("written", C.c_uint64),
+        ("solid", C.c_uint64),
+        ("removed_samples", C.c_uint64),
+        ("components", C.c_uint32),
+        ("removed", C.c_uint32),
+        ("listed", C.c_uint32),
+        ("reserved_", C.c_uint32),
+    ]
+
+
+def components_record(op: int, gap: float = 0.0, material: int = -1, min_samples: int = 0, seed=(0, 0, 0)) -> "vrt_components":
+    """A vrt_components record (vrt.h): op COMPONENTS_*; gap in density units; seed xyz for the seed ops."""
+    r = vrt_components()
+    r.op, r.material, r.gap, r.min_samples = int(op), int(material), float(gap), int(min_samples)
+    for i in range(3):
+        r.seed[i] = int(seed[i])
+    return r
+
+
+def components_dict(res: "vrt_components_result", listed) -> dict:
+    """What vrt_volume_components reported, as plain Python: the result's fields, and "list": one dict per record written."""
+    out = {"lo": tuple(res.lo), "hi": tuple(res.hi), "written": int(res.written), "solid": int(res.solid),
+           "removed_samples": int(res.removed_samples), "components": int(res.components), "removed": int(res.removed)}
+    out["list"] = [{"first": tuple(c.first), "lo": tuple(c.lo), "hi": tuple(c.hi), "removed": int(c.removed), "samples": int(c.samples)}
+                   for c in listed[:res.listed]]
+    return out
+
+
 class vrt_fill_result(C.Structure):
     _fields_ = [("lo", C.c_int32 * 3), ("hi", C.c_int32 * 3), ("filled", C.c_uint64), ("sweeps", C.c_uint32), ("reserved_", C.c_uint32)]
 
@@ -295,6 +345,8 @@ SYMBOLS = {
     "vrt_volume_apply_brushes": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.POINTER(vrt_brush), C.POINTER(vrt_brush_result)]),
     "vrt_volume_stamp": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.POINTER(vrt_stamp), C.POINTER(vrt_brush_result)]),
     "vrt_volume_smooth": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(vrt_smooth), C.POINTER(vrt_brush_result)]),
+    "vrt_volume_components": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(vrt_components), C.POINTER(vrt_component), C.c_int,
+                                        C.POINTER(vrt_components_result)]),
     "vrt_volume_fill_enclosed": (C.c_int, [C.c_void_p, C.c_int, C.c_float, C.c_int, C.POINTER(vrt_fill_result)]),
     "vrt_volume_redistance": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int),
                                         C.POINTER(vrt_redistance_result)]),

@@ -910,6 +910,31 @@ bool VHipRenderer::FillEnclosed(const Scene::VVoxelObject& object, float wall, i
     return MirrorBox(slot, *volume, res.lo, res.hi);
 }
 
+bool VHipRenderer::Components(const Scene::VVoxelObject& object, const vrt_components& rec, std::vector<vrt_component>* list, int listCapacity,
+                              vrt_components_result* result) {
+    if (!IsActive()) {
+        V_LOG_WARNING("Components() on an inactive renderer");
+        return false;
+    }
+    const VObjectPtr<Scene::VScene> scene = SceneRef.lock();
+    const VObjectPtr<Voxel::VVoxelVolume> volume = object.GetVoxelVolume();
+    if (!scene || !volume || listCapacity < 0) return false;
+    if (!SyncWithScene(*scene)) return false;
+    const int slot = SlotOf(volume.get());
+    if (slot < 0) {
+        V_LOG_ERROR("Components(): the object's volume is not part of the rendered scene");
+        return false;
+    }
+    const int capacity = list ? listCapacity : 0;
+    if (list) list->assign((size_t)capacity, vrt_component{});
+    vrt_components_result res;
+    if (!ok(vrt_volume_components(Ctx, slot, &rec, capacity > 0 ? list->data() : nullptr, capacity, &res), "vrt_volume_components")) return false;
+    if (list) list->resize(res.listed);
+    if (result) *result = res;
+    if (res.written == 0) return true;
+    return MirrorBox(slot, *volume, res.lo, res.hi);
+}
+
 bool VHipRenderer::Redistance(const Scene::VVoxelObject& object, int band, int from, const VIntVector* boxLo, const VIntVector* boxHi,
                               vrt_redistance_result* result) {
     if (!IsActive()) {

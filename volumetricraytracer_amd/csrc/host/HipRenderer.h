@@ -149,6 +149,13 @@ public:
        filled voxels get, or -1.  The written box is read back into the host VVoxelVolume like ApplyBrushes does.  False (after
        logging) on failure or when the object's volume is not in the scene. */
     bool FillEnclosed(const Scene::VVoxelObject& object, float wall = 1.f, int material = -1, vrt_fill_result* result = nullptr);
+    /* The connected pieces of a volume labelled, listed and removed on the device (vrt_volume_components; the rule: vrt.h), on the
+       volume of a placed object of the scene Render() would draw now (synced first).  list (may be nullptr) receives the first
+       listCapacity components in the list order.  The written box is read back into the host VVoxelVolume like ApplyBrushes does.
+       False (after logging) on failure — a seed without a solid sample around it among them — or when the object's volume is not in
+       the scene. */
+    bool Components(const Scene::VVoxelObject& object, const vrt_components& rec, std::vector<vrt_component>* list = nullptr, int listCapacity = 0,
+                    vrt_components_result* result = nullptr);
     /* The volume of a placed object rewritten on the device as the signed distance, within `band` cells, to its own zero surface
        (vrt_volume_redistance; the rule: vrt.h), over the samples boxLo..boxHi (inclusive xyz indices, clamped to the grid) or the
        whole grid without a box.  from: VRT_REDISTANCE_FROM_OUTSIDE for Voxelizer shells, filled or not, _FROM_BOTH for true distance

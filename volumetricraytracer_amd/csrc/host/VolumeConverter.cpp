@@ -1,6 +1,7 @@
 #include "VolumeConverter.h"
 
 #include "../../../include/vrt.h"
+#include "../components_core.h"
 #include "../fill_core.h"
 #include "../mesh_core.h"
 #include "../redistance_core.h"
@@ -10,6 +11,7 @@
 
 #include <algorithm>
 #include <cmath>
+#include <cstring>
 #include <iostream>
 #include <vector>
 
@@ -94,6 +96,141 @@ VVolumeConverter::VFillResult VVolumeConverter::FillEnclosed(Voxel::VVoxelVolume
     const VFillResult out = FillEnclosed(volume.GetVoxels().data(), volume.GetSize(), wall, material);
     if (out.Filled) volume.MakeDirty();
     return out;
+}
+
+static uint64_t g_min_island = 0;
+void VVolumeConverter::MakeMinIsland(uint64_t k) { g_min_island = k; }
+/* The record MakeMinIsland stands for: the gap is half a cell in the converter's density units (density * threshold is a length). */
+static vrt_components min_island_record(float cell, float threshold) {
+    vrt_components rec = {};
+    rec.op = VRT_COMPONENTS_REMOVE_SMALL;
+    rec.material = 0;
+    rec.gap = 0.5f * cell / threshold;
+    rec.min_samples = g_min_island;
+    return rec;
+}
+
+int VVolumeConverter::Components(Voxel::VVoxel* voxels, size_t n, bool texel16, const vrt_components& rec, vrt_component* list, int listCapacity,
+                                 vrt_components_result* result_or_null) {
+    namespace cc = vrt_components_core;
+    const int N = (int)n;
+    if (!voxels || !cc::valid(&rec, N, texel16, list, listCapacity)) return VRT_ERR_INVALID;
+    const size_t count = n * n * n;
+    const ptrdiff_t step[3] = {(ptrdiff_t)(n * n), 1, (ptrdiff_t)n}; /* x, y, z */
+    const auto density = [&](size_t i) { return texel16 ? voxels[i].Density * 0.01f : voxels[i].Density; };
+    /* labels: a scan in key order meets every component at its lowest key first and floods it from there */
+    std::vector<uint32_t> label(count, cc::kPassable);
+    std::vector<cc::Component> comps;
+    std::vector<uint32_t> queue;
+    for (size_t s = 0; s < count; s++) {
+        if (label[s] != cc::kPassable || !cc::solid(density(s))) continue;
+        cc::Component c{(uint32_t)s, 0u, {N, N, N}, {-1, -1, -1}};
+        queue.clear();
+        queue.push_back((uint32_t)s);
+        label[s] = (uint32_t)s;
+        for (size_t head = 0; head < queue.size(); head++) {
+            const size_t i = queue[head];
+            const size_t at[3] = {i / (n * n), i % n, (i / n) % n};
+            c.samples++;
+            for (int a = 0; a < 3; a++) {
+                c.lo[a] = std::min(c.lo[a], (int32_t)at[a]);
+                c.hi[a] = std::max(c.hi[a], (int32_t)at[a]);
+                for (int dir = -1; dir <= 1; dir += 2) {
+                    if (dir < 0 ? at[a] == 0 : at[a] + 1 >= n) continue;
+                    const size_t j = (size_t)((ptrdiff_t)i + dir * step[a]);
+                    if (label[j] != cc::kPassable || !cc::solid(density(j))) continue;
+                    label[j] = (uint32_t)s;
+                    queue.push_back((uint32_t)j);
+                }
+            }
+        }
+        comps.push_back(c);
+    }
+    std::sort(comps.begin(), comps.end(), cc::before);
+    uint32_t seedLabel = cc::kPassable;
+    if (cc::seeded(rec.op)) seedLabel = cc::seed_component(N, rec.seed, [&](int x, int y, int z) { return label[cc::key_of(N, x, y, z)]; });
+    cc::Decision how;
+    if (!cc::decide(rec, comps.data(), comps.size(), seedLabel, how)) return VRT_ERR_INVALID;
+    vrt_components_result out = {};
+    for (int a = 0; a < 3; a++) out.lo[a] = N, out.hi[a] = -1;
+    out.components = (uint32_t)comps.size();
+    for (size_t i = 0; i < comps.size(); i++) {
+        const cc::Component& c = comps[i];
+        const bool goes = cc::removes(rec.op) && cc::removed_by(how.mode, how.a, how.b, c.key, c.samples);
+        out.solid += c.samples;
+        if (goes) out.removed++, out.removed_samples += c.samples;
+        if (i < (size_t)listCapacity) {
+            vrt_component& r = list[i];
+            r = vrt_component{};
+            cc::first_of(N, c.key, r.first);
+            for (int a = 0; a < 3; a++) r.lo[a] = c.lo[a], r.hi[a] = c.hi[a];
+            r.removed = goes ? 1u : 0u;
+            r.samples = c.samples;
+            out.listed++;
+        }
+        if (goes) { /* mark its samples: the flood again, over labels */
+            queue.clear();
+            queue.push_back(c.key);
+            label[c.key] |= cc::kRemovedBit;
+            for (size_t head = 0; head < queue.size(); head++) {
+                const size_t j0 = queue[head];
+                const size_t at[3] = {j0 / (n * n), j0 % n, (j0 / n) % n};
+                for (int a = 0; a < 3; a++)
+                    for (int dir = -1; dir <= 1; dir += 2) {
+                        if (dir < 0 ? at[a] == 0 : at[a] + 1 >= n) continue;
+                        const size_t j = (size_t)((ptrdiff_t)j0 + dir * step[a]);
+                        if (label[j] != c.key) continue;
+                        label[j] |= cc::kRemovedBit;
+                        queue.push_back((uint32_t)j);
+                    }
+            }
+        }
+    }
+    /* the edit: every decision from the labels and the sample's own density, so the order of the writes does not matter */
+    for (size_t i = 0; out.removed > 0 && i < count; i++) {
+        const uint32_t own = label[i];
+        if (cc::label_solid(own) && cc::label_kept(own)) continue;
+        const float d = density(i);
+        const size_t at[3] = {i / (n * n), i % n, (i / n) % n};
+        float value;
+        if (cc::label_solid(own)) {
+            const float m = cc::removed_density(d, rec.gap);
+            value = texel16 ? vrt_fill::texel16_value(m) : m;
+            if (rec.material >= 0) voxels[i].Material = (uint8_t)rec.material;
+        } else {
+            if (!cc::halo_candidate(d, rec.gap)) continue;
+            bool removed = false, kept = false;
+            for (int a = 0; a < 3; a++)
+                for (int dir = -1; dir <= 1; dir += 2) {
+                    if (dir < 0 ? at[a] == 0 : at[a] + 1 >= n) continue;
+                    const uint32_t nb = label[(size_t)((ptrdiff_t)i + dir * step[a])];
+                    removed = removed || cc::label_removed(nb);
+                    kept = kept || cc::label_kept(nb);
+                }
+            if (!removed || kept) continue;
+            value = texel16 ? vrt_fill::texel16_value(rec.gap) : rec.gap;
+            uint32_t was, now;
+            memcpy(&was, &voxels[i].Density, 4), memcpy(&now, &value, 4);
+            if (was == now) continue;
+        }
+        voxels[i].Density = value;
+        out.written++;
+        for (int a = 0; a < 3; a++) {
+            out.lo[a] = std::min(out.lo[a], (int32_t)at[a]);
+            out.hi[a] = std::max(out.hi[a], (int32_t)at[a]);
+        }
+    }
+    if (result_or_null) *result_or_null = out;
+    return VRT_OK;
+}
+
+int VVolumeConverter::Components(Voxel::VVoxelVolume& volume, const vrt_components& rec, vrt_component* list, int listCapacity,
+                                 vrt_components_result* result_or_null) {
+    vrt_components_result res = {};
+    const int rc = Components(volume.GetVoxels().data(), volume.GetSize(), false, rec, list, listCapacity, &res);
+    if (rc == VRT_OK && res.written) volume.MakeDirty();
+    if (rc == VRT_OK && result_or_null) *result_or_null = res;
+    return rc;
 }
 
 static int g_sdf_band = 0;
@@ -407,6 +544,10 @@ std::shared_ptr<Voxel::VVoxelVolume> VVolumeConverter::ConvertMeshInfoToVoxelVol
         static_assert(sizeof(Voxel::VVoxel) == sizeof(vrt_voxel), "VVoxel must match the wire record");
         int rc = vrt_voxelize_mesh(g_device_ctx, kScratchSlot, resolution, extends, pos.data(), meshInfo.Vertices.size(), idx.data(), idx.size(), &skipped);
         if (rc == VRT_OK && g_solid) rc = vrt_volume_fill_enclosed(g_device_ctx, kScratchSlot, 1.f, 1, nullptr);
+        if (rc == VRT_OK && g_min_island > 0) {
+            const vrt_components rec = min_island_record(volume->GetCellSize(), threshold);
+            rc = vrt_volume_components(g_device_ctx, kScratchSlot, &rec, nullptr, 0, nullptr);
+        }
         if (rc == VRT_OK && g_sdf_band > 0) { /* lengths in the shell's own metric, density * thr */
             rc = vrt_volume_set_metric(g_device_ctx, kScratchSlot, threshold, 0.5f * threshold);
             if (rc == VRT_OK) rc = vrt_volume_redistance(g_device_ctx, kScratchSlot, g_sdf_band, VRT_REDISTANCE_FROM_OUTSIDE, nullptr, nullptr, nullptr);
@@ -436,6 +577,7 @@ std::shared_ptr<Voxel::VVoxelVolume> VVolumeConverter::ConvertMeshInfoToVoxelVol
         voxelize_face(*volume, t, threshold);
     }
     if (g_solid && !on_device) FillEnclosed(*volume, 1.f, 1);
+    if (g_min_island > 0 && !on_device) Components(*volume, min_island_record(volume->GetCellSize(), threshold), nullptr, 0, nullptr);
     if (g_sdf_band > 0 && !on_device) {
         volume->DensityScale = threshold;
         Redistance(*volume, g_sdf_band, VRT_REDISTANCE_FROM_OUTSIDE);

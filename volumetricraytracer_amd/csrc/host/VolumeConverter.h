@@ -19,6 +19,9 @@
 struct vrt_ctx; /* include/vrt.h */
 struct vrt_stamp;
 struct vrt_smooth;
+struct vrt_components;
+struct vrt_component;
+struct vrt_components_result;
 
 namespace VolumeRaytracer {
 namespace Voxelizer {
@@ -108,6 +111,19 @@ public:
     static VStampResult Smooth(Voxel::VVoxelVolume& volume, const ::vrt_smooth& smooth);
     /* The same on n^3 VVoxel records (index x*n*n + z*n + y); texel16: the records hold the integer field +-q of a VRT_FORMAT_TEXEL16 slot. */
     static VStampResult Smooth(Voxel::VVoxel* voxels, size_t n, bool texel16, const ::vrt_smooth& smooth);
+    /* Islands labelled, listed and removed, in place — the rule of vrt_volume_components (include/vrt.h; its arithmetic and argument
+       rules are csrc/components_core.h, shared with the HIP build), as a breadth-first flood per component in key order.  list,
+       listCapacity and result_or_null are that call's; so is the return value: VRT_OK, or VRT_ERR_INVALID for a record it refuses
+       and for a seed without a solid sample around it — nothing is written then.  Marks the volume dirty when it wrote. */
+    static int Components(Voxel::VVoxelVolume& volume, const ::vrt_components& rec, ::vrt_component* list, int listCapacity,
+                          ::vrt_components_result* result_or_null);
+    /* The same on n^3 VVoxel records (index x*n*n + z*n + y); texel16: the records hold the integer field +-q of a VRT_FORMAT_TEXEL16 slot. */
+    static int Components(Voxel::VVoxel* voxels, size_t n, bool texel16, const ::vrt_components& rec, ::vrt_component* list, int listCapacity,
+                          ::vrt_components_result* result_or_null);
+    /* k > 0: every converted volume loses its components of fewer than k samples (REMOVE_SMALL, gap half a cell, material 0) before
+       it is returned, after the fill of MakeSolid and ahead of MakeSdf's pass — on the device (vrt_volume_components) while
+       UseDevice names a context, on the host otherwise; the same volume, bit for bit.  0 switches it off. */
+    static void MakeMinIsland(uint64_t k);
     static bool ExtractResolutionFromName(const std::string& name, uint8_t& outResolution);
     /* extraction threshold of a volume: cell size · √3 (VolumeConverter.cpp:57) */
     static float ExtractionThreshold(const Voxel::VVoxelVolume& volume);

@@ -30,6 +30,9 @@
  *            [--sdf BAND]                   with --solid: after the fill every volume is redistanced on the device (VHipRenderer::Redistance, vrt_volume_redistance,
  *                                           FROM_OUTSIDE, BAND cells, 1..15) into a true signed distance; under --edit-device the box each dab wrote, grown by
  *                                           BAND, is redistanced again after the dab
+ *            [--keep-largest]               after the last frame, ahead of --mesh-out: of the first object's volume only the largest connected piece stays
+ *                                           (VHipRenderer::Components, vrt_volume_components, KEEP_LARGEST, gap half a cell, material 0): what a carve cut
+ *                                           loose does not reach the mesh
  *            [--mesh-out FILE]              after the last frame the first object's volume, as sculpted on the device, leaves as triangles: surface nets on the
  *                                           device (VHipRenderer::ExtractMesh, vrt_volume_extract_mesh) written as glTF (.gltf + .bin, or .glb); `voxelizer` reads it back
  *            [--pick X Y]                   every frame asks what lies under pixel (X, Y) (VHipRenderer::Pick: a GPU ray query) and prints the
@@ -112,6 +115,7 @@ int main(int argc, char** argv) {
     int frames = 60;
     unsigned W = 1024, H = 576;
     std::string scenePath, skyboxDir, outPath = "vrt_demo.ppm", meshOut;
+    bool keepLargest = false;
     bool identityDefaults = false;
     int editBrush = 0, sdf = 0;
     bool editFull = false, editDevice = false, editStamp = false, solid = false;
@@ -140,6 +144,7 @@ int main(int argc, char** argv) {
         else if (!strcmp(argv[i], "--solid")) solid = true;
         else if (!strcmp(argv[i], "--sdf") && i + 1 < argc) sdf = atoi(argv[++i]);
         else if (!strcmp(argv[i], "--mesh-out") && i + 1 < argc) meshOut = argv[++i];
+        else if (!strcmp(argv[i], "--keep-largest")) keepLargest = true;
         else if (!strcmp(argv[i], "--pick") && i + 2 < argc) {
             pick = true;
             pickX = atoi(argv[++i]);
@@ -217,6 +222,10 @@ int main(int argc, char** argv) {
     }
     if (!meshOut.empty() && !hip) {
         fprintf(stderr, "--mesh-out extracts on the device: it needs the HIP renderer\n");
+        return 1;
+    }
+    if (keepLargest && !hip) {
+        fprintf(stderr, "--keep-largest labels on the device: it needs the HIP renderer\n");
         return 1;
     }
     if (sdf != 0 && (!solid || sdf < 1 || sdf > 15)) {
@@ -401,15 +410,28 @@ int main(int argc, char** argv) {
             printf("wrote %s\n", outPath.c_str());
         }
     }
-    if (!meshOut.empty()) { /* the first object's volume as it is on the device now */
-        VObjectPtr<Scene::VVoxelObject> first;
-        for (const auto& placed : scene->GetAllPlacedObjects()) {
-            const auto object = std::dynamic_pointer_cast<Scene::VVoxelObject>(placed);
-            if (object && object->GetVoxelVolume()) {
-                first = object;
-                break;
-            }
+    VObjectPtr<Scene::VVoxelObject> first;
+    for (const auto& placed : scene->GetAllPlacedObjects()) {
+        const auto object = std::dynamic_pointer_cast<Scene::VVoxelObject>(placed);
+        if (object && object->GetVoxelVolume()) {
+            first = object;
+            break;
         }
+    }
+    if (keepLargest) { /* whatever the dabs cut loose goes */
+        if (!first) return 1;
+        const Voxel::VVoxelVolume& volume = *first->GetVoxelVolume();
+        vrt_components rec;
+        memset(&rec, 0, sizeof rec);
+        rec.op = VRT_COMPONENTS_KEEP_LARGEST;
+        rec.material = 0;
+        rec.gap = 0.5f * volume.GetCellSize() / volume.DensityScale;
+        vrt_components_result res;
+        if (!hip->Components(*first, rec, nullptr, 0, &res)) return 1;
+        printf("components: %u pieces of %llu solid voxels, %u removed (%llu voxels, %llu written)\n", res.components,
+               (unsigned long long)res.solid, res.removed, (unsigned long long)res.removed_samples, (unsigned long long)res.written);
+    }
+    if (!meshOut.empty()) { /* the first object's volume as it is on the device now */
         Voxelizer::VGLTFExporter::VEntry e;
         if (!first || !hip->ExtractMesh(*first, e.Mesh)) return 1;
         const Voxel::VVoxelVolume& volume = *first->GetVoxelVolume();

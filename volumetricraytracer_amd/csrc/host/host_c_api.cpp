@@ -190,6 +190,21 @@ int vrh_smooth(vrt_voxel* voxels, int n, float extent, float density_scale, int 
     return VRT_OK;
 }
 
+/* VVolumeConverter::Components on caller records: n^3 records edited in place (index x*n*n + z*n + y); texel16 != 0: the densities
+   are the integer field +-q; list, list_capacity and result_or_null as vrt_volume_components takes them, and its return value:
+   VRT_OK, or VRT_ERR_INVALID as that call returns it (a NULL pointer or a grid below 2 samples likewise). */
+int vrh_components(vrt_voxel* voxels, int n, int texel16, const vrt_components* rec, vrt_component* list_or_null, int list_capacity,
+                   vrt_components_result* result_or_null) {
+    if (!voxels || !rec || n < 2) {
+        g_error = "vrh_components: bad argument";
+        return VRT_ERR_INVALID;
+    }
+    const int rc = Voxelizer::VVolumeConverter::Components(reinterpret_cast<Voxel::VVoxel*>(voxels), (size_t)n, texel16 != 0, *rec, list_or_null,
+                                                           list_capacity, result_or_null);
+    if (rc != VRT_OK) g_error = "vrh_components: the record is refused, or its seed has no solid sample around it";
+    return rc;
+}
+
 /* VGLTFImporter::ImportScene on a .gltf / .glb file, mesh `mesh` (its index in the file): counts_out[2] = vertices, indices; the
    positions as the importer hands them to the converter (x100, re-centred on the bounds' middle; 3 floats per vertex) and the indices
    are copied when their pointer is given and the capacity suffices; name_out receives the mesh's name.  0 / -1. */

@@ -30,6 +30,7 @@
 #include "stamp_core.h"
 #include "brush_core.h"
 #include "smooth_core.h"
+#include "components_core.h"
 
 using namespace vrt;
 
@@ -97,6 +98,7 @@ static_assert(sizeof(vrt_brush) == 64 && sizeof(vrt_brush_result) == 32, "vrt.h 
 static_assert(sizeof(vrt_stamp) == 96, "vrt.h states this size");
 static_assert(sizeof(vrt_smooth) == 64, "vrt.h states this size");
 static_assert(sizeof(vrt_fill_result) == 40, "vrt.h states this size");
+static_assert(sizeof(vrt_components) == 64 && sizeof(vrt_component) == 48 && sizeof(vrt_components_result) == 64, "vrt.h states these sizes");
 static_assert(sizeof(vrt_redistance_result) == 48, "vrt.h states this size");
 static_assert(sizeof(vrt_mesh_result) == 40, "vrt.h states this size");
 static_assert(sizeof(DBrushList) <= 3072, "the brush records travel in the kernel-argument block");
@@ -229,6 +231,11 @@ struct DeviceState {
     /* vrt_volume_fill_enclosed: the rounds' flags, the passable mask and the exterior labels (grown on demand, shared by the slots) */
     void* fill_scratch = nullptr;
     size_t fill_scratch_cap = 0;
+    /* vrt_volume_components: the labels with their header, and the component table (grown on demand, shared by the slots) */
+    void* comp_scratch = nullptr;
+    size_t comp_scratch_cap = 0;
+    void* comp_table = nullptr;
+    size_t comp_table_cap = 0;
     /* vrt_volume_redistance: the tile table and the compact surfels (grown on demand, shared by the slots) */
     void* redist_table = nullptr;
     size_t redist_table_cap = 0;
@@ -568,6 +575,8 @@ void destroy_device(DeviceState& D) {
     if (D.d_box6) (void)hipFree(D.d_box6);
     if (D.d_brush) (void)hipFree(D.d_brush);
     if (D.fill_scratch) (void)hipFree(D.fill_scratch);
+    if (D.comp_scratch) (void)hipFree(D.comp_scratch);
+    if (D.comp_table) (void)hipFree(D.comp_table);
     if (D.redist_table) (void)hipFree(D.redist_table);
     if (D.redist_surfels) (void)hipFree(D.redist_surfels);
     if (D.mesh_scratch) (void)hipFree(D.mesh_scratch);
@@ -1088,6 +1097,120 @@ int fill_enclosed(vrt_ctx* ctx, int slot, float wall, int material, vrt_fill_res
         rc = rebuild_written(ctx, D, slot, got.lo, got.hi, got.low, changed);
         if (rc != VRT_OK) return rc;
     }
+    return finish_edit(ctx, changed);
+}
+
+/* vrt_volume_components: first every device gets its label memory; then every device labels its copy (launch_components_label),
+ * reports how many components it found, gets its table and fills it (launch_components_stats) — the volume is still untouched.
+ * Device 0's table, sorted, is the list; it and (seed ops) the labels around the seed decide the removal predicate, which is the
+ * same mode and scalars on every device.  Only then, and only when something goes, the edit runs per device
+ * (launch_components_apply, which reports like a brush launch) and what the slot derives from the samples is recomputed over the
+ * written box (rebuild_derived).  Afterwards every buffer equals what upload_volume builds from the edited volume. */
+int components(vrt_ctx* ctx, int slot, const vrt_components* rec, vrt_component* list, int list_capacity, vrt_components_result* result) {
+    namespace cc = vrt_components_core;
+    if (!ctx || !rec) return VRT_ERR_INVALID;
+    if (!valid_slot(slot) || !ctx->vol[slot].used) return VRT_ERR_SLOT;
+    HostVolume& h = ctx->vol[slot];
+    const int N = h.N;
+    const bool texel16 = h.format == VRT_FORMAT_TEXEL16;
+    if (!cc::valid(rec, N, texel16, list, list_capacity)) return VRT_ERR_INVALID;
+    vrt_components_result out;
+    memset(&out, 0, sizeof out);
+    for (int a = 0; a < 3; a++) out.lo[a] = N, out.hi[a] = -1;
+    int rc = quiesce(ctx);
+    if (rc != VRT_OK) return rc;
+    for (auto& D : ctx->dev) { /* every allocation comes before any write */
+        HIP_TRY(hipSetDevice(D.ordinal));
+        rc = ensure_buffer(D.comp_scratch, D.comp_scratch_cap, components_scratch_bytes(N));
+        if (rc != VRT_OK) return rc;
+    }
+    unsigned n_components = 0;
+    for (size_t di = 0; di < ctx->dev.size(); di++) {
+        DeviceState& D = ctx->dev[di];
+        HIP_TRY(hipSetDevice(D.ordinal));
+        HIP_TRY(launch_components_label(D.vol[slot].dense, texel16, N, D.comp_scratch, D.stream));
+        unsigned header[2];
+        HIP_TRY(hipMemcpyAsync(header, components_header(D.comp_scratch), sizeof header, hipMemcpyDeviceToHost, D.stream));
+        HIP_TRY(hipStreamSynchronize(D.stream));
+        if (header[0] != 0u || (di > 0 && header[1] != n_components)) {
+            fprintf(stderr, "[vrt] vrt_volume_components: the labelling of a grid of %d^3 gave up on device %d\n", N, D.ordinal);
+            return VRT_ERR_HIP;
+        }
+        n_components = header[1];
+        rc = ensure_buffer(D.comp_table, D.comp_table_cap, components_table_bytes(n_components));
+        if (rc != VRT_OK) return rc;
+        if (n_components > 0) HIP_TRY(launch_components_stats(N, D.comp_scratch, D.comp_table, n_components, D.stream));
+    }
+    std::vector<cc::Component> comps(n_components);
+    cc::Decision how;
+    if (n_components > 0) {
+        DeviceState& D0 = ctx->dev[0];
+        HIP_TRY(hipSetDevice(D0.ordinal));
+        std::vector<unsigned char> raw(components_table_bytes(n_components));
+        HIP_TRY(hipMemcpyAsync(raw.data(), D0.comp_table, raw.size(), hipMemcpyDeviceToHost, D0.stream));
+        unsigned gave_up = 0;
+        HIP_TRY(hipMemcpyAsync(&gave_up, components_header(D0.comp_scratch), sizeof gave_up, hipMemcpyDeviceToHost, D0.stream));
+        HIP_TRY(hipStreamSynchronize(D0.stream));
+        if (gave_up != 0u) return VRT_ERR_HIP;
+        for (size_t i = 0; i < comps.size(); i++) components_decode_row(raw.data(), i, N, comps[i]);
+        std::sort(comps.begin(), comps.end(), cc::before);
+    }
+    uint32_t seed_label = cc::kPassable;
+    if (cc::seeded(rec->op)) { /* the labels of the seed's neighbourhood: up to nine runs of three along y */
+        uint32_t around[3][3][3];
+        for (auto& plane : around)
+            for (auto& line : plane)
+                for (uint32_t& l : line) l = cc::kPassable;
+        DeviceState& D0 = ctx->dev[0];
+        HIP_TRY(hipSetDevice(D0.ordinal));
+        const int y0 = std::max(rec->seed[1] - 1, 0), y1 = std::min(rec->seed[1] + 1, N - 1);
+        for (int dx = -1; dx <= 1; dx++)
+            for (int dz = -1; dz <= 1; dz++) {
+                const int x = rec->seed[0] + dx, z = rec->seed[2] + dz;
+                if (x < 0 || z < 0 || x >= N || z >= N) continue;
+                HIP_TRY(hipMemcpyAsync(&around[dx + 1][dz + 1][y0 - rec->seed[1] + 1], components_labels(D0.comp_scratch) + cc::key_of(N, x, y0, z),
+                                       (size_t)(y1 - y0 + 1) * sizeof(uint32_t), hipMemcpyDeviceToHost, D0.stream));
+            }
+        HIP_TRY(hipStreamSynchronize(D0.stream));
+        seed_label = cc::seed_component(N, rec->seed, [&](int x, int y, int z) {
+            return around[x - rec->seed[0] + 1][z - rec->seed[2] + 1][y - rec->seed[1] + 1];
+        });
+    }
+    if (!cc::decide(*rec, comps.data(), comps.size(), seed_label, how)) return VRT_ERR_INVALID; /* nothing has been written */
+    out.components = n_components;
+    for (size_t i = 0; i < comps.size(); i++) {
+        const cc::Component& c = comps[i];
+        const bool goes = cc::removes(rec->op) && cc::removed_by(how.mode, how.a, how.b, c.key, c.samples);
+        out.solid += c.samples;
+        if (goes) out.removed++, out.removed_samples += c.samples;
+        if (i < (size_t)list_capacity) {
+            vrt_component& r = list[i];
+            memset(&r, 0, sizeof r);
+            cc::first_of(N, c.key, r.first);
+            for (int a = 0; a < 3; a++) r.lo[a] = c.lo[a], r.hi[a] = c.hi[a];
+            r.removed = goes ? 1u : 0u;
+            r.samples = c.samples;
+            out.listed++;
+        }
+    }
+    bool changed = false;
+    for (size_t di = 0; out.removed > 0 && di < ctx->dev.size(); di++) {
+        DeviceState& D = ctx->dev[di];
+        HIP_TRY(hipSetDevice(D.ordinal));
+        DeviceVolume& v = D.vol[slot];
+        HIP_TRY(launch_components_apply(texel16, v.dense, v.material, N, D.comp_scratch, D.comp_table, how.mode, how.a, how.b, rec->gap,
+                                        rec->material, D.d_brush, D.stream));
+        Written got;
+        rc = read_report(D, N, got);
+        if (rc != VRT_OK) return rc;
+        if (di == 0) {
+            for (int a = 0; a < 3; a++) out.lo[a] = got.lo[a], out.hi[a] = got.hi[a];
+            out.written = got.low;
+        }
+        rc = rebuild_written(ctx, D, slot, got.lo, got.hi, got.low, changed); /* every written sample is a density write */
+        if (rc != VRT_OK) return rc;
+    }
+    if (result) *result = out;
     return finish_edit(ctx, changed);
 }
 
@@ -1890,6 +2013,11 @@ int vrt_volume_smooth(vrt_ctx* ctx, int slot, const vrt_smooth* smooth, vrt_brus
 
 int vrt_volume_fill_enclosed(vrt_ctx* ctx, int slot, float wall, int material, vrt_fill_result* result_or_null) {
     return fill_enclosed(ctx, slot, wall, material, result_or_null);
+}
+
+int vrt_volume_components(vrt_ctx* ctx, int slot, const vrt_components* rec, vrt_component* list_or_null, int list_capacity,
+                          vrt_components_result* result_or_null) {
+    return components(ctx, slot, rec, list_or_null, list_capacity, result_or_null);
 }
 
 int vrt_volume_redistance(vrt_ctx* ctx, int slot, int band, int from, const int origin_xyz_or_null[3], const int size_xyz_or_null[3],

@@ -9,6 +9,9 @@
 namespace vrt_stamp_core {
 struct Rule; /* stamp_core.h */
 }
+namespace vrt_components_core {
+struct Component; /* components_core.h */
+}
 
 namespace vrt {
 
@@ -151,6 +154,28 @@ hipError_t launch_stamp_region(const vrt_stamp_core::Rule& rule, bool src_texel1
 size_t smooth_scratch_bytes(const EditBox& work);
 hipError_t launch_smooth(const vrt_smooth& rule, bool texel16, float* dense, uint8_t* material, int N, const EditBox& work,
                          const EditBox& region, void* scratch, DBrushSlot* slots, hipStream_t stream);
+
+/* vrt_volume_components (vrt_components.hip).  scratch: components_scratch_bytes(N) of device memory — a header of counters and two
+   words per sample: the labels (components_core.h) and, at every root's key, its row in the table —, valid from
+   launch_components_label to launch_components_apply.  table: components_table_bytes(components) of device memory, 32 B a component. */
+size_t components_scratch_bytes(int N);
+size_t components_table_bytes(unsigned components);
+/* device memory: the labels, one word per sample in the grid's own order, every solid sample's the lowest key of its component
+   once launch_components_label has run; the header's words {gave up, components} */
+const unsigned* components_labels(const void* scratch);
+const unsigned* components_header(const void* scratch);
+/* Labels every sample: the tiles on their own, the union of what meets across tile faces, every label made its root; counts the
+   roots.  A find or a union that ran into its cap leaves the header's first word non-zero. */
+hipError_t launch_components_label(const float* dense, bool texel16, int N, void* scratch, hipStream_t stream);
+/* One row of the table per component, in no particular order: its key, its samples and their box; `components`: the header's count. */
+hipError_t launch_components_stats(int N, void* scratch, void* table, unsigned components, hipStream_t stream);
+/* Row `row` of a host copy of the table. */
+void components_decode_row(const void* table, size_t row, int N, vrt_components_core::Component& out);
+/* The samples of every component the predicate removes (mode, a, b: components_core.h, removed_by) store removed_density (its texel
+   when texel16) and, material_id >= 0, that id; their halo stores the gap.  slots: zeroed, then the written samples' counts and box
+   (the edit report, above).  The labels are spent afterwards. */
+hipError_t launch_components_apply(bool texel16, float* dense, uint8_t* material, int N, void* scratch, const void* table, int mode, unsigned a,
+                                   unsigned b, float gap, int material_id, DBrushSlot* slots, hipStream_t stream);
 
 /* vrt_volume_extract_mesh (vrt_mesh.hip).  The cell box of a sample box, in xyz order (the mesh rule's own): its first cell, its cells
    per axis (one less than the samples; none when the box is one sample thick somewhere) and how many runs of 64 cells a row along y has. */

@@ -335,6 +335,21 @@ class VHipRenderer:
             self._mirror_box(slot, vol, lo, hi)
         return {"filled": int(res.filled), "lo": lo, "hi": hi, "sweeps": int(res.sweeps)}
 
+    def components(self, slot: int, rec: _abi.vrt_components, vol: Optional[VVoxelVolume] = None, list_capacity: int = 0) -> dict:
+        """vrt_volume_components: the 6-connected pieces of the solid samples (density <= 0 or NaN) of the volume resident in `slot`
+        labelled on the device, and the ones the record (_abi.components_record) names removed in place.  Given the slot's host
+        mirror `vol`, the written box is then read back as apply_brushes does.  Returns _abi.components_dict: the result's fields and
+        "list", the first `list_capacity` components by size.  A seed op whose seed has no solid sample around it raises
+        _abi.VrtError (ERR_INVALID) and writes nothing."""
+        self._require()
+        res = _abi.vrt_components_result()
+        lst = (_abi.vrt_component * max(int(list_capacity), 1))()
+        _abi.check(self._lib.vrt_volume_components(self._ctx, int(slot), C.byref(rec), lst if list_capacity > 0 else None, int(list_capacity),
+                                                   C.byref(res)), "vrt_volume_components")
+        if res.written and vol is not None:
+            self._mirror_box(slot, vol, tuple(res.lo), tuple(res.hi))
+        return _abi.components_dict(res, lst)
+
     def redistance(self, slot: int, vol: Optional[VVoxelVolume], band: int, from_: int = _abi.REDISTANCE_FROM_BOTH, lo=None, hi=None) -> dict:
         """vrt_volume_redistance: the samples lo..hi (inclusive xyz corners; both None: the whole grid) of the volume resident in
         `slot` rewritten on the device as the signed distance, within `band` cells (1..15), to the zero surface of the field the slot

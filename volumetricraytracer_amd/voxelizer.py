@@ -49,6 +49,9 @@ def load_host() -> C.CDLL:
                                   C.POINTER(_abi.vrt_stamp), C.POINTER(_abi.vrt_brush_result)]
         lib.vrh_smooth.restype = C.c_int
         lib.vrh_smooth.argtypes = [C.c_void_p, C.c_int, C.c_float, C.c_float, C.c_int, C.POINTER(_abi.vrt_smooth), C.POINTER(_abi.vrt_brush_result)]
+        lib.vrh_components.restype = C.c_int
+        lib.vrh_components.argtypes = [C.c_void_p, C.c_int, C.c_int, C.POINTER(_abi.vrt_components), C.POINTER(_abi.vrt_component), C.c_int,
+                                       C.POINTER(_abi.vrt_components_result)]
         lib.vrh_extract_mesh.restype = C.c_int
         lib.vrh_extract_mesh.argtypes = [C.c_void_p, C.c_int, C.c_float, C.c_int, C.c_float, C.POINTER(C.c_int), C.POINTER(C.c_int), C.c_void_p,
                                          C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.POINTER(_abi.vrt_mesh_result)]
@@ -106,6 +109,26 @@ def fill_enclosed_host(vol: VVoxelVolume, wall: float = 1.0, material: int = -1)
         vol.material_id = np.ascontiguousarray(rec["material"].reshape(vol.N, vol.N, vol.N))
         vol.dirty = True
     return {"filled": int(res.filled), "lo": tuple(res.lo), "hi": tuple(res.hi)}
+
+
+def components_host(vol: VVoxelVolume, rec: _abi.vrt_components, texel16: bool = False, list_capacity: int = 0) -> dict:
+    """VVolumeConverter::Components (the host build of vrt_volume_components's rule) on a volume's densities and material ids, in place.
+    texel16: the densities are the integer field +-q of a TEXEL16 slot.  Raises _abi.VrtError with the code vrt_volume_components
+    returns for a record it refuses or a seed without a solid sample around it.  Returns _abi.components_dict."""
+    lib = load_host()
+    buf = np.zeros(vol.N ** 3, dtype=np.dtype([("material", "u1"), ("pad", "u1", 3), ("density", "<f4")]))
+    buf["density"] = np.asarray(vol.density, np.float32).reshape(-1)
+    buf["material"] = np.asarray(vol.material_id, np.uint8).reshape(-1)
+    res = _abi.vrt_components_result()
+    lst = (_abi.vrt_component * max(int(list_capacity), 1))()
+    rc = lib.vrh_components(buf.ctypes.data, vol.N, int(bool(texel16)), C.byref(rec), lst if list_capacity > 0 else None, int(list_capacity),
+                            C.byref(res))
+    _abi.check(rc, "vrh_components")
+    if res.written:
+        vol.density = np.ascontiguousarray(buf["density"].reshape(vol.N, vol.N, vol.N))
+        vol.material_id = np.ascontiguousarray(buf["material"].reshape(vol.N, vol.N, vol.N))
+        vol.dirty = True
+    return _abi.components_dict(res, lst)
 
 
 def redistance_host(vol: VVoxelVolume, band: int, from_: int = _abi.REDISTANCE_FROM_BOTH, lo=None, hi=None, unit=None, texel16: bool = False) -> dict:
