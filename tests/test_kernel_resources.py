@@ -1,37 +1,21 @@
 """What the march's speed stands on besides its arithmetic, checked on the build's own ISA listing (no GPU): the register budgets
 that decide how many waves a SIMD holds, no scratch memory in the lean kernels, and no packed fp32 instruction anywhere (round 5
 measured v_pk_fma_f32 / v_pk_add_f32 2-5 % slower than the scalar instructions they replace: profiles/r05_ab_step_asm.txt).
-The listing is what csrc/build.sh keeps from -save-temps in $VRT_BUILD_TMP (default: build/hip inside the checkout); where the
-library was built elsewhere and the listing did not come with it the tests skip."""
+The listing is read by tests/isa_listing.py."""
 import os
 import re
 
-import pytest
-
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-LISTING = os.path.join(os.environ.get("VRT_BUILD_TMP", os.path.join(ROOT, "build", "hip")), "vrt_kernels-hip-amdgcn-amd-amdhsa-gfx950.s")
-LIB = os.path.join(ROOT, "volumetricraytracer_amd", "lib", "libvrt_hip.so")
+import isa_listing
 
 
 def _listing():
-    if not os.path.exists(LISTING) or not os.path.exists(LIB) or os.path.getmtime(LISTING) + 600 < os.path.getmtime(LIB):
-        pytest.skip("no ISA listing of this build here (it is written by csrc/build.sh next to the build's temporaries)")
-    return open(LISTING).read()
+    return isa_listing.listing_text("vrt_kernels")
 
 
-def _kernels(text):
-    meta = text[text.index("amdhsa.kernels:"):]
-    out = {}
-    for block in re.split(r"\n  - \.agpr_count:", meta)[1:]:
-        f = dict(re.findall(r"\.(name|vgpr_count|sgpr_count|private_segment_fixed_size|vgpr_spill_count):\s+(\S+)", block))
-        out[f["name"]] = {k: int(v) for k, v in f.items() if k != "name"}
-    return out
-
-
-def _march_kernels(k):
+def _march_kernels():
     """{(PATH, SINGLE, DIAG, DYN, REF): resources} of the march_kernel<PATH, SINGLE, DIAG, DYN, REF> instantiations (Itanium names)."""
     out = {}
-    for name, r in k.items():
+    for name, r in isa_listing.kernels("vrt_kernels").items():
         m = re.fullmatch(r"_ZN3vrt12march_kernelILi(\d+)ELb([01])ELb([01])ELb([01])ELb([01])EEEvNS_6DBlockE", name)
         if m:
             out[(int(m.group(1)),) + tuple(x == "1" for x in m.groups()[1:])] = r
@@ -39,7 +23,7 @@ def _march_kernels(k):
 
 
 def test_the_lean_kernels_fit_eight_waves_per_simd_and_use_no_scratch():
-    mk = _march_kernels(_kernels(_listing()))
+    mk = _march_kernels()
     # SINGLE, not the diagnostic build, every data path but the dense grid's (path 1: no tables, a debugging path at 66 registers)
     lean = {t: r for t, r in mk.items() if t[1] and not t[2] and t[0] != 1}
     assert len(lean) >= 16, sorted(mk)
@@ -52,7 +36,7 @@ def test_the_lean_kernels_fit_eight_waves_per_simd_and_use_no_scratch():
 
 
 def test_the_bvh_kernels_fit_seven_waves_per_simd():
-    mk = _march_kernels(_kernels(_listing()))
+    mk = _march_kernels()
     bvh = {t: r for t, r in mk.items() if t[0] != 1 and not t[1] and not t[2]}
     assert len(bvh) >= 8, sorted(mk)
     for t, r in bvh.items():
@@ -77,6 +61,6 @@ def test_the_hand_written_step_blocks_are_in_the_march_loops():
     assert m
     body = m.group(1)
     assert body.count("v_cmpx_gt_f32_e32") >= 2 and body.count("s_and_saveexec_b64") >= 2
-    src = open(os.path.join(os.path.dirname(LIB), "..", "csrc", "vrt_kernels.hip")).read()
+    src = open(os.path.join(isa_listing.ROOT, "volumetricraytracer_amd", "csrc", "vrt_kernels.hip")).read()
     block = src[src.index("void step_from_sample("):src.index("void step_over_empty_space(")]
     assert re.search(r':\s*"vcc",\s*"scc"\);', block), "step_from_sample must declare vcc and scc clobbered"

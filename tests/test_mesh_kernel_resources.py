@@ -1,27 +1,11 @@
 """The mesh kernels (csrc/vrt_mesh.hip) keep a cell's eight corner values, its vertex and its quads in registers: checked on the build's
 own ISA listing (no GPU), on the metadata block only — every kernel of the file has no private segment (scratch memory) and no spills.
-The listing is what csrc/build.sh keeps from -save-temps in $VRT_BUILD_TMP (default: build/hip inside the checkout); where the library
-was built elsewhere and the listing did not come with it the test skips, like tests/test_kernel_resources.py."""
-import os
-import re
-
-import pytest
-
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-LISTING = os.path.join(os.environ.get("VRT_BUILD_TMP", os.path.join(ROOT, "build", "hip")), "vrt_mesh-hip-amdgcn-amd-amdhsa-gfx950.s")
-LIB = os.path.join(ROOT, "volumetricraytracer_amd", "lib", "libvrt_hip.so")
-FIELDS = ("private_segment_fixed_size", "vgpr_spill_count", "sgpr_spill_count", "vgpr_count")
+The listing is read by tests/isa_listing.py."""
+import isa_listing
 
 
 def test_the_mesh_kernels_use_no_scratch_memory_and_spill_nothing():
-    if not os.path.exists(LISTING) or not os.path.exists(LIB) or os.path.getmtime(LISTING) + 600 < os.path.getmtime(LIB):
-        pytest.skip("no ISA listing of this build here (it is written by csrc/build.sh next to the build's temporaries)")
-    text = open(LISTING).read()
-    meta = text[text.index("amdhsa.kernels:"):]
-    kernels = {}
-    for block in re.split(r"\n  - \.agpr_count:", meta)[1:]:
-        f = dict(re.findall(r"\.(name|" + "|".join(FIELDS) + r"):\s+(\S+)", block))
-        kernels[f["name"]] = {k: int(f[k]) for k in FIELDS}
+    kernels = isa_listing.kernels("vrt_mesh")
     for stem, instances in (("mesh_count_kernel", 2), ("mesh_emit_kernel", 2), ("mesh_scan_reduce_kernel", 1), ("mesh_scan_sums_kernel", 1),
                             ("mesh_scan_apply_kernel", 1)):
         assert sum(stem in name for name in kernels) == instances, (stem, sorted(kernels))

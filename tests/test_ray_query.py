@@ -10,13 +10,12 @@ import subprocess
 import numpy as np
 import pytest
 
+import isa_listing
 import volumetricraytracer_amd as v
 from volumetricraytracer_amd import _abi
 from volumetricraytracer_amd import workloads as scenes
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-LISTING = os.path.join(os.environ.get("VRT_BUILD_TMP", os.path.join(ROOT, "build", "hip")), "vrt_kernels-hip-amdgcn-amd-amdhsa-gfx950.s")
-LIB = os.path.join(ROOT, "volumetricraytracer_amd", "lib", "libvrt_hip.so")
 
 
 def test_ray_and_hit_records_have_the_c_layout(tmp_path):
@@ -117,27 +116,19 @@ def test_argument_errors_without_a_gpu():
     assert lib.vrt_camera_rays(C.byref(abi), 64, 64, 2, pp, rp) == 0
 
 
-def _listing():
-    if not os.path.exists(LISTING) or not os.path.exists(LIB) or os.path.getmtime(LISTING) + 600 < os.path.getmtime(LIB):
-        pytest.skip("no ISA listing of this build here (it is written by csrc/build.sh next to the build's temporaries)")
-    return open(LISTING).read()
-
-
-def _query_kernels(text):
+def _query_kernels():
     """{(PATH, SINGLE, ANY, REF): resources} of the query_kernel<PATH, SINGLE, ANY, REF> instantiations (Itanium names)."""
-    meta = text[text.index("amdhsa.kernels:"):]
     out = {}
-    for block in re.split(r"\n  - \.agpr_count:", meta)[1:]:
-        f = dict(re.findall(r"\.(name|vgpr_count|private_segment_fixed_size|vgpr_spill_count|group_segment_fixed_size):\s+(\S+)", block))
-        m = re.fullmatch(r"_ZN3vrt12query_kernelILi(\d+)ELb([01])ELb([01])ELb([01])EEEvNS_6DQueryE", f["name"])
+    for name, r in isa_listing.kernels("vrt_kernels").items():
+        m = re.fullmatch(r"_ZN3vrt12query_kernelILi(\d+)ELb([01])ELb([01])ELb([01])EEEvNS_6DQueryE", name)
         if m:
-            out[(int(m.group(1)),) + tuple(x == "1" for x in m.groups()[1:])] = {k: int(x) for k, x in f.items() if k != "name"}
+            out[(int(m.group(1)),) + tuple(x == "1" for x in m.groups()[1:])] = r
     return out
 
 
 def test_the_query_kernel_is_built_within_the_lean_budget():
-    text = _listing()
-    qk = _query_kernels(text)
+    text = isa_listing.listing_text("vrt_kernels")
+    qk = _query_kernels()
     # every internal path: dense, bricks, int16 bricks, cell records, both Cube paths
     assert {t[0] for t in qk} == {1, 2, 8, 9, 10, 11}, sorted(qk)
     single_closest = {t: r for t, r in qk.items() if t[1] and not t[2]}

@@ -1,27 +1,11 @@
 """The stamp kernel (csrc/vrt_stamp.hip) hides its eight dependent-address loads per lane by occupancy alone: checked on the build's own
 ISA listing (no GPU), on the metadata block only — every instance has no private segment (scratch memory), no spills and at most 64
-VGPRs.  The listing is what csrc/build.sh keeps from -save-temps in $VRT_BUILD_TMP (default: build/hip inside the checkout); where the
-library was built elsewhere and the listing did not come with it the test skips, like tests/test_mesh_kernel_resources.py."""
-import os
-import re
-
-import pytest
-
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-LISTING = os.path.join(os.environ.get("VRT_BUILD_TMP", os.path.join(ROOT, "build", "hip")), "vrt_stamp-hip-amdgcn-amd-amdhsa-gfx950.s")
-LIB = os.path.join(ROOT, "volumetricraytracer_amd", "lib", "libvrt_hip.so")
-FIELDS = ("private_segment_fixed_size", "vgpr_spill_count", "sgpr_spill_count", "vgpr_count")
+VGPRs.  The listing is read by tests/isa_listing.py."""
+import isa_listing
 
 
 def test_the_stamp_kernels_use_no_scratch_memory_and_at_most_64_vgprs():
-    if not os.path.exists(LISTING) or not os.path.exists(LIB) or os.path.getmtime(LISTING) + 600 < os.path.getmtime(LIB):
-        pytest.skip("no ISA listing of this build here (it is written by csrc/build.sh next to the build's temporaries)")
-    text = open(LISTING).read()
-    meta = text[text.index("amdhsa.kernels:"):]
-    kernels = {}
-    for block in re.split(r"\n  - \.agpr_count:", meta)[1:]:
-        f = dict(re.findall(r"\.(name|" + "|".join(FIELDS) + r"):\s+(\S+)", block))
-        kernels[f["name"]] = {k: int(f[k]) for k in FIELDS}
+    kernels = isa_listing.kernels("vrt_stamp")
     assert sum("stamp_region_kernel" in name for name in kernels) == 4, sorted(kernels)  # {source F32, TEXEL16} x {destination F32, TEXEL16}
     assert len(kernels) == 4, sorted(kernels)
     for name, r in kernels.items():

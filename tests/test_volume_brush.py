@@ -10,12 +10,13 @@ import numpy as np
 import pytest
 
 import brush_ref as B
+import isa_listing
 import volume_ref as R
 import volumetricraytracer_amd as v
 from volumetricraytracer_amd import _abi
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-BRUSH_KERNELS = ("brush_region_kernel", "gather_region_kernel")
+BRUSH_KERNELS = {"brush_region_kernel": "vrt_brush", "gather_region_kernel": "vrt_volume"}  # kernel: its listing
 
 
 def test_brush_entry_points_refuse_a_null_context_without_a_gpu():
@@ -158,21 +159,9 @@ def test_reference_figures_of_the_carved_torus():
 
 
 def test_brush_kernels_use_no_scratch_memory():
-    listing = os.path.join(os.environ.get("VRT_BUILD_TMP", os.path.join(ROOT, "build", "hip")), "vrt_kernels-hip-amdgcn-amd-amdhsa-gfx950.s")
-    lib = os.path.join(ROOT, "volumetricraytracer_amd", "lib", "libvrt_hip.so")
-    if not os.path.exists(listing) or not os.path.exists(lib) or os.path.getmtime(listing) + 600 < os.path.getmtime(lib):
-        pytest.skip("no ISA listing of this build here (it is written by csrc/build.sh next to the build's temporaries)")
-    text = open(listing).read()
-    meta = text[text.index("amdhsa.kernels:"):]
-    found = {}
-    for block in re.split(r"\n  - \.agpr_count:", meta)[1:]:
-        f = dict(re.findall(r"\.(name|private_segment_fixed_size|vgpr_spill_count|group_segment_fixed_size):\s+(\S+)", block))
-        for k in BRUSH_KERNELS:
-            if re.search(r"\d" + k + r"(?:I|E)", f["name"]):
-                found.setdefault(k, []).append((f["name"], int(f["private_segment_fixed_size"]), int(f["vgpr_spill_count"]),
-                                                int(f["group_segment_fixed_size"])))
-    assert sorted(found) == sorted(BRUSH_KERNELS)
+    found = {k: isa_listing.instances(isa_listing.kernels(stem), k) for k, stem in BRUSH_KERNELS.items()}
+    assert all(found.values()), found
     assert len(found["brush_region_kernel"]) == 2  # F32 and TEXEL16
-    for k, inst in found.items():
-        for name, scratch, spills, lds in inst:
-            assert scratch == 0 and spills == 0 and lds == 0, (name, scratch, spills, lds)
+    for inst in found.values():
+        for name, r in inst.items():
+            assert r["private_segment_fixed_size"] == 0 and r["vgpr_spill_count"] == 0 and r["group_segment_fixed_size"] == 0, (name, r)

@@ -8,6 +8,7 @@ import subprocess
 import numpy as np
 import pytest
 
+import isa_listing
 import volumetricraytracer_amd as v
 from volumetricraytracer_amd import _abi
 
@@ -93,19 +94,9 @@ int main() {
 
 
 def test_edit_kernels_use_no_scratch_memory():
-    listing = os.path.join(os.environ.get("VRT_BUILD_TMP", os.path.join(ROOT, "build", "hip")), "vrt_kernels-hip-amdgcn-amd-amdhsa-gfx950.s")
-    lib = os.path.join(ROOT, "volumetricraytracer_amd", "lib", "libvrt_hip.so")
-    if not os.path.exists(listing) or not os.path.exists(lib) or os.path.getmtime(listing) + 600 < os.path.getmtime(lib):
-        pytest.skip("no ISA listing of this build here (it is written by csrc/build.sh next to the build's temporaries)")
-    text = open(listing).read()
-    meta = text[text.index("amdhsa.kernels:"):]
-    found = {}
-    for block in re.split(r"\n  - \.agpr_count:", meta)[1:]:
-        f = dict(re.findall(r"\.(name|private_segment_fixed_size|vgpr_spill_count):\s+(\S+)", block))
-        for k in EDIT_KERNELS:
-            if re.search(r"\d" + k + r"(?:I|E)", f["name"]):
-                found.setdefault(k, []).append((f["name"], int(f["private_segment_fixed_size"]), int(f["vgpr_spill_count"])))
-    assert sorted(found) == sorted(EDIT_KERNELS)
-    for k, inst in found.items():
-        for name, scratch, spills in inst:
-            assert scratch == 0 and spills == 0, (name, scratch, spills)
+    kernels = isa_listing.kernels("vrt_volume")
+    found = {k: isa_listing.instances(kernels, k) for k in EDIT_KERNELS}
+    assert all(found.values()), found
+    for inst in found.values():
+        for name, r in inst.items():
+            assert r["private_segment_fixed_size"] == 0 and r["vgpr_spill_count"] == 0, (name, r)

@@ -1,6 +1,6 @@
 /*
  * brush_core.h — what the analytic brush shapes of include/vrt.h (sphere, box, capsule) mean, once: the brush distance s for the
- * kernels of vrt_volume_apply_brushes (vrt_kernels.hip) and of vrt_volume_smooth (vrt_smooth.hip) and for the host pass of the latter
+ * kernels of vrt_volume_apply_brushes (vrt_brush.hip) and of vrt_volume_smooth (vrt_smooth.hip) and for the host pass of the latter
  * (csrc/host/VolumeConverter.cpp, g++), and — host only — the argument rules of a vrt_brush and the box of samples it can write.
  *
  * Plain floats, every expression evaluated as parenthesised in vrt.h, no fused multiply-add on either side (both builds compile
@@ -16,7 +16,7 @@
 #include <cmath>
 
 #include "../../include/vrt.h"
-#include "fill_core.h" /* VRT_HD */
+#include "grid_core.h"
 
 namespace vrt_brush_core {
 

@@ -2,7 +2,7 @@
  * components_core.h — the rules of vrt_volume_components (include/vrt.h) that its builds must agree on, once: the HIP kernels
  * (vrt_components.hip, hipcc), the host function of vrt_api.hip and the host pass (csrc/host/VolumeConverter.cpp, g++).
  *
- * d is a sample's density in the caller's units (the stored float, or stored * 0.01f of a VRT_FORMAT_TEXEL16 slot).  Plain floats,
+ * d is a sample's density in the caller's units (grid_core.h's decode of the stored float).  Plain floats,
  * one negation and one maximum, no fused multiply-add on either side: the builds produce the same bits.
  */
 #ifndef VRT_COMPONENTS_CORE_H
@@ -14,7 +14,7 @@
 #include <algorithm>
 
 #include "../../include/vrt.h"
-#include "fill_core.h"
+#include "grid_core.h"
 
 namespace vrt_components_core {
 
@@ -50,7 +50,7 @@ inline bool valid(const vrt_components* rec, int N, bool texel16, const vrt_comp
     if (rec->material < -1 || rec->material > 255) return false;
     if (!std::isfinite(rec->gap)) return false;
     if (removes(rec->op) && !(rec->gap > 0.0f)) return false;
-    if (removes(rec->op) && texel16 && vrt_fill::texel16_value(rec->gap) == 0.0f) return false;
+    if (removes(rec->op) && texel16 && vrt_grid::texel16_value(rec->gap) == 0.0f) return false;
     if (rec->op != VRT_COMPONENTS_REMOVE_SMALL && rec->min_samples != 0) return false;
     for (int a = 0; a < 3; a++)
         if (seeded(rec->op) ? (rec->seed[a] < 0 || rec->seed[a] >= N) : rec->seed[a] != 0) return false;

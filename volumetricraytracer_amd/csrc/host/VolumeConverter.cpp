@@ -3,6 +3,7 @@
 #include "../../../include/vrt.h"
 #include "../components_core.h"
 #include "../fill_core.h"
+#include "../grid_core.h"
 #include "../mesh_core.h"
 #include "../redistance_core.h"
 #include "../smooth_core.h"
@@ -117,7 +118,7 @@ int VVolumeConverter::Components(Voxel::VVoxel* voxels, size_t n, bool texel16, 
     if (!voxels || !cc::valid(&rec, N, texel16, list, listCapacity)) return VRT_ERR_INVALID;
     const size_t count = n * n * n;
     const ptrdiff_t step[3] = {(ptrdiff_t)(n * n), 1, (ptrdiff_t)n}; /* x, y, z */
-    const auto density = [&](size_t i) { return texel16 ? voxels[i].Density * 0.01f : voxels[i].Density; };
+    const auto density = [&](size_t i) { return vrt_grid::decode(voxels[i].Density, texel16); };
     /* labels: a scan in key order meets every component at its lowest key first and floods it from there */
     std::vector<uint32_t> label(count, cc::kPassable);
     std::vector<cc::Component> comps;
@@ -195,7 +196,7 @@ int VVolumeConverter::Components(Voxel::VVoxel* voxels, size_t n, bool texel16, 
         float value;
         if (cc::label_solid(own)) {
             const float m = cc::removed_density(d, rec.gap);
-            value = texel16 ? vrt_fill::texel16_value(m) : m;
+            value = texel16 ? vrt_grid::texel16_value(m) : m;
             if (rec.material >= 0) voxels[i].Material = (uint8_t)rec.material;
         } else {
             if (!cc::halo_candidate(d, rec.gap)) continue;
@@ -208,7 +209,7 @@ int VVolumeConverter::Components(Voxel::VVoxel* voxels, size_t n, bool texel16, 
                     kept = kept || cc::label_kept(nb);
                 }
             if (!removed || kept) continue;
-            value = texel16 ? vrt_fill::texel16_value(rec.gap) : rec.gap;
+            value = texel16 ? vrt_grid::texel16_value(rec.gap) : rec.gap;
             uint32_t was, now;
             memcpy(&was, &voxels[i].Density, 4), memcpy(&now, &value, 4);
             if (was == now) continue;
@@ -245,10 +246,10 @@ VVolumeConverter::VRedistanceResult VVolumeConverter::Redistance(Voxel::VVoxel* 
         glo[a] = std::max(lo[a] - reach, 0);
         ghi[a] = std::min(hi[a] + reach, N - 1);
     }
-    const auto at = [&](int x, int y, int z) { return ((size_t)x * n + (size_t)z) * n + (size_t)y; };
+    const auto at = [&](int x, int y, int z) { return vrt_grid::index(N, x, y, z); };
     const auto value = [&](int x, int y, int z) {
         const float d = voxels[at(x, y, z)].Density;
-        return R::clamped(texel16 ? d * 0.01f : d);
+        return R::clamped(vrt_grid::decode(d, texel16));
     };
     /* the surfels, kept per row (x, z) of the grown box with their y */
     struct Entry {
@@ -290,7 +291,7 @@ VVolumeConverter::VRedistanceResult VVolumeConverter::Redistance(Voxel::VVoxel* 
                 const bool is_out = R::outside(value(x, y, z));
                 const float D = R::banded(best, band);
                 const float m = R::signed_value(D, unit, is_out);
-                voxels[at(x, y, z)].Density = texel16 ? vrt_fill::texel16_value(m) : m;
+                voxels[at(x, y, z)].Density = texel16 ? vrt_grid::texel16_value(m) : m;
                 out.Written++;
                 if (D < (float)band) out.Near++;
             }
@@ -318,11 +319,11 @@ VVolumeConverter::VSurfaceMesh VVolumeConverter::ExtractMesh(const Voxel::VVoxel
     out.Lo = VIntVector(N, N, N);
     out.Hi = VIntVector(-1, -1, -1);
     if (cells[0] < 1 || cells[1] < 1 || cells[2] < 1) return out;
-    const auto at = [&](int x, int y, int z) { return ((size_t)x * n + (size_t)z) * n + (size_t)y; };
+    const auto at = [&](int x, int y, int z) { return vrt_grid::index(N, x, y, z); };
     const auto corners = [&](const int c[3], float f[8]) {
         for (int j = 0; j < 8; j++) {
             const float d = voxels[at(c[0] + (j & 1), c[1] + ((j >> 1) & 1), c[2] + (j >> 2))].Density;
-            f[j] = M::field(texel16 ? d * 0.01f : d, iso);
+            f[j] = M::field(vrt_grid::decode(d, texel16), iso);
         }
     };
     /* first pass, in the order of the cells' keys: the vertices, and every active cell's number */
@@ -387,7 +388,7 @@ VVolumeConverter::VStampResult VVolumeConverter::Stamp(Voxel::VVoxel* dst, size_
     int lo[3], hi[3];
     if (!S::valid(stamp) || !S::footprint(stamp, Ns, N, lo, hi)) return out;
     const S::Rule R = S::rule_of(stamp, Ns, unitDst, unitSrc);
-    const auto source_at = [&](int x, int y, int z) { return ((size_t)x * ns + (size_t)z) * ns + (size_t)y; };
+    const auto source_at = [&](int x, int y, int z) { return vrt_grid::index(Ns, x, y, z); };
     for (int x = lo[0]; x <= hi[0]; x++)
         for (int z = lo[2]; z <= hi[2]; z++)
             for (int y = lo[1]; y <= hi[1]; y++) {
@@ -399,14 +400,14 @@ VVolumeConverter::VStampResult VVolumeConverter::Stamp(Voxel::VVoxel* dst, size_
                 float s[8];
                 for (int j = 0; j < 8; j++) {
                     const float raw = src[source_at(c[0] + (j & 1), c[1] + ((j >> 1) & 1), c[2] + (j >> 2))].Density;
-                    s[j] = srcTexel16 ? raw * 0.01f : raw;
+                    s[j] = vrt_grid::decode(raw, srcTexel16);
                 }
                 Voxel::VVoxel& voxel = dst[((size_t)x * nd + (size_t)z) * nd + (size_t)y];
-                const float d = dstTexel16 ? voxel.Density * 0.01f : voxel.Density;
+                const float d = vrt_grid::decode(voxel.Density, dstTexel16);
                 const float v = S::value(S::trilinear(s, f[0], f[1], f[2]), R.gain, R.off);
                 float m;
                 if (!S::merge(R.op, d, v, R.k, R.rv, m)) continue;
-                voxel.Density = dstTexel16 ? vrt_fill::texel16_value(m) : m;
+                voxel.Density = dstTexel16 ? vrt_grid::texel16_value(m) : m;
                 if (R.material != VRT_STAMP_MATERIAL_KEEP) {
                     unsigned id = 0u;
                     if (R.material == VRT_STAMP_MATERIAL_SOURCE) id = src[source_at(S::nearest(c[0], f[0]), S::nearest(c[1], f[1]), S::nearest(c[2], f[2]))].Material;
@@ -440,14 +441,14 @@ VVolumeConverter::VStampResult VVolumeConverter::Smooth(Voxel::VVoxel* voxels, s
     const size_t count = (size_t)nx * nz * ny;
     const auto at = [&](int x, int y, int z) { return ((size_t)x * nz + (size_t)z) * ny + (size_t)y; }; /* box coordinates */
     const auto voxel_at = [&](int x, int y, int z) -> Voxel::VVoxel& {
-        return voxels[((size_t)(wlo[0] + x) * n + (size_t)(wlo[2] + z)) * n + (size_t)(wlo[1] + y)];
+        return voxels[vrt_grid::index(N, wlo[0] + x, wlo[1] + y, wlo[2] + z)];
     };
     std::vector<float> copy[2] = {std::vector<float>(count), std::vector<float>(count)}, weights(count);
     for (int x = 0; x < nx; x++)
         for (int z = 0; z < nz; z++)
             for (int y = 0; y < ny; y++) {
                 const int gx = wlo[0] + x, gy = wlo[1] + y, gz = wlo[2] + z;
-                copy[0][at(x, y, z)] = S::decode(voxel_at(x, y, z).Density, texel16);
+                copy[0][at(x, y, z)] = vrt_grid::decode(voxel_at(x, y, z).Density, texel16);
                 const bool boxed = gx >= lo[0] && gx <= hi[0] && gy >= lo[1] && gy <= hi[1] && gz >= lo[2] && gz <= hi[2];
                 weights[at(x, y, z)] = boxed ? S::weight(smooth, (float)gx, (float)gy, (float)gz) : S::kOutside;
             }

@@ -13,7 +13,7 @@
 #include <math.h>
 #include <stdint.h>
 
-#include "fill_core.h" /* VRT_HD */
+#include "grid_core.h"
 
 namespace vrt_mesh {
 

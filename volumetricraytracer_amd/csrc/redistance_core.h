@@ -12,7 +12,7 @@
 #include <math.h>
 #include <stdint.h>
 
-#include "fill_core.h" /* VRT_HD, texel16_value */
+#include "grid_core.h"
 
 namespace vrt_redist {
 

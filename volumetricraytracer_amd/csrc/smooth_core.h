@@ -17,7 +17,7 @@
 
 #include "../../include/vrt.h"
 #include "brush_core.h"
-#include "fill_core.h" /* VRT_HD, texel16_value */
+#include "grid_core.h"
 
 namespace vrt_smooth_core {
 
@@ -30,8 +30,7 @@ VRT_HD float weight(const vrt_smooth& r, float px, float py, float pz) {
 }
 VRT_HD bool in_region(float w) { return w >= 0.0f; }
 
-/* Step 2. */
-VRT_HD float decode(float stored, bool texel16) { return texel16 ? stored * 0.01f : stored; }
+/* Step 2 is grid_core.h's decode. */
 
 /* Step 3: one region sample through one pass; the six neighbours as the pass's input holds them (beyond the grid: f itself). */
 VRT_HD float relax(float f, float xm, float xp, float ym, float yp, float zm, float zp, float u) {
@@ -46,7 +45,7 @@ VRT_HD float pass_weight(const vrt_smooth& r, int p, float w) { return (r.reboun
 
 /* Step 5: the value a region sample would store and whether it is written — never a NaN, and only bits that differ. */
 VRT_HD bool stores(float m, float stored, bool texel16, float& value) {
-    value = texel16 ? vrt_fill::texel16_value(m) : m;
+    value = texel16 ? vrt_grid::texel16_value(m) : m;
     uint32_t a, b;
     memcpy(&a, &value, sizeof a);
     memcpy(&b, &stored, sizeof b);

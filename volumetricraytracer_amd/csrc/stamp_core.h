@@ -16,7 +16,7 @@
 #include <cmath>
 
 #include "../../include/vrt.h"
-#include "fill_core.h" /* VRT_HD, texel16_value */
+#include "grid_core.h"
 
 namespace vrt_stamp_core {
 
@@ -61,19 +61,10 @@ VRT_HD bool merge(int op, float d, float v, float k, float rv, float& m) {
         return v == v;
     }
     if (op == VRT_STAMP_ADD) {
-        m = fminf(d, v);
-        if (k > 0.0f) {
-            const float g = fmaxf(k - fabsf(d - v), 0.0f) / k;
-            m = m - ((g * g) * k) * 0.25f;
-        }
+        m = vrt_grid::union_blend(d, v, k);
         return v < rv && m < d;
     }
-    const float c = -v;
-    m = fmaxf(d, c);
-    if (k > 0.0f) {
-        const float g = fmaxf(k - fabsf(d - c), 0.0f) / k;
-        m = m + ((g * g) * k) * 0.25f;
-    }
+    m = vrt_grid::subtract_blend(d, v, k);
     return v < rv && m > d;
 }
 

@@ -1,6 +1,6 @@
 /*
  * voxelize_core.h — the arithmetic of the Voxelizer's hot loop, once, for both builds of it:
- * the CPU converter (csrc/host/VolumeConverter.cpp, g++) and the HIP kernel (vrt_kernels.hip, hipcc).
+ * the CPU converter (csrc/host/VolumeConverter.cpp, g++) and the HIP kernel (vrt_volume.hip, hipcc).
  *
  * Restates Voxelizer/Private/VolumeConverter.cpp:161-252 (VoxelizeFace), :681-701 (triangle bounding box →
  * voxel index box) and :703-781 (the 7-region point/triangle classification) of the reference.  Plain
@@ -14,11 +14,7 @@
 #include <math.h>
 #include <stdint.h>
 
-#if defined(__HIPCC__)
-#define VRT_HD __host__ __device__ inline
-#else
-#define VRT_HD inline
-#endif
+#include "grid_core.h" /* VRT_HD */
 
 namespace vrt_vox {
 

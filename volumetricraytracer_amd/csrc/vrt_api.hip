@@ -25,6 +25,7 @@
 #include "../../include/vrt.h"
 #include "vrt_device.h"
 #include "vrt_launch.h"
+#include "grid_core.h"
 #include "voxelize_core.h"
 #include "redistance_core.h"
 #include "stamp_core.h"
@@ -1985,7 +1986,7 @@ int vrt_volume_download(vrt_ctx* ctx, int slot, vrt_voxel* out) {
     const bool t16 = ctx->vol[slot].format == VRT_FORMAT_TEXEL16; /* integer field +-q: decode like DecodeDensity */
     for (size_t i = 0; i < count; i++) {
         out[i].material = mat[i];
-        out[i].density = t16 ? den[i] * 0.01f : den[i];
+        out[i].density = vrt_grid::decode(den[i], t16);
     }
     return VRT_OK;
 }

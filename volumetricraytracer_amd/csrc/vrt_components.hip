@@ -18,6 +18,7 @@
 #include <algorithm>
 
 #include "components_core.h"
+#include "fill_core.h" /* the 8^3 tiles and their row bytes */
 #include "edit_report.h"
 #include "vrt_launch.h"
 
@@ -84,7 +85,7 @@ __global__ __launch_bounds__(64) void components_local_kernel(const float* __res
         mine[k] = kPassable;
         if (inside && y0 + k < N) {
             const float s = dense[base + k];
-            if (solid(texel16 ? s * 0.01f : s)) mine[k] = base + k, solid_mask |= 1u << k;
+            if (solid(vrt_grid::decode(s, texel16))) mine[k] = base + k, solid_mask |= 1u << k;
         }
     }
     if (__any(solid_mask != 0u)) {
@@ -277,13 +278,13 @@ __global__ __launch_bounds__(256) void components_apply_kernel(float* __restrict
         const unsigned own = lab[i];
         if (label_solid(own) && label_kept(own)) continue;
         const float stored = dense[i];
-        const float d = TEXEL16 ? stored * 0.01f : stored;
+        const float d = vrt_grid::decode(stored, TEXEL16);
         const int y = (int)(i % sz);
         const size_t row = i / sz;
         const int x = (int)(row / sz), z = (int)(row % sz);
         if (label_solid(own)) {
             const float m = removed_density(d, gap);
-            dense[i] = TEXEL16 ? vrt_fill::texel16_value(m) : m;
+            dense[i] = TEXEL16 ? vrt_grid::texel16_value(m) : m;
             if (material_id >= 0) material[i] = (uint8_t)material_id;
             report.add(N, x, y, z, true);
             continue;
@@ -300,7 +301,7 @@ __global__ __launch_bounds__(256) void components_apply_kernel(float* __restrict
         look(z > 0, i - sz), look(z + 1 < N, i + sz);
         look(x > 0, i - sx), look(x + 1 < N, i + sx);
         if (!removed || kept) continue;
-        const float value = TEXEL16 ? vrt_fill::texel16_value(gap) : gap;
+        const float value = TEXEL16 ? vrt_grid::texel16_value(gap) : gap;
         if (__float_as_uint(value) == __float_as_uint(stored)) continue;
         dense[i] = value;
         report.add(N, x, y, z, true);

@@ -40,7 +40,7 @@ __global__ __launch_bounds__(256) void fill_mask_kernel(const float* __restrict_
             const int y = t * kTile + k;
             if (y >= N) break;
             const float s = dense[row * N + y];
-            p |= vrt_fill::passable(texel16 ? s * 0.01f : s) ? 1u << k : 0u;
+            p |= vrt_fill::passable(vrt_grid::decode(s, texel16)) ? 1u << k : 0u;
         }
         unsigned face = 0xffu;
         if (x > 0 && x < N - 1 && z > 0 && z < N - 1) face = (t == 0 ? 1u : 0u) | (t == (N - 1) / kTile ? 1u << ((N - 1) % kTile) : 0u);
@@ -116,8 +116,8 @@ __global__ __launch_bounds__(256) void fill_apply_kernel(float* __restrict__ den
         if ((((unsigned)pas[at] & ~(unsigned)lab[at]) >> (y % kTile) & 1u) == 0u) continue;
         const int x = (int)(row / (size_t)N), z = (int)(row % (size_t)N);
         const float stored = dense[i];
-        const float m = vrt_fill::filled_density(TEXEL16 ? stored * 0.01f : stored, wall);
-        dense[i] = TEXEL16 ? vrt_fill::texel16_value(m) : m;
+        const float m = vrt_fill::filled_density(vrt_grid::decode(stored, TEXEL16), wall);
+        dense[i] = TEXEL16 ? vrt_grid::texel16_value(m) : m;
         if (material_id >= 0) material[i] = (uint8_t)material_id;
         report.add(N, x, y, z, true); /* every write is a density write */
     }

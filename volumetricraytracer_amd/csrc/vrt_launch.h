@@ -1,4 +1,6 @@
-/* vrt_launch.h — host-callable launch wrappers implemented in vrt_kernels.hip. */
+/* vrt_launch.h — host-callable launch wrappers: the march and the ray queries (vrt_kernels.hip), what a slot derives from its dense grid
+   (vrt_volume.hip) and one file per edit call (vrt_brush.hip, vrt_fill.hip, vrt_redistance.hip, vrt_stamp.hip, vrt_smooth.hip,
+   vrt_components.hip, vrt_mesh.hip). */
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stddef.h>
@@ -51,6 +53,16 @@ struct EditBox {
     int lo[3];
     int n[3];
 };
+__host__ __device__ inline size_t box_count(const EditBox& b) { return (size_t)b.n[0] * b.n[1] * b.n[2]; }
+/* local index (x slowest, then z, then y) -> global coordinates */
+__host__ __device__ inline void box_coords(const EditBox& b, size_t i, int& x, int& z, int& y) {
+    y = b.lo[2] + (int)(i % (size_t)b.n[2]);
+    z = b.lo[1] + (int)((i / (size_t)b.n[2]) % (size_t)b.n[1]);
+    x = b.lo[0] + (int)(i / ((size_t)b.n[1] * b.n[2]));
+}
+__host__ __device__ inline size_t box_index(const EditBox& b, int x, int z, int y) {
+    return ((size_t)(x - b.lo[0]) * b.n[1] + (size_t)(z - b.lo[1])) * b.n[2] + (size_t)(y - b.lo[2]);
+}
 /* The staged box (VVoxel records, or floats followed by bytes when has_material; x slowest, then z, then y) -> dense + material,
    quantised like launch_quantize_field when texel16. */
 hipError_t launch_scatter_region(const void* staging, bool voxels, bool has_material, bool texel16, float* dense, uint8_t* material, int N,
@@ -104,7 +116,7 @@ struct DBrushSlot {
    written samples' counts and box (the edit report, above). */
 hipError_t launch_brush_region(const DBrushList& list, bool texel16, float* dense, uint8_t* material, int N, const EditBox& box,
                                DBrushSlot* slots, hipStream_t stream);
-/* vrt_volume_download_region: the samples of `box` as VVoxel records (x slowest, then z, then y), a TEXEL16 field decoded (* 0.01f). */
+/* vrt_volume_download_region: the samples of `box` as VVoxel records (x slowest, then z, then y), a TEXEL16 field decoded. */
 hipError_t launch_gather_region(const float* dense, const uint8_t* material, bool texel16, int N, const EditBox& box, void* voxels_out,
                                 hipStream_t stream);
 

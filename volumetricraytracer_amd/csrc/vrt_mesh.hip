@@ -47,12 +47,12 @@ __device__ __forceinline__ bool cell_of(const MeshGrid& G, unsigned r, int lane,
 /* The eight corner values of cell c; every corner of a cell of the cell box is a sample of the grid. */
 template <bool TEXEL16>
 __device__ __forceinline__ void load_corners(const float* __restrict__ dense, int N, const int c[3], float iso, float f[8]) {
-    const size_t i0 = ((size_t)c[0] * N + c[2]) * N + c[1];
+    const size_t i0 = vrt_grid::index(N, c[0], c[1], c[2]);
 #pragma unroll
     for (int j = 0; j < 8; j++) {
         const size_t i = i0 + (size_t)(j & 1) * N * N + (size_t)((j >> 1) & 1) + (size_t)(j >> 2) * N;
         const float s = dense[i];
-        f[j] = vrt_mesh::field(TEXEL16 ? s * 0.01f : s, iso);
+        f[j] = vrt_mesh::field(vrt_grid::decode(s, TEXEL16), iso);
     }
 }
 

@@ -32,7 +32,7 @@ struct TileRange {
 
 __device__ __forceinline__ float decoded(const float* __restrict__ dense, size_t i, bool texel16) {
     const float s = dense[i];
-    return vrt_redist::clamped(texel16 ? s * 0.01f : s);
+    return vrt_redist::clamped(vrt_grid::decode(s, texel16));
 }
 
 /* One wave per tile; lane = (z, y) of the tile, looping over x.  A sample of the grown box g (grid order {x, z, y}, inclusive) that has
@@ -59,7 +59,7 @@ __global__ __launch_bounds__(64) void redist_surfel_kernel(const float* __restri
         bool is_surfel = false;
         vrt_redist::Surfel s;
         if (row_in && x >= g.lo[0] && x < g.lo[0] + g.n[0]) { /* the grown box is clipped to the grid */
-            const size_t i = ((size_t)x * N + z) * N + y;
+            const size_t i = vrt_grid::index(N, x, y, z);
             const float e = decoded(dense, i, texel16);
             const bool out = vrt_redist::outside(e);
             /* xyz order: x, y, z */
@@ -137,10 +137,10 @@ __global__ __launch_bounds__(256) void redist_distance_kernel(float* __restrict_
     const int y = ty * kTile + (tid & 7), z = tz * kTile + ((tid >> 3) & 7), x0 = tx * kTile + (tid >> 6), x1 = x0 + 4;
     const bool row_in = z >= b.lo[1] && z < b.lo[1] + b.n[1] && y >= b.lo[2] && y < b.lo[2] + b.n[2];
     const bool in0 = row_in && x0 >= b.lo[0] && x0 < b.lo[0] + b.n[0], in1 = row_in && x1 >= b.lo[0] && x1 < b.lo[0] + b.n[0];
-    const size_t i0 = ((size_t)x0 * N + z) * N + y, i1 = ((size_t)x1 * N + z) * N + y;
+    const size_t i0 = vrt_grid::index(N, x0, y, z), i1 = vrt_grid::index(N, x1, y, z);
     bool out0 = false, out1 = false; /* the class, read before anything is stored */
-    if (in0) out0 = vrt_redist::outside(vrt_redist::clamped(TEXEL16 ? dense[i0] * 0.01f : dense[i0]));
-    if (in1) out1 = vrt_redist::outside(vrt_redist::clamped(TEXEL16 ? dense[i1] * 0.01f : dense[i1]));
+    if (in0) out0 = vrt_redist::outside(vrt_redist::clamped(vrt_grid::decode(dense[i0], TEXEL16)));
+    if (in1) out1 = vrt_redist::outside(vrt_redist::clamped(vrt_grid::decode(dense[i1], TEXEL16)));
     const float px0 = (float)x0, px1 = (float)x1, py = (float)y, pz = (float)z;
     float best0 = INFINITY, best1 = INFINITY;
 
@@ -170,7 +170,7 @@ __global__ __launch_bounds__(256) void redist_distance_kernel(float* __restrict_
     const auto store = [&](size_t i, int x, float best, bool is_out) {
         const float D = vrt_redist::banded(best, band);
         const float m = vrt_redist::signed_value(D, unit, is_out);
-        dense[i] = TEXEL16 ? vrt_fill::texel16_value(m) : m;
+        dense[i] = TEXEL16 ? vrt_grid::texel16_value(m) : m;
         report.add(N, x, y, z, D < (float)band); /* high half: the near samples */
     };
     if (in0) store(i0, x0, best0, out0);

@@ -36,7 +36,7 @@ __global__ __launch_bounds__(256) void smooth_gather_kernel(vrt_smooth R, const 
     const unsigned ny = (unsigned)work.n[2], nz = (unsigned)work.n[1];
     const unsigned row = i / ny, sx = row / nz;
     const int x = work.lo[0] + (int)sx, z = work.lo[1] + (int)(row - sx * nz), y = work.lo[2] + (int)(i - row * ny);
-    field[i] = S::decode(dense[((size_t)x * N + z) * N + y], TEXEL16);
+    field[i] = vrt_grid::decode(dense[vrt_grid::index(N, x, y, z)], TEXEL16);
     const bool boxed = x >= region.lo[0] && x < region.lo[0] + region.n[0] && z >= region.lo[1] && z < region.lo[1] + region.n[1] &&
                        y >= region.lo[2] && y < region.lo[2] + region.n[2];
     weights[i] = boxed ? S::weight(R, (float)x, (float)y, (float)z) : S::kOutside;
@@ -90,7 +90,7 @@ __global__ __launch_bounds__(256) void smooth_apply_kernel(int material_id, cons
         const unsigned ny = (unsigned)work.n[2], nz = (unsigned)work.n[1];
         const unsigned row = i / ny, sx = row / nz;
         const int x = work.lo[0] + (int)sx, z = work.lo[1] + (int)(row - sx * nz), y = work.lo[2] + (int)(i - row * ny);
-        const size_t g = ((size_t)x * N + z) * N + y;
+        const size_t g = vrt_grid::index(N, x, y, z);
         const float m = field[i];
         float value;
         if (S::stores(m, dense[g], TEXEL16, value)) {
@@ -101,8 +101,6 @@ __global__ __launch_bounds__(256) void smooth_apply_kernel(int material_id, cons
     }
     report.commit(slots, blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6));
 }
-
-size_t box_count(const EditBox& b) { return (size_t)b.n[0] * b.n[1] * b.n[2]; }
 
 }  // namespace
 

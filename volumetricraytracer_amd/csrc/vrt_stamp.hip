@@ -42,24 +42,24 @@ __global__ __launch_bounds__(256) void stamp_region_kernel(vrt_stamp_core::Rule 
             const int cx = S::cell_of(ux, ns), cy = S::cell_of(uy, ns), cz = S::cell_of(uz, ns);
             const float fx = ux - (float)cx, fy = uy - (float)cy, fz = uz - (float)cz;
             /* the source's grid is [x][z][y] like every dense grid: 0 <= c <= ns - 2 on every axis, so all eight taps lie inside it */
-            const size_t at = ((size_t)cx * ns + (size_t)cz) * ns + (size_t)cy;
+            const size_t at = vrt_grid::index(ns, cx, cy, cz);
             const size_t tx = (size_t)ns * ns, tz = (size_t)ns;
             float s[8];
 #pragma unroll
             for (int j = 0; j < 8; j++) {
                 const float raw = src[at + (j & 1 ? tx : 0) + (j & 2 ? 1 : 0) + (j & 4 ? tz : 0)];
-                s[j] = SRC16 ? raw * 0.01f : raw;
+                s[j] = vrt_grid::decode(raw, SRC16);
             }
-            const size_t g = ((size_t)x * N + z) * N + y;
+            const size_t g = vrt_grid::index(N, x, y, z);
             const float stored = dense[g];
-            const float d = DST16 ? stored * 0.01f : stored;
+            const float d = vrt_grid::decode(stored, DST16);
             const float v = S::value(S::trilinear(s, fx, fy, fz), R.gain, R.off);
             float m;
             if (!S::merge(R.op, d, v, R.k, R.rv, m)) continue;
-            dense[g] = DST16 ? vrt_fill::texel16_value(m) : m;
+            dense[g] = DST16 ? vrt_grid::texel16_value(m) : m;
             if (R.material != VRT_STAMP_MATERIAL_KEEP) {
                 unsigned id = 0u;
-                if (R.material == VRT_STAMP_MATERIAL_SOURCE)
+                if (R.material == VRT_STAMP_MATERIAL_SOURCE) /* grid_core.h's index, the nearest sample of each axis found where it is used */
                     id = src_material[((size_t)S::nearest(cx, fx) * ns + (size_t)S::nearest(cz, fz)) * ns + (size_t)S::nearest(cy, fy)];
                 material[g] = (uint8_t)S::written_material(R.op, R.material, m, id);
             }

@@ -119,7 +119,7 @@ def texel16_q(density) -> np.ndarray:
     q = trunc(a), except 0xffffffff when a >= 4294967040 (the largest fp32 below 2^32, +-inf included) and 0 when d is NaN;
     then q &= 0x7fff.  The texel's sign is d < 0, so a small negative density keeps it (-0.0) while NaN does not.  The
     reference's own (uint16_t)(abs(d) * 100.f) leaves out-of-range values undefined; this is the rule of the device quantiser
-    (texel16_value, vrt_kernels.hip, and vrt_set_volume_format in vrt.h), which every encoder here follows."""
+    (texel16_value, csrc/grid_core.h, and vrt_set_volume_format in vrt.h), which every encoder here follows."""
     d = np.asarray(density, dtype=np.float32)
     with np.errstate(over="ignore", invalid="ignore"):  # inf / NaN in, by design
         a = np.abs(d) * np.float32(100.0)
