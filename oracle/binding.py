@@ -100,6 +100,8 @@ def load() -> C.CDLL:
                                                 C.POINTER(vrto_literal_stats), C.c_int]
         lib.vrto_literal_octree_info.restype = C.c_int
         lib.vrto_literal_octree_info.argtypes = [C.POINTER(vrto_volume), C.POINTER(vrto_octree_info)]
+        lib.vrto_literal_octree_leaves.restype = C.c_int64
+        lib.vrto_literal_octree_leaves.argtypes = [C.POINTER(vrto_volume), C.c_void_p, C.c_int64]
         lib.vrto_debug_tables.restype = C.c_int
         lib.vrto_debug_tables.argtypes = [C.POINTER(vrto_volume), C.c_void_p, C.c_void_p, C.c_void_p]
         lib.vrto_debug_cube_table.restype = C.c_int
@@ -193,6 +195,15 @@ class OracleScene:
             raise RuntimeError(f"vrto_literal_octree_info failed: {rc}")
         return {"nodes": info.nodes, "leaves_at_depth": list(info.leaves_at_depth), "texture_edge": info.texture_edge,
                 "pointer_overflow": bool(info.pointer_overflow)}
+
+    def octree_leaves(self, slot: int) -> np.ndarray:
+        """int32 [L, 4]: (x, y, z of the first cell, depth) of every leaf of that octree, as the literal restatement holds it."""
+        n = load().vrto_literal_octree_leaves(C.byref(self.vols[slot]), None, 0)
+        if n < 0:
+            raise RuntimeError(f"vrto_literal_octree_leaves failed: {n}")
+        out = np.empty((n, 4), np.int32)
+        load().vrto_literal_octree_leaves(C.byref(self.vols[slot]), out.ctypes.data, n)
+        return out
 
     def trace(self, params: _abi.vrt_params, origin, direction, t_max: float = 10000.0):
         lib = load()

@@ -1900,4 +1900,26 @@ int vrto_literal_octree_info(const vrto_volume* vol, vrto_octree_info* out) {
     return VRT_OK;
 }
 
+/* Straight from build_literal's per-cell leaf depth: a leaf of depth d is named once, by the cell whose low (r - d) index bits
+   are all zero — its first cell, the CellIndex the reference's GPU node carries. */
+int64_t vrto_literal_octree_leaves(const vrto_volume* vol, int32_t* leaves_out, int64_t capacity) {
+    if (!vol || !vol->density || vol->resolution < 0 || vol->resolution > 8) return VRT_ERR_INVALID;
+    const int r = vol->resolution, N = (1 << r) + 1, C = N - 1;
+    LitVolume L;
+    build_literal(vol->density, N, r, L);
+    int64_t n = 0;
+    for (int x = 0; x < C; x++)
+        for (int z = 0; z < C; z++)
+            for (int y = 0; y < C; y++) {
+                const int d = L.leaf_depth[((size_t)x * C + z) * C + y], low = (1 << (r - d)) - 1;
+                if ((x & low) || (y & low) || (z & low)) continue;
+                if (leaves_out && n < capacity) {
+                    int32_t* o = leaves_out + 4 * n;
+                    o[0] = x, o[1] = y, o[2] = z, o[3] = d;
+                }
+                n++;
+            }
+    return n;
+}
+
 }  // extern "C"

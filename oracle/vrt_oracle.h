@@ -141,6 +141,10 @@ typedef struct vrto_octree_info {
     int32_t pointer_overflow;    /* 1: a child-block coordinate exceeds 255 and wraps in its 8-bit pointer texel (RDXVoxelVolume.cpp:282-284) */
 } vrto_octree_info;
 int vrto_literal_octree_info(const vrto_volume* vol, vrto_octree_info* out);
+/* The leaves of that tree, as the literal restatement holds it: 4 int32 per leaf {x, y, z of its first cell, depth}, in no
+ * particular order.  Returns the number of leaves (writes at most `capacity` of them; leaves_out may be NULL to count), or a
+ * negative error.  Unlike vrto_literal_octree_info it also takes resolution 0 (one cell, one leaf). */
+int64_t vrto_literal_octree_leaves(const vrto_volume* vol, int32_t* leaves_out, int64_t capacity);
 
 /* Debug: the two-level empty-space table the march uses for `vol` under its metric (step_max > 0) — skip_out: nb^3
  * Chebyshev brick distances D, nib_out: nb^3 words of sub-block nibbles — and (field_out, N^3 floats) the field the march
