@@ -24,6 +24,9 @@
  *                                   volumes: CSG of one resident volume, placed by a matrix, into another)
  *   vrt_volume_smooth               (no reference analogue beyond VVoxelVolume::SetVoxel, VoxelVolume.cpp:59-77, in a host loop: the
  *                                   relaxing brush — a weighted 7-point stencil inside a sphere / box / capsule region)
+ *   vrt_volume_warp                 (no reference analogue beyond VVoxelVolume::SetVoxel, VoxelVolume.cpp:59-77, in a host loop: grab,
+ *                                   twist, scale and inflate — inside a sphere / box / capsule region every sample takes its value from
+ *                                   elsewhere in the same volume)
  *   vrt_volume_fill_enclosed        (no reference analogue: its Voxelizer stops at the unsigned shell, Voxelizer/Private/VolumeConverter.cpp:30-84 —
  *                                   the shell of a closed mesh made solid on the resident volume, so that a SUBTRACT brush carves a solid)
  *   vrt_volume_components           (no reference analogue beyond VVoxelVolume::SetVoxel, VoxelVolume.cpp:59-77, in a host loop: the
@@ -513,6 +516,78 @@ typedef struct vrt_smooth {           /* 64 B */
  * plain iterations, the surface having retreated by 0.033 cells on average, and 0.056 after eight iterations with rebound 1, the
  * surface within 0.001 cells of where it was (eight plain iterations: a retreat of 0.131 cells).  DESIGN.md section 2 has the table. */
 int vrt_volume_smooth(vrt_ctx* ctx, int slot, const vrt_smooth* smooth, vrt_brush_result* result_or_null);
+
+/* The moving sculpt tools (no reference analogue beyond VVoxelVolume::SetVoxel in a host loop): grab (pull a region along), twist,
+ * pinch / scale and inflate.  All four are one operation: inside a brush shape with a soft edge every sample takes its new value from
+ * somewhere else in the same volume — the place an affine motion, faded out by the region's weight, brings it from — plus an optional
+ * offset.  Like the smooth brush it cannot work in place: every read sees the volume as it was before the call. */
+#define VRT_WARP_MATERIAL_KEEP   (-1) /* leave material ids alone */
+#define VRT_WARP_MATERIAL_SOURCE (-2) /* take the id of the nearest source sample */
+typedef struct vrt_warp {             /* 128 B */
+    int32_t shape;                    /* VRT_BRUSH_SPHERE / _BOX / _CAPSULE: the region, as vrt_brush */
+    int32_t material;                 /* 0..255, VRT_WARP_MATERIAL_KEEP or VRT_WARP_MATERIAL_SOURCE */
+    float a[3], b[3], radius;         /* as vrt_brush: cells, grid coordinates */
+    float strength;                   /* 0 < strength <= 1 */
+    float falloff;                    /* > 0, cells: the weight rises from 0 at the brush surface to strength at falloff cells inside */
+    float pull[12];                   /* row-major 3x4, grid coordinates (x, y, z): where a sample at full weight takes its value FROM */
+    float length_scale;               /* > 0: how lengths grow under the full motion (1 for a rigid motion; k for a scale by k) */
+    float inflate;                    /* cells: at full weight the shape grows (> 0) or shrinks (< 0) by it */
+    uint32_t reserved_[7];            /* 0 */
+} vrt_warp;
+
+/* Warps the resident slot inside the record's shape, in place, on every device.  Waits for work already enqueued on the context's
+ * devices (a frame begun before the call renders the old volume, one begun after renders the new one); device pointers of the slot do
+ * not change.  Afterwards every device buffer of the slot equals what a full upload of the edited volume holds (what the slot derives
+ * from its samples is rebuilt over the written box; nothing is rebuilt when no density changed), so frames and counters are those of
+ * the full upload.  A launch captured into a graph before the edit keeps the cull rectangle it was captured with (capture with
+ * VRT_FLAG_NO_CULL_RECT where an edit may grow the active box).
+ * The caller passes the matrix itself, not a pivot / rotation / scale, so that no trigonometry sits inside the contract; the adaptors
+ * build it from a motion (VHipRenderer::WarpFromMotion, warp_from_motion).
+ * Errors, all checked before any device state is touched: VRT_ERR_INVALID for a NULL context or record; an unknown shape; a
+ * non-finite field; strength outside (0, 1]; falloff <= 0; length_scale <= 0; the shape rules of vrt_volume_apply_brushes (a radius or
+ * half size that is not positive, a negative rounding radius, a capsule with a == b; a sphere's b is only checked for being finite); a
+ * material outside -2..255; non-zero reserved words.  pull need only be finite: a singular matrix is allowed, it flattens.
+ * VRT_ERR_SLOT for an unused slot.  VRT_ERR_OOM when the scratch memory (one float and one byte per sample of the region's box) cannot
+ * be allocated: it is allocated on every device before any sample is written, so the volume is untouched then.  A region that lies
+ * wholly outside the grid is VRT_OK and writes nothing (lo > hi).
+ * result_or_null: the written samples' count and box, from device 0 (all devices compute the same bytes).
+ *
+ * The rule is part of the contract.  All arithmetic is fp32, evaluated as parenthesised, no fused multiply-add; sqrtf and / are
+ * correctly rounded.  p = ((float)ix, (float)iy, (float)iz).
+ *   1. Region and weight.  s is the brush distance of the sample, exactly as at vrt_volume_apply_brushes (Sphere, Capsule, Box).
+ *      A sample is IN THE REGION iff s < 0.  t = fminf((-s) / falloff, 1.0f); h = (t*t) * (3.0f - (2.0f*t)) — a smoothstep, exactly 1
+ *      at t = 1; w = strength * h.
+ *   2. Source coordinate, per axis a.  U_a = ((pull[a][0]*p.x + pull[a][1]*p.y) + pull[a][2]*p.z) + pull[a][3];
+ *      r_a = p_a + (w * (U_a - p_a)); u_a = fminf(fmaxf(r_a, 0.0f), (float)(N-1)).  A NaN becomes 0 by fmaxf; a source beyond the grid
+ *      is the grid's face (clamp to edge).
+ *   3. Cell, fraction, decode, trilinear: steps 2 to 4 of vrt_volume_stamp with Ns = N, on this slot's own samples.
+ *      i_a = min(max((int)floorf(u_a), 0), N-2); f_a = u_a - (float)i_a; the eight corners decoded as for the brushes; every lerp is
+ *      (s0 * (1.0f - f)) + (s1 * f), on x, then y, then z.  Result T.
+ *   4. Value.  g = 1.0f + (w * (length_scale - 1.0f)).  off = inflate * unit with unit = cell / density_scale as for the brushes,
+ *      computed once on the host; wo = w * off.  m = (T * g) - wo.
+ *   5. Still samples.  A region sample with r_a == p_a on all three axes, g == 1.0f and wo == 0.0f keeps its bits and its id: an
+ *      identity motion writes nothing, also on a VRT_FORMAT_TEXEL16 slot (where decode + encode would move q = 5, 10, 15, 20, 23, ...
+ *      down by one).
+ *   6. Jacobi.  Every read of the call, densities and material ids alike, sees the volume as it was BEFORE the call: the result does
+ *      not depend on how the device schedules its work.
+ *   7. Write.  The value to store is m (F32) or the texel of m (TEXEL16: the rule at vrt_set_volume_format).  The new id is, with
+ *      material >= 0: m <= 0 ? material : 0; VRT_WARP_MATERIAL_KEEP: the old id; VRT_WARP_MATERIAL_SOURCE: the old id of the source
+ *      sample j_a = i_a + (f_a >= 0.5f ? 1 : 0).  A region sample that is not still and has m == m is written in density iff the
+ *      value to store differs IN BITS from the stored value, and in material iff the new id differs from the old one.  `written`
+ *      counts the samples written in either, and the box covers them.  NaN is never written; everything else keeps its bits.
+ * Choosing values.  pull is where things come FROM, so it is the inverse of the motion one sees: a grab by v is the identity with
+ * the translation -v; a twist or a scale about a pivot c is the inverse turn or 1/k about c (rows R^T / k, translation
+ * c - (R^T / k) c), with length_scale = k so that a distance field scaled by k stays one.  The map p -> r is one-to-one while
+ * strength * 1.5 / falloff * (the largest displacement |U - p| in the region) < 1: 1.5 is the smoothstep's steepest slope.  Beyond
+ * that the surface folds over itself near the region's edge; a larger falloff, or several calls with smaller motions, avoid it.
+ * Where w varies the result is not a distance field — the material is stretched there —, and vrt_volume_redistance over the written
+ * box grown by the band repairs it, as it does after a brush.  inflate assumes a field that is a distance near its surface.
+ * What the rule is worth: on 33^3, an analytic sphere SDF of 8 cells inside a ball region of 14 cells at falloff 2 and strength 1, the
+ * zero crossings (on grid edges) lie off the analytic moved sphere by an RMS (mean) radial error of 0.0270 (-0.0266) cells after a grab
+ * by (2.3, -1.1, 0.7), 0.0370 (-0.0367) after a grab by (0.5, 0.5, 0.5), 0.0305 (-0.0292) after a scale by 1.25 and
+ * 0.0049 (-0.0038) after an inflate by 1.5: the trilinear interpolant of a convex distance sags between samples, as under the
+ * stamp.  DESIGN.md section 2 has the table. */
+int vrt_volume_warp(vrt_ctx* ctx, int slot, const vrt_warp* warp, vrt_brush_result* result_or_null);
 
 /* Solid volumes from shells (no reference analogue: its Voxelizer stops at the shell).  vrt_voxelize_mesh and the CPU converter leave the
  * reference's UNSIGNED shell field, density = dist/thr - 0.5: inside a closed mesh the field is positive again, so a VRT_BRUSH_SUBTRACT dab

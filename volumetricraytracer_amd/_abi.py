@@ -78,6 +78,8 @@ STAMP_MATERIAL_KEEP, STAMP_MATERIAL_SOURCE = -1, -2
 
 # vrt_volume_smooth
 MAX_SMOOTH_ITERATIONS = 16
+# vrt_volume_warp
+WARP_MATERIAL_KEEP, WARP_MATERIAL_SOURCE = -1, -2
 
 # vrt_volume_components
 COMPONENTS_REPORT, COMPONENTS_KEEP_LARGEST, COMPONENTS_REMOVE_SMALL, COMPONENTS_KEEP_SEED, COMPONENTS_REMOVE_SEED = 0, 1, 2, 3, 4
@@ -262,6 +264,22 @@ class vrt_smooth(C.Structure):
     ]
 
 
+class vrt_warp(C.Structure):
+    _fields_ = [
+        ("shape", C.c_int32),
+        ("material", C.c_int32),
+        ("a", C.c_float * 3),
+        ("b", C.c_float * 3),
+        ("radius", C.c_float),
+        ("strength", C.c_float),
+        ("falloff", C.c_float),
+        ("pull", C.c_float * 12),
+        ("length_scale", C.c_float),
+        ("inflate", C.c_float),
+        ("reserved_", C.c_uint32 * 7),
+    ]
+
+
 class vrt_components(C.Structure):
     _fields_ = [
         ("op", C.c_int32),
@@ -345,6 +363,7 @@ SYMBOLS = {
     "vrt_volume_apply_brushes": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.POINTER(vrt_brush), C.POINTER(vrt_brush_result)]),
     "vrt_volume_stamp": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.POINTER(vrt_stamp), C.POINTER(vrt_brush_result)]),
     "vrt_volume_smooth": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(vrt_smooth), C.POINTER(vrt_brush_result)]),
+    "vrt_volume_warp": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(vrt_warp), C.POINTER(vrt_brush_result)]),
     "vrt_volume_components": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(vrt_components), C.POINTER(vrt_component), C.c_int,
                                         C.POINTER(vrt_components_result)]),
     "vrt_volume_fill_enclosed": (C.c_int, [C.c_void_p, C.c_int, C.c_float, C.c_int, C.POINTER(vrt_fill_result)]),

@@ -1,7 +1,7 @@
 /*
  * brush_core.h — what the analytic brush shapes of include/vrt.h (sphere, box, capsule) mean, once: the brush distance s for the
- * kernels of vrt_volume_apply_brushes (vrt_brush.hip) and of vrt_volume_smooth (vrt_smooth.hip) and for the host pass of the latter
- * (csrc/host/VolumeConverter.cpp, g++), and — host only — the argument rules of a vrt_brush and the box of samples it can write.
+ * kernels of vrt_volume_apply_brushes (vrt_brush.hip), of vrt_volume_smooth (vrt_smooth.hip) and of vrt_volume_warp (vrt_warp.hip) and
+ * for the host passes of the latter two (csrc/host/VolumeConverter.cpp, g++), and — host only — the argument rules of a vrt_brush and the box of samples it can write.
  *
  * Plain floats, every expression evaluated as parenthesised in vrt.h, no fused multiply-add on either side (both builds compile
  * without contraction; square root and division are correctly rounded): every build produces the same bits.
@@ -11,6 +11,7 @@
 
 #include <math.h>
 #include <stdint.h>
+#include <string.h>
 
 #include <algorithm>
 #include <cmath>
@@ -57,6 +58,19 @@ inline bool valid_brush(const vrt_brush& r) {
     if (r.material < -1 || r.material > 255) return false;
     if (r.op == VRT_BRUSH_PAINT) return r.material >= 0;
     return r.reach > 0.f && r.blend >= 0.f;
+}
+
+/* A region in the shape of a brush (any record with shape, a, b and radius as vrt_brush has them: vrt_smooth, vrt_warp) as the brush
+ * record whose shape it is: PAINT, so that brush_box adds no reach. */
+template <class Shape>
+inline vrt_brush region_brush(const Shape& r) {
+    vrt_brush b;
+    memset(&b, 0, sizeof b);
+    b.shape = r.shape;
+    b.op = VRT_BRUSH_PAINT;
+    for (int a = 0; a < 3; a++) b.a[a] = r.a[a], b.b[a] = r.b[a];
+    b.radius = r.radius;
+    return b;
 }
 
 /* The samples a record can write, xyz, inclusive: the shape's bounds grown by reach (PAINT: by nothing), by one sample and by the

@@ -1,5 +1,7 @@
 #include "HipRenderer.h"
 
+#include "../warp_core.h"
+
 #include <algorithm>
 
 #include <cmath>
@@ -821,6 +823,33 @@ bool VHipRenderer::SmoothVolume(const Scene::VVoxelObject& object, const vrt_smo
     if (result) *result = res;
     if (res.written == 0) return true;
     return MirrorBox(slot, *volume, res.lo, res.hi);
+}
+
+bool VHipRenderer::WarpVolume(const Scene::VVoxelObject& object, const vrt_warp& warp, vrt_brush_result* result) {
+    if (!IsActive()) {
+        V_LOG_WARNING("WarpVolume() on an inactive renderer");
+        return false;
+    }
+    const VObjectPtr<Scene::VScene> scene = SceneRef.lock();
+    const VObjectPtr<Voxel::VVoxelVolume> volume = object.GetVoxelVolume();
+    if (!scene || !volume) return false;
+    if (!SyncWithScene(*scene)) return false;
+    const int slot = SlotOf(volume.get());
+    if (slot < 0) {
+        V_LOG_ERROR("WarpVolume(): the object's volume is not part of the rendered scene");
+        return false;
+    }
+    vrt_brush_result res;
+    if (!ok(vrt_volume_warp(Ctx, slot, &warp, &res), "vrt_volume_warp")) return false;
+    if (result) *result = res;
+    if (res.written == 0) return true;
+    return MirrorBox(slot, *volume, res.lo, res.hi);
+}
+
+bool VHipRenderer::WarpFromMotion(const VVector& pivot, const VVector& translation, const VQuat& rotation, float scale, vrt_warp& rec) {
+    const double c[3] = {pivot.X, pivot.Y, pivot.Z}, t[3] = {translation.X, translation.Y, translation.Z};
+    const double q[4] = {rotation.x, rotation.y, rotation.z, rotation.w};
+    return vrt_warp_core::from_motion(c, t, q, (double)scale, rec.pull, rec.length_scale);
 }
 
 vrt_stamp VHipRenderer::StampFromPlacement(unsigned srcSize, const VVector& position, const VQuat& rotation, float scale, int op, int material,

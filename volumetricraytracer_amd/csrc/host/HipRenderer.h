@@ -126,6 +126,15 @@ public:
        is read back into the host VVoxelVolume like ApplyBrushes does.  False (after logging) on failure or when the object's volume is
        not in the scene. */
     bool SmoothVolume(const Scene::VVoxelObject& object, const vrt_smooth& smooth, vrt_brush_result* result = nullptr);
+    /* Grab, twist, scale and inflate on the device (vrt_volume_warp; the rule: vrt.h): inside the record's shape every sample of the
+       volume of a placed object of the scene Render() would draw now (synced first) takes its value from where the record's motion,
+       faded out by the region's weight, brings it from.  The written box is read back into the host VVoxelVolume like ApplyBrushes
+       does.  False (after logging) on failure or when the object's volume is not in the scene. */
+    bool WarpVolume(const Scene::VVoxelObject& object, const vrt_warp& warp, vrt_brush_result* result = nullptr);
+    /* pull and length_scale of `rec` from the motion one sees — a turn by `rotation` and a uniform scale about `pivot` (grid
+       coordinates of the volume, xyz), then a shift by `translation` (cells): the inverse motion, built in double and rounded once;
+       length_scale = scale.  The record's other fields stay.  False for a zero quaternion or a scale that is not positive. */
+    static bool WarpFromMotion(const VVector& pivot, const VVector& translation, const VQuat& rotation, float scale, vrt_warp& rec);
     /* CSG with an arbitrary shape on the device (vrt_volume_stamp; the rule: vrt.h): srcVolume — any volume, of any resolution, not one
        of the rendered scene — merged into the volume of a placed object of the scene Render() would draw now (synced first).  The
        source's centre sample is put at `position` (grid coordinates of the object's volume, xyz, fractions allowed), turned by

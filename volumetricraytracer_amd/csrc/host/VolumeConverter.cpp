@@ -9,6 +9,7 @@
 #include "../smooth_core.h"
 #include "../stamp_core.h"
 #include "../voxelize_core.h"
+#include "../warp_core.h"
 
 #include <algorithm>
 #include <cmath>
@@ -490,6 +491,51 @@ VVolumeConverter::VStampResult VVolumeConverter::Smooth(Voxel::VVoxel* voxels, s
 
 VVolumeConverter::VStampResult VVolumeConverter::Smooth(Voxel::VVoxelVolume& volume, const ::vrt_smooth& smooth) {
     const VStampResult out = Smooth(volume.GetVoxels().data(), volume.GetSize(), false, smooth);
+    if (out.Written) volume.MakeDirty();
+    return out;
+}
+
+VVolumeConverter::VStampResult VVolumeConverter::Warp(Voxel::VVoxel* voxels, size_t n, float unit, bool texel16, const ::vrt_warp& warp) {
+    namespace W = vrt_warp_core;
+    const int N = (int)n;
+    VStampResult out;
+    out.Lo = VIntVector(N, N, N);
+    out.Hi = VIntVector(-1, -1, -1);
+    int lo[3], hi[3];
+    if (!W::valid(warp) || !W::box(warp, N, lo, hi)) return out;
+    const float off = W::off_of(warp, unit);
+    /* the region's box, [x][z][y] like the grid: what every sample comes to, from the volume as it is; nothing is written yet */
+    const int nx = hi[0] - lo[0] + 1, ny = hi[1] - lo[1] + 1, nz = hi[2] - lo[2] + 1;
+    const size_t count = (size_t)nx * nz * ny;
+    std::vector<float> values(count);
+    std::vector<unsigned> ids(count);
+    std::vector<uint8_t> moved(count);
+    const auto stored_at = [&](size_t g) { return voxels[g].Density; };
+    const auto id_at = [&](size_t g) { return (unsigned)voxels[g].Material; };
+    size_t i = 0;
+    for (int x = lo[0]; x <= hi[0]; x++)
+        for (int z = lo[2]; z <= hi[2]; z++)
+            for (int y = lo[1]; y <= hi[1]; y++, i++) moved[i] = W::evaluate(warp, off, N, texel16, x, y, z, stored_at, id_at, values[i], ids[i]);
+    i = 0;
+    for (int x = lo[0]; x <= hi[0]; x++)
+        for (int z = lo[2]; z <= hi[2]; z++)
+            for (int y = lo[1]; y <= hi[1]; y++, i++) {
+                if (!moved[i]) continue;
+                Voxel::VVoxel& voxel = voxels[vrt_grid::index(N, x, y, z)];
+                const bool density = W::density_differs(values[i], voxel.Density), id = W::id_differs(ids[i], voxel.Material);
+                if (!density && !id) continue;
+                if (density) voxel.Density = values[i];
+                if (id) voxel.Material = (uint8_t)ids[i];
+                out.Lo = VIntVector(std::min(out.Lo.X, x), std::min(out.Lo.Y, y), std::min(out.Lo.Z, z));
+                out.Hi = VIntVector(std::max(out.Hi.X, x), std::max(out.Hi.Y, y), std::max(out.Hi.Z, z));
+                out.Written++;
+            }
+    return out;
+}
+
+VVolumeConverter::VStampResult VVolumeConverter::Warp(Voxel::VVoxelVolume& volume, const ::vrt_warp& warp) {
+    const float unit = vrt_stamp_core::unit_of((int)volume.GetSize(), volume.GetVolumeExtends(), volume.DensityScale);
+    const VStampResult out = Warp(volume.GetVoxels().data(), volume.GetSize(), unit, false, warp);
     if (out.Written) volume.MakeDirty();
     return out;
 }

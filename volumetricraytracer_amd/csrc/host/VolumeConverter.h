@@ -19,6 +19,7 @@
 struct vrt_ctx; /* include/vrt.h */
 struct vrt_stamp;
 struct vrt_smooth;
+struct vrt_warp;
 struct vrt_components;
 struct vrt_component;
 struct vrt_components_result;
@@ -111,6 +112,15 @@ public:
     static VStampResult Smooth(Voxel::VVoxelVolume& volume, const ::vrt_smooth& smooth);
     /* The same on n^3 VVoxel records (index x*n*n + z*n + y); texel16: the records hold the integer field +-q of a VRT_FORMAT_TEXEL16 slot. */
     static VStampResult Smooth(Voxel::VVoxel* voxels, size_t n, bool texel16, const ::vrt_smooth& smooth);
+    /* Grab, twist, scale and inflate, in place — the rule of vrt_volume_warp (include/vrt.h; its arithmetic is csrc/warp_core.h, shared
+       with the HIP kernels), as two plain loops over the region's box: the first computes what every sample comes to from the volume as
+       it is, the second stores the samples whose bits or id changed.  Lengths become density units through the volume's DensityScale.
+       Marks the volume dirty when it wrote.  The record must be one vrt_volume_warp accepts (vrt_warp_core::valid); otherwise nothing
+       is written.  The result is reported like Stamp's. */
+    static VStampResult Warp(Voxel::VVoxelVolume& volume, const ::vrt_warp& warp);
+    /* The same on n^3 VVoxel records (index x*n*n + z*n + y); unit: density units per cell; texel16: the records hold the integer field
+       +-q of a VRT_FORMAT_TEXEL16 slot. */
+    static VStampResult Warp(Voxel::VVoxel* voxels, size_t n, float unit, bool texel16, const ::vrt_warp& warp);
     /* Islands labelled, listed and removed, in place — the rule of vrt_volume_components (include/vrt.h; its arithmetic and argument
        rules are csrc/components_core.h, shared with the HIP build), as a breadth-first flood per component in key order.  list,
        listCapacity and result_or_null are that call's; so is the return value: VRT_OK, or VRT_ERR_INVALID for a record it refuses

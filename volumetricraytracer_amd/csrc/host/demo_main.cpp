@@ -23,6 +23,10 @@
  *            [--edit-smooth S]              with --edit-device or --edit-stamp: after every dab one smooth record runs at the dab's position — a sphere of 1.5 R
  *                                           cells, strength S, two iterations, no rebound (VHipRenderer::SmoothVolume, vrt_volume_smooth): the carve's
  *                                           staircase relaxed on the device; with --sdf BAND it runs before the redistance of the dab's box
+ *            [--edit-grab G]                with --edit-brush R and --edit-device: instead of carving, every frame grabs a ball of 1.5 R cells at the brush or
+ *                                           pick position and pulls it G cells along the direction from the volume's centre to that position — a bump
+ *                                           grows (G < 0: a dent) —, falloff 0.75 R, material ids kept (VHipRenderer::WarpVolume, vrt_volume_warp); with
+ *                                           --sdf BAND the written box grown by BAND is redistanced afterwards, as after a dab
  *            [--solid]                      the red sphere is built as the Voxelizer builds a mesh — an unsigned shell, density = |distance to its surface| / thr - 0.5
  *                                           with thr = cell * sqrt 3, positive again inside — and, after the upload, every volume of the scene has its enclosed
  *                                           cavities filled on the device (VHipRenderer::FillEnclosed, vrt_volume_fill_enclosed; wall 1, material 1): --edit-brush
@@ -119,7 +123,7 @@ int main(int argc, char** argv) {
     bool identityDefaults = false;
     int editBrush = 0, sdf = 0;
     bool editFull = false, editDevice = false, editStamp = false, solid = false;
-    float editSmooth = 0.f;
+    float editSmooth = 0.f, editGrab = 0.f;
     bool pick = false;
     int pickX = 0, pickY = 0;
     int mode = 0, inFlight = 3, block = 0; /* three frames in flight: the reference's swap chain (FrameCount, DXConstants.cpp:23) */
@@ -141,6 +145,7 @@ int main(int argc, char** argv) {
         else if (!strcmp(argv[i], "--edit-device")) editDevice = true;
         else if (!strcmp(argv[i], "--edit-stamp")) editStamp = editDevice = true;
         else if (!strcmp(argv[i], "--edit-smooth") && i + 1 < argc) editSmooth = (float)atof(argv[++i]);
+        else if (!strcmp(argv[i], "--edit-grab") && i + 1 < argc) editGrab = (float)atof(argv[++i]);
         else if (!strcmp(argv[i], "--solid")) solid = true;
         else if (!strcmp(argv[i], "--sdf") && i + 1 < argc) sdf = atoi(argv[++i]);
         else if (!strcmp(argv[i], "--mesh-out") && i + 1 < argc) meshOut = argv[++i];
@@ -211,6 +216,11 @@ int main(int argc, char** argv) {
         fprintf(stderr, "--edit-smooth S relaxes every dab on the device: it needs --edit-brush with --edit-device or --edit-stamp, and 0 < S <= 1\n");
         return 1;
     }
+    if (editGrab != 0.f && (!hip || !editDevice || editStamp || editSmooth != 0.f || editBrush <= 0 || !std::isfinite(editGrab))) {
+        fprintf(stderr, "--edit-grab G pulls the region of every dab on the device instead of carving it: it needs --edit-brush with --edit-device, "
+                        "without --edit-stamp and --edit-smooth, and a finite G\n");
+        return 1;
+    }
     if (editDevice && !hip) editDevice = false;
     if (pick && (!hip || block > 0)) {
         fprintf(stderr, "--pick asks the HIP renderer once per frame: drop --block\n");
@@ -260,7 +270,7 @@ int main(int argc, char** argv) {
     }
     const std::shared_ptr<Voxel::VVoxelVolume> stampTorus = editStamp ? InitStampTorus() : nullptr;
     int stampTurns = 0;
-    unsigned long long stampedVoxels = 0, smoothedVoxels = 0;
+    unsigned long long stampedVoxels = 0, smoothedVoxels = 0, warpedVoxels = 0;
     double kernel_ms = 0.0;
     bool warmUp = true; /* the untimed first frame prints no pick record */
     /* the brush: a sphere of editBrush cells around voxel c — a point that circles the red sphere's centre 12 cells out, 4 cells above
@@ -269,7 +279,24 @@ int main(int argc, char** argv) {
         if (editDevice) {
             vrt_brush_result wrote;
             bool done;
-            if (editStamp) { /* the torus, editBrush cells across its outer radius, a third of a radian further round every time: hard SUBTRACT */
+            if (editGrab != 0.f) { /* no carve: a ball half as large again pulled outwards, away from the volume's centre (straight up at it) */
+                const float mid = 0.5f * (float)(sphere1->GetVoxelVolume()->GetSize() - 1);
+                VVector dir((float)c.X - mid, (float)c.Y - mid, (float)c.Z - mid);
+                const float len = std::sqrt(dir.X * dir.X + dir.Y * dir.Y + dir.Z * dir.Z);
+                dir = len > 0.f ? VVector(dir.X / len, dir.Y / len, dir.Z / len) : VVector(0.f, 1.f, 0.f);
+                vrt_warp w;
+                memset(&w, 0, sizeof w);
+                w.shape = VRT_BRUSH_SPHERE;
+                w.material = VRT_WARP_MATERIAL_KEEP;
+                w.a[0] = (float)c.X, w.a[1] = (float)c.Y, w.a[2] = (float)c.Z;
+                w.radius = 1.5f * (float)editBrush;
+                w.strength = 1.f;
+                w.falloff = 0.75f * (float)editBrush;
+                done = Renderer::Hip::VHipRenderer::WarpFromMotion(VVector::ZERO, VVector(editGrab * dir.X, editGrab * dir.Y, editGrab * dir.Z),
+                                                                   VQuat(), 1.f, w) &&
+                       hip->WarpVolume(*sphere1, w, &wrote);
+                if (done) warpedVoxels += wrote.written;
+            } else if (editStamp) { /* the torus, editBrush cells across its outer radius, a third of a radian further round every time: hard SUBTRACT */
                 const VQuat turn = VQuat::FromAxisAngle(VVector::UP, 0.35f * (float)stampTurns++) * VQuat::FromAxisAngle(VVector::RIGHT, 0.5f);
                 done = hip->StampVolume(*sphere1, *stampTorus, VVector((float)c.X, (float)c.Y, (float)c.Z), turn, (float)editBrush / kStampOuter,
                                         VRT_STAMP_SUBTRACT, 0, 0.f, 0.f, 2.f, &wrote);
@@ -385,9 +412,10 @@ int main(int argc, char** argv) {
     const double wall = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
     if (sdf > 0 && editDevice && editBrush > 0) printf("sdf: %llu voxels redistanced around the dabs from %llu surfels\n", dabSamples, dabSurfels);
     if (editStamp) printf("stamp: %d torus stamps wrote %llu voxels on the device\n", stampTurns, stampedVoxels);
+    if (editGrab != 0.f) printf("grab: %g cells pulled %llu voxels around the brush positions on the device\n", editGrab, warpedVoxels);
     if (editSmooth > 0.f) printf("smooth: strength %g relaxed %llu voxels around the dabs on the device\n", editSmooth, smoothedVoxels);
     if (editBrush > 0)
-        printf("brush of %d cells, %s; ", editBrush, editStamp ? "device stamps" : (editDevice ? "device brushes" : (editFull ? "full uploads" : "region updates")));
+        printf("brush of %d cells, %s; ", editBrush, editGrab != 0.f ? "device grabs" : editStamp ? "device stamps" : (editDevice ? "device brushes" : (editFull ? "full uploads" : "region updates")));
     printf("%d frames %ux%u %s%s: %.3f ms/frame wall (%.0f frames/s)", frames, W, H, format.c_str(),
            block > 0 ? (", RenderBlock of " + std::to_string(block)).c_str() : (", " + std::to_string(inFlight) + " in flight").c_str(), wall / frames * 1e3, frames / wall);
     if (kernel_ms > 0.0) printf(", march kernel %.3f ms/%s", kernel_ms / (block > 0 ? (frames + block - 1) / block : frames), block > 0 ? "block" : "frame");

@@ -13,6 +13,7 @@
 #include "SceneConverter.h"
 #include "VolumeConverter.h"
 #include "../smooth_core.h"
+#include "../warp_core.h"
 #include "../stamp_core.h"
 
 using namespace VolumeRaytracer;
@@ -186,6 +187,21 @@ int vrh_smooth(vrt_voxel* voxels, int n, float extent, float density_scale, int 
         return VRT_ERR_INVALID;
     }
     const auto r = Voxelizer::VVolumeConverter::Smooth(reinterpret_cast<Voxel::VVoxel*>(voxels), (size_t)n, texel16 != 0, *smooth);
+    if (result_or_null) *result_or_null = vrt_brush_result{{r.Lo.X, r.Lo.Y, r.Lo.Z}, {r.Hi.X, r.Hi.Y, r.Hi.Z}, (uint64_t)r.Written};
+    return VRT_OK;
+}
+
+/* VVolumeConverter::Warp on caller records: n^3 records edited in place (index x*n*n + z*n + y); extent and density_scale give the
+   grid's density units per cell as vrt_volume_warp derives them (the record's inflate is in cells); texel16 != 0: the densities are the
+   integer field +-q; result_or_null as vrt_volume_warp reports.  The record passes the argument rules of vrt_volume_warp: VRT_OK, or
+   VRT_ERR_INVALID as that call returns it (a NULL pointer or a grid below 2 samples likewise). */
+int vrh_warp(vrt_voxel* voxels, int n, float extent, float density_scale, int texel16, const vrt_warp* warp, vrt_brush_result* result_or_null) {
+    if (!voxels || !warp || n < 2 || !vrt_warp_core::valid(*warp)) {
+        g_error = "vrh_warp: bad argument";
+        return VRT_ERR_INVALID;
+    }
+    const auto r = Voxelizer::VVolumeConverter::Warp(reinterpret_cast<Voxel::VVoxel*>(voxels), (size_t)n, vrt_stamp_core::unit_of(n, extent, density_scale),
+                                                     texel16 != 0, *warp);
     if (result_or_null) *result_or_null = vrt_brush_result{{r.Lo.X, r.Lo.Y, r.Lo.Z}, {r.Hi.X, r.Hi.Y, r.Hi.Z}, (uint64_t)r.Written};
     return VRT_OK;
 }

@@ -57,16 +57,7 @@ VRT_HD unsigned written_material(int material, float m) { return m <= 0.0f ? (un
 
 /* ---- host only: what a call derives once ---- */
 
-/* The region as the brush record whose shape it is: PAINT, so that brush_box adds no reach. */
-inline vrt_brush region_brush(const vrt_smooth& r) {
-    vrt_brush b;
-    memset(&b, 0, sizeof b);
-    b.shape = r.shape;
-    b.op = VRT_BRUSH_PAINT;
-    for (int a = 0; a < 3; a++) b.a[a] = r.a[a], b.b[a] = r.b[a];
-    b.radius = r.radius;
-    return b;
-}
+using vrt_brush_core::region_brush; /* the region as the PAINT record whose shape it is */
 
 /* The argument rules of vrt.h that need no slot: everything but the NULL pointers and the slot itself. */
 inline bool valid(const vrt_smooth& r) {

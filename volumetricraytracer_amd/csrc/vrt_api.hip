@@ -31,6 +31,7 @@
 #include "stamp_core.h"
 #include "brush_core.h"
 #include "smooth_core.h"
+#include "warp_core.h"
 #include "components_core.h"
 
 using namespace vrt;
@@ -98,6 +99,7 @@ static_assert(sizeof(vrt_ray) == 32 && sizeof(vrt_hit) == 48, "query_kernel read
 static_assert(sizeof(vrt_brush) == 64 && sizeof(vrt_brush_result) == 32, "vrt.h states these sizes");
 static_assert(sizeof(vrt_stamp) == 96, "vrt.h states this size");
 static_assert(sizeof(vrt_smooth) == 64, "vrt.h states this size");
+static_assert(sizeof(vrt_warp) == 128, "vrt.h states this size");
 static_assert(sizeof(vrt_fill_result) == 40, "vrt.h states this size");
 static_assert(sizeof(vrt_components) == 64 && sizeof(vrt_component) == 48 && sizeof(vrt_components_result) == 64, "vrt.h states these sizes");
 static_assert(sizeof(vrt_redistance_result) == 48, "vrt.h states this size");
@@ -247,7 +249,8 @@ struct DeviceState {
     size_t mesh_scratch_cap = 0;
     void* mesh_out = nullptr;
     size_t mesh_out_cap = 0;
-    /* vrt_volume_smooth: two fp32 copies of the work box and its weights (grown on demand, shared by the slots) */
+    /* vrt_volume_smooth: two fp32 copies of the work box and its weights; vrt_volume_warp: the value to store and the new id of every
+       sample of the region's box (grown on demand, shared by the slots and by the two calls) */
     void* smooth_scratch = nullptr;
     size_t smooth_scratch_cap = 0;
     /* vrt_trace_rays_host: the rays and then the hit records of a batch (grown on demand) */
@@ -861,7 +864,7 @@ int read_report(DeviceState& D, int N, Written& got) {
     }
     return VRT_OK;
 }
-vrt_brush_result brush_result(const Written& got) { /* brushes, stamp, smooth */
+vrt_brush_result brush_result(const Written& got) { /* brushes, stamp, smooth, warp */
     return vrt_brush_result{{got.lo[0], got.lo[1], got.lo[2]}, {got.hi[0], got.hi[1], got.hi[2]}, got.low};
 }
 
@@ -1046,6 +1049,45 @@ int smooth_volume(vrt_ctx* ctx, int slot, const vrt_smooth* rec, vrt_brush_resul
         if (rc != VRT_OK) return rc;
         if (di == 0 && result) *result = brush_result(got);
         rc = rebuild_written(ctx, D, slot, got.lo, got.hi, got.low, changed); /* every written sample is a density write */
+        if (rc != VRT_OK) return rc;
+    }
+    return finish_edit(ctx, changed);
+}
+
+/* vrt_volume_warp: the value to store and the new id of every sample of the region's box are computed into scratch memory from the
+ * volume as it is, then the samples whose bits or id changed are stored (launch_warp), which reports their box; what the slot derives
+ * from its samples is then recomputed over that box (rebuild_derived) — or not at all when no density changed.  The scratch memory of
+ * every device is there before the first sample is written.  Afterwards every buffer of the slot equals what upload_volume builds from
+ * the edited volume. */
+int warp_volume(vrt_ctx* ctx, int slot, const vrt_warp* rec, vrt_brush_result* result) {
+    if (!ctx || !rec || !vrt_warp_core::valid(*rec)) return VRT_ERR_INVALID;
+    if (!valid_slot(slot) || !ctx->vol[slot].used) return VRT_ERR_SLOT;
+    HostVolume& h = ctx->vol[slot];
+    const int N = h.N;
+    if (result) *result = vrt_brush_result{{N, N, N}, {-1, -1, -1}, 0};
+    int lo[3], hi[3];
+    if (!vrt_warp_core::box(*rec, N, lo, hi)) return VRT_OK; /* wholly outside the grid */
+    const EditBox region = derived_boxes(h, lo, hi).samples;
+    const float off = vrt_warp_core::off_of(*rec, vrt_stamp_core::unit_of(N, h.extent, h.density_scale));
+    int rc = quiesce(ctx);
+    if (rc != VRT_OK) return rc;
+    for (auto& D : ctx->dev) { /* every allocation comes before any write */
+        HIP_TRY(hipSetDevice(D.ordinal));
+        rc = ensure_buffer(D.smooth_scratch, D.smooth_scratch_cap, warp_scratch_bytes(region));
+        if (rc != VRT_OK) return rc;
+    }
+    bool changed = false;
+    for (size_t di = 0; di < ctx->dev.size(); di++) {
+        DeviceState& D = ctx->dev[di];
+        HIP_TRY(hipSetDevice(D.ordinal));
+        DeviceVolume& v = D.vol[slot];
+        HIP_TRY(launch_warp(*rec, off, h.format == VRT_FORMAT_TEXEL16, v.dense, v.material, N, region, D.smooth_scratch, D.d_brush, D.stream));
+        Written got;
+        rc = read_report(D, N, got);
+        if (rc != VRT_OK) return rc;
+        if (di == 0 && result) *result = brush_result(got);
+        /* the density writes count: nothing written, or only material ids, and no derived structure changes */
+        rc = rebuild_written(ctx, D, slot, got.lo, got.hi, got.high, changed);
         if (rc != VRT_OK) return rc;
     }
     return finish_edit(ctx, changed);
@@ -2010,6 +2052,9 @@ int vrt_volume_stamp(vrt_ctx* ctx, int dst_slot, int src_slot, const vrt_stamp* 
 
 int vrt_volume_smooth(vrt_ctx* ctx, int slot, const vrt_smooth* smooth, vrt_brush_result* result_or_null) {
     return smooth_volume(ctx, slot, smooth, result_or_null);
+}
+int vrt_volume_warp(vrt_ctx* ctx, int slot, const vrt_warp* warp, vrt_brush_result* result_or_null) {
+    return warp_volume(ctx, slot, warp, result_or_null);
 }
 
 int vrt_volume_fill_enclosed(vrt_ctx* ctx, int slot, float wall, int material, vrt_fill_result* result_or_null) {

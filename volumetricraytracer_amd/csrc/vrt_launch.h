@@ -1,6 +1,6 @@
 /* vrt_launch.h — host-callable launch wrappers: the march and the ray queries (vrt_kernels.hip), what a slot derives from its dense grid
    (vrt_volume.hip) and one file per edit call (vrt_brush.hip, vrt_fill.hip, vrt_redistance.hip, vrt_stamp.hip, vrt_smooth.hip,
-   vrt_components.hip, vrt_mesh.hip). */
+   vrt_warp.hip, vrt_components.hip, vrt_mesh.hip). */
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stddef.h>
@@ -99,7 +99,7 @@ struct DBrushList {
     float unit; /* density units per cell: cell / density_scale */
     DBrush rec[VRT_MAX_BRUSHES];
 };
-/* The edit report: what a launch of an edit call (brushes, fill, redistance, stamp, smooth) or of the mesh count reports (device memory,
+/* The edit report: what a launch of an edit call (brushes, fill, redistance, stamp, smooth, warp) or of the mesh count reports (device memory,
    zeroed by the launch; the kernels' side is edit_report.h): the written samples' box and counts, kept in kBrushSlots partial records
    that the host merges — thousands of waves report at once, and atomics on one word take their turns (a single record made the brush
    launch 25 times longer than the scatter of the same box).  Every field grows from 0 = nothing written. */
@@ -107,8 +107,8 @@ constexpr int kBrushSlots = 64;
 struct DBrushSlot {
     uint32_t inv_lo[3];        /* N - lowest written x, y, z */
     uint32_t hi1[3];           /* 1 + highest written x, y, z */
-    unsigned long long counts; /* samples written (low half; N^3 < 2^32) and, of those, the ones the op singles out (high half) — brushes:
-                                  samples whose density was written (0: only material ids changed, no derived structure to rebuild);
+    unsigned long long counts; /* samples written (low half; N^3 < 2^32) and, of those, the ones the op singles out (high half) — brushes
+                                  and warp: samples whose density was written (0: only material ids changed, no derived structure to rebuild);
                                   redistance: samples nearer than the band; fill, stamp, smooth: all of them */
     uint32_t pad_[24];         /* one 128-byte line per slot */
 };
@@ -166,6 +166,15 @@ hipError_t launch_stamp_region(const vrt_stamp_core::Rule& rule, bool src_texel1
 size_t smooth_scratch_bytes(const EditBox& work);
 hipError_t launch_smooth(const vrt_smooth& rule, bool texel16, float* dense, uint8_t* material, int N, const EditBox& work,
                          const EditBox& region, void* scratch, DBrushSlot* slots, hipStream_t stream);
+
+/* vrt_volume_warp (vrt_warp.hip): the rule of warp_core.h.  region: the box outside which no sample is in the region; off: the
+   record's inflate in density units (warp_core.h, off_of).  scratch: warp_scratch_bytes(region) of device memory — the value to store
+   (one float) and the new id (one byte) of every sample of the box.  Computes both from the volume as it is, writing nothing to it, then
+   stores the samples whose bits or id changed; slots: zeroed, then the written samples' counts and box (the edit report, above), with
+   the count of density writes in the high half of `counts`. */
+size_t warp_scratch_bytes(const EditBox& region);
+hipError_t launch_warp(const vrt_warp& rule, float off, bool texel16, float* dense, uint8_t* material, int N, const EditBox& region,
+                       void* scratch, DBrushSlot* slots, hipStream_t stream);
 
 /* vrt_volume_components (vrt_components.hip).  scratch: components_scratch_bytes(N) of device memory — a header of counters and two
    words per sample: the labels (components_core.h) and, at every root's key, its row in the table —, valid from

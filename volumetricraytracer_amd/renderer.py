@@ -78,6 +78,51 @@ def smooth_record(shape: int, a, b, radius: float, strength: float = 0.5, iterat
     return r
 
 
+def _inverse_turn_and_scale(rotation_xyzw, scale: float, who: str) -> np.ndarray:
+    """R^T / scale in double, R being the turn of the quaternion (any length but 0)."""
+    x, y, z, w = (float(c) for c in rotation_xyzw)
+    n = (x * x + y * y + z * z + w * w) ** 0.5
+    if not n > 0.0 or not float(scale) > 0.0:
+        raise ValueError(f"{who}: a zero quaternion or a scale that is not positive")
+    x, y, z, w = x / n, y / n, z / n, w / n
+    rot = np.array([[1 - 2 * (y * y + z * z), 2 * (x * y - z * w), 2 * (x * z + y * w)],
+                    [2 * (x * y + z * w), 1 - 2 * (x * x + z * z), 2 * (y * z - x * w)],
+                    [2 * (x * z - y * w), 2 * (y * z + x * w), 1 - 2 * (x * x + y * y)]], np.float64)
+    return rot.T / float(scale)
+
+
+IDENTITY_PULL = (1.0, 0.0, 0.0, 0.0, 0.0, 1.0, 0.0, 0.0, 0.0, 0.0, 1.0, 0.0)
+
+
+def warp_record(shape: int, a, b, radius: float, pull=IDENTITY_PULL, length_scale: float = 1.0, inflate: float = 0.0, strength: float = 1.0,
+                falloff: float = 1.0, material: int = _abi.WARP_MATERIAL_KEEP) -> _abi.vrt_warp:
+    """A vrt_warp record: the region is the shape of a brush record (as smooth_record takes it); pull is the row-major 3x4 matrix (12
+    values, or a [3, 4] array) that says where a sample at full weight takes its value FROM, in grid coordinates xyz — the inverse of
+    the motion one sees (warp_from_motion builds it); inflate in cells (vrt.h)."""
+    m = np.asarray(pull, dtype=np.float64).reshape(12)
+    r = _abi.vrt_warp()
+    r.shape, r.material = int(shape), int(material)
+    for i in range(3):
+        r.a[i], r.b[i] = float(a[i]), float(b[i])
+    for i in range(12):
+        r.pull[i] = float(m[i])
+    r.radius, r.strength, r.falloff, r.length_scale, r.inflate = float(radius), float(strength), float(falloff), float(length_scale), float(inflate)
+    return r
+
+
+def warp_from_motion(pivot, translation=(0.0, 0.0, 0.0), rotation=(0.0, 0.0, 0.0, 1.0), scale: float = 1.0):
+    """(pull, length_scale) of a vrt_warp record for the motion one sees: a turn by the quaternion `rotation` (xyzw) and a uniform
+    `scale` about `pivot` (grid coordinates xyz), then a shift by `translation` (cells) — p' = pivot + scale R (p - pivot) +
+    translation.  pull is the inverse motion, p = pivot + R^T (p' - pivot - translation) / scale, built in double; pull is a [3, 4]
+    float64 array that warp_record rounds to fp32 once; length_scale = scale."""
+    lin = _inverse_turn_and_scale(rotation, scale, "warp_from_motion")
+    c = np.asarray(pivot, np.float64).reshape(3)
+    m = np.zeros((3, 4), np.float64)
+    m[:, :3] = lin
+    m[:, 3] = c - lin @ (c + np.asarray(translation, np.float64).reshape(3))
+    return m, float(scale)
+
+
 def stamp_record(op: int, dst_to_src, length_scale: float = 1.0, offset: float = 0.0, blend: float = 0.0, reach: float = 2.0,
                  material: int = _abi.STAMP_MATERIAL_KEEP) -> _abi.vrt_stamp:
     """A vrt_stamp record from the matrix itself: dst_to_src is the row-major 3x4 matrix (12 values, or a [3, 4] array) that takes
@@ -97,15 +142,7 @@ def stamp_from_placement(src_N: int, position, rotation_xyzw=(0.0, 0.0, 0.0, 1.0
     `position` (destination grid coordinates xyz, fractions allowed), turned by the quaternion `rotation_xyzw` about it, and one
     source cell covers `scale` destination cells.  The matrix u = R^T (p - position) / scale + (src_N - 1) / 2 is built in double
     and rounded to fp32 once; length_scale = scale."""
-    x, y, z, w = (float(c) for c in rotation_xyzw)
-    n = (x * x + y * y + z * z + w * w) ** 0.5
-    if not n > 0.0 or not float(scale) > 0.0:
-        raise ValueError("stamp_from_placement: a zero quaternion or a scale that is not positive")
-    x, y, z, w = x / n, y / n, z / n, w / n
-    rot = np.array([[1 - 2 * (y * y + z * z), 2 * (x * y - z * w), 2 * (x * z + y * w)],
-                    [2 * (x * y + z * w), 1 - 2 * (x * x + z * z), 2 * (y * z - x * w)],
-                    [2 * (x * z - y * w), 2 * (y * z + x * w), 1 - 2 * (x * x + y * y)]], np.float64)
-    lin = rot.T / float(scale)
+    lin = _inverse_turn_and_scale(rotation_xyzw, scale, "stamp_from_placement")
     m = np.zeros((3, 4), np.float64)
     m[:, :3] = lin
     m[:, 3] = -lin @ np.asarray(position, np.float64).reshape(3) + (int(src_N) - 1) / 2.0
@@ -306,6 +343,19 @@ class VHipRenderer:
         self._require()
         res = _abi.vrt_brush_result()
         _abi.check(self._lib.vrt_volume_smooth(self._ctx, int(slot), C.byref(smooth), C.byref(res)), "vrt_volume_smooth")
+        lo, hi = tuple(res.lo), tuple(res.hi)
+        if res.written and vol is not None:
+            self._mirror_box(slot, vol, lo, hi)
+        return {"written": int(res.written), "lo": lo, "hi": hi}
+
+    def warp_volume(self, slot: int, warp: _abi.vrt_warp, vol: Optional[VVoxelVolume] = None) -> dict:
+        """vrt_volume_warp: the volume resident in `slot` grabbed, twisted, scaled or inflated on the device inside the record's shape
+        (warp_record): every sample there takes its value from where the record's motion, faded out by the region's weight, brings it
+        from.  Given the slot's host mirror `vol`, the written box is then read back as apply_brushes does.  Returns {"written", "lo",
+        "hi"} (xyz, inclusive; lo > hi when nothing was written)."""
+        self._require()
+        res = _abi.vrt_brush_result()
+        _abi.check(self._lib.vrt_volume_warp(self._ctx, int(slot), C.byref(warp), C.byref(res)), "vrt_volume_warp")
         lo, hi = tuple(res.lo), tuple(res.hi)
         if res.written and vol is not None:
             self._mirror_box(slot, vol, lo, hi)

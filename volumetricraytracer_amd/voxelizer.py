@@ -47,6 +47,8 @@ def load_host() -> C.CDLL:
         lib.vrh_stamp.restype = C.c_int
         lib.vrh_stamp.argtypes = [C.c_void_p, C.c_int, C.c_float, C.c_float, C.c_int, C.c_void_p, C.c_int, C.c_float, C.c_float, C.c_int,
                                   C.POINTER(_abi.vrt_stamp), C.POINTER(_abi.vrt_brush_result)]
+        lib.vrh_warp.restype = C.c_int
+        lib.vrh_warp.argtypes = [C.c_void_p, C.c_int, C.c_float, C.c_float, C.c_int, C.POINTER(_abi.vrt_warp), C.POINTER(_abi.vrt_brush_result)]
         lib.vrh_smooth.restype = C.c_int
         lib.vrh_smooth.argtypes = [C.c_void_p, C.c_int, C.c_float, C.c_float, C.c_int, C.POINTER(_abi.vrt_smooth), C.POINTER(_abi.vrt_brush_result)]
         lib.vrh_components.restype = C.c_int
@@ -193,6 +195,25 @@ def smooth_host(vol: VVoxelVolume, smooth: _abi.vrt_smooth, texel16: bool = Fals
     rc = lib.vrh_smooth(rec.ctypes.data, vol.N, float(vol.VolumeExtends), float(vol.density_scale), int(bool(texel16)), C.byref(smooth),
                         C.byref(res))
     _abi.check(rc, "vrh_smooth")
+    if res.written:
+        vol.density = np.ascontiguousarray(rec["density"].reshape(vol.N, vol.N, vol.N))
+        vol.material_id = np.ascontiguousarray(rec["material"].reshape(vol.N, vol.N, vol.N))
+        vol.dirty = True
+    return {"written": int(res.written), "lo": tuple(res.lo), "hi": tuple(res.hi)}
+
+
+def warp_host(vol: VVoxelVolume, warp: _abi.vrt_warp, texel16: bool = False) -> dict:
+    """VVolumeConverter::Warp (the host build of vrt_volume_warp's rule) on a volume's densities and material ids, in place.
+    texel16: the densities are the integer field +-q of a TEXEL16 slot.  Raises _abi.VrtError with the code vrt_volume_warp returns
+    for a record it refuses.  Returns {"written", "lo", "hi"} (xyz, inclusive; lo > hi when nothing was written)."""
+    lib = load_host()
+    dtype = np.dtype([("material", "u1"), ("pad", "u1", 3), ("density", "<f4")])
+    rec = np.zeros(vol.N ** 3, dtype=dtype)
+    rec["density"] = np.asarray(vol.density, np.float32).reshape(-1)
+    rec["material"] = np.asarray(vol.material_id, np.uint8).reshape(-1)
+    res = _abi.vrt_brush_result()
+    rc = lib.vrh_warp(rec.ctypes.data, vol.N, float(vol.VolumeExtends), float(vol.density_scale), int(bool(texel16)), C.byref(warp), C.byref(res))
+    _abi.check(rc, "vrh_warp")
     if res.written:
         vol.density = np.ascontiguousarray(rec["density"].reshape(vol.N, vol.N, vol.N))
         vol.material_id = np.ascontiguousarray(rec["material"].reshape(vol.N, vol.N, vol.N))
