@@ -178,7 +178,8 @@ def sphere_in_constant(N: int, centre, radius: float, unit: float, far: float = 
 
 # ---- frames around an edit -----------------------------------------------------------------------------------------------------------
 
-EDIT_OPS = ("stamp", "fill", "redistance")
+EDIT_OPS = ("stamp", "fill", "redistance", "smooth", "warp", "components")
+ANALYTIC_OPS = ("stamp", "smooth", "warp", "components")  # on config3_torus(6); the others on the Voxelizer's shell of it
 
 
 def stamp_source():
@@ -193,11 +194,38 @@ def frame_stamp(vol) -> object:
     return v.stamp_from_placement(17, (c + 18.0, c, c + 8.0), K.quat((1, 1, 0), 30.0), 0.6, op=S.SUBTRACT, material=0)
 
 
+def frame_smooth(vol) -> object:
+    """A dab of 6 cells on the side of config3_torus(6) that faces the camera: the tube's outer equator lies 24.6 cells out along +x."""
+    c = (vol.N - 1) / 2.0
+    return v.smooth_record(B.SPHERE, (c + 22.0, c + 0.4, c + 4.0), (0.0, 0.0, 0.0), 6.0, strength=1.0, iterations=8, falloff=2.0)
+
+
+def frame_warp(vol) -> object:
+    """A ball of 9 cells about the tube's outer equator grabbed by 4.5 cells outwards, towards the camera: the surface ends 29 cells out,
+    in a brick beyond the active box's last one (the box ends with the brick of cell 32 + 24.6 + 0.5: brick 14 of 16)."""
+    c = (vol.N - 1) / 2.0
+    pull = v.warp_from_motion((0.0, 0.0, 0.0), translation=(4.5, 0.0, 1.0))[0]
+    return v.warp_record(B.SPHERE, (c + 22.0, c, c + 2.0), (0.0, 0.0, 0.0), 9.0, pull=pull, falloff=4.0, material=-2)
+
+
+def frame_island(vol) -> object:
+    """A ball of 3 cells above the torus' hole on the camera's side, 15.9 cells from the ring's centre line: an island of its own."""
+    c = (vol.N - 1) / 2.0
+    return v.sphere_brush(B.ADD, (c + 10.0, c, c + 14.0), 3.0, 0.0, 2.0, 1)
+
+
+def frame_components(vol) -> object:
+    """Every component of fewer than 1000 samples goes — the island has about 113, the torus 13 000 — and leaves a gap of half a cell."""
+    from volumetricraytracer_amd import _abi
+    return _abi.components_record(_abi.COMPONENTS_REMOVE_SMALL, gap=0.5 * float(B.units(vol.N, vol.VolumeExtends, vol.density_scale)[1]),
+                                  material=0, min_samples=1000)
+
+
 def edit_scene(op: str):
     """(scene, its volume) for the frames around `op`, F32 so that the oracle marches the host mirror: the analytic torus for the stamp,
-    the Voxelizer's shell of it for the fill and the redistance."""
+    the smooth, the warp and the components call, the Voxelizer's shell of it for the fill and the redistance."""
     from volumetricraytracer_amd import workloads as scenes
-    if op == "stamp":
+    if op in ANALYTIC_OPS:
         sc = scenes.config3_torus(6, 16)
         vol = sc.volumes()[0]
         vol.step_max = 0.5 * vol.GetCellSize()
@@ -209,16 +237,26 @@ def edit_scene(op: str):
 
 
 def host_edit(op: str, vol, prepare_only: bool = False):
-    """The host pass of what device_edit does, on the host volume in place: the fill that precedes the redistance (prepare), then the
-    op itself."""
+    """The host pass of what device_edit does, on the host volume in place: the fill that precedes the redistance and the island that
+    the components call removes (prepare; the brush by its numpy rule, tests/brush_ref.py), then the op itself."""
     from volumetricraytracer_amd import voxelizer as vx
     if op == "redistance":
         vx.fill_enclosed_host(vol, 1.0, 1)
+    if op == "components":
+        got = B.apply(vol.density, vol.material_id, R.F32, [frame_island(vol)], vol.VolumeExtends, vol.density_scale)
+        assert got["written"] > 50, got
     if prepare_only:
         return
     if op == "stamp":
         vx.stamp_host(vol, stamp_source(), frame_stamp(vol))
     elif op == "fill":
         vx.fill_enclosed_host(vol, 1.0, 1)
+    elif op == "smooth":
+        assert vx.smooth_host(vol, frame_smooth(vol))["written"] > 100
+    elif op == "warp":
+        assert vx.warp_host(vol, frame_warp(vol))["written"] > 100
+    elif op == "components":
+        got = vx.components_host(vol, frame_components(vol))
+        assert got["removed"] == 1 and got["written"] > 50, got
     else:
         vx.redistance_host(vol, 3, RR.OUTSIDE)

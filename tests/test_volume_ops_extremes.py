@@ -122,3 +122,14 @@ def test_the_case_tables_reach_what_they_are_for():
             assert not np.isnan(t).any() and (t == np.round(t)).all()
     assert X.fill_fields(3)["sealed"][1:] == (1, (1, 1, 1), (1, 1, 1)) and X.fill_fields(5)["sealed"][1:] == (27, (1, 1, 1), (3, 3, 3))
     assert X.fill_fields(2)["sealed"][1] == 0
+
+
+def test_the_grab_of_the_frame_tests_grows_the_active_box():
+    """The frames around the warp say that a stale active box would show only if the grab moves the surface into a brick beyond the
+    box: along +x here, towards the camera."""
+    sc, vol = X.edit_scene("warp")
+    box = lambda: R.tables(np.array(vol.density, np.float32), R.F32, vol.density_scale, vol.step_max)["active_box"]
+    before = box()
+    X.host_edit("warp", vol)
+    after = box()
+    assert (after[:3] <= before[:3]).all() and (after[3:] >= before[3:]).all() and after[3] > before[3], (before, after)

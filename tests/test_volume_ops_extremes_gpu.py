@@ -432,16 +432,18 @@ def test_redistance_in_the_far_corner_at_257(renderer, fmt):
     assert_same_buffers(have, buffers(renderer, FULL), f"257^3 far corner, format {fmt}, against a full upload")
 
 
-# ---- C. frames around a stamp, a fill and a redistance; two devices -----------------------------------------------------------------
+# ---- C. frames around a stamp, a fill, a redistance, a smooth, a warp and a components call; two devices -----------------------------------------------------------------
 
 def prepare_edit(r, op, vol):
     """What the edit needs on the device beforehand, the scene's volume being resident in slot 0: the stamp's source in a spare slot;
-    the fill that makes the shell a solid to redistance."""
+    the fill that makes the shell a solid to redistance; the island that the components call removes."""
     if op == "stamp":
         src = X.stamp_source()
         upload_field(r, SPARE, src, R.F32, K.stored("sphere", 17, "src", R.F32), src.material_id)
     elif op == "redistance":
         assert r.fill_enclosed(0, vol, 1.0, 1)["filled"] > 1000
+    elif op == "components":
+        assert r.apply_brushes(0, vol, [X.frame_island(vol)])["written"] > 50
 
 
 def device_edit(r, op, vol):
@@ -452,6 +454,15 @@ def device_edit(r, op, vol):
     elif op == "fill":
         got = r.fill_enclosed(0, vol, 1.0, 1)
         assert got["filled"] > 1000, got
+    elif op == "smooth":
+        got = r.smooth_volume(0, X.frame_smooth(vol), vol)
+        assert got["written"] > 100, got
+    elif op == "warp":
+        got = r.warp_volume(0, X.frame_warp(vol), vol)
+        assert got["written"] > 100, got
+    elif op == "components":
+        got = r.components(0, X.frame_components(vol), vol)
+        assert got["removed"] == 1 and got["written"] > 50, got
     else:
         got = r.redistance(0, vol, 3, RR.OUTSIDE)
         assert got["near"] > 1000, got
