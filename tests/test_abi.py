@@ -75,6 +75,16 @@ def test_argument_errors_without_touching_the_gpu():
     assert lib.vrt_render_block(None, None, None, None, None) == _abi.VRT_ERR_INVALID
     assert lib.vrt_render_rows(None, None, 0, 0, None, None) == _abi.VRT_ERR_INVALID
     assert lib.vrt_gather_tiles(None, None, None, 0, 0, None) == _abi.VRT_ERR_NOT_READY  # no context, no communicator
+    # every entry point that returns a status refuses a null context with every other argument null or zero: an entry point
+    # whose definition lost its declaration's signature would read something else for its context
+    no_communicator = {"vrt_comm_expect_sizes", "vrt_gather_tiles", "vrt_exchange_tiles"}
+    statuses = {}
+    for name, (restype, argtypes) in sorted(_abi.SYMBOLS.items()):
+        if restype is C.c_int:
+            statuses[name] = getattr(lib, name)(*[t() for t in argtypes])
+    assert set(_abi.SYMBOLS) - set(statuses) == {"vrt_debug_wave_records", "vrt_strerror", "vrt_version"}  # these return no int
+    for name, status in statuses.items():
+        assert status == (_abi.VRT_ERR_NOT_READY if name in no_communicator else _abi.VRT_ERR_INVALID), name
 
 
 def test_no_fallback_when_library_missing(tmp_path):

@@ -1,4 +1,4 @@
-/* vrt_components.hip — the kernels of vrt_volume_components (include/vrt.h): the 6-connected components of a resident volume's solid
+/* vrt_components.hip — vrt_volume_components (include/vrt.h), kernels to driver: the 6-connected components of a resident volume's solid
  * samples (!(d > 0)), their sizes and boxes, and the edit that removes some of them.
  *
  * A label is one word per sample (components_core.h): a solid sample starts with its own key (x*N + z)*N + y, a passable one holds
@@ -15,12 +15,15 @@
  * Every find and every union loop is capped and raises a flag that the host turns into VRT_ERR_HIP. */
 #include <hip/hip_runtime.h>
 
+#include <string.h>
+
 #include <algorithm>
+#include <vector>
 
 #include "components_core.h"
 #include "fill_core.h" /* the 8^3 tiles and their row bytes */
 #include "edit_report.h"
-#include "vrt_launch.h"
+#include "vrt_context.h"
 
 namespace vrt {
 
@@ -314,13 +317,18 @@ unsigned* labels_of(void* scratch) { return reinterpret_cast<unsigned*>(static_c
 unsigned* rows_of(void* scratch, int N) { return labels_of(scratch) + (size_t)N * N * N; }
 unsigned stride_grid(size_t count, size_t most) { return (unsigned)std::max<size_t>(1, std::min<size_t>((count + 255) / 256, most)); }
 
-}  // namespace
-
+/* scratch: components_scratch_bytes(N) of device memory — a header of counters and two
+   words per sample: the labels (components_core.h) and, at every root's key, its row in the table —, valid from
+   launch_components_label to launch_components_apply.  table: components_table_bytes(components) of device memory, 32 B a component. */
 size_t components_scratch_bytes(int N) { return kHeaderBytes + 2 * sizeof(unsigned) * (size_t)N * N * N; }
 size_t components_table_bytes(unsigned components) { return std::max<size_t>(1, components) * sizeof(DComponent); }
+/* device memory: the labels, one word per sample in the grid's own order, every solid sample's the lowest key of its component
+   once launch_components_label has run; the header's words {gave up, components} */
 const unsigned* components_labels(const void* scratch) { return labels_of(const_cast<void*>(scratch)); }
 const unsigned* components_header(const void* scratch) { return header_of(const_cast<void*>(scratch)); }
 
+/* Labels every sample: the tiles on their own, the union of what meets across tile faces, every label made its root; counts the
+   roots.  A find or a union that ran into its cap leaves the header's first word non-zero. */
 hipError_t launch_components_label(const float* dense, bool texel16, int N, void* scratch, hipStream_t stream) {
     hipError_t e = hipMemsetAsync(scratch, 0, kHeaderBytes, stream);
     if (e != hipSuccess) return e;
@@ -333,6 +341,7 @@ hipError_t launch_components_label(const float* dense, bool texel16, int N, void
     return hipGetLastError();
 }
 
+/* One row of the table per component, in no particular order: its key, its samples and their box; `components`: the header's count. */
 hipError_t launch_components_stats(int N, void* scratch, void* table, unsigned components, hipStream_t stream) {
     const size_t count = (size_t)N * N * N;
     hipLaunchKernelGGL(components_roots_kernel, dim3(stride_grid(count, 1u << 16)), dim3(256), 0, stream, N, labels_of(scratch), rows_of(scratch, N),
@@ -343,6 +352,7 @@ hipError_t launch_components_stats(int N, void* scratch, void* table, unsigned c
     return hipGetLastError();
 }
 
+/* Row `row` of a host copy of the table. */
 void components_decode_row(const void* table, size_t row, int N, vrt_components_core::Component& out) {
     const DComponent& c = static_cast<const DComponent*>(table)[row];
     out.key = c.key;
@@ -350,6 +360,9 @@ void components_decode_row(const void* table, size_t row, int N, vrt_components_
     for (int a = 0; a < 3; a++) out.lo[a] = N - (int)c.inv_lo[a], out.hi[a] = (int)c.hi1[a] - 1;
 }
 
+/* The samples of every component the predicate removes (mode, a, b: components_core.h, removed_by) store removed_density (its texel
+   when texel16) and, material_id >= 0, that id; their halo stores the gap.  slots: zeroed, then the written samples' counts and box
+   (the edit report, vrt_launch.h).  The labels are spent afterwards. */
 hipError_t launch_components_apply(bool texel16, float* dense, uint8_t* material, int N, void* scratch, const void* table, int mode, unsigned a,
                                    unsigned b, float gap, int material_id, DBrushSlot* slots, hipStream_t stream) {
     hipError_t e = clear_report(slots, stream);
@@ -367,4 +380,128 @@ hipError_t launch_components_apply(bool texel16, float* dense, uint8_t* material
     return hipGetLastError();
 }
 
+}  // namespace
+
 }  // namespace vrt
+
+using namespace vrt;
+
+static_assert(sizeof(vrt_components) == 64 && sizeof(vrt_component) == 48 && sizeof(vrt_components_result) == 64, "vrt.h states these sizes");
+
+extern "C" {
+
+/* vrt_volume_components: first every device gets its label memory; then every device labels its copy (launch_components_label),
+ * reports how many components it found, gets its table and fills it (launch_components_stats) — the volume is still untouched.
+ * Device 0's table, sorted, is the list; it and (seed ops) the labels around the seed decide the removal predicate, which is the
+ * same mode and scalars on every device.  Only then, and only when something goes, the edit runs per device
+ * (launch_components_apply, which reports like a brush launch) and what the slot derives from the samples is recomputed over the
+ * written box (rebuild_derived).  Afterwards every buffer equals what upload_volume builds from the edited volume. */
+int vrt_volume_components(vrt_ctx* ctx, int slot, const vrt_components* rec, vrt_component* list, int list_capacity, vrt_components_result* result) {
+    namespace cc = vrt_components_core;
+    if (!ctx || !rec) return VRT_ERR_INVALID;
+    if (!valid_slot(slot) || !ctx->vol[slot].used) return VRT_ERR_SLOT;
+    HostVolume& h = ctx->vol[slot];
+    const int N = h.N;
+    const bool texel16 = h.format == VRT_FORMAT_TEXEL16;
+    if (!cc::valid(rec, N, texel16, list, list_capacity)) return VRT_ERR_INVALID;
+    vrt_components_result out;
+    memset(&out, 0, sizeof out);
+    for (int a = 0; a < 3; a++) out.lo[a] = N, out.hi[a] = -1;
+    int rc = quiesce(ctx);
+    if (rc != VRT_OK) return rc;
+    for (auto& D : ctx->dev) { /* every allocation comes before any write */
+        HIP_TRY(hipSetDevice(D.ordinal));
+        rc = ensure_buffer(D.buf[kBufCompLabels], components_scratch_bytes(N));
+        if (rc != VRT_OK) return rc;
+    }
+    unsigned n_components = 0;
+    for (size_t di = 0; di < ctx->dev.size(); di++) {
+        DeviceState& D = ctx->dev[di];
+        HIP_TRY(hipSetDevice(D.ordinal));
+        HIP_TRY(launch_components_label(D.vol[slot].dense, texel16, N, D.buf[kBufCompLabels].p, D.stream));
+        unsigned header[2];
+        HIP_TRY(hipMemcpyAsync(header, components_header(D.buf[kBufCompLabels].p), sizeof header, hipMemcpyDeviceToHost, D.stream));
+        HIP_TRY(hipStreamSynchronize(D.stream));
+        if (header[0] != 0u || (di > 0 && header[1] != n_components)) {
+            fprintf(stderr, "[vrt] vrt_volume_components: the labelling of a grid of %d^3 gave up on device %d\n", N, D.ordinal);
+            return VRT_ERR_HIP;
+        }
+        n_components = header[1];
+        rc = ensure_buffer(D.buf[kBufCompTable], components_table_bytes(n_components));
+        if (rc != VRT_OK) return rc;
+        if (n_components > 0) HIP_TRY(launch_components_stats(N, D.buf[kBufCompLabels].p, D.buf[kBufCompTable].p, n_components, D.stream));
+    }
+    std::vector<cc::Component> comps(n_components);
+    cc::Decision how;
+    if (n_components > 0) {
+        DeviceState& D0 = ctx->dev[0];
+        HIP_TRY(hipSetDevice(D0.ordinal));
+        std::vector<unsigned char> raw(components_table_bytes(n_components));
+        HIP_TRY(hipMemcpyAsync(raw.data(), D0.buf[kBufCompTable].p, raw.size(), hipMemcpyDeviceToHost, D0.stream));
+        unsigned gave_up = 0;
+        HIP_TRY(hipMemcpyAsync(&gave_up, components_header(D0.buf[kBufCompLabels].p), sizeof gave_up, hipMemcpyDeviceToHost, D0.stream));
+        HIP_TRY(hipStreamSynchronize(D0.stream));
+        if (gave_up != 0u) return VRT_ERR_HIP;
+        for (size_t i = 0; i < comps.size(); i++) components_decode_row(raw.data(), i, N, comps[i]);
+        std::sort(comps.begin(), comps.end(), cc::before);
+    }
+    uint32_t seed_label = cc::kPassable;
+    if (cc::seeded(rec->op)) { /* the labels of the seed's neighbourhood: up to nine runs of three along y */
+        uint32_t around[3][3][3];
+        for (auto& plane : around)
+            for (auto& line : plane)
+                for (uint32_t& l : line) l = cc::kPassable;
+        DeviceState& D0 = ctx->dev[0];
+        HIP_TRY(hipSetDevice(D0.ordinal));
+        const int y0 = std::max(rec->seed[1] - 1, 0), y1 = std::min(rec->seed[1] + 1, N - 1);
+        for (int dx = -1; dx <= 1; dx++)
+            for (int dz = -1; dz <= 1; dz++) {
+                const int x = rec->seed[0] + dx, z = rec->seed[2] + dz;
+                if (x < 0 || z < 0 || x >= N || z >= N) continue;
+                HIP_TRY(hipMemcpyAsync(&around[dx + 1][dz + 1][y0 - rec->seed[1] + 1], components_labels(D0.buf[kBufCompLabels].p) + cc::key_of(N, x, y0, z),
+                                       (size_t)(y1 - y0 + 1) * sizeof(uint32_t), hipMemcpyDeviceToHost, D0.stream));
+            }
+        HIP_TRY(hipStreamSynchronize(D0.stream));
+        seed_label = cc::seed_component(N, rec->seed, [&](int x, int y, int z) {
+            return around[x - rec->seed[0] + 1][z - rec->seed[2] + 1][y - rec->seed[1] + 1];
+        });
+    }
+    if (!cc::decide(*rec, comps.data(), comps.size(), seed_label, how)) return VRT_ERR_INVALID; /* nothing has been written */
+    out.components = n_components;
+    for (size_t i = 0; i < comps.size(); i++) {
+        const cc::Component& c = comps[i];
+        const bool goes = cc::removes(rec->op) && cc::removed_by(how.mode, how.a, how.b, c.key, c.samples);
+        out.solid += c.samples;
+        if (goes) out.removed++, out.removed_samples += c.samples;
+        if (i < (size_t)list_capacity) {
+            vrt_component& r = list[i];
+            memset(&r, 0, sizeof r);
+            cc::first_of(N, c.key, r.first);
+            for (int a = 0; a < 3; a++) r.lo[a] = c.lo[a], r.hi[a] = c.hi[a];
+            r.removed = goes ? 1u : 0u;
+            r.samples = c.samples;
+            out.listed++;
+        }
+    }
+    bool changed = false;
+    for (size_t di = 0; out.removed > 0 && di < ctx->dev.size(); di++) {
+        DeviceState& D = ctx->dev[di];
+        HIP_TRY(hipSetDevice(D.ordinal));
+        DeviceVolume& v = D.vol[slot];
+        HIP_TRY(launch_components_apply(texel16, v.dense, v.material, N, D.buf[kBufCompLabels].p, D.buf[kBufCompTable].p, how.mode, how.a, how.b, rec->gap,
+                                        rec->material, D.d_brush, D.stream));
+        Written got;
+        rc = read_report(D, N, got);
+        if (rc != VRT_OK) return rc;
+        if (di == 0) {
+            for (int a = 0; a < 3; a++) out.lo[a] = got.lo[a], out.hi[a] = got.hi[a];
+            out.written = got.low;
+        }
+        rc = rebuild_written(ctx, D, slot, got.lo, got.hi, got.low, changed); /* every written sample is a density write */
+        if (rc != VRT_OK) return rc;
+    }
+    if (result) *result = out;
+    return finish_edit(ctx, changed);
+}
+
+}  // extern "C"

@@ -1,0 +1,250 @@
+/* vrt_context.h — the host runtime's state and the few functions more than one unit calls: the context and what it keeps per device and
+   per slot, and the skeleton every volume edit call follows, which the calls' own units (vrt_<call>.hip) build their drivers
+   from.  What only one unit needs stays in that unit. */
+#pragma once
+#include <hip/hip_runtime.h>
+#include <stddef.h>
+#include <stdint.h>
+#include <stdio.h>
+
+#include <vector>
+
+#include "../../include/vrt.h"
+#include "vrt_device.h"
+#include "vrt_launch.h"
+
+namespace vrt {
+
+constexpr int kStatSlots = 16; /* streams that may have launches in flight at once without sharing a counter buffer */
+constexpr int kRing = 256; /* per-launch event pairs + stat slots kept for vrt_timing_history */
+
+struct HostVolume {
+    bool used = false;
+    int resolution = 0, N = 0, nb = 0;
+    float extent = 0.f;
+    int format = VRT_FORMAT_F32;
+    int abox[6] = {0, 0, 0, -1, -1, -1}; /* bounding box of the near bricks {min x, z, y, max x, z, y} (with the empty-space table) */
+    float density_scale = 1.f;
+    float step_max = 0.f; /* <= 0: unbounded */
+    vrt_material mat = {{0.8f, 0.8f, 0.8f, 1.0f}, 0.8f, 0.0f};
+    int tex[3] = {-1, -1, -1};            /* albedo, normal, rm texture ids; -1 unbound */
+    float tex_scale[2] = {100.f, 100.f};  /* VMaterial::TextureScale default, Material.h:33 */
+};
+
+struct HostTexture {
+    bool used = false;
+    int width = 0, height = 0;
+    uint8_t first[4] = {0, 0, 0, 0}; /* texel (0,0): a 1x1 image is a constant (DVolume::tex_const) */
+};
+
+struct DeviceVolume {
+    float* dense = nullptr;
+    void* bricks = nullptr;       /* fp32 or int16 records, by the slot's format */
+    void* cells = nullptr;        /* VRT_FORMAT_TEXEL16: 16-byte cell records (VRT_PATH_CELLS) */
+    uint8_t* material = nullptr;
+    uint8_t* skip = nullptr;      /* 2 x nb^3 bytes: the empty-space table (level 1) and its build scratch */
+    unsigned* nib = nullptr;      /* nb^3 words: the empty-space table, level 2 (sub-block nibbles) */
+    bool skip_valid = false;      /* tables built for the current metric (only when step_max > 0) */
+    uint8_t* cube_skip = nullptr; /* 2 x nb^3 bytes: the Cube modes' distance-to-solid table and its build scratch */
+    /* 2 x nb^3 bytes, the seeds (0 / 255) of the level-1 table (valid while skip_valid) and of the Cube table (always valid) — the tables
+       keep distances, from which an edit could not recover the seeds. */
+    uint8_t* seeds = nullptr;
+};
+
+/* The grid's axis order is {x, z, y}: grid axis a is xyz axis grid_axis(a), and the other way round. */
+constexpr int grid_axis(int a) { return a == 0 ? 0 : (a == 1 ? 2 : 1); }
+
+/* The small read-only arrays a launch dereferences, in ONE device allocation so that a frame in flight can keep its
+   own snapshot while the application already edits the scene for the next frame. */
+struct SceneArrays {
+    DVolume vols[VRT_MAX_VOLUMES];
+    DInstance inst[VRT_MAX_INSTANCES];
+    DBvhNode nodes[kMaxBvhNodes];
+    DPointLight point[VRT_MAX_POINT_LIGHTS];
+    DSpotLight spot[VRT_MAX_SPOT_LIGHTS];
+};
+
+/* One frame in flight (vrt_render_begin / vrt_render_end): stream, completion event, scene snapshot, device frame and
+   a pinned host frame. */
+struct FrameSlot {
+    hipStream_t stream = nullptr;  /* the device's flight stream (shared by the slots) */
+    hipEvent_t marched = nullptr;  /* the slot's march is done: its read-back may start (copy stream) */
+    hipEvent_t done = nullptr;
+    SceneArrays* d_scene = nullptr;
+    SceneArrays* h_scene = nullptr; /* pinned */
+    void* d_fb = nullptr;
+    void* h_fb = nullptr; /* pinned */
+    size_t fb_bytes = 0;
+    bool busy = false;
+    int ring = 0;       /* event-ring slot of the launch (timing) */
+};
+
+constexpr size_t kStatsBytesMax = (size_t)512 << 20; /* per-wave counters of one launch (1080p: 1.1 MB per frame, 3840x2160: 4.2 MB) */
+constexpr size_t kPassBytesMax = (size_t)4 << 30; /* hit records of one launch of the full closest hit in passes (1080p: 42 MB per frame) */
+
+/* A per-device cache buffer that a call grows on demand (ensure_buffer) and vrt_destroy frees.  Shared by the slots; nothing clears
+   one between calls. */
+struct Buffer {
+    void* p = nullptr;
+    size_t cap = 0;
+};
+enum BufferId {
+    kBufEditStaging,   /* vrt_volume_update_region and vrt_volume_download_region: the box's staging copy */
+    kBufEditScratch,   /* rebuild_derived over an edit's box: the level-2 table's region scratch */
+    kBufFill,          /* vrt_volume_fill_enclosed: the rounds' flags, the passable mask and the exterior labels */
+    kBufCompLabels,    /* vrt_volume_components: the labels with their header ... */
+    kBufCompTable,     /* ... and the component table */
+    kBufRedistTable,   /* vrt_volume_redistance: the tile table ... */
+    kBufRedistSurfels, /* ... and the compact surfels */
+    kBufMeshScratch,   /* vrt_volume_extract_mesh: the runs' records with their scan ... */
+    kBufMeshOut,       /* ... and the staged mesh */
+    kBufSmoothWarp,    /* vrt_volume_smooth: two fp32 copies of the work box and its weights; vrt_volume_warp: the value to store and the
+                          new id of every sample of the region's box (one buffer for the two calls) */
+    kBufQuery,         /* vrt_trace_rays_host: the rays and then the hit records of a batch */
+    kBufCount
+};
+
+struct DeviceState {
+    int ordinal = 0;
+    hipStream_t stream = nullptr;
+    DeviceVolume vol[VRT_MAX_VOLUMES];
+    DVolume* d_vols = nullptr;
+    DInstance* d_inst = nullptr;
+    DBvhNode* d_nodes = nullptr;
+    DPointLight* d_point = nullptr;
+    DSpotLight* d_spot = nullptr;
+    uint8_t* d_env = nullptr;
+    uint8_t* tex[VRT_MAX_TEXTURES] = {};
+    float* fb = nullptr;
+    size_t fb_bytes = 0;
+    /* per-wave records: one counter buffer per launch STREAM (kStatSlots streams at a time, least recently used
+       slot recycled), so frames in flight on different streams — the reference keeps 3 (DXConstants.cpp:23) — never
+       share one, and launches on one stream, which run in order, reuse theirs.  Buffers only ever grow, and an
+       outgrown buffer is retired, not freed, until vrt_destroy: a launch captured into a hipGraph has its buffer's
+       address baked into the kernarg and may be replayed at any later time. */
+    unsigned* d_stats[kStatSlots] = {};
+    size_t stats_cap[kStatSlots] = {}; /* blocks */
+    hipStream_t stats_stream[kStatSlots] = {};
+    bool stats_bound[kStatSlots] = {};
+    uint64_t stats_used[kStatSlots] = {}; /* launch number of the last use (LRU) */
+    std::vector<unsigned*> stats_retired;
+    /* three-pass full closest hit: hit records of a launch (16 + 4 bytes per pixel of the block's tiles + 8 per wave), per launch
+       stream like the counters, allocated by the first such launch of that size */
+    /* launches of more than kMaxBlockFrames frames: the frames' camera records, packed into pinned host memory and copied ahead of
+       the launch on its stream (per launch stream, like the counters); `cams_copied` says when the pinned copy may be packed again */
+    DCam* d_cams[kStatSlots] = {};
+    DCam* h_cams[kStatSlots] = {};
+    hipEvent_t cams_copied[kStatSlots] = {};
+    /* launches over per-frame scene state (vrt_block::scenes): the frames' sections (DDyn + instances + BVH + lights, kDynStride bytes
+       each), packed into pinned host memory and copied ahead of the launch together with the camera records */
+    char* d_dyn[kStatSlots] = {};
+    char* h_dyn[kStatSlots] = {};
+    void* d_pass[kStatSlots] = {};
+    size_t pass_cap[kStatSlots] = {}; /* records */
+    std::vector<void*> pass_retired;
+    /* vrt_render_block_host: the block's frames on the device and in pinned host memory (grown, never shrunk) */
+    void* d_blockfb = nullptr;
+    void* h_blockfb = nullptr;
+    size_t blockfb_bytes = 0;
+    hipStream_t copy_stream = nullptr;
+    hipStream_t flight_stream = nullptr; /* vrt_render_begin: the marches of the frames in flight */
+    hipEvent_t part_done = nullptr;
+    bool peer_to_first = false;  /* this device maps device 0's memory (hipDeviceEnablePeerAccess succeeded): the strided 2D gather copy may be used */
+    int last_slot = 0;
+    unsigned* d_diag = nullptr;  /* allocated on first use of VRT_FLAG_DIAG_TIMELINE (never in a capture) */
+    Buffer buf[kBufCount];       /* the calls' cache buffers (BufferId) */
+    int* d_box6 = nullptr;       /* rebuild_derived: the near bricks' box of the level-1 table */
+    /* the edit report of the brushes, stamp, smooth, fill, redistance and the mesh count: what the launch wrote (kBrushSlots partial
+       records, vrt_launch.h); quiesce allocates them */
+    DBrushSlot* d_brush = nullptr;
+    int last_blocks = 0;         /* workgroups per frame of the last launch */
+    int last_frames = 1;         /* frames of the last launch: vrt_last_timing / vrt_debug_wave_records read its LAST frame's records */
+    bool last_diag = false;
+    int last_form = 0;           /* vrt_debug_last_kernel_form */
+    hipEvent_t joined = nullptr; /* multi-device vrt_render: this device's strips have arrived in device 0's frame */
+    hipEvent_t ev0[kRing];
+    hipEvent_t ev1[kRing];
+    FrameSlot slot[VRT_FRAMES_IN_FLIGHT];
+    bool events_ok = false;
+    int ring_frames[kRing] = {}; /* frames the launch in this ring slot covered (vrt_timing_history_frames) */
+    bool timed[kRing] = {}; /* launch in this ring slot recorded its event pair (false: captured into a graph, or VRT_FLAG_NO_TIMING) */
+};
+
+}  // namespace vrt
+
+struct vrt_ctx {
+    std::vector<vrt::DeviceState> dev;
+    vrt::HostVolume vol[VRT_MAX_VOLUMES];
+    vrt::HostTexture tex[VRT_MAX_TEXTURES];
+    int env_size = 0;
+    int upload_format = VRT_FORMAT_F32; /* vrt_set_volume_format: device format of the following uploads */
+    bool have_scene = false;
+    bool arrays_uploaded = false; /* the device copies of inst / nodes / point / spot hold the packed scene (pack_scene defers them while frames are in flight) */
+    bool scene_stale = true; /* a volume was uploaded / freed / re-measured since the scene arrays were packed (boxes, BVH) */
+    vrt_scene scene;
+    vrt::DInstance inst[VRT_MAX_INSTANCES];
+    vrt::DBvhNode nodes[vrt::kMaxBvhNodes];
+    int n_nodes = 0;
+    vrt::DPointLight point[VRT_MAX_POINT_LIGHTS];
+    vrt::DSpotLight spot[VRT_MAX_SPOT_LIGHTS];
+    /* launch history */
+    uint64_t launches = 0;
+    int last_devices = 0; /* how many devices took part in the last launch */
+    uint32_t last_w = 0, last_h = 0;
+    float last_gather_ms = 0.f, last_total_ms = 0.f;
+    float* gather = nullptr; /* full frame on device 0 (multi-device only) */
+    size_t gather_bytes = 0;
+    void* comm = nullptr;    /* ncclComm_t of vrt_comm_init (one process per GPU) */
+    int comm_world = 0, comm_rank = 0;
+    bool sizes_agreed = false;
+    size_t expect_tile_bytes = 0, expect_chunk_bytes = 0; /* vrt_comm_expect_sizes: what every rank agreed to pass (0: not agreed, unchecked) */
+};
+
+#define HIP_TRY(expr)                                                                              \
+    do {                                                                                           \
+        hipError_t e_ = (expr);                                                                    \
+        if (e_ != hipSuccess) {                                                                    \
+            fprintf(stderr, "[vrt] %s failed: %s (%s:%d)\n", #expr, hipGetErrorString(e_), __FILE__, \
+                    __LINE__);                                                                     \
+            return e_ == hipErrorOutOfMemory ? VRT_ERR_OOM : VRT_ERR_HIP;                           \
+        }                                                                                          \
+    } while (0)
+
+namespace vrt {
+
+inline bool valid_slot(int slot) { return slot >= 0 && slot < VRT_MAX_VOLUMES; }
+
+/* Grows a per-device cache buffer to at least `bytes` (its contents are not kept). */
+int ensure_buffer(Buffer& b, size_t bytes);
+
+/* ---- The volume slots (vrt_slots.hip) ---- */
+/* One slot as the kernels read it (a DVolume of the volume table, or of a frame in flight's snapshot). */
+void fill_dvolume(const vrt_ctx* ctx, const DeviceState& D, const HostVolume& h, const DeviceVolume& d, DVolume& out);
+/* The volume table of every device, from the slots as they are now. */
+int sync_volume_table(vrt_ctx* ctx);
+/* Frees what one device holds of a slot. */
+int free_device_volume(DeviceState& D, int slot);
+
+/* ---- What the volume edit calls share (defined in vrt_slots.hip) ---- */
+/* The caller's sample box: origin + size, or (both NULL, where the call allows it) the whole grid, as its first and last sample. */
+int clip_box(int N, const int* origin, const int* size, int lo[3], int hi[3]);
+/* Once per call, ahead of the first write: waits for what is enqueued on every device and gives each its report records. */
+int quiesce(vrt_ctx* ctx);
+struct Written {
+    int lo[3], hi[3];
+    unsigned long long low, high;
+};
+/* What a launch reported on D's stream (one synchronisation): the written box in xyz and the two halves of `counts`. */
+int read_report(DeviceState& D, int N, Written& got);
+vrt_brush_result brush_result(const Written& got);
+struct DerivedBoxes {
+    EditBox samples, cells, bricks;
+};
+/* The {x, z, y} boxes of samples, cells and bricks that an edit of the samples lo..hi (xyz, inclusive) touches. */
+DerivedBoxes derived_boxes(const HostVolume& h, const int lo_xyz[3], const int hi_xyz[3]);
+/* One device's samples are written: what the slot derives from them, recomputed over the xyz box lo..hi, unless `relevant` is 0. */
+int rebuild_written(vrt_ctx* ctx, DeviceState& D, int slot, const int lo[3], const int hi[3], unsigned long long relevant, bool& changed);
+/* After the last device: when something changed, the scene is stale and the volume table follows. */
+int finish_edit(vrt_ctx* ctx, bool changed);
+
+}  // namespace vrt

@@ -1,4 +1,4 @@
-/* vrt_fill.hip — the kernels of vrt_volume_fill_enclosed (include/vrt.h): which passable samples (d > 0) of a resident volume the
+/* vrt_fill.hip — vrt_volume_fill_enclosed (include/vrt.h), kernels to driver: which passable samples (d > 0) of a resident volume the
  * grid's faces cannot reach through 6-neighbour steps over passable samples, and the edit that turns them solid.
  *
  * Labels ("exterior") live in a scratch buffer next to the passable mask, both as bits: a row of samples along y is row_bytes(N)
@@ -8,11 +8,13 @@
  * on another workgroup anywhere: convergence comes from the host launching rounds until one changes nothing. */
 #include <hip/hip_runtime.h>
 
+#include <math.h>
+
 #include <algorithm>
 
 #include "fill_core.h"
 #include "edit_report.h"
-#include "vrt_launch.h"
+#include "vrt_context.h"
 
 namespace vrt {
 
@@ -21,6 +23,7 @@ namespace {
 using vrt_fill::kTile;
 
 constexpr size_t kFlagBytes = 256; /* the rounds' flags, ahead of the two bit grids */
+constexpr int kFillRoundsPerRead = 8; /* propagation rounds enqueued between two reads of their flags: one stream sync per batch */
 static_assert(kFillRoundsPerRead * sizeof(int) <= kFlagBytes, "one flag per round of a batch");
 
 /* Passable mask of every row byte, and the seeds: the passable samples with an index 0 or N - 1 on some axis.  One lane per byte:
@@ -129,18 +132,22 @@ uint8_t* pas_of(void* scratch) { return static_cast<uint8_t*>(scratch) + kFlagBy
 uint8_t* lab_of(void* scratch, int N) { return pas_of(scratch) + bits_bytes(N); }
 unsigned stride_grid(size_t count) { return (unsigned)std::max<size_t>(1, std::min<size_t>((count + 255) / 256, 1u << 16)); }
 
-}  // namespace
-
+/* scratch: fill_scratch_bytes(N) of device memory holding the flags of a batch of rounds, the
+   passable mask and the exterior labels (one bit per sample each), valid from launch_fill_mask to launch_fill_apply. */
 size_t fill_scratch_bytes(int N) { return kFlagBytes + 2 * bits_bytes(N); }
 
+/* the flags of a batch of rounds (device memory) */
 const int* fill_round_flags(const void* scratch) { return static_cast<const int*>(scratch); }
 
+/* The mask of the samples with d > 0 (a TEXEL16 field decoded) and the seeds: those of them on a face of the grid. */
 hipError_t launch_fill_mask(const float* dense, bool texel16, int N, void* scratch, hipStream_t stream) {
     hipLaunchKernelGGL(fill_mask_kernel, dim3(stride_grid(bits_bytes(N))), dim3(256), 0, stream, dense, (int)texel16, N, pas_of(scratch),
                        lab_of(scratch, N));
     return hipGetLastError();
 }
 
+/* `rounds` (1 .. kFillRoundsPerRead) propagation rounds, one workgroup per 8^3 tile each; round r sets fill_round_flags(scratch)[r]
+   (device memory, zeroed first) when it labelled a sample.  A round that labelled none has reached the exterior set. */
 hipError_t launch_fill_rounds(int N, void* scratch, int rounds, hipStream_t stream) {
     if (rounds < 1 || rounds > kFillRoundsPerRead) return hipErrorInvalidValue;
     hipError_t e = hipMemsetAsync(scratch, 0, kFlagBytes, stream);
@@ -152,6 +159,8 @@ hipError_t launch_fill_rounds(int N, void* scratch, int rounds, hipStream_t stre
     return hipGetLastError();
 }
 
+/* Every passable sample without a label stores -(d + wall) (its texel when texel16) and, material_id >= 0, that id; slots: zeroed, then
+   the written samples' counts and box (the edit report, vrt_launch.h). */
 hipError_t launch_fill_apply(bool texel16, float* dense, uint8_t* material, int N, const void* scratch, float wall, int material_id,
                              DBrushSlot* slots, hipStream_t stream) {
     hipError_t e = clear_report(slots, stream);
@@ -167,4 +176,64 @@ hipError_t launch_fill_apply(bool texel16, float* dense, uint8_t* material, int 
     return hipGetLastError();
 }
 
+}  // namespace
+
 }  // namespace vrt
+
+using namespace vrt;
+
+static_assert(sizeof(vrt_fill_result) == 40, "vrt.h states this size");
+
+extern "C" {
+
+/* vrt_volume_fill_enclosed: per device, the passable mask and the face seeds (launch_fill_mask), propagation rounds in batches of
+ * kFillRoundsPerRead with one read of their flags per batch until a round labels nothing, then the edit of the samples left without a
+ * label (launch_fill_apply), which reports like a brush launch; what the slot derives from the samples is recomputed over the written
+ * box (rebuild_derived).  Afterwards every buffer equals what upload_volume builds from the filled volume. */
+int vrt_volume_fill_enclosed(vrt_ctx* ctx, int slot, float wall, int material, vrt_fill_result* result) {
+    if (!ctx) return VRT_ERR_INVALID;
+    if (!valid_slot(slot) || !ctx->vol[slot].used) return VRT_ERR_SLOT;
+    if (!std::isfinite(wall) || wall < 0.f || material < -1 || material > 255) return VRT_ERR_INVALID;
+    HostVolume& h = ctx->vol[slot];
+    const int N = h.N;
+    if (result) *result = vrt_fill_result{{N, N, N}, {-1, -1, -1}, 0, 0, 0};
+    const bool texel16 = h.format == VRT_FORMAT_TEXEL16;
+    /* a round that changes something labels at least one sample, so no run needs more rounds than the grid has samples */
+    const unsigned long long round_cap = (unsigned long long)N * N * N + 1ull;
+    int rc = quiesce(ctx);
+    if (rc != VRT_OK) return rc;
+    bool changed = false;
+    for (size_t di = 0; di < ctx->dev.size(); di++) {
+        DeviceState& D = ctx->dev[di];
+        HIP_TRY(hipSetDevice(D.ordinal));
+        DeviceVolume& v = D.vol[slot];
+        rc = ensure_buffer(D.buf[kBufFill], fill_scratch_bytes(N));
+        if (rc != VRT_OK) return rc;
+        HIP_TRY(launch_fill_mask(v.dense, texel16, N, D.buf[kBufFill].p, D.stream));
+        unsigned long long rounds = 0;
+        for (bool settled = false; !settled;) {
+            if (rounds >= round_cap) {
+                fprintf(stderr, "[vrt] vrt_volume_fill_enclosed: %llu rounds without settling on a grid of %d^3\n", rounds, N);
+                return VRT_ERR_HIP;
+            }
+            int flags[kFillRoundsPerRead];
+            HIP_TRY(launch_fill_rounds(N, D.buf[kBufFill].p, kFillRoundsPerRead, D.stream));
+            HIP_TRY(hipMemcpyAsync(flags, fill_round_flags(D.buf[kBufFill].p), sizeof flags, hipMemcpyDeviceToHost, D.stream));
+            HIP_TRY(hipStreamSynchronize(D.stream));
+            rounds += kFillRoundsPerRead;
+            for (int f : flags) settled = settled || f == 0;
+        }
+        HIP_TRY(launch_fill_apply(texel16, v.dense, v.material, N, D.buf[kBufFill].p, wall, material, D.d_brush, D.stream));
+        Written got;
+        rc = read_report(D, N, got);
+        if (rc != VRT_OK) return rc;
+        if (di == 0 && result)
+            *result = vrt_fill_result{{got.lo[0], got.lo[1], got.lo[2]}, {got.hi[0], got.hi[1], got.hi[2]}, got.low,
+                                      (uint32_t)std::min<unsigned long long>(rounds, 0xffffffffull), 0};
+        rc = rebuild_written(ctx, D, slot, got.lo, got.hi, got.low, changed);
+        if (rc != VRT_OK) return rc;
+    }
+    return finish_edit(ctx, changed);
+}
+
+}  // extern "C"

@@ -1,19 +1,12 @@
-/* vrt_launch.h — host-callable launch wrappers: the march and the ray queries (vrt_kernels.hip), what a slot derives from its dense grid
-   (vrt_volume.hip) and one file per edit call (vrt_brush.hip, vrt_fill.hip, vrt_redistance.hip, vrt_stamp.hip, vrt_smooth.hip,
-   vrt_warp.hip, vrt_components.hip, vrt_mesh.hip). */
+/* vrt_launch.h — what one unit launches for another: the march and the ray queries (vrt_kernels.hip), what a slot derives from its dense
+   grid (vrt_volume.hip), and the box and report records every edit unit shares with its kernels.  A volume call's own launches, scratch
+   layout and kernarg structs live in its vrt_<call>.hip. */
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stddef.h>
 #include <stdint.h>
 #include "../../include/vrt.h"
 #include "vrt_device.h"
-
-namespace vrt_stamp_core {
-struct Rule; /* stamp_core.h */
-}
-namespace vrt_components_core {
-struct Component; /* components_core.h */
-}
 
 namespace vrt {
 
@@ -63,10 +56,6 @@ __host__ __device__ inline void box_coords(const EditBox& b, size_t i, int& x, i
 __host__ __device__ inline size_t box_index(const EditBox& b, int x, int z, int y) {
     return ((size_t)(x - b.lo[0]) * b.n[1] + (size_t)(z - b.lo[1])) * b.n[2] + (size_t)(y - b.lo[2]);
 }
-/* The staged box (VVoxel records, or floats followed by bytes when has_material; x slowest, then z, then y) -> dense + material,
-   quantised like launch_quantize_field when texel16. */
-hipError_t launch_scatter_region(const void* staging, bool voxels, bool has_material, bool texel16, float* dense, uint8_t* material, int N,
-                                 const EditBox& box, hipStream_t stream);
 /* dense grid -> the brick records of `format` (fp32: 512 B, VRT_FORMAT_TEXEL16: 256 B of int16) and, when cells_or_null (VRT_PATH_CELLS),
    the 64 cell records of 8 int16 of every brick of a brick box. */
 hipError_t launch_retile_region(const float* dense, void* bricks, void* cells_or_null, int format, int N, int nb, const EditBox& bricks_box,
@@ -85,20 +74,6 @@ size_t nibble_region_scratch_bytes(int N, const EditBox& changed);
 hipError_t launch_nibble_region(const float* dense, unsigned* nib, void* scratch, int N, int nb, float density_scale, float step_max,
                                 const EditBox& changed, hipStream_t stream);
 
-/* vrt_volume_apply_brushes: one record as the kernel reads it — the caller's vrt_brush with the blend width already in density
-   units (k = blend * unit) and the sample box outside which the record writes nothing, in the grid's own axis order {x, z, y}. */
-struct DBrush {
-    int32_t shape, op;
-    float a[3], b[3];
-    float radius, k, reach;
-    int32_t material;
-    int32_t lo[3], hi[3]; /* inclusive, clipped to the grid */
-};
-struct DBrushList {
-    int32_t n;
-    float unit; /* density units per cell: cell / density_scale */
-    DBrush rec[VRT_MAX_BRUSHES];
-};
 /* The edit report: what a launch of an edit call (brushes, fill, redistance, stamp, smooth, warp) or of the mesh count reports (device memory,
    zeroed by the launch; the kernels' side is edit_report.h): the written samples' box and counts, kept in kBrushSlots partial records
    that the host merges — thousands of waves report at once, and atomics on one word take their turns (a single record made the brush
@@ -112,116 +87,5 @@ struct DBrushSlot {
                                   redistance: samples nearer than the band; fill, stamp, smooth: all of them */
     uint32_t pad_[24];         /* one 128-byte line per slot */
 };
-/* The records of `list`, in order, over the samples of `box` (the union of the records' boxes), in place; slots: zeroed, then the
-   written samples' counts and box (the edit report, above). */
-hipError_t launch_brush_region(const DBrushList& list, bool texel16, float* dense, uint8_t* material, int N, const EditBox& box,
-                               DBrushSlot* slots, hipStream_t stream);
-/* vrt_volume_download_region: the samples of `box` as VVoxel records (x slowest, then z, then y), a TEXEL16 field decoded. */
-hipError_t launch_gather_region(const float* dense, const uint8_t* material, bool texel16, int N, const EditBox& box, void* voxels_out,
-                                hipStream_t stream);
-
-
-/* vrt_volume_fill_enclosed (vrt_fill.hip).  scratch: fill_scratch_bytes(N) of device memory holding the flags of a batch of rounds, the
-   passable mask and the exterior labels (one bit per sample each), valid from launch_fill_mask to launch_fill_apply. */
-constexpr int kFillRoundsPerRead = 8; /* propagation rounds enqueued between two reads of their flags: one stream sync per batch */
-size_t fill_scratch_bytes(int N);
-/* The mask of the samples with d > 0 (a TEXEL16 field decoded) and the seeds: those of them on a face of the grid. */
-hipError_t launch_fill_mask(const float* dense, bool texel16, int N, void* scratch, hipStream_t stream);
-/* `rounds` (1 .. kFillRoundsPerRead) propagation rounds, one workgroup per 8^3 tile each; round r sets fill_round_flags(scratch)[r]
-   (device memory, zeroed first) when it labelled a sample.  A round that labelled none has reached the exterior set. */
-hipError_t launch_fill_rounds(int N, void* scratch, int rounds, hipStream_t stream);
-const int* fill_round_flags(const void* scratch);
-/* Every passable sample without a label stores -(d + wall) (its texel when texel16) and, material_id >= 0, that id; slots: zeroed, then
-   the written samples' counts and box (the edit report, above). */
-hipError_t launch_fill_apply(bool texel16, float* dense, uint8_t* material, int N, const void* scratch, float wall, int material_id,
-                             DBrushSlot* slots, hipStream_t stream);
-
-/* vrt_volume_redistance (vrt_redistance.hip).  table: redistance_table_bytes(N) of device memory — the surfel counter and one
-   {start, count} range per 8^3 tile of the grid —, valid from launch_redistance_count to launch_redistance_distance.  grown: the box
-   grown by band + 1 and clipped to the grid; boxes are in the grid's own axis order like every EditBox. */
-size_t redistance_table_bytes(int N);
-size_t redistance_surfel_bytes(unsigned surfels);
-const unsigned* redistance_surfel_count(const void* table); /* device memory: the total after launch_redistance_count */
-/* Zeroes the table, then counts the surfels of every tile of `grown` and reserves their ranges. */
-hipError_t launch_redistance_count(const float* dense, bool texel16, int N, int from, const EditBox& grown, void* table, hipStream_t stream);
-/* Writes the surfels (centre xyz, normal xyz: 24 B) into their tiles' ranges; `capacity` surfels fit. */
-hipError_t launch_redistance_surfels(const float* dense, bool texel16, int N, int from, const EditBox& grown, void* table, void* surfels,
-                                     unsigned capacity, hipStream_t stream);
-/* Every sample of `box` stores its banded signed distance (its texel when texel16), in place; slots: zeroed, then the written samples'
-   box and count (the edit report, above), with the count of samples nearer than the band in the high half of `counts`. */
-hipError_t launch_redistance_distance(bool texel16, float* dense, int N, int band, float unit, const EditBox& box, const void* table,
-                                      const void* surfels, DBrushSlot* slots, hipStream_t stream);
-
-/* vrt_volume_stamp (vrt_stamp.hip): the rule of stamp_core.h over the destination samples of `box` (the footprint: outside it the
-   source's box cannot be hit), in place; the source's dense and material grids are only read and must not be the destination's.
-   slots: zeroed, then the written samples' counts and box (the edit report, above). */
-hipError_t launch_stamp_region(const vrt_stamp_core::Rule& rule, bool src_texel16, const float* src_dense, const uint8_t* src_material,
-                               bool dst_texel16, float* dense, uint8_t* material, int N, const EditBox& box, DBrushSlot* slots,
-                               hipStream_t stream);
-
-/* vrt_volume_smooth (vrt_smooth.hip): the rule of smooth_core.h.  work: the region's box grown by one sample and clipped to the grid;
-   region: the box outside which no sample is in the region.  scratch: smooth_scratch_bytes(work) of device memory — two fp32 copies
-   of the work box and its weights.  Gathers the work box, runs the record's passes from one copy to the other (one launch each), then
-   stores the region samples whose bits changed; slots: zeroed, then the written samples' counts and box (the edit report, above). */
-size_t smooth_scratch_bytes(const EditBox& work);
-hipError_t launch_smooth(const vrt_smooth& rule, bool texel16, float* dense, uint8_t* material, int N, const EditBox& work,
-                         const EditBox& region, void* scratch, DBrushSlot* slots, hipStream_t stream);
-
-/* vrt_volume_warp (vrt_warp.hip): the rule of warp_core.h.  region: the box outside which no sample is in the region; off: the
-   record's inflate in density units (warp_core.h, off_of).  scratch: warp_scratch_bytes(region) of device memory — the value to store
-   (one float) and the new id (one byte) of every sample of the box.  Computes both from the volume as it is, writing nothing to it, then
-   stores the samples whose bits or id changed; slots: zeroed, then the written samples' counts and box (the edit report, above), with
-   the count of density writes in the high half of `counts`. */
-size_t warp_scratch_bytes(const EditBox& region);
-hipError_t launch_warp(const vrt_warp& rule, float off, bool texel16, float* dense, uint8_t* material, int N, const EditBox& region,
-                       void* scratch, DBrushSlot* slots, hipStream_t stream);
-
-/* vrt_volume_components (vrt_components.hip).  scratch: components_scratch_bytes(N) of device memory — a header of counters and two
-   words per sample: the labels (components_core.h) and, at every root's key, its row in the table —, valid from
-   launch_components_label to launch_components_apply.  table: components_table_bytes(components) of device memory, 32 B a component. */
-size_t components_scratch_bytes(int N);
-size_t components_table_bytes(unsigned components);
-/* device memory: the labels, one word per sample in the grid's own order, every solid sample's the lowest key of its component
-   once launch_components_label has run; the header's words {gave up, components} */
-const unsigned* components_labels(const void* scratch);
-const unsigned* components_header(const void* scratch);
-/* Labels every sample: the tiles on their own, the union of what meets across tile faces, every label made its root; counts the
-   roots.  A find or a union that ran into its cap leaves the header's first word non-zero. */
-hipError_t launch_components_label(const float* dense, bool texel16, int N, void* scratch, hipStream_t stream);
-/* One row of the table per component, in no particular order: its key, its samples and their box; `components`: the header's count. */
-hipError_t launch_components_stats(int N, void* scratch, void* table, unsigned components, hipStream_t stream);
-/* Row `row` of a host copy of the table. */
-void components_decode_row(const void* table, size_t row, int N, vrt_components_core::Component& out);
-/* The samples of every component the predicate removes (mode, a, b: components_core.h, removed_by) store removed_density (its texel
-   when texel16) and, material_id >= 0, that id; their halo stores the gap.  slots: zeroed, then the written samples' counts and box
-   (the edit report, above).  The labels are spent afterwards. */
-hipError_t launch_components_apply(bool texel16, float* dense, uint8_t* material, int N, void* scratch, const void* table, int mode, unsigned a,
-                                   unsigned b, float gap, int material_id, DBrushSlot* slots, hipStream_t stream);
-
-/* vrt_volume_extract_mesh (vrt_mesh.hip).  The cell box of a sample box, in xyz order (the mesh rule's own): its first cell, its cells
-   per axis (one less than the samples; none when the box is one sample thick somewhere) and how many runs of 64 cells a row along y has. */
-struct MeshGrid {
-    int N;
-    int lo[3];
-    int n[3];
-    int runs_y;
-};
-MeshGrid mesh_grid(int N, const int lo_xyz[3], const int hi_xyz[3]); /* the samples lo..hi, inclusive */
-bool mesh_grid_empty(const MeshGrid& grid);
-/* scratch: mesh_scratch_bytes(grid) of device memory — the totals, the scan's block sums and one 16-byte record per run —, valid from
-   launch_mesh_count to launch_mesh_emit. */
-size_t mesh_scratch_bytes(const MeshGrid& grid);
-/* device memory: vertices (low half) and quads (high half) of the whole mesh after launch_mesh_count */
-const unsigned long long* mesh_totals(const void* scratch);
-/* Counts every run's vertices and quads and turns the counts into the runs' first vertex and first quad (a prefix sum in run order);
-   slots: zeroed, then the active cells' box in inv_lo / hi1 (the edit report, above; `counts` stays 0).  Not for an
-   empty grid. */
-hipError_t launch_mesh_count(const float* dense, bool texel16, const MeshGrid& grid, float iso, void* scratch, DBrushSlot* slots,
-                             hipStream_t stream);
-/* Writes the vertices (3 floats of object space, 3 floats of normal, 1 material byte each) and the quads (6 indices each) at their
-   numbers; any output may be NULL and is skipped.  vertex_cap / quad_cap: what the outputs hold. */
-hipError_t launch_mesh_emit(const float* dense, const uint8_t* material, bool texel16, const MeshGrid& grid, float iso, float cell, float extent,
-                            void* scratch, float* positions, float* normals, uint8_t* materials, uint32_t* indices, unsigned vertex_cap,
-                            unsigned quad_cap, hipStream_t stream);
 
 }  // namespace vrt

@@ -1,4 +1,4 @@
-/* vrt_mesh.hip — the kernels of vrt_volume_extract_mesh (include/vrt.h): the zero surface of (field - iso) over a box of a resident
+/* vrt_mesh.hip — vrt_volume_extract_mesh (include/vrt.h), kernels to driver: the zero surface of (field - iso) over a box of a resident
  * volume as an indexed triangle mesh, by naive surface nets.  The rule is csrc/mesh_core.h.
  *
  * The unit of work is a run: 64 consecutive cells along y of one (x, z) row of the cell box, one wave, lane = cell.  Runs are numbered
@@ -13,11 +13,22 @@
  *           the output does not depend on how the device schedules its waves. */
 #include <hip/hip_runtime.h>
 
+#include <math.h>
+
 #include "mesh_core.h"
 #include "edit_report.h"
-#include "vrt_launch.h"
+#include "vrt_context.h"
 
 namespace vrt {
+
+/* The cell box of a sample box, in xyz order (the mesh rule's own): its first cell, its cells
+   per axis (one less than the samples; none when the box is one sample thick somewhere) and how many runs of 64 cells a row along y has. */
+struct MeshGrid {
+    int N;
+    int lo[3];
+    int n[3];
+    int runs_y;
+};
 
 namespace {
 
@@ -232,8 +243,7 @@ u64* totals_of(void* scratch) { return static_cast<u64*>(scratch); }
 u64* sums_of(void* scratch) { return reinterpret_cast<u64*>(static_cast<char*>(scratch) + kHeaderBytes); }
 Run* records_of(void* scratch, unsigned n_runs) { return reinterpret_cast<Run*>(static_cast<char*>(scratch) + kHeaderBytes + sums_bytes(n_runs)); }
 
-}  // namespace
-
+/* the samples lo..hi, inclusive */
 MeshGrid mesh_grid(int N, const int lo_xyz[3], const int hi_xyz[3]) {
     MeshGrid G;
     G.N = N;
@@ -247,13 +257,19 @@ MeshGrid mesh_grid(int N, const int lo_xyz[3], const int hi_xyz[3]) {
 
 bool mesh_grid_empty(const MeshGrid& G) { return G.n[0] < 1 || G.n[1] < 1 || G.n[2] < 1; }
 
+/* scratch: mesh_scratch_bytes(grid) of device memory — the totals, the scan's block sums and one 16-byte record per run —, valid from
+   launch_mesh_count to launch_mesh_emit. */
 size_t mesh_scratch_bytes(const MeshGrid& G) {
     const unsigned n_runs = runs_of(G);
     return kHeaderBytes + sums_bytes(n_runs) + (size_t)n_runs * sizeof(Run);
 }
 
+/* device memory: vertices (low half) and quads (high half) of the whole mesh after launch_mesh_count */
 const unsigned long long* mesh_totals(const void* scratch) { return static_cast<const unsigned long long*>(scratch); }
 
+/* Counts every run's vertices and quads and turns the counts into the runs' first vertex and first quad (a prefix sum in run order);
+   slots: zeroed, then the active cells' box in inv_lo / hi1 (the edit report, vrt_launch.h; `counts` stays 0).  Not for an
+   empty grid. */
 hipError_t launch_mesh_count(const float* dense, bool texel16, const MeshGrid& G, float iso, void* scratch, DBrushSlot* slots, hipStream_t stream) {
     if (mesh_grid_empty(G)) return hipErrorInvalidValue;
     hipError_t e = clear_report(slots, stream);
@@ -271,6 +287,8 @@ hipError_t launch_mesh_count(const float* dense, bool texel16, const MeshGrid& G
     return hipGetLastError();
 }
 
+/* Writes the vertices (3 floats of object space, 3 floats of normal, 1 material byte each) and the quads (6 indices each) at their
+   numbers; any output may be NULL and is skipped.  vertex_cap / quad_cap: what the outputs hold. */
 hipError_t launch_mesh_emit(const float* dense, const uint8_t* material, bool texel16, const MeshGrid& G, float iso, float cell, float extent,
                             void* scratch, float* positions, float* normals, uint8_t* materials, uint32_t* indices, unsigned vertex_cap,
                             unsigned quad_cap, hipStream_t stream) {
@@ -287,4 +305,71 @@ hipError_t launch_mesh_emit(const float* dense, const uint8_t* material, bool te
     return hipGetLastError();
 }
 
+}  // namespace
+
 }  // namespace vrt
+
+using namespace vrt;
+
+static_assert(sizeof(vrt_mesh_result) == 40, "vrt.h states this size");
+
+extern "C" {
+
+/* vrt_volume_extract_mesh, on device 0: the runs of the cell box are counted and scanned (launch_mesh_count), the host reads the two
+ * totals and the active cells' box, checks the caller's capacities and sizes the staged mesh, the runs write it (launch_mesh_emit) and
+ * the arrays the caller asked for are copied out.  The slot is only read. */
+int vrt_volume_extract_mesh(vrt_ctx* ctx, int slot, float iso, const int* origin, const int* size, float* positions, float* normals, uint8_t* materials,
+                 size_t vertex_capacity, uint32_t* indices, size_t index_capacity, vrt_mesh_result* result) {
+    if (!ctx || !std::isfinite(iso)) return VRT_ERR_INVALID;
+    if ((origin == nullptr) != (size == nullptr)) return VRT_ERR_INVALID; /* ahead of the slot's check, as ever; clip_box needs the slot's N */
+    if (!valid_slot(slot) || !ctx->vol[slot].used) return VRT_ERR_SLOT;
+    const HostVolume& h = ctx->vol[slot];
+    const int N = h.N;
+    int lo[3], hi[3];
+    int rc = clip_box(N, origin, size, lo, hi);
+    if (rc != VRT_OK) return rc;
+    const bool wanted = positions || normals || materials || indices;
+    const bool texel16 = h.format == VRT_FORMAT_TEXEL16;
+    const float cell = (h.extent * 2.0f) / (float)(N - 1);
+    rc = quiesce(ctx);
+    if (rc != VRT_OK) return rc;
+    vrt_mesh_result got = {{N, N, N}, {-1, -1, -1}, 0, 0};
+    const MeshGrid grid = mesh_grid(N, lo, hi);
+    DeviceState& D = ctx->dev[0];
+    if (!mesh_grid_empty(grid)) {
+        HIP_TRY(hipSetDevice(D.ordinal));
+        rc = ensure_buffer(D.buf[kBufMeshScratch], mesh_scratch_bytes(grid));
+        if (rc != VRT_OK) return rc;
+        HIP_TRY(launch_mesh_count(D.vol[slot].dense, texel16, grid, iso, D.buf[kBufMeshScratch].p, D.d_brush, D.stream));
+        unsigned long long totals = 0;
+        Written cells; /* the active cells' box */
+        HIP_TRY(hipMemcpyAsync(&totals, mesh_totals(D.buf[kBufMeshScratch].p), sizeof totals, hipMemcpyDeviceToHost, D.stream));
+        rc = read_report(D, N, cells); /* the totals arrive in the same synchronisation */
+        if (rc != VRT_OK) return rc;
+        got = vrt_mesh_result{{cells.lo[0], cells.lo[1], cells.lo[2]}, {cells.hi[0], cells.hi[1], cells.hi[2]}, totals & 0xffffffffull, totals >> 32};
+    }
+    if (result) *result = got;
+    if (!wanted) return VRT_OK;
+    if (vertex_capacity < got.vertices || index_capacity < 6 * got.quads) return VRT_ERR_INVALID;
+    if (got.vertices == 0) return VRT_OK;
+    /* the staged mesh: positions, normals, indices, materials, each where the one before ends (all but the last a multiple of 4 bytes) */
+    const size_t V = (size_t)got.vertices, Q = (size_t)got.quads;
+    const size_t at_normals = V * 3 * sizeof(float), at_indices = at_normals * 2, at_materials = at_indices + Q * 6 * sizeof(uint32_t);
+    rc = ensure_buffer(D.buf[kBufMeshOut], at_materials + V);
+    if (rc != VRT_OK) return rc;
+    char* out = static_cast<char*>(D.buf[kBufMeshOut].p);
+    float* d_positions = positions ? reinterpret_cast<float*>(out) : nullptr;
+    float* d_normals = normals ? reinterpret_cast<float*>(out + at_normals) : nullptr;
+    uint32_t* d_indices = indices && Q ? reinterpret_cast<uint32_t*>(out + at_indices) : nullptr;
+    uint8_t* d_materials = materials ? reinterpret_cast<uint8_t*>(out + at_materials) : nullptr;
+    HIP_TRY(launch_mesh_emit(D.vol[slot].dense, D.vol[slot].material, texel16, grid, iso, cell, h.extent, D.buf[kBufMeshScratch].p, d_positions, d_normals,
+                             d_materials, d_indices, (unsigned)V, (unsigned)Q, D.stream));
+    if (d_positions) HIP_TRY(hipMemcpyAsync(positions, d_positions, at_normals, hipMemcpyDeviceToHost, D.stream));
+    if (d_normals) HIP_TRY(hipMemcpyAsync(normals, d_normals, at_normals, hipMemcpyDeviceToHost, D.stream));
+    if (d_indices) HIP_TRY(hipMemcpyAsync(indices, d_indices, Q * 6 * sizeof(uint32_t), hipMemcpyDeviceToHost, D.stream));
+    if (d_materials) HIP_TRY(hipMemcpyAsync(materials, d_materials, V, hipMemcpyDeviceToHost, D.stream));
+    HIP_TRY(hipStreamSynchronize(D.stream));
+    return VRT_OK;
+}
+
+}  // extern "C"

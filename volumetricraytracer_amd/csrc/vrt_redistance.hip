@@ -1,4 +1,4 @@
-/* vrt_redistance.hip — the kernels of vrt_volume_redistance (include/vrt.h): the samples of a box of a resident volume rewritten as the
+/* vrt_redistance.hip — vrt_volume_redistance (include/vrt.h), kernels to driver: the samples of a box of a resident volume rewritten as the
  * signed distance, within a band, to the zero surface of the field the slot holds.  The rule is csrc/redistance_core.h.
  *
  * Two passes over 8^3-sample tiles aligned with the grid.  The surfel pass (one wave per tile of the box grown by band + 1) classifies
@@ -10,10 +10,11 @@
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
+#include <vector>
 
 #include "redistance_core.h"
 #include "edit_report.h"
-#include "vrt_launch.h"
+#include "vrt_context.h"
 
 namespace vrt {
 
@@ -193,8 +194,9 @@ void tile_span(const EditBox& box, int first[3], dim3& grid) {
     grid = dim3(n[2], n[1], n[0]); /* y fastest, like the grid */
 }
 
-}  // namespace
-
+/* table: redistance_table_bytes(N) of device memory — the surfel counter and one
+   {start, count} range per 8^3 tile of the grid —, valid from launch_redistance_count to launch_redistance_distance.  grown: the box
+   grown by band + 1 and clipped to the grid; boxes are in the grid's own axis order like every EditBox. */
 size_t redistance_table_bytes(int N) {
     const size_t T = (size_t)tiles_of(N);
     return kHeaderBytes + T * T * T * sizeof(TileRange);
@@ -202,8 +204,10 @@ size_t redistance_table_bytes(int N) {
 
 size_t redistance_surfel_bytes(unsigned surfels) { return std::max<size_t>(surfels, 1) * 6 * sizeof(float); }
 
+/* device memory: the total after launch_redistance_count */
 const unsigned* redistance_surfel_count(const void* table) { return static_cast<const unsigned*>(table); }
 
+/* Zeroes the table, then counts the surfels of every tile of `grown` and reserves their ranges. */
 hipError_t launch_redistance_count(const float* dense, bool texel16, int N, int from, const EditBox& grown, void* table, hipStream_t stream) {
     hipError_t e = hipMemsetAsync(table, 0, redistance_table_bytes(N), stream);
     if (e != hipSuccess) return e;
@@ -215,6 +219,7 @@ hipError_t launch_redistance_count(const float* dense, bool texel16, int N, int 
     return hipGetLastError();
 }
 
+/* Writes the surfels (centre xyz, normal xyz: 24 B) into their tiles' ranges; `capacity` surfels fit. */
 hipError_t launch_redistance_surfels(const float* dense, bool texel16, int N, int from, const EditBox& grown, void* table, void* surfels,
                                      unsigned capacity, hipStream_t stream) {
     int first[3];
@@ -225,6 +230,8 @@ hipError_t launch_redistance_surfels(const float* dense, bool texel16, int N, in
     return hipGetLastError();
 }
 
+/* Every sample of `box` stores its banded signed distance (its texel when texel16), in place; slots: zeroed, then the written samples'
+   box and count (the edit report, vrt_launch.h), with the count of samples nearer than the band in the high half of `counts`. */
 hipError_t launch_redistance_distance(bool texel16, float* dense, int N, int band, float unit, const EditBox& box, const void* table,
                                       const void* surfels, DBrushSlot* slots, hipStream_t stream) {
     if (band < 1 || band > vrt_redist::kMaxBand) return hipErrorInvalidValue;
@@ -244,4 +251,71 @@ hipError_t launch_redistance_distance(bool texel16, float* dense, int N, int ban
     return hipGetLastError();
 }
 
+}  // namespace
+
 }  // namespace vrt
+
+using namespace vrt;
+
+static_assert(sizeof(vrt_redistance_result) == 48, "vrt.h states this size");
+
+extern "C" {
+
+/* vrt_volume_redistance: first, on every device, the surfels of the box grown by band + 1 are counted (launch_redistance_count) and the
+ * buffer that holds them is grown — nothing of the volume has been written when that fails —; then per device the surfels are written,
+ * the box's samples become banded signed distances in place (launch_redistance_distance, which reports like a brush launch), and what
+ * the slot derives from the samples is recomputed over the box (rebuild_derived).  Afterwards every buffer equals what upload_volume
+ * builds from the redistanced volume. */
+int vrt_volume_redistance(vrt_ctx* ctx, int slot, int band, int from, const int* origin, const int* size, vrt_redistance_result* result) {
+    if (!ctx) return VRT_ERR_INVALID;
+    if (!valid_slot(slot) || !ctx->vol[slot].used) return VRT_ERR_SLOT;
+    if (band < 1 || band > vrt_redist::kMaxBand) return VRT_ERR_INVALID;
+    if (from != VRT_REDISTANCE_FROM_BOTH && from != VRT_REDISTANCE_FROM_OUTSIDE && from != VRT_REDISTANCE_FROM_INSIDE) return VRT_ERR_INVALID;
+    HostVolume& h = ctx->vol[slot];
+    const int N = h.N;
+    int lo[3], hi[3], glo[3], ghi[3];
+    int rc = clip_box(N, origin, size, lo, hi);
+    if (rc != VRT_OK) return rc;
+    for (int a = 0; a < 3; a++) {
+        glo[a] = std::max(lo[a] - vrt_redist::cull_reach(band), 0);
+        ghi[a] = std::min(hi[a] + vrt_redist::cull_reach(band), N - 1);
+    }
+    const EditBox box = derived_boxes(h, lo, hi).samples;
+    const EditBox grown = derived_boxes(h, glo, ghi).samples;
+    const bool texel16 = h.format == VRT_FORMAT_TEXEL16;
+    const float cell = (h.extent * 2.0f) / (float)(N - 1);
+    const float unit = cell / h.density_scale;
+    rc = quiesce(ctx);
+    if (rc != VRT_OK) return rc;
+    std::vector<unsigned> surfels(ctx->dev.size(), 0u);
+    for (size_t di = 0; di < ctx->dev.size(); di++) { /* everything that can run out of memory, before any sample is written */
+        DeviceState& D = ctx->dev[di];
+        HIP_TRY(hipSetDevice(D.ordinal));
+        rc = ensure_buffer(D.buf[kBufRedistTable], redistance_table_bytes(N));
+        if (rc != VRT_OK) return rc;
+        HIP_TRY(launch_redistance_count(D.vol[slot].dense, texel16, N, from, grown, D.buf[kBufRedistTable].p, D.stream));
+        HIP_TRY(hipMemcpyAsync(&surfels[di], redistance_surfel_count(D.buf[kBufRedistTable].p), sizeof(unsigned), hipMemcpyDeviceToHost, D.stream));
+        HIP_TRY(hipStreamSynchronize(D.stream));
+        rc = ensure_buffer(D.buf[kBufRedistSurfels], redistance_surfel_bytes(surfels[di]));
+        if (rc != VRT_OK) return rc;
+    }
+    bool changed = false;
+    for (size_t di = 0; di < ctx->dev.size(); di++) {
+        DeviceState& D = ctx->dev[di];
+        HIP_TRY(hipSetDevice(D.ordinal));
+        DeviceVolume& v = D.vol[slot];
+        if (surfels[di] > 0u)
+            HIP_TRY(launch_redistance_surfels(v.dense, texel16, N, from, grown, D.buf[kBufRedistTable].p, D.buf[kBufRedistSurfels].p, surfels[di], D.stream));
+        HIP_TRY(launch_redistance_distance(texel16, v.dense, N, band, unit, box, D.buf[kBufRedistTable].p, D.buf[kBufRedistSurfels].p, D.d_brush, D.stream));
+        Written got;
+        rc = read_report(D, N, got);
+        if (rc != VRT_OK) return rc;
+        if (di == 0 && result)
+            *result = vrt_redistance_result{{got.lo[0], got.lo[1], got.lo[2]}, {got.hi[0], got.hi[1], got.hi[2]}, got.low, got.high, surfels[di], 0};
+        rc = rebuild_written(ctx, D, slot, lo, hi, 1, changed); /* the requested box, whatever was reported */
+        if (rc != VRT_OK) return rc;
+    }
+    return finish_edit(ctx, changed);
+}
+
+}  // extern "C"

@@ -1,4 +1,4 @@
-/* vrt_smooth.hip — the kernels of vrt_volume_smooth (include/vrt.h): the relaxing brush.  It is a stencil — a sample's new value
+/* vrt_smooth.hip — vrt_volume_smooth (include/vrt.h), kernels to driver: the relaxing brush.  It is a stencil — a sample's new value
  * depends on its neighbours' old values — so it cannot work in place with one lane per sample as the brushes and the stamp do.  The
  * work box (the region's box grown by one sample) is decoded once into fp32 scratch memory, every pass reads one copy of it and writes
  * the other (Jacobi: the result does not depend on the schedule), and only the last kernel touches the volume: it stores the samples
@@ -14,7 +14,7 @@
 
 #include "smooth_core.h"
 #include "edit_report.h"
-#include "vrt_launch.h"
+#include "vrt_context.h"
 
 namespace vrt {
 
@@ -102,8 +102,10 @@ __global__ __launch_bounds__(256) void smooth_apply_kernel(int material_id, cons
     report.commit(slots, blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6));
 }
 
-}  // namespace
-
+/* The rule of smooth_core.h.  work: the region's box grown by one sample and clipped to the grid;
+   region: the box outside which no sample is in the region.  scratch: smooth_scratch_bytes(work) of device memory — two fp32 copies
+   of the work box and its weights.  Gathers the work box, runs the record's passes from one copy to the other (one launch each), then
+   stores the region samples whose bits changed; slots: zeroed, then the written samples' counts and box (the edit report, vrt_launch.h). */
 size_t smooth_scratch_bytes(const EditBox& work) { return 3 * box_count(work) * sizeof(float); }
 
 hipError_t launch_smooth(const vrt_smooth& rule, bool texel16, float* dense, uint8_t* material, int N, const EditBox& work,
@@ -131,4 +133,50 @@ hipError_t launch_smooth(const vrt_smooth& rule, bool texel16, float* dense, uin
     return hipGetLastError();
 }
 
+}  // namespace
+
 }  // namespace vrt
+
+using namespace vrt;
+
+static_assert(sizeof(vrt_smooth) == 64, "vrt.h states this size");
+
+extern "C" {
+
+/* vrt_volume_smooth: the work box (the region's box grown by one sample) is relaxed in scratch memory and the region samples whose
+ * bits changed are stored (launch_smooth), which reports their box; what the slot derives from its samples is then recomputed over
+ * that box (rebuild_derived) — or not at all when nothing was written.  The scratch memory of every device is there before the first
+ * sample is written.  Afterwards every buffer of the slot equals what upload_volume builds from the edited volume. */
+int vrt_volume_smooth(vrt_ctx* ctx, int slot, const vrt_smooth* rec, vrt_brush_result* result) {
+    if (!ctx || !rec || !vrt_smooth_core::valid(*rec)) return VRT_ERR_INVALID;
+    if (!valid_slot(slot) || !ctx->vol[slot].used) return VRT_ERR_SLOT;
+    HostVolume& h = ctx->vol[slot];
+    const int N = h.N;
+    if (result) *result = vrt_brush_result{{N, N, N}, {-1, -1, -1}, 0};
+    int lo[3], hi[3], work_lo[3], work_hi[3];
+    if (!vrt_smooth_core::boxes(*rec, N, lo, hi, work_lo, work_hi)) return VRT_OK; /* wholly outside the grid */
+    const EditBox region = derived_boxes(h, lo, hi).samples, work = derived_boxes(h, work_lo, work_hi).samples;
+    int rc = quiesce(ctx);
+    if (rc != VRT_OK) return rc;
+    for (auto& D : ctx->dev) { /* every allocation comes before any write */
+        HIP_TRY(hipSetDevice(D.ordinal));
+        rc = ensure_buffer(D.buf[kBufSmoothWarp], smooth_scratch_bytes(work));
+        if (rc != VRT_OK) return rc;
+    }
+    bool changed = false;
+    for (size_t di = 0; di < ctx->dev.size(); di++) {
+        DeviceState& D = ctx->dev[di];
+        HIP_TRY(hipSetDevice(D.ordinal));
+        DeviceVolume& v = D.vol[slot];
+        HIP_TRY(launch_smooth(*rec, h.format == VRT_FORMAT_TEXEL16, v.dense, v.material, N, work, region, D.buf[kBufSmoothWarp].p, D.d_brush, D.stream));
+        Written got;
+        rc = read_report(D, N, got);
+        if (rc != VRT_OK) return rc;
+        if (di == 0 && result) *result = brush_result(got);
+        rc = rebuild_written(ctx, D, slot, got.lo, got.hi, got.low, changed); /* every written sample is a density write */
+        if (rc != VRT_OK) return rc;
+    }
+    return finish_edit(ctx, changed);
+}
+
+}  // extern "C"

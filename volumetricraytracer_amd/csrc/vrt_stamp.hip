@@ -1,4 +1,4 @@
-/* vrt_stamp.hip — the kernel of vrt_volume_stamp (include/vrt.h): CSG of one resident volume into another.  Every sample of the
+/* vrt_stamp.hip — vrt_volume_stamp (include/vrt.h), kernels to driver: CSG of one resident volume into another.  Every sample of the
  * footprint box of the destination is taken through the caller's matrix into the source's grid, the source's dense grid is sampled
  * trilinearly there, and the value is merged into the destination by the rule of stamp_core.h (shared with the host pass).
  *
@@ -11,7 +11,7 @@
 
 #include "stamp_core.h"
 #include "edit_report.h"
-#include "vrt_launch.h"
+#include "vrt_context.h"
 
 namespace vrt {
 
@@ -68,8 +68,9 @@ __global__ __launch_bounds__(256) void stamp_region_kernel(vrt_stamp_core::Rule 
     report.commit(slots, (blockIdx.y * gridDim.x + blockIdx.x) * (blockDim.x >> 6) + (threadIdx.x >> 6));
 }
 
-}  // namespace
-
+/* The rule of stamp_core.h over the destination samples of `box` (the footprint: outside it the
+   source's box cannot be hit), in place; the source's dense and material grids are only read and must not be the destination's.
+   slots: zeroed, then the written samples' counts and box (the edit report, vrt_launch.h). */
 hipError_t launch_stamp_region(const vrt_stamp_core::Rule& rule, bool src_texel16, const float* src_dense, const uint8_t* src_material,
                                bool dst_texel16, float* dense, uint8_t* material, int N, const EditBox& box, DBrushSlot* slots,
                                hipStream_t stream) {
@@ -88,4 +89,50 @@ hipError_t launch_stamp_region(const vrt_stamp_core::Rule& rule, bool src_texel1
     return hipGetLastError();
 }
 
+}  // namespace
+
 }  // namespace vrt
+
+using namespace vrt;
+
+static_assert(sizeof(vrt_stamp) == 96, "vrt.h states this size");
+
+extern "C" {
+
+/* vrt_volume_stamp: the source slot's dense grid gathered into the destination's over the footprint of the source's box
+ * (launch_stamp_region), which reports the box of the samples it wrote; what the destination derives from its samples is then
+ * recomputed over that box (rebuild_derived) — or not at all when nothing was written.  The source slot is only read.  Afterwards
+ * every buffer of the destination equals what upload_volume builds from the edited volume. */
+int vrt_volume_stamp(vrt_ctx* ctx, int dst_slot, int src_slot, const vrt_stamp* rec, vrt_brush_result* result) {
+    if (!ctx || !rec || dst_slot == src_slot || !vrt_stamp_core::valid(*rec)) return VRT_ERR_INVALID;
+    if (!valid_slot(dst_slot) || !valid_slot(src_slot) || !ctx->vol[dst_slot].used || !ctx->vol[src_slot].used) return VRT_ERR_SLOT;
+    HostVolume& h = ctx->vol[dst_slot];
+    const HostVolume& hs = ctx->vol[src_slot];
+    const int N = h.N;
+    if (result) *result = vrt_brush_result{{N, N, N}, {-1, -1, -1}, 0};
+    int lo[3], hi[3];
+    if (!vrt_stamp_core::footprint(*rec, hs.N, N, lo, hi)) return VRT_OK; /* wholly outside the grid */
+    const vrt_stamp_core::Rule rule = vrt_stamp_core::rule_of(*rec, hs.N, vrt_stamp_core::unit_of(N, h.extent, h.density_scale),
+                                                    vrt_stamp_core::unit_of(hs.N, hs.extent, hs.density_scale));
+    const EditBox foot = derived_boxes(h, lo, hi).samples;
+    int rc = quiesce(ctx);
+    if (rc != VRT_OK) return rc;
+    bool changed = false;
+    for (size_t di = 0; di < ctx->dev.size(); di++) {
+        DeviceState& D = ctx->dev[di];
+        HIP_TRY(hipSetDevice(D.ordinal));
+        DeviceVolume& v = D.vol[dst_slot];
+        const DeviceVolume& vs = D.vol[src_slot];
+        HIP_TRY(launch_stamp_region(rule, hs.format == VRT_FORMAT_TEXEL16, vs.dense, vs.material, h.format == VRT_FORMAT_TEXEL16, v.dense,
+                                    v.material, N, foot, D.d_brush, D.stream));
+        Written got;
+        rc = read_report(D, N, got);
+        if (rc != VRT_OK) return rc;
+        if (di == 0 && result) *result = brush_result(got);
+        rc = rebuild_written(ctx, D, dst_slot, got.lo, got.hi, got.low, changed); /* every written sample is a density write */
+        if (rc != VRT_OK) return rc;
+    }
+    return finish_edit(ctx, changed);
+}
+
+}  // extern "C"

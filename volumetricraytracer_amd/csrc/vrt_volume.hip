@@ -13,8 +13,7 @@
 
 #include "grid_core.h"
 #include "voxelize_core.h"
-#include "vrt_device.h"
-#include "vrt_launch.h"
+#include "vrt_context.h"
 
 namespace vrt {
 
@@ -385,8 +384,10 @@ hipError_t launch_texels_to_field(const void* texels, float* density, uint8_t* m
 static unsigned stride_grid(size_t count) { return (unsigned)std::max<size_t>(1, std::min<size_t>((count + 255) / 256, 1u << 16)); }
 static unsigned box_blocks(const EditBox& b) { return (unsigned)box_count(b); }
 
-hipError_t launch_scatter_region(const void* staging, bool voxels, bool has_material, bool texel16, float* dense, uint8_t* material, int N,
-                                 const EditBox& box, hipStream_t stream) {
+/* The staged box (VVoxel records, or floats followed by bytes when has_material; x slowest, then z, then y) -> dense + material,
+   quantised like launch_quantize_field when texel16. */
+static hipError_t launch_scatter_region(const void* staging, bool voxels, bool has_material, bool texel16, float* dense, uint8_t* material, int N,
+                                        const EditBox& box, hipStream_t stream) {
     const unsigned grid = stride_grid(box_count(box));
     if (voxels)
         hipLaunchKernelGGL(scatter_region_kernel<true>, dim3(grid), dim3(256), 0, stream, staging, dense, material, N, box, (int)texel16, 1);
@@ -396,8 +397,9 @@ hipError_t launch_scatter_region(const void* staging, bool voxels, bool has_mate
     return hipGetLastError();
 }
 
-hipError_t launch_gather_region(const float* dense, const uint8_t* material, bool texel16, int N, const EditBox& box, void* voxels_out,
-                                hipStream_t stream) {
+/* vrt_volume_download_region: the samples of `box` as VVoxel records (x slowest, then z, then y), a TEXEL16 field decoded. */
+static hipError_t launch_gather_region(const float* dense, const uint8_t* material, bool texel16, int N, const EditBox& box, void* voxels_out,
+                                       hipStream_t stream) {
     const unsigned grid = stride_grid(box_count(box));
     hipLaunchKernelGGL(gather_region_kernel, dim3(grid), dim3(256), 0, stream, dense, material, static_cast<uint2*>(voxels_out), N, box, (int)texel16);
     return hipGetLastError();
@@ -514,4 +516,79 @@ hipError_t launch_split_voxels(const void* voxels, float* density, uint8_t* mate
     return hipGetLastError();
 }
 
+/* vrt_volume_update_region / _update_voxels: the box's samples in place on every device, then what the slot derives from them, where
+ * the box can change it (rebuild_derived).  Afterwards every buffer equals what upload_volume builds from the edited volume.  The two
+ * entry points choose the input form and have refused a null argument of theirs. */
+static int update_region(vrt_ctx* ctx, int slot, const int origin[3], const int size[3], const float* density, const uint8_t* material,
+                         const vrt_voxel* voxels) {
+    if (!valid_slot(slot) || !ctx->vol[slot].used) return VRT_ERR_SLOT;
+    HostVolume& h = ctx->vol[slot];
+    const int N = h.N;
+    int first[3], last[3];
+    int rc = clip_box(N, origin, size, first, last);
+    if (rc != VRT_OK) return rc;
+    const EditBox box = derived_boxes(h, first, last).samples;
+    const size_t count = (size_t)size[0] * size[1] * size[2];
+    const size_t staged = voxels ? count * sizeof(vrt_voxel) : count * (sizeof(float) + (material ? 1 : 0));
+    const bool texel16 = h.format == VRT_FORMAT_TEXEL16;
+    rc = quiesce(ctx);
+    if (rc != VRT_OK) return rc;
+    bool changed = false;
+    for (auto& D : ctx->dev) {
+        HIP_TRY(hipSetDevice(D.ordinal));
+        DeviceVolume& v = D.vol[slot];
+        rc = ensure_buffer(D.buf[kBufEditStaging], staged);
+        if (rc != VRT_OK) return rc;
+        if (voxels) {
+            HIP_TRY(hipMemcpyAsync(D.buf[kBufEditStaging].p, voxels, staged, hipMemcpyHostToDevice, D.stream));
+        } else {
+            HIP_TRY(hipMemcpyAsync(D.buf[kBufEditStaging].p, density, count * sizeof(float), hipMemcpyHostToDevice, D.stream));
+            if (material)
+                HIP_TRY(hipMemcpyAsync(static_cast<char*>(D.buf[kBufEditStaging].p) + count * sizeof(float), material, count, hipMemcpyHostToDevice, D.stream));
+        }
+        HIP_TRY(launch_scatter_region(D.buf[kBufEditStaging].p, voxels != nullptr, material != nullptr, texel16, v.dense, v.material, N, box, D.stream));
+        rc = rebuild_written(ctx, D, slot, first, last, count, changed); /* reads no report: its own box, always */
+        if (rc != VRT_OK) return rc;
+    }
+    return finish_edit(ctx, changed);
+}
+
 }  // namespace vrt
+
+using namespace vrt;
+
+extern "C" {
+
+int vrt_volume_update_region(vrt_ctx* ctx, int slot, const int origin_xyz[3], const int size_xyz[3], const float* density,
+                             const uint8_t* material_or_null) {
+    if (!ctx || !origin_xyz || !size_xyz || !density) return VRT_ERR_INVALID;
+    return update_region(ctx, slot, origin_xyz, size_xyz, density, material_or_null, nullptr);
+}
+
+int vrt_volume_update_voxels(vrt_ctx* ctx, int slot, const int origin_xyz[3], const int size_xyz[3], const vrt_voxel* voxels) {
+    if (!ctx || !origin_xyz || !size_xyz || !voxels) return VRT_ERR_INVALID;
+    return update_region(ctx, slot, origin_xyz, size_xyz, nullptr, nullptr, voxels);
+}
+
+/* vrt_volume_download_region: the box through the cached staging buffer of device 0 (gather_region_kernel), then one copy. */
+int vrt_volume_download_region(vrt_ctx* ctx, int slot, const int origin[3], const int size[3], vrt_voxel* out) {
+    if (!ctx || !origin || !size || !out) return VRT_ERR_INVALID;
+    if (!valid_slot(slot) || !ctx->vol[slot].used) return VRT_ERR_SLOT;
+    const HostVolume& h = ctx->vol[slot];
+    int lo[3], hi[3];
+    int rc = clip_box(h.N, origin, size, lo, hi);
+    if (rc != VRT_OK) return rc;
+    const EditBox box = derived_boxes(h, lo, hi).samples;
+    const size_t bytes = (size_t)size[0] * size[1] * size[2] * sizeof(vrt_voxel);
+    DeviceState& D = ctx->dev[0];
+    HIP_TRY(hipSetDevice(D.ordinal));
+    rc = ensure_buffer(D.buf[kBufEditStaging], bytes);
+    if (rc != VRT_OK) return rc;
+    const DeviceVolume& v = D.vol[slot];
+    HIP_TRY(launch_gather_region(v.dense, v.material, h.format == VRT_FORMAT_TEXEL16, h.N, box, D.buf[kBufEditStaging].p, D.stream));
+    HIP_TRY(hipMemcpyAsync(out, D.buf[kBufEditStaging].p, bytes, hipMemcpyDeviceToHost, D.stream));
+    HIP_TRY(hipStreamSynchronize(D.stream));
+    return VRT_OK;
+}
+
+}  // extern "C"

@@ -1,4 +1,4 @@
-/* vrt_warp.hip — the kernels of vrt_volume_warp (include/vrt.h): grab, twist, scale and inflate.  Every sample of the region takes its
+/* vrt_warp.hip — vrt_volume_warp (include/vrt.h), kernels to driver: grab, twist, scale and inflate.  Every sample of the region takes its
  * value from somewhere else in the same volume, so the call cannot work in place with one lane per sample: a lane would read what
  * another has just written.  The sample kernel therefore writes nothing to the volume — it computes, for every sample of the region's
  * box, the value to store and the new material id into scratch memory —, and the apply kernel stores the samples whose bits or id
@@ -18,8 +18,9 @@
 #include <hip/hip_runtime.h>
 
 #include "warp_core.h"
+#include "stamp_core.h" /* unit_of */
 #include "edit_report.h"
-#include "vrt_launch.h"
+#include "vrt_context.h"
 
 namespace vrt {
 
@@ -79,8 +80,11 @@ __global__ __launch_bounds__(256) void warp_apply_kernel(const float* __restrict
     report.commit(slots, blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6));
 }
 
-}  // namespace
-
+/* The rule of warp_core.h.  region: the box outside which no sample is in the region; off: the
+   record's inflate in density units (warp_core.h, off_of).  scratch: warp_scratch_bytes(region) of device memory — the value to store
+   (one float) and the new id (one byte) of every sample of the box.  Computes both from the volume as it is, writing nothing to it, then
+   stores the samples whose bits or id changed; slots: zeroed, then the written samples' counts and box (the edit report, vrt_launch.h), with
+   the count of density writes in the high half of `counts`. */
 size_t warp_scratch_bytes(const EditBox& region) { return box_count(region) * (sizeof(float) + 1); }
 
 hipError_t launch_warp(const vrt_warp& rule, float off, bool texel16, float* dense, uint8_t* material, int N, const EditBox& region,
@@ -102,4 +106,53 @@ hipError_t launch_warp(const vrt_warp& rule, float off, bool texel16, float* den
     return hipGetLastError();
 }
 
+}  // namespace
+
 }  // namespace vrt
+
+using namespace vrt;
+
+static_assert(sizeof(vrt_warp) == 128, "vrt.h states this size");
+
+extern "C" {
+
+/* vrt_volume_warp: the value to store and the new id of every sample of the region's box are computed into scratch memory from the
+ * volume as it is, then the samples whose bits or id changed are stored (launch_warp), which reports their box; what the slot derives
+ * from its samples is then recomputed over that box (rebuild_derived) — or not at all when no density changed.  The scratch memory of
+ * every device is there before the first sample is written.  Afterwards every buffer of the slot equals what upload_volume builds from
+ * the edited volume. */
+int vrt_volume_warp(vrt_ctx* ctx, int slot, const vrt_warp* rec, vrt_brush_result* result) {
+    if (!ctx || !rec || !vrt_warp_core::valid(*rec)) return VRT_ERR_INVALID;
+    if (!valid_slot(slot) || !ctx->vol[slot].used) return VRT_ERR_SLOT;
+    HostVolume& h = ctx->vol[slot];
+    const int N = h.N;
+    if (result) *result = vrt_brush_result{{N, N, N}, {-1, -1, -1}, 0};
+    int lo[3], hi[3];
+    if (!vrt_warp_core::box(*rec, N, lo, hi)) return VRT_OK; /* wholly outside the grid */
+    const EditBox region = derived_boxes(h, lo, hi).samples;
+    const float off = vrt_warp_core::off_of(*rec, vrt_stamp_core::unit_of(N, h.extent, h.density_scale));
+    int rc = quiesce(ctx);
+    if (rc != VRT_OK) return rc;
+    for (auto& D : ctx->dev) { /* every allocation comes before any write */
+        HIP_TRY(hipSetDevice(D.ordinal));
+        rc = ensure_buffer(D.buf[kBufSmoothWarp], warp_scratch_bytes(region));
+        if (rc != VRT_OK) return rc;
+    }
+    bool changed = false;
+    for (size_t di = 0; di < ctx->dev.size(); di++) {
+        DeviceState& D = ctx->dev[di];
+        HIP_TRY(hipSetDevice(D.ordinal));
+        DeviceVolume& v = D.vol[slot];
+        HIP_TRY(launch_warp(*rec, off, h.format == VRT_FORMAT_TEXEL16, v.dense, v.material, N, region, D.buf[kBufSmoothWarp].p, D.d_brush, D.stream));
+        Written got;
+        rc = read_report(D, N, got);
+        if (rc != VRT_OK) return rc;
+        if (di == 0 && result) *result = brush_result(got);
+        /* the density writes count: nothing written, or only material ids, and no derived structure changes */
+        rc = rebuild_written(ctx, D, slot, got.lo, got.hi, got.high, changed);
+        if (rc != VRT_OK) return rc;
+    }
+    return finish_edit(ctx, changed);
+}
+
+}  // extern "C"
