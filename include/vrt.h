@@ -197,7 +197,17 @@ typedef struct vrt_spot_light {
     float cos_falloff_angle;  /* cos(FalloffAngle/2) */
 } vrt_spot_light;
 
-/* VSceneConstantBuffer + TLAS instance list: RaytracingHlsl.h:53-62, RDXScene.cpp:454-545,703-724. */
+/* VSceneConstantBuffer + TLAS instance list: RaytracingHlsl.h:53-62, RDXScene.cpp:454-545,703-724.
+ *
+ * Limits.  n_instances outside 0 .. VRT_MAX_INSTANCES is refused (VRT_ERR_INVALID).  The light counts are CLAMPED, silently: a
+ * count above VRT_MAX_POINT_LIGHTS / VRT_MAX_SPOT_LIGHTS renders like the count at the limit — the records beyond the arrays below
+ * do not exist and are never read — in vrt_scene_set, in every frame of vrt_block::scenes and in every kernel form alike; a
+ * negative count is refused.
+ *
+ * Ties.  Where a ray meets the surfaces of several instances at exactly the same t (instances placed on top of each other), the
+ * closest hit — the shaded pixel, vrt_hit::instance, voxel and material — is that of the LOWEST instance index, in every render
+ * mode, whatever order the instance BVH is walked in: an instance hides another only by a smaller t, never by its place in the
+ * tree. */
 typedef struct vrt_scene {
     float cam_position[3];
     float cam_rotation[4];   /* quaternion x,y,z,w; forward = q·(+X), up = q·(+Z)  (Core/Private/Vector.cpp:42-46) */
