@@ -31,6 +31,8 @@
  *                                   the shell of a closed mesh made solid on the resident volume, so that a SUBTRACT brush carves a solid)
  *   vrt_volume_components           (no reference analogue beyond VVoxelVolume::SetVoxel, VoxelVolume.cpp:59-77, in a host loop: the
  *                                   6-connected pieces of the resident volume labelled, listed, and the unwanted ones removed)
+ *   vrt_volume_history, _undo,      (no reference analogue: a per-slot history of the 4^3 tiles each edit call changed, kept on the device, and
+ *   _redo, _history_info            the edits taken back or done again from it bit for bit)
  *   vrt_volume_redistance           (no reference analogue: whatever field the resident volume holds rewritten, within a band, as the
  *                                   signed distance to its own zero surface — what ADD brushes, blends and offsets assume)
  *   vrt_volume_extract_mesh         (no reference analogue: its Voxelizer goes one way, glTF -> .vox; the resident volume's surface
@@ -855,6 +857,70 @@ int vrt_volume_extract_mesh(vrt_ctx* ctx, int slot, float iso,
  * download.  Argument checks as vrt_volume_update_region's.  On a VRT_FORMAT_TEXEL16 slot the decoded values (q * 0.01f) re-quantise
  * when uploaded again and need not give q back — as with vrt_volume_download. */
 int vrt_volume_download_region(vrt_ctx* ctx, int slot, const int origin_xyz[3], const int size_xyz[3], vrt_voxel* out);
+
+/* Undo and redo of volume edits (no reference analogue): a per-slot edit history that lives on the device.  Off by default; while it
+ * is off every call does exactly what it does without it. */
+#define VRT_HISTORY_TILE 4            /* a history tile is 4 x 4 x 4 samples, aligned to multiples of 4 on every axis */
+#define VRT_HISTORY_TILE_BYTES 336    /* device bytes one stored tile costs: 64 x 4 B of density bits + 64 B of ids + 4 B of key, padded to 16 */
+
+typedef struct vrt_history_info {     /* 64 B */
+    int32_t  enabled, max_entries;
+    uint64_t max_bytes;
+    uint32_t undo_entries, redo_entries;
+    uint64_t bytes;                   /* tiles held (undo + redo) x VRT_HISTORY_TILE_BYTES, per device */
+    uint64_t dropped;                 /* entries lost to the limits since the history was turned on */
+    uint64_t top_tiles;               /* tiles of the entry vrt_volume_undo would take next; 0 when none */
+    uint32_t reserved_[4];            /* 0 */
+} vrt_history_info;
+
+/* Turns the slot's history on with these limits (both > 0), or off (both 0: every entry is freed, `dropped` starts again at 0 with the
+ * next turning on).  Turning on a history that is on changes only the limits and drops entries until they hold: the oldest undo entries
+ * first, then — with no undo entry left — the redo entries furthest ahead; `dropped` counts them.
+ *
+ * What records an entry.  While the history is on, each call of vrt_volume_update_region, _update_voxels, _apply_brushes, _stamp (the
+ * destination slot only; the source records nothing), _smooth, _warp, _fill_enclosed, _components and _redistance on the slot records
+ * ONE entry, if and only if it changed the bits of at least one sample — the 32 stored bits of its density or its id byte.  A call
+ * that changes no bit (VRT_COMPONENTS_REPORT, a brush outside the grid, an update with the bytes already held) records nothing and
+ * leaves the redo stack alone.
+ * What an entry holds: the changed tiles and no others.  A changed tile is an aligned tile with at least one sample whose bits differ
+ * between before and after the call; the entry holds the stored bits and ids of all 64 samples of each such tile as they were before
+ * the call (on a VRT_FORMAT_TEXEL16 slot the dense grid's own float of the integer field +-q, not a decoded value, so nothing is
+ * quantised again).  The layout inside the device is free; an entry's tile count and `bytes` are contract.
+ * The stacks.  Recording an entry empties the redo stack (those entries do not count as dropped).  Then, while undo_entries >
+ * max_entries or bytes > max_bytes, the oldest undo entry is dropped and `dropped` counts it.  When the new entry exceeds max_bytes on
+ * its own, or the memory of its record cannot be allocated on some device, the slot's whole history is dropped, the new entry
+ * included, and `dropped` counts every entry lost (the undo entries and the new one); the limits stay.  The edit call itself returns
+ * what it returns without a history, with one exception: the copy of its footprint as it was (4 B + 1 B per sample — of the brushes'
+ * box, the update's box, the stamp's conservative box, the region's box of smooth and warp, the requested box of redistance, the whole
+ * grid for fill_enclosed and for a components call that removes something) is allocated on every device before any sample is written;
+ * when that fails the call returns VRT_ERR_OOM and the volume is untouched.
+ * What the history is not.  vrt_volume_set_metric, _set_material and _set_textures are neither recorded nor undone and leave the stacks
+ * alone.  vrt_volume_upload* and vrt_voxelize_mesh onto the slot drop its entries (not counted) and keep its limits; vrt_volume_free
+ * drops them and turns the history off.
+ * Errors, all checked before any state is touched: VRT_ERR_INVALID for a NULL context, max_entries < 0, or exactly one of the two
+ * limits 0; VRT_ERR_SLOT for an unused slot. */
+int vrt_volume_history(vrt_ctx* ctx, int slot, int max_entries, uint64_t max_bytes);   /* 0, 0: off, everything freed */
+/* The slot's history as it stands (all zero but the struct's own zeros while it is off).  VRT_ERR_INVALID for a NULL context or a
+ * NULL out; VRT_ERR_SLOT for an unused slot. */
+int vrt_volume_history_info(vrt_ctx* ctx, int slot, vrt_history_info* out);
+/* vrt_volume_undo takes the `steps` newest undo entries, newest first: every stored tile of an entry is swapped with the volume's
+ * current tile — the volume gets the stored bits and ids, the record keeps what the volume held — and the entry is then a redo entry.
+ * vrt_volume_redo is the mirror image, oldest redo entry first (the one undone last), and makes undo entries again.  Neither
+ * allocates.  After the swaps, what the slot derives from its samples is rebuilt once over the union box of the samples whose bits
+ * changed; nothing is rebuilt when no density bit changed; the scene and the volume table follow as after any edit.  Like the edit
+ * calls, both wait for work already enqueued on the context's devices, run on every device, keep the slot's device pointers, and leave
+ * a launch captured into a graph the cull rectangle it was captured with.
+ * result_or_null, from device 0: lo / hi, xyz and inclusive, the union box of the samples whose bits (density or id) changed, lo > hi
+ * when none did; `written` the sum, over the entries taken, of the samples that entry's swap changed — a sample two entries touch counts
+ * twice.
+ * The guarantee.  After an undo of the k newest entries the dense grid and the material grid hold, bit for bit (NaN payloads and
+ * -0.0f included: comparisons and copies work on bits), what they held before the k-th newest recorded call; every other buffer of
+ * the slot equals what a full upload of that volume under the slot's CURRENT metric holds.  After the matching redo every buffer
+ * equals what it held after those calls.
+ * Errors, all checked before any device state is touched: VRT_ERR_INVALID for a NULL context, a slot whose history is off, steps < 1
+ * or steps above the depth of the stack asked for; VRT_ERR_SLOT for an unused slot. */
+int vrt_volume_undo(vrt_ctx* ctx, int slot, int steps, vrt_brush_result* result_or_null);
+int vrt_volume_redo(vrt_ctx* ctx, int slot, int steps, vrt_brush_result* result_or_null);
 
 /* Tests: the raw bytes of one device buffer of a slot on device `device_index` of the context.  *size_out (when not NULL) = the
  * buffer's size; out == NULL only asks for it; a capacity below the size is VRT_ERR_INVALID.  The tables are the first nb^3

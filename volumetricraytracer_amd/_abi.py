@@ -340,6 +340,16 @@ class vrt_mesh_result(C.Structure):
     _fields_ = [("lo", C.c_int32 * 3), ("hi", C.c_int32 * 3), ("vertices", C.c_uint64), ("quads", C.c_uint64)]
 
 
+class vrt_history_info(C.Structure):
+    _fields_ = [("enabled", C.c_int32), ("max_entries", C.c_int32), ("max_bytes", C.c_uint64), ("undo_entries", C.c_uint32),
+                ("redo_entries", C.c_uint32), ("bytes", C.c_uint64), ("dropped", C.c_uint64), ("top_tiles", C.c_uint64),
+                ("reserved_", C.c_uint32 * 4)]
+
+
+# vrt_volume_history: a history tile is 4^3 samples and costs HISTORY_TILE_BYTES of device memory
+HISTORY_TILE = 4
+HISTORY_TILE_BYTES = 336
+
 REDISTANCE_FROM_BOTH, REDISTANCE_FROM_OUTSIDE, REDISTANCE_FROM_INSIDE = 0, 1, 2
 
 SYMBOLS = {
@@ -372,6 +382,10 @@ SYMBOLS = {
     "vrt_volume_extract_mesh": (C.c_int, [C.c_void_p, C.c_int, C.c_float, C.POINTER(C.c_int), C.POINTER(C.c_int), C.c_void_p, C.c_void_p,
                                           C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.POINTER(vrt_mesh_result)]),
     "vrt_volume_download_region": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int), C.c_void_p]),
+    "vrt_volume_history": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_uint64]),
+    "vrt_volume_history_info": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(vrt_history_info)]),
+    "vrt_volume_undo": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.POINTER(vrt_brush_result)]),
+    "vrt_volume_redo": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.POINTER(vrt_brush_result)]),
     "vrt_debug_volume_bytes": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_size_t, C.POINTER(C.c_size_t)]),
     "vrt_env_upload": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p]),
     "vrt_scene_set": (C.c_int, [C.c_void_p, C.POINTER(vrt_scene)]),

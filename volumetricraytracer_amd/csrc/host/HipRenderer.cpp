@@ -846,6 +846,44 @@ bool VHipRenderer::WarpVolume(const Scene::VVoxelObject& object, const vrt_warp&
     return MirrorBox(slot, *volume, res.lo, res.hi);
 }
 
+int VHipRenderer::SyncedSlotOf(const Scene::VVoxelObject& object, const char* who) {
+    if (!IsActive()) {
+        V_LOG_WARNING((std::string(who) + "() on an inactive renderer").c_str());
+        return -1;
+    }
+    const VObjectPtr<Scene::VScene> scene = SceneRef.lock();
+    const VObjectPtr<Voxel::VVoxelVolume> volume = object.GetVoxelVolume();
+    if (!scene || !volume || !SyncWithScene(*scene)) return -1;
+    const int slot = SlotOf(volume.get());
+    if (slot < 0) V_LOG_ERROR((std::string(who) + "(): the object's volume is not part of the rendered scene").c_str());
+    return slot;
+}
+
+bool VHipRenderer::EnableHistory(const Scene::VVoxelObject& object, int maxEntries, uint64_t maxBytes) {
+    const int slot = SyncedSlotOf(object, "EnableHistory");
+    return slot >= 0 && ok(vrt_volume_history(Ctx, slot, maxEntries, maxBytes), "vrt_volume_history");
+}
+
+bool VHipRenderer::HistoryInfo(const Scene::VVoxelObject& object, vrt_history_info& out) {
+    const int slot = SyncedSlotOf(object, "HistoryInfo");
+    return slot >= 0 && ok(vrt_volume_history_info(Ctx, slot, &out), "vrt_volume_history_info");
+}
+
+bool VHipRenderer::StepHistory(const Scene::VVoxelObject& object, int steps, bool redo, vrt_brush_result* result) {
+    const int slot = SyncedSlotOf(object, redo ? "Redo" : "Undo");
+    if (slot < 0) return false;
+    vrt_brush_result res;
+    if (!ok(redo ? vrt_volume_redo(Ctx, slot, steps, &res) : vrt_volume_undo(Ctx, slot, steps, &res), redo ? "vrt_volume_redo" : "vrt_volume_undo"))
+        return false;
+    if (result) *result = res;
+    if (res.written == 0) return true;
+    return MirrorBox(slot, *object.GetVoxelVolume(), res.lo, res.hi);
+}
+
+bool VHipRenderer::Undo(const Scene::VVoxelObject& object, int steps, vrt_brush_result* result) { return StepHistory(object, steps, false, result); }
+
+bool VHipRenderer::Redo(const Scene::VVoxelObject& object, int steps, vrt_brush_result* result) { return StepHistory(object, steps, true, result); }
+
 bool VHipRenderer::WarpFromMotion(const VVector& pivot, const VVector& translation, const VQuat& rotation, float scale, vrt_warp& rec) {
     const double c[3] = {pivot.X, pivot.Y, pivot.Z}, t[3] = {translation.X, translation.Y, translation.Z};
     const double q[4] = {rotation.x, rotation.y, rotation.z, rotation.w};

@@ -131,6 +131,16 @@ public:
        faded out by the region's weight, brings it from.  The written box is read back into the host VVoxelVolume like ApplyBrushes
        does.  False (after logging) on failure or when the object's volume is not in the scene. */
     bool WarpVolume(const Scene::VVoxelObject& object, const vrt_warp& warp, vrt_brush_result* result = nullptr);
+    /* Undo and redo on the device (vrt_volume_history, _undo, _redo; the contract: vrt.h) for the volume of a placed object of the scene
+       Render() would draw now (synced first).  EnableHistory: from now on every device-side edit of the volume that changes a bit
+       records the 4^3 tiles it changed as they were, within maxEntries entries and maxBytes bytes per device (0, 0: off, everything
+       freed); uploading the volume whole again empties the history.  Undo / Redo take `steps` entries in one call, bit for bit also
+       with VolumeFormat VRT_FORMAT_TEXEL16; the changed box is read back into the host VVoxelVolume like SmoothVolume does.  False
+       (after logging) on failure — more steps than the stack holds among them — or when the object's volume is not in the scene. */
+    bool EnableHistory(const Scene::VVoxelObject& object, int maxEntries, uint64_t maxBytes);
+    bool HistoryInfo(const Scene::VVoxelObject& object, vrt_history_info& out);
+    bool Undo(const Scene::VVoxelObject& object, int steps = 1, vrt_brush_result* result = nullptr);
+    bool Redo(const Scene::VVoxelObject& object, int steps = 1, vrt_brush_result* result = nullptr);
     /* pull and length_scale of `rec` from the motion one sees — a turn by `rotation` and a uniform scale about `pivot` (grid
        coordinates of the volume, xyz), then a shift by `translation` (cells): the inverse motion, built in double and rounded once;
        length_scale = scale.  The record's other fields stay.  False for a zero quaternion or a scale that is not positive. */
@@ -183,6 +193,8 @@ public:
 private:
     bool SyncWithScene(Scene::VScene& scene);
     int SlotOf(const Voxel::VVoxelVolume* volume) const; /* -1: not uploaded */
+    int SyncedSlotOf(const Scene::VVoxelObject& object, const char* who); /* the scene synced, then SlotOf; -1 after logging */
+    bool StepHistory(const Scene::VVoxelObject& object, int steps, bool redo, vrt_brush_result* result);
     bool MirrorBox(int slot, Voxel::VVoxelVolume& volume, const int lo[3], const int hi[3]); /* device box -> host volume */
     bool FillSceneStruct(Scene::VScene& scene, vrt_scene& out, std::vector<const Scene::VVoxelObject*>* objects = nullptr);
     std::vector<const Scene::VVoxelObject*> QueryObjects; /* instance -> placed object of the last query's scene */

@@ -34,6 +34,10 @@
  *            [--sdf BAND]                   with --solid: after the fill every volume is redistanced on the device (VHipRenderer::Redistance, vrt_volume_redistance,
  *                                           FROM_OUTSIDE, BAND cells, 1..15) into a true signed distance; under --edit-device the box each dab wrote, grown by
  *                                           BAND, is redistanced again after the dab
+ *            [--undo K]                     with --edit-device or --edit-stamp: the first object's volume keeps an edit history on the device from the first
+ *                                           frame (VHipRenderer::EnableHistory, vrt_volume_history); after the last frame the K newest entries are undone
+ *                                           in one call (VHipRenderer::Undo, vrt_volume_undo), ahead of --keep-largest and --mesh-out, and the history's
+ *                                           state is printed before and after
  *            [--keep-largest]               after the last frame, ahead of --mesh-out: of the first object's volume only the largest connected piece stays
  *                                           (VHipRenderer::Components, vrt_volume_components, KEEP_LARGEST, gap half a cell, material 0): what a carve cut
  *                                           loose does not reach the mesh
@@ -120,6 +124,7 @@ int main(int argc, char** argv) {
     unsigned W = 1024, H = 576;
     std::string scenePath, skyboxDir, outPath = "vrt_demo.ppm", meshOut;
     bool keepLargest = false;
+    int undoSteps = 0;
     bool identityDefaults = false;
     int editBrush = 0, sdf = 0;
     bool editFull = false, editDevice = false, editStamp = false, solid = false;
@@ -150,6 +155,7 @@ int main(int argc, char** argv) {
         else if (!strcmp(argv[i], "--sdf") && i + 1 < argc) sdf = atoi(argv[++i]);
         else if (!strcmp(argv[i], "--mesh-out") && i + 1 < argc) meshOut = argv[++i];
         else if (!strcmp(argv[i], "--keep-largest")) keepLargest = true;
+        else if (!strcmp(argv[i], "--undo") && i + 1 < argc) undoSteps = atoi(argv[++i]);
         else if (!strcmp(argv[i], "--pick") && i + 2 < argc) {
             pick = true;
             pickX = atoi(argv[++i]);
@@ -238,10 +244,29 @@ int main(int argc, char** argv) {
         fprintf(stderr, "--keep-largest labels on the device: it needs the HIP renderer\n");
         return 1;
     }
+    if (undoSteps != 0 && (!hip || !editDevice || editBrush <= 0 || undoSteps < 1)) {
+        fprintf(stderr, "--undo K takes back K device-side edits: it needs --edit-brush with --edit-device or --edit-stamp, and K >= 1\n");
+        return 1;
+    }
     if (sdf != 0 && (!solid || sdf < 1 || sdf > 15)) {
         fprintf(stderr, "--sdf BAND (1..15) redistances what --solid filled: give both\n");
         return 1;
     }
+    VObjectPtr<Scene::VVoxelObject> first;
+    for (const auto& placed : scene->GetAllPlacedObjects()) {
+        const auto object = std::dynamic_pointer_cast<Scene::VVoxelObject>(placed);
+        if (object && object->GetVoxelVolume()) {
+            first = object;
+            break;
+        }
+    }
+    auto printHistory = [&]() {
+        vrt_history_info info;
+        if (!hip->HistoryInfo(*first, info)) return false;
+        printf("history: enabled %d undo_entries %u redo_entries %u bytes %llu dropped %llu top_tiles %llu\n", info.enabled, info.undo_entries,
+               info.redo_entries, (unsigned long long)info.bytes, (unsigned long long)info.dropped, (unsigned long long)info.top_tiles);
+        return true;
+    };
     if (solid) { /* uploads the scene, fills every volume's cavities in place; the host mirrors follow, so nothing is left dirty */
         unsigned long long filled = 0;
         for (const auto& placed : scene->GetAllPlacedObjects()) {
@@ -268,6 +293,9 @@ int main(int argc, char** argv) {
         scene->PostRender();
         printf("sdf: band %d, %llu surfels, %llu voxels nearer than the band, redistanced on the device\n", sdf, surfels, near);
     }
+    /* --undo: the history is on before the first dab; what --solid and --sdf did above is not part of it.  256 entries or 256 MiB */
+    if (undoSteps > 0 && (!first || !hip->EnableHistory(*first, 256, (uint64_t)256 << 20))) return 1;
+    if (undoSteps > 0) scene->PostRender(); /* the scene is on the device now: no dab is followed by an upload that would empty the history */
     const std::shared_ptr<Voxel::VVoxelVolume> stampTorus = editStamp ? InitStampTorus() : nullptr;
     int stampTurns = 0;
     unsigned long long stampedVoxels = 0, smoothedVoxels = 0, warpedVoxels = 0;
@@ -438,13 +466,13 @@ int main(int argc, char** argv) {
             printf("wrote %s\n", outPath.c_str());
         }
     }
-    VObjectPtr<Scene::VVoxelObject> first;
-    for (const auto& placed : scene->GetAllPlacedObjects()) {
-        const auto object = std::dynamic_pointer_cast<Scene::VVoxelObject>(placed);
-        if (object && object->GetVoxelVolume()) {
-            first = object;
-            break;
-        }
+    if (undoSteps > 0) { /* the K newest dabs taken back on the device, bit for bit; the host mirror follows */
+        vrt_brush_result res;
+        if (!printHistory() || !hip->Undo(*first, undoSteps, &res)) return 1;
+        scene->PostRender();
+        printf("undo: %d entries, %llu voxels restored in (%d, %d, %d)..(%d, %d, %d)\n", undoSteps, (unsigned long long)res.written, res.lo[0], res.lo[1],
+               res.lo[2], res.hi[0], res.hi[1], res.hi[2]);
+        if (!printHistory()) return 1;
     }
     if (keepLargest) { /* whatever the dabs cut loose goes */
         if (!first) return 1;

@@ -162,6 +162,7 @@ int vrt_volume_apply_brushes(vrt_ctx* ctx, int slot, int n_rec, const vrt_brush*
     const bool texel16 = h.format == VRT_FORMAT_TEXEL16;
     int rc = quiesce(ctx);
     if (rc != VRT_OK) return rc;
+    if ((rc = history_capture(ctx, slot, foot)) != VRT_OK) return rc;
     bool changed = false;
     for (size_t di = 0; di < ctx->dev.size(); di++) {
         DeviceState& D = ctx->dev[di];
@@ -171,6 +172,7 @@ int vrt_volume_apply_brushes(vrt_ctx* ctx, int slot, int n_rec, const vrt_brush*
         Written got;
         rc = read_report(D, N, got);
         if (rc != VRT_OK) return rc;
+        if ((rc = history_record(ctx, D, slot, got.lo, got.hi)) != VRT_OK) return rc;
         if (di == 0 && result) *result = brush_result(got);
         /* the density writes count: nothing written, or only material ids, and no derived structure changes */
         rc = rebuild_written(ctx, D, slot, got.lo, got.hi, got.high, changed);

@@ -483,6 +483,8 @@ int vrt_volume_components(vrt_ctx* ctx, int slot, const vrt_components* rec, vrt
             out.listed++;
         }
     }
+    const int zero[3] = {0, 0, 0}, last[3] = {N - 1, N - 1, N - 1}; /* only a call that removes something has a footprint: the whole grid */
+    if (out.removed > 0 && (rc = history_capture(ctx, slot, derived_boxes(h, zero, last).samples)) != VRT_OK) return rc;
     bool changed = false;
     for (size_t di = 0; out.removed > 0 && di < ctx->dev.size(); di++) {
         DeviceState& D = ctx->dev[di];
@@ -493,6 +495,7 @@ int vrt_volume_components(vrt_ctx* ctx, int slot, const vrt_components* rec, vrt
         Written got;
         rc = read_report(D, N, got);
         if (rc != VRT_OK) return rc;
+        if ((rc = history_record(ctx, D, slot, got.lo, got.hi)) != VRT_OK) return rc;
         if (di == 0) {
             for (int a = 0; a < 3; a++) out.lo[a] = got.lo[a], out.hi[a] = got.hi[a];
             out.written = got.low;

@@ -51,6 +51,32 @@ struct DeviceVolume {
     uint8_t* seeds = nullptr;
 };
 
+/* A slot's edit history (vrt_volume_history).  The stacks exist once, on the host: one tile count per entry, oldest first in
+   `undo`, and in `redo` the entry vrt_volume_redo takes next last.  Every device keeps its own record of each entry (DeviceHistory, in
+   the same order): volumes are replicated and every device computes the same bytes. */
+struct HostHistory {
+    bool on = false;
+    int max_entries = 0;
+    uint64_t max_bytes = 0;
+    std::vector<uint64_t> undo, redo; /* tiles per entry */
+    uint64_t dropped = 0;
+    /* the edit call in progress: its footprint sits in every device's kBufHistory (history_capture), until history_record has seen the
+       last device; `lost`: the call has nothing (more) to record — no bit changed, or its entry went with the whole history */
+    bool captured = false, lost = false;
+    EditBox foot = {{0, 0, 0}, {0, 0, 0}};
+    uint64_t tiles() const {
+        uint64_t n = 0;
+        for (uint64_t t : undo) n += t;
+        for (uint64_t t : redo) n += t;
+        return n;
+    }
+};
+/* One device's records of a slot's entries: `tiles` tile records of VRT_HISTORY_TILE_BYTES each (vrt_history.hip), one allocation per
+   entry.  free_device_volume frees them with the slot. */
+struct DeviceHistory {
+    std::vector<void*> undo, redo;
+};
+
 /* The grid's axis order is {x, z, y}: grid axis a is xyz axis grid_axis(a), and the other way round. */
 constexpr int grid_axis(int a) { return a == 0 ? 0 : (a == 1 ? 2 : 1); }
 
@@ -101,6 +127,8 @@ enum BufferId {
     kBufSmoothWarp,    /* vrt_volume_smooth: two fp32 copies of the work box and its weights; vrt_volume_warp: the value to store and the
                           new id of every sample of the region's box (one buffer for the two calls) */
     kBufQuery,         /* vrt_trace_rays_host: the rays and then the hit records of a batch */
+    kBufHistory,       /* an edit call on a slot whose history is on: the tile counters, then the stored bits (4 B) and the id (1 B) of
+                          every sample of the call's footprint as they were before it */
     kBufCount
 };
 
@@ -108,6 +136,7 @@ struct DeviceState {
     int ordinal = 0;
     hipStream_t stream = nullptr;
     DeviceVolume vol[VRT_MAX_VOLUMES];
+    DeviceHistory hist[VRT_MAX_VOLUMES];
     DVolume* d_vols = nullptr;
     DInstance* d_inst = nullptr;
     DBvhNode* d_nodes = nullptr;
@@ -175,6 +204,7 @@ struct DeviceState {
 struct vrt_ctx {
     std::vector<vrt::DeviceState> dev;
     vrt::HostVolume vol[VRT_MAX_VOLUMES];
+    vrt::HostHistory hist[VRT_MAX_VOLUMES];
     vrt::HostTexture tex[VRT_MAX_TEXTURES];
     int env_size = 0;
     int upload_format = VRT_FORMAT_F32; /* vrt_set_volume_format: device format of the following uploads */
@@ -222,7 +252,7 @@ int ensure_buffer(Buffer& b, size_t bytes);
 void fill_dvolume(const vrt_ctx* ctx, const DeviceState& D, const HostVolume& h, const DeviceVolume& d, DVolume& out);
 /* The volume table of every device, from the slots as they are now. */
 int sync_volume_table(vrt_ctx* ctx);
-/* Frees what one device holds of a slot. */
+/* Frees what one device holds of a slot, the records of its history included. */
 int free_device_volume(DeviceState& D, int slot);
 
 /* ---- What the volume edit calls share (defined in vrt_slots.hip) ---- */
@@ -230,6 +260,17 @@ int free_device_volume(DeviceState& D, int slot);
 int clip_box(int N, const int* origin, const int* size, int lo[3], int hi[3]);
 /* Once per call, ahead of the first write: waits for what is enqueued on every device and gives each its report records. */
 int quiesce(vrt_ctx* ctx);
+/* A slot whose history is on (both do nothing otherwise).  After quiesce and ahead of the first write: the samples of the call's footprint
+   (grid order) copied aside on every device; VRT_ERR_OOM, and nothing written, when a device has no memory for that. */
+int history_capture(vrt_ctx* ctx, int slot, const EditBox& foot);
+/* After read_report, per device: the tiles of the xyz box lo..hi (what the launch reported it wrote) that differ in bits from the copy
+   become the device's record of a new undo entry; the first device also keeps the host's books (redo emptied, the limits applied).
+   A box with lo > hi, or one without a changed tile, records nothing. */
+int history_record(vrt_ctx* ctx, DeviceState& D, int slot, const int lo[3], const int hi[3]);
+/* Frees every entry of the slot on every device; the limits stay.  counted: the entries count as dropped. */
+void history_drop(vrt_ctx* ctx, int slot, bool counted);
+/* Drops the oldest undo entries (then, with none left, the redo entries furthest ahead) until the slot's limits hold. */
+void history_trim(vrt_ctx* ctx, int slot);
 struct Written {
     int lo[3], hi[3];
     unsigned long long low, high;

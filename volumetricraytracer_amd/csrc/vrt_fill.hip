@@ -202,6 +202,8 @@ int vrt_volume_fill_enclosed(vrt_ctx* ctx, int slot, float wall, int material, v
     const unsigned long long round_cap = (unsigned long long)N * N * N + 1ull;
     int rc = quiesce(ctx);
     if (rc != VRT_OK) return rc;
+    const int zero[3] = {0, 0, 0}, last[3] = {N - 1, N - 1, N - 1};
+    if ((rc = history_capture(ctx, slot, derived_boxes(h, zero, last).samples)) != VRT_OK) return rc;
     bool changed = false;
     for (size_t di = 0; di < ctx->dev.size(); di++) {
         DeviceState& D = ctx->dev[di];
@@ -227,6 +229,7 @@ int vrt_volume_fill_enclosed(vrt_ctx* ctx, int slot, float wall, int material, v
         Written got;
         rc = read_report(D, N, got);
         if (rc != VRT_OK) return rc;
+        if ((rc = history_record(ctx, D, slot, got.lo, got.hi)) != VRT_OK) return rc;
         if (di == 0 && result)
             *result = vrt_fill_result{{got.lo[0], got.lo[1], got.lo[2]}, {got.hi[0], got.hi[1], got.hi[2]}, got.low,
                                       (uint32_t)std::min<unsigned long long>(rounds, 0xffffffffull), 0};

@@ -287,6 +287,7 @@ int vrt_volume_redistance(vrt_ctx* ctx, int slot, int band, int from, const int*
     const float unit = cell / h.density_scale;
     rc = quiesce(ctx);
     if (rc != VRT_OK) return rc;
+    if ((rc = history_capture(ctx, slot, box)) != VRT_OK) return rc;
     std::vector<unsigned> surfels(ctx->dev.size(), 0u);
     for (size_t di = 0; di < ctx->dev.size(); di++) { /* everything that can run out of memory, before any sample is written */
         DeviceState& D = ctx->dev[di];
@@ -310,6 +311,7 @@ int vrt_volume_redistance(vrt_ctx* ctx, int slot, int band, int from, const int*
         Written got;
         rc = read_report(D, N, got);
         if (rc != VRT_OK) return rc;
+        if ((rc = history_record(ctx, D, slot, got.lo, got.hi)) != VRT_OK) return rc;
         if (di == 0 && result)
             *result = vrt_redistance_result{{got.lo[0], got.lo[1], got.lo[2]}, {got.hi[0], got.hi[1], got.hi[2]}, got.low, got.high, surfels[di], 0};
         rc = rebuild_written(ctx, D, slot, lo, hi, 1, changed); /* the requested box, whatever was reported */

@@ -95,6 +95,10 @@ int free_device_volume(DeviceState& D, int slot) {
     if (v.cube_skip) HIP_TRY(hipFree(v.cube_skip));
     if (v.seeds) HIP_TRY(hipFree(v.seeds));
     v = DeviceVolume();
+    for (std::vector<void*>* stack : {&D.hist[slot].undo, &D.hist[slot].redo}) {
+        for (void* record : *stack) HIP_TRY(hipFree(record));
+        stack->clear();
+    }
     return VRT_OK;
 }
 
@@ -197,6 +201,8 @@ int upload_volume(vrt_ctx* ctx, int slot, uint8_t resolution, float extent, cons
     const int N = (1 << resolution) + 1; /* VoxelVolume.cpp:23 */
     const int nb = (N - 1 + kBrickCells - 1) / kBrickCells;
     const size_t count = (size_t)N * N * N;
+    ctx->hist[slot].undo.clear(); /* a new volume: its history starts empty, with the limits it had */
+    ctx->hist[slot].redo.clear();
     for (auto& D : ctx->dev) {
         int rc = free_device_volume(D, slot);
         if (rc != VRT_OK) return rc;
@@ -297,6 +303,110 @@ int quiesce(vrt_ctx* ctx) {
         HIP_TRY(hipSetDevice(D.ordinal));
         HIP_TRY(hipDeviceSynchronize());
         if (!D.d_brush) HIP_TRY(hipMalloc(&D.d_brush, kBrushSlots * sizeof(DBrushSlot)));
+    }
+    return VRT_OK;
+}
+
+/* ---- The edit history's share of the skeleton (the kernels: vrt_history.hip) ----
+ * Frees one entry's record on every device that has it: the first of a stack, or all. */
+static void free_records(vrt_ctx* ctx, int slot, bool redo, bool all) {
+    for (auto& D : ctx->dev) {
+        std::vector<void*>& stack = redo ? D.hist[slot].redo : D.hist[slot].undo;
+        if (stack.empty() || hipSetDevice(D.ordinal) != hipSuccess) continue;
+        for (size_t i = 0; i < (all ? stack.size() : 1); i++) (void)hipFree(stack[i]);
+        stack.erase(stack.begin(), all ? stack.end() : stack.begin() + 1);
+    }
+}
+
+void history_drop(vrt_ctx* ctx, int slot, bool counted) {
+    HostHistory& hh = ctx->hist[slot];
+    if (counted) hh.dropped += hh.undo.size() + hh.redo.size();
+    hh.undo.clear();
+    hh.redo.clear();
+    free_records(ctx, slot, false, true);
+    free_records(ctx, slot, true, true);
+}
+
+void history_trim(vrt_ctx* ctx, int slot) {
+    HostHistory& hh = ctx->hist[slot];
+    while (hh.on && (hh.undo.size() > (size_t)hh.max_entries || hh.tiles() * VRT_HISTORY_TILE_BYTES > hh.max_bytes)) {
+        std::vector<uint64_t>& stack = hh.undo.empty() ? hh.redo : hh.undo; /* both stacks keep the entry to go at their front */
+        if (stack.empty()) break;
+        free_records(ctx, slot, &stack == &hh.redo, false);
+        stack.erase(stack.begin());
+        hh.dropped++;
+    }
+}
+
+int history_capture(vrt_ctx* ctx, int slot, const EditBox& foot) {
+    HostHistory& hh = ctx->hist[slot];
+    hh.captured = false;
+    if (!hh.on) return VRT_OK;
+    for (auto& D : ctx->dev) { /* every allocation comes before any write */
+        HIP_TRY(hipSetDevice(D.ordinal));
+        int rc = ensure_buffer(D.buf[kBufHistory], history_scratch_bytes(foot));
+        if (rc != VRT_OK) return rc;
+    }
+    for (auto& D : ctx->dev) {
+        HIP_TRY(hipSetDevice(D.ordinal));
+        HIP_TRY(launch_history_capture(D.vol[slot].dense, D.vol[slot].material, ctx->vol[slot].N, foot, D.buf[kBufHistory].p, D.stream));
+    }
+    hh.foot = foot;
+    hh.captured = true;
+    hh.lost = false;
+    return VRT_OK;
+}
+
+/* The first pass counts the changed tiles, the host sizes the record exactly, the second pass fills it.  The first device keeps the books
+ * for all: it empties the redo stack, pushes the entry and applies the limits; the others add their record of the same entry. */
+int history_record(vrt_ctx* ctx, DeviceState& D, int slot, const int lo[3], const int hi[3]) {
+    HostHistory& hh = ctx->hist[slot];
+    if (!hh.on || !hh.captured) return VRT_OK;
+    const bool first = &D == &ctx->dev.front();
+    if (&D == &ctx->dev.back()) hh.captured = false; /* the call's last word */
+    if (hh.lost || lo[0] > hi[0] || lo[1] > hi[1] || lo[2] > hi[2]) return VRT_OK;
+    const HostVolume& h = ctx->vol[slot];
+    const DeviceVolume& v = D.vol[slot];
+    const EditBox tiles = history_tile_box(derived_boxes(h, lo, hi).samples);
+    void* scratch = D.buf[kBufHistory].p;
+    unsigned count = 0;
+    HIP_TRY(launch_history_compact(v.dense, v.material, h.N, hh.foot, scratch, tiles, nullptr, 0u, D.stream));
+    HIP_TRY(hipMemcpyAsync(&count, history_changed_tiles(scratch), sizeof count, hipMemcpyDeviceToHost, D.stream));
+    HIP_TRY(hipStreamSynchronize(D.stream));
+    if (first) {
+        if (count == 0u) {
+            hh.lost = true; /* no bit changed, on any device: nothing is recorded and the redo stack stays */
+            return VRT_OK;
+        }
+        hh.redo.clear();
+        free_records(ctx, slot, true, true);
+        if ((uint64_t)count * VRT_HISTORY_TILE_BYTES > hh.max_bytes) { /* larger than the history may be: everything goes, this entry too */
+            hh.dropped++;
+            hh.lost = true;
+        } else {
+            hh.undo.push_back(count);
+        }
+    } else if (count != hh.undo.back()) {
+        fprintf(stderr, "[vrt] edit history: device %d changed %u tiles, the first device %llu\n", D.ordinal, count, (unsigned long long)hh.undo.back());
+        hh.lost = true;
+    }
+    void* record = nullptr;
+    if (!hh.lost) {
+        HIP_TRY(hipSetDevice(D.ordinal));
+        if (hipMalloc(&record, (size_t)count * VRT_HISTORY_TILE_BYTES) != hipSuccess) {
+            (void)hipGetLastError(); /* no memory for the record: the edit stands, the history does not */
+            hh.lost = true;
+        }
+    }
+    if (hh.lost) {
+        history_drop(ctx, slot, true);
+        return hipSetDevice(D.ordinal) == hipSuccess ? VRT_OK : VRT_ERR_HIP;
+    }
+    D.hist[slot].undo.push_back(record);
+    HIP_TRY(launch_history_compact(v.dense, v.material, h.N, hh.foot, scratch, tiles, record, count, D.stream));
+    if (first) {
+        history_trim(ctx, slot);
+        HIP_TRY(hipSetDevice(D.ordinal));
     }
     return VRT_OK;
 }
@@ -505,6 +615,7 @@ int vrt_volume_free(vrt_ctx* ctx, int slot) {
         if (rc != VRT_OK) return rc;
     }
     ctx->vol[slot] = HostVolume();
+    ctx->hist[slot] = HostHistory();
     ctx->scene_stale = true;
     return sync_volume_table(ctx);
 }

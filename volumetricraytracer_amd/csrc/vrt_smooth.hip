@@ -158,6 +158,7 @@ int vrt_volume_smooth(vrt_ctx* ctx, int slot, const vrt_smooth* rec, vrt_brush_r
     const EditBox region = derived_boxes(h, lo, hi).samples, work = derived_boxes(h, work_lo, work_hi).samples;
     int rc = quiesce(ctx);
     if (rc != VRT_OK) return rc;
+    if ((rc = history_capture(ctx, slot, region)) != VRT_OK) return rc;
     for (auto& D : ctx->dev) { /* every allocation comes before any write */
         HIP_TRY(hipSetDevice(D.ordinal));
         rc = ensure_buffer(D.buf[kBufSmoothWarp], smooth_scratch_bytes(work));
@@ -172,6 +173,7 @@ int vrt_volume_smooth(vrt_ctx* ctx, int slot, const vrt_smooth* rec, vrt_brush_r
         Written got;
         rc = read_report(D, N, got);
         if (rc != VRT_OK) return rc;
+        if ((rc = history_record(ctx, D, slot, got.lo, got.hi)) != VRT_OK) return rc;
         if (di == 0 && result) *result = brush_result(got);
         rc = rebuild_written(ctx, D, slot, got.lo, got.hi, got.low, changed); /* every written sample is a density write */
         if (rc != VRT_OK) return rc;

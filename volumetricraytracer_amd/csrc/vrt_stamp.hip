@@ -117,6 +117,7 @@ int vrt_volume_stamp(vrt_ctx* ctx, int dst_slot, int src_slot, const vrt_stamp* 
     const EditBox foot = derived_boxes(h, lo, hi).samples;
     int rc = quiesce(ctx);
     if (rc != VRT_OK) return rc;
+    if ((rc = history_capture(ctx, dst_slot, foot)) != VRT_OK) return rc;
     bool changed = false;
     for (size_t di = 0; di < ctx->dev.size(); di++) {
         DeviceState& D = ctx->dev[di];
@@ -128,6 +129,7 @@ int vrt_volume_stamp(vrt_ctx* ctx, int dst_slot, int src_slot, const vrt_stamp* 
         Written got;
         rc = read_report(D, N, got);
         if (rc != VRT_OK) return rc;
+        if ((rc = history_record(ctx, D, dst_slot, got.lo, got.hi)) != VRT_OK) return rc;
         if (di == 0 && result) *result = brush_result(got);
         rc = rebuild_written(ctx, D, dst_slot, got.lo, got.hi, got.low, changed); /* every written sample is a density write */
         if (rc != VRT_OK) return rc;

@@ -533,6 +533,7 @@ static int update_region(vrt_ctx* ctx, int slot, const int origin[3], const int 
     const bool texel16 = h.format == VRT_FORMAT_TEXEL16;
     rc = quiesce(ctx);
     if (rc != VRT_OK) return rc;
+    if ((rc = history_capture(ctx, slot, box)) != VRT_OK) return rc;
     bool changed = false;
     for (auto& D : ctx->dev) {
         HIP_TRY(hipSetDevice(D.ordinal));
@@ -547,6 +548,7 @@ static int update_region(vrt_ctx* ctx, int slot, const int origin[3], const int 
                 HIP_TRY(hipMemcpyAsync(static_cast<char*>(D.buf[kBufEditStaging].p) + count * sizeof(float), material, count, hipMemcpyHostToDevice, D.stream));
         }
         HIP_TRY(launch_scatter_region(D.buf[kBufEditStaging].p, voxels != nullptr, material != nullptr, texel16, v.dense, v.material, N, box, D.stream));
+        if ((rc = history_record(ctx, D, slot, first, last)) != VRT_OK) return rc;
         rc = rebuild_written(ctx, D, slot, first, last, count, changed); /* reads no report: its own box, always */
         if (rc != VRT_OK) return rc;
     }

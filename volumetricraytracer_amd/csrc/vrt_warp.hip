@@ -133,6 +133,7 @@ int vrt_volume_warp(vrt_ctx* ctx, int slot, const vrt_warp* rec, vrt_brush_resul
     const float off = vrt_warp_core::off_of(*rec, vrt_stamp_core::unit_of(N, h.extent, h.density_scale));
     int rc = quiesce(ctx);
     if (rc != VRT_OK) return rc;
+    if ((rc = history_capture(ctx, slot, region)) != VRT_OK) return rc;
     for (auto& D : ctx->dev) { /* every allocation comes before any write */
         HIP_TRY(hipSetDevice(D.ordinal));
         rc = ensure_buffer(D.buf[kBufSmoothWarp], warp_scratch_bytes(region));
@@ -147,6 +148,7 @@ int vrt_volume_warp(vrt_ctx* ctx, int slot, const vrt_warp* rec, vrt_brush_resul
         Written got;
         rc = read_report(D, N, got);
         if (rc != VRT_OK) return rc;
+        if ((rc = history_record(ctx, D, slot, got.lo, got.hi)) != VRT_OK) return rc;
         if (di == 0 && result) *result = brush_result(got);
         /* the density writes count: nothing written, or only material ids, and no derived structure changes */
         rc = rebuild_written(ctx, D, slot, got.lo, got.hi, got.high, changed);

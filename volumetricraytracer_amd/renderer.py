@@ -420,6 +420,42 @@ class VHipRenderer:
             self._mirror_box(slot, vol, wlo, whi)
         return {"written": int(res.written), "near": int(res.near), "surfels": int(res.surfels), "lo": wlo, "hi": whi}
 
+    def enable_history(self, slot: int, max_entries: int, max_bytes: int) -> None:
+        """vrt_volume_history: from now on every edit call on the volume resident in `slot` that changes a bit records, on the
+        device, the 4^3 tiles it changed as they were — at most max_entries undo entries and max_bytes bytes per device, the oldest
+        entries going first.  (0, 0) turns the history off and frees it.  Uploading over the slot empties the history; freeing the
+        slot turns it off."""
+        self._require()
+        _abi.check(self._lib.vrt_volume_history(self._ctx, int(slot), int(max_entries), int(max_bytes)), "vrt_volume_history")
+
+    def history_info(self, slot: int) -> dict:
+        """vrt_volume_history_info: {"enabled", "max_entries", "max_bytes", "undo_entries", "redo_entries", "bytes", "dropped",
+        "top_tiles"} — bytes is tiles held x _abi.HISTORY_TILE_BYTES, top_tiles the tiles of the entry undo would take next."""
+        self._require()
+        info = _abi.vrt_history_info()
+        _abi.check(self._lib.vrt_volume_history_info(self._ctx, int(slot), C.byref(info)), "vrt_volume_history_info")
+        return {name: int(getattr(info, name)) for name, _ in _abi.vrt_history_info._fields_ if name != "reserved_"}
+
+    def undo(self, slot: int, steps: int = 1, vol: Optional[VVoxelVolume] = None) -> dict:
+        """vrt_volume_undo: the `steps` newest recorded edits of the volume resident in `slot` taken back on the device, bit for bit
+        (also on a TEXEL16 slot, where a download and an update of the same box are not).  Given the slot's host mirror `vol`, the
+        changed box is then read back as apply_brushes does.  Returns {"written", "lo", "hi"} (xyz, inclusive; lo > hi when no
+        sample changed); written sums the samples each entry changed."""
+        return self._step_history("vrt_volume_undo", slot, steps, vol)
+
+    def redo(self, slot: int, steps: int = 1, vol: Optional[VVoxelVolume] = None) -> dict:
+        """vrt_volume_redo: the `steps` edits undone last, done again; otherwise as undo."""
+        return self._step_history("vrt_volume_redo", slot, steps, vol)
+
+    def _step_history(self, call: str, slot: int, steps: int, vol: Optional[VVoxelVolume]) -> dict:
+        self._require()
+        res = _abi.vrt_brush_result()
+        _abi.check(getattr(self._lib, call)(self._ctx, int(slot), int(steps), C.byref(res)), call)
+        lo, hi = tuple(res.lo), tuple(res.hi)
+        if res.written and vol is not None:
+            self._mirror_box(slot, vol, lo, hi)
+        return {"written": int(res.written), "lo": lo, "hi": hi}
+
     def extract_mesh(self, slot: int, iso: float = 0.0, lo=None, hi=None):
         """vrt_volume_extract_mesh: the surface density = iso of the volume resident in `slot`, over the samples lo..hi (inclusive xyz
         corners; both None: the whole grid), as an indexed triangle mesh built on the device by surface nets: one call that counts,
