@@ -15,6 +15,8 @@
  *   vrt_set_volume_format,          VDXVoxelVolume::EncodeVoxel  RDXVoxelVolume.cpp:399-421 (the 4-byte volume texel,
  *   vrt_volume_upload_texels        DecodeDensity Shaders/Include/Voxel.hlsli:254-266)
  *   vrt_volume_set_material         VDXVoxelVolume::UpdateGeometryConstantBuffer  :368-397
+ *   vrt_volume_set_palette,         (no reference analogue: its shaders ignore VVoxel::Material — a palette of materials per volume slot,
+ *   vrt_volume_get_palette          and every hit shaded with the entry of the material id of the voxel it lands on)
  *   vrt_volume_update_region,       VVoxelVolume::SetVoxel / MakeDirty / IsDirty  Voxel/Private/VoxelVolume.cpp:59-137, and
  *   vrt_volume_update_voxels        VDXVoxelVolume::UpdateFromVoxelVolume  RDXVoxelVolume.cpp:33-60 (re-upload of a dirty volume),
  *                                   for a box of voxels instead of the whole volume
@@ -301,6 +303,49 @@ int vrt_set_volume_format(vrt_ctx* ctx, int format);
  * G = q & 0xff, B = A = material.  Always VRT_FORMAT_TEXEL16. */
 int vrt_volume_upload_texels(vrt_ctx* ctx, int slot, uint8_t resolution, float extent, const uint8_t* rgba8_texels);
 int vrt_volume_set_material(vrt_ctx* ctx, int slot, const vrt_material* material);
+/* Per-voxel materials: a palette per volume slot.  Every sample of a resident volume carries a material id (vrt_voxel::material; what
+ * VRT_BRUSH_PAINT writes and the other volume calls keep).  With a palette on its slot, a hit renders with the vrt_material of its id.
+ *
+ * n in 1 .. VRT_MAX_PALETTE with entries != NULL gives the slot a palette of n entries, replicated on every device of the context;
+ * n == 0 takes it away (entries may then be NULL).  Default: none, and a slot without a palette renders exactly as it always did.
+ * Each entry becomes device constants exactly as vrt_volume_set_material derives the slot's own (clamped roughness and metallic,
+ * k = (roughness + 1)^2 / 8 from the unclamped roughness, the raw pair for the textured modes): a palette whose entries all equal M
+ * renders what vrt_volume_set_material(M) renders, bit for bit.  The call waits for the work already enqueued on every device, as the
+ * edit calls do.
+ *
+ * Which entry a hit gets — all fp32, evaluated as parenthesised, no fused multiply-add:
+ *   1. p = the object-space hit point of the level's ray (the camera ray, or the ray behind a mirror bounce), computed as for
+ *      vrt_hit::voxel.  Per axis a:  g_a = (p_a + extent) * inv_cell,  c_a = clamp(floor(g_a), 0, N-2),  f_a = g_a - (float)c_a.
+ *   2. Corner j = dx + 2 dy + 4 dz of cell c is sample (c_x+dx, c_y+dy, c_z+dz).  It is INSIDE when its decoded density d is not NaN
+ *      and d <= 0 (d: the stored float, or stored * 0.01f on a VRT_FORMAT_TEXEL16 slot — i.e. the stored integer field's sign; -0.0f
+ *      counts as <= 0).
+ *   3. The chosen corner is the INSIDE corner with the smallest ((f_x-dx)^2 + (f_y-dy)^2) + (f_z-dz)^2, the lowest j on a tie.  With no
+ *      INSIDE corner: the sample vrt_hit::voxel names (the nearest one).
+ *   4. id = the chosen sample's material byte.  id < n takes palette entry id, any other id the slot's own vrt_material.  From there on
+ *      as always: the textured modes multiply albedo and the roughness / metallic factors onto that surface, the normal map tilts the
+ *      normal, roughness < 0.3 decides the mirror bounce, unlit modes store the entry's albedo.
+ * (Not the nearest sample: PAINT, the Voxelizer and fill_enclosed put ids on inside samples only, and the sample nearest to a point of
+ * the zero surface is an outside one about half the time.)  vrt_hit::material keeps its meaning.
+ *
+ * Which launches take it.  A launch whose scene (vrt_block::scenes: any frame's scene) has an instance of a slot with a palette is a full
+ * closest hit in ONE kernel, however many frames the block has and even where lights and materials alone would allow the lean kernel:
+ * vrt_debug_last_kernel_form reports VRT_FORM_FULL | VRT_FORM_PALETTE and never VRT_FORM_PASSES; VRT_FORM_MAY_BOUNCE also counts palette
+ * entries with roughness < 0.3.  VRT_FLAG_FULL_THREE_PASS with a palette in sight is VRT_ERR_UNSUPPORTED, refused before any state
+ * changes; VRT_FLAG_DIAG_TIMELINE is ignored, as the full closest hit ignores it anyway.
+ *
+ * Lifetime.  The palette follows the slot's vrt_material: vrt_volume_upload*, vrt_voxelize_mesh and vrt_volume_upload_texels into a used
+ * slot keep it (as they keep the material), vrt_volume_free frees it, and a slot used for the first time starts without one.
+ * vrt_set_volume_format touches neither.  Like vrt_volume_set_material the call is neither recorded in nor undone by the edit history and
+ * leaves the stacks alone; the painted ids are, so undoing a PAINT dab changes the next frame.
+ *
+ * Errors, all checked before any state changes: VRT_ERR_INVALID for a NULL context, n < 0 or n > VRT_MAX_PALETTE, n > 0 with NULL
+ * entries, or a non-finite field in any entry; VRT_ERR_SLOT for an unused slot. */
+#define VRT_MAX_PALETTE 256
+int vrt_volume_set_palette(vrt_ctx* ctx, int slot, int n, const vrt_material* entries_or_null);
+/* What vrt_volume_set_palette was given, bit for bit: *n_out entries (0: no palette) into entries_or_null[0 .. capacity).  A capacity
+ * below n is VRT_ERR_INVALID with *n_out filled in (capacity 0 with NULL entries asks for n alone, when the slot has a palette).
+ * VRT_ERR_INVALID for a NULL context or n_out, a negative capacity, or capacity > 0 with NULL entries; VRT_ERR_SLOT for an unused slot. */
+int vrt_volume_get_palette(vrt_ctx* ctx, int slot, int capacity, vrt_material* entries_or_null, int* n_out);
 /* density_scale: object-space length of one density unit (1 for metric SDFs; the Voxelizer's
  * extraction threshold for its shell volumes).  step_max: largest object-space step that is
  * safe to take from any sample (<= 0: unbounded). */
@@ -894,7 +939,7 @@ typedef struct vrt_history_info {     /* 64 B */
  * box, the update's box, the stamp's conservative box, the region's box of smooth and warp, the requested box of redistance, the whole
  * grid for fill_enclosed and for a components call that removes something) is allocated on every device before any sample is written;
  * when that fails the call returns VRT_ERR_OOM and the volume is untouched.
- * What the history is not.  vrt_volume_set_metric, _set_material and _set_textures are neither recorded nor undone and leave the stacks
+ * What the history is not.  vrt_volume_set_metric, _set_material, _set_palette and _set_textures are neither recorded nor undone and leave the stacks
  * alone.  vrt_volume_upload* and vrt_voxelize_mesh onto the slot drop its entries (not counted) and keep its limits; vrt_volume_free
  * drops them and turns the history off.
  * Errors, all checked before any state is touched: VRT_ERR_INVALID for a NULL context, max_entries < 0, or exactly one of the two
@@ -1163,6 +1208,7 @@ long long vrt_debug_wave_records(vrt_ctx* ctx, int which, uint32_t* out, long lo
 #define VRT_FORM_MAY_BOUNCE 8  /* bounces allowed and some material can mirror */
 #define VRT_FORM_LEAN_REF 16   /* the lean kernel's instantiation that folds constant (1x1) textures in and honours
                                   VRT_FLAG_REFERENCE_VIEW_VECTOR / _BOUNDARY_TEXELS */
+#define VRT_FORM_PALETTE 32    /* a slot with a palette (vrt_volume_set_palette) is instanced by the launch's scene(s) */
 int vrt_debug_last_kernel_form(vrt_ctx* ctx);
 
 /* Diagnostics: the rate (G trilinear samples per second) the chip sustains for the march's inner operation in isolation — the 8 taps of a

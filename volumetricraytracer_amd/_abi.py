@@ -38,7 +38,8 @@ MODE_CUBE_UNLIT = 5
 MODE_CUBE_NOTEX = 6
 MODE_CUBE_NOTEX_UNLIT = 7
 
-FORM_FULL, FORM_PASSES, FORM_TEXTURED, FORM_MAY_BOUNCE, FORM_LEAN_REF = 1, 2, 4, 8, 16  # vrt_debug_last_kernel_form
+FORM_FULL, FORM_PASSES, FORM_TEXTURED, FORM_MAY_BOUNCE, FORM_LEAN_REF, FORM_PALETTE = 1, 2, 4, 8, 16, 32  # vrt_debug_last_kernel_form
+VRT_MAX_PALETTE = 256
 FLAG_DIAG_TIMELINE = 4
 FLAG_OUTPUT_RGBA8 = 8
 FLAG_NO_TIMING = 16
@@ -360,6 +361,8 @@ SYMBOLS = {
     "vrt_set_volume_format": (C.c_int, [C.c_void_p, C.c_int]),
     "vrt_volume_upload_texels": (C.c_int, [C.c_void_p, C.c_int, C.c_uint8, C.c_float, C.c_void_p]),
     "vrt_volume_set_material": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(vrt_material)]),
+    "vrt_volume_set_palette": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.POINTER(vrt_material)]),
+    "vrt_volume_get_palette": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.POINTER(vrt_material), C.POINTER(C.c_int)]),
     "vrt_volume_set_metric": (C.c_int, [C.c_void_p, C.c_int, C.c_float, C.c_float]),
     "vrt_texture_upload": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p]),
     "vrt_texture_free": (C.c_int, [C.c_void_p, C.c_int]),

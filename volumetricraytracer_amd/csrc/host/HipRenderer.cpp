@@ -884,6 +884,21 @@ bool VHipRenderer::Undo(const Scene::VVoxelObject& object, int steps, vrt_brush_
 
 bool VHipRenderer::Redo(const Scene::VVoxelObject& object, int steps, vrt_brush_result* result) { return StepHistory(object, steps, true, result); }
 
+bool VHipRenderer::SetPalette(const Scene::VVoxelObject& object, const std::vector<VMaterial>& entries) {
+    const int slot = SyncedSlotOf(object, "SetPalette");
+    if (slot < 0) return false;
+    std::vector<vrt_material> rec;
+    rec.reserve(entries.size());
+    for (const VMaterial& m : entries)
+        rec.push_back(vrt_material{{m.AlbedoColor.R, m.AlbedoColor.G, m.AlbedoColor.B, m.AlbedoColor.A}, m.Roughness, m.Metallic});
+    return ok(vrt_volume_set_palette(Ctx, slot, (int)rec.size(), rec.empty() ? nullptr : rec.data()), "vrt_volume_set_palette");
+}
+
+bool VHipRenderer::ClearPalette(const Scene::VVoxelObject& object) {
+    const int slot = SyncedSlotOf(object, "ClearPalette");
+    return slot >= 0 && ok(vrt_volume_set_palette(Ctx, slot, 0, nullptr), "vrt_volume_set_palette");
+}
+
 bool VHipRenderer::WarpFromMotion(const VVector& pivot, const VVector& translation, const VQuat& rotation, float scale, vrt_warp& rec) {
     const double c[3] = {pivot.X, pivot.Y, pivot.Z}, t[3] = {translation.X, translation.Y, translation.Z};
     const double q[4] = {rotation.x, rotation.y, rotation.z, rotation.w};

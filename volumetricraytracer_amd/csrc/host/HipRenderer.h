@@ -141,6 +141,14 @@ public:
     bool HistoryInfo(const Scene::VVoxelObject& object, vrt_history_info& out);
     bool Undo(const Scene::VVoxelObject& object, int steps = 1, vrt_brush_result* result = nullptr);
     bool Redo(const Scene::VVoxelObject& object, int steps = 1, vrt_brush_result* result = nullptr);
+    /* Per-voxel materials (vrt_volume_set_palette; the rule: vrt.h) for the volume of a placed object of the scene Render() would draw
+       now (synced first): entry i is the surface of the voxels whose material id is i (what VRT_BRUSH_PAINT writes), ids beyond the
+       palette keep the volume's own VMaterial; of an entry's VMaterial the albedo colour, roughness and metallic count, the textures
+       stay the volume's.  1 .. VRT_MAX_PALETTE entries; ClearPalette takes the palette away.  The palette stays with the slot as its
+       material does, until the volume leaves the scene.  False (after logging) on failure or when the object's volume is not in the
+       scene. */
+    bool SetPalette(const Scene::VVoxelObject& object, const std::vector<VMaterial>& entries);
+    bool ClearPalette(const Scene::VVoxelObject& object);
     /* pull and length_scale of `rec` from the motion one sees — a turn by `rotation` and a uniform scale about `pivot` (grid
        coordinates of the volume, xyz), then a shift by `translation` (cells): the inverse motion, built in double and rounded once;
        length_scale = scale.  The record's other fields stay.  False for a zero quaternion or a scale that is not positive. */

@@ -38,6 +38,10 @@
  *                                           frame (VHipRenderer::EnableHistory, vrt_volume_history); after the last frame the K newest entries are undone
  *                                           in one call (VHipRenderer::Undo, vrt_volume_undo), ahead of --keep-largest and --mesh-out, and the history's
  *                                           state is printed before and after
+ *            [--paint K]                    with --edit-device: the first object's slot gets a palette of K + 1 fixed colours (VHipRenderer::SetPalette,
+ *                                           vrt_volume_set_palette: entry 0 the volume's own material, then K hues), and every dab is followed by a
+ *                                           VRT_BRUSH_PAINT sphere of 1.5 R cells with material id 1 + dab % K: the carved surface comes out coloured.
+ *                                           Under --undo the paint is an entry of its own, so K counts carves and paints alike
  *            [--keep-largest]               after the last frame, ahead of --mesh-out: of the first object's volume only the largest connected piece stays
  *                                           (VHipRenderer::Components, vrt_volume_components, KEEP_LARGEST, gap half a cell, material 0): what a carve cut
  *                                           loose does not reach the mesh
@@ -48,6 +52,7 @@
  *                                           sphere, and a frame whose pick misses it edits nothing
  */
 #include <chrono>
+#include <algorithm>
 #include <cmath>
 #include <cstdio>
 #include <cstdlib>
@@ -125,6 +130,7 @@ int main(int argc, char** argv) {
     std::string scenePath, skyboxDir, outPath = "vrt_demo.ppm", meshOut;
     bool keepLargest = false;
     int undoSteps = 0;
+    int paintK = 0, paintDabs = 0, paintedDabs = 0;
     bool identityDefaults = false;
     int editBrush = 0, sdf = 0;
     bool editFull = false, editDevice = false, editStamp = false, solid = false;
@@ -156,6 +162,7 @@ int main(int argc, char** argv) {
         else if (!strcmp(argv[i], "--mesh-out") && i + 1 < argc) meshOut = argv[++i];
         else if (!strcmp(argv[i], "--keep-largest")) keepLargest = true;
         else if (!strcmp(argv[i], "--undo") && i + 1 < argc) undoSteps = atoi(argv[++i]);
+        else if (!strcmp(argv[i], "--paint") && i + 1 < argc) paintK = atoi(argv[++i]);
         else if (!strcmp(argv[i], "--pick") && i + 2 < argc) {
             pick = true;
             pickX = atoi(argv[++i]);
@@ -248,6 +255,10 @@ int main(int argc, char** argv) {
         fprintf(stderr, "--undo K takes back K device-side edits: it needs --edit-brush with --edit-device or --edit-stamp, and K >= 1\n");
         return 1;
     }
+    if (paintK != 0 && (!hip || !editDevice || editBrush <= 0 || paintK < 1 || paintK > VRT_MAX_PALETTE - 1)) {
+        fprintf(stderr, "--paint K colours what the device-side dabs touch: it needs --edit-brush with --edit-device, and 1 <= K <= %d\n", VRT_MAX_PALETTE - 1);
+        return 1;
+    }
     if (sdf != 0 && (!solid || sdf < 1 || sdf > 15)) {
         fprintf(stderr, "--sdf BAND (1..15) redistances what --solid filled: give both\n");
         return 1;
@@ -296,6 +307,19 @@ int main(int argc, char** argv) {
     /* --undo: the history is on before the first dab; what --solid and --sdf did above is not part of it.  256 entries or 256 MiB */
     if (undoSteps > 0 && (!first || !hip->EnableHistory(*first, 256, (uint64_t)256 << 20))) return 1;
     if (undoSteps > 0) scene->PostRender(); /* the scene is on the device now: no dab is followed by an upload that would empty the history */
+    if (paintK > 0) { /* --paint: entry 0 the volume's own material, then K hues round the colour circle at its roughness */
+        if (!first) return 1;
+        std::vector<VMaterial> palette(1, first->GetVoxelVolume()->GetMaterial());
+        for (int k = 0; k < paintK; k++) {
+            VMaterial m = palette[0];
+            const float h = 6.f * (float)k / (float)paintK, x = 1.f - std::fabs(std::fmod(h, 2.f) - 1.f);
+            const float rgb[6][3] = {{1.f, x, 0.f}, {x, 1.f, 0.f}, {0.f, 1.f, x}, {0.f, x, 1.f}, {x, 0.f, 1.f}, {1.f, 0.f, x}};
+            const float* c = rgb[std::min((int)h, 5)];
+            m.AlbedoColor = VColor(0.15f + 0.8f * c[0], 0.15f + 0.8f * c[1], 0.15f + 0.8f * c[2], 1.f);
+            palette.push_back(m);
+        }
+        if (!hip->SetPalette(*first, palette)) return 1;
+    }
     const std::shared_ptr<Voxel::VVoxelVolume> stampTorus = editStamp ? InitStampTorus() : nullptr;
     int stampTurns = 0;
     unsigned long long stampedVoxels = 0, smoothedVoxels = 0, warpedVoxels = 0;
@@ -339,6 +363,16 @@ int main(int argc, char** argv) {
                 b.reach = 2.f;
                 b.material = 0;
                 done = hip->ApplyBrushes(*sphere1, {b}, &wrote);
+            }
+            if (done && paintK > 0) { /* the dab's surroundings painted: ids only, the field stays */
+                vrt_brush b;
+                memset(&b, 0, sizeof b);
+                b.shape = VRT_BRUSH_SPHERE;
+                b.op = VRT_BRUSH_PAINT;
+                b.a[0] = (float)c.X, b.a[1] = (float)c.Y, b.a[2] = (float)c.Z;
+                b.radius = 1.5f * (float)editBrush;
+                b.material = 1 + paintDabs++ % paintK;
+                if (hip->ApplyBrushes(*first, {b})) paintedDabs++;
             }
             if (done && editSmooth > 0.f) { /* the dab relaxed: a sphere half as large again, two plain iterations */
                 vrt_smooth s;
@@ -439,6 +473,7 @@ int main(int argc, char** argv) {
     }
     const double wall = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
     if (sdf > 0 && editDevice && editBrush > 0) printf("sdf: %llu voxels redistanced around the dabs from %llu surfels\n", dabSamples, dabSurfels);
+    if (paintK > 0) printf("paint: %d of %d dabs painted with ids 1..%d, rendered through a palette of %d entries\n", paintedDabs, paintDabs, paintK, paintK + 1);
     if (editStamp) printf("stamp: %d torus stamps wrote %llu voxels on the device\n", stampTurns, stampedVoxels);
     if (editGrab != 0.f) printf("grab: %g cells pulled %llu voxels around the brush positions on the device\n", editGrab, warpedVoxels);
     if (editSmooth > 0.f) printf("smooth: strength %g relaxed %llu voxels around the dabs on the device\n", editSmooth, smoothedVoxels);

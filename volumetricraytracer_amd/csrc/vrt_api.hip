@@ -27,6 +27,8 @@ int init_device(DeviceState& D, int ordinal) {
     HIP_TRY(hipStreamCreateWithFlags(&D.stream, hipStreamNonBlocking));
     HIP_TRY(hipMalloc(&D.d_vols, sizeof(DVolume) * VRT_MAX_VOLUMES));
     HIP_TRY(hipMemset(D.d_vols, 0, sizeof(DVolume) * VRT_MAX_VOLUMES));
+    HIP_TRY(hipMalloc(&D.d_pal, sizeof(DPalSlot) * VRT_MAX_VOLUMES));
+    HIP_TRY(hipMemset(D.d_pal, 0, sizeof(DPalSlot) * VRT_MAX_VOLUMES));
     HIP_TRY(hipMalloc(&D.d_inst, sizeof(DInstance) * VRT_MAX_INSTANCES));
     HIP_TRY(hipMalloc(&D.d_nodes, sizeof(DBvhNode) * kMaxBvhNodes));
     HIP_TRY(hipMalloc(&D.d_point, sizeof(DPointLight) * VRT_MAX_POINT_LIGHTS));
@@ -41,12 +43,16 @@ int init_device(DeviceState& D, int ordinal) {
 
 void destroy_device(DeviceState& D) {
     if (hipSetDevice(D.ordinal) != hipSuccess) return;
-    for (int i = 0; i < VRT_MAX_VOLUMES; i++) (void)free_device_volume(D, i);
+    for (int i = 0; i < VRT_MAX_VOLUMES; i++) {
+        (void)free_device_volume(D, i);
+        (void)free_device_palette(D, i);
+    }
     for (Buffer& b : D.buf)
         if (b.p) (void)hipFree(b.p);
     if (D.d_box6) (void)hipFree(D.d_box6);
     if (D.d_brush) (void)hipFree(D.d_brush);
     if (D.d_vols) (void)hipFree(D.d_vols);
+    if (D.d_pal) (void)hipFree(D.d_pal);
     if (D.d_inst) (void)hipFree(D.d_inst);
     if (D.d_nodes) (void)hipFree(D.d_nodes);
     if (D.d_point) (void)hipFree(D.d_point);

@@ -29,6 +29,7 @@ struct HostVolume {
     vrt_material mat = {{0.8f, 0.8f, 0.8f, 1.0f}, 0.8f, 0.0f};
     int tex[3] = {-1, -1, -1};            /* albedo, normal, rm texture ids; -1 unbound */
     float tex_scale[2] = {100.f, 100.f};  /* VMaterial::TextureScale default, Material.h:33 */
+    std::vector<vrt_material> palette;    /* vrt_volume_set_palette's entries as given (empty: no palette); follows `mat` */
 };
 
 struct HostTexture {
@@ -88,6 +89,7 @@ struct SceneArrays {
     DBvhNode nodes[kMaxBvhNodes];
     DPointLight point[VRT_MAX_POINT_LIGHTS];
     DSpotLight spot[VRT_MAX_SPOT_LIGHTS];
+    DPalSlot pal[VRT_MAX_VOLUMES]; /* the palette table (DFrame::pal) */
 };
 
 /* One frame in flight (vrt_render_begin / vrt_render_end): stream, completion event, scene snapshot, device frame and
@@ -138,6 +140,8 @@ struct DeviceState {
     DeviceVolume vol[VRT_MAX_VOLUMES];
     DeviceHistory hist[VRT_MAX_VOLUMES];
     DVolume* d_vols = nullptr;
+    DPalSlot* d_pal = nullptr;                       /* the palette table, packed with the volume table (sync_volume_table) */
+    DPalEntry* pal_entries[VRT_MAX_VOLUMES] = {};    /* a slot's VRT_MAX_PALETTE records, from its first palette until vrt_volume_free */
     DInstance* d_inst = nullptr;
     DBvhNode* d_nodes = nullptr;
     DPointLight* d_point = nullptr;
@@ -250,10 +254,16 @@ int ensure_buffer(Buffer& b, size_t bytes);
 /* ---- The volume slots (vrt_slots.hip) ---- */
 /* One slot as the kernels read it (a DVolume of the volume table, or of a frame in flight's snapshot). */
 void fill_dvolume(const vrt_ctx* ctx, const DeviceState& D, const HostVolume& h, const DeviceVolume& d, DVolume& out);
-/* The volume table of every device, from the slots as they are now. */
+/* One slot's row of the palette table. */
+void fill_dpalslot(const DeviceState& D, int slot, const HostVolume& h, DPalSlot& out);
+/* Whether an instance of the scene refers to a slot with a palette. */
+bool palette_in_sight(const vrt_ctx* ctx, const vrt_scene& sc);
+/* The volume table and the palette table of every device, from the slots as they are now. */
 int sync_volume_table(vrt_ctx* ctx);
-/* Frees what one device holds of a slot, the records of its history included. */
+/* Frees what one device holds of a slot, the records of its history included — but not its palette records, which like the slot's
+   material outlive an upload into the slot (free_device_palette: vrt_volume_free, vrt_destroy). */
 int free_device_volume(DeviceState& D, int slot);
+int free_device_palette(DeviceState& D, int slot);
 
 /* ---- What the volume edit calls share (defined in vrt_slots.hip) ---- */
 /* The caller's sample box: origin + size, or (both NULL, where the call allows it) the whole grid, as its first and last sample. */

@@ -47,6 +47,24 @@ inline int grid_blocks(int tiles_x, int tiles_y, int tile_map) {
     return ((st + 7) / 8) * 8 * 16; /* whole supertiles, a multiple of 8 of them */
 }
 
+/* A slot's palette (vrt_volume_set_palette): per entry what DVolume holds of the slot's vrt_material, derived by the same host function
+ * (material_constants, vrt_slots.hip).  32 bytes: two 16-byte loads. */
+struct DPalEntry {
+    float tint[3];
+    float roughness;       /* clamped to [0,1] */
+    float metallic;        /* clamped to [0,1] */
+    float k;               /* (roughness+1)^2 / 8 from the unclamped roughness */
+    float roughness_raw, metallic_raw;
+};
+static_assert(sizeof(DPalEntry) == 32, "a palette record is two 16-byte loads");
+/* One slot's row of the palette table (DFrame::pal), which only the PAL instantiations of march_kernel_full read: n == 0, no palette. */
+struct DPalSlot {
+    const uint8_t* material;   /* the slot's N^3 material ids, in the dense grid's order */
+    const DPalEntry* entries;  /* n records */
+    int32_t n;
+    int32_t pad_;
+};
+
 /* Per-volume record (VGeometryConstantBuffer analogue). */
 struct DVolume {
     const float* dense;    /* N^3 fp32, index x*N*N + z*N + y (VRT_FORMAT_TEXEL16: the integer field +-q as floats) */
@@ -214,6 +232,9 @@ struct DFrame {
     const void* dyn;           /* per-frame scene state (vrt_block::scenes): n_frames sections of kDynStride bytes in device memory, each a
                                   DDyn record followed by the frame's instances, BVH nodes, point and spot lights; null: every frame of the
                                   launch renders the scene in this struct.  Read by the DYN instantiations of the march kernels only */
+    const DPalSlot* pal;       /* the palette table, one row per volume slot, when an instance of the launch's scene(s) refers to a slot with a
+                                  palette; null otherwise.  Last, so that no other field moves: read by the PAL instantiations of
+                                  march_kernel_full only */
 };
 
 /* The header of a march launch's kernarg: a copy of everything a wave that does NOT march reads (four out of five waves of the

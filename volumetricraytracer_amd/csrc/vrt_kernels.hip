@@ -1580,9 +1580,10 @@ __device__ __forceinline__ F3 rotate_vector(F3 v, Q4 r) {
 }
 
 /* Material at a hit in the textured modes (unbound slots are exact identities). */
+/* raw: the surface's unclamped {roughness, metallic} — the slot's own pair (DVolume::roughness_raw), or a palette entry's. */
 template <bool CONST_ONLY = false>
 __device__ __forceinline__ void textured_surface(const DVolume* __restrict__ V, const DInstance* __restrict__ I, F3 hit_world,
-                                                 F3& albedo, F3& n, float& rough, float& metal) {
+                                                 F3& albedo, F3& n, float& rough, float& metal, const float* __restrict__ raw) {
     const F3 op = mul33(I->w2o, f3(hit_world.x - I->pos[0], hit_world.y - I->pos[1], hit_world.z - I->pos[2]));
     const F3 no = mul33(I->w2o, n);
     const F3 an = f3(fabsf(no.x), fabsf(no.y), fabsf(no.z));
@@ -1594,8 +1595,8 @@ __device__ __forceinline__ void textured_surface(const DVolume* __restrict__ V, 
     }
     if (V->tex_px[2] != nullptr) {
         const F3 t = tri_sample<CONST_ONLY>(V, 2, op, blend, false);
-        rough = minf_(maxf_(V->roughness_raw * t.x, 0.0f), 1.0f);
-        metal = minf_(maxf_(V->metallic_raw * t.y, 0.0f), 1.0f);
+        rough = minf_(maxf_(raw[0] * t.x, 0.0f), 1.0f);
+        metal = minf_(maxf_(raw[1] * t.y, 0.0f), 1.0f);
     }
     if (V->tex_px[1] != nullptr) {
         F3 t = tri_sample<CONST_ONLY>(V, 1, op, blend, true);
@@ -1603,6 +1604,13 @@ __device__ __forceinline__ void textured_surface(const DVolume* __restrict__ V, 
         n = mul33(I->o2w, rotate_vector(f3(t.z, t.x, t.y), quat_from_x(no)));
     }
 }
+template <bool CONST_ONLY = false>
+__device__ __forceinline__ void textured_surface(const DVolume* __restrict__ V, const DInstance* __restrict__ I, F3 hit_world,
+                                                 F3& albedo, F3& n, float& rough, float& metal) {
+    textured_surface<CONST_ONLY>(V, I, hit_world, albedo, n, rough, metal, &V->roughness_raw);
+}
+static_assert(offsetof(DVolume, metallic_raw) == offsetof(DVolume, roughness_raw) + sizeof(float) &&
+              offsetof(DPalEntry, metallic_raw) == offsetof(DPalEntry, roughness_raw) + sizeof(float), "textured_surface reads the raw pair as raw[0], raw[1]");
 
 /* The prologue every per-lane primary-ray kernel shares: header, then the camera record (two scalar-load waits, wherever the cameras
  * live), the wave's tile and the lane's pixel, and whether any ray of the wave can reach anything. */
@@ -1812,10 +1820,82 @@ __device__ __forceinline__ F3 direct_light_from_bits(const DFrame& F, F3 so, F3 
     return sum;
 }
 
+/* The surface of a hit on a slot with a palette (vrt_volume_set_palette states the rule): of the hit point's cell, the INSIDE corner
+ * (stored density <= 0; the integer field of a VRT_FORMAT_TEXEL16 slot has its density's sign) nearest to the point, the lowest corner
+ * on a tie — or, with no INSIDE corner, the nearest sample as vrt_hit::voxel names it; that sample's material id picks the entry.  An
+ * id beyond the palette keeps the slot's own material.  Eight dense loads, one byte, two 16-byte loads, everything per lane, behind
+ * the march, and one branch (has the lane's slot a palette?): the rest are selects, so that the kernel's scalar registers — it spills
+ * them already — hold no further exec masks.  The table's address is read from the kernarg segment here, not kept across the marches.
+ * albedo .. raw (the unclamped {roughness, metallic}) come in as the slot's own and go out as the entry's where there is one. */
+template <bool PINNED>
+__device__ __forceinline__ void palette_surface(const DInstance* __restrict__ I, const DVolume* __restrict__ V, F3 o, F3 d, float t,
+                                                F3& albedo, float& rough, float& metal, float& kk, float raw[2]) {
+    typedef float pf4 __attribute__((ext_vector_type(4)));
+    typedef unsigned pu2 __attribute__((ext_vector_type(2)));
+    /* (a load of its own, like camera_again's.  PINNED: the statement may not leave the level loop either — hoisted, the address is
+       one more scalar pair held, and spilled, across every march — and, having a side effect, it ends the scheduling region at the
+       lookup: the kernel then spills fewer scalar registers than its twin without PAL, at more vector registers, which the four-wave
+       floor of march_kernel_full keeps in the twin's tier.  The dense path's kernels do not fit that floor without scratch and keep
+       the plain form; tests/test_palette_kernel_resources.py has the figures) */
+    size_t ka = (size_t)__builtin_amdgcn_kernarg_segment_ptr();
+    if constexpr (PINNED) asm volatile("; palette table" : "+s"(ka));
+    else asm("; palette table" : "+s"(ka));
+    ka += offsetof(DBlock, f) + offsetof(DFrame, pal);
+    const pu2 kw = *(const pu2 __attribute__((address_space(4)))*)ka;
+    const DPalSlot* table = reinterpret_cast<const DPalSlot*>((size_t)kw.x | ((size_t)kw.y << 32));
+    const DPalSlot P = table[I->slot];
+    if (P.n <= 0) return;
+    /* the hit point in object space, as query_kernel computes it for vrt_hit::voxel */
+    const F3 oo = mul33(I->w2o, f3(o.x - I->pos[0], o.y - I->pos[1], o.z - I->pos[2]));
+    const F3 od = mul33(I->w2o, d);
+    const int N = V->N;
+    const float ext = V->extent, ic = V->inv_cell, cmax = (float)(N - 2), nmax = (float)(N - 1);
+    const float gx = (__builtin_fmaf(od.x, t, oo.x) + ext) * ic, gy = (__builtin_fmaf(od.y, t, oo.y) + ext) * ic,
+                gz = (__builtin_fmaf(od.z, t, oo.z) + ext) * ic;
+    /* (the integer clamps keep a NaN point inside the grid too) */
+    const int cx = min(max((int)__builtin_amdgcn_fmed3f(floorf(gx), 0.0f, cmax), 0), N - 2);
+    const int cy = min(max((int)__builtin_amdgcn_fmed3f(floorf(gy), 0.0f, cmax), 0), N - 2);
+    const int cz = min(max((int)__builtin_amdgcn_fmed3f(floorf(gz), 0.0f, cmax), 0), N - 2);
+    const float fx = gx - (float)cx, fy = gy - (float)cy, fz = gz - (float)cz;
+    const unsigned n1 = (unsigned)N, n2 = n1 * n1;
+    const unsigned base = ((unsigned)cx * n1 + (unsigned)cz) * n1 + (unsigned)cy; /* grid order x, z, y; N <= 513: below 2^28 */
+    float s[8];
+#pragma unroll
+    for (int j = 0; j < 8; j++) s[j] = V->dense[base + (unsigned)(j & 1) * n2 + (unsigned)(j >> 2) * n1 + (unsigned)((j >> 1) & 1)];
+    /* (one compare per select: an outside corner is infinitely far, a strict < keeps the lowest corner on a tie) */
+    int best = -1;
+    float best_d2 = __builtin_inff();
+#pragma unroll
+    for (int j = 0; j < 8; j++) {
+        const float ex = fx - (float)(j & 1), ey = fy - (float)((j >> 1) & 1), ez = fz - (float)(j >> 2);
+        const float d2 = s[j] <= 0.0f ? (ex * ex + ey * ey) + ez * ez : __builtin_inff(); /* (NaN <= 0 is false; -0 <= 0 true) */
+        const bool take = d2 < best_d2;
+        best = take ? j : best;
+        best_d2 = take ? d2 : best_d2;
+    }
+    const int nx = min(max((int)__builtin_amdgcn_fmed3f(floorf(gx + 0.5f), 0.0f, nmax), 0), N - 1);
+    const int ny = min(max((int)__builtin_amdgcn_fmed3f(floorf(gy + 0.5f), 0.0f, nmax), 0), N - 1);
+    const int nz = min(max((int)__builtin_amdgcn_fmed3f(floorf(gz + 0.5f), 0.0f, nmax), 0), N - 1);
+    const int vx = best >= 0 ? cx + (best & 1) : nx, vy = best >= 0 ? cy + ((best >> 1) & 1) : ny, vz = best >= 0 ? cz + (best >> 2) : nz;
+    const int id = (int)P.material[((unsigned)vx * n1 + (unsigned)vz) * n1 + (unsigned)vy];
+    const bool in = id < P.n;
+    const pf4* E = reinterpret_cast<const pf4*>(P.entries + (in ? id : 0)); /* (entry 0 exists: read, and not used) */
+    const pf4 e0 = E[0], e1 = E[1];
+    albedo = in ? f3(e0.x, e0.y, e0.z) : albedo;
+    rough = in ? e0.w : rough;
+    metal = in ? e1.x : metal;
+    kk = in ? e1.y : kk;
+    raw[0] = in ? e1.z : raw[0];
+    raw[1] = in ? e1.w : raw[1];
+}
+
 /* SHADE_PASS: third pass of the three-pass form (below): the camera ray's hit comes from the first pass's record, the verdicts of its
- * light shadow rays from the second's bits; everything behind a mirror bounce is traced here as in the one-kernel form. */
-template <int PATH, bool SINGLE, bool SHADE_PASS = false, bool DYN = false>
-__global__ __launch_bounds__(kMarchThreads) __attribute__((amdgpu_waves_per_eu(VRT_FULL_WAVES))) void march_kernel_full(const DBlock B) {
+ * light shadow rays from the second's bits; everything behind a mirror bounce is traced here as in the one-kernel form.
+ * PAL: an instance of the launch refers to a slot with a palette (DFrame::pal): a hit on such a slot takes its surface from the palette
+ * entry of its material id (palette_surface).  One-kernel form only. */
+template <int PATH, bool SINGLE, bool SHADE_PASS = false, bool DYN = false, bool PAL = false>
+__global__ __launch_bounds__(kMarchThreads) __attribute__((amdgpu_waves_per_eu((PAL && PATH != VRT_PATH_DENSE) ? 4 : VRT_FULL_WAVES))) void march_kernel_full(const DBlock B) {
+    static_assert(!PAL || (!SINGLE && !SHADE_PASS), "the palette is looked up in the one-kernel form");
     const int frame = (int)blockIdx.y;
     DFrame Fd;
     const DFrame& F = frame_view<DYN>(B, frame, Fd);
@@ -1873,15 +1953,23 @@ __global__ __launch_bounds__(kMarchThreads) __attribute__((amdgpu_waves_per_eu(V
             const DVolume* V = SINGLE ? F.vol0 : F.vols + F.inst[inst].slot;
             F3 albedo = f3(V->tint[0], V->tint[1], V->tint[2]);
             float rough = V->roughness, metal = V->metallic;
+            /* PAL: the surface's k and raw pair come with it from the palette (or stay the slot's); otherwise read where they always were */
+            float pal_kk = 0.0f, pal_raw[2] = {0.0f, 0.0f};
+            if constexpr (PAL) {
+                pal_kk = V->k;
+                pal_raw[0] = V->roughness_raw;
+                pal_raw[1] = V->metallic_raw;
+                palette_surface<PATH != VRT_PATH_DENSE>(F.inst + inst, V, o, d, t_hit, albedo, rough, metal, pal_kk, pal_raw);
+            }
             if (F.textured) {
                 const F3 hp = f3(__builtin_fmaf(d.x, t_hit, o.x), __builtin_fmaf(d.y, t_hit, o.y), __builtin_fmaf(d.z, t_hit, o.z));
-                textured_surface(V, SINGLE ? F.inst : F.inst + inst, hp, albedo, n, rough, metal);
+                                textured_surface(V, SINGLE ? F.inst : F.inst + inst, hp, albedo, n, rough, metal, PAL ? pal_raw : &V->roughness_raw);
             }
             if (F.unlit) {
                 color = albedo;
                 break;
             }
-            const float kk = V->k;
+            const float kk = PAL ? pal_kk : V->k;
             /* the camera ray is the one ray whose direction the reference leaves un-normalised (VRT_FLAG_REFERENCE_VIEW_VECTOR) */
             const float vs = (level == 1 && F.view_vec) ? camera_len(F, C, px, py) : 1.0f;
             const F3 so = shadow_origin(F, o, d, t_hit, vs);
@@ -2488,6 +2576,7 @@ static hipError_t launch_full_t(const DBlock& B, hipStream_t stream) {
     const DFrame& F = B.f;
     const int grid = grid_blocks(F.tiles_x, F.tiles_y, F.tile_map);
     if (grid <= 0) return hipSuccess;
+    if (F.pal != nullptr && F.hit_rec != nullptr) return hipErrorInvalidValue; /* (the passes have no PAL instantiation) */
     const dim3 g((unsigned)(grid * kMarchGridMul), (unsigned)F.n_frames), t(kMarchThreads);
     if (F.dyn != nullptr) { /* per-frame scene state: the DYN instantiations */
         if (F.hit_rec != nullptr) {
@@ -2496,7 +2585,8 @@ static hipError_t launch_full_t(const DBlock& B, hipStream_t stream) {
             if (F.may_bounce) hipLaunchKernelGGL((march_kernel_full<PATH, false, true, true>), g, t, 0, stream, B);
             return hipGetLastError();
         }
-        hipLaunchKernelGGL((march_kernel_full<PATH, SINGLE, false, true>), g, t, 0, stream, B);
+        if (F.pal != nullptr) hipLaunchKernelGGL((march_kernel_full<PATH, false, false, true, true>), g, t, 0, stream, B);
+        else hipLaunchKernelGGL((march_kernel_full<PATH, SINGLE, false, true>), g, t, 0, stream, B);
         return hipGetLastError();
     }
     if (F.hit_rec != nullptr) { /* three passes, see primary_pass_kernel */
@@ -2505,7 +2595,8 @@ static hipError_t launch_full_t(const DBlock& B, hipStream_t stream) {
         if (F.may_bounce) hipLaunchKernelGGL((march_kernel_full<PATH, false, true>), g, t, 0, stream, B);
         return hipGetLastError();
     }
-    hipLaunchKernelGGL((march_kernel_full<PATH, SINGLE>), g, t, 0, stream, B);
+    if (F.pal != nullptr) hipLaunchKernelGGL((march_kernel_full<PATH, false, false, false, true>), g, t, 0, stream, B);
+    else hipLaunchKernelGGL((march_kernel_full<PATH, SINGLE>), g, t, 0, stream, B);
     return hipGetLastError();
 }
 

@@ -300,6 +300,8 @@ int check_params(const vrt_ctx* ctx, const vrt_params* p, bool own_scenes = fals
         ((p->flags & VRT_FLAG_FULL_ONE_KERNEL) && (p->flags & VRT_FLAG_FULL_THREE_PASS)))
         return VRT_ERR_INVALID;
     if (!ctx->have_scene && !own_scenes) return VRT_ERR_NOT_READY;
+    /* (a block's own scenes: vrt_render_block looks at them, once they are validated) */
+    if (!own_scenes && (p->flags & VRT_FLAG_FULL_THREE_PASS) && palette_in_sight(ctx, ctx->scene)) return VRT_ERR_UNSUPPORTED;
     return VRT_OK;
 }
 
@@ -419,6 +421,7 @@ void cull_rect(const vrt_ctx* ctx, const vrt_params* p, DCam& F, const vrt_scene
 /* Which closest-hit kernel a frame of this scene needs. */
 struct ClosestHitForm {
     bool textured, full, may_bounce;
+    bool palette; /* an instanced slot has a palette: the full closest hit's PAL instantiation, one kernel */
 };
 ClosestHitForm form_of_scene(const vrt_ctx* ctx, const vrt_params* p, const vrt_scene& sc) {
     /* the lean kernel covers directional light + shadow; the full closest hit is only launched when the
@@ -426,27 +429,33 @@ ClosestHitForm form_of_scene(const vrt_ctx* ctx, const vrt_params* p, const vrt_
     /* textured modes read the material textures; a frame needs that code only when a bound texture is in sight */
     const bool tex_mode = p->mode == VRT_MODE_INTERP || p->mode == VRT_MODE_INTERP_UNLIT || p->mode == VRT_MODE_CUBE ||
                           p->mode == VRT_MODE_CUBE_UNLIT;
-    bool smooth = false;
+    bool smooth = false, palette = false;
     bool textured = false, images = false; /* a bound texture in sight; one that is more than a single texel */
     for (int i = 0; i < sc.n_instances; i++) {
         const HostVolume& hv = ctx->vol[sc.instances[i].volume_slot];
-        float rough = hv.mat.roughness;
-        for (int k = 0; tex_mode && k < 3; k++) {
-            if (hv.tex[k] < 0 || !ctx->tex[hv.tex[k]].used) continue;
-            const HostTexture& t = ctx->tex[hv.tex[k]];
-            textured = true;
-            if (t.width != 1 || t.height != 1) images = true;
-            /* a constant RM texel scales the roughness by its red channel — times a tri-planar blend sum that is 1 to a few ulp: the
-               lower bound decides whether the material can mirror */
-            else if (k == 2) rough = hv.mat.roughness * ((float)t.first[0] / 255.0f) * (hv.mat.roughness >= 0.0f ? 0.99999f : 1.00001f);
+        /* the slot's own material, then the entries of its palette: any of them may be what a hit renders with */
+        for (size_t e = 0; e <= hv.palette.size(); e++) {
+            const float raw = e == 0 ? hv.mat.roughness : hv.palette[e - 1].roughness;
+            float rough = raw;
+            for (int k = 0; tex_mode && k < 3; k++) {
+                if (hv.tex[k] < 0 || !ctx->tex[hv.tex[k]].used) continue;
+                const HostTexture& t = ctx->tex[hv.tex[k]];
+                textured = true;
+                if (t.width != 1 || t.height != 1) images = true;
+                /* a constant RM texel scales the roughness by its red channel — times a tri-planar blend sum that is 1 to a few ulp: the
+                   lower bound decides whether the material can mirror */
+                else if (k == 2) rough = raw * ((float)t.first[0] / 255.0f) * (raw >= 0.0f ? 0.99999f : 1.00001f);
+            }
+            smooth = smooth || std::min(std::max(rough, 0.0f), 1.0f) < 0.3f;
         }
-        smooth = smooth || std::min(std::max(rough, 0.0f), 1.0f) < 0.3f;
+        palette = palette || !hv.palette.empty();
     }
     /* A 1x1 texture is a constant (the reference's default normal texel on every material without a normal map, RDXScene.cpp:241-260):
        folded into the lean kernel's REF instantiation — no fetch, no full closest hit.  Only real images need the texture code. */
     ClosestHitForm f;
     f.textured = textured;
-    f.full = sc.n_point_lights > 0 || sc.n_spot_lights > 0 || (p->max_bounces > 0 && smooth) || images;
+    f.palette = palette;
+    f.full = sc.n_point_lights > 0 || sc.n_spot_lights > 0 || (p->max_bounces > 0 && smooth) || images || palette;
     f.may_bounce = p->max_bounces > 0 && (smooth || images); /* (a roughness IMAGE can make any material mirror) */
     return f;
 }
@@ -454,12 +463,13 @@ ClosestHitForm form_of_scene(const vrt_ctx* ctx, const vrt_params* p, const vrt_
    need (the full closest hit renders a frame without extra lights like the lean kernel does: same pixels, same counters). */
 ClosestHitForm closest_hit_form(const vrt_ctx* ctx, const vrt_params* p, const vrt_scene* scenes = nullptr, int n_scenes = 0) {
     if (!scenes) return form_of_scene(ctx, p, ctx->scene);
-    ClosestHitForm u = {false, false, false};
+    ClosestHitForm u = {false, false, false, false};
     for (int f = 0; f < n_scenes; f++) {
         const ClosestHitForm x = form_of_scene(ctx, p, scenes[f]);
         u.textured = u.textured || x.textured;
         u.full = u.full || x.full;
         u.may_bounce = u.may_bounce || x.may_bounce;
+        u.palette = u.palette || x.palette;
     }
     return u;
 }
@@ -521,6 +531,7 @@ void build_frame(const vrt_ctx* ctx, const DeviceState& D, const vrt_params* p, 
     F.out = out;
     F.stats = stats;
     F.vol0 = ctx->scene.n_instances == 1 ? F.vols + ctx->scene.instances[0].volume_slot : nullptr;
+    F.pal = form.palette ? (snapshot ? snapshot->pal : D.d_pal) : nullptr;
 }
 
 /* Enqueue n_frames frames of one tile on one device as ONE launch (grid.y = frame): frame f from cams[f] (null: the scene's own
@@ -643,7 +654,8 @@ int enqueue_rows(vrt_ctx* ctx, DeviceState& D, const vrt_params* p, const RowSet
     }
     /* the full closest hit of a block of frames runs as three passes (vrt_kernels.hip, primary_pass_kernel); a lone frame as one
        kernel: three launches would pay a launch's latency-bound tail three times */
-    const bool passes = F.full && !F.diag && ((n_frames > 1 && !(p->flags & VRT_FLAG_FULL_ONE_KERNEL)) || (p->flags & VRT_FLAG_FULL_THREE_PASS));
+    if (F.pal != nullptr && (p->flags & VRT_FLAG_FULL_THREE_PASS)) return VRT_ERR_UNSUPPORTED; /* (check_params and vrt_render_block refuse it earlier) */
+    const bool passes = F.pal == nullptr && F.full && !F.diag && ((n_frames > 1 && !(p->flags & VRT_FLAG_FULL_ONE_KERNEL)) || (p->flags & VRT_FLAG_FULL_THREE_PASS));
     if (passes) {
         const size_t per_frame = (size_t)D.last_blocks * 256, records = per_frame * (size_t)n_frames;
         if (per_frame > 0xffffffffull) return VRT_ERR_INVALID;
@@ -662,7 +674,7 @@ int enqueue_rows(vrt_ctx* ctx, DeviceState& D, const vrt_params* p, const RowSet
     }
     D.last_diag = F.diag != 0;
     D.last_form = (F.full ? VRT_FORM_FULL : 0) | (passes ? VRT_FORM_PASSES : 0) | (F.textured ? VRT_FORM_TEXTURED : 0) |
-                  (F.may_bounce ? VRT_FORM_MAY_BOUNCE : 0) | ((!F.full && (F.textured || F.view_vec || F.zero_outside)) ? VRT_FORM_LEAN_REF : 0);
+                  (F.may_bounce ? VRT_FORM_MAY_BOUNCE : 0) | (F.pal != nullptr ? VRT_FORM_PALETTE : 0) | ((!F.full && (F.textured || F.view_vec || F.zero_outside)) ? VRT_FORM_LEAN_REF : 0);
     if (F.diag) {
         if (stat_blocks > (size_t)kMaxBlocks) return VRT_ERR_INVALID; /* the timeline buffer holds kMaxBlocks workgroups */
         if (!D.d_diag) HIP_TRY(hipMalloc(&D.d_diag, sizeof(unsigned) * kDiagRecord * 4 * (size_t)kMaxBlocks));
@@ -844,6 +856,8 @@ int vrt_render_block(vrt_ctx* ctx, const vrt_params* params, const vrt_block* bl
             rc = validate_scene(ctx, block->scenes + f);
             if (rc != VRT_OK) return rc;
         }
+        if ((params->flags & VRT_FLAG_FULL_THREE_PASS) && closest_hit_form(ctx, params, block->scenes, block->n_frames).palette)
+            return VRT_ERR_UNSUPPORTED;
     }
     RowSet rs;
     if (block->strip_rows > 0) {
@@ -876,7 +890,8 @@ int vrt_render_block(vrt_ctx* ctx, const vrt_params* params, const vrt_block* bl
     int chunk = (params->flags & VRT_FLAG_BLOCK_PER_FRAME) ? 1 : (capture != hipStreamCaptureStatusNone || block->n_frames <= kMaxBlockFrames) ? kMaxBlockFrames : kMaxLaunchFrames;
     {   /* the full closest hit in passes keeps 20 bytes per pixel of the launch's tiles between its passes: at most kPassBytesMax per launch */
         const size_t per_frame = (size_t)((params->width + 15) / 16) * (size_t)((rs.rows + 15) / 16) * 256 * (sizeof(HitRecord) + sizeof(unsigned));
-        if (per_frame > 0 && closest_hit_form(ctx, params, block->scenes, block->n_frames).full)
+        const ClosestHitForm form = closest_hit_form(ctx, params, block->scenes, block->n_frames);
+        if (per_frame > 0 && form.full && !form.palette) /* (a palette: one kernel, no records) */
             chunk = (int)std::max<size_t>(1, std::min<size_t>((size_t)chunk, kPassBytesMax / per_frame));
     }
     {   /* a launch's grid holds at most 8 * kMaxBlocks workgroups (enqueue_rows), and its per-wave counters — 128 bytes per workgroup and
@@ -1121,7 +1136,10 @@ int vrt_render_begin(vrt_ctx* ctx, const vrt_params* params, int slot) {
     }
     /* snapshot of everything the kernel dereferences besides the volumes themselves: later vrt_scene_set /
        vrt_volume_set_* calls do not reach a frame that is already in flight */
-    for (int i = 0; i < VRT_MAX_VOLUMES; i++) fill_dvolume(ctx, D, ctx->vol[i], D.vol[i], S.h_scene->vols[i]);
+    for (int i = 0; i < VRT_MAX_VOLUMES; i++) {
+        fill_dvolume(ctx, D, ctx->vol[i], D.vol[i], S.h_scene->vols[i]);
+        fill_dpalslot(D, i, ctx->vol[i], S.h_scene->pal[i]);
+    }
     memcpy(S.h_scene->inst, ctx->inst, sizeof S.h_scene->inst);
     memcpy(S.h_scene->nodes, ctx->nodes, sizeof S.h_scene->nodes);
     memcpy(S.h_scene->point, ctx->point, sizeof S.h_scene->point);

@@ -22,6 +22,24 @@ using namespace vrt;
 
 namespace vrt {
 
+/* What the kernels read of a vrt_material: the slot's own (DVolume) and every palette entry (DPalEntry) come from here. */
+struct MaterialConstants {
+    float tint[3], roughness, metallic, k, roughness_raw, metallic_raw;
+};
+static MaterialConstants material_constants(const vrt_material& m) {
+    MaterialConstants c;
+    c.tint[0] = m.tint[0];
+    c.tint[1] = m.tint[1];
+    c.tint[2] = m.tint[2];
+    c.roughness = std::min(std::max(m.roughness, 0.0f), 1.0f);
+    c.metallic = std::min(std::max(m.metallic, 0.0f), 1.0f);
+    float r1 = m.roughness + 1.0f;
+    c.k = (r1 * r1) / 8.0f; /* RDXVoxelVolume.cpp:383 */
+    c.roughness_raw = m.roughness;
+    c.metallic_raw = m.metallic;
+    return c;
+}
+
 void fill_dvolume(const vrt_ctx* ctx, const DeviceState& D, const HostVolume& h, const DeviceVolume& d, DVolume& out) {
     memset(&out, 0, sizeof out);
     if (!h.used) return;
@@ -39,8 +57,9 @@ void fill_dvolume(const vrt_ctx* ctx, const DeviceState& D, const HostVolume& h,
     }
     out.tex_scale[0] = h.tex_scale[0];
     out.tex_scale[1] = h.tex_scale[1];
-    out.roughness_raw = h.mat.roughness;
-    out.metallic_raw = h.mat.metallic;
+    const MaterialConstants mc = material_constants(h.mat);
+    out.roughness_raw = mc.roughness_raw;
+    out.metallic_raw = mc.metallic_raw;
     out.dense = d.dense;
     out.bricks = d.bricks;
     out.cells = d.cells;
@@ -54,13 +73,12 @@ void fill_dvolume(const vrt_ctx* ctx, const DeviceState& D, const HostVolume& h,
     out.density_scale = h.format == VRT_FORMAT_TEXEL16 ? h.density_scale * 0.01f : h.density_scale;
     out.format = h.format;
     out.step_max = h.step_max > 0.0f ? h.step_max : std::numeric_limits<float>::infinity();
-    out.tint[0] = h.mat.tint[0];
-    out.tint[1] = h.mat.tint[1];
-    out.tint[2] = h.mat.tint[2];
-    out.roughness = std::min(std::max(h.mat.roughness, 0.0f), 1.0f);
-    out.metallic = std::min(std::max(h.mat.metallic, 0.0f), 1.0f);
-    float r1 = h.mat.roughness + 1.0f;
-    out.k = (r1 * r1) / 8.0f; /* RDXVoxelVolume.cpp:383 */
+    out.tint[0] = mc.tint[0];
+    out.tint[1] = mc.tint[1];
+    out.tint[2] = mc.tint[2];
+    out.roughness = mc.roughness;
+    out.metallic = mc.metallic;
+    out.k = mc.k;
     out.skip = (h.step_max > 0.0f && d.skip_valid) ? d.skip : nullptr;
     out.nib = out.skip ? d.nib : nullptr;
     for (int a = 0; a < 3; a++) { /* brick box {x, z, y} -> object-space box per axis x, y, z */
@@ -73,13 +91,40 @@ void fill_dvolume(const vrt_ctx* ctx, const DeviceState& D, const HostVolume& h,
     out.cube_skip = d.cube_skip;
 }
 
+void fill_dpalslot(const DeviceState& D, int slot, const HostVolume& h, DPalSlot& out) {
+    memset(&out, 0, sizeof out);
+    if (!h.used || h.palette.empty() || !D.pal_entries[slot] || !D.vol[slot].material) return;
+    out.material = D.vol[slot].material;
+    out.entries = D.pal_entries[slot];
+    out.n = (int32_t)h.palette.size();
+}
+
+bool palette_in_sight(const vrt_ctx* ctx, const vrt_scene& sc) {
+    for (int i = 0; i < sc.n_instances; i++)
+        if (!ctx->vol[sc.instances[i].volume_slot].palette.empty()) return true;
+    return false;
+}
+
 int sync_volume_table(vrt_ctx* ctx) {
     DVolume table[VRT_MAX_VOLUMES];
+    DPalSlot pal[VRT_MAX_VOLUMES];
     for (auto& D : ctx->dev) {
-        for (int i = 0; i < VRT_MAX_VOLUMES; i++) fill_dvolume(ctx, D, ctx->vol[i], D.vol[i], table[i]);
+        for (int i = 0; i < VRT_MAX_VOLUMES; i++) {
+            fill_dvolume(ctx, D, ctx->vol[i], D.vol[i], table[i]);
+            fill_dpalslot(D, i, ctx->vol[i], pal[i]);
+        }
         HIP_TRY(hipSetDevice(D.ordinal));
         HIP_TRY(hipMemcpy(D.d_vols, table, sizeof table, hipMemcpyHostToDevice));
+        HIP_TRY(hipMemcpy(D.d_pal, pal, sizeof pal, hipMemcpyHostToDevice));
     }
+    return VRT_OK;
+}
+
+int free_device_palette(DeviceState& D, int slot) {
+    if (!D.pal_entries[slot]) return VRT_OK;
+    HIP_TRY(hipSetDevice(D.ordinal));
+    HIP_TRY(hipFree(D.pal_entries[slot]));
+    D.pal_entries[slot] = nullptr;
     return VRT_OK;
 }
 
@@ -270,6 +315,7 @@ int upload_volume(vrt_ctx* ctx, int slot, uint8_t resolution, float extent, cons
         h.density_scale = 1.0f;
         h.step_max = 0.0f;
         h.mat = vrt_material{{0.8f, 0.8f, 0.8f, 1.0f}, 0.8f, 0.0f};
+        h.palette.clear();
         h.tex[0] = h.tex[1] = h.tex[2] = -1;
         h.tex_scale[0] = h.tex_scale[1] = 100.f;
     }
@@ -562,6 +608,49 @@ int vrt_volume_set_material(vrt_ctx* ctx, int slot, const vrt_material* material
     return sync_volume_table(ctx);
 }
 
+int vrt_volume_set_palette(vrt_ctx* ctx, int slot, int n, const vrt_material* entries) {
+    if (!ctx || n < 0 || n > VRT_MAX_PALETTE || (n > 0 && !entries)) return VRT_ERR_INVALID;
+    for (int i = 0; i < n; i++) {
+        const vrt_material& m = entries[i];
+        if (!std::isfinite(m.tint[0]) || !std::isfinite(m.tint[1]) || !std::isfinite(m.tint[2]) || !std::isfinite(m.tint[3]) ||
+            !std::isfinite(m.roughness) || !std::isfinite(m.metallic))
+            return VRT_ERR_INVALID;
+    }
+    if (!valid_slot(slot) || !ctx->vol[slot].used) return VRT_ERR_SLOT;
+    HostVolume& h = ctx->vol[slot];
+    if (n == 0 && h.palette.empty()) return VRT_OK;
+    for (auto& D : ctx->dev) { /* frames in flight still read the old records */
+        HIP_TRY(hipSetDevice(D.ordinal));
+        HIP_TRY(hipDeviceSynchronize());
+        if (n > 0 && !D.pal_entries[slot]) HIP_TRY(hipMalloc(&D.pal_entries[slot], sizeof(DPalEntry) * VRT_MAX_PALETTE));
+    }
+    if (n > 0) {
+        DPalEntry rec[VRT_MAX_PALETTE];
+        memset(rec, 0, sizeof rec);
+        for (int i = 0; i < n; i++) {
+            const MaterialConstants mc = material_constants(entries[i]);
+            static_assert(sizeof(MaterialConstants) == sizeof(DPalEntry), "a palette record is the material's constants");
+            memcpy(&rec[i], &mc, sizeof mc);
+        }
+        for (auto& D : ctx->dev) {
+            HIP_TRY(hipSetDevice(D.ordinal));
+            HIP_TRY(hipMemcpy(D.pal_entries[slot], rec, sizeof rec, hipMemcpyHostToDevice));
+        }
+    }
+    h.palette.assign(entries, entries + n);
+    return sync_volume_table(ctx);
+}
+
+int vrt_volume_get_palette(vrt_ctx* ctx, int slot, int capacity, vrt_material* entries, int* n_out) {
+    if (!ctx || !n_out || capacity < 0 || (capacity > 0 && !entries)) return VRT_ERR_INVALID;
+    if (!valid_slot(slot) || !ctx->vol[slot].used) return VRT_ERR_SLOT;
+    const std::vector<vrt_material>& pal = ctx->vol[slot].palette;
+    *n_out = (int)pal.size();
+    if (capacity < (int)pal.size()) return VRT_ERR_INVALID;
+    if (!pal.empty()) memcpy(entries, pal.data(), pal.size() * sizeof(vrt_material));
+    return VRT_OK;
+}
+
 int vrt_volume_set_metric(vrt_ctx* ctx, int slot, float density_scale, float step_max) {
     if (!ctx || !(density_scale > 0.0f)) return VRT_ERR_INVALID;
     if (!valid_slot(slot) || !ctx->vol[slot].used) return VRT_ERR_SLOT;
@@ -612,6 +701,7 @@ int vrt_volume_free(vrt_ctx* ctx, int slot) {
         HIP_TRY(hipSetDevice(D.ordinal));
         HIP_TRY(hipDeviceSynchronize());
         int rc = free_device_volume(D, slot);
+        if (rc == VRT_OK) rc = free_device_palette(D, slot);
         if (rc != VRT_OK) return rc;
     }
     ctx->vol[slot] = HostVolume();

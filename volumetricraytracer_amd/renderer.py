@@ -503,6 +503,32 @@ class VHipRenderer:
                                                      float(vol.Material.TextureScale[1])), "vrt_volume_set_textures")
         self._bound_tex[slot] = tuple(ids)
 
+    def set_palette(self, slot: int, entries) -> None:
+        """vrt_volume_set_palette: per-voxel materials for the slot.  entries: a sequence of (tint4, roughness, metallic), or an (n, 6)
+        array of rows (r, g, b, a, roughness, metallic), n in 1..256; empty or None takes the palette away.  A hit then renders with the
+        entry of the material id of the voxel it lands on (the rule: vrt.h); ids beyond the palette keep the slot's own material."""
+        self._require()
+        rows = []
+        if entries is not None:
+            if isinstance(entries, np.ndarray):
+                rows = [tuple(float(x) for x in r) for r in np.asarray(entries, dtype=np.float32).reshape(-1, 6)]
+            else:
+                rows = [tuple(float(x) for x in tint) + (float(rough), float(metal)) for tint, rough, metal in entries]
+        arr = (_abi.vrt_material * max(len(rows), 1))()
+        for m, r in zip(arr, rows):
+            m.tint[:] = r[:4]
+            m.roughness, m.metallic = r[4], r[5]
+        _abi.check(self._lib.vrt_volume_set_palette(self._ctx, slot, len(rows), arr if rows else None), "vrt_volume_set_palette")
+
+    def get_palette(self, slot: int) -> np.ndarray:
+        """vrt_volume_get_palette: the slot's palette as an (n, 6) float32 array of rows (r, g, b, a, roughness, metallic), bit for bit
+        what set_palette was given; n == 0 without a palette."""
+        self._require()
+        arr = (_abi.vrt_material * _abi.VRT_MAX_PALETTE)()
+        n = C.c_int(0)
+        _abi.check(self._lib.vrt_volume_get_palette(self._ctx, slot, _abi.VRT_MAX_PALETTE, arr, C.byref(n)), "vrt_volume_get_palette")
+        return np.array([list(m.tint) + [m.roughness, m.metallic] for m in arr[:n.value]], dtype=np.float32).reshape(-1, 6)
+
     def voxelize_mesh(self, slot: int, positions: np.ndarray, indices: np.ndarray, resolution: int, extent: float) -> int:
         """The Voxelizer's hot loop on the device (vrt_voxelize_mesh): fills `slot` with the shell field of a
         triangle mesh given in volume space; returns the number of skipped (degenerate) triangles.  The slot is
