@@ -49,6 +49,8 @@
  *                                   Renderer/DX/Resources/Shaders/Raytracing.hlsl:26-455)
  *   vrt_last_timing                 (no reference analogue; FPS counter Engine.cpp:250-262)
  *   vrt_trace_rays*, vrt_camera_rays (no reference analogue: its DXR TraceRay calls live only inside its shaders)
+ *   vrt_query_points*               (no reference analogue: the distance from a point to the scene's nearest surface, its direction, and
+ *                                   the point's projection onto that surface)
  *
  * Error convention: 0 = OK, negative = error.  The reference logs and returns early
  * (DXRenderer.cpp:220-225); the adaptor maps negative codes onto that behaviour.
@@ -1181,6 +1183,81 @@ int vrt_trace_rays_host(vrt_ctx* ctx, const vrt_params* params, int query, int n
  * scene's camera, bit for bit (origin, normalised direction), t_max = 10000 (the kernel's primary t_max).  VRT_ERR_INVALID for a
  * NULL pointer (n > 0), n < 0, a frame size outside 1..16384 or a pixel outside the frame, before anything is written. */
 int vrt_camera_rays(const vrt_scene* scene, int width, int height, int n, const int32_t* pixels_xy, vrt_ray* rays_out);
+
+/* Distance queries (no reference analogue): how far a world-space point is from the nearest surface of the resident scene and in which
+ * direction (iterations == 0), and where the nearest surface point is (iterations > 0: the point is moved onto the surface).  Colliding
+ * particles against a sculpt, resting a brush or a stamp on the surface, snapping a placement to it, sphere-casting (the caller marches
+ * its own spheres with the returned radius).  A ray query cannot stand in: a ray needs a direction, and the normal is what is asked for.
+ *
+ * What the number is worth.  It is exact (up to the trilinear interpolant) on a slot that holds a true signed distance, i.e. after
+ * vrt_volume_redistance, within its band.  On the Voxelizer's shells it is, through density_scale / step_max (vrt_volume_set_metric), a
+ * safe lower bound of the empty radius around the point — what the march itself steps by.  Elsewhere it is whatever the field says.
+ * Outside every box it is the distance to the nearest box, a lower bound: a volume has no surface outside its box.
+ *
+ * The rule is part of the contract.  All arithmetic is fp32, evaluated as parenthesised, no fused multiply-add; sqrtf and / are
+ * correctly rounded.  dot(u,v) = (u.x*v.x + u.y*v.y) + u.z*v.z.
+ * Evaluation E(p) of a world point p: over the scene's instances i, in index order, V being the instance's volume:
+ *   1. Object point.  q = W (p - position), W the world-to-object matrix R^T S^-1 of the instance as the march applies it to a ray's
+ *      origin: W[i][j] = R[j][i] * (1.0f / scale[j]), R the rotation matrix of the quaternion (entries 1 - 2(yy + zz), 2(xy - wz), ...
+ *      from the products xx = x*x, ...), q_a = (W[a][0]*r.x + W[a][1]*r.y) + W[a][2]*r.z with r = p - position.  For rotation
+ *      (0,0,0,1), scale (1,1,1) and position (0,0,0), W is exactly the identity and q == p.
+ *   2. Scale factor.  smin = fminf(fminf(|sx|, |sy|), |sz|) of the instance's scale: the conservative factor from object lengths to
+ *      world lengths.
+ *   3. Box.  e_a = fabsf(q_a) - extent.  The point is IN THE BOX iff e_a <= 0 on all three axes.  Otherwise the instance's value is the
+ *      box bound b = sqrtf(dot(m, m)) * smin with m_a = fmaxf(e_a, 0); a box bound is not SAMPLED.
+ *   4. Sample (in the box).  Per axis g_a = (q_a + extent) * inv_cell (inv_cell = 1.0f / cell, cell = (extent * 2.0f) / (float)(N - 1)),
+ *      c_a = min(max((int)floorf(g_a), 0), N-2), f_a = g_a - (float)c_a.  The eight corner samples s[dx][dy][dz] of cell c, decoded as
+ *      for the brushes: the stored float, or stored * 0.01f on a VRT_FORMAT_TEXEL16 slot.  Every lerp is (s0 * (1.0f - f)) + (s1 * f).
+ *      The value t is the trilinear interpolant on x, then y, then z (vrt_volume_stamp's rule, step 4).  The gradient: G_x lerps the four
+ *      differences s[1][dy][dz] - s[0][dy][dz] on y then z; G_y the four y-differences on x then z; G_z the four z-differences on x then
+ *      y.  A NaN t: the instance contributes nothing.  d = t * density_scale (the caller's, vrt_volume_set_metric, without the 0.01 of
+ *      TEXEL16); when the slot's step_max is finite and > 0, d = fminf(d, step_max) — the march does not trust a sample further than
+ *      that either.  The instance's value is d * smin; it is SAMPLED.
+ *   5. Minimum.  The record takes the smallest value over the contributing instances, the lowest index on a tie (as vrt_hit): the
+ *      first contributing instance, then every later one whose value is < the minimum so far.  `instance` is that index whether or
+ *      not the value is SAMPLED.
+ *   6. The fields of a SAMPLED minimum.  h_a = (W[0][a]*G.x + W[1][a]*G.y) + W[2][a]*G.z (W transposed times G); H = dot(h,h); the
+ *      normal is (0,0,0) when H == 0 or H is not finite, else h_a / sqrtf(H).  voxel and material: what vrt_hit::voxel / material
+ *      define for the object point q, voxel[a] = clamp(floor(g_a + 0.5), 0, N-1).
+ * Query.  iterations == 0: the record is E(p), position = p, moves = 0.  iterations = K > 0: repeat at most K times — evaluate E(p); stop
+ * if the record is not SAMPLED, if its normal is (0,0,0), or if fabsf(distance) <= tolerance; otherwise p_a = p_a - (normal_a * distance)
+ * and moves++.  The record returned is E at the final p (after K moves, one more evaluation): a projection is, by definition, K + 1
+ * plain queries chained on the host.  A point with a non-finite coordinate (the input, or a moved point) is not an error: it gets the
+ * "nothing contributes" record — distance +inf, instance -1, flags 0, the position echoed. */
+#define VRT_MAX_PROJECT_ITERATIONS 16
+#define VRT_POINT_SAMPLED 1   /* vrt_point_result::flags bit 0 */
+
+typedef struct vrt_point {            /* 16 B */
+    float position[3];                /* world space */
+    float reserved_;                  /* 0 */
+} vrt_point;
+
+typedef struct vrt_point_result {     /* 64 B */
+    float distance;       /* world units, see the rule; +inf when nothing contributes */
+    float normal[3];      /* world-space unit vector, inside -> outside; 0 unless SAMPLED */
+    int32_t instance;     /* the instance the minimum came from; -1 when nothing contributes */
+    int32_t voxel[3];     /* nearest grid sample, exactly as vrt_hit::voxel; -1 unless SAMPLED */
+    uint32_t material;    /* that sample's id; 0 unless SAMPLED */
+    uint32_t flags;       /* VRT_POINT_SAMPLED: the minimum is a sample of an instance's field, not a box bound */
+    uint32_t moves;       /* projection moves made (0 for a plain query) */
+    float position[3];    /* where the record was evaluated: the input, or the projected point */
+    uint32_t reserved_[2];
+} vrt_point_result;
+
+/* n points from device memory into n records in device memory, asynchronous on hip_stream, on the first device of the context.
+ * Argument errors are checked before anything is enqueued: VRT_ERR_INVALID for a NULL context, a NULL buffer with n > 0, n < 0,
+ * iterations outside 0 .. VRT_MAX_PROJECT_ITERATIONS, or a tolerance that is negative or not finite; VRT_ERR_NOT_READY without a scene;
+ * n == 0 is OK and launches nothing.  Allocates nothing, so it can be captured into a hipGraph (the grids' and the scene arrays'
+ * addresses are baked in: a region edit or a brush dab shows in a replay, a full re-upload or a new scene does not).  Like
+ * vrt_trace_rays, a vrt_scene_set that was deferred while frames were in flight is applied ahead of the query; on a capturing stream
+ * that is VRT_ERR_NOT_READY.  Queries leave the render's bookkeeping alone: vrt_last_timing, the timing and launch histories, the
+ * kernel form and the per-wave records read the same before and after any number of them.  The kernel reads the slots' dense grids and
+ * material ids only, so every data path and both formats answer alike. */
+int vrt_query_points(vrt_ctx* ctx, int iterations, float tolerance, int n, const vrt_point* device_points,
+                     vrt_point_result* device_results, void* hip_stream);
+/* The same from and into host arrays, synchronous: staged through a context-owned device buffer (vrt_trace_rays_host's), reallocated
+ * only when a larger batch arrives. */
+int vrt_query_points_host(vrt_ctx* ctx, int iterations, float tolerance, int n, const vrt_point* points, vrt_point_result* results);
 
 int vrt_last_timing(vrt_ctx* ctx, vrt_timing* out);
 /* Kernel durations (ms) of the last n vrt_render_rows/vrt_render launches, oldest first;

@@ -219,6 +219,28 @@ class vrt_hit(C.Structure):
     ]
 
 
+MAX_PROJECT_ITERATIONS = 16
+POINT_SAMPLED = 1  # vrt_point_result.flags bit 0
+
+
+class vrt_point(C.Structure):
+    _fields_ = [("position", C.c_float * 3), ("reserved_", C.c_float)]
+
+
+class vrt_point_result(C.Structure):
+    _fields_ = [
+        ("distance", C.c_float),
+        ("normal", C.c_float * 3),
+        ("instance", C.c_int32),
+        ("voxel", C.c_int32 * 3),
+        ("material", C.c_uint32),
+        ("flags", C.c_uint32),
+        ("moves", C.c_uint32),
+        ("position", C.c_float * 3),
+        ("reserved_", C.c_uint32 * 2),
+    ]
+
+
 class vrt_brush(C.Structure):
     _fields_ = [
         ("shape", C.c_int32),
@@ -408,6 +430,8 @@ SYMBOLS = {
     "vrt_trace_rays": (C.c_int, [C.c_void_p, C.POINTER(vrt_params), C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]),
     "vrt_trace_rays_host": (C.c_int, [C.c_void_p, C.POINTER(vrt_params), C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
     "vrt_camera_rays": (C.c_int, [C.POINTER(vrt_scene), C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
+    "vrt_query_points": (C.c_int, [C.c_void_p, C.c_int, C.c_float, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "vrt_query_points_host": (C.c_int, [C.c_void_p, C.c_int, C.c_float, C.c_int, C.c_void_p, C.c_void_p]),
     "vrt_last_timing": (C.c_int, [C.c_void_p, C.POINTER(vrt_timing)]),
     "vrt_timing_history": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(C.c_float)]),
     "vrt_launch_history": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(C.c_float), C.POINTER(C.c_int)]),

@@ -758,6 +758,22 @@ bool VHipRenderer::TraceRays(const std::vector<vrt_ray>& rays, std::vector<vrt_h
               "vrt_trace_rays_host");
 }
 
+bool VHipRenderer::QueryPoints(const std::vector<VVector>& points, int iterations, float tolerance, std::vector<vrt_point_result>& results) {
+    if (!IsActive()) {
+        V_LOG_WARNING("QueryPoints() on an inactive renderer");
+        return false;
+    }
+    const VObjectPtr<Scene::VScene> scene = SceneRef.lock();
+    if (!scene || points.size() > (size_t)INT32_MAX) return false;
+    if (!SyncWithScene(*scene)) return false;
+    vrt_scene s;
+    if (!FillSceneStruct(*scene, s, &QueryObjects)) return false;
+    std::vector<vrt_point> in(points.size());
+    for (size_t i = 0; i < points.size(); i++) in[i] = vrt_point{{points[i].X, points[i].Y, points[i].Z}, 0.f};
+    results.resize(points.size());
+    return ok(vrt_query_points_host(Ctx, iterations, tolerance, (int)in.size(), in.data(), results.data()), "vrt_query_points_host");
+}
+
 int VHipRenderer::SlotOf(const Voxel::VVoxelVolume* volume) const {
     int slot = -1;
     for (size_t i = 0; i < Uploaded.size(); i++)

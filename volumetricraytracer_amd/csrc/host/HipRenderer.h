@@ -106,6 +106,11 @@ public:
        in, one vrt_hit per ray out.  anyHit: occlusion within each ray's t_max (instance 0 when blocked, -1 when clear).  False
        (after logging) on failure. */
     bool TraceRays(const std::vector<vrt_ray>& rays, std::vector<vrt_hit>& hits, bool anyHit = false);
+    /* Distance queries on the GPU (vrt_query_points_host) against the scene Render() would draw now (synced first): world-space points
+       in, one vrt_point_result per point out — the distance to the nearest surface and its direction; with iterations > 0 the points
+       are first moved onto that surface (at most that many moves, stopping within `tolerance` world units of it).  HitObject-style
+       lookup: the records' instance indexes the same objects as a hit's.  False (after logging) on failure. */
+    bool QueryPoints(const std::vector<VVector>& points, int iterations, float tolerance, std::vector<vrt_point_result>& results);
     /* The closest hit under pixel (px, py) of the current output size: the camera ray the march kernel casts for it
        (vrt_camera_rays), traced as TraceRays does.  False when the pixel lies outside the frame or the query fails; a miss is
        true with out.instance = -1. */

@@ -50,6 +50,9 @@
  *            [--pick X Y]                   every frame asks what lies under pixel (X, Y) (VHipRenderer::Pick: a GPU ray query) and prints the
  *                                           hit record; with --edit-brush the brush is centred on the picked voxel when the pick hits the red
  *                                           sphere, and a frame whose pick misses it edits nothing
+ *            [--probe X Y Z]                every frame asks how far the world point (X, Y, Z) is from the nearest surface (VHipRenderer::QueryPoints: a
+ *                                           GPU distance query) and prints the record, ahead of the frame's edit; with --edit-brush --edit-device the
+ *                                           distance moves as the dabs carve towards the point or away from it
  */
 #include <chrono>
 #include <algorithm>
@@ -137,6 +140,8 @@ int main(int argc, char** argv) {
     float editSmooth = 0.f, editGrab = 0.f;
     bool pick = false;
     int pickX = 0, pickY = 0;
+    bool probe = false;
+    VVector probeAt;
     int mode = 0, inFlight = 3, block = 0; /* three frames in flight: the reference's swap chain (FrameCount, DXConstants.cpp:23) */
     std::string format = "bgra8", volumes = "texel16";
     for (int i = 1; i < argc; i++) {
@@ -167,6 +172,11 @@ int main(int argc, char** argv) {
             pick = true;
             pickX = atoi(argv[++i]);
             pickY = atoi(argv[++i]);
+        } else if (!strcmp(argv[i], "--probe") && i + 3 < argc) {
+            probe = true;
+            probeAt.X = (float)atof(argv[++i]);
+            probeAt.Y = (float)atof(argv[++i]);
+            probeAt.Z = (float)atof(argv[++i]);
         }
     }
 
@@ -237,6 +247,10 @@ int main(int argc, char** argv) {
     if (editDevice && !hip) editDevice = false;
     if (pick && (!hip || block > 0)) {
         fprintf(stderr, "--pick asks the HIP renderer once per frame: drop --block\n");
+        return 1;
+    }
+    if (probe && (!hip || block > 0)) {
+        fprintf(stderr, "--probe asks the HIP renderer once per frame: drop --block\n");
         return 1;
     }
     if (solid && !hip) {
@@ -426,6 +440,17 @@ int main(int argc, char** argv) {
         sphere1->Position = VQuat::FromAxisAngle(VVector::UP, angle) * rel1;
         sphere2->Position = VQuat::FromAxisAngle(VVector::RIGHT, angle) * rel2;
         scene->Touch();
+        if (probe) { /* how far the world point is from the nearest surface now, before this frame's edit */
+            std::vector<vrt_point_result> rec;
+            if (!hip->QueryPoints({probeAt}, 0, 0.f, rec) || rec.size() != 1) {
+                if (!warmUp) printf("frame %d probe (%g, %g, %g): failed\n", f, probeAt.X, probeAt.Y, probeAt.Z);
+            } else if (!warmUp) {
+                const vrt_point_result& r = rec[0];
+                printf("frame %d probe (%g, %g, %g): instance %d distance %.4f normal (%.4f, %.4f, %.4f) voxel (%d, %d, %d) material %u sampled %u\n", f,
+                       probeAt.X, probeAt.Y, probeAt.Z, r.instance, r.distance, r.normal[0], r.normal[1], r.normal[2], r.voxel[0], r.voxel[1], r.voxel[2],
+                       r.material, r.flags & VRT_POINT_SAMPLED);
+            }
+        }
         if (pick) { /* what lies under the pixel now, before this frame's edit */
             vrt_hit h;
             if (!hip->Pick(pickX, pickY, h)) {

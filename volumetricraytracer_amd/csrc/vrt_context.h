@@ -128,7 +128,8 @@ enum BufferId {
     kBufMeshOut,       /* ... and the staged mesh */
     kBufSmoothWarp,    /* vrt_volume_smooth: two fp32 copies of the work box and its weights; vrt_volume_warp: the value to store and the
                           new id of every sample of the region's box (one buffer for the two calls) */
-    kBufQuery,         /* vrt_trace_rays_host: the rays and then the hit records of a batch */
+    kBufQuery,         /* vrt_trace_rays_host: the rays and then the hit records of a batch; vrt_query_points_host: the points and then
+                          their records (both calls are synchronous, so one buffer serves the two) */
     kBufHistory,       /* an edit call on a slot whose history is on: the tile counters, then the stored bits (4 B) and the id (1 B) of
                           every sample of the call's footprint as they were before it */
     kBufCount
@@ -250,6 +251,12 @@ inline bool valid_slot(int slot) { return slot >= 0 && slot < VRT_MAX_VOLUMES; }
 
 /* Grows a per-device cache buffer to at least `bytes` (its contents are not kept). */
 int ensure_buffer(Buffer& b, size_t bytes);
+
+/* ---- The scene (vrt_render.hip) ---- */
+/* For a query launch on the first device that takes no vrt_params (vrt_query_points): applies a scene set that was deferred while frames
+   were in flight (VRT_ERR_NOT_READY on a capturing stream), then fills F's scene and volume records as a ray query's are filled.
+   Touches none of the render's bookkeeping and allocates nothing. */
+int query_scene(vrt_ctx* ctx, hipStream_t stream, DFrame& F);
 
 /* ---- The volume slots (vrt_slots.hip) ---- */
 /* One slot as the kernels read it (a DVolume of the volume table, or of a frame in flight's snapshot). */

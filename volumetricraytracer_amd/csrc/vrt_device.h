@@ -117,8 +117,10 @@ struct DInstance {
     float sh_od[3];
     float sh_inv[3];
     float sh_inv_len;
-    float pad_;
+    float smin;            /* fminf(fminf(|sx|, |sy|), |sz|) of the instance's scale: the conservative factor from object lengths to world
+                              lengths (vrt_query_points; the march kernels do not read it).  It took the struct's padding word: nothing moved */
 };
+static_assert(sizeof(DInstance) == 120 && offsetof(DInstance, smin) == 116, "smin sits in what was the padding word");
 
 /* Flat AABB BVH over instance world boxes, nodes in preorder, threaded.  Leaf: left = -(instance+1); inner: left = the node's
  * own index + 1.  right = the node that follows this node's whole subtree in preorder (n_nodes behind the last): where the

@@ -102,7 +102,21 @@ void pack_instance(const vrt_instance& in, DInstance& out) {
     out.pos[1] = in.position[1];
     out.pos[2] = in.position[2];
     out.slot = in.volume_slot;
-    out.pad_ = 0.f;
+    out.smin = fminf(fminf(fabsf(in.scale[0]), fabsf(in.scale[1])), fabsf(in.scale[2]));
+}
+
+/* vrt_query_points' rule, step 1, rests on this: an unrotated, unscaled instance packs to exactly the identity (1 - 2 * 0 and 2 * (0 +- 0)
+   are exact), so that its object point is the world point.  Checked once per process, at the first scene that is packed. */
+bool identity_packs_exactly() {
+    vrt_instance in;
+    memset(&in, 0, sizeof in);
+    in.rotation[3] = 1.0f;
+    in.scale[0] = in.scale[1] = in.scale[2] = 1.0f;
+    DInstance out;
+    pack_instance(in, out);
+    for (int i = 0; i < 9; i++)
+        if (out.w2o[i] != (i % 4 == 0 ? 1.0f : 0.0f)) return false;
+    return out.smin == 1.0f;
 }
 
 /* Constants of the directional light's shadow ray in an instance's object space — the very expressions of the
@@ -258,6 +272,8 @@ int upload_scene_arrays(vrt_ctx* ctx) {
 }
 
 int pack_scene(vrt_ctx* ctx) {
+    static const bool identity_ok = identity_packs_exactly();
+    if (!identity_ok) return VRT_ERR_UNSUPPORTED; /* (a build whose host arithmetic is not IEEE fp32 as written) */
     pack_scene_arrays(ctx, ctx->scene, ctx->inst, ctx->nodes, ctx->n_nodes, ctx->point, ctx->spot);
     ctx->arrays_uploaded = false;
     /* While frames are in flight (vrt_render_begin: each carries its own snapshot of these arrays, copied on its own stream) the
@@ -725,6 +741,28 @@ int enqueue_query(vrt_ctx* ctx, const vrt_params* p, int query, int n, const voi
 }
 
 }  // namespace
+
+namespace vrt {
+
+/* The resident scene as a query launch on the first device reads it (vrt_context.h): enqueue_query's steps for a call without
+   vrt_params.  Of F only the scene and volume records mean anything. */
+int query_scene(vrt_ctx* ctx, hipStream_t stream, DFrame& F) {
+    DeviceState& D = ctx->dev[0];
+    HIP_TRY(hipSetDevice(D.ordinal));
+    if (!ctx->arrays_uploaded) { /* deferred by pack_scene (frames were in flight): now, as enqueue_rows does */
+        hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
+        if (stream != nullptr && hipStreamIsCapturing(stream, &cs) == hipSuccess && cs != hipStreamCaptureStatusNone) return VRT_ERR_NOT_READY;
+        const int rc = upload_scene_arrays(ctx);
+        if (rc != VRT_OK) return rc;
+    }
+    vrt_params p;
+    memset(&p, 0, sizeof p);
+    p.width = p.height = 1;
+    build_frame(ctx, D, &p, RowSet{}, nullptr, nullptr, F);
+    return VRT_OK;
+}
+
+}  // namespace vrt
 
 extern "C" {
 

@@ -21,6 +21,25 @@ RAY_DTYPE = np.dtype([("origin", "<f4", 3), ("t_max", "<f4"), ("direction", "<f4
 HIT_DTYPE = np.dtype([("t", "<f4"), ("normal", "<f4", 3), ("instance", "<i4"), ("voxel", "<i4", 3), ("material", "<u4"),
                       ("steps", "<u4"), ("reserved_", "<u4", 2)])
 assert RAY_DTYPE.itemsize == C.sizeof(_abi.vrt_ray) and HIT_DTYPE.itemsize == C.sizeof(_abi.vrt_hit)
+POINT_DTYPE = np.dtype([("position", "<f4", 3), ("reserved_", "<f4")])
+POINT_RESULT_DTYPE = np.dtype([("distance", "<f4"), ("normal", "<f4", 3), ("instance", "<i4"), ("voxel", "<i4", 3), ("material", "<u4"),
+                               ("flags", "<u4"), ("moves", "<u4"), ("position", "<f4", 3), ("reserved_", "<u4", 2)])
+assert POINT_DTYPE.itemsize == C.sizeof(_abi.vrt_point) and POINT_RESULT_DTYPE.itemsize == C.sizeof(_abi.vrt_point_result)
+
+
+def make_points(points) -> np.ndarray:
+    """A vrt_point array from [n, 3] world-space positions."""
+    p = np.asarray(points, dtype=np.float32).reshape(-1, 3)
+    out = np.zeros(len(p), POINT_DTYPE)
+    out["position"] = p
+    return out
+
+
+def point_results_to_dict(res: np.ndarray) -> dict:
+    """The fields of a vrt_point_result array as separate numpy arrays; sampled = flags & VRT_POINT_SAMPLED."""
+    return {"distance": res["distance"].copy(), "normal": res["normal"].copy(), "instance": res["instance"].copy(),
+            "voxel": res["voxel"].copy(), "material": res["material"].copy(), "sampled": (res["flags"] & _abi.POINT_SAMPLED) != 0,
+            "moves": res["moves"].copy(), "position": res["position"].copy()}
 
 
 def make_rays(origins, directions, t_max=10000.0) -> np.ndarray:
@@ -725,6 +744,31 @@ class VHipRenderer:
         r = self.camera_rays([(px, py)])
         out = self.trace_rays(r["origin"], r["direction"], r["t_max"], params=params)
         return {k: (v[0] if v.ndim == 1 else v[0].copy()) for k, v in out.items()}
+
+    # -- distance queries (vrt_query_points*) -------------------------------------------------------------------------------------------
+    def query_points(self, points, iterations: int = 0, tolerance: float = 0.0) -> dict:
+        """How far world-space points are from the nearest surface of the synced scene, and in which direction, on the GPU
+        (vrt_query_points_host): a dict of numpy arrays distance, normal, instance, voxel, material, sampled, moves, position.
+        iterations > 0 moves every point onto the surface first (project_points).  Syncs the scene first."""
+        self._require()
+        self.SyncWithScene()
+        pts = make_points(points)
+        res = np.zeros(len(pts), POINT_RESULT_DTYPE)
+        _abi.check(self._lib.vrt_query_points_host(self._ctx, int(iterations), float(tolerance), len(pts), pts.ctypes.data_as(C.c_void_p),
+                                                   res.ctypes.data_as(C.c_void_p)), "vrt_query_points_host")
+        return point_results_to_dict(res)
+
+    def query_points_device(self, iterations: int, tolerance: float, n: int, points_ptr: int, results_ptr: int, stream: int = 0) -> None:
+        """Asynchronous query of n vrt_point records in device memory into n vrt_point_result records (vrt_query_points);
+        allocates nothing, so it can be captured into a graph.  Does not sync the scene."""
+        self._require()
+        _abi.check(self._lib.vrt_query_points(self._ctx, int(iterations), float(tolerance), int(n), C.c_void_p(points_ptr),
+                                              C.c_void_p(results_ptr), C.c_void_p(stream)), "vrt_query_points")
+
+    def project_points(self, points, iterations: int = 8, tolerance: float = 1e-4) -> dict:
+        """The points moved onto the nearest surface: up to `iterations` moves of p - normal * distance, stopping within `tolerance`
+        (world units) of it; the records of the moved points, `position` being where they ended."""
+        return self.query_points(points, iterations=iterations, tolerance=tolerance)
 
     # -- multi-GPU exchange, one process per GPU (vrt_comm_* / vrt_gather_tiles: RCCL ncclGather) --------------------
     @staticmethod
