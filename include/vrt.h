@@ -39,7 +39,9 @@
  *                                   signed distance to its own zero surface — what ADD brushes, blends and offsets assume)
  *   vrt_volume_extract_mesh         (no reference analogue: its Voxelizer goes one way, glTF -> .vox; the resident volume's surface
  *                                   back out as an indexed triangle mesh, by surface nets)
- *   vrt_volume_free                 VRDXScene::RemoveVoxelVolume  Renderer/DX/Private/RDXScene.cpp:663-701
+ *   vrt_volume_measure,             (no reference analogue: the resident volume's solid volume, surface area, centre of mass, inertia,
+ *   vrt_measure_properties          tight bounds and amount of every material id, as integer sums computed on the device)
+ *   vrt_volume_free                VRDXScene::RemoveVoxelVolume  Renderer/DX/Private/RDXScene.cpp:663-701
  *   vrt_env_upload                  VRDXScene::InitEnvironmentMap RDXScene.cpp:181-199
  *   vrt_scene_set                   VRDXScene::SyncWithScene + PrepareForRendering
  *                                   RDXScene.cpp:109-118, 150-174, 454-545, 703-755
@@ -899,6 +901,85 @@ int vrt_volume_extract_mesh(vrt_ctx* ctx, int slot, float iso,
                             size_t vertex_capacity,
                             uint32_t* indices_or_null, size_t index_capacity,
                             vrt_mesh_result* result_or_null);
+
+/* How much of a resident volume there is and where its mass sits (no reference analogue): solid volume, surface area, centre of mass,
+ * inertia, tight bounds and the amount of every material id of the level set d <= iso over a box of samples — a printer's material
+ * estimate, a rigid body's mass properties, a tool's framing box — without a download of N^3 x 8 B. */
+#define VRT_MEASURE_SUBSAMPLES 4      /* per axis and cell: 64 sub-samples per cell */
+
+typedef struct vrt_measure_result {   /* 176 B; integers only: the same on every device and on the host, bit for bit */
+    int32_t  lo[3], hi[3];            /* xyz, inclusive: the CELLS with at least one INSIDE sub-sample; lo > hi when none */
+    uint64_t subsamples;              /* S0: INSIDE sub-samples */
+    uint64_t moment1[3];              /* S1: sum of X_a over them */
+    uint64_t moment2[6];              /* S2: sums of X_x X_x, X_y X_y, X_z X_z, X_x X_y, X_x X_z, X_y X_z */
+    uint64_t solid_samples;           /* INSIDE grid samples of the sample box */
+    uint64_t active_cells;            /* == vrt_mesh_result::vertices for the same iso and box */
+    uint64_t crossings[3];            /* grid edges along x, y, z with both ends in the sample box whose ends differ in class */
+    uint64_t quads;                   /* == vrt_mesh_result::quads for the same iso and box */
+    uint64_t area_q;                  /* sum over those quads of their area in 2^-16 cell^2, rule 6 */
+    uint64_t reserved_[2];            /* 0 */
+} vrt_measure_result;
+
+/* Synchronous, and otherwise as vrt_volume_extract_mesh: waits for work already enqueued on the context's devices, reads the dense grid
+ * and the material grid of device 0, writes nothing to the slot — every vrt_debug_volume_bytes buffer reads the same before and after —,
+ * is not recorded in the slot's edit history and does not touch its stacks.  Both box pointers NULL: the whole grid; otherwise the
+ * samples [origin, origin + size) as vrt_volume_update_region takes them.  material_samples_or_null: 256 counts, the INSIDE samples of
+ * the sample box per material id.
+ * Errors, all checked before anything is written: VRT_ERR_INVALID for a NULL context or result, a non-finite iso, one box pointer NULL
+ * and the other not, or a box that vrt_volume_update_region would refuse; VRT_ERR_SLOT for an unused slot; VRT_ERR_OOM when the
+ * accumulators (one small buffer the context keeps) cannot be allocated.  A box one sample thick on some axis has no cells: its cell
+ * sums are 0 with lo > hi; solid_samples, crossings and the material counts still count.
+ *
+ * The rule is part of the contract.  All floating-point arithmetic is fp32, evaluated as parenthesised, no fused multiply-add; sqrtf
+ * is correctly rounded; dot(u,v) = (u.x*v.x + u.y*v.y) + u.z*v.z, len(u) = sqrtf(dot(u,u)).  Everything that is summed is an integer,
+ * so the result does not depend on how the device schedules its work.
+ *   1. Decode and class: vrt_volume_extract_mesh's rule 1.  d is the stored float, or stored * 0.01f (VRT_FORMAT_TEXEL16);
+ *      f = -0.0f when d is NaN, else fminf(fmaxf(d - iso, -1e18f), 1e18f).  A sample is OUTSIDE when f > 0, else INSIDE; at iso 0 that
+ *      is vrt_volume_components' SOLID.
+ *   2. Cells: the mesh rule's step 2 — the cell box, the corner numbering j = dx + 2*dy + 4*dz; a cell is active when its corners are not
+ *      all of one class.
+ *   3. Sub-samples.  A cell with all corners INSIDE has 64 INSIDE sub-samples, a cell with all corners OUTSIDE none (this is the rule,
+ *      not a shortcut: it also settles what an underflowing product would).  An active cell is sampled at the 4^3 points with the
+ *      fractions u_i = 0.125f + 0.25f * (float)i, i = 0..3, per axis (all exact).  There t is the trilinear interpolant of the eight
+ *      f: along x, then y, then z, every lerp (s0 * (1.0f - u)) + (s1 * u) — vrt_volume_stamp's step 4.  The sub-sample is INSIDE
+ *      when !(t > 0).
+ *   4. Integer position.  Sub-sample (i_x, i_y, i_z) of cell c sits at X_a = 8*c_a + 2*i_a + 1, in units of cell / 8 from sample 0.
+ *      subsamples, moment1 and moment2 are the exact integer sums over the INSIDE sub-samples of the cell box; lo / hi bound the cells
+ *      that have one.  Nothing overflows: at N = 513 X <= 8*511 + 7 < 4096 = 2^12 and there are 512^3 * 64 = 2^33 sub-samples, so
+ *      S0 <= 2^33, S1 < 2^45 and S2 < 2^57 (1.5e17) < 2^64.
+ *   5. Sample counts, over the sample box: solid_samples, the INSIDE samples; material_samples[id], those of them with that material
+ *      id (they sum to solid_samples); crossings[a], the grid edges from a sample to the next one on axis a, both in the box, whose
+ *      ends differ in class.
+ *   6. Area.  The quads of vrt_volume_extract_mesh's rule 4 for the same iso and box, with the vertices of its rule 3 in grid
+ *      coordinates, p_a = (float)c_a + (s_a / (float)k), in that rule's order v0..v3.  With cross(u, w) = (u.y*w.z - u.z*w.y,
+ *      u.z*w.x - u.x*w.z, u.x*w.y - u.y*w.x): A = 0.5f * len(cross(v1 - v0, v2 - v0)) + 0.5f * len(cross(v2 - v0, v3 - v0)).  The
+ *      quad adds (uint64_t)floorf(A * 65536.0f + 0.5f) to area_q; A < 2^8, so the product is exact before the rounding.
+ *   7. vrt_measure_properties, in double: cell = (double)((extent * 2.0f) / (float)(N - 1)), h = cell / 8, the unit of X, and
+ *      s = 2 * h = cell / 4, the side of the cube a sub-sample stands for.  volume = S0 * s^3;
+ *      area = (area_q / 65536) * cell^2; centroid_a = (S1_a / S0) * h - extent.  Central second moments C_ab =
+ *      (S2_ab - S1_a * S1_b / S0) * h^2 * s^3, plus S0 * s^5 / 12 on the diagonal (each sub-cube's own); inertia = tr(C) * 1 - C:
+ *      inertia_xx = C_yy + C_zz, inertia_xy = -C_xy, and so on — for unit density, so mass = volume.  box_lo_a = lo_a * cell - extent,
+ *      box_hi_a = (hi_a + 1) * cell - extent.  With S0 == 0 everything but the box is 0, and the box is empty (lo > hi).
+ * What the rule is worth: on a sphere of 10.4 cells (33^3, centre off the grid) the volume is 0.9954 of the analytic one, the area
+ * 0.9943, the centroid lies 0.00082 cells from the centre and the inertia's diagonal is within 0.0075 of 8/15 pi r^5 (below it);
+ * DESIGN.md section 4 has the figures.  Both surfaces are chord surfaces, which lie inside a convex body: the zero set of the
+ * trilinear interpolant for the volume, and for the area the surface nets mesh, whose vertices lie up to 0.035 cells inside. */
+int vrt_volume_measure(vrt_ctx* ctx, int slot, float iso,
+                       const int origin_xyz_or_null[3], const int size_xyz_or_null[3],
+                       vrt_measure_result* result,
+                       uint64_t* material_samples_or_null /* 256: INSIDE samples of the sample box per material id */);
+
+typedef struct vrt_mass_properties {  /* 136 B; doubles, object space of the volume (the frame of vrt_hit::voxel), unit density */
+    double volume, area;
+    double centroid[3];
+    double inertia[6];                /* about the centroid: xx, yy, zz, xy, xz, yz */
+    double box_lo[3], box_hi[3];
+} vrt_mass_properties;
+
+/* Host only — no context, no GPU (as vrt_camera_rays): rule 7 on a result of vrt_volume_measure for a volume of that resolution and
+ * extent.  VRT_ERR_INVALID for a NULL pointer or a resolution above VRT_MAX_RESOLUTION. */
+int vrt_measure_properties(const vrt_measure_result* m, uint8_t resolution, float extent, vrt_mass_properties* out);
+
 /* Reads the box [origin, origin+size) of device 0's slot as VVoxel records: box order as vrt_volume_update_voxels takes it, decode
  * as vrt_volume_download's.  Only the box's bytes cross the bus, so a host mirror can follow a device-side edit without a full
  * download.  Argument checks as vrt_volume_update_region's.  On a VRT_FORMAT_TEXEL16 slot the decoded values (q * 0.01f) re-quantise

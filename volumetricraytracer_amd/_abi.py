@@ -363,6 +363,49 @@ class vrt_mesh_result(C.Structure):
     _fields_ = [("lo", C.c_int32 * 3), ("hi", C.c_int32 * 3), ("vertices", C.c_uint64), ("quads", C.c_uint64)]
 
 
+class vrt_measure_result(C.Structure):
+    _fields_ = [("lo", C.c_int32 * 3), ("hi", C.c_int32 * 3), ("subsamples", C.c_uint64), ("moment1", C.c_uint64 * 3),
+                ("moment2", C.c_uint64 * 6), ("solid_samples", C.c_uint64), ("active_cells", C.c_uint64), ("crossings", C.c_uint64 * 3),
+                ("quads", C.c_uint64), ("area_q", C.c_uint64), ("reserved_", C.c_uint64 * 2)]
+
+
+class vrt_mass_properties(C.Structure):
+    _fields_ = [("volume", C.c_double), ("area", C.c_double), ("centroid", C.c_double * 3), ("inertia", C.c_double * 6),
+                ("box_lo", C.c_double * 3), ("box_hi", C.c_double * 3)]
+
+
+MEASURE_SUBSAMPLES = 4
+
+
+def measure_dict(res: "vrt_measure_result", counts=None) -> dict:
+    """A vrt_measure_result (and the 256 material counts) as plain Python ints."""
+    out = {"lo": tuple(res.lo), "hi": tuple(res.hi), "subsamples": int(res.subsamples), "moment1": tuple(int(x) for x in res.moment1),
+           "moment2": tuple(int(x) for x in res.moment2), "solid_samples": int(res.solid_samples), "active_cells": int(res.active_cells),
+           "crossings": tuple(int(x) for x in res.crossings), "quads": int(res.quads), "area_q": int(res.area_q)}
+    if counts is not None:
+        out["material_samples"] = tuple(int(x) for x in counts)
+    return out
+
+
+def measure_record(m: dict) -> "vrt_measure_result":
+    """The way back from measure_dict."""
+    res = vrt_measure_result()
+    res.lo[:], res.hi[:] = m["lo"], m["hi"]
+    res.moment1[:], res.moment2[:], res.crossings[:] = m["moment1"], m["moment2"], m["crossings"]
+    for name in ("subsamples", "solid_samples", "active_cells", "quads", "area_q"):
+        setattr(res, name, m[name])
+    return res
+
+
+def mass_properties(m: dict, resolution: int, extent: float) -> dict:
+    """vrt_measure_properties (host only) on a measure_dict: {"volume", "area", "centroid", "inertia", "box_lo", "box_hi"} as floats, in
+    the volume's object space, for unit density."""
+    out = vrt_mass_properties()
+    check(load().vrt_measure_properties(C.byref(measure_record(m)), int(resolution), float(extent), C.byref(out)), "vrt_measure_properties")
+    return {"volume": out.volume, "area": out.area, "centroid": tuple(out.centroid), "inertia": tuple(out.inertia),
+            "box_lo": tuple(out.box_lo), "box_hi": tuple(out.box_hi)}
+
+
 class vrt_history_info(C.Structure):
     _fields_ = [("enabled", C.c_int32), ("max_entries", C.c_int32), ("max_bytes", C.c_uint64), ("undo_entries", C.c_uint32),
                 ("redo_entries", C.c_uint32), ("bytes", C.c_uint64), ("dropped", C.c_uint64), ("top_tiles", C.c_uint64),
@@ -406,6 +449,9 @@ SYMBOLS = {
                                         C.POINTER(vrt_redistance_result)]),
     "vrt_volume_extract_mesh": (C.c_int, [C.c_void_p, C.c_int, C.c_float, C.POINTER(C.c_int), C.POINTER(C.c_int), C.c_void_p, C.c_void_p,
                                           C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.POINTER(vrt_mesh_result)]),
+    "vrt_volume_measure": (C.c_int, [C.c_void_p, C.c_int, C.c_float, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(vrt_measure_result),
+                                     C.POINTER(C.c_uint64)]),
+    "vrt_measure_properties": (C.c_int, [C.POINTER(vrt_measure_result), C.c_uint8, C.c_float, C.POINTER(vrt_mass_properties)]),
     "vrt_volume_download_region": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int), C.c_void_p]),
     "vrt_volume_history": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_uint64]),
     "vrt_volume_history_info": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(vrt_history_info)]),

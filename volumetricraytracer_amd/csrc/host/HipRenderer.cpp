@@ -1101,6 +1101,29 @@ bool VHipRenderer::ExtractMesh(const Scene::VVoxelObject& object, Voxelizer::VVo
               "vrt_volume_extract_mesh");
 }
 
+bool VHipRenderer::MeasureVolume(const Scene::VVoxelObject& object, vrt_mass_properties& out, float iso, const VIntVector* boxLo, const VIntVector* boxHi,
+                                 vrt_measure_result* result, uint64_t* materialSamples) {
+    if (!IsActive()) {
+        V_LOG_WARNING("MeasureVolume() on an inactive renderer");
+        return false;
+    }
+    const VObjectPtr<Voxel::VVoxelVolume> volume = object.GetVoxelVolume();
+    if (!volume || (boxLo == nullptr) != (boxHi == nullptr)) return false;
+    const int slot = SyncedSlotOf(object, "MeasureVolume()");
+    if (slot < 0) return false;
+    int lo[3], size[3];
+    if (boxLo) {
+        const int last = (int)volume->GetSize() - 1;
+        lo[0] = std::max(boxLo->X, 0), lo[1] = std::max(boxLo->Y, 0), lo[2] = std::max(boxLo->Z, 0);
+        size[0] = std::min(boxHi->X, last) - lo[0] + 1, size[1] = std::min(boxHi->Y, last) - lo[1] + 1, size[2] = std::min(boxHi->Z, last) - lo[2] + 1;
+        if (size[0] < 1 || size[1] < 1 || size[2] < 1) return false;
+    }
+    vrt_measure_result res;
+    if (!ok(vrt_volume_measure(Ctx, slot, iso, boxLo ? lo : nullptr, boxLo ? size : nullptr, &res, materialSamples), "vrt_volume_measure")) return false;
+    if (result) *result = res;
+    return ok(vrt_measure_properties(&res, volume->GetResolution(), volume->GetVolumeExtends(), &out), "vrt_measure_properties");
+}
+
 bool VHipRenderer::Pick(int px, int py, vrt_hit& out) {
     const VObjectPtr<Scene::VScene> scene = SceneRef.lock();
     if (!IsActive() || !scene || px < 0 || py < 0 || (unsigned)px >= Width || (unsigned)py >= Height) return false;

@@ -202,6 +202,13 @@ public:
        logging) on failure or when the object's volume is not in the scene. */
     bool ExtractMesh(const Scene::VVoxelObject& object, Voxelizer::VVolumeConverter::VSurfaceMesh& out, float iso = 0.f,
                      const VIntVector* boxLo = nullptr, const VIntVector* boxHi = nullptr);
+    /* How much of the volume of a placed object lies at density <= iso as it is on the device now, and where (vrt_volume_measure:
+       integer sums on the device; the rule: vrt.h), over the samples boxLo..boxHi (inclusive xyz indices, clamped to the grid) or the
+       whole grid without a box: volume, area, centroid, inertia and bounds in the volume's object space for unit density
+       (vrt_measure_properties), and on request the record of sums itself and the INSIDE samples per material id (256 counts).  The
+       scene is synced first; the volume is only read.  False (after logging) on failure or when the object's volume is not in the scene. */
+    bool MeasureVolume(const Scene::VVoxelObject& object, vrt_mass_properties& out, float iso = 0.f, const VIntVector* boxLo = nullptr,
+                       const VIntVector* boxHi = nullptr, vrt_measure_result* result = nullptr, uint64_t* materialSamples = nullptr);
 
 private:
     bool SyncWithScene(Scene::VScene& scene);

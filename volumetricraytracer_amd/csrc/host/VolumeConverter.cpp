@@ -4,6 +4,7 @@
 #include "../components_core.h"
 #include "../fill_core.h"
 #include "../grid_core.h"
+#include "../measure_core.h"
 #include "../mesh_core.h"
 #include "../redistance_core.h"
 #include "../smooth_core.h"
@@ -377,6 +378,77 @@ VVolumeConverter::VSurfaceMesh VVolumeConverter::ExtractMesh(const Voxel::VVoxel
     const int lo[3] = {boxLo ? boxLo->X : 0, boxLo ? boxLo->Y : 0, boxLo ? boxLo->Z : 0};
     const int hi[3] = {boxHi ? boxHi->X : last, boxHi ? boxHi->Y : last, boxHi ? boxHi->Z : last};
     return ExtractMesh(volume.GetVoxels().data(), volume.GetSize(), volume.GetVolumeExtends(), false, iso, lo, hi);
+}
+
+void VVolumeConverter::Measure(const Voxel::VVoxel* voxels, size_t n, bool texel16, float iso, const int lo[3], const int hi[3],
+                               ::vrt_measure_result& out, uint64_t* materialSamplesOrNull) {
+    namespace M = vrt_mesh;
+    namespace R = vrt_measure;
+    const int N = (int)n;
+    const auto at = [&](int x, int y, int z) { return vrt_grid::index(N, x, y, z); };
+    const auto value = [&](int x, int y, int z) { return M::field(vrt_grid::decode(voxels[at(x, y, z)].Density, texel16), iso); };
+    const auto corners = [&](const int c[3], float f[8]) {
+        for (int j = 0; j < 8; j++) f[j] = value(c[0] + (j & 1), c[1] + ((j >> 1) & 1), c[2] + (j >> 2));
+    };
+    out = ::vrt_measure_result{};
+    for (int a = 0; a < 3; a++) out.lo[a] = N, out.hi[a] = -1;
+    if (materialSamplesOrNull) std::fill(materialSamplesOrNull, materialSamplesOrNull + 256, (uint64_t)0);
+    /* the samples of the box */
+    for (int x = lo[0]; x <= hi[0]; x++)
+        for (int z = lo[2]; z <= hi[2]; z++)
+            for (int y = lo[1]; y <= hi[1]; y++) {
+                const int s[3] = {x, y, z};
+                const bool is_out = M::outside(value(x, y, z));
+                if (!is_out) {
+                    out.solid_samples++;
+                    if (materialSamplesOrNull) materialSamplesOrNull[voxels[at(x, y, z)].Material]++;
+                }
+                for (int a = 0; a < 3; a++) {
+                    if (s[a] + 1 > hi[a]) continue;
+                    if (M::outside(value(x + (a == 0), y + (a == 1), z + (a == 2))) != is_out) out.crossings[a]++;
+                }
+            }
+    /* the cells of the cell box */
+    R::Sums sums;
+    R::clear(sums);
+    for (int x = lo[0]; x < hi[0]; x++)
+        for (int z = lo[2]; z < hi[2]; z++)
+            for (int y = lo[1]; y < hi[1]; y++) {
+                const int c[3] = {x, y, z};
+                float f[8];
+                corners(c, f);
+                if (R::add_cell(sums, c, f) != 0u)
+                    for (int a = 0; a < 3; a++) out.lo[a] = std::min(out.lo[a], c[a]), out.hi[a] = std::max(out.hi[a], c[a]);
+                const unsigned classes = M::corner_classes(f);
+                if (!M::active(classes)) continue;
+                out.active_cells++;
+                const unsigned quads = M::owned_quads(classes, c, lo);
+                for (int a = 0; a < 3; a++) {
+                    if (!((quads >> a) & 1u)) continue;
+                    int q_cells[4][3];
+                    M::quad_cells(a, c, q_cells);
+                    float q[4][3];
+                    for (int i = 0; i < 4; i++) {
+                        float g[8];
+                        corners(q_cells[i], g);
+                        const M::Vertex v = M::cell_vertex(q_cells[i], g);
+                        for (int b = 0; b < 3; b++) q[i][b] = v.p[b];
+                    }
+                    out.quads++;
+                    out.area_q += R::quad_area_q(q, (classes & 1u) != 0u);
+                }
+            }
+    out.subsamples = sums.s0;
+    for (int a = 0; a < 3; a++) out.moment1[a] = sums.s1[a];
+    for (int a = 0; a < 6; a++) out.moment2[a] = sums.s2[a];
+}
+
+void VVolumeConverter::Measure(const Voxel::VVoxelVolume& volume, ::vrt_measure_result& out, uint64_t* materialSamplesOrNull, float iso,
+                               const VIntVector* boxLo, const VIntVector* boxHi) {
+    const int last = (int)volume.GetSize() - 1;
+    const int lo[3] = {boxLo ? boxLo->X : 0, boxLo ? boxLo->Y : 0, boxLo ? boxLo->Z : 0};
+    const int hi[3] = {boxHi ? boxHi->X : last, boxHi ? boxHi->Y : last, boxHi ? boxHi->Z : last};
+    Measure(volume.GetVoxels().data(), volume.GetSize(), false, iso, lo, hi, out, materialSamplesOrNull);
 }
 
 VVolumeConverter::VStampResult VVolumeConverter::Stamp(Voxel::VVoxel* dst, size_t nd, float unitDst, bool dstTexel16, const Voxel::VVoxel* src,

@@ -23,6 +23,7 @@ struct vrt_warp;
 struct vrt_components;
 struct vrt_component;
 struct vrt_components_result;
+struct vrt_measure_result;
 
 namespace VolumeRaytracer {
 namespace Voxelizer {
@@ -89,6 +90,16 @@ public:
     /* The same on n^3 VVoxel records (index x*n*n + z*n + y) over the samples lo..hi (xyz, inclusive, inside the grid); extent: the
        volume's half size; texel16: the records hold the integer field +-q of a VRT_FORMAT_TEXEL16 slot. */
     static VSurfaceMesh ExtractMesh(const Voxel::VVoxel* voxels, size_t n, float extent, bool texel16, float iso, const int lo[3], const int hi[3]);
+    /* How much of a volume there is and where it sits, over a box of samples (the whole grid without one) — the rule of
+       vrt_volume_measure (include/vrt.h; its arithmetic is csrc/measure_core.h, shared with the HIP kernel), as plain loops: the
+       record of integer sums that call fills, and the INSIDE samples per material id in materialSamplesOrNull[256].  The volume is only
+       read.  vrt_measure_properties turns the record into volume, area, centroid and inertia. */
+    static void Measure(const Voxel::VVoxelVolume& volume, ::vrt_measure_result& out, uint64_t* materialSamplesOrNull = nullptr, float iso = 0.f,
+                        const VIntVector* boxLo = nullptr, const VIntVector* boxHi = nullptr);
+    /* The same on n^3 VVoxel records (index x*n*n + z*n + y) over the samples lo..hi (xyz, inclusive, inside the grid); texel16: the
+       records hold the integer field +-q of a VRT_FORMAT_TEXEL16 slot. */
+    static void Measure(const Voxel::VVoxel* voxels, size_t n, bool texel16, float iso, const int lo[3], const int hi[3],
+                        ::vrt_measure_result& out, uint64_t* materialSamplesOrNull);
     /* What Stamp wrote: the samples' count and their inclusive xyz box (Lo > Hi when none). */
     struct VStampResult {
         VIntVector Lo, Hi;

@@ -45,6 +45,9 @@
  *            [--keep-largest]               after the last frame, ahead of --mesh-out: of the first object's volume only the largest connected piece stays
  *                                           (VHipRenderer::Components, vrt_volume_components, KEEP_LARGEST, gap half a cell, material 0): what a carve cut
  *                                           loose does not reach the mesh
+ *            [--measure]                    after the last frame and after --keep-largest: one line with the volume, area and centroid of the first object's
+ *                                           volume as it is on the device now, in its object space (VHipRenderer::MeasureVolume, vrt_volume_measure and
+ *                                           vrt_measure_properties), and, when --paint gave it a palette, the volume of every material id that occurs
  *            [--mesh-out FILE]              after the last frame the first object's volume, as sculpted on the device, leaves as triangles: surface nets on the
  *                                           device (VHipRenderer::ExtractMesh, vrt_volume_extract_mesh) written as glTF (.gltf + .bin, or .glb); `voxelizer` reads it back
  *            [--pick X Y]                   every frame asks what lies under pixel (X, Y) (VHipRenderer::Pick: a GPU ray query) and prints the
@@ -132,6 +135,7 @@ int main(int argc, char** argv) {
     unsigned W = 1024, H = 576;
     std::string scenePath, skyboxDir, outPath = "vrt_demo.ppm", meshOut;
     bool keepLargest = false;
+    bool measure = false;
     int undoSteps = 0;
     int paintK = 0, paintDabs = 0, paintedDabs = 0;
     bool identityDefaults = false;
@@ -166,6 +170,7 @@ int main(int argc, char** argv) {
         else if (!strcmp(argv[i], "--sdf") && i + 1 < argc) sdf = atoi(argv[++i]);
         else if (!strcmp(argv[i], "--mesh-out") && i + 1 < argc) meshOut = argv[++i];
         else if (!strcmp(argv[i], "--keep-largest")) keepLargest = true;
+        else if (!strcmp(argv[i], "--measure")) measure = true;
         else if (!strcmp(argv[i], "--undo") && i + 1 < argc) undoSteps = atoi(argv[++i]);
         else if (!strcmp(argv[i], "--paint") && i + 1 < argc) paintK = atoi(argv[++i]);
         else if (!strcmp(argv[i], "--pick") && i + 2 < argc) {
@@ -259,6 +264,10 @@ int main(int argc, char** argv) {
     }
     if (!meshOut.empty() && !hip) {
         fprintf(stderr, "--mesh-out extracts on the device: it needs the HIP renderer\n");
+        return 1;
+    }
+    if (measure && !hip) {
+        fprintf(stderr, "--measure sums on the device: it needs the HIP renderer\n");
         return 1;
     }
     if (keepLargest && !hip) {
@@ -546,6 +555,18 @@ int main(int argc, char** argv) {
         if (!hip->Components(*first, rec, nullptr, 0, &res)) return 1;
         printf("components: %u pieces of %llu solid voxels, %u removed (%llu voxels, %llu written)\n", res.components,
                (unsigned long long)res.solid, res.removed, (unsigned long long)res.removed_samples, (unsigned long long)res.written);
+    }
+    if (measure) { /* how much of the first object's volume there is now, and of which id */
+        vrt_mass_properties p;
+        std::vector<uint64_t> ids(256, 0);
+        if (!first || !hip->MeasureVolume(*first, p, 0.f, nullptr, nullptr, nullptr, ids.data())) return 1;
+        printf("measure: volume %.6g area %.6g centroid (%.6g, %.6g, %.6g)", p.volume, p.area, p.centroid[0], p.centroid[1], p.centroid[2]);
+        if (paintK > 0) { /* per id, as samples times the cell's volume */
+            const double cell = (double)first->GetVoxelVolume()->GetCellSize(), cell3 = cell * cell * cell;
+            for (int id = 0; id < 256; id++)
+                if (ids[id] != 0) printf(" id %d: %.6g", id, (double)ids[id] * cell3);
+        }
+        printf("\n");
     }
     if (!meshOut.empty()) { /* the first object's volume as it is on the device now */
         Voxelizer::VGLTFExporter::VEntry e;

@@ -159,6 +159,26 @@ int vrh_extract_mesh(const vrt_voxel* voxels, int n, float extent, int texel16, 
     return 0;
 }
 
+/* VVolumeConverter::Measure on caller records: n^3 VVoxel records (index x*n*n + z*n + y), only read; texel16 != 0: the densities are the
+   integer field +-q; the box, the result and the 256 material counts as vrt_volume_measure takes them.  0 / -1, nothing written. */
+int vrh_measure(const vrt_voxel* voxels, int n, int texel16, float iso, const int* origin_xyz_or_null, const int* size_xyz_or_null,
+                vrt_measure_result* result, uint64_t* material_samples_or_null) {
+    bool good = voxels && result && n >= 2 && std::isfinite(iso) && (origin_xyz_or_null == nullptr) == (size_xyz_or_null == nullptr);
+    int lo[3] = {0, 0, 0}, hi[3] = {n - 1, n - 1, n - 1};
+    for (int a = 0; good && origin_xyz_or_null && a < 3; a++) {
+        good = size_xyz_or_null[a] >= 1 && origin_xyz_or_null[a] >= 0 && (long long)origin_xyz_or_null[a] + size_xyz_or_null[a] <= n;
+        lo[a] = origin_xyz_or_null[a];
+        hi[a] = origin_xyz_or_null[a] + size_xyz_or_null[a] - 1;
+    }
+    if (!good) {
+        g_error = "vrh_measure: bad argument";
+        return -1;
+    }
+    Voxelizer::VVolumeConverter::Measure(reinterpret_cast<const Voxel::VVoxel*>(voxels), (size_t)n, texel16 != 0, iso, lo, hi, *result,
+                                         material_samples_or_null);
+    return 0;
+}
+
 /* VVolumeConverter::Stamp on caller records: nd^3 destination records edited in place and ns^3 source records only read (index
    x*n*n + z*n + y); extent and density_scale of each grid give its density units per cell as vrt_volume_stamp derives them; texel16 != 0:
    that grid's densities are the integer field +-q; result_or_null as vrt_volume_stamp reports.  The record passes the argument rules of

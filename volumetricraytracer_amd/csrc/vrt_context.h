@@ -132,6 +132,7 @@ enum BufferId {
                           their records (both calls are synchronous, so one buffer serves the two) */
     kBufHistory,       /* an edit call on a slot whose history is on: the tile counters, then the stored bits (4 B) and the id (1 B) of
                           every sample of the call's footprint as they were before it */
+    kBufMeasure,       /* vrt_volume_measure: the accumulators (2.2 KB, allocated by the first call) */
     kBufCount
 };
 

@@ -500,6 +500,23 @@ class VHipRenderer:
                        "vrt_volume_extract_mesh")
         return positions, normals, materials, indices, {"vertices": V, "quads": Q, "lo": tuple(res.lo), "hi": tuple(res.hi)}
 
+    def measure(self, slot: int, iso: float = 0.0, lo=None, hi=None) -> dict:
+        """vrt_volume_measure: how much of the volume resident in `slot` lies at density <= iso, and where, over the samples lo..hi
+        (inclusive xyz corners; both None: the whole grid), summed on the device.  The slot is only read.  Returns _abi.measure_dict's
+        dict: the record's integer fields ("lo", "hi", "subsamples", "moment1", "moment2", "solid_samples", "active_cells",
+        "crossings", "quads", "area_q") and "material_samples" (256 counts); _abi.mass_properties turns it into volume, area,
+        centroid and inertia."""
+        self._require()
+        if (lo is None) != (hi is None):
+            raise ValueError("measure: give both corners of the box or neither")
+        origin = size = None
+        if lo is not None:
+            origin = (C.c_int * 3)(*[int(a) for a in lo])
+            size = (C.c_int * 3)(*[int(b) - int(a) + 1 for a, b in zip(lo, hi)])
+        res, counts = _abi.vrt_measure_result(), (C.c_uint64 * 256)()
+        _abi.check(self._lib.vrt_volume_measure(self._ctx, slot, float(iso), origin, size, C.byref(res), counts), "vrt_volume_measure")
+        return _abi.measure_dict(res, counts)
+
     def download_region(self, slot: int, lo, hi):
         """vrt_volume_download_region: the voxels lo..hi (inclusive xyz corners) of the slot on device 0 as (density float32,
         material uint8), both indexed [x, z, y] like VVoxelVolume.density; a TEXEL16 slot decodes like download_volume."""

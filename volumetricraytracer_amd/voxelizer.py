@@ -57,6 +57,9 @@ def load_host() -> C.CDLL:
         lib.vrh_extract_mesh.restype = C.c_int
         lib.vrh_extract_mesh.argtypes = [C.c_void_p, C.c_int, C.c_float, C.c_int, C.c_float, C.POINTER(C.c_int), C.POINTER(C.c_int), C.c_void_p,
                                          C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.POINTER(_abi.vrt_mesh_result)]
+        lib.vrh_measure.restype = C.c_int
+        lib.vrh_measure.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_float, C.POINTER(C.c_int), C.POINTER(C.c_int),
+                                    C.POINTER(_abi.vrt_measure_result), C.POINTER(C.c_uint64)]
         lib.vrh_gltf_mesh.restype = C.c_int
         lib.vrh_gltf_mesh.argtypes = [C.c_char_p, C.c_int, C.POINTER(C.c_size_t), C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_char_p, C.c_size_t]
         lib.vrh_vox_rewrite.restype = C.c_int
@@ -247,6 +250,27 @@ def extract_mesh_host(vol: VVoxelVolume, iso: float = 0.0, lo=None, hi=None, tex
                                   C.byref(res)) != 0:
         raise RuntimeError("vrh_extract_mesh: " + lib.vrh_last_error().decode(errors="replace"))
     return positions, normals, materials, indices, {"vertices": V, "quads": Q, "lo": tuple(res.lo), "hi": tuple(res.hi)}
+
+
+def measure_host(vol: VVoxelVolume, iso: float = 0.0, lo=None, hi=None, texel16: bool = False) -> dict:
+    """VVolumeConverter::Measure (the host build of vrt_volume_measure's rule) on a volume's densities and material ids, over the samples
+    lo..hi (inclusive xyz corners; both None: the whole grid).  texel16: the densities are the integer field +-q of a TEXEL16 slot.  The
+    volume is only read.  Returns _abi.measure_dict's dict: the record's integer fields and "material_samples" (256 counts);
+    _abi.mass_properties turns it into volume, area, centroid and inertia."""
+    lib = load_host()
+    if (lo is None) != (hi is None):
+        raise ValueError("measure_host: give both corners of the box or neither")
+    rec = np.zeros(vol.N ** 3, dtype=np.dtype([("material", "u1"), ("pad", "u1", 3), ("density", "<f4")]))
+    rec["density"] = np.asarray(vol.density, np.float32).reshape(-1)
+    rec["material"] = np.asarray(vol.material_id, np.uint8).reshape(-1)
+    origin = size = None
+    if lo is not None:
+        origin = (C.c_int * 3)(*[int(a) for a in lo])
+        size = (C.c_int * 3)(*[int(b) - int(a) + 1 for a, b in zip(lo, hi)])
+    res, counts = _abi.vrt_measure_result(), (C.c_uint64 * 256)()
+    if lib.vrh_measure(rec.ctypes.data, vol.N, int(bool(texel16)), float(iso), origin, size, C.byref(res), counts) != 0:
+        raise RuntimeError("vrh_measure: " + lib.vrh_last_error().decode(errors="replace"))
+    return _abi.measure_dict(res, counts)
 
 
 def import_gltf_mesh(path: str, mesh: int = 0):
