@@ -1378,8 +1378,9 @@ def test_render_rows_can_be_captured_into_a_graph(renderer, oracle_lib):
     assert np.abs(out.cpu().numpy() - ref).max() <= TOL
     t = renderer.last_timing()
     assert t["kernel_ms"] == 0.0 and t["primary_steps"] == st["primary_steps"] and t["hits"] == st["hits"]
-    # larger launches on the capture stream and on five other streams (more streams than counter slots): every counter
-    # slot is grown or recycled; the graph must still replay into memory that is alive
+    # larger launches on the capture stream and on five other streams: the capture stream's counter buffer is outgrown and
+    # retired; the graph must still replay into memory that is alive (more streams than there are records, 16, and the
+    # take-over of a record: tests/test_launch_streams_gpu.py)
     big = v.default_params(640, 360, scenes.min_cell(sc), 255, shadow=True)
     bigbuf = torch.zeros((360, 640, 4), dtype=torch.float32, device="cuda:0")
     for stream in [side] + [torch.cuda.Stream() for _ in range(5)]:

@@ -66,27 +66,24 @@ void destroy_device(DeviceState& D) {
         if (S.done) (void)hipEventDestroy(S.done);
         if (S.d_scene) (void)hipFree(S.d_scene);
         if (S.h_scene) (void)hipHostFree(S.h_scene);
-        if (S.d_fb) (void)hipFree(S.d_fb);
-        if (S.h_fb) (void)hipHostFree(S.h_fb);
+        if (S.d_fb.p) (void)hipFree(S.d_fb.p);
+        if (S.h_fb.p) (void)hipHostFree(S.h_fb.p);
     }
-    if (D.fb) (void)hipFree(D.fb);
-    for (int i = 0; i < kStatSlots; i++)
-        if (D.d_stats[i]) (void)hipFree(D.d_stats[i]);
-    for (unsigned* r : D.stats_retired) (void)hipFree(r);
-    for (int i = 0; i < kStatSlots; i++) {
-        if (D.d_cams[i]) (void)hipFree(D.d_cams[i]);
-        if (D.h_cams[i]) (void)hipHostFree(D.h_cams[i]);
-        if (D.d_dyn[i]) (void)hipFree(D.d_dyn[i]);
-        if (i == 0 && D.d_blockfb) (void)hipFree(D.d_blockfb);
-        if (i == 0 && D.h_blockfb) (void)hipHostFree(D.h_blockfb);
-        if (i == 0 && D.copy_stream) (void)hipStreamDestroy(D.copy_stream);
-        if (i == 0 && D.part_done) (void)hipEventDestroy(D.part_done);
-        if (D.h_dyn[i]) (void)hipHostFree(D.h_dyn[i]);
-        if (D.cams_copied[i]) (void)hipEventDestroy(D.cams_copied[i]);
+    if (D.fb.p) (void)hipFree(D.fb.p);
+    for (LaunchStream& L : D.launch) {
+        if (L.d_stats) (void)hipFree(L.d_stats);
+        if (L.d_cams) (void)hipFree(L.d_cams);
+        if (L.h_cams) (void)hipHostFree(L.h_cams);
+        if (L.cams_copied) (void)hipEventDestroy(L.cams_copied);
+        if (L.d_dyn) (void)hipFree(L.d_dyn);
+        if (L.h_dyn) (void)hipHostFree(L.h_dyn);
+        if (L.d_pass) (void)hipFree(L.d_pass);
     }
-    for (int i = 0; i < kStatSlots; i++)
-        if (D.d_pass[i]) (void)hipFree(D.d_pass[i]);
-    for (void* r : D.pass_retired) (void)hipFree(r);
+    for (void* r : D.retired) (void)hipFree(r);
+    if (D.d_blockfb.p) (void)hipFree(D.d_blockfb.p);
+    if (D.h_blockfb.p) (void)hipHostFree(D.h_blockfb.p);
+    if (D.copy_stream) (void)hipStreamDestroy(D.copy_stream);
+    if (D.part_done) (void)hipEventDestroy(D.part_done);
     if (D.d_diag) (void)hipFree(D.d_diag);
     if (D.joined) (void)hipEventDestroy(D.joined);
     if (D.events_ok)
@@ -101,16 +98,18 @@ void destroy_device(DeviceState& D) {
 
 namespace vrt {
 
-/* Grows a per-device cache buffer to at least `bytes` (its contents are not kept). */
-int ensure_buffer(Buffer& b, size_t bytes) {
+/* Grows a buffer to at least `bytes` (its contents are not kept): device memory, or pinned host memory. */
+static int grow_buffer(Buffer& b, size_t bytes, bool pinned) {
     if (b.cap >= bytes) return VRT_OK;
-    if (b.p) HIP_TRY(hipFree(b.p));
+    if (b.p) HIP_TRY(pinned ? hipHostFree(b.p) : hipFree(b.p));
     b.p = nullptr;
     b.cap = 0;
-    HIP_TRY(hipMalloc(&b.p, bytes));
+    HIP_TRY(pinned ? hipHostMalloc(&b.p, bytes, hipHostMallocDefault) : hipMalloc(&b.p, bytes));
     b.cap = bytes;
     return VRT_OK;
 }
+int ensure_buffer(Buffer& b, size_t bytes) { return grow_buffer(b, bytes, false); }
+int ensure_pinned_buffer(Buffer& b, size_t bytes) { return grow_buffer(b, bytes, true); }
 
 }  // namespace vrt
 
@@ -157,7 +156,7 @@ int vrt_destroy(vrt_ctx* ctx) {
     for (auto& D : ctx->dev) {
         if (hipSetDevice(D.ordinal) == hipSuccess) (void)hipDeviceSynchronize();
     }
-    if (ctx->gather && !ctx->dev.empty() && hipSetDevice(ctx->dev[0].ordinal) == hipSuccess) (void)hipFree(ctx->gather);
+    if (ctx->gather.p && !ctx->dev.empty() && hipSetDevice(ctx->dev[0].ordinal) == hipSuccess) (void)hipFree(ctx->gather.p);
     for (auto& D : ctx->dev) destroy_device(D);
     delete ctx;
     return VRT_OK;

@@ -15,7 +15,7 @@
 
 namespace vrt {
 
-constexpr int kStatSlots = 16; /* streams that may have launches in flight at once without sharing a counter buffer */
+constexpr int kStatSlots = 16; /* streams that may have launches in flight at once without sharing a LaunchStream record */
 constexpr int kRing = 256; /* per-launch event pairs + stat slots kept for vrt_timing_history */
 
 struct HostVolume {
@@ -92,6 +92,13 @@ struct SceneArrays {
     DPalSlot pal[VRT_MAX_VOLUMES]; /* the palette table (DFrame::pal) */
 };
 
+/* A buffer that a call grows on demand and vrt_destroy frees: device memory (ensure_buffer) or pinned host memory
+   (ensure_pinned_buffer).  Nothing clears one between calls. */
+struct Buffer {
+    void* p = nullptr;
+    size_t cap = 0;
+};
+
 /* One frame in flight (vrt_render_begin / vrt_render_end): stream, completion event, scene snapshot, device frame and
    a pinned host frame. */
 struct FrameSlot {
@@ -100,9 +107,7 @@ struct FrameSlot {
     hipEvent_t done = nullptr;
     SceneArrays* d_scene = nullptr;
     SceneArrays* h_scene = nullptr; /* pinned */
-    void* d_fb = nullptr;
-    void* h_fb = nullptr; /* pinned */
-    size_t fb_bytes = 0;
+    Buffer d_fb, h_fb;  /* h_fb: pinned */
     bool busy = false;
     int ring = 0;       /* event-ring slot of the launch (timing) */
 };
@@ -110,12 +115,30 @@ struct FrameSlot {
 constexpr size_t kStatsBytesMax = (size_t)512 << 20; /* per-wave counters of one launch (1080p: 1.1 MB per frame, 3840x2160: 4.2 MB) */
 constexpr size_t kPassBytesMax = (size_t)4 << 30; /* hit records of one launch of the full closest hit in passes (1080p: 42 MB per frame) */
 
-/* A per-device cache buffer that a call grows on demand (ensure_buffer) and vrt_destroy frees.  Shared by the slots; nothing clears
-   one between calls. */
-struct Buffer {
-    void* p = nullptr;
-    size_t cap = 0;
+/* What one launch STREAM owns (DeviceState::launch: kStatSlots streams at a time, the least recently used record taken over), so that
+   frames in flight on different streams — the reference keeps 3 (DXConstants.cpp:23) — never share any of it, and launches on one
+   stream, which run in order, reuse theirs.  Buffers only ever grow, and an outgrown buffer is retired (DeviceState::retired), not
+   freed, until vrt_destroy: a launch captured into a hipGraph has its buffers' addresses baked into the kernarg and may be replayed at
+   any later time.  vrt_render.hip claims and sizes a record; destroy_device frees it. */
+struct LaunchStream {
+    hipStream_t stream = nullptr;
+    bool bound = false;  /* `stream` has launched with this record */
+    uint64_t used = 0;   /* launch number of the last use (LRU) */
+    unsigned* d_stats = nullptr; /* per-wave records: the counters of the stream's last launch */
+    size_t stats_cap = 0;        /* blocks */
+    /* launches of more than kMaxBlockFrames frames: the frames' camera records, packed into pinned host memory and copied ahead of
+       the launch on its stream; `cams_copied` says when the pinned copy may be packed again */
+    DCam *d_cams = nullptr, *h_cams = nullptr;
+    hipEvent_t cams_copied = nullptr;
+    /* launches over per-frame scene state (vrt_block::scenes): the frames' sections (DDyn + instances + BVH + lights, kDynStride bytes
+       each), packed into pinned host memory and copied ahead of the launch together with the camera records */
+    char *d_dyn = nullptr, *h_dyn = nullptr;
+    /* three-pass full closest hit: hit records of a launch (16 + 4 bytes per pixel of the block's tiles + 8 per wave), allocated by
+       the first such launch of that size */
+    void* d_pass = nullptr;
+    size_t pass_cap = 0; /* records */
 };
+
 enum BufferId {
     kBufEditStaging,   /* vrt_volume_update_region and vrt_volume_download_region: the box's staging copy */
     kBufEditScratch,   /* rebuild_derived over an edit's box: the level-2 table's region scratch */
@@ -150,42 +173,15 @@ struct DeviceState {
     DSpotLight* d_spot = nullptr;
     uint8_t* d_env = nullptr;
     uint8_t* tex[VRT_MAX_TEXTURES] = {};
-    float* fb = nullptr;
-    size_t fb_bytes = 0;
-    /* per-wave records: one counter buffer per launch STREAM (kStatSlots streams at a time, least recently used
-       slot recycled), so frames in flight on different streams — the reference keeps 3 (DXConstants.cpp:23) — never
-       share one, and launches on one stream, which run in order, reuse theirs.  Buffers only ever grow, and an
-       outgrown buffer is retired, not freed, until vrt_destroy: a launch captured into a hipGraph has its buffer's
-       address baked into the kernarg and may be replayed at any later time. */
-    unsigned* d_stats[kStatSlots] = {};
-    size_t stats_cap[kStatSlots] = {}; /* blocks */
-    hipStream_t stats_stream[kStatSlots] = {};
-    bool stats_bound[kStatSlots] = {};
-    uint64_t stats_used[kStatSlots] = {}; /* launch number of the last use (LRU) */
-    std::vector<unsigned*> stats_retired;
-    /* three-pass full closest hit: hit records of a launch (16 + 4 bytes per pixel of the block's tiles + 8 per wave), per launch
-       stream like the counters, allocated by the first such launch of that size */
-    /* launches of more than kMaxBlockFrames frames: the frames' camera records, packed into pinned host memory and copied ahead of
-       the launch on its stream (per launch stream, like the counters); `cams_copied` says when the pinned copy may be packed again */
-    DCam* d_cams[kStatSlots] = {};
-    DCam* h_cams[kStatSlots] = {};
-    hipEvent_t cams_copied[kStatSlots] = {};
-    /* launches over per-frame scene state (vrt_block::scenes): the frames' sections (DDyn + instances + BVH + lights, kDynStride bytes
-       each), packed into pinned host memory and copied ahead of the launch together with the camera records */
-    char* d_dyn[kStatSlots] = {};
-    char* h_dyn[kStatSlots] = {};
-    void* d_pass[kStatSlots] = {};
-    size_t pass_cap[kStatSlots] = {}; /* records */
-    std::vector<void*> pass_retired;
-    /* vrt_render_block_host: the block's frames on the device and in pinned host memory (grown, never shrunk) */
-    void* d_blockfb = nullptr;
-    void* h_blockfb = nullptr;
-    size_t blockfb_bytes = 0;
-    hipStream_t copy_stream = nullptr;
+    Buffer fb;                        /* vrt_render: this device's frame, or its compact tile of strips */
+    LaunchStream launch[kStatSlots];  /* the launch streams' records */
+    std::vector<void*> retired;       /* counter buffers and hit records that a stream outgrew: freed by vrt_destroy */
+    Buffer d_blockfb, h_blockfb;      /* vrt_render_block_host: the block's frames on the device and in pinned host memory */
+    hipStream_t copy_stream = nullptr;   /* read-backs under the march (ensure_copy_stream), with `part_done` */
     hipStream_t flight_stream = nullptr; /* vrt_render_begin: the marches of the frames in flight */
     hipEvent_t part_done = nullptr;
     bool peer_to_first = false;  /* this device maps device 0's memory (hipDeviceEnablePeerAccess succeeded): the strided 2D gather copy may be used */
-    int last_slot = 0;
+    int last_slot = 0;           /* the record in `launch` of the last launch's stream: vrt_last_timing / vrt_debug_wave_records read its counters */
     unsigned* d_diag = nullptr;  /* allocated on first use of VRT_FLAG_DIAG_TIMELINE (never in a capture) */
     Buffer buf[kBufCount];       /* the calls' cache buffers (BufferId) */
     int* d_box6 = nullptr;       /* rebuild_derived: the near bricks' box of the level-1 table */
@@ -228,8 +224,7 @@ struct vrt_ctx {
     int last_devices = 0; /* how many devices took part in the last launch */
     uint32_t last_w = 0, last_h = 0;
     float last_gather_ms = 0.f, last_total_ms = 0.f;
-    float* gather = nullptr; /* full frame on device 0 (multi-device only) */
-    size_t gather_bytes = 0;
+    vrt::Buffer gather;      /* full frame on device 0 (multi-device only) */
     void* comm = nullptr;    /* ncclComm_t of vrt_comm_init (one process per GPU) */
     int comm_world = 0, comm_rank = 0;
     bool sizes_agreed = false;
@@ -250,8 +245,9 @@ namespace vrt {
 
 inline bool valid_slot(int slot) { return slot >= 0 && slot < VRT_MAX_VOLUMES; }
 
-/* Grows a per-device cache buffer to at least `bytes` (its contents are not kept). */
+/* Grows a buffer to at least `bytes` (its contents are not kept; the caller sees to it that nothing enqueued still uses the old one). */
 int ensure_buffer(Buffer& b, size_t bytes);
+int ensure_pinned_buffer(Buffer& b, size_t bytes);
 
 /* ---- The scene (vrt_render.hip) ---- */
 /* For a query launch on the first device that takes no vrt_params (vrt_query_points): applies a scene set that was deferred while frames

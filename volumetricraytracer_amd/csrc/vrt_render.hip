@@ -351,6 +351,59 @@ struct RowSet {
     int strip_rows = 0, strip_first = 0, strip_stride = 0;
 };
 
+/* The rows or strips a caller names (a vrt_block's fields; strip_rows > 0: strips) as a RowSet, or VRT_ERR_INVALID.  The entry points do
+   not refuse the same things — kRowsOrStrips, vrt_render_rows and vrt_render_block: sound strips, or strip_rows 0 and rows inside the frame
+   (a negative strip_rows is invalid); kStripsOnly, vrt_render_strips: strip_rows 0 is invalid too; kCountOnly, vrt_render_block_host, which
+   sizes its buffers ahead of vrt_render_block's own check: only that n_strips (strips or not) is not negative and the row count 0 .. 16384. */
+enum RowCheck { kRowsOrStrips, kStripsOnly, kCountOnly };
+int row_set(const vrt_block& b, int height, RowCheck check, RowSet& rs) {
+    const long long strip_rows = (long long)b.n_strips * b.strip_rows;
+    if (check == kCountOnly) {
+        const long long rows = b.strip_rows > 0 ? strip_rows : (long long)b.rows;
+        if (b.n_strips < 0 || rows < 0 || rows > 16384) return VRT_ERR_INVALID;
+        rs = RowSet{0, (int)rows, 0, 0, 0};
+    } else if (b.strip_rows > 0) {
+        if (b.strip_stride < 1 || b.first_strip < 0 || b.first_strip >= b.strip_stride || b.n_strips < 0 || strip_rows > 16384) return VRT_ERR_INVALID;
+        rs = RowSet{0, (int)strip_rows, b.strip_rows, b.first_strip, b.strip_stride};
+    } else {
+        if (check == kStripsOnly || b.strip_rows < 0 || b.row0 < 0 || b.rows < 0 || b.row0 + b.rows > height) return VRT_ERR_INVALID;
+        rs = RowSet{b.row0, b.rows, 0, 0, 0};
+    }
+    return VRT_OK;
+}
+
+/* Bytes of one pixel of the output: four floats, or RGBA8 / BGRA8. */
+inline size_t pixel_bytes(uint32_t flags) { return (flags & VRT_FLAG_OUTPUT_RGBA8) ? 4 : 16; }
+
+/* Whether what is enqueued on the stream is being captured into a hipGraph.  The null stream, and a query that fails, mean "not capturing". */
+bool capturing(hipStream_t stream) {
+    hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
+    return stream != nullptr && hipStreamIsCapturing(stream, &cs) == hipSuccess && cs != hipStreamCaptureStatusNone;
+}
+
+/* The upload of the scene arrays that pack_scene deferred (frames were in flight), ahead of the first launch that reads the context's
+   device copies: now — with synchronous copies, so VRT_ERR_NOT_READY on a capturing stream. */
+int flush_scene_arrays(vrt_ctx* ctx, hipStream_t stream) {
+    if (ctx->arrays_uploaded) return VRT_OK;
+    return capturing(stream) ? VRT_ERR_NOT_READY : upload_scene_arrays(ctx);
+}
+
+/* The books of a launch that is enqueued (vrt_render fills in its two durations afterwards). */
+void note_launch(vrt_ctx* ctx, int devices, int w, int h) {
+    ctx->launches++;
+    ctx->last_devices = devices;
+    ctx->last_w = (uint32_t)w;
+    ctx->last_h = (uint32_t)h;
+    ctx->last_gather_ms = ctx->last_total_ms = 0.f;
+}
+
+/* The stream of the read-backs that run under a march, and the event they wait for. */
+int ensure_copy_stream(DeviceState& D) {
+    if (!D.copy_stream) HIP_TRY(hipStreamCreateWithFlags(&D.copy_stream, hipStreamNonBlocking));
+    if (!D.part_done) HIP_TRY(hipEventCreateWithFlags(&D.part_done, hipEventDisableTiming));
+    return VRT_OK;
+}
+
 /* Screen rectangle of everything a primary ray can reach (DFrame::cull_*): the corners of every instance's active box
    (object space -> world -> camera -> pixel), double precision, two pixels of margin.  Any corner at or behind the camera
    plane: the whole frame. */
@@ -490,8 +543,17 @@ ClosestHitForm closest_hit_form(const vrt_ctx* ctx, const vrt_params* p, const v
     return u;
 }
 
-void build_frame(const vrt_ctx* ctx, const DeviceState& D, const vrt_params* p, const RowSet& rs, float* out,
-                 unsigned* stats, DFrame& F, const SceneArrays* snapshot = nullptr, const vrt_scene* scenes = nullptr, int n_scenes = 0) {
+/* The frames of one launch: frame f from cams[f] (null: the scene's own camera) or — per-frame scene state — from scenes[f], into
+   out + f * stride bytes.  snapshot: a frame in flight reads the scene from its own copy of the arrays. */
+struct LaunchFrames {
+    int n = 1;
+    const vrt_camera* cams = nullptr;
+    size_t stride = 0;
+    const vrt_scene* scenes = nullptr;
+    const SceneArrays* snapshot = nullptr;
+};
+
+void build_frame(const vrt_ctx* ctx, const DeviceState& D, const vrt_params* p, const RowSet& rs, float* out, DFrame& F, const LaunchFrames& fr = LaunchFrames{}) {
     const int row0 = rs.row0, rows = rs.rows;
     memset(&F, 0, sizeof F);
     F.inv_w = 1.0f / (float)p->width;
@@ -529,7 +591,7 @@ void build_frame(const vrt_ctx* ctx, const DeviceState& D, const vrt_params* p, 
     F.strip_rows = rs.strip_rows;
     F.strip_first = rs.strip_first;
     F.strip_stride = rs.strip_stride;
-    const ClosestHitForm form = closest_hit_form(ctx, p, scenes, n_scenes);
+    const ClosestHitForm form = closest_hit_form(ctx, p, fr.scenes, fr.n);
     F.textured = form.textured ? 1 : 0;
     F.full = form.full ? 1 : 0;
     F.may_bounce = form.may_bounce ? 1 : 0;
@@ -537,175 +599,223 @@ void build_frame(const vrt_ctx* ctx, const DeviceState& D, const vrt_params* p, 
     F.n_nodes = ctx->n_nodes;
     F.n_point = std::min(ctx->scene.n_point_lights, VRT_MAX_POINT_LIGHTS);
     F.n_spot = std::min(ctx->scene.n_spot_lights, VRT_MAX_SPOT_LIGHTS);
-    F.vols = snapshot ? snapshot->vols : D.d_vols;
-    F.inst = snapshot ? snapshot->inst : D.d_inst;
-    F.nodes = snapshot ? snapshot->nodes : D.d_nodes;
-    F.point = snapshot ? snapshot->point : D.d_point;
-    F.spot = snapshot ? snapshot->spot : D.d_spot;
+    F.vols = fr.snapshot ? fr.snapshot->vols : D.d_vols;
+    F.inst = fr.snapshot ? fr.snapshot->inst : D.d_inst;
+    F.nodes = fr.snapshot ? fr.snapshot->nodes : D.d_nodes;
+    F.point = fr.snapshot ? fr.snapshot->point : D.d_point;
+    F.spot = fr.snapshot ? fr.snapshot->spot : D.d_spot;
     F.env = ctx->env_size > 0 ? D.d_env : nullptr;
     F.env_size = ctx->env_size;
     F.out = out;
-    F.stats = stats;
     F.vol0 = ctx->scene.n_instances == 1 ? F.vols + ctx->scene.instances[0].volume_slot : nullptr;
-    F.pal = form.palette ? (snapshot ? snapshot->pal : D.d_pal) : nullptr;
+    F.pal = form.palette ? (fr.snapshot ? fr.snapshot->pal : D.d_pal) : nullptr;
 }
 
-/* Enqueue n_frames frames of one tile on one device as ONE launch (grid.y = frame): frame f from cams[f] (null: the scene's own
-   camera) into out + f * frame_stride bytes.  No allocation after the stream's first launch of that size, no host sync. */
-int enqueue_rows(vrt_ctx* ctx, DeviceState& D, const vrt_params* p, const RowSet& rs, float* out, hipStream_t stream,
-                 int ring, const SceneArrays* snapshot = nullptr, int n_frames = 1, const vrt_camera* cams = nullptr, size_t frame_stride = 0,
-                 const vrt_scene* scenes = nullptr) {
-    if (n_frames < 1 || n_frames > kMaxLaunchFrames) return VRT_ERR_INVALID;
-    /* more cameras than the kernarg segment holds, or per-frame scene state (its records live in device memory, the cameras with them) */
-    const bool device_cams = n_frames > kMaxBlockFrames || scenes != nullptr;
-    DBlock B;
-    memset(B.cam, 0, sizeof B.cam); /* (the whole struct travels as the kernarg: no stale stack bytes behind the block's frames) */
-    DFrame& F = B.f;
-    build_frame(ctx, D, p, rs, out, nullptr, F, snapshot, scenes, n_frames);
+/* On the take-over of a launch stream's record (vrt_context.h, LaunchStream): the record's previous stream may still be running a full
+   closest hit in passes, or a launch with its cameras in device memory: hit records and camera records (unlike the counters) decide
+   pixels: wait for the device once before another stream takes them over (a 17th stream: rare).  A capturing stream does not wait. */
+bool take_over_waits(const LaunchStream& L, bool captured) { return L.bound && (L.d_pass != nullptr || L.d_cams != nullptr) && !captured; }
+
+/* The stream's record for launch number `launch`: the one it holds, or — a stream not seen lately — an unused or the least recently used one. */
+int claim_launch_stream(DeviceState& D, hipStream_t stream, bool captured, uint64_t launch, int& slot) {
+    int lru = 0;
+    slot = -1;
+    for (int i = 0; i < kStatSlots; i++) {
+        const LaunchStream &a = D.launch[i], &b = D.launch[lru];
+        if (a.bound && a.stream == stream) slot = i;
+        if ((!a.bound && b.bound) || (a.bound == b.bound && a.used < b.used)) lru = i;
+    }
+    if (slot < 0) {
+        slot = lru;
+        if (take_over_waits(D.launch[slot], captured)) HIP_TRY(hipDeviceSynchronize());
+        D.launch[slot].bound = true;
+        D.launch[slot].stream = stream;
+    }
+    D.launch[slot].used = launch;
+    return VRT_OK;
+}
+
+/* Grows one of a record's buffers to `want` units (`bytes`): the stream's first launch of that size.  The outgrown buffer is retired,
+   not freed: a captured graph may still use it. */
+template <class T> int grow_retiring(DeviceState& D, T*& p, size_t& cap, size_t want, size_t bytes) {
+    if (cap >= want) return VRT_OK;
+    T* grown = nullptr;
+    HIP_TRY(hipMalloc(&grown, bytes));
+    if (p) D.retired.push_back(p);
+    p = grown;
+    cap = want;
+    return VRT_OK;
+}
+/* Counters for `blocks` workgroups, all frames counted (the only allocation of a launch that needs no other records). */
+int ensure_counters(DeviceState& D, LaunchStream& L, size_t blocks) {
+    return grow_retiring(D, L.d_stats, L.stats_cap, blocks, sizeof(unsigned) * kStatRecord * 4 * blocks);
+}
+/* Hit records of the full closest hit in passes, per_frame for each of n frames (per record a HitRecord and an auxiliary word, per 64
+   records a mask), and F pointed at them. */
+int ensure_hit_records(DeviceState& D, LaunchStream& L, size_t per_frame, int n, DFrame& F) {
+    const size_t records = per_frame * (size_t)n;
+    const int rc = grow_retiring(D, L.d_pass, L.pass_cap, records, records * (sizeof(HitRecord) + sizeof(unsigned)) + records / 64 * sizeof(unsigned long long));
+    if (rc != VRT_OK) return rc;
+    char* base = static_cast<char*>(L.d_pass);
+    F.hit_rec = reinterpret_cast<HitRecord*>(base);
+    F.hit_mask = reinterpret_cast<unsigned long long*>(base + L.pass_cap * sizeof(HitRecord));
+    F.hit_aux = reinterpret_cast<unsigned*>(base + L.pass_cap * sizeof(HitRecord) + L.pass_cap / 64 * sizeof(unsigned long long));
+    F.rec_stride = (uint32_t)per_frame;
+    return VRT_OK;
+}
+/* Camera records — and, `sections`, scene sections — of kMaxLaunchFrames frames, on the device and pinned.  Where they exist: the previous
+   launch's copy has read the pinned records (long ago, normally) before they are packed again. */
+int ensure_camera_records(LaunchStream& L, bool sections) {
+    if (!L.d_cams) {
+        HIP_TRY(hipMalloc(&L.d_cams, sizeof(DCam) * kMaxLaunchFrames));
+        HIP_TRY(hipHostMalloc(&L.h_cams, sizeof(DCam) * kMaxLaunchFrames));
+        HIP_TRY(hipEventCreateWithFlags(&L.cams_copied, hipEventDisableTiming));
+    } else {
+        HIP_TRY(hipEventSynchronize(L.cams_copied));
+    }
+    if (sections && !L.d_dyn) {
+        HIP_TRY(hipMalloc(&L.d_dyn, (size_t)kDynStride * kMaxLaunchFrames));
+        HIP_TRY(hipHostMalloc(&L.h_dyn, (size_t)kDynStride * kMaxLaunchFrames));
+    }
+    return VRT_OK;
+}
+
+/* What the steps of a launch (enqueue_rows) agree on: data path, workgroups per frame, the single-instance kernel form; device_cams: more
+   cameras than the kernarg segment holds, or per-frame scene state (its records live in device memory, the cameras with them); passes:
+   the full closest hit runs as three passes; captured: the stream is being captured into a graph. */
+struct LaunchPlan {
+    int path = 0, blocks = 0;
+    bool single = false, device_cams = false, passes = false, captured = false;
+};
+
+/* Step 1, refuse: fills F with what the launch's frames share, and refuses what cannot be launched — every check there is, in the order
+   they have always had, ahead of the first write to D or to a launch record.  (The deferred scene upload stands among them because its
+   refusal does; it writes the device's scene arrays, none of the launch's books.) */
+int plan_launch(vrt_ctx* ctx, const DeviceState& D, const vrt_params* p, const RowSet& rs, float* out, hipStream_t stream, const LaunchFrames& fr, DFrame& F, LaunchPlan& plan) {
+    if (fr.n < 1 || fr.n > kMaxLaunchFrames) return VRT_ERR_INVALID;
+    plan.device_cams = fr.n > kMaxBlockFrames || fr.scenes != nullptr;
+    build_frame(ctx, D, p, rs, out, F, fr);
     if ((long long)F.tiles_x * F.tiles_y > kMaxBlocks / 2) return VRT_ERR_INVALID;
-    bool single = ctx->scene.n_instances == 1;
-    if (scenes) { /* one kernel form for the launch: the single-instance one only when every frame has exactly one instance */
-        if (snapshot || (p->flags & VRT_FLAG_DIAG_TIMELINE)) return VRT_ERR_INVALID;
-        single = true;
-        for (int f = 0; f < n_frames; f++) single = single && scenes[f].n_instances == 1;
+    plan.single = ctx->scene.n_instances == 1;
+    if (fr.scenes) { /* one kernel form for the launch: the single-instance one only when every frame has exactly one instance */
+        if (fr.snapshot || (p->flags & VRT_FLAG_DIAG_TIMELINE)) return VRT_ERR_INVALID;
+        plan.single = true;
+        for (int f = 0; f < fr.n; f++) plan.single = plan.single && fr.scenes[f].n_instances == 1;
         F.vol0 = nullptr;
     }
-    const int path = resolve_path(ctx, p->path, single, p->mode, scenes, n_frames);
-    if (path < 0) return path;
-    if (!snapshot && !scenes && !ctx->arrays_uploaded) { /* deferred by pack_scene (frames were in flight): now */
-        hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
-        if (stream != nullptr && hipStreamIsCapturing(stream, &cs) == hipSuccess && cs != hipStreamCaptureStatusNone) return VRT_ERR_NOT_READY;
-        const int rc = upload_scene_arrays(ctx);
-        if (rc != VRT_OK) return rc;
-    }
-    D.last_blocks = grid_blocks(F.tiles_x, F.tiles_y, F.tile_map);
-    if ((long long)D.last_blocks * n_frames > 8LL * kMaxBlocks) return VRT_ERR_INVALID;
-    D.last_frames = n_frames;
-    F.n_frames = n_frames;
-    F.frame_stride = frame_stride;
-    F.stats_stride = (uint32_t)((size_t)D.last_blocks * 4 * kStatRecord);
-    const vrt_camera own = scene_camera(ctx->scene);
-    for (int f = 0; f < n_frames && !device_cams; f++) {
-        pack_camera(cams ? cams[f] : own, p->width, p->height, B.cam[f]);
-        cull_rect(ctx, p, B.cam[f]);
-    }
-    const size_t stat_blocks = (size_t)D.last_blocks * (size_t)n_frames; /* one record set per (frame, wave) */
-    int slot = -1;
-    for (int i = 0; i < kStatSlots; i++)
-        if (D.stats_bound[i] && D.stats_stream[i] == stream) slot = i;
-    if (slot < 0) { /* a stream not seen lately: take the least recently used slot */
-        slot = 0;
-        for (int i = 1; i < kStatSlots; i++) {
-            const bool freer = !D.stats_bound[i] && D.stats_bound[slot];
-            const bool older = D.stats_bound[i] == D.stats_bound[slot] && D.stats_used[i] < D.stats_used[slot];
-            if (freer || older) slot = i;
-        }
-        /* the slot's previous stream may still be running a full closest hit in passes, or a launch with its cameras in device memory:
-           hit records and camera records (unlike the counters) decide pixels: wait for the device once before another stream takes
-           them over (a 17th stream: rare) */
-        if (D.stats_bound[slot] && (D.d_pass[slot] != nullptr || D.d_cams[slot] != nullptr)) {
-            hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
-            if (stream == nullptr || hipStreamIsCapturing(stream, &cs) != hipSuccess || cs == hipStreamCaptureStatusNone)
-                HIP_TRY(hipDeviceSynchronize());
-        }
-        D.stats_bound[slot] = true;
-        D.stats_stream[slot] = stream;
-    }
-    D.stats_used[slot] = ctx->launches;
-    if (D.stats_cap[slot] < stat_blocks) { /* first launch of this size on this stream: the only allocation on this path */
-        unsigned* grown = nullptr;
-        HIP_TRY(hipMalloc(&grown, sizeof(unsigned) * kStatRecord * 4 * stat_blocks));
-        if (D.d_stats[slot]) D.stats_retired.push_back(D.d_stats[slot]); /* a captured graph may still write to it */
-        D.d_stats[slot] = grown;
-        D.stats_cap[slot] = stat_blocks;
-    }
-    D.last_slot = slot;
-    F.stats = D.d_stats[slot];
-    if (device_cams) {
-        hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
-        if (stream != nullptr && hipStreamIsCapturing(stream, &cs) == hipSuccess && cs != hipStreamCaptureStatusNone)
-            return VRT_ERR_INVALID; /* (a replay would copy whatever the pinned records hold by then; vrt_render_block captures in kernarg-sized launches) */
-        if (!D.d_cams[slot]) {
-            HIP_TRY(hipMalloc(&D.d_cams[slot], sizeof(DCam) * kMaxLaunchFrames));
-            HIP_TRY(hipHostMalloc(&D.h_cams[slot], sizeof(DCam) * kMaxLaunchFrames));
-            HIP_TRY(hipEventCreateWithFlags(&D.cams_copied[slot], hipEventDisableTiming));
-        } else {
-            HIP_TRY(hipEventSynchronize(D.cams_copied[slot])); /* the previous launch's copy has read the pinned records (long ago, normally) */
-        }
-        if (scenes && !D.d_dyn[slot]) {
-            HIP_TRY(hipMalloc(&D.d_dyn[slot], (size_t)kDynStride * kMaxLaunchFrames));
-            HIP_TRY(hipHostMalloc(&D.h_dyn[slot], (size_t)kDynStride * kMaxLaunchFrames));
-        }
-        for (int f = 0; f < n_frames; f++) {
-            if (!scenes) {
-                pack_camera(cams ? cams[f] : own, p->width, p->height, D.h_cams[slot][f]);
-                cull_rect(ctx, p, D.h_cams[slot][f]);
-                continue;
-            }
-            /* frame f's scene as vrt_scene_set would pack it (instances, BVH rebuilt per frame like the reference's TLAS,
-               DXRenderer.cpp:809-825; lights), its camera and its own cull rectangle */
-            const vrt_scene& sc = scenes[f];
-            char* sec = D.h_dyn[slot] + (size_t)f * kDynStride;
-            DDyn* rec = reinterpret_cast<DDyn*>(sec);
-            DInstance* inst = reinterpret_cast<DInstance*>(sec + kDynInstOff);
-            memset(rec, 0, sizeof *rec);
-            pack_scene_arrays(ctx, sc, inst, reinterpret_cast<DBvhNode*>(sec + kDynNodesOff), rec->n_nodes,
-                              reinterpret_cast<DPointLight*>(sec + kDynPointOff), reinterpret_cast<DSpotLight*>(sec + kDynSpotOff));
-            memcpy(rec->light_dir, sc.light_dir, sizeof rec->light_dir);
-            rec->light_strength = sc.light_strength;
-            rec->n_inst = sc.n_instances;
-            rec->n_point = std::min(sc.n_point_lights, VRT_MAX_POINT_LIGHTS);
-            rec->n_spot = std::min(sc.n_spot_lights, VRT_MAX_SPOT_LIGHTS);
-            rec->vol0_slot = sc.n_instances > 0 ? sc.instances[0].volume_slot : 0;
-            pack_camera(scene_camera(sc), p->width, p->height, D.h_cams[slot][f]);
-            cull_rect(ctx, p, D.h_cams[slot][f], &sc, inst);
-        }
-        HIP_TRY(hipMemcpyAsync(D.d_cams[slot], D.h_cams[slot], sizeof(DCam) * (size_t)n_frames, hipMemcpyHostToDevice, stream));
-        if (scenes) {
-            HIP_TRY(hipMemcpyAsync(D.d_dyn[slot], D.h_dyn[slot], (size_t)kDynStride * (size_t)n_frames, hipMemcpyHostToDevice, stream));
-            F.dyn = D.d_dyn[slot];
-        }
-        HIP_TRY(hipEventRecord(D.cams_copied[slot], stream));
-        F.cams = D.d_cams[slot];
-    }
+    plan.path = resolve_path(ctx, p->path, plan.single, p->mode, fr.scenes, fr.n);
+    if (plan.path < 0) return plan.path;
+    const int rc = (fr.snapshot || fr.scenes) ? VRT_OK : flush_scene_arrays(ctx, stream); /* (the launch reads the context's device copies) */
+    if (rc != VRT_OK) return rc;
+    plan.blocks = grid_blocks(F.tiles_x, F.tiles_y, F.tile_map);
+    if ((long long)plan.blocks * fr.n > 8LL * kMaxBlocks) return VRT_ERR_INVALID;
+    plan.captured = capturing(stream);
+    if (plan.device_cams && plan.captured) return VRT_ERR_INVALID; /* (a replay would copy whatever the pinned records hold by then; vrt_render_block captures in kernarg-sized launches) */
     /* the full closest hit of a block of frames runs as three passes (vrt_kernels.hip, primary_pass_kernel); a lone frame as one
        kernel: three launches would pay a launch's latency-bound tail three times */
     if (F.pal != nullptr && (p->flags & VRT_FLAG_FULL_THREE_PASS)) return VRT_ERR_UNSUPPORTED; /* (check_params and vrt_render_block refuse it earlier) */
-    const bool passes = F.pal == nullptr && F.full && !F.diag && ((n_frames > 1 && !(p->flags & VRT_FLAG_FULL_ONE_KERNEL)) || (p->flags & VRT_FLAG_FULL_THREE_PASS));
-    if (passes) {
-        const size_t per_frame = (size_t)D.last_blocks * 256, records = per_frame * (size_t)n_frames;
-        if (per_frame > 0xffffffffull) return VRT_ERR_INVALID;
-        if (D.pass_cap[slot] < records) {
-            void* grown = nullptr;
-            HIP_TRY(hipMalloc(&grown, records * (sizeof(HitRecord) + sizeof(unsigned)) + records / 64 * sizeof(unsigned long long)));
-            if (D.d_pass[slot]) D.pass_retired.push_back(D.d_pass[slot]);
-            D.d_pass[slot] = grown;
-            D.pass_cap[slot] = records;
+    plan.passes = F.pal == nullptr && F.full && !F.diag && ((fr.n > 1 && !(p->flags & VRT_FLAG_FULL_ONE_KERNEL)) || (p->flags & VRT_FLAG_FULL_THREE_PASS));
+    if (plan.passes && (size_t)plan.blocks * 256 > 0xffffffffull) return VRT_ERR_INVALID;
+    if (F.diag && (size_t)plan.blocks * (size_t)fr.n > (size_t)kMaxBlocks) return VRT_ERR_INVALID; /* the timeline buffer holds kMaxBlocks workgroups */
+    F.n_frames = fr.n;
+    F.frame_stride = fr.stride;
+    F.stats_stride = (uint32_t)((size_t)plan.blocks * 4 * kStatRecord);
+    return VRT_OK;
+}
+
+/* Frame f's scene as vrt_scene_set would pack it (instances, BVH rebuilt per frame like the reference's TLAS, DXRenderer.cpp:809-825;
+   lights) into its section `sec`, its camera and its own cull rectangle into `cam`. */
+void pack_scene_section(const vrt_ctx* ctx, const vrt_params* p, const vrt_scene& sc, char* sec, DCam& cam) {
+    DDyn* rec = reinterpret_cast<DDyn*>(sec);
+    DInstance* inst = reinterpret_cast<DInstance*>(sec + kDynInstOff);
+    memset(rec, 0, sizeof *rec);
+    pack_scene_arrays(ctx, sc, inst, reinterpret_cast<DBvhNode*>(sec + kDynNodesOff), rec->n_nodes,
+                      reinterpret_cast<DPointLight*>(sec + kDynPointOff), reinterpret_cast<DSpotLight*>(sec + kDynSpotOff));
+    memcpy(rec->light_dir, sc.light_dir, sizeof rec->light_dir);
+    rec->light_strength = sc.light_strength;
+    rec->n_inst = sc.n_instances;
+    rec->n_point = std::min(sc.n_point_lights, VRT_MAX_POINT_LIGHTS);
+    rec->n_spot = std::min(sc.n_spot_lights, VRT_MAX_SPOT_LIGHTS);
+    rec->vol0_slot = sc.n_instances > 0 ? sc.instances[0].volume_slot : 0;
+    pack_camera(scene_camera(sc), p->width, p->height, cam);
+    cull_rect(ctx, p, cam, &sc, inst);
+}
+
+/* Step 3, pack the frames: their cameras into the kernarg (B.cam), or — device_cams — into the stream's pinned camera records, with the
+   frames' scene sections where the launch has per-frame scenes, followed by their copies to the device on the launch's stream. */
+int pack_frames(const vrt_ctx* ctx, const vrt_params* p, const LaunchFrames& fr, const LaunchPlan& plan, LaunchStream& L, hipStream_t stream, DBlock& B) {
+    const vrt_camera own = scene_camera(ctx->scene);
+    DCam* cam = plan.device_cams ? L.h_cams : B.cam;
+    for (int f = 0; f < fr.n; f++) {
+        if (fr.scenes) {
+            pack_scene_section(ctx, p, fr.scenes[f], L.h_dyn + (size_t)f * kDynStride, cam[f]);
+        } else {
+            pack_camera(fr.cams ? fr.cams[f] : own, p->width, p->height, cam[f]);
+            cull_rect(ctx, p, cam[f]);
         }
-        char* base = static_cast<char*>(D.d_pass[slot]);
-        F.hit_rec = reinterpret_cast<HitRecord*>(base);
-        F.hit_mask = reinterpret_cast<unsigned long long*>(base + D.pass_cap[slot] * sizeof(HitRecord));
-        F.hit_aux = reinterpret_cast<unsigned*>(base + D.pass_cap[slot] * sizeof(HitRecord) + D.pass_cap[slot] / 64 * sizeof(unsigned long long));
-        F.rec_stride = (uint32_t)per_frame;
     }
-    D.last_diag = F.diag != 0;
-    D.last_form = (F.full ? VRT_FORM_FULL : 0) | (passes ? VRT_FORM_PASSES : 0) | (F.textured ? VRT_FORM_TEXTURED : 0) |
-                  (F.may_bounce ? VRT_FORM_MAY_BOUNCE : 0) | (F.pal != nullptr ? VRT_FORM_PALETTE : 0) | ((!F.full && (F.textured || F.view_vec || F.zero_outside)) ? VRT_FORM_LEAN_REF : 0);
-    if (F.diag) {
-        if (stat_blocks > (size_t)kMaxBlocks) return VRT_ERR_INVALID; /* the timeline buffer holds kMaxBlocks workgroups */
-        if (!D.d_diag) HIP_TRY(hipMalloc(&D.d_diag, sizeof(unsigned) * kDiagRecord * 4 * (size_t)kMaxBlocks));
-        F.diag_buf = D.d_diag;
+    if (!plan.device_cams) return VRT_OK;
+    HIP_TRY(hipMemcpyAsync(L.d_cams, L.h_cams, sizeof(DCam) * (size_t)fr.n, hipMemcpyHostToDevice, stream));
+    if (fr.scenes) {
+        HIP_TRY(hipMemcpyAsync(L.d_dyn, L.h_dyn, (size_t)kDynStride * (size_t)fr.n, hipMemcpyHostToDevice, stream));
+        B.f.dyn = L.d_dyn;
     }
-    /* a launch that is being captured into a hipGraph is not timed: the event pair would become graph nodes and
-       never hold a time stamp of its own (vrt_last_timing / vrt_timing_history report 0 ms for it) */
-    hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
-    if (stream != nullptr && hipStreamIsCapturing(stream, &cap) != hipSuccess) cap = hipStreamCaptureStatusNone;
-    D.timed[ring] = cap == hipStreamCaptureStatusNone && !(p->flags & VRT_FLAG_NO_TIMING);
-    D.ring_frames[ring] = n_frames;
+    HIP_TRY(hipEventRecord(L.cams_copied, stream));
+    B.f.cams = L.d_cams;
+    return VRT_OK;
+}
+
+/* Enqueue fr.n frames of one tile on one device as ONE launch (grid.y = frame).  No allocation after the stream's first launch of that
+   size; no host synchronisation but a take-over's (take_over_waits) and the wait for the pinned camera records. */
+int enqueue_rows(vrt_ctx* ctx, DeviceState& D, const vrt_params* p, const RowSet& rs, float* out, hipStream_t stream, int ring, const LaunchFrames& fr = LaunchFrames{}) {
+    DBlock B;
+    memset(B.cam, 0, sizeof B.cam); /* (the whole struct travels as the kernarg: no stale stack bytes behind the block's frames) */
+    DFrame& F = B.f;
+    LaunchPlan plan;
+    int rc = plan_launch(ctx, D, p, rs, out, stream, fr, F, plan);
+    if (rc != VRT_OK) return rc;
+    int slot = 0; /* step 2, claim and size the stream's record */
+    rc = claim_launch_stream(D, stream, plan.captured, ctx->launches, slot);
+    if (rc != VRT_OK) return rc;
+    LaunchStream& L = D.launch[slot];
+    rc = ensure_counters(D, L, (size_t)plan.blocks * (size_t)fr.n); /* one record set per (frame, wave) */
+    if (rc == VRT_OK && plan.device_cams) rc = ensure_camera_records(L, fr.scenes != nullptr);
+    if (rc != VRT_OK) return rc;
+    F.stats = L.d_stats;
+    rc = pack_frames(ctx, p, fr, plan, L, stream, B);                                                  /* step 3 */
+    if (rc == VRT_OK && plan.passes) rc = ensure_hit_records(D, L, (size_t)plan.blocks * 256, fr.n, F); /* step 4 */
+    if (rc != VRT_OK) return rc;
+    if (F.diag && !D.d_diag) HIP_TRY(hipMalloc(&D.d_diag, sizeof(unsigned) * kDiagRecord * 4 * (size_t)kMaxBlocks));
+    F.diag_buf = F.diag ? D.d_diag : nullptr;
+    /* step 5, timing and launch.  A launch that is being captured into a hipGraph is not timed: the event pair would become graph nodes
+       and never hold a time stamp of its own (vrt_last_timing / vrt_timing_history report 0 ms for it) */
+    D.timed[ring] = !plan.captured && !(p->flags & VRT_FLAG_NO_TIMING);
+    D.ring_frames[ring] = fr.n;
     if (D.timed[ring]) HIP_TRY(hipEventRecord(D.ev0[ring], stream));
     fill_header(B.h, F); /* (last: F is complete) */
-    HIP_TRY(launch_march(B, path, single, stream));
+    HIP_TRY(launch_march(B, plan.path, plan.single, stream));
+    /* what vrt_last_timing, vrt_debug_wave_records and vrt_debug_last_kernel_form say of the last launch: of one that was made */
+    D.last_blocks = plan.blocks;
+    D.last_frames = fr.n;
+    D.last_slot = slot;
+    D.last_diag = F.diag != 0;
+    D.last_form = (F.full ? VRT_FORM_FULL : 0) | (plan.passes ? VRT_FORM_PASSES : 0) | (F.textured ? VRT_FORM_TEXTURED : 0) |
+                  (F.may_bounce ? VRT_FORM_MAY_BOUNCE : 0) | (F.pal != nullptr ? VRT_FORM_PALETTE : 0) | ((!F.full && (F.textured || F.view_vec || F.zero_outside)) ? VRT_FORM_LEAN_REF : 0);
     if (D.timed[ring]) HIP_TRY(hipEventRecord(D.ev1[ring], stream));
+    return VRT_OK;
+}
+
+/* vrt_render_rows and vrt_render_strips: the rows that `b` names, one frame, one launch on the first device. */
+int render_tile(vrt_ctx* ctx, const vrt_params* params, const vrt_block& b, RowCheck check, void* device_rgba, void* hip_stream) {
+    int rc = check_params(ctx, params);
+    if (rc != VRT_OK) return rc;
+    RowSet rs;
+    if (row_set(b, params->height, check, rs) != VRT_OK || (!device_rgba && rs.rows > 0)) return VRT_ERR_INVALID;
+    DeviceState& D = ctx->dev[0];
+    HIP_TRY(hipSetDevice(D.ordinal));
+    rc = enqueue_rows(ctx, D, params, rs, static_cast<float*>(device_rgba), static_cast<hipStream_t>(hip_stream), (int)(ctx->launches % kRing));
+    if (rc != VRT_OK) return rc;
+    note_launch(ctx, 1, params->width, rs.rows);
     return VRT_OK;
 }
 
@@ -723,15 +833,11 @@ int enqueue_query(vrt_ctx* ctx, const vrt_params* p, int query, int n, const voi
     const int path = resolve_path(ctx, p->path, single, p->mode);
     if (path < 0) return path;
     HIP_TRY(hipSetDevice(D.ordinal));
-    if (!ctx->arrays_uploaded) { /* deferred by pack_scene (frames were in flight): now, as enqueue_rows does */
-        hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
-        if (stream != nullptr && hipStreamIsCapturing(stream, &cs) == hipSuccess && cs != hipStreamCaptureStatusNone) return VRT_ERR_NOT_READY;
-        const int rc = upload_scene_arrays(ctx);
-        if (rc != VRT_OK) return rc;
-    }
+    const int rc = flush_scene_arrays(ctx, stream);
+    if (rc != VRT_OK) return rc;
     DQuery Q;
     memset(&Q, 0, sizeof Q); /* (the whole struct travels as the kernarg) */
-    build_frame(ctx, D, p, RowSet{}, nullptr, nullptr, Q.f);
+    build_frame(ctx, D, p, RowSet{}, nullptr, Q.f);
     Q.rays = rays;
     Q.hits = hits;
     Q.n = n;
@@ -749,16 +855,12 @@ namespace vrt {
 int query_scene(vrt_ctx* ctx, hipStream_t stream, DFrame& F) {
     DeviceState& D = ctx->dev[0];
     HIP_TRY(hipSetDevice(D.ordinal));
-    if (!ctx->arrays_uploaded) { /* deferred by pack_scene (frames were in flight): now, as enqueue_rows does */
-        hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
-        if (stream != nullptr && hipStreamIsCapturing(stream, &cs) == hipSuccess && cs != hipStreamCaptureStatusNone) return VRT_ERR_NOT_READY;
-        const int rc = upload_scene_arrays(ctx);
-        if (rc != VRT_OK) return rc;
-    }
+    const int rc = flush_scene_arrays(ctx, stream);
+    if (rc != VRT_OK) return rc;
     vrt_params p;
     memset(&p, 0, sizeof p);
     p.width = p.height = 1;
-    build_frame(ctx, D, &p, RowSet{}, nullptr, nullptr, F);
+    build_frame(ctx, D, &p, RowSet{}, nullptr, F);
     return VRT_OK;
 }
 
@@ -783,24 +885,10 @@ int vrt_scene_set(vrt_ctx* ctx, const vrt_scene* scene) {
 }
 
 int vrt_render_rows(vrt_ctx* ctx, const vrt_params* params, int row0, int rows, void* device_rgba, void* hip_stream) {
-    int rc = check_params(ctx, params);
-    if (rc != VRT_OK) return rc;
-    if (row0 < 0 || rows < 0 || row0 + rows > params->height || (!device_rgba && rows > 0)) return VRT_ERR_INVALID;
-    DeviceState& D = ctx->dev[0];
-    HIP_TRY(hipSetDevice(D.ordinal));
-    const int ring = (int)(ctx->launches % kRing);
-    RowSet rs;
-    rs.row0 = row0;
-    rs.rows = rows;
-    rc = enqueue_rows(ctx, D, params, rs, static_cast<float*>(device_rgba), static_cast<hipStream_t>(hip_stream), ring);
-    if (rc != VRT_OK) return rc;
-    ctx->launches++;
-    ctx->last_devices = 1;
-    ctx->last_w = (uint32_t)params->width;
-    ctx->last_h = (uint32_t)rows;
-    ctx->last_gather_ms = 0.f;
-    ctx->last_total_ms = 0.f;
-    return VRT_OK;
+    vrt_block b = {};
+    b.row0 = row0;
+    b.rows = rows;
+    return render_tile(ctx, params, b, kRowsOrStrips, device_rgba, hip_stream);
 }
 
 int vrt_trace_rays(vrt_ctx* ctx, const vrt_params* params, int query, int n, const vrt_ray* device_rays, vrt_hit* device_hits,
@@ -860,28 +948,12 @@ int vrt_camera_rays(const vrt_scene* scene, int width, int height, int n, const 
 
 int vrt_render_strips(vrt_ctx* ctx, const vrt_params* params, int strip_rows, int first_strip, int strip_stride, int n_strips,
                       void* device_rgba, void* hip_stream) {
-    int rc = check_params(ctx, params);
-    if (rc != VRT_OK) return rc;
-    if (strip_rows < 1 || strip_stride < 1 || first_strip < 0 || first_strip >= strip_stride || n_strips < 0 ||
-        (long long)n_strips * strip_rows > 16384 || (!device_rgba && n_strips > 0))
-        return VRT_ERR_INVALID;
-    DeviceState& D = ctx->dev[0];
-    HIP_TRY(hipSetDevice(D.ordinal));
-    const int ring = (int)(ctx->launches % kRing);
-    RowSet rs;
-    rs.rows = n_strips * strip_rows;
-    rs.strip_rows = strip_rows;
-    rs.strip_first = first_strip;
-    rs.strip_stride = strip_stride;
-    rc = enqueue_rows(ctx, D, params, rs, static_cast<float*>(device_rgba), static_cast<hipStream_t>(hip_stream), ring);
-    if (rc != VRT_OK) return rc;
-    ctx->launches++;
-    ctx->last_devices = 1;
-    ctx->last_w = (uint32_t)params->width;
-    ctx->last_h = (uint32_t)rs.rows;
-    ctx->last_gather_ms = 0.f;
-    ctx->last_total_ms = 0.f;
-    return VRT_OK;
+    vrt_block b = {};
+    b.strip_rows = strip_rows;
+    b.first_strip = first_strip;
+    b.strip_stride = strip_stride;
+    b.n_strips = n_strips;
+    return render_tile(ctx, params, b, kStripsOnly, device_rgba, hip_stream);
 }
 
 int vrt_render_block(vrt_ctx* ctx, const vrt_params* params, const vrt_block* block, void* device_rgba, void* hip_stream) {
@@ -898,34 +970,17 @@ int vrt_render_block(vrt_ctx* ctx, const vrt_params* params, const vrt_block* bl
             return VRT_ERR_UNSUPPORTED;
     }
     RowSet rs;
-    if (block->strip_rows > 0) {
-        if (block->strip_stride < 1 || block->first_strip < 0 || block->first_strip >= block->strip_stride || block->n_strips < 0 ||
-            (long long)block->n_strips * block->strip_rows > 16384)
-            return VRT_ERR_INVALID;
-        rs.rows = block->n_strips * block->strip_rows;
-        rs.strip_rows = block->strip_rows;
-        rs.strip_first = block->first_strip;
-        rs.strip_stride = block->strip_stride;
-    } else {
-        if (block->strip_rows < 0 || block->row0 < 0 || block->rows < 0 || block->row0 + block->rows > params->height) return VRT_ERR_INVALID;
-        rs.row0 = block->row0;
-        rs.rows = block->rows;
-    }
-    const size_t frame_bytes = (size_t)rs.rows * (size_t)params->width * ((params->flags & VRT_FLAG_OUTPUT_RGBA8) ? 4 : 16);
-    const size_t pixel_bytes = (params->flags & VRT_FLAG_OUTPUT_RGBA8) ? 4 : 16;
-    if (block->frame_stride_bytes < frame_bytes || block->frame_stride_bytes % pixel_bytes != 0) return VRT_ERR_INVALID;
+    if (row_set(*block, params->height, kRowsOrStrips, rs) != VRT_OK) return VRT_ERR_INVALID;
+    const size_t frame_bytes = (size_t)rs.rows * (size_t)params->width * pixel_bytes(params->flags);
+    if (block->frame_stride_bytes < frame_bytes || block->frame_stride_bytes % pixel_bytes(params->flags) != 0) return VRT_ERR_INVALID;
     DeviceState& D = ctx->dev[0];
     HIP_TRY(hipSetDevice(D.ordinal));
     hipStream_t stream = static_cast<hipStream_t>(hip_stream);
-    /* ONE launch per kMaxBlockFrames frames (grid.y = frame; only the camera differs between the frames, it travels in the
-       kernarg): the dispatcher back-fills the wave slots a frame's latency-bound tail leaves empty with the next frame's waves.
-       VRT_FLAG_BLOCK_PER_FRAME: one launch per frame, back to back (what this entry point did before; A/B and tests) */
-    /* up to kMaxBlockFrames frames the cameras travel in the kernarg segment; a larger block is still ONE launch, its camera records
-       copied to the device ahead of it on the stream (a launch's latency-bound tail is paid once per launch) — unless the stream is
-       being captured into a graph: then launches of kernarg size */
-    hipStreamCaptureStatus capture = hipStreamCaptureStatusNone;
-    if (stream != nullptr && hipStreamIsCapturing(stream, &capture) != hipSuccess) capture = hipStreamCaptureStatusNone;
-    int chunk = (params->flags & VRT_FLAG_BLOCK_PER_FRAME) ? 1 : (capture != hipStreamCaptureStatusNone || block->n_frames <= kMaxBlockFrames) ? kMaxBlockFrames : kMaxLaunchFrames;
+    /* ONE launch (grid.y = frame): the dispatcher back-fills the wave slots a frame's latency-bound tail leaves empty with the next frame's
+       waves, and the tail is paid once per launch.  Up to kMaxBlockFrames frames the cameras travel in the kernarg segment; a larger block
+       has its camera records copied to the device ahead of it on the stream — unless the stream is being captured into a graph: then
+       launches of kernarg size.  VRT_FLAG_BLOCK_PER_FRAME: one launch per frame, back to back (A/B and tests) */
+    int chunk = (params->flags & VRT_FLAG_BLOCK_PER_FRAME) ? 1 : (block->n_frames <= kMaxBlockFrames || capturing(stream)) ? kMaxBlockFrames : kMaxLaunchFrames;
     {   /* the full closest hit in passes keeps 20 bytes per pixel of the launch's tiles between its passes: at most kPassBytesMax per launch */
         const size_t per_frame = (size_t)((params->width + 15) / 16) * (size_t)((rs.rows + 15) / 16) * 256 * (sizeof(HitRecord) + sizeof(unsigned));
         const ClosestHitForm form = closest_hit_form(ctx, params, block->scenes, block->n_frames);
@@ -943,52 +998,38 @@ int vrt_render_block(vrt_ctx* ctx, const vrt_params* params, const vrt_block* bl
     }
     vrt_params q = *params;
     for (int f = 0; f < block->n_frames; f += chunk) {
-        const int n = std::min(chunk, block->n_frames - f);
+        LaunchFrames fr;
+        fr.n = std::min(chunk, block->n_frames - f);
+        fr.cams = block->cameras ? block->cameras + f : nullptr;
+        fr.stride = (size_t)block->frame_stride_bytes;
+        fr.scenes = block->scenes ? block->scenes + f : nullptr;
         /* per-frame launches: the block's first frame is its timing sample (an event pair costs 5-7 us of queue time) */
         q.flags = (f == 0 || chunk > 1) ? params->flags : (params->flags | VRT_FLAG_NO_TIMING);
-        const int ring = (int)(ctx->launches % kRing);
         rc = enqueue_rows(ctx, D, &q, rs, reinterpret_cast<float*>(static_cast<char*>(device_rgba) + (size_t)f * block->frame_stride_bytes), stream,
-                          ring, nullptr, n, block->cameras ? block->cameras + f : nullptr, (size_t)block->frame_stride_bytes,
-                          block->scenes ? block->scenes + f : nullptr);
+                          (int)(ctx->launches % kRing), fr);
         if (rc != VRT_OK) return rc;
-        ctx->launches++;
+        note_launch(ctx, 1, params->width, rs.rows);
     }
-    ctx->last_devices = 1;
-    ctx->last_w = (uint32_t)params->width;
-    ctx->last_h = (uint32_t)rs.rows;
-    ctx->last_gather_ms = 0.f;
-    ctx->last_total_ms = 0.f;
     return VRT_OK;
 }
 
 int vrt_render_block_host(vrt_ctx* ctx, const vrt_params* params, const vrt_block* block, const void** host_frames) {
     if (!ctx || !params || !block || !host_frames || ctx->dev.size() != 1) return VRT_ERR_INVALID;
     if (params->width <= 0 || params->height <= 0 || block->n_frames < 1 || block->n_frames > kMaxLaunchFrames) return VRT_ERR_INVALID;
-    const long long rows = block->strip_rows > 0 ? (long long)block->n_strips * block->strip_rows : (long long)block->rows;
-    if (block->n_strips < 0 || rows < 0 || rows > 16384) return VRT_ERR_INVALID;
-    const size_t frame_bytes = (size_t)rows * (size_t)params->width * ((params->flags & VRT_FLAG_OUTPUT_RGBA8) ? 4 : 16);
+    RowSet rs; /* (its row count only: vrt_render_block checks the rest) */
+    if (row_set(*block, params->height, kCountOnly, rs) != VRT_OK) return VRT_ERR_INVALID;
+    const size_t frame_bytes = (size_t)rs.rows * (size_t)params->width * pixel_bytes(params->flags);
     const size_t need = std::max<size_t>(frame_bytes * (size_t)block->n_frames, 16);
     if (need > ((size_t)4 << 30)) return VRT_ERR_INVALID;
-    { /* refuse bad parameters BEFORE the block buffers are touched */
-        const int rc = check_params(ctx, params, block->scenes != nullptr);
-        if (rc != VRT_OK) return rc;
-    }
+    int rc = check_params(ctx, params, block->scenes != nullptr); /* refuse bad parameters BEFORE the block buffers are touched */
+    if (rc != VRT_OK) return rc;
     DeviceState& D = ctx->dev[0];
     HIP_TRY(hipSetDevice(D.ordinal));
-    if (D.blockfb_bytes < need) {
-        HIP_TRY(hipStreamSynchronize(D.stream));
-        if (D.d_blockfb) HIP_TRY(hipFree(D.d_blockfb));
-        if (D.h_blockfb) HIP_TRY(hipHostFree(D.h_blockfb));
-        D.d_blockfb = D.h_blockfb = nullptr;
-        D.blockfb_bytes = 0;
-        HIP_TRY(hipMalloc(&D.d_blockfb, need));
-        HIP_TRY(hipHostMalloc(&D.h_blockfb, need, hipHostMallocDefault));
-        D.blockfb_bytes = need;
-    }
-    if (!D.copy_stream) {
-        HIP_TRY(hipStreamCreateWithFlags(&D.copy_stream, hipStreamNonBlocking));
-        HIP_TRY(hipEventCreateWithFlags(&D.part_done, hipEventDisableTiming));
-    }
+    if (D.d_blockfb.cap < need || D.h_blockfb.cap < need) HIP_TRY(hipStreamSynchronize(D.stream)); /* (nothing reads the buffers that go) */
+    rc = ensure_buffer(D.d_blockfb, need);
+    if (rc == VRT_OK) rc = ensure_pinned_buffer(D.h_blockfb, need);
+    if (rc == VRT_OK) rc = ensure_copy_stream(D);
+    if (rc != VRT_OK) return rc;
     /* In parts: the copy of one part (its own stream) runs under the march of the next.  The march is ~4x faster than the copy over
        PCIe (1080p RGBA8: 0.04 against 0.16 ms per frame), so what the parts buy is that the first frames do not wait for the last. */
     const int part = block->n_frames <= 32 ? block->n_frames : 32;
@@ -999,16 +1040,16 @@ int vrt_render_block_host(vrt_ctx* ctx, const vrt_params* params, const vrt_bloc
         b.frame_stride_bytes = frame_bytes;
         if (b.cameras) b.cameras += f;
         if (b.scenes) b.scenes += f;
-        char* dst = static_cast<char*>(D.d_blockfb) + (size_t)f * frame_bytes;
-        const int rc = vrt_render_block(ctx, params, &b, dst, D.stream);
+        char* dst = static_cast<char*>(D.d_blockfb.p) + (size_t)f * frame_bytes;
+        rc = vrt_render_block(ctx, params, &b, dst, D.stream);
         if (rc != VRT_OK) return rc;
         HIP_TRY(hipEventRecord(D.part_done, D.stream));
         HIP_TRY(hipStreamWaitEvent(D.copy_stream, D.part_done, 0));
-        HIP_TRY(hipMemcpyAsync(static_cast<char*>(D.h_blockfb) + (size_t)f * frame_bytes, dst, frame_bytes * (size_t)n, hipMemcpyDeviceToHost, D.copy_stream));
+        HIP_TRY(hipMemcpyAsync(static_cast<char*>(D.h_blockfb.p) + (size_t)f * frame_bytes, dst, frame_bytes * (size_t)n, hipMemcpyDeviceToHost, D.copy_stream));
     }
     HIP_TRY(hipStreamSynchronize(D.copy_stream));
     HIP_TRY(hipStreamSynchronize(D.stream));
-    *host_frames = D.h_blockfb;
+    *host_frames = D.h_blockfb.p;
     return VRT_OK;
 }
 
@@ -1017,7 +1058,7 @@ int vrt_render(vrt_ctx* ctx, const vrt_params* params, float* host_rgba_or_null)
     if (rc != VRT_OK) return rc;
     const int n = (int)ctx->dev.size();
     const int W = params->width, H = params->height;
-    const size_t row_bytes = (size_t)W * ((params->flags & VRT_FLAG_OUTPUT_RGBA8) ? 4 : 4 * sizeof(float));
+    const size_t row_bytes = (size_t)W * pixel_bytes(params->flags);
     auto t0 = std::chrono::steady_clock::now();
 
     /* One device: the whole frame.  Several: 8-row strips (one row of waves, what bench.py's ranks use: samples max / mean over 8
@@ -1030,48 +1071,25 @@ int vrt_render(vrt_ctx* ctx, const vrt_params* params, float* host_rgba_or_null)
 
     for (int g = 0; g < n; g++) {
         DeviceState& D = ctx->dev[(size_t)g];
-        const size_t need = std::max<size_t>((size_t)tile_rows * row_bytes, 16);
         HIP_TRY(hipSetDevice(D.ordinal));
-        if (D.fb_bytes < need) {
-            if (D.fb) HIP_TRY(hipFree(D.fb));
-            D.fb = nullptr;
-            D.fb_bytes = 0;
-            HIP_TRY(hipMalloc(&D.fb, need));
-            D.fb_bytes = need;
-        }
+        rc = ensure_buffer(D.fb, std::max<size_t>((size_t)tile_rows * row_bytes, 16));
+        if (rc != VRT_OK) return rc;
     }
     if (n > 1) {
-        const size_t need = (size_t)H * row_bytes;
         HIP_TRY(hipSetDevice(ctx->dev[0].ordinal));
-        if (ctx->gather_bytes < need) {
-            if (ctx->gather) HIP_TRY(hipFree(ctx->gather));
-            ctx->gather = nullptr;
-            ctx->gather_bytes = 0;
-            HIP_TRY(hipMalloc(&ctx->gather, need));
-            ctx->gather_bytes = need;
-        }
+        rc = ensure_buffer(ctx->gather, (size_t)H * row_bytes);
+        if (rc != VRT_OK) return rc;
     }
 
     const int ring = (int)(ctx->launches % kRing);
     for (int g = 0; g < n; g++) {
         DeviceState& D = ctx->dev[(size_t)g];
         HIP_TRY(hipSetDevice(D.ordinal));
-        RowSet rs;
-        if (n > 1) {
-            rs.rows = tile_rows;
-            rs.strip_rows = kStripRows;
-            rs.strip_first = g;
-            rs.strip_stride = n;
-        } else {
-            rs.rows = H;
-        }
-        rc = enqueue_rows(ctx, D, params, rs, D.fb, D.stream, ring);
+        const RowSet rs = n > 1 ? RowSet{0, tile_rows, kStripRows, g, n} : RowSet{0, H, 0, 0, 0}; /* its strips g, g + n, ...; or the whole frame */
+        rc = enqueue_rows(ctx, D, params, rs, static_cast<float*>(D.fb.p), D.stream, ring);
         if (rc != VRT_OK) return rc;
     }
-    ctx->launches++;
-    ctx->last_devices = n;
-    ctx->last_w = (uint32_t)W;
-    ctx->last_h = (uint32_t)H;
+    note_launch(ctx, n, W, H);
 
     float gather_ms = 0.f;
     if (n > 1) {
@@ -1087,8 +1105,8 @@ int vrt_render(vrt_ctx* ctx, const vrt_params* params, float* host_rgba_or_null)
             HIP_TRY(hipSetDevice(D.ordinal));
             int whole = 0; /* strips of this device that lie wholly inside the frame */
             while (whole < strips_per && ((whole * n + g) + 1) * kStripRows <= H) whole++;
-            char* dst = reinterpret_cast<char*>(ctx->gather) + (size_t)g * strip_bytes;
-            const char* src = reinterpret_cast<const char*>(D.fb);
+            char* dst = static_cast<char*>(ctx->gather.p) + (size_t)g * strip_bytes;
+            const char* src = static_cast<const char*>(D.fb.p);
             /* the strided 2D copy needs device 0's memory mapped into this device (checked at vrt_create: an asynchronous failure of an
                unmapped peer copy would only surface at the final synchronise); VRT_GATHER_PER_STRIP=1 forces the per-strip path.
                (Unverified on more than one physical GPU in any round: no multi-GPU box was available.) */
@@ -1103,7 +1121,7 @@ int vrt_render(vrt_ctx* ctx, const vrt_params* params, float* host_rgba_or_null)
             }
             const int frame_row = (whole * n + g) * kStripRows;
             if (whole < strips_per && frame_row < H) /* the frame's last, partial strip */
-                HIP_TRY(hipMemcpyPeerAsync(reinterpret_cast<char*>(ctx->gather) + (size_t)frame_row * row_bytes, ctx->dev[0].ordinal,
+                HIP_TRY(hipMemcpyPeerAsync(static_cast<char*>(ctx->gather.p) + (size_t)frame_row * row_bytes, ctx->dev[0].ordinal,
                                            src + (size_t)whole * strip_bytes, D.ordinal, (size_t)(H - frame_row) * row_bytes, D.stream));
             if (g > 0) {
                 if (!D.joined) HIP_TRY(hipEventCreateWithFlags(&D.joined, hipEventDisableTiming));
@@ -1124,13 +1142,13 @@ int vrt_render(vrt_ctx* ctx, const vrt_params* params, float* host_rgba_or_null)
         gather_ms = std::max(0.f, all_ms - march_ms);
         if (host_rgba_or_null) {
             HIP_TRY(hipSetDevice(ctx->dev[0].ordinal));
-            HIP_TRY(hipMemcpy(host_rgba_or_null, ctx->gather, (size_t)H * row_bytes, hipMemcpyDeviceToHost));
+            HIP_TRY(hipMemcpy(host_rgba_or_null, ctx->gather.p, (size_t)H * row_bytes, hipMemcpyDeviceToHost));
         }
     } else {
         DeviceState& D = ctx->dev[0];
         HIP_TRY(hipSetDevice(D.ordinal));
         if (host_rgba_or_null)
-            HIP_TRY(hipMemcpyAsync(host_rgba_or_null, D.fb, (size_t)H * row_bytes, hipMemcpyDeviceToHost, D.stream));
+            HIP_TRY(hipMemcpyAsync(host_rgba_or_null, D.fb.p, (size_t)H * row_bytes, hipMemcpyDeviceToHost, D.stream));
         HIP_TRY(hipStreamSynchronize(D.stream));
     }
     ctx->last_gather_ms = gather_ms;
@@ -1146,11 +1164,7 @@ int vrt_render_begin(vrt_ctx* ctx, const vrt_params* params, int slot) {
     FrameSlot& S = D.slot[slot];
     if (S.busy) return VRT_ERR_NOT_READY; /* vrt_render_end(slot) first */
     HIP_TRY(hipSetDevice(D.ordinal));
-    const size_t need = (size_t)params->width * params->height * ((params->flags & VRT_FLAG_OUTPUT_RGBA8) ? 4 : 16);
-    if (!D.copy_stream) {
-        HIP_TRY(hipStreamCreateWithFlags(&D.copy_stream, hipStreamNonBlocking));
-        HIP_TRY(hipEventCreateWithFlags(&D.part_done, hipEventDisableTiming));
-    }
+    const size_t need = (size_t)params->width * params->height * pixel_bytes(params->flags);
     if (!D.flight_stream) HIP_TRY(hipStreamCreateWithFlags(&D.flight_stream, hipStreamNonBlocking));
     if (!S.done) {
         /* ONE march stream and ONE copy stream for all the frame slots (a slot owns its buffers and two events): the marches run back
@@ -1163,15 +1177,10 @@ int vrt_render_begin(vrt_ctx* ctx, const vrt_params* params, int slot) {
         HIP_TRY(hipMalloc(&S.d_scene, sizeof(SceneArrays)));
         HIP_TRY(hipHostMalloc(reinterpret_cast<void**>(&S.h_scene), sizeof(SceneArrays), hipHostMallocDefault));
     }
-    if (S.fb_bytes < need) {
-        if (S.d_fb) HIP_TRY(hipFree(S.d_fb));
-        if (S.h_fb) HIP_TRY(hipHostFree(S.h_fb));
-        S.d_fb = S.h_fb = nullptr;
-        S.fb_bytes = 0;
-        HIP_TRY(hipMalloc(&S.d_fb, need));
-        HIP_TRY(hipHostMalloc(&S.h_fb, need, hipHostMallocDefault));
-        S.fb_bytes = need;
-    }
+    rc = ensure_copy_stream(D);
+    if (rc == VRT_OK) rc = ensure_buffer(S.d_fb, need); /* (the slot is not busy: nothing reads its frames) */
+    if (rc == VRT_OK) rc = ensure_pinned_buffer(S.h_fb, need);
+    if (rc != VRT_OK) return rc;
     /* snapshot of everything the kernel dereferences besides the volumes themselves: later vrt_scene_set /
        vrt_volume_set_* calls do not reach a frame that is already in flight */
     for (int i = 0; i < VRT_MAX_VOLUMES; i++) {
@@ -1184,22 +1193,17 @@ int vrt_render_begin(vrt_ctx* ctx, const vrt_params* params, int slot) {
     memcpy(S.h_scene->spot, ctx->spot, sizeof S.h_scene->spot);
     HIP_TRY(hipMemcpyAsync(S.d_scene, S.h_scene, sizeof(SceneArrays), hipMemcpyHostToDevice, S.stream));
     const int ring = (int)(ctx->launches % kRing);
-    RowSet rs;
-    rs.rows = params->height;
-    rc = enqueue_rows(ctx, D, params, rs, static_cast<float*>(S.d_fb), S.stream, ring, S.d_scene);
+    LaunchFrames fr;
+    fr.snapshot = S.d_scene;
+    rc = enqueue_rows(ctx, D, params, RowSet{0, params->height, 0, 0, 0}, static_cast<float*>(S.d_fb.p), S.stream, ring, fr);
     if (rc != VRT_OK) return rc;
     HIP_TRY(hipEventRecord(S.marched, S.stream));
     HIP_TRY(hipStreamWaitEvent(D.copy_stream, S.marched, 0));
-    HIP_TRY(hipMemcpyAsync(S.h_fb, S.d_fb, need, hipMemcpyDeviceToHost, D.copy_stream));
+    HIP_TRY(hipMemcpyAsync(S.h_fb.p, S.d_fb.p, need, hipMemcpyDeviceToHost, D.copy_stream));
     HIP_TRY(hipEventRecord(S.done, D.copy_stream));
     S.busy = true;
     S.ring = ring;
-    ctx->launches++;
-    ctx->last_devices = 1;
-    ctx->last_w = (uint32_t)params->width;
-    ctx->last_h = (uint32_t)params->height;
-    ctx->last_gather_ms = 0.f;
-    ctx->last_total_ms = 0.f;
+    note_launch(ctx, 1, params->width, params->height);
     return VRT_OK;
 }
 
@@ -1211,7 +1215,7 @@ int vrt_render_end(vrt_ctx* ctx, int slot, const void** host_pixels) {
     HIP_TRY(hipSetDevice(D.ordinal));
     HIP_TRY(hipEventSynchronize(S.done));
     S.busy = false;
-    if (host_pixels) *host_pixels = S.h_fb;
+    if (host_pixels) *host_pixels = S.h_fb.p;
     return VRT_OK;
 }
 
@@ -1235,7 +1239,7 @@ int vrt_last_timing(vrt_ctx* ctx, vrt_timing* out) {
         kernel_ms = std::max(kernel_ms, ms);
         std::vector<unsigned> rec((size_t)D.last_blocks * 4 * kStatRecord);
         if (D.last_blocks > 0)
-            HIP_TRY(hipMemcpy(rec.data(), D.d_stats[D.last_slot] + (size_t)(D.last_frames - 1) * rec.size(), rec.size() * sizeof(unsigned),
+            HIP_TRY(hipMemcpy(rec.data(), D.launch[D.last_slot].d_stats + (size_t)(D.last_frames - 1) * rec.size(), rec.size() * sizeof(unsigned),
                               hipMemcpyDeviceToHost));
         for (size_t w = 0; w < (size_t)D.last_blocks * 4; w++)
             for (int k = 0; k < kStatWords; k++) tot[k] += rec[w * kStatRecord + k];
@@ -1299,7 +1303,7 @@ long long vrt_debug_wave_records(vrt_ctx* ctx, int which, uint32_t* out, long lo
     if (out && max_words > 0) {
         HIP_TRY(hipSetDevice(D.ordinal));
         HIP_TRY(hipDeviceSynchronize());
-        const uint32_t* src = (diag ? D.d_diag : D.d_stats[D.last_slot]) + (whole ? 0 : (size_t)(D.last_frames - 1) * (size_t)frame_words);
+        const uint32_t* src = (diag ? D.d_diag : D.launch[D.last_slot].d_stats) + (whole ? 0 : (size_t)(D.last_frames - 1) * (size_t)frame_words);
         HIP_TRY(hipMemcpy(out, src, sizeof(uint32_t) * (size_t)std::min(words, max_words), hipMemcpyDeviceToHost));
     }
     return words;
