@@ -152,6 +152,18 @@ def test_each_call_kind_on_its_own(res, fmt):
     assert recorded >= (7 if res >= 3 else 3)
 
 
+@pytest.mark.parametrize("fmt", X.FORMATS)
+@pytest.mark.parametrize("res", [1, 3])  # N = 3: every tile is partial; 9: one full tile and a last tile one sample thick
+def test_each_call_kind_on_its_own_over_two_devices(res, fmt):
+    """The context is fresh, so every scratch and history buffer of both devices is allocated by the first call of its kind: each call
+    has to have all of them, on both devices, before it writes a sample on either."""
+    steps = kinds_program(res, fmt)
+    with v.VHipRenderer(devices=(0, 0)) as r:
+        recorded = run_with_history(r, f"kinds at resolution {res}, two devices", steps, devices=(0, 1))
+    print(f"resolution {res}, format {fmt}, two devices: {recorded} of 9 edits recorded an entry")
+    assert recorded >= (7 if res >= 3 else 3)
+
+
 def test_a_whole_grid_fill_of_65_cubed():
     """4913 tiles in the grid, of which the fill's written box meets hundreds: many workgroups of four waves, one wave per tile."""
     case = volume_case("6", _abi.FORMAT_F32)

@@ -158,27 +158,18 @@ int vrt_volume_apply_brushes(vrt_ctx* ctx, int slot, int n_rec, const vrt_brush*
         }
     }
     if (list.n == 0) return VRT_OK;
-    const EditBox foot = derived_boxes(h, ulo, uhi).samples;
     const bool texel16 = h.format == VRT_FORMAT_TEXEL16;
-    int rc = quiesce(ctx);
-    if (rc != VRT_OK) return rc;
-    if ((rc = history_capture(ctx, slot, foot)) != VRT_OK) return rc;
-    bool changed = false;
-    for (size_t di = 0; di < ctx->dev.size(); di++) {
-        DeviceState& D = ctx->dev[di];
-        HIP_TRY(hipSetDevice(D.ordinal));
+    Edit e;
+    e.slot = slot;
+    e.foot = derived_boxes(h, ulo, uhi).samples;
+    e.rebuild = Edit::kDensityWrites; /* nothing written, or only material ids, and no derived structure changes */
+    e.write = [&](DeviceState& D, size_t) -> int {
         DeviceVolume& v = D.vol[slot];
-        HIP_TRY(launch_brush_region(list, texel16, v.dense, v.material, N, foot, D.d_brush, D.stream));
-        Written got;
-        rc = read_report(D, N, got);
-        if (rc != VRT_OK) return rc;
-        if ((rc = history_record(ctx, D, slot, got.lo, got.hi)) != VRT_OK) return rc;
-        if (di == 0 && result) *result = brush_result(got);
-        /* the density writes count: nothing written, or only material ids, and no derived structure changes */
-        rc = rebuild_written(ctx, D, slot, got.lo, got.hi, got.high, changed);
-        if (rc != VRT_OK) return rc;
-    }
-    return finish_edit(ctx, changed);
+        HIP_TRY(launch_brush_region(list, texel16, v.dense, v.material, N, e.foot, D.d_brush, D.stream));
+        return VRT_OK;
+    };
+    e.reported = [&](const Written& got) { if (result) *result = brush_result(got); };
+    return run_edit(ctx, e);
 }
 
 }  // extern "C"

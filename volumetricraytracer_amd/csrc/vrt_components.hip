@@ -409,7 +409,7 @@ int vrt_volume_components(vrt_ctx* ctx, int slot, const vrt_components* rec, vrt
     for (int a = 0; a < 3; a++) out.lo[a] = N, out.hi[a] = -1;
     int rc = quiesce(ctx);
     if (rc != VRT_OK) return rc;
-    for (auto& D : ctx->dev) { /* every allocation comes before any write */
+    for (auto& D : ctx->dev) { /* the read phase allocates all the call needs: its run_edit has nothing left to prepare */
         HIP_TRY(hipSetDevice(D.ordinal));
         rc = ensure_buffer(D.buf[kBufCompLabels], components_scratch_bytes(N));
         if (rc != VRT_OK) return rc;
@@ -483,28 +483,26 @@ int vrt_volume_components(vrt_ctx* ctx, int slot, const vrt_components* rec, vrt
             out.listed++;
         }
     }
-    const int zero[3] = {0, 0, 0}, last[3] = {N - 1, N - 1, N - 1}; /* only a call that removes something has a footprint: the whole grid */
-    if (out.removed > 0 && (rc = history_capture(ctx, slot, derived_boxes(h, zero, last).samples)) != VRT_OK) return rc;
-    bool changed = false;
-    for (size_t di = 0; out.removed > 0 && di < ctx->dev.size(); di++) {
-        DeviceState& D = ctx->dev[di];
-        HIP_TRY(hipSetDevice(D.ordinal));
-        DeviceVolume& v = D.vol[slot];
-        HIP_TRY(launch_components_apply(texel16, v.dense, v.material, N, D.buf[kBufCompLabels].p, D.buf[kBufCompTable].p, how.mode, how.a, how.b, rec->gap,
-                                        rec->material, D.d_brush, D.stream));
-        Written got;
-        rc = read_report(D, N, got);
-        if (rc != VRT_OK) return rc;
-        if ((rc = history_record(ctx, D, slot, got.lo, got.hi)) != VRT_OK) return rc;
-        if (di == 0) {
+    if (out.removed > 0) { /* only a call that removes something is an edit; its footprint is the whole grid */
+        const int zero[3] = {0, 0, 0}, last[3] = {N - 1, N - 1, N - 1};
+        Edit e;
+        e.slot = slot;
+        e.foot = derived_boxes(h, zero, last).samples;
+        e.rebuild = Edit::kWrites; /* every written sample is a density write */
+        e.write = [&](DeviceState& D, size_t) -> int {
+            DeviceVolume& v = D.vol[slot];
+            HIP_TRY(launch_components_apply(texel16, v.dense, v.material, N, D.buf[kBufCompLabels].p, D.buf[kBufCompTable].p, how.mode, how.a, how.b,
+                                            rec->gap, rec->material, D.d_brush, D.stream));
+            return VRT_OK;
+        };
+        e.reported = [&](const Written& got) {
             for (int a = 0; a < 3; a++) out.lo[a] = got.lo[a], out.hi[a] = got.hi[a];
             out.written = got.low;
-        }
-        rc = rebuild_written(ctx, D, slot, got.lo, got.hi, got.low, changed); /* every written sample is a density write */
-        if (rc != VRT_OK) return rc;
+        };
+        if ((rc = run_edit(ctx, e)) != VRT_OK) return rc;
     }
     if (result) *result = out;
-    return finish_edit(ctx, changed);
+    return VRT_OK;
 }
 
 }  // extern "C"

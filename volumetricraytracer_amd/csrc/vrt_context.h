@@ -1,12 +1,13 @@
 /* vrt_context.h — the host runtime's state and the few functions more than one unit calls: the context and what it keeps per device and
-   per slot, and the skeleton every volume edit call follows, which the calls' own units (vrt_<call>.hip) build their drivers
-   from.  What only one unit needs stays in that unit. */
+   per slot, and run_edit, which owns the sequence of every volume edit call: a call's own unit (vrt_<call>.hip) checks its
+   arguments and hands run_edit an Edit, the parts that differ.  What only one unit needs stays in that unit. */
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stddef.h>
 #include <stdint.h>
 #include <stdio.h>
 
+#include <functional>
 #include <vector>
 
 #include "../../include/vrt.h"
@@ -61,10 +62,6 @@ struct HostHistory {
     uint64_t max_bytes = 0;
     std::vector<uint64_t> undo, redo; /* tiles per entry */
     uint64_t dropped = 0;
-    /* the edit call in progress: its footprint sits in every device's kBufHistory (history_capture), until history_record has seen the
-       last device; `lost`: the call has nothing (more) to record — no bit changed, or its entry went with the whole history */
-    bool captured = false, lost = false;
-    EditBox foot = {{0, 0, 0}, {0, 0, 0}};
     uint64_t tiles() const {
         uint64_t n = 0;
         for (uint64_t t : undo) n += t;
@@ -272,34 +269,63 @@ int free_device_palette(DeviceState& D, int slot);
 /* ---- What the volume edit calls share (defined in vrt_slots.hip) ---- */
 /* The caller's sample box: origin + size, or (both NULL, where the call allows it) the whole grid, as its first and last sample. */
 int clip_box(int N, const int* origin, const int* size, int lo[3], int hi[3]);
-/* Once per call, ahead of the first write: waits for what is enqueued on every device and gives each its report records. */
-int quiesce(vrt_ctx* ctx);
-/* A slot whose history is on (both do nothing otherwise).  After quiesce and ahead of the first write: the samples of the call's footprint
-   (grid order) copied aside on every device; VRT_ERR_OOM, and nothing written, when a device has no memory for that. */
-int history_capture(vrt_ctx* ctx, int slot, const EditBox& foot);
-/* After read_report, per device: the tiles of the xyz box lo..hi (what the launch reported it wrote) that differ in bits from the copy
-   become the device's record of a new undo entry; the first device also keeps the host's books (redo emptied, the limits applied).
-   A box with lo > hi, or one without a changed tile, records nothing. */
-int history_record(vrt_ctx* ctx, DeviceState& D, int slot, const int lo[3], const int hi[3]);
-/* Frees every entry of the slot on every device; the limits stay.  counted: the entries count as dropped. */
-void history_drop(vrt_ctx* ctx, int slot, bool counted);
-/* Drops the oldest undo entries (then, with none left, the redo entries furthest ahead) until the slot's limits hold. */
-void history_trim(vrt_ctx* ctx, int slot);
-struct Written {
-    int lo[3], hi[3];
-    unsigned long long low, high;
-};
-/* What a launch reported on D's stream (one synchronisation): the written box in xyz and the two halves of `counts`. */
-int read_report(DeviceState& D, int N, Written& got);
-vrt_brush_result brush_result(const Written& got);
 struct DerivedBoxes {
     EditBox samples, cells, bricks;
 };
 /* The {x, z, y} boxes of samples, cells and bricks that an edit of the samples lo..hi (xyz, inclusive) touches. */
 DerivedBoxes derived_boxes(const HostVolume& h, const int lo_xyz[3], const int hi_xyz[3]);
-/* One device's samples are written: what the slot derives from them, recomputed over the xyz box lo..hi, unless `relevant` is 0. */
-int rebuild_written(vrt_ctx* ctx, DeviceState& D, int slot, const int lo[3], const int hi[3], unsigned long long relevant, bool& changed);
-/* After the last device: when something changed, the scene is stale and the volume table follows. */
-int finish_edit(vrt_ctx* ctx, bool changed);
+/* What a call wrote on one device: the written box in xyz and the two halves of the edit report's `counts`. */
+struct Written {
+    int lo[3], hi[3];
+    unsigned long long low, high;
+};
+vrt_brush_result brush_result(const Written& got);
+
+/* What differs between the edit calls; the sequence itself is run_edit's. */
+struct Edit {
+    int slot = 0;
+    EditBox foot = {{0, 0, 0}, {0, 0, 0}}; /* the samples the call may write: what a history copies aside */
+    bool records = true;                   /* the call becomes an entry of the slot's history (undo and redo do not) */
+    /* Which box is rebuilt, and what counts as relevant (nothing relevant: no rebuild). */
+    enum Rebuild {
+        kDensityWrites, /* the reported box, with the report's high half: brushes, warp, undo and redo */
+        kWrites,        /* the reported box, with its low half: stamp, smooth, fill, components */
+        kFootprint      /* `foot`, always, whatever was reported: redistance, update_region */
+    } rebuild = kWrites;
+    bool reports = true; /* `write` leaves an edit report; false (update_region): the written box is `foot` and its count */
+    /* Everything that can run out of memory.  May launch kernels that only read the volume, and may synchronise. */
+    std::function<int(DeviceState&, size_t di)> prepare;
+    /* The launches and copies that write samples and, where the call reports, the report. */
+    std::function<int(DeviceState&, size_t di)> write;
+    /* Device 0's report, for the caller's result record. */
+    std::function<void(const Written&)> reported;
+};
+/* One volume edit call, after its argument checks, in this order: quiesce; `prepare` on every device; on a slot whose history is on (and
+   e.records) the capture buffers of every device, then the capture copies; per device `write`, the report (or the footprint), the
+   history record, `reported` on device 0, the rebuild; then, when something changed, the scene is stale and the volume table follows.
+   The rule: every allocation comes before any write.  No `write` runs before every `prepare` and every history allocation has succeeded
+   on every device, so a VRT_ERR_OOM from there leaves the volume untouched on all of them. */
+int run_edit(vrt_ctx* ctx, const Edit& e);
+
+/* Once per call, ahead of the first write: waits for what is enqueued on every device and gives each its report records (run_edit; the
+   mesh and measure calls, which read a report without editing). */
+int quiesce(vrt_ctx* ctx);
+/* What a launch reported on D's stream (one synchronisation): the written box in xyz and the two halves of `counts`. */
+int read_report(DeviceState& D, int N, Written& got);
+
+/* ---- The edit history's share of run_edit (vrt_history.hip) ---- */
+/* One call's working state: `captured`, its footprint `foot` sits in every device's kBufHistory; `lost`, the call has nothing (more) to
+   record — no bit changed, or its entry went with the whole history. */
+struct HistoryCall {
+    bool captured = false, lost = false;
+    EditBox foot = {{0, 0, 0}, {0, 0, 0}};
+};
+/* A slot whose history is on (both do nothing otherwise).  Ahead of the first write: the capture buffer of every device, then the samples
+   of the footprint (grid order) copied aside on each; VRT_ERR_OOM, and nothing written, when a device has no memory for that. */
+int history_capture(vrt_ctx* ctx, int slot, const EditBox& foot, HistoryCall& call);
+/* After device di's write: the tiles of the xyz box lo..hi (what was written) that differ in bits from the copy become the device's record
+   of a new undo entry; device 0 also keeps the host's books (redo emptied, the limits applied).  A box with lo > hi, or one without a
+   changed tile, records nothing. */
+int history_record(vrt_ctx* ctx, size_t di, int slot, HistoryCall& call, const int lo[3], const int hi[3]);
 
 }  // namespace vrt

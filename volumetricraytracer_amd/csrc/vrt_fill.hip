@@ -189,7 +189,7 @@ extern "C" {
 /* vrt_volume_fill_enclosed: per device, the passable mask and the face seeds (launch_fill_mask), propagation rounds in batches of
  * kFillRoundsPerRead with one read of their flags per batch until a round labels nothing, then the edit of the samples left without a
  * label (launch_fill_apply), which reports like a brush launch; what the slot derives from the samples is recomputed over the written
- * box (rebuild_derived).  Afterwards every buffer equals what upload_volume builds from the filled volume. */
+ * box (rebuild_derived).  The scratch memory of every device is there before the first sample is written.  Afterwards every buffer equals what upload_volume builds from the filled volume. */
 int vrt_volume_fill_enclosed(vrt_ctx* ctx, int slot, float wall, int material, vrt_fill_result* result) {
     if (!ctx) return VRT_ERR_INVALID;
     if (!valid_slot(slot) || !ctx->vol[slot].used) return VRT_ERR_SLOT;
@@ -200,19 +200,18 @@ int vrt_volume_fill_enclosed(vrt_ctx* ctx, int slot, float wall, int material, v
     const bool texel16 = h.format == VRT_FORMAT_TEXEL16;
     /* a round that changes something labels at least one sample, so no run needs more rounds than the grid has samples */
     const unsigned long long round_cap = (unsigned long long)N * N * N + 1ull;
-    int rc = quiesce(ctx);
-    if (rc != VRT_OK) return rc;
     const int zero[3] = {0, 0, 0}, last[3] = {N - 1, N - 1, N - 1};
-    if ((rc = history_capture(ctx, slot, derived_boxes(h, zero, last).samples)) != VRT_OK) return rc;
-    bool changed = false;
-    for (size_t di = 0; di < ctx->dev.size(); di++) {
-        DeviceState& D = ctx->dev[di];
-        HIP_TRY(hipSetDevice(D.ordinal));
+    unsigned long long rounds = 0; /* of the device whose `write` ran last: device 0's when `reported` reads it */
+    Edit e;
+    e.slot = slot;
+    e.foot = derived_boxes(h, zero, last).samples;
+    e.rebuild = Edit::kWrites; /* every written sample is a density write */
+    e.prepare = [&](DeviceState& D, size_t) { return ensure_buffer(D.buf[kBufFill], fill_scratch_bytes(N)); };
+    /* mask and rounds write the scratch only; the volume's first write is launch_fill_apply */
+    e.write = [&](DeviceState& D, size_t) -> int {
         DeviceVolume& v = D.vol[slot];
-        rc = ensure_buffer(D.buf[kBufFill], fill_scratch_bytes(N));
-        if (rc != VRT_OK) return rc;
         HIP_TRY(launch_fill_mask(v.dense, texel16, N, D.buf[kBufFill].p, D.stream));
-        unsigned long long rounds = 0;
+        rounds = 0;
         for (bool settled = false; !settled;) {
             if (rounds >= round_cap) {
                 fprintf(stderr, "[vrt] vrt_volume_fill_enclosed: %llu rounds without settling on a grid of %d^3\n", rounds, N);
@@ -226,17 +225,14 @@ int vrt_volume_fill_enclosed(vrt_ctx* ctx, int slot, float wall, int material, v
             for (int f : flags) settled = settled || f == 0;
         }
         HIP_TRY(launch_fill_apply(texel16, v.dense, v.material, N, D.buf[kBufFill].p, wall, material, D.d_brush, D.stream));
-        Written got;
-        rc = read_report(D, N, got);
-        if (rc != VRT_OK) return rc;
-        if ((rc = history_record(ctx, D, slot, got.lo, got.hi)) != VRT_OK) return rc;
-        if (di == 0 && result)
+        return VRT_OK;
+    };
+    e.reported = [&](const Written& got) {
+        if (result)
             *result = vrt_fill_result{{got.lo[0], got.lo[1], got.lo[2]}, {got.hi[0], got.hi[1], got.hi[2]}, got.low,
                                       (uint32_t)std::min<unsigned long long>(rounds, 0xffffffffull), 0};
-        rc = rebuild_written(ctx, D, slot, got.lo, got.hi, got.low, changed);
-        if (rc != VRT_OK) return rc;
-    }
-    return finish_edit(ctx, changed);
+    };
+    return run_edit(ctx, e);
 }
 
 }  // extern "C"

@@ -1,9 +1,9 @@
 /* vrt_history.hip — vrt_volume_history, _history_info, _undo and _redo (include/vrt.h), kernels to driver: a slot's edit history, kept on
  * the device as the changed 4^3 tiles of every recorded call.  Three kernels.  Capture copies an edit's footprint aside before the edit
  * writes; compact, after it, finds the tiles of the written box that differ from the copy in bits and stores them as they were — both
- * launched by the two helpers every edit driver calls (history_capture, history_record: vrt_slots.hip); swap exchanges an entry's tiles
- * with the volume's, which is undo and redo alike.  Everything compares and copies bits: the kernels never read a density as a float.
- * The stacks and their limits are host bookkeeping (HostHistory, vrt_context.h). */
+ * launched by the two functions run_edit calls (history_capture, history_record: vrt_context.h); swap exchanges an entry's tiles with
+ * the volume's, which is undo and redo alike.  Everything compares and copies bits: the kernels never read a density as a float.
+ * The stacks and their limits are host bookkeeping (HostHistory, vrt_context.h), kept here too. */
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -14,7 +14,28 @@
 
 namespace vrt {
 
+/* A history tile is the aligned VRT_HISTORY_TILE^3 samples whose tile coordinates {x, z, y} make its key (tx * T + tz) * T + ty,
+   T = history_tiles_per_axis(N); a record holds `tiles` DHistoryTile in no particular order. */
+struct DHistoryTile {
+    uint32_t bits[64];  /* the stored density bits of sample (4 tx + (l >> 4), 4 tz + ((l >> 2) & 3), 4 ty + (l & 3)) at l; 0 beyond the grid */
+    uint8_t ids[64];
+    uint32_t key;
+    uint32_t pad_[3];
+};
+static_assert(sizeof(DHistoryTile) == VRT_HISTORY_TILE_BYTES, "vrt.h states this size");
+__host__ __device__ inline int history_tiles_per_axis(int N) { return (N + VRT_HISTORY_TILE - 1) / VRT_HISTORY_TILE; }
+
 namespace {
+
+/* The tiles that meet a sample box, as a box of tile coordinates. */
+EditBox history_tile_box(const EditBox& samples) {
+    EditBox t;
+    for (int a = 0; a < 3; a++) {
+        t.lo[a] = samples.lo[a] / VRT_HISTORY_TILE;
+        t.n[a] = (samples.lo[a] + samples.n[a] - 1) / VRT_HISTORY_TILE - t.lo[a] + 1;
+    }
+    return t;
+}
 
 constexpr size_t kCounterBytes = 16; /* counter 0: changed tiles (first pass); counter 1: places taken in the record (second pass) */
 
@@ -122,12 +143,12 @@ __global__ __launch_bounds__(256) void history_swap_kernel(DHistoryTile* __restr
 
 unsigned wave_blocks(size_t waves) { return (unsigned)((waves + 3) / 4); }
 
-}  // namespace
-
+/* scratch: history_scratch_bytes(foot) of device memory — two counters, then the footprint's bits and ids. */
 size_t history_scratch_bytes(const EditBox& foot) { return kCounterBytes + box_count(foot) * 5; }
 
-const unsigned* history_changed_tiles(const void* scratch) { return static_cast<const unsigned*>(scratch); }
+const unsigned* history_changed_tiles(const void* scratch) { return static_cast<const unsigned*>(scratch); } /* device memory: counter 0 */
 
+/* Zeroes the counters and copies the samples of `foot` into the scratch. */
 hipError_t launch_history_capture(const float* dense, const uint8_t* material, int N, const EditBox& foot, void* scratch, hipStream_t stream) {
     hipError_t e = hipMemsetAsync(scratch, 0, kCounterBytes, stream);
     if (e != hipSuccess) return e;
@@ -139,6 +160,9 @@ hipError_t launch_history_capture(const float* dense, const uint8_t* material, i
     return hipGetLastError();
 }
 
+/* One wave per tile of `tiles`: a tile with a sample whose bits or id differ from the scratch copy (samples outside `foot` were not
+   written) counts into counter 0 (record_or_null == nullptr), or takes the next of the record's `capacity` places, by counter 1, for
+   the 64 samples as they were. */
 hipError_t launch_history_compact(const float* dense, const uint8_t* material, int N, const EditBox& foot, void* scratch, const EditBox& tiles,
                                   void* record_or_null, unsigned capacity, hipStream_t stream) {
     const size_t n_tiles = box_count(tiles);
@@ -157,11 +181,120 @@ hipError_t launch_history_compact(const float* dense, const uint8_t* material, i
     return hipGetLastError();
 }
 
+/* One wave per tile of the record: record and volume exchange the tile's samples; the samples whose bits or id changed go into the edit
+   report (density changes in the high half).  slots: NOT zeroed here — the entries of one call add up. */
 hipError_t launch_history_swap(void* record, unsigned tiles, float* dense, uint8_t* material, int N, DBrushSlot* slots, hipStream_t stream) {
     if (tiles == 0) return hipSuccess;
     hipLaunchKernelGGL(history_swap_kernel, dim3(wave_blocks(tiles)), dim3(256), 0, stream, static_cast<DHistoryTile*>(record), tiles,
                        reinterpret_cast<uint32_t*>(dense), material, N, slots);
     return hipGetLastError();
+}
+
+/* ---- The host's books ----
+ * Frees one entry's record on every device that has it: the first of a stack, or all. */
+void free_records(vrt_ctx* ctx, int slot, bool redo, bool all) {
+    for (auto& D : ctx->dev) {
+        std::vector<void*>& stack = redo ? D.hist[slot].redo : D.hist[slot].undo;
+        if (stack.empty() || hipSetDevice(D.ordinal) != hipSuccess) continue;
+        for (size_t i = 0; i < (all ? stack.size() : 1); i++) (void)hipFree(stack[i]);
+        stack.erase(stack.begin(), all ? stack.end() : stack.begin() + 1);
+    }
+}
+
+/* Frees every entry of the slot on every device; the limits stay.  counted: the entries count as dropped. */
+void history_drop(vrt_ctx* ctx, int slot, bool counted) {
+    HostHistory& hh = ctx->hist[slot];
+    if (counted) hh.dropped += hh.undo.size() + hh.redo.size();
+    hh.undo.clear();
+    hh.redo.clear();
+    free_records(ctx, slot, false, true);
+    free_records(ctx, slot, true, true);
+}
+
+/* Drops the oldest undo entries (then, with none left, the redo entries furthest ahead) until the slot's limits hold. */
+void history_trim(vrt_ctx* ctx, int slot) {
+    HostHistory& hh = ctx->hist[slot];
+    while (hh.on && (hh.undo.size() > (size_t)hh.max_entries || hh.tiles() * VRT_HISTORY_TILE_BYTES > hh.max_bytes)) {
+        std::vector<uint64_t>& stack = hh.undo.empty() ? hh.redo : hh.undo; /* both stacks keep the entry to go at their front */
+        if (stack.empty()) break;
+        free_records(ctx, slot, &stack == &hh.redo, false);
+        stack.erase(stack.begin());
+        hh.dropped++;
+    }
+}
+
+}  // namespace
+
+/* ---- The history's share of run_edit ---- */
+int history_capture(vrt_ctx* ctx, int slot, const EditBox& foot, HistoryCall& call) {
+    call = HistoryCall();
+    if (!ctx->hist[slot].on) return VRT_OK;
+    for (auto& D : ctx->dev) {
+        HIP_TRY(hipSetDevice(D.ordinal));
+        int rc = ensure_buffer(D.buf[kBufHistory], history_scratch_bytes(foot));
+        if (rc != VRT_OK) return rc;
+    }
+    for (auto& D : ctx->dev) {
+        HIP_TRY(hipSetDevice(D.ordinal));
+        HIP_TRY(launch_history_capture(D.vol[slot].dense, D.vol[slot].material, ctx->vol[slot].N, foot, D.buf[kBufHistory].p, D.stream));
+    }
+    call.foot = foot;
+    call.captured = true;
+    return VRT_OK;
+}
+
+/* The first pass counts the changed tiles, the host sizes the record exactly, the second pass fills it.  Device 0 keeps the books for
+ * all: it empties the redo stack, pushes the entry and applies the limits; the others add their record of the same entry. */
+int history_record(vrt_ctx* ctx, size_t di, int slot, HistoryCall& call, const int lo[3], const int hi[3]) {
+    HostHistory& hh = ctx->hist[slot];
+    if (!hh.on || !call.captured) return VRT_OK;
+    if (call.lost || lo[0] > hi[0] || lo[1] > hi[1] || lo[2] > hi[2]) return VRT_OK;
+    DeviceState& D = ctx->dev[di];
+    const bool first = di == 0;
+    const HostVolume& h = ctx->vol[slot];
+    const DeviceVolume& v = D.vol[slot];
+    const EditBox tiles = history_tile_box(derived_boxes(h, lo, hi).samples);
+    void* scratch = D.buf[kBufHistory].p;
+    unsigned count = 0;
+    HIP_TRY(launch_history_compact(v.dense, v.material, h.N, call.foot, scratch, tiles, nullptr, 0u, D.stream));
+    HIP_TRY(hipMemcpyAsync(&count, history_changed_tiles(scratch), sizeof count, hipMemcpyDeviceToHost, D.stream));
+    HIP_TRY(hipStreamSynchronize(D.stream));
+    if (first) {
+        if (count == 0u) {
+            call.lost = true; /* no bit changed, on any device: nothing is recorded and the redo stack stays */
+            return VRT_OK;
+        }
+        hh.redo.clear();
+        free_records(ctx, slot, true, true);
+        if ((uint64_t)count * VRT_HISTORY_TILE_BYTES > hh.max_bytes) { /* larger than the history may be: everything goes, this entry too */
+            hh.dropped++;
+            call.lost = true;
+        } else {
+            hh.undo.push_back(count);
+        }
+    } else if (count != hh.undo.back()) {
+        fprintf(stderr, "[vrt] edit history: device %d changed %u tiles, the first device %llu\n", D.ordinal, count, (unsigned long long)hh.undo.back());
+        call.lost = true;
+    }
+    void* record = nullptr;
+    if (!call.lost) {
+        HIP_TRY(hipSetDevice(D.ordinal));
+        if (hipMalloc(&record, (size_t)count * VRT_HISTORY_TILE_BYTES) != hipSuccess) {
+            (void)hipGetLastError(); /* no memory for the record: the edit stands, the history does not */
+            call.lost = true;
+        }
+    }
+    if (call.lost) {
+        history_drop(ctx, slot, true);
+        return hipSetDevice(D.ordinal) == hipSuccess ? VRT_OK : VRT_ERR_HIP;
+    }
+    D.hist[slot].undo.push_back(record);
+    HIP_TRY(launch_history_compact(v.dense, v.material, h.N, call.foot, scratch, tiles, record, count, D.stream));
+    if (first) {
+        history_trim(ctx, slot);
+        HIP_TRY(hipSetDevice(D.ordinal));
+    }
+    return VRT_OK;
 }
 
 }  // namespace vrt
@@ -173,7 +306,7 @@ static_assert(sizeof(vrt_history_info) == 64, "vrt.h states this size");
 namespace {
 
 /* vrt_volume_undo (redo false) and vrt_volume_redo: the `steps` last entries of the stack asked for, last first, swapped on every
- * device into one edit report per device; then the rebuild over the reported box, and the entries change stacks. */
+ * device into one edit report per device; run_edit rebuilds over the reported box, and then the entries change stacks. */
 int step_history(vrt_ctx* ctx, int slot, int steps, bool redo, vrt_brush_result* result) {
     if (!ctx) return VRT_ERR_INVALID;
     if (!valid_slot(slot) || !ctx->vol[slot].used) return VRT_ERR_SLOT;
@@ -183,27 +316,23 @@ int step_history(vrt_ctx* ctx, int slot, int steps, bool redo, vrt_brush_result*
     if (!hh.on || steps < 1 || (size_t)steps > from.size()) return VRT_ERR_INVALID;
     const int N = ctx->vol[slot].N;
     if (result) *result = vrt_brush_result{{N, N, N}, {-1, -1, -1}, 0};
-    int rc = quiesce(ctx);
-    if (rc != VRT_OK) return rc;
-    bool changed = false;
-    for (size_t di = 0; di < ctx->dev.size(); di++) {
-        DeviceState& D = ctx->dev[di];
-        HIP_TRY(hipSetDevice(D.ordinal));
+    Edit e;
+    e.slot = slot;
+    e.records = false; /* a step through the history is no entry of it, so it has no footprint to copy aside either */
+    e.rebuild = Edit::kDensityWrites; /* nothing changed, or only material ids, and no derived structure changes */
+    e.write = [&](DeviceState& D, size_t) -> int {
         DeviceVolume& v = D.vol[slot];
         const std::vector<void*>& rec = redo ? D.hist[slot].redo : D.hist[slot].undo;
         HIP_TRY(clear_report(D.d_brush, D.stream));
         for (int k = 0; k < steps; k++) {
-            const size_t e = from.size() - 1 - (size_t)k;
-            HIP_TRY(launch_history_swap(rec[e], (unsigned)from[e], v.dense, v.material, N, D.d_brush, D.stream));
+            const size_t at = from.size() - 1 - (size_t)k;
+            HIP_TRY(launch_history_swap(rec[at], (unsigned)from[at], v.dense, v.material, N, D.d_brush, D.stream));
         }
-        Written got;
-        rc = read_report(D, N, got);
-        if (rc != VRT_OK) return rc;
-        if (di == 0 && result) *result = brush_result(got);
-        /* the density changes count: nothing changed, or only material ids, and no derived structure changes */
-        rc = rebuild_written(ctx, D, slot, got.lo, got.hi, got.high, changed);
-        if (rc != VRT_OK) return rc;
-    }
+        return VRT_OK;
+    };
+    e.reported = [&](const Written& got) { if (result) *result = brush_result(got); };
+    int rc = run_edit(ctx, e);
+    if (rc != VRT_OK) return rc;
     for (int k = 0; k < steps; k++) {
         to.push_back(from.back());
         from.pop_back();
@@ -213,7 +342,7 @@ int step_history(vrt_ctx* ctx, int slot, int steps, bool redo, vrt_brush_result*
             (redo ? dh.redo : dh.undo).pop_back();
         }
     }
-    return finish_edit(ctx, changed);
+    return VRT_OK;
 }
 
 }  // namespace

@@ -88,38 +88,4 @@ struct DBrushSlot {
     uint32_t pad_[24];         /* one 128-byte line per slot */
 };
 
-/* The edit history (vrt_history.hip; the helpers of the edit skeleton in vrt_slots.hip launch these).  A history tile is the aligned
-   VRT_HISTORY_TILE^3 samples whose tile coordinates {x, z, y} make its key (tx * T + tz) * T + ty, T = history_tiles_per_axis(N); a
-   record holds `tiles` DHistoryTile in no particular order. */
-struct DHistoryTile {
-    uint32_t bits[64];  /* the stored density bits of sample (4 tx + (l >> 4), 4 tz + ((l >> 2) & 3), 4 ty + (l & 3)) at l; 0 beyond the grid */
-    uint8_t ids[64];
-    uint32_t key;
-    uint32_t pad_[3];
-};
-static_assert(sizeof(DHistoryTile) == VRT_HISTORY_TILE_BYTES, "vrt.h states this size");
-__host__ __device__ inline int history_tiles_per_axis(int N) { return (N + VRT_HISTORY_TILE - 1) / VRT_HISTORY_TILE; }
-/* The tiles that meet a sample box, as a box of tile coordinates. */
-inline EditBox history_tile_box(const EditBox& samples) {
-    EditBox t;
-    for (int a = 0; a < 3; a++) {
-        t.lo[a] = samples.lo[a] / VRT_HISTORY_TILE;
-        t.n[a] = (samples.lo[a] + samples.n[a] - 1) / VRT_HISTORY_TILE - t.lo[a] + 1;
-    }
-    return t;
-}
-/* scratch: history_scratch_bytes(foot) of device memory — two counters, then the footprint's bits and ids. */
-size_t history_scratch_bytes(const EditBox& foot);
-/* Zeroes the counters and copies the samples of `foot` into the scratch. */
-hipError_t launch_history_capture(const float* dense, const uint8_t* material, int N, const EditBox& foot, void* scratch, hipStream_t stream);
-/* One wave per tile of `tiles`: a tile with a sample whose bits or id differ from the scratch copy (samples outside `foot` were not
-   written) counts into counter 0 (record_or_null == nullptr), or takes the next of the record's `capacity` places, by counter 1, for
-   the 64 samples as they were. */
-hipError_t launch_history_compact(const float* dense, const uint8_t* material, int N, const EditBox& foot, void* scratch, const EditBox& tiles,
-                                  void* record_or_null, unsigned capacity, hipStream_t stream);
-const unsigned* history_changed_tiles(const void* scratch); /* device memory: counter 0 */
-/* One wave per tile of the record: record and volume exchange the tile's samples; the samples whose bits or id changed go into the edit
-   report (density changes in the high half).  slots: NOT zeroed here — the entries of one call add up. */
-hipError_t launch_history_swap(void* record, unsigned tiles, float* dense, uint8_t* material, int N, DBrushSlot* slots, hipStream_t stream);
-
 }  // namespace vrt

@@ -285,39 +285,31 @@ int vrt_volume_redistance(vrt_ctx* ctx, int slot, int band, int from, const int*
     const bool texel16 = h.format == VRT_FORMAT_TEXEL16;
     const float cell = (h.extent * 2.0f) / (float)(N - 1);
     const float unit = cell / h.density_scale;
-    rc = quiesce(ctx);
-    if (rc != VRT_OK) return rc;
-    if ((rc = history_capture(ctx, slot, box)) != VRT_OK) return rc;
     std::vector<unsigned> surfels(ctx->dev.size(), 0u);
-    for (size_t di = 0; di < ctx->dev.size(); di++) { /* everything that can run out of memory, before any sample is written */
-        DeviceState& D = ctx->dev[di];
-        HIP_TRY(hipSetDevice(D.ordinal));
-        rc = ensure_buffer(D.buf[kBufRedistTable], redistance_table_bytes(N));
+    Edit e;
+    e.slot = slot;
+    e.foot = box;
+    e.rebuild = Edit::kFootprint; /* the requested box, whatever was reported */
+    e.prepare = [&](DeviceState& D, size_t di) -> int {
+        int rc = ensure_buffer(D.buf[kBufRedistTable], redistance_table_bytes(N));
         if (rc != VRT_OK) return rc;
         HIP_TRY(launch_redistance_count(D.vol[slot].dense, texel16, N, from, grown, D.buf[kBufRedistTable].p, D.stream));
         HIP_TRY(hipMemcpyAsync(&surfels[di], redistance_surfel_count(D.buf[kBufRedistTable].p), sizeof(unsigned), hipMemcpyDeviceToHost, D.stream));
         HIP_TRY(hipStreamSynchronize(D.stream));
-        rc = ensure_buffer(D.buf[kBufRedistSurfels], redistance_surfel_bytes(surfels[di]));
-        if (rc != VRT_OK) return rc;
-    }
-    bool changed = false;
-    for (size_t di = 0; di < ctx->dev.size(); di++) {
-        DeviceState& D = ctx->dev[di];
-        HIP_TRY(hipSetDevice(D.ordinal));
+        return ensure_buffer(D.buf[kBufRedistSurfels], redistance_surfel_bytes(surfels[di]));
+    };
+    e.write = [&](DeviceState& D, size_t di) -> int {
         DeviceVolume& v = D.vol[slot];
         if (surfels[di] > 0u)
             HIP_TRY(launch_redistance_surfels(v.dense, texel16, N, from, grown, D.buf[kBufRedistTable].p, D.buf[kBufRedistSurfels].p, surfels[di], D.stream));
         HIP_TRY(launch_redistance_distance(texel16, v.dense, N, band, unit, box, D.buf[kBufRedistTable].p, D.buf[kBufRedistSurfels].p, D.d_brush, D.stream));
-        Written got;
-        rc = read_report(D, N, got);
-        if (rc != VRT_OK) return rc;
-        if ((rc = history_record(ctx, D, slot, got.lo, got.hi)) != VRT_OK) return rc;
-        if (di == 0 && result)
-            *result = vrt_redistance_result{{got.lo[0], got.lo[1], got.lo[2]}, {got.hi[0], got.hi[1], got.hi[2]}, got.low, got.high, surfels[di], 0};
-        rc = rebuild_written(ctx, D, slot, lo, hi, 1, changed); /* the requested box, whatever was reported */
-        if (rc != VRT_OK) return rc;
-    }
-    return finish_edit(ctx, changed);
+        return VRT_OK;
+    };
+    e.reported = [&](const Written& got) {
+        if (result)
+            *result = vrt_redistance_result{{got.lo[0], got.lo[1], got.lo[2]}, {got.hi[0], got.hi[1], got.hi[2]}, got.low, got.high, surfels[0], 0};
+    };
+    return run_edit(ctx, e);
 }
 
 }  // extern "C"

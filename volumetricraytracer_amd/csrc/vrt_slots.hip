@@ -1,7 +1,7 @@
 /*
  * vrt_slots.hip — the volume slots behind include/vrt.h: uploads (densities, VVoxel records, the reference's volume texels, a triangle
  * mesh through the device Voxelizer), what a slot derives from its dense grid (rebuild_derived, over the launches of vrt_volume.hip),
- * the volume table the kernels read, and the skeleton every volume edit call builds its driver from (declared in
+ * the volume table the kernels read, and run_edit, the one sequence every volume edit call runs through (declared in
  * vrt_context.h).  The job VDXVoxelVolume did with D3D12 resources (RDXVoxelVolume.cpp:33-60,294-397).  Host code only.
  */
 #include <hip/hip_runtime.h>
@@ -343,116 +343,12 @@ int clip_box(int N, const int* origin, const int* size, int lo[3], int hi[3]) {
 }
 
 /* Ahead of the first write: what is already enqueued on any device comes first (frames in flight render the old volume), and every
- * device has its report records.  An edit call's other allocations are its own; none of them follows a write either. */
+ * device has its report records. */
 int quiesce(vrt_ctx* ctx) {
     for (auto& D : ctx->dev) {
         HIP_TRY(hipSetDevice(D.ordinal));
         HIP_TRY(hipDeviceSynchronize());
         if (!D.d_brush) HIP_TRY(hipMalloc(&D.d_brush, kBrushSlots * sizeof(DBrushSlot)));
-    }
-    return VRT_OK;
-}
-
-/* ---- The edit history's share of the skeleton (the kernels: vrt_history.hip) ----
- * Frees one entry's record on every device that has it: the first of a stack, or all. */
-static void free_records(vrt_ctx* ctx, int slot, bool redo, bool all) {
-    for (auto& D : ctx->dev) {
-        std::vector<void*>& stack = redo ? D.hist[slot].redo : D.hist[slot].undo;
-        if (stack.empty() || hipSetDevice(D.ordinal) != hipSuccess) continue;
-        for (size_t i = 0; i < (all ? stack.size() : 1); i++) (void)hipFree(stack[i]);
-        stack.erase(stack.begin(), all ? stack.end() : stack.begin() + 1);
-    }
-}
-
-void history_drop(vrt_ctx* ctx, int slot, bool counted) {
-    HostHistory& hh = ctx->hist[slot];
-    if (counted) hh.dropped += hh.undo.size() + hh.redo.size();
-    hh.undo.clear();
-    hh.redo.clear();
-    free_records(ctx, slot, false, true);
-    free_records(ctx, slot, true, true);
-}
-
-void history_trim(vrt_ctx* ctx, int slot) {
-    HostHistory& hh = ctx->hist[slot];
-    while (hh.on && (hh.undo.size() > (size_t)hh.max_entries || hh.tiles() * VRT_HISTORY_TILE_BYTES > hh.max_bytes)) {
-        std::vector<uint64_t>& stack = hh.undo.empty() ? hh.redo : hh.undo; /* both stacks keep the entry to go at their front */
-        if (stack.empty()) break;
-        free_records(ctx, slot, &stack == &hh.redo, false);
-        stack.erase(stack.begin());
-        hh.dropped++;
-    }
-}
-
-int history_capture(vrt_ctx* ctx, int slot, const EditBox& foot) {
-    HostHistory& hh = ctx->hist[slot];
-    hh.captured = false;
-    if (!hh.on) return VRT_OK;
-    for (auto& D : ctx->dev) { /* every allocation comes before any write */
-        HIP_TRY(hipSetDevice(D.ordinal));
-        int rc = ensure_buffer(D.buf[kBufHistory], history_scratch_bytes(foot));
-        if (rc != VRT_OK) return rc;
-    }
-    for (auto& D : ctx->dev) {
-        HIP_TRY(hipSetDevice(D.ordinal));
-        HIP_TRY(launch_history_capture(D.vol[slot].dense, D.vol[slot].material, ctx->vol[slot].N, foot, D.buf[kBufHistory].p, D.stream));
-    }
-    hh.foot = foot;
-    hh.captured = true;
-    hh.lost = false;
-    return VRT_OK;
-}
-
-/* The first pass counts the changed tiles, the host sizes the record exactly, the second pass fills it.  The first device keeps the books
- * for all: it empties the redo stack, pushes the entry and applies the limits; the others add their record of the same entry. */
-int history_record(vrt_ctx* ctx, DeviceState& D, int slot, const int lo[3], const int hi[3]) {
-    HostHistory& hh = ctx->hist[slot];
-    if (!hh.on || !hh.captured) return VRT_OK;
-    const bool first = &D == &ctx->dev.front();
-    if (&D == &ctx->dev.back()) hh.captured = false; /* the call's last word */
-    if (hh.lost || lo[0] > hi[0] || lo[1] > hi[1] || lo[2] > hi[2]) return VRT_OK;
-    const HostVolume& h = ctx->vol[slot];
-    const DeviceVolume& v = D.vol[slot];
-    const EditBox tiles = history_tile_box(derived_boxes(h, lo, hi).samples);
-    void* scratch = D.buf[kBufHistory].p;
-    unsigned count = 0;
-    HIP_TRY(launch_history_compact(v.dense, v.material, h.N, hh.foot, scratch, tiles, nullptr, 0u, D.stream));
-    HIP_TRY(hipMemcpyAsync(&count, history_changed_tiles(scratch), sizeof count, hipMemcpyDeviceToHost, D.stream));
-    HIP_TRY(hipStreamSynchronize(D.stream));
-    if (first) {
-        if (count == 0u) {
-            hh.lost = true; /* no bit changed, on any device: nothing is recorded and the redo stack stays */
-            return VRT_OK;
-        }
-        hh.redo.clear();
-        free_records(ctx, slot, true, true);
-        if ((uint64_t)count * VRT_HISTORY_TILE_BYTES > hh.max_bytes) { /* larger than the history may be: everything goes, this entry too */
-            hh.dropped++;
-            hh.lost = true;
-        } else {
-            hh.undo.push_back(count);
-        }
-    } else if (count != hh.undo.back()) {
-        fprintf(stderr, "[vrt] edit history: device %d changed %u tiles, the first device %llu\n", D.ordinal, count, (unsigned long long)hh.undo.back());
-        hh.lost = true;
-    }
-    void* record = nullptr;
-    if (!hh.lost) {
-        HIP_TRY(hipSetDevice(D.ordinal));
-        if (hipMalloc(&record, (size_t)count * VRT_HISTORY_TILE_BYTES) != hipSuccess) {
-            (void)hipGetLastError(); /* no memory for the record: the edit stands, the history does not */
-            hh.lost = true;
-        }
-    }
-    if (hh.lost) {
-        history_drop(ctx, slot, true);
-        return hipSetDevice(D.ordinal) == hipSuccess ? VRT_OK : VRT_ERR_HIP;
-    }
-    D.hist[slot].undo.push_back(record);
-    HIP_TRY(launch_history_compact(v.dense, v.material, h.N, hh.foot, scratch, tiles, record, count, D.stream));
-    if (first) {
-        history_trim(ctx, slot);
-        HIP_TRY(hipSetDevice(D.ordinal));
     }
     return VRT_OK;
 }
@@ -479,18 +375,50 @@ vrt_brush_result brush_result(const Written& got) { /* brushes, stamp, smooth, w
 }
 
 /* One device's samples are written: what the slot derives from them, recomputed over the xyz box lo..hi (rebuild_derived) — unless
- * `relevant`, the count of writes that can change a derived structure, is 0.  Then, once: the scene and the volume table follow. */
-int rebuild_written(vrt_ctx* ctx, DeviceState& D, int slot, const int lo[3], const int hi[3], unsigned long long relevant, bool& changed) {
+ * `relevant`, the count of writes that can change a derived structure, is 0. */
+static int rebuild_written(vrt_ctx* ctx, DeviceState& D, int slot, const int lo[3], const int hi[3], unsigned long long relevant, bool& changed) {
     if (relevant == 0) return VRT_OK;
     changed = true;
     HostVolume& h = ctx->vol[slot];
     const DerivedBoxes written = derived_boxes(h, lo, hi);
     return rebuild_derived(ctx, D, slot, &written, false, h.abox);
 }
-int finish_edit(vrt_ctx* ctx, bool changed) {
+/* After the last device: when something changed, the scene is stale and the volume table follows. */
+static int finish_edit(vrt_ctx* ctx, bool changed) {
     if (!changed) return VRT_OK;
     ctx->scene_stale = true;
     return sync_volume_table(ctx);
+}
+
+/* The sequence of every volume edit call; its order, and the rule that order keeps, are stated at the declaration (vrt_context.h). */
+int run_edit(vrt_ctx* ctx, const Edit& e) {
+    const HostVolume& h = ctx->vol[e.slot];
+    const int N = h.N;
+    int rc = quiesce(ctx);
+    if (rc != VRT_OK) return rc;
+    for (size_t di = 0; e.prepare && di < ctx->dev.size(); di++) {
+        HIP_TRY(hipSetDevice(ctx->dev[di].ordinal));
+        if ((rc = e.prepare(ctx->dev[di], di)) != VRT_OK) return rc;
+    }
+    HistoryCall call;
+    if (e.records && (rc = history_capture(ctx, e.slot, e.foot, call)) != VRT_OK) return rc;
+    Written foot; /* the footprint in xyz, with its count */
+    for (int a = 0; a < 3; a++) foot.lo[grid_axis(a)] = e.foot.lo[a], foot.hi[grid_axis(a)] = e.foot.lo[a] + e.foot.n[a] - 1;
+    foot.low = foot.high = box_count(e.foot);
+    bool changed = false;
+    for (size_t di = 0; di < ctx->dev.size(); di++) {
+        DeviceState& D = ctx->dev[di];
+        HIP_TRY(hipSetDevice(D.ordinal));
+        if ((rc = e.write(D, di)) != VRT_OK) return rc;
+        Written got = foot;
+        if (e.reports && (rc = read_report(D, N, got)) != VRT_OK) return rc;
+        if ((rc = history_record(ctx, di, e.slot, call, got.lo, got.hi)) != VRT_OK) return rc;
+        if (di == 0 && e.reported) e.reported(got);
+        const Written& box = e.rebuild == Edit::kFootprint ? foot : got;
+        rc = rebuild_written(ctx, D, e.slot, box.lo, box.hi, e.rebuild == Edit::kDensityWrites ? got.high : box.low, changed);
+        if (rc != VRT_OK) return rc;
+    }
+    return finish_edit(ctx, changed);
 }
 
 }  // namespace vrt

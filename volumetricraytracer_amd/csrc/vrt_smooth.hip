@@ -156,29 +156,18 @@ int vrt_volume_smooth(vrt_ctx* ctx, int slot, const vrt_smooth* rec, vrt_brush_r
     int lo[3], hi[3], work_lo[3], work_hi[3];
     if (!vrt_smooth_core::boxes(*rec, N, lo, hi, work_lo, work_hi)) return VRT_OK; /* wholly outside the grid */
     const EditBox region = derived_boxes(h, lo, hi).samples, work = derived_boxes(h, work_lo, work_hi).samples;
-    int rc = quiesce(ctx);
-    if (rc != VRT_OK) return rc;
-    if ((rc = history_capture(ctx, slot, region)) != VRT_OK) return rc;
-    for (auto& D : ctx->dev) { /* every allocation comes before any write */
-        HIP_TRY(hipSetDevice(D.ordinal));
-        rc = ensure_buffer(D.buf[kBufSmoothWarp], smooth_scratch_bytes(work));
-        if (rc != VRT_OK) return rc;
-    }
-    bool changed = false;
-    for (size_t di = 0; di < ctx->dev.size(); di++) {
-        DeviceState& D = ctx->dev[di];
-        HIP_TRY(hipSetDevice(D.ordinal));
+    Edit e;
+    e.slot = slot;
+    e.foot = region;
+    e.rebuild = Edit::kWrites; /* every written sample is a density write */
+    e.prepare = [&](DeviceState& D, size_t) { return ensure_buffer(D.buf[kBufSmoothWarp], smooth_scratch_bytes(work)); };
+    e.write = [&](DeviceState& D, size_t) -> int {
         DeviceVolume& v = D.vol[slot];
         HIP_TRY(launch_smooth(*rec, h.format == VRT_FORMAT_TEXEL16, v.dense, v.material, N, work, region, D.buf[kBufSmoothWarp].p, D.d_brush, D.stream));
-        Written got;
-        rc = read_report(D, N, got);
-        if (rc != VRT_OK) return rc;
-        if ((rc = history_record(ctx, D, slot, got.lo, got.hi)) != VRT_OK) return rc;
-        if (di == 0 && result) *result = brush_result(got);
-        rc = rebuild_written(ctx, D, slot, got.lo, got.hi, got.low, changed); /* every written sample is a density write */
-        if (rc != VRT_OK) return rc;
-    }
-    return finish_edit(ctx, changed);
+        return VRT_OK;
+    };
+    e.reported = [&](const Written& got) { if (result) *result = brush_result(got); };
+    return run_edit(ctx, e);
 }
 
 }  // extern "C"

@@ -114,27 +114,19 @@ int vrt_volume_stamp(vrt_ctx* ctx, int dst_slot, int src_slot, const vrt_stamp* 
     if (!vrt_stamp_core::footprint(*rec, hs.N, N, lo, hi)) return VRT_OK; /* wholly outside the grid */
     const vrt_stamp_core::Rule rule = vrt_stamp_core::rule_of(*rec, hs.N, vrt_stamp_core::unit_of(N, h.extent, h.density_scale),
                                                     vrt_stamp_core::unit_of(hs.N, hs.extent, hs.density_scale));
-    const EditBox foot = derived_boxes(h, lo, hi).samples;
-    int rc = quiesce(ctx);
-    if (rc != VRT_OK) return rc;
-    if ((rc = history_capture(ctx, dst_slot, foot)) != VRT_OK) return rc;
-    bool changed = false;
-    for (size_t di = 0; di < ctx->dev.size(); di++) {
-        DeviceState& D = ctx->dev[di];
-        HIP_TRY(hipSetDevice(D.ordinal));
+    Edit e;
+    e.slot = dst_slot;
+    e.foot = derived_boxes(h, lo, hi).samples;
+    e.rebuild = Edit::kWrites; /* every written sample is a density write */
+    e.write = [&](DeviceState& D, size_t) -> int {
         DeviceVolume& v = D.vol[dst_slot];
         const DeviceVolume& vs = D.vol[src_slot];
         HIP_TRY(launch_stamp_region(rule, hs.format == VRT_FORMAT_TEXEL16, vs.dense, vs.material, h.format == VRT_FORMAT_TEXEL16, v.dense,
-                                    v.material, N, foot, D.d_brush, D.stream));
-        Written got;
-        rc = read_report(D, N, got);
-        if (rc != VRT_OK) return rc;
-        if ((rc = history_record(ctx, D, dst_slot, got.lo, got.hi)) != VRT_OK) return rc;
-        if (di == 0 && result) *result = brush_result(got);
-        rc = rebuild_written(ctx, D, dst_slot, got.lo, got.hi, got.low, changed); /* every written sample is a density write */
-        if (rc != VRT_OK) return rc;
-    }
-    return finish_edit(ctx, changed);
+                                    v.material, N, e.foot, D.d_brush, D.stream));
+        return VRT_OK;
+    };
+    e.reported = [&](const Written& got) { if (result) *result = brush_result(got); };
+    return run_edit(ctx, e);
 }
 
 }  // extern "C"

@@ -531,15 +531,14 @@ static int update_region(vrt_ctx* ctx, int slot, const int origin[3], const int 
     const size_t count = (size_t)size[0] * size[1] * size[2];
     const size_t staged = voxels ? count * sizeof(vrt_voxel) : count * (sizeof(float) + (material ? 1 : 0));
     const bool texel16 = h.format == VRT_FORMAT_TEXEL16;
-    rc = quiesce(ctx);
-    if (rc != VRT_OK) return rc;
-    if ((rc = history_capture(ctx, slot, box)) != VRT_OK) return rc;
-    bool changed = false;
-    for (auto& D : ctx->dev) {
-        HIP_TRY(hipSetDevice(D.ordinal));
+    Edit e;
+    e.slot = slot;
+    e.foot = box;
+    e.rebuild = Edit::kFootprint;
+    e.reports = false; /* the scatter writes every sample of its box */
+    e.prepare = [&](DeviceState& D, size_t) { return ensure_buffer(D.buf[kBufEditStaging], staged); };
+    e.write = [&](DeviceState& D, size_t) -> int {
         DeviceVolume& v = D.vol[slot];
-        rc = ensure_buffer(D.buf[kBufEditStaging], staged);
-        if (rc != VRT_OK) return rc;
         if (voxels) {
             HIP_TRY(hipMemcpyAsync(D.buf[kBufEditStaging].p, voxels, staged, hipMemcpyHostToDevice, D.stream));
         } else {
@@ -548,11 +547,9 @@ static int update_region(vrt_ctx* ctx, int slot, const int origin[3], const int 
                 HIP_TRY(hipMemcpyAsync(static_cast<char*>(D.buf[kBufEditStaging].p) + count * sizeof(float), material, count, hipMemcpyHostToDevice, D.stream));
         }
         HIP_TRY(launch_scatter_region(D.buf[kBufEditStaging].p, voxels != nullptr, material != nullptr, texel16, v.dense, v.material, N, box, D.stream));
-        if ((rc = history_record(ctx, D, slot, first, last)) != VRT_OK) return rc;
-        rc = rebuild_written(ctx, D, slot, first, last, count, changed); /* reads no report: its own box, always */
-        if (rc != VRT_OK) return rc;
-    }
-    return finish_edit(ctx, changed);
+        return VRT_OK;
+    };
+    return run_edit(ctx, e);
 }
 
 }  // namespace vrt

@@ -131,30 +131,18 @@ int vrt_volume_warp(vrt_ctx* ctx, int slot, const vrt_warp* rec, vrt_brush_resul
     if (!vrt_warp_core::box(*rec, N, lo, hi)) return VRT_OK; /* wholly outside the grid */
     const EditBox region = derived_boxes(h, lo, hi).samples;
     const float off = vrt_warp_core::off_of(*rec, vrt_stamp_core::unit_of(N, h.extent, h.density_scale));
-    int rc = quiesce(ctx);
-    if (rc != VRT_OK) return rc;
-    if ((rc = history_capture(ctx, slot, region)) != VRT_OK) return rc;
-    for (auto& D : ctx->dev) { /* every allocation comes before any write */
-        HIP_TRY(hipSetDevice(D.ordinal));
-        rc = ensure_buffer(D.buf[kBufSmoothWarp], warp_scratch_bytes(region));
-        if (rc != VRT_OK) return rc;
-    }
-    bool changed = false;
-    for (size_t di = 0; di < ctx->dev.size(); di++) {
-        DeviceState& D = ctx->dev[di];
-        HIP_TRY(hipSetDevice(D.ordinal));
+    Edit e;
+    e.slot = slot;
+    e.foot = region;
+    e.rebuild = Edit::kDensityWrites; /* nothing written, or only material ids, and no derived structure changes */
+    e.prepare = [&](DeviceState& D, size_t) { return ensure_buffer(D.buf[kBufSmoothWarp], warp_scratch_bytes(region)); };
+    e.write = [&](DeviceState& D, size_t) -> int {
         DeviceVolume& v = D.vol[slot];
         HIP_TRY(launch_warp(*rec, off, h.format == VRT_FORMAT_TEXEL16, v.dense, v.material, N, region, D.buf[kBufSmoothWarp].p, D.d_brush, D.stream));
-        Written got;
-        rc = read_report(D, N, got);
-        if (rc != VRT_OK) return rc;
-        if ((rc = history_record(ctx, D, slot, got.lo, got.hi)) != VRT_OK) return rc;
-        if (di == 0 && result) *result = brush_result(got);
-        /* the density writes count: nothing written, or only material ids, and no derived structure changes */
-        rc = rebuild_written(ctx, D, slot, got.lo, got.hi, got.high, changed);
-        if (rc != VRT_OK) return rc;
-    }
-    return finish_edit(ctx, changed);
+        return VRT_OK;
+    };
+    e.reported = [&](const Written& got) { if (result) *result = brush_result(got); };
+    return run_edit(ctx, e);
 }
 
 }  // extern "C"
