@@ -53,6 +53,8 @@
  *   vrt_trace_rays*, vrt_camera_rays (no reference analogue: its DXR TraceRay calls live only inside its shaders)
  *   vrt_query_points*               (no reference analogue: the distance from a point to the scene's nearest surface, its direction, and
  *                                   the point's projection onto that surface)
+ *   vrt_query_contacts              (no reference analogue: where the surface of one placed instance touches or enters another — the
+ *                                   surface points of A in or near B, as compact contact records)
  *
  * Error convention: 0 = OK, negative = error.  The reference logs and returns early
  * (DXRenderer.cpp:220-225); the adaptor maps negative codes onto that behaviour.
@@ -1339,6 +1341,65 @@ int vrt_query_points(vrt_ctx* ctx, int iterations, float tolerance, int n, const
 /* The same from and into host arrays, synchronous: staged through a context-owned device buffer (vrt_trace_rays_host's), reallocated
  * only when a larger batch arrives. */
 int vrt_query_points_host(vrt_ctx* ctx, int iterations, float tolerance, int n, const vrt_point* points, vrt_point_result* results);
+
+/* Contact queries (no reference analogue): where two placed instances of the resident scene touch — two sculpts, a stamp source held
+ * over its target, an object dropped on another.  The surface points of instance A (vrt_volume_extract_mesh's vertices at iso 0 over
+ * A's whole grid, taken into world space) that lie in or near instance B (vrt_query_points' value of B alone there) come back as
+ * records in the order of A's cells.  The call is ONE-SIDED: it finds the points of A's surface in B, not the points of B's surface
+ * in A; a caller who wants both sides calls it twice with the indices swapped.  The two instances may refer to one slot.
+ *
+ * The rule is part of the contract.  All arithmetic is fp32, evaluated as parenthesised, no fused multiply-add; sqrtf and / are
+ * correctly rounded.
+ *   1. Surface points of A.  vrt_volume_extract_mesh's rule, steps 1 to 3, at iso 0 over the whole grid of A's slot: every active
+ *      cell yields its grid position p, its normal n and its material.  Object point o_a = (p_a * cell) - extent.
+ *   2. World point.  w_a = ((O[a][0]*o.x + O[a][1]*o.y) + O[a][2]*o.z) + position_a, O[i][j] = scale[i] * R[i][j], R the quaternion
+ *      matrix of vrt_query_points' step 1 — A's object-to-world matrix as vrt_scene_set packs it.
+ *   3. B at w.  vrt_query_points' steps 1, 2, 3, 4 and 6 for instance B alone.  The cell is a CANDIDATE when w is finite, lies IN B's
+ *      BOX and the interpolant there is not NaN; its value d * smin includes the step_max clamp: exactly the number vrt_query_points
+ *      reports.  (A box bound is no candidate: a volume has no surface outside its box.)
+ *   4. Contact.  A candidate is a contact iff value <= margin.  distance, normal and material_b are the record of vrt_query_points;
+ *      position = w; normal_a is h_a = (WA[0][a]*n.x + WA[1][a]*n.y) + WA[2][a]*n.z, WA being A's world-to-object matrix, normalised
+ *      as in vrt_query_points' step 6 — (0,0,0) when dot(h,h) is 0 or not finite; material_a and cell_a are the vertex's.
+ *   5. Order.  Contacts are numbered in the order of their cells' keys (cx*N + cz)*N + cy.  min_distance is a minimum; candidates,
+ *      contacts, lo and hi are integers; no float is summed.  The output does not depend on how the device schedules its work.
+ *   6. Skipping.  Cells whose point cannot lie in B's box are skipped: the host derives a conservative cell box of A from the corners
+ *      of B's box in double precision, as vrt_volume_stamp does for its footprint.  No field of the result depends on that box.
+ * Consequence: a contact's distance, normal and material_b are, bit for bit, what vrt_query_points (iterations 0) reports at
+ * `position` in a scene that holds instance B alone, and `position` is the fp32 transform of step 2 of vrt_volume_extract_mesh's vertex.
+ * What the rule is worth: DESIGN.md section 2 has the figures — on two overlapping spheres the deepest distance is the analytic overlap
+ * up to the two surfaces' sag, and the deepest contact's normal follows the line of centres to a few degrees. */
+typedef struct vrt_contact {          /* 64 B: four 16-byte words */
+    float    position[3];             /* world space: the surface point of A */
+    float    distance;                /* B's value there, world units; < 0 = penetration */
+    float    normal[3];               /* B's world normal there, inside -> outside; 0 when degenerate */
+    uint32_t material_a;              /* the mesh rule's vertex material of A's cell */
+    float    normal_a[3];             /* A's vertex normal in world space; 0 when degenerate */
+    uint32_t material_b;              /* vrt_query_points' step 6: the id of B's nearest sample */
+    int32_t  cell_a[3];               /* xyz: the cell of A that made the point */
+    uint32_t reserved_;               /* 0 */
+} vrt_contact;
+
+typedef struct vrt_contacts_result {  /* 48 B */
+    int32_t  lo[3], hi[3];            /* xyz, inclusive: the cells of A with a contact; lo = (N,N,N) > hi = (-1,-1,-1) when none */
+    uint64_t contacts;
+    uint64_t candidates;              /* active cells of A whose point B SAMPLES with a non-NaN value (step 3) */
+    float    min_distance;            /* the smallest distance over the contacts; +inf when none */
+    uint32_t reserved_;               /* 0 */
+} vrt_contacts_result;
+
+/* Synchronous, on device 0, in the manner of vrt_volume_extract_mesh: a vrt_scene_set that was deferred while frames were in flight is
+ * applied first (as vrt_query_points does), the call waits for work already enqueued on the context's devices, reads the two slots'
+ * dense and material grids and writes nothing to any slot: every vrt_debug_volume_bytes buffer reads the same before and after.  It is
+ * not recorded in an edit history and leaves the render's bookkeeping alone (vrt_last_timing, the timing and launch histories, the
+ * kernel form, the per-wave records).  contacts_or_null == NULL with capacity 0 only counts and fills the result: count, allocate,
+ * call again.  The records arrive in host memory.
+ * Errors, all checked before anything is written: VRT_ERR_INVALID for a NULL context or result, a margin that is negative or not
+ * finite, contacts_or_null == NULL with capacity > 0, or instance_a == instance_b; VRT_ERR_NOT_READY without a scene; VRT_ERR_INVALID
+ * for an index outside 0 .. n_instances - 1 of the resident scene; VRT_ERR_INVALID, with the result filled in and no output byte
+ * touched, when records were asked for and capacity < contacts; VRT_ERR_OOM when scratch memory cannot be had.  Disjoint boxes are
+ * VRT_OK with zeros. */
+int vrt_query_contacts(vrt_ctx* ctx, int instance_a, int instance_b, float margin,
+                       vrt_contact* contacts_or_null, size_t capacity, vrt_contacts_result* result);
 
 int vrt_last_timing(vrt_ctx* ctx, vrt_timing* out);
 /* Kernel durations (ms) of the last n vrt_render_rows/vrt_render launches, oldest first;

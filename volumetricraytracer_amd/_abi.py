@@ -241,6 +241,36 @@ class vrt_point_result(C.Structure):
     ]
 
 
+class vrt_contact(C.Structure):
+    _fields_ = [
+        ("position", C.c_float * 3),
+        ("distance", C.c_float),
+        ("normal", C.c_float * 3),
+        ("material_a", C.c_uint32),
+        ("normal_a", C.c_float * 3),
+        ("material_b", C.c_uint32),
+        ("cell_a", C.c_int32 * 3),
+        ("reserved_", C.c_uint32),
+    ]
+
+
+class vrt_contacts_result(C.Structure):
+    _fields_ = [
+        ("lo", C.c_int32 * 3),
+        ("hi", C.c_int32 * 3),
+        ("contacts", C.c_uint64),
+        ("candidates", C.c_uint64),
+        ("min_distance", C.c_float),
+        ("reserved_", C.c_uint32),
+    ]
+
+
+def contacts_result_dict(res: "vrt_contacts_result") -> dict:
+    """A vrt_contacts_result as plain Python values."""
+    return {"lo": tuple(res.lo), "hi": tuple(res.hi), "contacts": int(res.contacts), "candidates": int(res.candidates),
+            "min_distance": float(res.min_distance)}
+
+
 class vrt_brush(C.Structure):
     _fields_ = [
         ("shape", C.c_int32),
@@ -478,6 +508,7 @@ SYMBOLS = {
     "vrt_camera_rays": (C.c_int, [C.POINTER(vrt_scene), C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
     "vrt_query_points": (C.c_int, [C.c_void_p, C.c_int, C.c_float, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]),
     "vrt_query_points_host": (C.c_int, [C.c_void_p, C.c_int, C.c_float, C.c_int, C.c_void_p, C.c_void_p]),
+    "vrt_query_contacts": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_float, C.c_void_p, C.c_size_t, C.POINTER(vrt_contacts_result)]),
     "vrt_last_timing": (C.c_int, [C.c_void_p, C.POINTER(vrt_timing)]),
     "vrt_timing_history": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(C.c_float)]),
     "vrt_launch_history": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(C.c_float), C.POINTER(C.c_int)]),

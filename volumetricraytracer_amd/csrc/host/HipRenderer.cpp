@@ -774,6 +774,34 @@ bool VHipRenderer::QueryPoints(const std::vector<VVector>& points, int iteration
     return ok(vrt_query_points_host(Ctx, iterations, tolerance, (int)in.size(), in.data(), results.data()), "vrt_query_points_host");
 }
 
+bool VHipRenderer::QueryContacts(const Scene::VVoxelObject& objectA, const Scene::VVoxelObject& objectB, float margin,
+                                 std::vector<vrt_contact>& contacts, vrt_contacts_result* result) {
+    if (!IsActive()) {
+        V_LOG_WARNING("QueryContacts() on an inactive renderer");
+        return false;
+    }
+    const VObjectPtr<Scene::VScene> scene = SceneRef.lock();
+    if (!scene || !SyncWithScene(*scene)) return false;
+    vrt_scene s;
+    if (!FillSceneStruct(*scene, s, &QueryObjects)) return false;
+    int a = -1, b = -1;
+    for (size_t i = 0; i < QueryObjects.size(); i++) {
+        if (QueryObjects[i] == &objectA && a < 0) a = (int)i;
+        if (QueryObjects[i] == &objectB && b < 0) b = (int)i;
+    }
+    if (a < 0 || b < 0) {
+        V_LOG_ERROR("QueryContacts(): an object is not part of the rendered scene");
+        return false;
+    }
+    vrt_contacts_result got;
+    contacts.clear();
+    if (!ok(vrt_query_contacts(Ctx, a, b, margin, nullptr, 0, &got), "vrt_query_contacts")) return false;
+    contacts.resize((size_t)got.contacts);
+    if (got.contacts > 0 && !ok(vrt_query_contacts(Ctx, a, b, margin, contacts.data(), contacts.size(), &got), "vrt_query_contacts")) return false;
+    if (result) *result = got;
+    return true;
+}
+
 int VHipRenderer::SlotOf(const Voxel::VVoxelVolume* volume) const {
     int slot = -1;
     for (size_t i = 0; i < Uploaded.size(); i++)

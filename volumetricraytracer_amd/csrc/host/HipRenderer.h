@@ -111,6 +111,12 @@ public:
        are first moved onto that surface (at most that many moves, stopping within `tolerance` world units of it).  HitObject-style
        lookup: the records' instance indexes the same objects as a hit's.  False (after logging) on failure. */
     bool QueryPoints(const std::vector<VVector>& points, int iterations, float tolerance, std::vector<vrt_point_result>& results);
+    /* Contact queries on the GPU (vrt_query_contacts) between two placed objects of the scene Render() would draw now (synced first):
+       the points of objectA's surface that lie in objectB or within `margin` world units of its surface, as vrt_contact records in
+       the order of objectA's cells — counted, then fetched.  One-sided: swap the objects for objectB's surface in objectA.  False
+       (after logging) on failure, or when an object is not part of the scene. */
+    bool QueryContacts(const Scene::VVoxelObject& objectA, const Scene::VVoxelObject& objectB, float margin, std::vector<vrt_contact>& contacts,
+                       vrt_contacts_result* result = nullptr);
     /* The closest hit under pixel (px, py) of the current output size: the camera ray the march kernel casts for it
        (vrt_camera_rays), traced as TraceRays does.  False when the pixel lies outside the frame or the query fails; a miss is
        true with out.instance = -1. */

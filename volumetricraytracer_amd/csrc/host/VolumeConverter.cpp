@@ -4,6 +4,7 @@
 #include "../components_core.h"
 #include "../fill_core.h"
 #include "../grid_core.h"
+#include "../contacts_core.h"
 #include "../measure_core.h"
 #include "../mesh_core.h"
 #include "../redistance_core.h"
@@ -449,6 +450,57 @@ void VVolumeConverter::Measure(const Voxel::VVoxelVolume& volume, ::vrt_measure_
     const int lo[3] = {boxLo ? boxLo->X : 0, boxLo ? boxLo->Y : 0, boxLo ? boxLo->Z : 0};
     const int hi[3] = {boxHi ? boxHi->X : last, boxHi ? boxHi->Y : last, boxHi ? boxHi->Z : last};
     Measure(volume.GetVoxels().data(), volume.GetSize(), false, iso, lo, hi, out, materialSamplesOrNull);
+}
+
+void VVolumeConverter::Contacts(const VPlacedVolume& a, const VPlacedVolume& b, float margin, std::vector<::vrt_contact>& contacts,
+                                ::vrt_contacts_result& result, bool clip) {
+    namespace M = vrt_mesh;
+    namespace K = vrt_contacts;
+    K::Side A, B;
+    K::place(A, a.Position, a.Rotation, a.Scale);
+    K::grid(A, (int)a.N, a.Extent, a.Texel16, a.DensityScale, a.StepMax);
+    K::place(B, b.Position, b.Rotation, b.Scale);
+    K::grid(B, (int)b.N, b.Extent, b.Texel16, b.DensityScale, b.StepMax);
+    const int N = A.N;
+    contacts.clear();
+    result = ::vrt_contacts_result{{N, N, N}, {-1, -1, -1}, 0, 0, INFINITY, 0};
+    int lo[3] = {0, 0, 0}, hi[3] = {N - 2, N - 2, N - 2};
+    if (clip && !K::cell_box(A, B, lo, hi)) return;
+    unsigned best = K::kNoKey;
+    for (int x = lo[0]; x <= hi[0]; x++)
+        for (int z = lo[2]; z <= hi[2]; z++)
+            for (int y = lo[1]; y <= hi[1]; y++) {
+                const int c[3] = {x, y, z};
+                float f[8];
+                for (int j = 0; j < 8; j++) {
+                    const float d = a.Voxels[vrt_grid::index(N, x + (j & 1), y + ((j >> 1) & 1), z + (j >> 2))].Density;
+                    f[j] = M::field(vrt_grid::decode(d, a.Texel16), 0.0f);
+                }
+                const unsigned classes = M::corner_classes(f);
+                if (!M::active(classes)) continue;
+                const M::Vertex v = M::cell_vertex(c, f);
+                float w[3], s[8], value;
+                K::world_point(A, v.p, w);
+                K::Probe P;
+                if (!K::locate(B, w, P)) continue;
+                for (int j = 0; j < 8; j++) {
+                    const float d = b.Voxels[vrt_grid::index(B.N, P.c[0] + (j & 1), P.c[1] + ((j >> 1) & 1), P.c[2] + (j >> 2))].Density;
+                    s[j] = vrt_grid::decode(d, b.Texel16);
+                }
+                if (!K::value_at(B, P, s, value)) continue;
+                result.candidates++;
+                if (!(value <= margin)) continue;
+                const int ja = M::material_corner(classes);
+                const uint32_t material_a = a.Voxels[vrt_grid::index(N, x + (ja & 1), y + ((ja >> 1) & 1), z + (ja >> 2))].Material;
+                int near[3];
+                K::nearest_sample(B, P, near);
+                const uint32_t material_b = b.Voxels[vrt_grid::index(B.N, near[0], near[1], near[2])].Material;
+                contacts.push_back(K::contact(A, B, c, w, v.n, material_a, P, s, value, material_b));
+                best = std::min(best, K::distance_key(value));
+                for (int i = 0; i < 3; i++) result.lo[i] = std::min(result.lo[i], c[i]), result.hi[i] = std::max(result.hi[i], c[i]);
+            }
+    result.contacts = contacts.size();
+    result.min_distance = K::key_distance(best);
 }
 
 VVolumeConverter::VStampResult VVolumeConverter::Stamp(Voxel::VVoxel* dst, size_t nd, float unitDst, bool dstTexel16, const Voxel::VVoxel* src,

@@ -24,6 +24,8 @@ struct vrt_components;
 struct vrt_component;
 struct vrt_components_result;
 struct vrt_measure_result;
+struct vrt_contact;
+struct vrt_contacts_result;
 
 namespace VolumeRaytracer {
 namespace Voxelizer {
@@ -100,6 +102,23 @@ public:
        records hold the integer field +-q of a VRT_FORMAT_TEXEL16 slot. */
     static void Measure(const Voxel::VVoxel* voxels, size_t n, bool texel16, float iso, const int lo[3], const int hi[3],
                         ::vrt_measure_result& out, uint64_t* materialSamplesOrNull);
+    /* One side of Contacts: n^3 VVoxel records (index x*n*n + z*n + y), only read, with the slot's metric (Texel16: the records hold
+       the integer field +-q of a VRT_FORMAT_TEXEL16 slot; StepMax <= 0: unbounded) and the instance's placement as a vrt_instance
+       holds it (Rotation: quaternion x, y, z, w). */
+    struct VPlacedVolume {
+        const Voxel::VVoxel* Voxels = nullptr;
+        size_t N = 0;
+        float Extent = 0.f;
+        bool Texel16 = false;
+        float DensityScale = 1.f, StepMax = 0.f;
+        float Position[3] = {0.f, 0.f, 0.f}, Rotation[4] = {0.f, 0.f, 0.f, 1.f}, Scale[3] = {1.f, 1.f, 1.f};
+    };
+    /* Where the surface of `a` touches or enters `b` — the rule of vrt_query_contacts (include/vrt.h; its arithmetic is
+       csrc/contacts_core.h over csrc/mesh_core.h, shared with the HIP kernels), as one plain loop over a's cells in the order of their
+       keys: the records that call returns, in its order, and its result.  One-sided, as that call is.  clip = false walks all of a's
+       cells instead of the conservative cell box of the rule's step 6: the same output, which is what a test of that box compares. */
+    static void Contacts(const VPlacedVolume& a, const VPlacedVolume& b, float margin, std::vector<::vrt_contact>& contacts,
+                         ::vrt_contacts_result& result, bool clip = true);
     /* What Stamp wrote: the samples' count and their inclusive xyz box (Lo > Hi when none). */
     struct VStampResult {
         VIntVector Lo, Hi;

@@ -56,6 +56,9 @@
  *            [--probe X Y Z]                every frame asks how far the world point (X, Y, Z) is from the nearest surface (VHipRenderer::QueryPoints: a
  *                                           GPU distance query) and prints the record, ahead of the frame's edit; with --edit-brush --edit-device the
  *                                           distance moves as the dabs carve towards the point or away from it
+ *            [--contacts I J]               after the last frame: where the surface of the scene's I-th voxel object touches or enters the J-th
+ *                                           (VHipRenderer::QueryContacts, vrt_query_contacts: a GPU contact query, one-sided) — one line with the
+ *                                           contact count, the candidates and the deepest distance
  */
 #include <chrono>
 #include <algorithm>
@@ -146,6 +149,7 @@ int main(int argc, char** argv) {
     int pickX = 0, pickY = 0;
     bool probe = false;
     VVector probeAt;
+    int contactsA = -1, contactsB = -1;
     int mode = 0, inFlight = 3, block = 0; /* three frames in flight: the reference's swap chain (FrameCount, DXConstants.cpp:23) */
     std::string format = "bgra8", volumes = "texel16";
     for (int i = 1; i < argc; i++) {
@@ -177,6 +181,13 @@ int main(int argc, char** argv) {
             pick = true;
             pickX = atoi(argv[++i]);
             pickY = atoi(argv[++i]);
+        } else if (!strcmp(argv[i], "--contacts") && i + 2 < argc) {
+            contactsA = atoi(argv[++i]);
+            contactsB = atoi(argv[++i]);
+            if (contactsA < 0 || contactsB < 0 || contactsA == contactsB) {
+                fprintf(stderr, "--contacts I J takes two different object indices\n");
+                return 1;
+            }
         } else if (!strcmp(argv[i], "--probe") && i + 3 < argc) {
             probe = true;
             probeAt.X = (float)atof(argv[++i]);
@@ -256,6 +267,10 @@ int main(int argc, char** argv) {
     }
     if (probe && (!hip || block > 0)) {
         fprintf(stderr, "--probe asks the HIP renderer once per frame: drop --block\n");
+        return 1;
+    }
+    if (contactsA >= 0 && !hip) {
+        fprintf(stderr, "--contacts asks the device: it needs the HIP renderer\n");
         return 1;
     }
     if (solid && !hip) {
@@ -567,6 +582,22 @@ int main(int argc, char** argv) {
                 if (ids[id] != 0) printf(" id %d: %.6g", id, (double)ids[id] * cell3);
         }
         printf("\n");
+    }
+    if (contactsA >= 0) { /* where object I's surface touches or enters object J, as the volumes are on the device now */
+        std::vector<VObjectPtr<Scene::VVoxelObject>> objects;
+        for (const auto& placed : scene->GetAllPlacedObjects()) {
+            const auto object = std::dynamic_pointer_cast<Scene::VVoxelObject>(placed);
+            if (object && object->GetVoxelVolume()) objects.push_back(object);
+        }
+        if ((size_t)contactsA >= objects.size() || (size_t)contactsB >= objects.size()) {
+            fprintf(stderr, "--contacts %d %d: the scene has %zu voxel objects\n", contactsA, contactsB, objects.size());
+            return 1;
+        }
+        std::vector<vrt_contact> found;
+        vrt_contacts_result res;
+        if (!hip->QueryContacts(*objects[(size_t)contactsA], *objects[(size_t)contactsB], 0.f, found, &res)) return 1;
+        printf("contacts %d %d: %llu contacts of %llu candidates, deepest distance %.4f\n", contactsA, contactsB, (unsigned long long)res.contacts,
+               (unsigned long long)res.candidates, res.min_distance);
     }
     if (!meshOut.empty()) { /* the first object's volume as it is on the device now */
         Voxelizer::VGLTFExporter::VEntry e;

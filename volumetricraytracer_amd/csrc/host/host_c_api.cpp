@@ -179,6 +179,52 @@ int vrh_measure(const vrt_voxel* voxels, int n, int texel16, float iso, const in
     return 0;
 }
 
+/* One side of vrh_contacts: n^3 VVoxel records (index x*n*n + z*n + y), only read, the slot's metric as vrt_volume_set_metric takes it
+   (texel16 != 0: the densities are the integer field +-q) and the placement as a vrt_instance holds it. */
+typedef struct vrh_placed_volume {
+    const vrt_voxel* voxels;
+    int32_t n;
+    int32_t texel16;
+    float extent, density_scale, step_max;
+    float position[3], rotation[4], scale[3];
+} vrh_placed_volume;
+
+/* VVolumeConverter::Contacts on caller records: margin, the records, their capacity and the result as vrt_query_contacts takes them
+   (contacts_or_null NULL with capacity 0: count only); clip == 0 walks all of a's cells instead of the conservative cell box.  0 / -1;
+   -2 with the result filled in and no record written: the capacity is too small. */
+int vrh_contacts(const vrh_placed_volume* a, const vrh_placed_volume* b, float margin, int clip, vrt_contact* contacts_or_null, size_t capacity,
+                 vrt_contacts_result* result) {
+    const auto good = [](const vrh_placed_volume* v) {
+        return v && v->voxels && v->n >= 2 && v->scale[0] != 0.f && v->scale[1] != 0.f && v->scale[2] != 0.f;
+    };
+    if (!good(a) || !good(b) || !result || !std::isfinite(margin) || margin < 0.f || (!contacts_or_null && capacity > 0)) {
+        g_error = "vrh_contacts: bad argument";
+        return -1;
+    }
+    const auto side = [](const vrh_placed_volume& v) {
+        Voxelizer::VVolumeConverter::VPlacedVolume s;
+        s.Voxels = reinterpret_cast<const Voxel::VVoxel*>(v.voxels);
+        s.N = (size_t)v.n;
+        s.Extent = v.extent;
+        s.Texel16 = v.texel16 != 0;
+        s.DensityScale = v.density_scale;
+        s.StepMax = v.step_max;
+        memcpy(s.Position, v.position, sizeof s.Position);
+        memcpy(s.Rotation, v.rotation, sizeof s.Rotation);
+        memcpy(s.Scale, v.scale, sizeof s.Scale);
+        return s;
+    };
+    std::vector<vrt_contact> found;
+    Voxelizer::VVolumeConverter::Contacts(side(*a), side(*b), margin, found, *result, clip != 0);
+    if (!contacts_or_null) return 0;
+    if (capacity < found.size()) {
+        g_error = "vrh_contacts: capacity too small";
+        return -2;
+    }
+    if (!found.empty()) memcpy(contacts_or_null, found.data(), found.size() * sizeof(vrt_contact));
+    return 0;
+}
+
 /* VVolumeConverter::Stamp on caller records: nd^3 destination records edited in place and ns^3 source records only read (index
    x*n*n + z*n + y); extent and density_scale of each grid give its density units per cell as vrt_volume_stamp derives them; texel16 != 0:
    that grid's densities are the integer field +-q; result_or_null as vrt_volume_stamp reports.  The record passes the argument rules of

@@ -144,8 +144,8 @@ enum BufferId {
     kBufCompTable,     /* ... and the component table */
     kBufRedistTable,   /* vrt_volume_redistance: the tile table ... */
     kBufRedistSurfels, /* ... and the compact surfels */
-    kBufMeshScratch,   /* vrt_volume_extract_mesh: the runs' records with their scan ... */
-    kBufMeshOut,       /* ... and the staged mesh */
+    kBufMeshScratch,   /* vrt_volume_extract_mesh and vrt_query_contacts: the runs' records with their scan ... */
+    kBufMeshOut,       /* ... and the staged mesh or contact records (both calls are synchronous, so one pair serves the two) */
     kBufSmoothWarp,    /* vrt_volume_smooth: two fp32 copies of the work box and its weights; vrt_volume_warp: the value to store and the
                           new id of every sample of the region's box (one buffer for the two calls) */
     kBufQuery,         /* vrt_trace_rays_host: the rays and then the hit records of a batch; vrt_query_points_host: the points and then

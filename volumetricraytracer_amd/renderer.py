@@ -25,6 +25,9 @@ POINT_DTYPE = np.dtype([("position", "<f4", 3), ("reserved_", "<f4")])
 POINT_RESULT_DTYPE = np.dtype([("distance", "<f4"), ("normal", "<f4", 3), ("instance", "<i4"), ("voxel", "<i4", 3), ("material", "<u4"),
                                ("flags", "<u4"), ("moves", "<u4"), ("position", "<f4", 3), ("reserved_", "<u4", 2)])
 assert POINT_DTYPE.itemsize == C.sizeof(_abi.vrt_point) and POINT_RESULT_DTYPE.itemsize == C.sizeof(_abi.vrt_point_result)
+CONTACT_DTYPE = np.dtype([("position", "<f4", 3), ("distance", "<f4"), ("normal", "<f4", 3), ("material_a", "<u4"), ("normal_a", "<f4", 3),
+                          ("material_b", "<u4"), ("cell_a", "<i4", 3), ("reserved_", "<u4")])
+assert CONTACT_DTYPE.itemsize == C.sizeof(_abi.vrt_contact)
 
 
 def make_points(points) -> np.ndarray:
@@ -40,6 +43,13 @@ def point_results_to_dict(res: np.ndarray) -> dict:
     return {"distance": res["distance"].copy(), "normal": res["normal"].copy(), "instance": res["instance"].copy(),
             "voxel": res["voxel"].copy(), "material": res["material"].copy(), "sampled": (res["flags"] & _abi.POINT_SAMPLED) != 0,
             "moves": res["moves"].copy(), "position": res["position"].copy()}
+
+
+def contacts_to_dict(rec: np.ndarray, res: "_abi.vrt_contacts_result") -> dict:
+    """A CONTACT_DTYPE array and its vrt_contacts_result as one dict: the records' fields as separate numpy arrays, and the result's."""
+    out = {k: rec[k].copy() for k in ("position", "distance", "normal", "material_a", "normal_a", "material_b", "cell_a")}
+    out.update(_abi.contacts_result_dict(res))
+    return out
 
 
 def make_rays(origins, directions, t_max=10000.0) -> np.ndarray:
@@ -786,6 +796,22 @@ class VHipRenderer:
         """The points moved onto the nearest surface: up to `iterations` moves of p - normal * distance, stopping within `tolerance`
         (world units) of it; the records of the moved points, `position` being where they ended."""
         return self.query_points(points, iterations=iterations, tolerance=tolerance)
+
+    # -- contact queries (vrt_query_contacts) ----------------------------------------------------------------------------------------
+    def query_contacts(self, a: int, b: int, margin: float = 0.0) -> dict:
+        """Where the surface of instance `a` of the synced scene touches or enters instance `b`, on the GPU (vrt_query_contacts: counted,
+        then fetched): the points of a's surface whose distance to b's surface is <= margin (world units), in the order of a's cells.  A
+        dict of numpy arrays position, distance, normal, material_a, normal_a, material_b, cell_a, with the result's lo, hi, contacts,
+        candidates and min_distance.  One-sided: swap a and b for b's surface in a.  Syncs the scene first."""
+        self._require()
+        self.SyncWithScene()
+        res = _abi.vrt_contacts_result()
+        call = self._lib.vrt_query_contacts
+        _abi.check(call(self._ctx, int(a), int(b), float(margin), None, 0, C.byref(res)), "vrt_query_contacts")
+        rec = np.zeros(int(res.contacts), CONTACT_DTYPE)
+        if len(rec):
+            _abi.check(call(self._ctx, int(a), int(b), float(margin), rec.ctypes.data_as(C.c_void_p), len(rec), C.byref(res)), "vrt_query_contacts")
+        return contacts_to_dict(rec, res)
 
     # -- multi-GPU exchange, one process per GPU (vrt_comm_* / vrt_gather_tiles: RCCL ncclGather) --------------------
     @staticmethod

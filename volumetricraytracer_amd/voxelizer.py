@@ -57,6 +57,9 @@ def load_host() -> C.CDLL:
         lib.vrh_extract_mesh.restype = C.c_int
         lib.vrh_extract_mesh.argtypes = [C.c_void_p, C.c_int, C.c_float, C.c_int, C.c_float, C.POINTER(C.c_int), C.POINTER(C.c_int), C.c_void_p,
                                          C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.POINTER(_abi.vrt_mesh_result)]
+        lib.vrh_contacts.restype = C.c_int
+        lib.vrh_contacts.argtypes = [C.POINTER(vrh_placed_volume), C.POINTER(vrh_placed_volume), C.c_float, C.c_int, C.c_void_p, C.c_size_t,
+                                     C.POINTER(_abi.vrt_contacts_result)]
         lib.vrh_measure.restype = C.c_int
         lib.vrh_measure.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_float, C.POINTER(C.c_int), C.POINTER(C.c_int),
                                     C.POINTER(_abi.vrt_measure_result), C.POINTER(C.c_uint64)]
@@ -250,6 +253,47 @@ def extract_mesh_host(vol: VVoxelVolume, iso: float = 0.0, lo=None, hi=None, tex
                                   C.byref(res)) != 0:
         raise RuntimeError("vrh_extract_mesh: " + lib.vrh_last_error().decode(errors="replace"))
     return positions, normals, materials, indices, {"vertices": V, "quads": Q, "lo": tuple(res.lo), "hi": tuple(res.hi)}
+
+
+class vrh_placed_volume(C.Structure):
+    """One side of vrh_contacts (csrc/host/host_c_api.cpp)."""
+    _fields_ = [("voxels", C.c_void_p), ("n", C.c_int32), ("texel16", C.c_int32), ("extent", C.c_float), ("density_scale", C.c_float),
+                ("step_max", C.c_float), ("position", C.c_float * 3), ("rotation", C.c_float * 4), ("scale", C.c_float * 3)]
+
+
+def contacts_host(stored_a, material_a, placed_a: dict, stored_b, material_b, placed_b: dict, margin: float = 0.0, clip: bool = True) -> dict:
+    """VVolumeConverter::Contacts (the host build of vrt_query_contacts' rule): where the surface of volume a touches or enters volume b.
+    stored_*: what a slot's dense grid holds, float32 [x, z, y] (texel16: the integer field +-q); material_*: the ids, uint8, same order
+    (None: zeros); placed_*: {"extent", and optionally "texel16", "density_scale", "step_max", "position", "rotation" (x, y, z, w),
+    "scale"}.  clip = False walks all of a's cells instead of the rule's conservative cell box: the same output.  Returns
+    renderer.contacts_to_dict's dict."""
+    from .renderer import CONTACT_DTYPE, contacts_to_dict
+
+    lib = load_host()
+    keep = []
+
+    def side(stored, material, placed):
+        stored = np.asarray(stored, np.float32)
+        n = stored.shape[0]
+        rec = np.zeros(n ** 3, dtype=np.dtype([("material", "u1"), ("pad", "u1", 3), ("density", "<f4")]))
+        rec["density"] = stored.reshape(-1)
+        if material is not None:
+            rec["material"] = np.asarray(material, np.uint8).reshape(-1)
+        keep.append(rec)
+        return vrh_placed_volume(rec.ctypes.data, n, int(bool(placed.get("texel16", False))), float(placed["extent"]),
+                                 float(placed.get("density_scale", 1.0)), float(placed.get("step_max", 0.0)),
+                                 (C.c_float * 3)(*[float(x) for x in placed.get("position", (0.0, 0.0, 0.0))]),
+                                 (C.c_float * 4)(*[float(x) for x in placed.get("rotation", (0.0, 0.0, 0.0, 1.0))]),
+                                 (C.c_float * 3)(*[float(x) for x in placed.get("scale", (1.0, 1.0, 1.0))]))
+
+    a, b = side(stored_a, material_a, placed_a), side(stored_b, material_b, placed_b)
+    res = _abi.vrt_contacts_result()
+    if lib.vrh_contacts(C.byref(a), C.byref(b), float(margin), int(bool(clip)), None, 0, C.byref(res)) != 0:
+        raise RuntimeError("vrh_contacts: " + lib.vrh_last_error().decode(errors="replace"))
+    rec = np.zeros(int(res.contacts), CONTACT_DTYPE)
+    if len(rec) and lib.vrh_contacts(C.byref(a), C.byref(b), float(margin), int(bool(clip)), rec.ctypes.data, len(rec), C.byref(res)) != 0:
+        raise RuntimeError("vrh_contacts: " + lib.vrh_last_error().decode(errors="replace"))
+    return contacts_to_dict(rec, res)
 
 
 def measure_host(vol: VVoxelVolume, iso: float = 0.0, lo=None, hi=None, texel16: bool = False) -> dict:
