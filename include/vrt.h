@@ -1052,6 +1052,85 @@ int vrt_volume_history_info(vrt_ctx* ctx, int slot, vrt_history_info* out);
 int vrt_volume_undo(vrt_ctx* ctx, int slot, int steps, vrt_brush_result* result_or_null);
 int vrt_volume_redo(vrt_ctx* ctx, int slot, int steps, vrt_brush_result* result_or_null);
 
+/* A slot's mask (no reference analogue): protected samples that the volume edit calls leave alone.  A slot may carry a mask of one bit
+ * per grid sample, replicated on every device as the slot is; a set bit means PROTECTED.  A slot has no mask until vrt_volume_mask_apply
+ * or _mask_upload gives it one.
+ *
+ * The rule.  Seven calls honour the mask of the slot they write: vrt_volume_apply_brushes, _stamp (the destination's mask; a mask on
+ * the source slot is ignored), _smooth, _warp, _fill_enclosed, _components and _redistance.  An honouring call runs exactly as it does
+ * without a mask; then every protected sample gets back the stored density bits and the material id it had when the call began, and
+ * everything the slot derives is rebuilt as after any edit: afterwards every vrt_debug_volume_bytes buffer equals what a full upload of
+ * where(mask, before, unmasked result) holds.  Exact to the bit: the put-back compares and copies bits (a VRT_FORMAT_TEXEL16 slot's
+ * own float of +-q, NaN payloads, -0.0f).  Protected samples are still READ by the call — smooth's neighbour means, redistance's
+ * seeds — so they act as fixed boundary values; a call that iterates (smooth, fill) may move them between its own iterations, and only
+ * the state at its end counts.
+ * The call's result record (vrt_brush_result, vrt_fill_result, vrt_components_result, vrt_redistance_result) is that of the unmasked
+ * run: it reports what the call wrote BEFORE protection put samples back, and the box rebuilt is that box.  How many samples were put
+ * back is vrt_mask_info::restored: the protected samples whose density bits or material id differed from what they were when the call
+ * began, in the latest honouring call on the slot that edited, on device 0 (0 for a call whose footprint misses every protected sample).
+ * A call that ends before it edits — a refused argument, brushes none of which reaches the grid, VRT_COMPONENTS_REPORT, a components
+ * call that finds nothing to remove — is not such a call and leaves `restored` as it stood.
+ * What does not honour the mask.  vrt_volume_update_region and _update_voxels write through it: the host is the authority over its own
+ * uploads.  vrt_volume_undo and _redo write through it: an undo must restore exactly.  Every full upload into the slot
+ * (vrt_volume_upload, _upload_voxels, _upload_texels, vrt_voxelize_mesh) and vrt_volume_free drop the slot's mask.
+ * The mask is no part of the edit history: a slot whose history is on records the tiles that differ AFTER the put-back (a masked edit
+ * that ends with no bit changed records nothing and keeps the redo stack), and neither undo nor redo changes the mask.
+ * A mask without a set bit behaves, observably, as no mask, with restored = 0, and costs an edit nothing.  Otherwise an honouring call
+ * copies its footprint aside first (5 B per sample, as the history does, once for both), allocated on every device before any sample is
+ * written: VRT_ERR_OOM, and the volume untouched, when that fails. */
+#define VRT_MAX_MASK_OPS   32
+#define VRT_MAX_MASK_STEPS 64
+enum { VRT_MASK_ALL = 0, VRT_MASK_SHAPE = 1, VRT_MASK_MATERIAL = 2, VRT_MASK_SOLID = 3,
+       VRT_MASK_INVERT = 4, VRT_MASK_GROW = 5, VRT_MASK_SHRINK = 6 };
+typedef struct vrt_mask_op {          /* 64 B */
+    int32_t kind, value;              /* value: 1 protect, 0 release (ALL, SHAPE, MATERIAL, SOLID); must be 0 otherwise */
+    int32_t shape;                    /* SHAPE: VRT_BRUSH_SPHERE / _BOX / _CAPSULE */
+    float a[3], b[3], radius;         /* SHAPE: as vrt_brush, cells / grid coordinates */
+    int32_t material;                 /* MATERIAL: 0..255 */
+    int32_t steps;                    /* GROW, SHRINK: 1..VRT_MAX_MASK_STEPS */
+    uint32_t reserved_[4];            /* 0 */
+} vrt_mask_op;
+typedef struct vrt_mask_info {        /* 48 B */
+    int32_t on, pad_;                 /* the slot has a mask (even one without a set bit) */
+    uint64_t masked;                  /* set bits */
+    int32_t lo[3], hi[3];             /* xyz, inclusive, of the set bits; lo > hi ({N, N, N}, {-1, -1, -1}) when none */
+    uint64_t restored;                /* see the rule */
+} vrt_mask_info;
+/* Gives a slot without a mask an all-zero one, then applies the n records in order, each to what the one before left (one call with n
+ * records leaves what n calls of one record leave):
+ *   ALL       every sample gets `value`.
+ *   SHAPE     every sample with s <= 0 gets `value`; s is the distance of vrt_brush's shapes at p = ((float)ix, (float)iy, (float)iz),
+ *             the arithmetic written out at vrt_brush and VRT_BRUSH_PAINT's test.
+ *   MATERIAL  every sample whose material id equals `material` gets `value`.
+ *   SOLID     every sample that is INSIDE at iso 0 gets `value`: rule 1 of vrt_volume_extract_mesh, !(d > 0) on the decoded density
+ *             (NaN is INSIDE).
+ *   INVERT    every bit flips.
+ *   GROW      `steps` times: a sample becomes protected when it or one of its six axis neighbours inside the grid is.
+ *   SHRINK    `steps` times: the complement of GROW applied to the complement — a sample stays protected only when it and all of its
+ *             six neighbours inside the grid are; beyond the grid's faces counts as protected, so a mask is not eaten from the boundary.
+ * Like the edit calls, waits for work enqueued on the context's devices first; writes nothing to the slot's volume buffers.
+ * info_or_null: the slot's vrt_mask_info after the call (`restored` as it stood).
+ * Errors, all checked before any device state is touched: VRT_ERR_INVALID for a NULL context, NULL records with n > 0, n outside
+ * 0..VRT_MAX_MASK_OPS, an unknown kind or shape, a `value` other than 0 or 1 or non-zero where it must be 0, a SHAPE record that
+ * vrt_volume_apply_brushes would refuse as a PAINT region (non-finite fields, radius / half sizes not positive, capsule a == b), a
+ * MATERIAL record's material outside 0..255, a GROW / SHRINK record's steps outside 1..VRT_MAX_MASK_STEPS, non-zero reserved words;
+ * VRT_ERR_SLOT for an unused slot; VRT_ERR_OOM when the mask or its scratch cannot be allocated — the slot and any mask it had are
+ * then untouched. */
+int vrt_volume_mask_apply(vrt_ctx* ctx, int slot, int n, const vrt_mask_op* ops, vrt_mask_info* info_or_null);
+/* Replaces the slot's mask (or gives it one): N^3 bytes in grid order (x slowest, y fastest, as vrt_volume_upload's material array),
+ * non-zero = protected.  Waits like vrt_volume_mask_apply.  VRT_ERR_INVALID for a NULL context or NULL bytes, VRT_ERR_SLOT,
+ * VRT_ERR_OOM as there. */
+int vrt_volume_mask_upload(vrt_ctx* ctx, int slot, const uint8_t* bytes);
+/* N^3 bytes of 0 / 1 in the same order, from device 0; a slot without a mask gives zeros.  VRT_ERR_INVALID for a NULL context or a
+ * NULL out, VRT_ERR_SLOT, VRT_ERR_OOM when the staging copy cannot be allocated. */
+int vrt_volume_mask_download(vrt_ctx* ctx, int slot, uint8_t* out);
+/* Frees the slot's mask on every device (after the work enqueued there); fine on a slot without one.  VRT_ERR_INVALID for a NULL
+ * context, VRT_ERR_SLOT for an unused slot. */
+int vrt_volume_mask_clear(vrt_ctx* ctx, int slot);
+/* The slot's mask as it stands (all zero, lo / hi "none", on a slot without one).  VRT_ERR_INVALID for a NULL context or a NULL out,
+ * VRT_ERR_SLOT for an unused slot. */
+int vrt_volume_mask_info(vrt_ctx* ctx, int slot, vrt_mask_info* out);
+
 /* Tests: the raw bytes of one device buffer of a slot on device `device_index` of the context.  *size_out (when not NULL) = the
  * buffer's size; out == NULL only asks for it; a capacity below the size is VRT_ERR_INVALID.  The tables are the first nb^3
  * entries (without their build scratch); SKIP and NIB are empty while the slot has no empty-space table (step_max <= 0);

@@ -448,6 +448,36 @@ HISTORY_TILE_BYTES = 336
 
 REDISTANCE_FROM_BOTH, REDISTANCE_FROM_OUTSIDE, REDISTANCE_FROM_INSIDE = 0, 1, 2
 
+# vrt_volume_mask_apply
+MAX_MASK_OPS = 32
+MAX_MASK_STEPS = 64
+MASK_ALL, MASK_SHAPE, MASK_MATERIAL, MASK_SOLID, MASK_INVERT, MASK_GROW, MASK_SHRINK = 0, 1, 2, 3, 4, 5, 6
+
+
+class vrt_mask_op(C.Structure):
+    _fields_ = [("kind", C.c_int32), ("value", C.c_int32), ("shape", C.c_int32), ("a", C.c_float * 3), ("b", C.c_float * 3),
+                ("radius", C.c_float), ("material", C.c_int32), ("steps", C.c_int32), ("reserved_", C.c_uint32 * 4)]
+
+
+class vrt_mask_info(C.Structure):
+    _fields_ = [("on", C.c_int32), ("pad_", C.c_int32), ("masked", C.c_uint64), ("lo", C.c_int32 * 3), ("hi", C.c_int32 * 3),
+                ("restored", C.c_uint64)]
+
+
+def mask_op(kind: int, value: int = 0, shape: int = 0, a=(0.0, 0.0, 0.0), b=(0.0, 0.0, 0.0), radius: float = 0.0, material: int = 0,
+            steps: int = 0) -> "vrt_mask_op":
+    """A vrt_mask_op record (vrt.h): kind MASK_*; value 1 protects and 0 releases; shape, a, b, radius as a vrt_brush has them."""
+    r = vrt_mask_op()
+    r.kind, r.value, r.shape, r.radius, r.material, r.steps = int(kind), int(value), int(shape), float(radius), int(material), int(steps)
+    for i in range(3):
+        r.a[i], r.b[i] = float(a[i]), float(b[i])
+    return r
+
+
+def mask_info_dict(info: "vrt_mask_info") -> dict:
+    """A vrt_mask_info as plain Python values."""
+    return {"on": int(info.on), "masked": int(info.masked), "lo": tuple(info.lo), "hi": tuple(info.hi), "restored": int(info.restored)}
+
 SYMBOLS = {
     "vrt_create": (C.c_int, [C.POINTER(C.c_void_p), C.c_int, C.POINTER(C.c_int)]),
     "vrt_destroy": (C.c_int, [C.c_void_p]),
@@ -487,6 +517,11 @@ SYMBOLS = {
     "vrt_volume_history_info": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(vrt_history_info)]),
     "vrt_volume_undo": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.POINTER(vrt_brush_result)]),
     "vrt_volume_redo": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.POINTER(vrt_brush_result)]),
+    "vrt_volume_mask_apply": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.POINTER(vrt_mask_op), C.POINTER(vrt_mask_info)]),
+    "vrt_volume_mask_upload": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p]),
+    "vrt_volume_mask_download": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p]),
+    "vrt_volume_mask_clear": (C.c_int, [C.c_void_p, C.c_int]),
+    "vrt_volume_mask_info": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(vrt_mask_info)]),
     "vrt_debug_volume_bytes": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_size_t, C.POINTER(C.c_size_t)]),
     "vrt_env_upload": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p]),
     "vrt_scene_set": (C.c_int, [C.c_void_p, C.POINTER(vrt_scene)]),

@@ -928,6 +928,41 @@ bool VHipRenderer::Undo(const Scene::VVoxelObject& object, int steps, vrt_brush_
 
 bool VHipRenderer::Redo(const Scene::VVoxelObject& object, int steps, vrt_brush_result* result) { return StepHistory(object, steps, true, result); }
 
+bool VHipRenderer::MaskVolume(const Scene::VVoxelObject& object, const std::vector<vrt_mask_op>& ops, vrt_mask_info* info) {
+    const int slot = SyncedSlotOf(object, "MaskVolume");
+    if (slot < 0 || ops.size() > (size_t)VRT_MAX_MASK_OPS) return false;
+    return ok(vrt_volume_mask_apply(Ctx, slot, (int)ops.size(), ops.empty() ? nullptr : ops.data(), info), "vrt_volume_mask_apply");
+}
+
+bool VHipRenderer::SetMask(const Scene::VVoxelObject& object, const std::vector<uint8_t>& bytes) {
+    const int slot = SyncedSlotOf(object, "SetMask");
+    if (slot < 0) return false;
+    const size_t n = object.GetVoxelVolume()->GetSize();
+    if (bytes.size() != n * n * n) {
+        V_LOG_ERROR("SetMask(): the mask needs one byte per voxel of the volume");
+        return false;
+    }
+    return ok(vrt_volume_mask_upload(Ctx, slot, bytes.data()), "vrt_volume_mask_upload");
+}
+
+bool VHipRenderer::GetMask(const Scene::VVoxelObject& object, std::vector<uint8_t>& bytes) {
+    const int slot = SyncedSlotOf(object, "GetMask");
+    if (slot < 0) return false;
+    const size_t n = object.GetVoxelVolume()->GetSize();
+    bytes.resize(n * n * n);
+    return ok(vrt_volume_mask_download(Ctx, slot, bytes.data()), "vrt_volume_mask_download");
+}
+
+bool VHipRenderer::ClearMask(const Scene::VVoxelObject& object) {
+    const int slot = SyncedSlotOf(object, "ClearMask");
+    return slot >= 0 && ok(vrt_volume_mask_clear(Ctx, slot), "vrt_volume_mask_clear");
+}
+
+bool VHipRenderer::MaskInfo(const Scene::VVoxelObject& object, vrt_mask_info& out) {
+    const int slot = SyncedSlotOf(object, "MaskInfo");
+    return slot >= 0 && ok(vrt_volume_mask_info(Ctx, slot, &out), "vrt_volume_mask_info");
+}
+
 bool VHipRenderer::SetPalette(const Scene::VVoxelObject& object, const std::vector<VMaterial>& entries) {
     const int slot = SyncedSlotOf(object, "SetPalette");
     if (slot < 0) return false;

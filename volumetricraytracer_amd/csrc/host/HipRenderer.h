@@ -152,6 +152,19 @@ public:
     bool HistoryInfo(const Scene::VVoxelObject& object, vrt_history_info& out);
     bool Undo(const Scene::VVoxelObject& object, int steps = 1, vrt_brush_result* result = nullptr);
     bool Redo(const Scene::VVoxelObject& object, int steps = 1, vrt_brush_result* result = nullptr);
+    /* Protected voxels (vrt_volume_mask_*; the rule: vrt.h) for the volume of a placed object of the scene Render() would draw now
+       (synced first): ApplyBrushes, StampVolume, SmoothVolume, WarpVolume, FillEnclosed, Components and Redistance leave a protected
+       voxel as it was, while an upload of the host volume's dirty box, Undo and Redo write through.  MaskVolume applies records
+       (at most VRT_MAX_MASK_OPS: all, a brush shape, a material id, the solid voxels, invert, grow, shrink) to the mask in order, giving
+       the volume an empty mask first when it has none; SetMask / GetMask move a whole mask as one byte per voxel (index
+       x*n*n + z*n + y, non-zero = protected); ClearMask takes it away; MaskInfo reports the protected voxels' count and box and how
+       many of them the latest edit had changed and got back.  The mask stays with the slot until the volume is uploaded whole again or
+       leaves the scene.  False (after logging) on failure or when the object's volume is not in the scene. */
+    bool MaskVolume(const Scene::VVoxelObject& object, const std::vector<vrt_mask_op>& ops, vrt_mask_info* info = nullptr);
+    bool SetMask(const Scene::VVoxelObject& object, const std::vector<uint8_t>& bytes);
+    bool GetMask(const Scene::VVoxelObject& object, std::vector<uint8_t>& bytes);
+    bool ClearMask(const Scene::VVoxelObject& object);
+    bool MaskInfo(const Scene::VVoxelObject& object, vrt_mask_info& out);
     /* Per-voxel materials (vrt_volume_set_palette; the rule: vrt.h) for the volume of a placed object of the scene Render() would draw
        now (synced first): entry i is the surface of the voxels whose material id is i (what VRT_BRUSH_PAINT writes), ids beyond the
        palette keep the volume's own VMaterial; of an entry's VMaterial the albedo colour, roughness and metallic count, the textures

@@ -4,6 +4,7 @@
 #include "../components_core.h"
 #include "../fill_core.h"
 #include "../grid_core.h"
+#include "../mask_core.h"
 #include "../contacts_core.h"
 #include "../measure_core.h"
 #include "../mesh_core.h"
@@ -662,6 +663,73 @@ VVolumeConverter::VStampResult VVolumeConverter::Warp(Voxel::VVoxelVolume& volum
     const VStampResult out = Warp(volume.GetVoxels().data(), volume.GetSize(), unit, false, warp);
     if (out.Written) volume.MakeDirty();
     return out;
+}
+
+bool VVolumeConverter::MaskOps(const Voxel::VVoxel* voxels, size_t n, bool texel16, uint8_t* maskBytes, int nOps, const ::vrt_mask_op* ops,
+                               ::vrt_mask_info* info_or_null) {
+    namespace M = vrt_mask_core;
+    const int N = (int)n;
+    if (!M::valid_mask_ops(nOps, ops)) return false;
+    /* the bytes as the device keeps them: words of 64 samples along y */
+    const int W = M::row_words(N);
+    std::vector<uint64_t> mask(M::word_count(N), 0ull), next;
+    for (int x = 0; x < N; x++)
+        for (int z = 0; z < N; z++)
+            for (int y = 0; y < N; y++)
+                if (maskBytes[vrt_grid::index(N, x, y, z)]) mask[M::word_index(N, x, z, y >> 6)] |= 1ull << (y & 63);
+    for (int r = 0; r < nOps; r++) {
+        const ::vrt_mask_op& op = ops[r];
+        if (op.kind == VRT_MASK_INVERT) {
+            for (size_t i = 0; i < mask.size(); i++) mask[i] ^= M::live_bits(N, (int)(i % (size_t)W));
+        } else if (op.kind == VRT_MASK_GROW || op.kind == VRT_MASK_SHRINK) {
+            const bool shrink = op.kind == VRT_MASK_SHRINK;
+            for (int s = 0; s < op.steps; s++) {
+                next.assign(mask.size(), 0ull);
+                const auto word = [&](int x, int z, int j) -> uint64_t {
+                    if (x < 0 || x >= N || z < 0 || z >= N || j < 0 || j >= W) return 0ull;
+                    const uint64_t v = mask[M::word_index(N, x, z, j)];
+                    return shrink ? M::shrink_in(v, M::live_bits(N, j)) : v;
+                };
+                for (int x = 0; x < N; x++)
+                    for (int z = 0; z < N; z++)
+                        for (int j = 0; j < W; j++) {
+                            const uint64_t live = M::live_bits(N, j);
+                            const uint64_t grown = M::grow_word(word(x, z, j), word(x, z, j - 1), word(x, z, j + 1), word(x - 1, z, j),
+                                                                word(x + 1, z, j), word(x, z - 1, j), word(x, z + 1, j), live);
+                            next[M::word_index(N, x, z, j)] = shrink ? M::shrink_out(grown, live) : grown;
+                        }
+                mask.swap(next);
+            }
+        } else { /* the selecting kinds, over every sample: a SHAPE's box is an optimisation of the device's */
+            for (int x = 0; x < N; x++)
+                for (int z = 0; z < N; z++)
+                    for (int j = 0; j < W; j++) {
+                        uint64_t sel = 0ull;
+                        for (int y = j * 64; y < std::min(N, j * 64 + 64); y++) {
+                            const Voxel::VVoxel& v = voxels[vrt_grid::index(N, x, y, z)];
+                            if (M::selects(op, x, y, z, v.Density, (unsigned)v.Material, texel16)) sel |= 1ull << (y & 63);
+                        }
+                        uint64_t& w = mask[M::word_index(N, x, z, j)];
+                        w = M::assign(w, sel, op.value);
+                    }
+        }
+    }
+    ::vrt_mask_info info;
+    memset(&info, 0, sizeof info);
+    info.on = 1;
+    for (int a = 0; a < 3; a++) info.lo[a] = N, info.hi[a] = -1;
+    for (int x = 0; x < N; x++)
+        for (int z = 0; z < N; z++)
+            for (int y = 0; y < N; y++) {
+                const bool set = (mask[M::word_index(N, x, z, y >> 6)] >> (y & 63)) & 1ull;
+                maskBytes[vrt_grid::index(N, x, y, z)] = set ? 1 : 0;
+                if (!set) continue;
+                const int p[3] = {x, y, z};
+                info.masked++;
+                for (int a = 0; a < 3; a++) info.lo[a] = std::min(info.lo[a], p[a]), info.hi[a] = std::max(info.hi[a], p[a]);
+            }
+    if (info_or_null) *info_or_null = info;
+    return true;
 }
 
 bool VVolumeConverter::ExtractResolutionFromName(const std::string& name, uint8_t& outResolution) {

@@ -24,6 +24,8 @@ struct vrt_components;
 struct vrt_component;
 struct vrt_components_result;
 struct vrt_measure_result;
+struct vrt_mask_op;
+struct vrt_mask_info;
 struct vrt_contact;
 struct vrt_contacts_result;
 
@@ -164,6 +166,13 @@ public:
        it is returned, after the fill of MakeSolid and ahead of MakeSdf's pass — on the device (vrt_volume_components) while
        UseDevice names a context, on the host otherwise; the same volume, bit for bit.  0 switches it off. */
     static void MakeMinIsland(uint64_t k);
+    /* The records of a vrt_volume_mask_apply call on a mask kept as bytes — the rule of that call (include/vrt.h; layout, predicates,
+       word arithmetic and argument rules are csrc/mask_core.h, shared with the HIP kernels), as plain loops: n^3 VVoxel records, only
+       read (index x*n*n + z*n + y; texel16: they hold the integer field +-q of a VRT_FORMAT_TEXEL16 slot), and n^3 mask bytes in the same
+       order, non-zero = protected on the way in, 0 / 1 on the way out.  info_or_null: the set bits' count and box as that call reports
+       them (`restored` 0).  False, and nothing written, for records that call refuses. */
+    static bool MaskOps(const Voxel::VVoxel* voxels, size_t n, bool texel16, uint8_t* maskBytes, int nOps, const ::vrt_mask_op* ops,
+                        ::vrt_mask_info* info_or_null = nullptr);
     static bool ExtractResolutionFromName(const std::string& name, uint8_t& outResolution);
     /* extraction threshold of a volume: cell size · √3 (VolumeConverter.cpp:57) */
     static float ExtractionThreshold(const Voxel::VVoxelVolume& volume);

@@ -42,6 +42,10 @@
  *                                           vrt_volume_set_palette: entry 0 the volume's own material, then K hues), and every dab is followed by a
  *                                           VRT_BRUSH_PAINT sphere of 1.5 R cells with material id 1 + dab % K: the carved surface comes out coloured.
  *                                           Under --undo the paint is an entry of its own, so K counts carves and paints alike
+ *            [--edit-mask]                  with --edit-device or --edit-stamp: before the first dab the half x < N / 2 of the first object's volume is
+ *                                           protected with one BOX record (VHipRenderer::MaskVolume, vrt_volume_mask_apply), so the carved track stops
+ *                                           at that plane: every dab, smooth, grab and redistance leaves the protected voxels as they were; after the last
+ *                                           frame the mask's state is printed
  *            [--keep-largest]               after the last frame, ahead of --mesh-out: of the first object's volume only the largest connected piece stays
  *                                           (VHipRenderer::Components, vrt_volume_components, KEEP_LARGEST, gap half a cell, material 0): what a carve cut
  *                                           loose does not reach the mesh
@@ -143,7 +147,7 @@ int main(int argc, char** argv) {
     int paintK = 0, paintDabs = 0, paintedDabs = 0;
     bool identityDefaults = false;
     int editBrush = 0, sdf = 0;
-    bool editFull = false, editDevice = false, editStamp = false, solid = false;
+    bool editFull = false, editDevice = false, editStamp = false, editMask = false, solid = false;
     float editSmooth = 0.f, editGrab = 0.f;
     bool pick = false;
     int pickX = 0, pickY = 0;
@@ -168,6 +172,7 @@ int main(int argc, char** argv) {
         else if (!strcmp(argv[i], "--edit-full")) editFull = true;
         else if (!strcmp(argv[i], "--edit-device")) editDevice = true;
         else if (!strcmp(argv[i], "--edit-stamp")) editStamp = editDevice = true;
+        else if (!strcmp(argv[i], "--edit-mask")) editMask = true;
         else if (!strcmp(argv[i], "--edit-smooth") && i + 1 < argc) editSmooth = (float)atof(argv[++i]);
         else if (!strcmp(argv[i], "--edit-grab") && i + 1 < argc) editGrab = (float)atof(argv[++i]);
         else if (!strcmp(argv[i], "--solid")) solid = true;
@@ -297,6 +302,10 @@ int main(int argc, char** argv) {
         fprintf(stderr, "--paint K colours what the device-side dabs touch: it needs --edit-brush with --edit-device, and 1 <= K <= %d\n", VRT_MAX_PALETTE - 1);
         return 1;
     }
+    if (editMask && (!hip || !editDevice || editBrush <= 0)) {
+        fprintf(stderr, "--edit-mask protects half of the volume from the device-side dabs: it needs --edit-brush with --edit-device or --edit-stamp\n");
+        return 1;
+    }
     if (sdf != 0 && (!solid || sdf < 1 || sdf > 15)) {
         fprintf(stderr, "--sdf BAND (1..15) redistances what --solid filled: give both\n");
         return 1;
@@ -357,6 +366,21 @@ int main(int argc, char** argv) {
             palette.push_back(m);
         }
         if (!hip->SetPalette(*first, palette)) return 1;
+    }
+    if (editMask) { /* --edit-mask: one BOX record over the samples with x < N / 2, ahead of the first dab */
+        if (!first) return 1;
+        const float n = (float)first->GetVoxelVolume()->GetSize(), mid = 0.5f * (n - 1.f);
+        vrt_mask_op box;
+        memset(&box, 0, sizeof box);
+        box.kind = VRT_MASK_SHAPE;
+        box.value = 1;
+        box.shape = VRT_BRUSH_BOX;
+        box.a[0] = 0.f, box.a[1] = mid, box.a[2] = mid;
+        box.b[0] = std::floor(0.5f * n) - 0.5f, box.b[1] = n, box.b[2] = n;
+        vrt_mask_info info;
+        if (!hip->MaskVolume(*first, {box}, &info)) return 1;
+        scene->PostRender(); /* the scene is on the device now: no dab is followed by an upload that would drop the mask */
+        printf("mask: %llu voxels protected, x %d..%d\n", (unsigned long long)info.masked, info.lo[0], info.hi[0]);
     }
     const std::shared_ptr<Voxel::VVoxelVolume> stampTorus = editStamp ? InitStampTorus() : nullptr;
     int stampTurns = 0;
@@ -525,6 +549,12 @@ int main(int argc, char** argv) {
     if (paintK > 0) printf("paint: %d of %d dabs painted with ids 1..%d, rendered through a palette of %d entries\n", paintedDabs, paintDabs, paintK, paintK + 1);
     if (editStamp) printf("stamp: %d torus stamps wrote %llu voxels on the device\n", stampTurns, stampedVoxels);
     if (editGrab != 0.f) printf("grab: %g cells pulled %llu voxels around the brush positions on the device\n", editGrab, warpedVoxels);
+    if (editMask) {
+        vrt_mask_info info;
+        if (!hip->MaskInfo(*first, info)) return 1;
+        printf("mask: on %d, %llu voxels protected; the last edit had changed %llu of them and got them back\n", info.on,
+               (unsigned long long)info.masked, (unsigned long long)info.restored);
+    }
     if (editSmooth > 0.f) printf("smooth: strength %g relaxed %llu voxels around the dabs on the device\n", editSmooth, smoothedVoxels);
     if (editBrush > 0)
         printf("brush of %d cells, %s; ", editBrush, editGrab != 0.f ? "device grabs" : editStamp ? "device stamps" : (editDevice ? "device brushes" : (editFull ? "full uploads" : "region updates")));

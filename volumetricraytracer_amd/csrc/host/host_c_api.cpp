@@ -287,6 +287,19 @@ int vrh_components(vrt_voxel* voxels, int n, int texel16, const vrt_components* 
     return rc;
 }
 
+/* VVolumeConverter::MaskOps on caller arrays: n^3 records only read (index x*n*n + z*n + y; texel16 != 0: the densities are the integer
+   field +-q) and n^3 mask bytes in the same order, edited in place (non-zero = protected in, 0 / 1 out); ops and info_or_null as
+   vrt_volume_mask_apply takes them, and its return value: VRT_OK, or VRT_ERR_INVALID as that call returns it (a NULL pointer or a grid
+   below 2 samples likewise) — nothing is written then. */
+int vrh_mask_apply(const vrt_voxel* voxels, int n, int texel16, uint8_t* mask_bytes, int n_ops, const vrt_mask_op* ops, vrt_mask_info* info_or_null) {
+    if (!voxels || !mask_bytes || n < 2 ||
+        !Voxelizer::VVolumeConverter::MaskOps(reinterpret_cast<const Voxel::VVoxel*>(voxels), (size_t)n, texel16 != 0, mask_bytes, n_ops, ops, info_or_null)) {
+        g_error = "vrh_mask_apply: bad argument";
+        return VRT_ERR_INVALID;
+    }
+    return VRT_OK;
+}
+
 /* VGLTFImporter::ImportScene on a .gltf / .glb file, mesh `mesh` (its index in the file): counts_out[2] = vertices, indices; the
    positions as the importer hands them to the converter (x100, re-centred on the bounds' middle; 3 floats per vertex) and the indices
    are copied when their pointer is given and the capacity suffices; name_out receives the mesh's name.  0 / -1. */

@@ -51,6 +51,17 @@ struct DeviceVolume {
     /* 2 x nb^3 bytes, the seeds (0 / 255) of the level-1 table (valid while skip_valid) and of the Cube table (always valid) — the tables
        keep distances, from which an edit could not recover the seeds. */
     uint8_t* seeds = nullptr;
+    /* the slot's mask (vrt_volume_mask_*): one bit per sample in mask_core.h's layout, or nullptr while the slot has none */
+    uint64_t* mask = nullptr;
+};
+
+/* A slot's mask as the host knows it (the bits live on every device, DeviceVolume::mask): the count of set bits and their box, kept
+   after every call that changes the mask, so that an edit of a slot whose mask has no set bit launches nothing for it. */
+struct HostMask {
+    bool on = false;
+    uint64_t masked = 0;
+    int lo[3] = {0, 0, 0}, hi[3] = {-1, -1, -1}; /* xyz, inclusive; lo > hi when masked == 0 */
+    uint64_t restored = 0;                       /* vrt_mask_info::restored */
 };
 
 /* A slot's edit history (vrt_volume_history).  The stacks exist once, on the host: one tile count per entry, oldest first in
@@ -153,6 +164,8 @@ enum BufferId {
     kBufHistory,       /* an edit call on a slot whose history is on: the tile counters, then the stored bits (4 B) and the id (1 B) of
                           every sample of the call's footprint as they were before it */
     kBufMeasure,       /* vrt_volume_measure: the accumulators (2.2 KB, allocated by the first call) */
+    kBufMask,          /* vrt_volume_mask_apply, _upload and _download: the count record, then GROW's second copy of the mask or the
+                          staged bytes */
     kBufCount
 };
 
@@ -204,6 +217,7 @@ struct vrt_ctx {
     std::vector<vrt::DeviceState> dev;
     vrt::HostVolume vol[VRT_MAX_VOLUMES];
     vrt::HostHistory hist[VRT_MAX_VOLUMES];
+    vrt::HostMask mask[VRT_MAX_VOLUMES];
     vrt::HostTexture tex[VRT_MAX_TEXTURES];
     int env_size = 0;
     int upload_format = VRT_FORMAT_F32; /* vrt_set_volume_format: device format of the following uploads */
@@ -286,6 +300,7 @@ struct Edit {
     int slot = 0;
     EditBox foot = {{0, 0, 0}, {0, 0, 0}}; /* the samples the call may write: what a history copies aside */
     bool records = true;                   /* the call becomes an entry of the slot's history (undo and redo do not) */
+    bool masked = true;                    /* the call honours the slot's mask (update_region, undo and redo write through it) */
     /* Which box is rebuilt, and what counts as relevant (nothing relevant: no rebuild). */
     enum Rebuild {
         kDensityWrites, /* the reported box, with the report's high half: brushes, warp, undo and redo */
@@ -301,8 +316,9 @@ struct Edit {
     std::function<void(const Written&)> reported;
 };
 /* One volume edit call, after its argument checks, in this order: quiesce; `prepare` on every device; on a slot whose history is on (and
-   e.records) the capture buffers of every device, then the capture copies; per device `write`, the report (or the footprint), the
-   history record, `reported` on device 0, the rebuild; then, when something changed, the scene is stale and the volume table follows.
+   e.records), or whose mask has a set bit (and e.masked), the capture buffers of every device, then the capture copies; per device
+   `write`, the mask's put-back (enqueued), the report (or the footprint), the history record, `reported` on device 0, the rebuild; then,
+   when something changed, the scene is stale and the volume table follows.
    The rule: every allocation comes before any write.  No `write` runs before every `prepare` and every history allocation has succeeded
    on every device, so a VRT_ERR_OOM from there leaves the volume untouched on all of them. */
 int run_edit(vrt_ctx* ctx, const Edit& e);
@@ -313,19 +329,34 @@ int quiesce(vrt_ctx* ctx);
 /* What a launch reported on D's stream (one synchronisation): the written box in xyz and the two halves of `counts`. */
 int read_report(DeviceState& D, int N, Written& got);
 
-/* ---- The edit history's share of run_edit (vrt_history.hip) ---- */
-/* One call's working state: `captured`, its footprint `foot` sits in every device's kBufHistory; `lost`, the call has nothing (more) to
-   record — no bit changed, or its entry went with the whole history. */
+/* ---- The shares of the edit history (vrt_history.hip) and of the mask (vrt_mask.hip) in run_edit ---- */
+/* One call's working state: `captured`, the samples of `foot` sit in every device's kBufHistory as they were before the call — for the
+   history (`records`: `foot` is the call's footprint), for the mask's put-back (`protects`), or for both; `lost`, the call has nothing
+   (more) to record — no bit changed, or its entry went with the whole history. */
 struct HistoryCall {
-    bool captured = false, lost = false;
+    bool captured = false, lost = false, records = false, protects = false;
     EditBox foot = {{0, 0, 0}, {0, 0, 0}};
 };
-/* A slot whose history is on (both do nothing otherwise).  Ahead of the first write: the capture buffer of every device, then the samples
-   of the footprint (grid order) copied aside on each; VRT_ERR_OOM, and nothing written, when a device has no memory for that. */
-int history_capture(vrt_ctx* ctx, int slot, const EditBox& foot, HistoryCall& call);
+/* Ahead of the first write, when the call records (a slot whose history is on, and `records`) or protects (`masked`, and the slot's mask
+   has a set bit): the capture buffer of every device, then the samples of the footprint (grid order) copied aside on each;
+   VRT_ERR_OOM, and nothing written, when a device has no memory for that.  Does nothing otherwise.  A call that only protects copies
+   the footprint clipped to the box of the mask's set bits, and nothing when the two do not meet. */
+int history_capture(vrt_ctx* ctx, int slot, const EditBox& foot, bool records, bool masked, HistoryCall& call);
 /* After device di's write: the tiles of the xyz box lo..hi (what was written) that differ in bits from the copy become the device's record
    of a new undo entry; device 0 also keeps the host's books (redo emptied, the limits applied).  A box with lo > hi, or one without a
-   changed tile, records nothing. */
+   changed tile, records nothing; so does a call that does not record. */
 int history_record(vrt_ctx* ctx, size_t di, int slot, HistoryCall& call, const int lo[3], const int hi[3]);
+/* Where a capture buffer keeps the copy of `count` samples: their stored bits, their ids, and a 64-bit counter the history leaves
+   alone, zeroed with the copy (the put-back's count of restored samples). */
+struct CaptureView {
+    const uint32_t* bits;
+    const uint8_t* ids;
+    unsigned long long* restored;
+};
+CaptureView capture_view(void* scratch, size_t count);
+/* After device di's write, ahead of its report and the history record, for a call that protects: enqueues the put-back — every protected
+   sample of call.foot gets back the bits and the id of the copy — and, on device 0, the copy of its count of the samples that differed
+   into the slot's `restored`, which holds it after the stream's next synchronisation (read_report's). */
+int mask_put_back(vrt_ctx* ctx, size_t di, int slot, const HistoryCall& call);
 
 }  // namespace vrt

@@ -37,7 +37,8 @@ EditBox history_tile_box(const EditBox& samples) {
     return t;
 }
 
-constexpr size_t kCounterBytes = 16; /* counter 0: changed tiles (first pass); counter 1: places taken in the record (second pass) */
+/* counter 0: changed tiles (first pass); counter 1: places taken in the record (second pass); the other 8 bytes: capture_view's */
+constexpr size_t kCounterBytes = 16;
 
 __host__ __device__ inline unsigned* counters_of(void* scratch) { return static_cast<unsigned*>(scratch); }
 __host__ __device__ inline uint32_t* bits_of(void* scratch) { return reinterpret_cast<uint32_t*>(static_cast<char*>(scratch) + kCounterBytes); }
@@ -226,28 +227,44 @@ void history_trim(vrt_ctx* ctx, int slot) {
 }  // namespace
 
 /* ---- The history's share of run_edit ---- */
-int history_capture(vrt_ctx* ctx, int slot, const EditBox& foot, HistoryCall& call) {
+int history_capture(vrt_ctx* ctx, int slot, const EditBox& foot, bool records, bool masked, HistoryCall& call) {
     call = HistoryCall();
-    if (!ctx->hist[slot].on) return VRT_OK;
+    call.records = records && ctx->hist[slot].on;
+    call.protects = masked;
+    call.foot = foot;
+    if (!call.records && call.protects) { /* the put-back alone needs no more than the footprint within the set bits' box */
+        const HostMask& hm = ctx->mask[slot];
+        for (int a = 0; a < 3; a++) {
+            const int lo = std::max(foot.lo[a], hm.lo[grid_axis(a)]), hi = std::min(foot.lo[a] + foot.n[a] - 1, hm.hi[grid_axis(a)]);
+            if (lo > hi) call.protects = false;
+            call.foot.lo[a] = lo;
+            call.foot.n[a] = hi - lo + 1;
+        }
+    }
+    if (!call.records && !call.protects) return VRT_OK;
     for (auto& D : ctx->dev) {
         HIP_TRY(hipSetDevice(D.ordinal));
-        int rc = ensure_buffer(D.buf[kBufHistory], history_scratch_bytes(foot));
+        int rc = ensure_buffer(D.buf[kBufHistory], history_scratch_bytes(call.foot));
         if (rc != VRT_OK) return rc;
     }
     for (auto& D : ctx->dev) {
         HIP_TRY(hipSetDevice(D.ordinal));
-        HIP_TRY(launch_history_capture(D.vol[slot].dense, D.vol[slot].material, ctx->vol[slot].N, foot, D.buf[kBufHistory].p, D.stream));
+        HIP_TRY(launch_history_capture(D.vol[slot].dense, D.vol[slot].material, ctx->vol[slot].N, call.foot, D.buf[kBufHistory].p, D.stream));
     }
-    call.foot = foot;
     call.captured = true;
     return VRT_OK;
+}
+
+CaptureView capture_view(void* scratch, size_t count) {
+    static_assert(kCounterBytes >= 2 * sizeof(unsigned) + sizeof(unsigned long long), "the history's two counters, then the put-back's");
+    return CaptureView{bits_of(scratch), ids_of(scratch, count), reinterpret_cast<unsigned long long*>(counters_of(scratch) + 2)};
 }
 
 /* The first pass counts the changed tiles, the host sizes the record exactly, the second pass fills it.  Device 0 keeps the books for
  * all: it empties the redo stack, pushes the entry and applies the limits; the others add their record of the same entry. */
 int history_record(vrt_ctx* ctx, size_t di, int slot, HistoryCall& call, const int lo[3], const int hi[3]) {
     HostHistory& hh = ctx->hist[slot];
-    if (!hh.on || !call.captured) return VRT_OK;
+    if (!hh.on || !call.captured || !call.records) return VRT_OK;
     if (call.lost || lo[0] > hi[0] || lo[1] > hi[1] || lo[2] > hi[2]) return VRT_OK;
     DeviceState& D = ctx->dev[di];
     const bool first = di == 0;
@@ -319,6 +336,7 @@ int step_history(vrt_ctx* ctx, int slot, int steps, bool redo, vrt_brush_result*
     Edit e;
     e.slot = slot;
     e.records = false; /* a step through the history is no entry of it, so it has no footprint to copy aside either */
+    e.masked = false;  /* and it restores exactly: through the slot's mask */
     e.rebuild = Edit::kDensityWrites; /* nothing changed, or only material ids, and no derived structure changes */
     e.write = [&](DeviceState& D, size_t) -> int {
         DeviceVolume& v = D.vol[slot];

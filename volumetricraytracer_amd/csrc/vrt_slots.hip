@@ -139,6 +139,7 @@ int free_device_volume(DeviceState& D, int slot) {
     if (v.nib) HIP_TRY(hipFree(v.nib));
     if (v.cube_skip) HIP_TRY(hipFree(v.cube_skip));
     if (v.seeds) HIP_TRY(hipFree(v.seeds));
+    if (v.mask) HIP_TRY(hipFree(v.mask));
     v = DeviceVolume();
     for (std::vector<void*>* stack : {&D.hist[slot].undo, &D.hist[slot].redo}) {
         for (void* record : *stack) HIP_TRY(hipFree(record));
@@ -248,6 +249,7 @@ int upload_volume(vrt_ctx* ctx, int slot, uint8_t resolution, float extent, cons
     const size_t count = (size_t)N * N * N;
     ctx->hist[slot].undo.clear(); /* a new volume: its history starts empty, with the limits it had */
     ctx->hist[slot].redo.clear();
+    ctx->mask[slot] = HostMask(); /* a new volume has no mask: free_device_volume frees the bits */
     for (auto& D : ctx->dev) {
         int rc = free_device_volume(D, slot);
         if (rc != VRT_OK) return rc;
@@ -400,8 +402,11 @@ int run_edit(vrt_ctx* ctx, const Edit& e) {
         HIP_TRY(hipSetDevice(ctx->dev[di].ordinal));
         if ((rc = e.prepare(ctx->dev[di], di)) != VRT_OK) return rc;
     }
+    HostMask& hm = ctx->mask[e.slot];
+    const bool protects = e.masked && hm.on;
+    if (protects) hm.restored = 0; /* the latest honouring call's */
     HistoryCall call;
-    if (e.records && (rc = history_capture(ctx, e.slot, e.foot, call)) != VRT_OK) return rc;
+    if ((rc = history_capture(ctx, e.slot, e.foot, e.records, protects && hm.masked > 0, call)) != VRT_OK) return rc;
     Written foot; /* the footprint in xyz, with its count */
     for (int a = 0; a < 3; a++) foot.lo[grid_axis(a)] = e.foot.lo[a], foot.hi[grid_axis(a)] = e.foot.lo[a] + e.foot.n[a] - 1;
     foot.low = foot.high = box_count(e.foot);
@@ -410,8 +415,11 @@ int run_edit(vrt_ctx* ctx, const Edit& e) {
         DeviceState& D = ctx->dev[di];
         HIP_TRY(hipSetDevice(D.ordinal));
         if ((rc = e.write(D, di)) != VRT_OK) return rc;
+        /* the put-back is enqueued behind the write and touches no report record: the report's one synchronisation serves both */
+        if (call.protects && (rc = mask_put_back(ctx, di, e.slot, call)) != VRT_OK) return rc;
         Written got = foot;
         if (e.reports && (rc = read_report(D, N, got)) != VRT_OK) return rc;
+        if (!e.reports && call.protects) HIP_TRY(hipStreamSynchronize(D.stream));
         if ((rc = history_record(ctx, di, e.slot, call, got.lo, got.hi)) != VRT_OK) return rc;
         if (di == 0 && e.reported) e.reported(got);
         const Written& box = e.rebuild == Edit::kFootprint ? foot : got;
@@ -634,6 +642,7 @@ int vrt_volume_free(vrt_ctx* ctx, int slot) {
     }
     ctx->vol[slot] = HostVolume();
     ctx->hist[slot] = HostHistory();
+    ctx->mask[slot] = HostMask();
     ctx->scene_stale = true;
     return sync_volume_table(ctx);
 }

@@ -536,6 +536,7 @@ static int update_region(vrt_ctx* ctx, int slot, const int origin[3], const int 
     e.foot = box;
     e.rebuild = Edit::kFootprint;
     e.reports = false; /* the scatter writes every sample of its box */
+    e.masked = false;  /* ... through the slot's mask: the host is the authority over its own uploads */
     e.prepare = [&](DeviceState& D, size_t) { return ensure_buffer(D.buf[kBufEditStaging], staged); };
     e.write = [&](DeviceState& D, size_t) -> int {
         DeviceVolume& v = D.vol[slot];

@@ -485,6 +485,47 @@ class VHipRenderer:
             self._mirror_box(slot, vol, lo, hi)
         return {"written": int(res.written), "lo": lo, "hi": hi}
 
+    def mask_apply(self, slot: int, ops) -> dict:
+        """vrt_volume_mask_apply: the mask records (_abi.mask_op, at most _abi.MAX_MASK_OPS), in order, on the mask of the volume
+        resident in `slot` — protected samples that apply_brushes, stamp_volume, smooth_volume, warp_volume, fill_enclosed, components
+        and redistance leave as they were (update_region, undo and redo write through; an upload into the slot drops the mask).  A
+        slot without a mask gets an empty one first.  Returns mask_info's dict."""
+        self._require()
+        ops = list(ops)
+        arr = (_abi.vrt_mask_op * max(1, len(ops)))(*ops)
+        info = _abi.vrt_mask_info()
+        _abi.check(self._lib.vrt_volume_mask_apply(self._ctx, int(slot), len(ops), arr, C.byref(info)), "vrt_volume_mask_apply")
+        return _abi.mask_info_dict(info)
+
+    def mask_upload(self, slot: int, mask) -> dict:
+        """vrt_volume_mask_upload: the slot's mask from an array indexed [x, z, y] like VVoxelVolume.material_id, non-zero (or True) =
+        protected.  Returns mask_info's dict."""
+        self._require()
+        m = np.ascontiguousarray(np.asarray(mask) != 0, dtype=np.uint8)
+        _abi.check(self._lib.vrt_volume_mask_upload(self._ctx, int(slot), m.ctypes.data_as(C.c_void_p)), "vrt_volume_mask_upload")
+        return self.mask_info(slot)
+
+    def mask_download(self, slot: int, N: int) -> np.ndarray:
+        """vrt_volume_mask_download: the mask of the slot (grid size N) on device 0 as a bool array indexed [x, z, y]; all False on a
+        slot without a mask."""
+        self._require()
+        out = np.zeros((int(N),) * 3, np.uint8)
+        _abi.check(self._lib.vrt_volume_mask_download(self._ctx, int(slot), out.ctypes.data_as(C.c_void_p)), "vrt_volume_mask_download")
+        return out != 0
+
+    def mask_clear(self, slot: int) -> None:
+        """vrt_volume_mask_clear: the slot's mask freed on every device; fine on a slot without one."""
+        self._require()
+        _abi.check(self._lib.vrt_volume_mask_clear(self._ctx, int(slot)), "vrt_volume_mask_clear")
+
+    def mask_info(self, slot: int) -> dict:
+        """vrt_volume_mask_info: {"on", "masked", "lo", "hi", "restored"} — the set bits' count and box (xyz, inclusive; lo > hi when
+        none), and how many protected samples the latest honouring edit call had changed and got back."""
+        self._require()
+        info = _abi.vrt_mask_info()
+        _abi.check(self._lib.vrt_volume_mask_info(self._ctx, int(slot), C.byref(info)), "vrt_volume_mask_info")
+        return _abi.mask_info_dict(info)
+
     def extract_mesh(self, slot: int, iso: float = 0.0, lo=None, hi=None):
         """vrt_volume_extract_mesh: the surface density = iso of the volume resident in `slot`, over the samples lo..hi (inclusive xyz
         corners; both None: the whole grid), as an indexed triangle mesh built on the device by surface nets: one call that counts,

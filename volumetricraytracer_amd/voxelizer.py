@@ -54,6 +54,8 @@ def load_host() -> C.CDLL:
         lib.vrh_components.restype = C.c_int
         lib.vrh_components.argtypes = [C.c_void_p, C.c_int, C.c_int, C.POINTER(_abi.vrt_components), C.POINTER(_abi.vrt_component), C.c_int,
                                        C.POINTER(_abi.vrt_components_result)]
+        lib.vrh_mask_apply.restype = C.c_int
+        lib.vrh_mask_apply.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int, C.POINTER(_abi.vrt_mask_op), C.POINTER(_abi.vrt_mask_info)]
         lib.vrh_extract_mesh.restype = C.c_int
         lib.vrh_extract_mesh.argtypes = [C.c_void_p, C.c_int, C.c_float, C.c_int, C.c_float, C.POINTER(C.c_int), C.POINTER(C.c_int), C.c_void_p,
                                          C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.POINTER(_abi.vrt_mesh_result)]
