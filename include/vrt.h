@@ -333,6 +333,15 @@ int vrt_volume_set_material(vrt_ctx* ctx, int slot, const vrt_material* material
  * (Not the nearest sample: PAINT, the Voxelizer and fill_enclosed put ids on inside samples only, and the sample nearest to a point of
  * the zero surface is an outside one about half the time.)  vrt_hit::material keeps its meaning.
  *
+ * A Cube-mode hit (VRT_MODE_CUBE*) renders the entered cell's nearest INSIDE sample, by the same rule.  Such a hit lies on the face through
+ * which the ray enters the solid cell: g_a is integral along that axis but for its fp32 rounding, which must not decide between the entered
+ * cell and the one before it (whose corners may all be outside: its nearest sample would carry another id).  In a Cube mode step 1
+ * therefore names the cell on the far side of that face: let a* be the axis on which g_a is nearest to an integer k = rint(g_a), the
+ * lowest axis on a tie; if |g_a* - k| <= 0.00390625f (2^-8 cells: the hit lies on a face), c_a* = clamp(k - 1, 0, N-2) where the ray's
+ * object-space direction along a* is negative and clamp(k, 0, N-2) otherwise.  The other axes, and a hit that lies on no face (a ray that
+ * starts inside a solid cell), keep floor(g_a);  f_a = g_a - (float)c_a  as before.  The entered cell's corner 0 is INSIDE — that is what
+ * makes the cell solid.
+ *
  * Which launches take it.  A launch whose scene (vrt_block::scenes: any frame's scene) has an instance of a slot with a palette is a full
  * closest hit in ONE kernel, however many frames the block has and even where lights and materials alone would allow the lean kernel:
  * vrt_debug_last_kernel_form reports VRT_FORM_FULL | VRT_FORM_PALETTE and never VRT_FORM_PASSES; VRT_FORM_MAY_BOUNCE also counts palette

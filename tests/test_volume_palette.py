@@ -1,7 +1,8 @@
 """Per-voxel materials without a GPU: the C-ABI, header, Python and adaptor surface of vrt_volume_set_palette / _get_palette; the unit
 cases of the rule that gives a hit its entry (tests/palette_ref.py, restating include/vrt.h); and the painted sphere of the GPU tests
 under the CPU oracle's own hits: the share of hit pixels too near a decision boundary to be compared bit for bit stays below the cap,
-and both painted ids show."""
+and both painted ids show — for the painted sphere and for every scene and case of tests/test_volume_palette_paths_gpu.py (the Cube cases
+through the seven-point criterion and through the header's Cube rule), which must meet their caps here before a GPU sees them."""
 import ctypes as C
 import os
 
@@ -13,6 +14,7 @@ from oracle.binding import OracleScene
 
 import brush_ref
 import palette_ref as pr
+import volume_ref as R
 from volume_ref import F32, TEXEL16
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -102,7 +104,161 @@ def test_the_clamped_cell_at_the_grids_far_faces():
     assert list(ids) == [2, 2]
 
 
+def test_the_seven_points_keep_a_face_between_equal_corner_sets_and_drop_one_where_the_nearest_inside_corners_differ():
+    d, m = _grid()
+    d[1, :, :] = -1.0                        # the whole plane x = 1 is INSIDE: corners dx = 1 of cell 0, dx = 0 of cell 1
+    m[1, :, :] = 5
+    on_face = _at(1.0, 0.25, 0.25)           # on the face between cells (0, 0, 0) and (1, 0, 0)
+    ids, same = pr.seven_point_ids(d, m, 1.0, on_face)
+    assert ids[0] == 5 and same[0]           # the same INSIDE corners on both sides, the same nearest one: kept
+    assert pr.entry_ids(d, m, 1.0, on_face)[1][0] == 0.0  # ... where entry_ids' own distance would leave it out
+    ids, dist = pr.seven_point_dist(d, m, 1.0, on_face)
+    assert ids[0] == 5 and np.isinf(dist[0])
+    d, m = _grid()
+    d[0, 0, 0], d[2, 0, 0] = -1.0, -1.0      # cell 0's only INSIDE corner is sample x = 0, cell 1's is sample x = 2
+    m[0, 0, 0], m[2, 0, 0] = 6, 7
+    ids, same = pr.seven_point_ids(d, m, 1.0, on_face)
+    assert ids[0] in (6, 7) and not same[0]  # the two cells name different samples: dropped
+    assert list(pr.seven_point_ids(d, m, 1.0, _at(0.75, 0.25, 0.25))[0]) == [6] and pr.seven_point_ids(d, m, 1.0, _at(0.75, 0.25, 0.25))[1][0]
+    # a point m / 2 from a bisector is dropped, one 2 m from it kept (m = MARGIN_CELLS cells of 1.0)
+    d, m = _grid()
+    d[0, 0, 0] = d[1, 0, 0] = -1.0
+    m[0, 0, 0], m[1, 0, 0] = 5, 6
+    assert not pr.seven_point_ids(d, m, 1.0, _at(0.5 + 0.5 * pr.MARGIN_CELLS, 0.25, 0.25))[1][0]
+    assert pr.seven_point_ids(d, m, 1.0, _at(0.5 + 2.0 * pr.MARGIN_CELLS, 0.25, 0.25))[1][0]
+
+
 # ---- the painted sphere under the oracle -------------------------------------------------------------------------------------------
+def _oracle_hits(sc, p):
+    osc = OracleScene(sc)
+    o, d = osc.camera_rays(pr.WIDTH, pr.HEIGHT, pr.all_pixels())
+    hit, t, _ = osc.trace_batch(p, o, d, threads=8)
+    return o, d, t, hit
+
+
+def _twin(what, sc, p, inst, vol, need, o, d, t, on, floor_px=None):
+    """The oracle's hits `on` (a mask) of instance `inst` through the criterion of p's mode: the excluded share stays below the cap and
+    every id of `need` shows on at least pr.ID_SHARE of the hits (floor_px: id -> a least count of pixels besides)."""
+    obj = sc.Objects[inst]
+    pts = pr.object_points(obj.Position, obj.Rotation, obj.Scale, o[on], d[on], t[on])
+    ids, dist = pr.ids_of(pr.decoded_density(vol), vol.material_id, p, pts)
+    n = int(on.sum())
+    ok = dist >= pr.MARGIN_CELLS
+    excluded = int((~ok).sum())
+    counts = {k: int((ids == k).sum()) for k in sorted(set(ids.tolist()))}
+    print(f"{what}: hit pixels {n}, excluded {excluded} ({100.0 * excluded / max(n, 1):.2f} %), ids {counts}")
+    assert n > 100
+    assert excluded < pr.excluded_cap(p) * n
+    for k in need:
+        assert int((ok & (ids == k)).sum()) >= pr.ID_SHARE * n, k
+    for k, least in (floor_px or {}).items():
+        assert int((ok & (ids == k)).sum()) >= least, k
+    return ids, ok
+
+
+def test_every_case_of_the_paths_suite_meets_its_caps_under_the_oracle(oracle_lib):
+    for name in pr.CASES:
+        sc, p, vol = pr.case_scene(name)
+        o, d, t, hit = _oracle_hits(sc, p)
+        on = hit & (pr.instance_of_points(sc, o, d, np.where(hit, t, 0.0)) == 0)
+        _twin(name, sc, p, 0, vol, (1, 2), o, d, t, on)
+
+
+def test_the_cube_rule_names_the_entered_cell():
+    d, m = _grid()
+    d[0, 0, 0], d[2, 0, 0] = -1.0, -1.0      # cell 0's only INSIDE corner is sample x = 0, cell 1's is sample x = 2
+    m[0, 0, 0], m[2, 0, 0] = 6, 7
+    on_face = _at(1.0, 0.25, 0.25)
+    for wobble in (-1e-6, 0.0, 1e-6):        # however the hit point was rounded about the face
+        p = on_face + np.array([[wobble, 0.0, 0.0]])
+        ids, dist = pr.entry_ids(d, m, 1.0, p, np.array([[-1.0, 0.2, 0.3]]))   # travelling towards -x: cell 0 is entered
+        assert ids[0] == 6 and abs(dist[0] - float(pr.CUBE_SNAP)) < 1e-5
+        ids, dist = pr.entry_ids(d, m, 1.0, p, np.array([[1.0, 0.2, 0.3]]))    # towards +x: cell 1
+        assert ids[0] == 7 and abs(dist[0] - float(pr.CUBE_SNAP)) < 1e-5
+    assert float(pr.CUBE_SNAP) == 0.00390625 and "0.00390625f" in open(os.path.join(ROOT, "include", "vrt.h")).read()
+    _, c, _ = pr.hit_cells(3, 1.0, _at(0.99, 0.26, 0.27), np.array([[-1.0, 1.0, 1.0]]))  # on no face: g's own floor
+    assert list(c[0]) == [0, 0, 0]
+    _, c, _ = pr.hit_cells(3, 1.0, _at(0.999, 1.002, 0.27), np.array([[1.0, -1.0, 1.0]]))  # x is the nearer to an integer: y keeps its floor
+    assert list(c[0]) == [1, 1, 0]
+
+
+def test_the_cube_scenes_from_above_enter_through_high_faces_and_meet_the_caps_by_the_cube_rule(oracle_lib):
+    for name in ("cube", "cube16"):
+        sc, p, vol = pr.case_scene(name, cube_view=None)
+        o, d, t, hit = _oracle_hits(sc, p)
+        obj = sc.Objects[0]
+        pts = pr.object_points(obj.Position, obj.Rotation, obj.Scale, o[hit], d[hit], t[hit])
+        od = pr.object_directions(obj.Rotation, obj.Scale, d[hit])
+        dec = pr.decoded_density(vol)
+        ids, dist = pr.entry_ids(dec, vol.material_id, pr.EXTENT, pts, od)
+        n, ok = int(hit.sum()), dist >= pr.MARGIN_CELLS
+        _, c, _ = pr.hit_cells(vol.N, pr.EXTENT, pts, od)
+        high = np.any((np.abs(pts + pr.EXTENT - np.round(pts + pr.EXTENT)) < 1e-3) & (od < 0), axis=1)
+        plain, _ = pr.entry_ids(dec, vol.material_id, pr.EXTENT, pts)
+        print(f"{name} from above: hit pixels {n}, excluded {int((~ok).sum())}, ids {[int((ids == k).sum()) for k in (0, 1, 2)]}, through a high face "
+              f"{int(high.sum())}; by the rule without the Cube step: ids {[int((plain == k).sum()) for k in (0, 1, 2)]}")
+        assert n > 500 and int((~ok).sum()) < pr.EXCLUDED_CAP * n
+        assert np.all(dec[c[ok, 0], c[ok, 2], c[ok, 1]] <= 0)  # the named cell is solid: its own sample is INSIDE
+        assert int((ids == 0).sum()) == 0 and int(high.sum()) > 0.5 * n
+        for k in (1, 2):
+            assert int((ok & (ids == k)).sum()) >= pr.ID_SHARE * n
+
+
+def test_the_slots_scene_meets_its_caps_under_the_oracle(oracle_lib):
+    sc, p, vols = pr.slots_scene()
+    o, d, t, hit = _oracle_hits(sc, p)
+    inst = pr.instance_of_points(sc, o, d, np.where(hit, t, 0.0))
+    for i, slot in enumerate(pr.SLOTS_INSTANCES):
+        on = hit & (inst == i)
+        assert int(on.sum()) > 100, i
+        if slot != 0:
+            _twin(f"instance {i} (slot {slot})", sc, p, i, vols[slot], (1, 2), o, d, t, on)
+
+
+def test_the_bounce_and_textured_scenes_meet_their_caps_under_the_oracle(oracle_lib):
+    for what, (sc, p, vol) in (("bounce", pr.bounce_scene()), ("textured", pr.textured_scene())):
+        o, d, t, hit = _oracle_hits(sc, p)
+        on = hit & (pr.instance_of_points(sc, o, d, np.where(hit, t, 0.0)) == 0)
+        _twin(what, sc, p, 0, vol, (1, 2), o, d, t, on)
+        assert int((hit & ~on).sum()) > 50 or len(sc.Objects) == 1  # the second object shows
+        if what == "bounce":  # with the whole sphere a mirror every one of its pixels bounces once and no reflected ray returns to it
+            vol.Material = pr.material_of(pr.SLOT_MIRROR)
+            _, st = OracleScene(sc).render(p, threads=8)
+            print(f"bounce: the sphere as a mirror: {st['bounce_rays']} bounce rays on {int(on.sum())} pixels")
+            assert st["bounce_rays"] == int(on.sum())
+
+
+def test_the_far_scene_has_hits_without_an_inside_corner_whose_nearest_sample_and_corner_0_differ(oracle_lib):
+    sc, p, vol = pr.far_scene()
+    o, d, t, hit = _oracle_hits(sc, p)
+    ids, ok = _twin("far", sc, p, 0, vol, (1, 2), o, d, t, hit)
+    obj = sc.Objects[0]
+    pts = pr.object_points(obj.Position, obj.Rotation, obj.Scale, o[hit], d[hit], t[hit])
+    bare, corner0 = pr.without_inside_corner(pr.decoded_density(vol), vol.material_id, pr.EXTENT, pts)
+    print(f"far: {int((bare & ok).sum())} compared hits in a cell without an INSIDE corner, corner 0 of another id on {int((bare & ok & (corner0 != ids)).sum())}")
+    assert int((bare & ok).sum()) >= 50 and int((bare & ok & (corner0 != ids)).sum()) >= 20
+    assert set(ids[bare].tolist()) == {0, 1}
+
+
+def test_the_zeros_scenes_plant_both_zeros_and_meet_their_caps_under_the_oracle(oracle_lib):
+    for fmt in (F32, TEXEL16):
+        sc, p, vol = pr.zeros_scene(fmt)
+        stored = R.dense_field(vol.density, fmt)
+        band = np.abs(pr.sphere_volume().density) < f32(pr.ZERO_BAND)
+        assert band.sum() > 200 and np.all(stored[band] == 0)
+        i = np.arange(vol.N)
+        odd = ((i[:, None, None] + i[None, :, None] + i[None, None, :]) & 1) == 1
+        assert np.array_equal(np.signbit(stored[band]), odd[band]) and odd[band].any() and (~odd[band]).any()  # -0 and +0 alternate
+        assert np.all(pr.decoded_density(vol)[band] <= 0) and np.array_equal(pr.decoded_density(vol), brush_ref.decode(stored, fmt))
+        assert set(np.unique(vol.material_id[band])) == set(pr.ZERO_IDS)
+        for a, b in ((vol.material_id[1:], vol.material_id[:-1]), (vol.material_id[:, 1:], vol.material_id[:, :-1]),
+                     (vol.material_id[:, :, 1:], vol.material_id[:, :, :-1])):
+            both = (a > 0) & (b > 0)
+            assert both.any() and np.all(a[both] != b[both])  # INSIDE neighbours along every axis carry different ids
+        o, d, t, hit = _oracle_hits(sc, p)
+        _twin(f"zeros, format {fmt}", sc, p, 0, vol, pr.ZERO_IDS, o, d, t, hit, floor_px={255: 20})
+
+
 def test_the_test_scenes_exclusion_share_and_both_ids(oracle_lib):
     vol = pr.sphere_volume()
     stored, material = vol.density.copy(), vol.material_id.copy()
@@ -111,6 +267,11 @@ def test_the_test_scenes_exclusion_share_and_both_ids(oracle_lib):
     assert res["written"] > 0 and np.array_equal(stored, vol.density)
     x = np.arange(vol.N)[:, None, None]
     assert np.array_equal(material == 2, (stored <= 0) & (x > pr.PAINT_X)) and np.array_equal(material == 1, (stored <= 0) & (x < pr.PAINT_X))
+    assert np.array_equal(pr.paint_on_host(pr.sphere_volume()).material_id, material)  # the paths suite paints on the host: the same ids
+    v16 = pr.sphere_volume(TEXEL16)
+    s16, m16 = R.dense_field(v16.density, TEXEL16), (R.dense_field(v16.density, TEXEL16) <= 0).astype(np.uint8)
+    brush_ref.apply(s16, m16, TEXEL16, [pr.paint_record()], pr.EXTENT, 1.0)
+    assert np.array_equal(pr.paint_on_host(v16).material_id, m16) and set(np.unique(m16)) == {0, 1, 2}
     sc = pr.painted_sphere_scene(vol)
     p = pr.scene_params(sc)
     osc = OracleScene(sc)

@@ -4,7 +4,10 @@ hit's entry as the whole slot's material — the entry named by the numpy restat
 hit — also through a block of frames with per-frame scenes, behind a mirror bounce and in a textured mode; ids beyond the palette keep
 the slot's material; the palette comes and goes without a trace, follows undo, and bad arguments change nothing.  Pixels nearer than
 palette_ref.MARGIN_CELLS to a place where the rule's decision changes are left out (the device rounds the hit point in fp32), and
-their share is capped."""
+their share is capped.  The helpers these tests share with tests/test_volume_palette_paths_gpu.py live in tests/palette_ref.py; that
+suite runs the same comparison on every kernel path (the Cube modes among them) with and without per-frame scenes, on slots and instances
+whose numbers differ, with two palettes, where only an entry or only the slot mirrors, under a roughness / metallic texture, on two
+devices, on -0 / +0 samples with id 255, and on many hits without an INSIDE corner."""
 import ctypes as C
 
 import numpy as np
@@ -15,6 +18,7 @@ from volumetricraytracer_amd import _abi
 
 import brush_ref
 import palette_ref as pr
+from palette_ref import bits, camera_hits, check_composition, frame, material_of, uniform_frames, use
 from volume_ref import F32
 
 pytestmark = pytest.mark.gpu
@@ -27,30 +31,6 @@ def pal(oracle_lib):
     """A context of this module's own."""
     with v.VHipRenderer() as r:
         yield r
-
-
-def use(r, sc, p):
-    """The scene synced, and no palette left on its slots by an earlier test (a palette stays with its slot like the material)."""
-    r.SetSceneToRender(sc)
-    r.ResizeRenderOutput(p.width, p.height)
-    r.params_override = p
-    r.SetRendererMode(p.mode)
-    r.SyncWithScene()
-    for slot in range(len(sc.volumes())):
-        r.set_palette(slot, None)
-
-
-def frame(r):
-    img = r.Render().copy()
-    return img, r.last_timing(), r.last_kernel_form()
-
-
-def bits(img):
-    return np.ascontiguousarray(img, np.float32).view(np.uint32)
-
-
-def material_of(entry):
-    return v.VMaterial(tuple(entry[0]), entry[1], entry[2])
 
 
 def painted(r, fmt=_abi.FORMAT_F32, mirror=False, mode=_abi.MODE_INTERP_NOTEX, max_bounces=0, texture=None):
@@ -68,50 +48,12 @@ def painted(r, fmt=_abi.FORMAT_F32, mirror=False, mode=_abi.MODE_INTERP_NOTEX, m
     return sc, p, vol
 
 
-def camera_hits(r, p):
-    rays = r.camera_rays(pr.all_pixels(), p.width, p.height)
-    got = r.trace_rays(rays["origin"], rays["direction"], params=p)
-    return rays, got
-
-
 def entry_of_hits(r, sc, rays, got, which):
     """ids and boundary distances of the hits `which` (a mask over the pixels) on instance 0, from the volume as the device holds it."""
     dv = r.download_volume(0, pr.RESOLUTION, pr.EXTENT)
     obj = sc.Objects[0]
     pts = pr.object_points(obj.Position, obj.Rotation, obj.Scale, rays["origin"][which], rays["direction"][which], got["t"][which])
     return pr.entry_ids(dv.density, dv.material_id, pr.EXTENT, pts)
-
-
-def uniform_frames(r, vol, entries):
-    """U_k: no palette, the slot's material = entry k, the full closest hit in one kernel."""
-    out = []
-    keep = vol.Material
-    for e in entries:
-        m = material_of(e)
-        m.AlbedoTexture, m.TextureScale = keep.AlbedoTexture, keep.TextureScale
-        vol.Material = m
-        img, _, form = frame(r)
-        assert form & _abi.FORM_FULL and not form & (_abi.FORM_PALETTE | _abi.FORM_PASSES)
-        out.append(img)
-    vol.Material = keep
-    return out
-
-
-def check_composition(P, U, ids, dist, hit_idx, n_hit, need=(1, 2)):
-    """P == U[id] bit for bit at every hit pixel (flat indices hit_idx) whose boundary distance exceeds the margin."""
-    ok = dist >= pr.MARGIN_CELLS
-    excluded = int((~ok).sum())
-    Pb = bits(P).reshape(-1, 4)
-    wrong = 0
-    for k in sorted(set(ids[ok].tolist())):
-        sel = hit_idx[ok & (ids == k)]
-        wrong += int(np.any(Pb[sel] != bits(U[k]).reshape(-1, 4)[sel], axis=1).sum())
-    counts = {k: int((ids == k).sum()) for k in sorted(set(ids.tolist()))}
-    print(f"hit pixels {n_hit}, compared {int(ok.sum())}, excluded {excluded} ({100.0 * excluded / max(n_hit, 1):.2f} %), wrong {wrong}, ids {counts}")
-    assert excluded < pr.EXCLUDED_CAP * n_hit
-    for k in need:
-        assert int((ok & (ids == k)).sum()) > 0, k
-    assert wrong == 0
 
 
 # ---- 1. a palette of equal entries is the material ---------------------------------------------------------------------------------

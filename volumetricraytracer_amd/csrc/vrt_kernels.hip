@@ -1820,6 +1820,8 @@ __device__ __forceinline__ F3 direct_light_from_bits(const DFrame& F, F3 so, F3 
     return sum;
 }
 
+constexpr float kPaletteCubeSnap = 0.00390625f; /* 2^-8 cells: how near a face a Cube-mode hit lies (palette_surface) */
+
 /* The surface of a hit on a slot with a palette (vrt_volume_set_palette states the rule): of the hit point's cell, the INSIDE corner
  * (stored density <= 0; the integer field of a VRT_FORMAT_TEXEL16 slot has its density's sign) nearest to the point, the lowest corner
  * on a tie — or, with no INSIDE corner, the nearest sample as vrt_hit::voxel names it; that sample's material id picks the entry.  An
@@ -1827,7 +1829,7 @@ __device__ __forceinline__ F3 direct_light_from_bits(const DFrame& F, F3 so, F3 
  * the march, and one branch (has the lane's slot a palette?): the rest are selects, so that the kernel's scalar registers — it spills
  * them already — hold no further exec masks.  The table's address is read from the kernarg segment here, not kept across the marches.
  * albedo .. raw (the unclamped {roughness, metallic}) come in as the slot's own and go out as the entry's where there is one. */
-template <bool PINNED>
+template <bool PINNED, bool CUBE>
 __device__ __forceinline__ void palette_surface(const DInstance* __restrict__ I, const DVolume* __restrict__ V, F3 o, F3 d, float t,
                                                 F3& albedo, float& rough, float& metal, float& kk, float raw[2]) {
     typedef float pf4 __attribute__((ext_vector_type(4)));
@@ -1852,10 +1854,22 @@ __device__ __forceinline__ void palette_surface(const DInstance* __restrict__ I,
     const float ext = V->extent, ic = V->inv_cell, cmax = (float)(N - 2), nmax = (float)(N - 1);
     const float gx = (__builtin_fmaf(od.x, t, oo.x) + ext) * ic, gy = (__builtin_fmaf(od.y, t, oo.y) + ext) * ic,
                 gz = (__builtin_fmaf(od.z, t, oo.z) + ext) * ic;
+    /* CUBE: the hit lies on the face through which the ray entered the solid cell, g integral along that axis but for its rounding,
+       which must not choose between the entered cell and the one before it: along the axis on which g is nearest to an integer k (the
+       lowest on a tie), and within 2^-8 of it, the cell is k's on the side the ray travels to (vrt.h states it with the rule) */
+    float qx = floorf(gx), qy = floorf(gy), qz = floorf(gz);
+    if constexpr (CUBE) {
+        const float kx = __builtin_rintf(gx), ky = __builtin_rintf(gy), kz = __builtin_rintf(gz);
+        const float ax = fabsf(gx - kx), ay = fabsf(gy - ky), az = fabsf(gz - kz);
+        const bool ux = ax <= ay && ax <= az, uy = !ux && ay <= az, uz = !ux && !uy;
+        qx = (ux && ax <= kPaletteCubeSnap) ? (od.x < 0.0f ? kx - 1.0f : kx) : qx;
+        qy = (uy && ay <= kPaletteCubeSnap) ? (od.y < 0.0f ? ky - 1.0f : ky) : qy;
+        qz = (uz && az <= kPaletteCubeSnap) ? (od.z < 0.0f ? kz - 1.0f : kz) : qz;
+    }
     /* (the integer clamps keep a NaN point inside the grid too) */
-    const int cx = min(max((int)__builtin_amdgcn_fmed3f(floorf(gx), 0.0f, cmax), 0), N - 2);
-    const int cy = min(max((int)__builtin_amdgcn_fmed3f(floorf(gy), 0.0f, cmax), 0), N - 2);
-    const int cz = min(max((int)__builtin_amdgcn_fmed3f(floorf(gz), 0.0f, cmax), 0), N - 2);
+    const int cx = min(max((int)__builtin_amdgcn_fmed3f(qx, 0.0f, cmax), 0), N - 2);
+    const int cy = min(max((int)__builtin_amdgcn_fmed3f(qy, 0.0f, cmax), 0), N - 2);
+    const int cz = min(max((int)__builtin_amdgcn_fmed3f(qz, 0.0f, cmax), 0), N - 2);
     const float fx = gx - (float)cx, fy = gy - (float)cy, fz = gz - (float)cz;
     const unsigned n1 = (unsigned)N, n2 = n1 * n1;
     const unsigned base = ((unsigned)cx * n1 + (unsigned)cz) * n1 + (unsigned)cy; /* grid order x, z, y; N <= 513: below 2^28 */
@@ -1959,7 +1973,7 @@ __global__ __launch_bounds__(kMarchThreads) __attribute__((amdgpu_waves_per_eu((
                 pal_kk = V->k;
                 pal_raw[0] = V->roughness_raw;
                 pal_raw[1] = V->metallic_raw;
-                palette_surface<PATH != VRT_PATH_DENSE>(F.inst + inst, V, o, d, t_hit, albedo, rough, metal, pal_kk, pal_raw);
+                palette_surface<PATH != VRT_PATH_DENSE, PATH == kPathCube || PATH == kPathCube16>(F.inst + inst, V, o, d, t_hit, albedo, rough, metal, pal_kk, pal_raw);
             }
             if (F.textured) {
                 const F3 hp = f3(__builtin_fmaf(d.x, t_hit, o.x), __builtin_fmaf(d.y, t_hit, o.y), __builtin_fmaf(d.z, t_hit, o.z));
