@@ -8,7 +8,7 @@ import re
 
 import isa_listing
 
-KERNELS = ("contacts_count_kernel", "contacts_emit_kernel", "contacts_scan_reduce_kernel", "contacts_scan_sums_kernel", "contacts_scan_apply_kernel")
+KERNELS = ("contacts_count_kernel", "contacts_emit_kernel", "run_scan_reduce_kernel", "run_scan_sums_kernel", "run_scan_apply_kernel")
 
 
 def body_of(text, stem):

@@ -6,8 +6,8 @@ import isa_listing
 
 def test_the_mesh_kernels_use_no_scratch_memory_and_spill_nothing():
     kernels = isa_listing.kernels("vrt_mesh")
-    for stem, instances in (("mesh_count_kernel", 2), ("mesh_emit_kernel", 2), ("mesh_scan_reduce_kernel", 1), ("mesh_scan_sums_kernel", 1),
-                            ("mesh_scan_apply_kernel", 1)):
+    for stem, instances in (("mesh_count_kernel", 2), ("mesh_emit_kernel", 2), ("run_scan_reduce_kernel", 1), ("run_scan_sums_kernel", 1),
+                            ("run_scan_apply_kernel", 1)):
         assert sum(stem in name for name in kernels) == instances, (stem, sorted(kernels))
     assert len(kernels) == 7, sorted(kernels)
     for name, r in kernels.items():

@@ -358,7 +358,7 @@ MESH_513_BOX = ((0, 200, 0), (512, 329, 512))  # 513 x 130 x 513 samples
 
 
 def test_mesh_on_513():
-    """mesh_scan_sums_kernel scans the sums of blocks of 256 * 8 = 2048 runs, 256 sums at a time, and carries a running total from one
+    """run_scan_sums_kernel (grid_device.h) scans the sums of blocks of 256 * 8 = 2048 runs, 256 sums at a time, and carries a running total from one
     chunk of sums to the next: the second chunk exists from 256 * 2048 = 524 288 runs on.  A run is 64 cells along y of one (x, z) row,
     runs are numbered x slowest: 257^3 has 256 * 256 * 4 = 262 144 of them.  A box of 513 x 130 x 513 samples on 513^3 has 512 * 512 rows
     of ceil(129 / 64) = 3 runs, 786 432, and run 524 288 lies in x = 341 (524 288 / (512 * 3) = 341.33).  The sphere of 40 cells is

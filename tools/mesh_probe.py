@@ -6,7 +6,7 @@ totals, emit pass, copy of the four arrays to the caller), the count-only call (
 the totals), and the host converter (VVolumeConverter::ExtractMesh through vrh_extract_mesh: its count call and its fetch call, each of
 which runs the whole pass) on the same field.  Medians over --reps calls after --warmup untimed ones (the first call grows the
 scratch buffers).  The kernels' own time comes from a kernel trace of this probe, in a run of its own
-(rocprofv3 --kernel-trace --stats -- python tools/mesh_probe.py --no-host: the rows mesh_count_kernel, mesh_scan_*_kernel and
+(rocprofv3 --kernel-trace --stats -- python tools/mesh_probe.py --no-host: the rows mesh_count_kernel, run_scan_*_kernel and
 mesh_emit_kernel).  count_pass_bytes_read is what the count pass has to read once, N^3 floats; over the count kernel's time it gives
 the rate to hold against the HBM peak.  Prints one JSON line.
 

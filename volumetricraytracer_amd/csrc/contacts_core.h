@@ -1,12 +1,12 @@
 /*
  * contacts_core.h — the rule of vrt_query_contacts (include/vrt.h), steps 2 to 4, that its builds must agree on, once: the HIP kernels
  * (vrt_contacts.hip, hipcc) and the host pass (csrc/host/VolumeConverter.cpp, g++).  Step 1 is mesh_core.h's, the samples' format
- * grid_core.h's.
+ * grid_core.h's, and what step 3 takes from vrt_query_points is points_core.h's: this header feeds those functions from a Side.
  *
  * Plain floats, every expression evaluated as parenthesised, no fused multiply-add on either side (both builds compile without
  * contraction), sqrtf and / correctly rounded: the two builds produce the same bits.  Vectors and indices are xyz; tap j of a cell is the
  * sample at offset (j & 1, (j >> 1) & 1, j >> 2), as mesh_core.h numbers a cell's corners.  Nothing here reads memory: the caller
- * fetches the eight taps of the cell that locate() names, so that the HIP build decides how they are loaded.
+ * fetches the eight taps of the cell that probe() names, so that the HIP build decides how they are loaded.
  */
 #ifndef VRT_CONTACTS_CORE_H
 #define VRT_CONTACTS_CORE_H
@@ -18,6 +18,7 @@
 #include "../../include/vrt.h"
 #include "grid_core.h"
 #include "mesh_core.h"
+#include "points_core.h"
 
 namespace vrt_contacts {
 
@@ -33,9 +34,6 @@ struct Side {
     float density_scale;          /* the caller's, without the 0.01 of VRT_FORMAT_TEXEL16 */
     float step_max;               /* +inf when unbounded */
 };
-
-VRT_HD float dot(float ax, float ay, float az, float bx, float by, float bz) { return (ax * bx + ay * by) + az * bz; }
-VRT_HD float lerp(float s0, float s1, float f) { return (s0 * (1.0f - f)) + (s1 * f); }
 
 /* Host only: a placement as vrt_scene_set packs it (the points rule's steps 1 and 2, the contacts rule's O). */
 inline void place(Side& s, const float position[3], const float rotation[4], const float scale[3]) {
@@ -78,69 +76,32 @@ struct Probe {
     float f[3], g[3];
 };
 
-/* Step 3, the points rule's steps 1, 3 and the addresses of 4: false when w is not finite or lies outside B's box. */
-VRT_HD bool locate(const Side& B, const float w[3], Probe& P) {
-    if (!(__builtin_isfinite(w[0]) && __builtin_isfinite(w[1]) && __builtin_isfinite(w[2]))) return false;
-    const float rx = w[0] - B.pos[0], ry = w[1] - B.pos[1], rz = w[2] - B.pos[2];
-    const float* m = B.w2o;
-    const float q[3] = {dot(m[0], m[1], m[2], rx, ry, rz), dot(m[3], m[4], m[5], rx, ry, rz), dot(m[6], m[7], m[8], rx, ry, rz)};
-    if (!(fabsf(q[0]) - B.extent <= 0.0f && fabsf(q[1]) - B.extent <= 0.0f && fabsf(q[2]) - B.extent <= 0.0f)) return false;
-    for (int a = 0; a < 3; a++) {
-        P.g[a] = (q[a] + B.extent) * B.inv_cell;
-        const int i = (int)floorf(P.g[a]);
-        P.c[a] = i < 0 ? 0 : (i > B.N - 2 ? B.N - 2 : i);
-        P.f[a] = P.g[a] - (float)P.c[a];
-    }
+/* Step 3, the points rule's steps 1, 3 and the addresses of 4 for B alone: false when w is not finite or lies outside B's box. */
+VRT_HD bool probe(const Side& B, const float w[3], Probe& P) {
+    float q[3], e[3];
+    if (!vrt_points::finite(w)) return false;
+    vrt_points::object_point(B.w2o, B.pos, w, q);
+    if (!vrt_points::in_box(q, B.extent, e)) return false;
+    vrt_points::cell_and_fractions(q, B.extent, B.inv_cell, B.N, P.g, P.c, P.f);
     return true;
 }
 
-/* The points rule's step 4 on the decoded taps s: false when the interpolant is NaN (no candidate), else B's value at the point. */
-VRT_HD bool value_at(const Side& B, const Probe& P, const float s[8], float& value) {
-    const float fx = P.f[0], fy = P.f[1], fz = P.f[2];
-    const float t = lerp(lerp(lerp(s[0], s[1], fx), lerp(s[2], s[3], fx), fy), lerp(lerp(s[4], s[5], fx), lerp(s[6], s[7], fx), fy), fz);
-    if (t != t) return false;
-    float d = t * B.density_scale;
-    if (B.step_max < INFINITY && B.step_max > 0.0f) d = fminf(d, B.step_max);
-    value = d * B.smin;
-    return true;
+/* Step 3, the points rule's step 4 on B's decoded taps s: false when the interpolant is NaN (no candidate), else B's value at the point. */
+VRT_HD bool value_of(const Side& B, const Probe& P, const float s[8], float& value) {
+    return vrt_points::value_at(s, P.f, B.density_scale, B.step_max, B.smin, value);
 }
 
-/* The points rule's step 6: W transposed times g, normalised; 0 when its length is 0 or not finite. */
-VRT_HD void world_normal(const Side& S, const float g[3], float n[3]) {
-    const float* m = S.w2o;
-    const float hx = (m[0] * g[0] + m[3] * g[1]) + m[6] * g[2];
-    const float hy = (m[1] * g[0] + m[4] * g[1]) + m[7] * g[2];
-    const float hz = (m[2] * g[0] + m[5] * g[1]) + m[8] * g[2];
-    const float H = dot(hx, hy, hz, hx, hy, hz);
-    n[0] = n[1] = n[2] = 0.0f;
-    if (H != 0.0f && __builtin_isfinite(H)) {
-        const float len = sqrtf(H);
-        n[0] = hx / len, n[1] = hy / len, n[2] = hz / len;
-    }
-}
-
-/* The gradient of the points rule's step 4 on the decoded taps. */
-VRT_HD void gradient_at(const Probe& P, const float s[8], float G[3]) {
-    const float fx = P.f[0], fy = P.f[1], fz = P.f[2];
-    G[0] = lerp(lerp(s[1] - s[0], s[3] - s[2], fy), lerp(s[5] - s[4], s[7] - s[6], fy), fz);
-    G[1] = lerp(lerp(s[2] - s[0], s[3] - s[1], fx), lerp(s[6] - s[4], s[7] - s[5], fx), fz);
-    G[2] = lerp(lerp(s[4] - s[0], s[5] - s[1], fx), lerp(s[6] - s[2], s[7] - s[3], fx), fy);
-}
-
-/* The nearest sample of B to the point, as vrt_hit::voxel: where material_b is read. */
-VRT_HD void nearest_sample(const Side& B, const Probe& P, int v[3]) {
-    const float last = (float)(B.N - 1);
-    for (int a = 0; a < 3; a++) v[a] = (int)fminf(fmaxf(floorf(P.g[a] + 0.5f), 0.0f), last);
-}
-
-/* Step 4: the record of a contact.  w: the world point; value: value_at's; s: B's decoded taps; n_a: A's vertex normal (step 1). */
+/* Step 4: the record of a contact, with the points rule's step 6 for B's gradient and for A's normal.  w: the world point; value:
+   value_of's; s: B's decoded taps; n_a: A's vertex normal (step 1). */
 VRT_HD vrt_contact contact(const Side& A, const Side& B, const int cell_a[3], const float w[3], const float n_a[3], uint32_t material_a,
                            const Probe& P, const float s[8], float value, uint32_t material_b) {
     vrt_contact r;
-    float G[3], n[3], na[3];
-    gradient_at(P, s, G);
-    world_normal(B, G, n);
-    world_normal(A, n_a, na);
+    float G[3], h[3], n[3], na[3];
+    vrt_points::gradient_at(s, P.f, G);
+    vrt_points::transposed_times(B.w2o, G, h);
+    vrt_points::normalised(h, n);
+    vrt_points::transposed_times(A.w2o, n_a, h);
+    vrt_points::normalised(h, na);
     for (int a = 0; a < 3; a++) {
         r.position[a] = w[a];
         r.normal[a] = n[a];

@@ -1,6 +1,6 @@
 /*
- * grid_core.h — the dense grid's sample format (include/vrt.h), once, for everything that reads or writes a slot's samples: the HIP
- * kernels that build and edit a slot (hipcc) and the host passes (csrc/host/VolumeConverter.cpp, g++).
+ * grid_core.h — the dense grid's sample format (include/vrt.h) and the sampler of a cell, once, for everything that reads or writes a
+ * slot's samples: the HIP kernels that build, edit and query a slot (hipcc) and the host passes (csrc/host/VolumeConverter.cpp, g++).
  *
  * A slot keeps N^3 floats in [x][z][y] order, y fastest.  A VRT_FORMAT_TEXEL16 slot stores the integer +-q of the reference's 16-bit
  * volume texel in each; every other slot stores the density itself.  Plain floats, every expression evaluated as parenthesised, no
@@ -26,6 +26,28 @@ VRT_HD size_t index(int N, I x, I y, I z) { return ((size_t)x * N + z) * N + y; 
 
 /* A stored sample as a density in the caller's units. */
 VRT_HD float decode(float stored, bool texel16) { return texel16 ? stored * 0.01f : stored; }
+
+/* A cell is the cube between eight neighbouring samples; cell c has sample c as its corner 0, and its corner j is the sample at offset
+   (j & 1, (j >> 1) & 1, j >> 2).  Where corner j of cell c (xyz) sits: */
+VRT_HD size_t corner_index(int N, const int c[3], int j) { return index(N, c[0] + (j & 1), c[1] + ((j >> 1) & 1), c[2] + (j >> 2)); }
+
+/* The cell of the grid coordinate u of an axis of n samples, 0 <= u <= n - 1; its fraction is u - (float)cell, in [0, 1]. */
+VRT_HD int cell_of(float u, int n) {
+    const int i = (int)floorf(u);
+    return i < 0 ? 0 : (i > n - 2 ? n - 2 : i);
+}
+
+/* The sampler of a cell, for every call that reads the field between samples (stamp, warp, measure, points, contacts): a lerp is exact
+   at both ends, and the interpolant goes x, then y, then z over the corner values s, that is
+   lerp(lerp(lerp(s0, s1, fx), lerp(s2, s3, fx), fy), lerp(lerp(s4, s5, fx), lerp(s6, s7, fx), fy), fz). */
+VRT_HD float lerp(float s0, float s1, float f) { return (s0 * (1.0f - f)) + (s1 * f); }
+VRT_HD float trilinear(const float s[8], float fx, float fy, float fz) {
+    const float c00 = lerp(s[0], s[1], fx), c10 = lerp(s[2], s[3], fx), c01 = lerp(s[4], s[5], fx), c11 = lerp(s[6], s[7], fx);
+    return lerp(lerp(c00, c10, fy), lerp(c01, c11, fy), fz);
+}
+
+/* The sample of an axis nearest to fraction f of `cell`: where stamp and warp take a material id from. */
+VRT_HD int nearest(int cell, float f) { return cell + (f >= 0.5f ? 1 : 0); }
 
 /* The 16-bit texel of a density as the integer +-q (the rule at vrt_set_volume_format): what a VRT_FORMAT_TEXEL16 slot stores. */
 VRT_HD float texel16_value(float d) {

@@ -29,6 +29,16 @@ using vrt_vox::TriangleFrame;
 
 inline vrt_vox::V3 to_v3(const VVector& v) { return vrt_vox::v3(v.X, v.Y, v.Z); }
 
+/* The decoded densities of the eight corners of cell c of an N^3 grid, in grid_core.h's corner order: the taps of every host pass that
+   samples a cell.  corner_fields: each less iso, as the mesh rule reads a corner (vrt_mesh::field). */
+inline void corner_densities(const Voxel::VVoxel* voxels, int N, bool texel16, const int c[3], float s[8]) {
+    for (int j = 0; j < 8; j++) s[j] = vrt_grid::decode(voxels[vrt_grid::corner_index(N, c, j)].Density, texel16);
+}
+inline void corner_fields(const Voxel::VVoxel* voxels, int N, bool texel16, float iso, const int c[3], float f[8]) {
+    corner_densities(voxels, N, texel16, c, f);
+    for (int j = 0; j < 8; j++) f[j] = vrt_mesh::field(f[j], iso);
+}
+
 /* One triangle into the volume: every voxel of its index box keeps the smaller of its density and the
    shell density of its distance to this triangle (VoxelizeFace, VolumeConverter.cpp:161-252).  The
    arithmetic lives in ../voxelize_core.h, shared with the HIP kernel. */
@@ -323,13 +333,7 @@ VVolumeConverter::VSurfaceMesh VVolumeConverter::ExtractMesh(const Voxel::VVoxel
     out.Lo = VIntVector(N, N, N);
     out.Hi = VIntVector(-1, -1, -1);
     if (cells[0] < 1 || cells[1] < 1 || cells[2] < 1) return out;
-    const auto at = [&](int x, int y, int z) { return vrt_grid::index(N, x, y, z); };
-    const auto corners = [&](const int c[3], float f[8]) {
-        for (int j = 0; j < 8; j++) {
-            const float d = voxels[at(c[0] + (j & 1), c[1] + ((j >> 1) & 1), c[2] + (j >> 2))].Density;
-            f[j] = M::field(vrt_grid::decode(d, texel16), iso);
-        }
-    };
+    const auto corners = [&](const int c[3], float f[8]) { corner_fields(voxels, N, texel16, iso, c, f); };
     /* first pass, in the order of the cells' keys: the vertices, and every active cell's number */
     constexpr uint32_t kNone = 0xffffffffu;
     std::vector<uint32_t> number((size_t)cells[0] * cells[1] * cells[2], kNone);
@@ -346,8 +350,7 @@ VVolumeConverter::VSurfaceMesh VVolumeConverter::ExtractMesh(const Voxel::VVoxel
                 const M::Vertex v = M::cell_vertex(c, f);
                 for (int a = 0; a < 3; a++) out.Positions.push_back(M::object_coordinate(v.p[a], cell, extent));
                 for (int a = 0; a < 3; a++) out.Normals.push_back(v.n[a]);
-                const int j = M::material_corner(classes);
-                out.Materials.push_back(voxels[at(x + (j & 1), y + ((j >> 1) & 1), z + (j >> 2))].Material);
+                out.Materials.push_back(voxels[vrt_grid::corner_index(N, c, M::material_corner(classes))].Material);
                 out.Lo = VIntVector(std::min(out.Lo.X, x), std::min(out.Lo.Y, y), std::min(out.Lo.Z, z));
                 out.Hi = VIntVector(std::max(out.Hi.X, x), std::max(out.Hi.Y, y), std::max(out.Hi.Z, z));
             }
@@ -389,9 +392,7 @@ void VVolumeConverter::Measure(const Voxel::VVoxel* voxels, size_t n, bool texel
     const int N = (int)n;
     const auto at = [&](int x, int y, int z) { return vrt_grid::index(N, x, y, z); };
     const auto value = [&](int x, int y, int z) { return M::field(vrt_grid::decode(voxels[at(x, y, z)].Density, texel16), iso); };
-    const auto corners = [&](const int c[3], float f[8]) {
-        for (int j = 0; j < 8; j++) f[j] = value(c[0] + (j & 1), c[1] + ((j >> 1) & 1), c[2] + (j >> 2));
-    };
+    const auto corners = [&](const int c[3], float f[8]) { corner_fields(voxels, N, texel16, iso, c, f); };
     out = ::vrt_measure_result{};
     for (int a = 0; a < 3; a++) out.lo[a] = N, out.hi[a] = -1;
     if (materialSamplesOrNull) std::fill(materialSamplesOrNull, materialSamplesOrNull + 256, (uint64_t)0);
@@ -473,28 +474,21 @@ void VVolumeConverter::Contacts(const VPlacedVolume& a, const VPlacedVolume& b, 
             for (int y = lo[1]; y <= hi[1]; y++) {
                 const int c[3] = {x, y, z};
                 float f[8];
-                for (int j = 0; j < 8; j++) {
-                    const float d = a.Voxels[vrt_grid::index(N, x + (j & 1), y + ((j >> 1) & 1), z + (j >> 2))].Density;
-                    f[j] = M::field(vrt_grid::decode(d, a.Texel16), 0.0f);
-                }
+                corner_fields(a.Voxels, N, a.Texel16, 0.0f, c, f);
                 const unsigned classes = M::corner_classes(f);
                 if (!M::active(classes)) continue;
                 const M::Vertex v = M::cell_vertex(c, f);
                 float w[3], s[8], value;
                 K::world_point(A, v.p, w);
                 K::Probe P;
-                if (!K::locate(B, w, P)) continue;
-                for (int j = 0; j < 8; j++) {
-                    const float d = b.Voxels[vrt_grid::index(B.N, P.c[0] + (j & 1), P.c[1] + ((j >> 1) & 1), P.c[2] + (j >> 2))].Density;
-                    s[j] = vrt_grid::decode(d, b.Texel16);
-                }
-                if (!K::value_at(B, P, s, value)) continue;
+                if (!K::probe(B, w, P)) continue;
+                corner_densities(b.Voxels, B.N, b.Texel16, P.c, s);
+                if (!K::value_of(B, P, s, value)) continue;
                 result.candidates++;
                 if (!(value <= margin)) continue;
-                const int ja = M::material_corner(classes);
-                const uint32_t material_a = a.Voxels[vrt_grid::index(N, x + (ja & 1), y + ((ja >> 1) & 1), z + (ja >> 2))].Material;
+                const uint32_t material_a = a.Voxels[vrt_grid::corner_index(N, c, M::material_corner(classes))].Material;
                 int near[3];
-                K::nearest_sample(B, P, near);
+                vrt_points::nearest_sample(P.g, B.N, near);
                 const uint32_t material_b = b.Voxels[vrt_grid::index(B.N, near[0], near[1], near[2])].Material;
                 contacts.push_back(K::contact(A, B, c, w, v.n, material_a, P, s, value, material_b));
                 best = std::min(best, K::distance_key(value));
@@ -514,29 +508,25 @@ VVolumeConverter::VStampResult VVolumeConverter::Stamp(Voxel::VVoxel* dst, size_
     int lo[3], hi[3];
     if (!S::valid(stamp) || !S::footprint(stamp, Ns, N, lo, hi)) return out;
     const S::Rule R = S::rule_of(stamp, Ns, unitDst, unitSrc);
-    const auto source_at = [&](int x, int y, int z) { return vrt_grid::index(Ns, x, y, z); };
     for (int x = lo[0]; x <= hi[0]; x++)
         for (int z = lo[2]; z <= hi[2]; z++)
             for (int y = lo[1]; y <= hi[1]; y++) {
                 const float px = (float)x, py = (float)y, pz = (float)z;
                 const float u[3] = {S::source_coord(R.m, 0, px, py, pz), S::source_coord(R.m, 1, px, py, pz), S::source_coord(R.m, 2, px, py, pz)};
                 if (!S::inside(u[0], Ns) || !S::inside(u[1], Ns) || !S::inside(u[2], Ns)) continue;
-                const int c[3] = {S::cell_of(u[0], Ns), S::cell_of(u[1], Ns), S::cell_of(u[2], Ns)};
+                const int c[3] = {vrt_grid::cell_of(u[0], Ns), vrt_grid::cell_of(u[1], Ns), vrt_grid::cell_of(u[2], Ns)};
                 const float f[3] = {u[0] - (float)c[0], u[1] - (float)c[1], u[2] - (float)c[2]};
                 float s[8];
-                for (int j = 0; j < 8; j++) {
-                    const float raw = src[source_at(c[0] + (j & 1), c[1] + ((j >> 1) & 1), c[2] + (j >> 2))].Density;
-                    s[j] = vrt_grid::decode(raw, srcTexel16);
-                }
+                corner_densities(src, Ns, srcTexel16, c, s);
                 Voxel::VVoxel& voxel = dst[((size_t)x * nd + (size_t)z) * nd + (size_t)y];
                 const float d = vrt_grid::decode(voxel.Density, dstTexel16);
-                const float v = S::value(S::trilinear(s, f[0], f[1], f[2]), R.gain, R.off);
+                const float v = S::value(vrt_grid::trilinear(s, f[0], f[1], f[2]), R.gain, R.off);
                 float m;
                 if (!S::merge(R.op, d, v, R.k, R.rv, m)) continue;
                 voxel.Density = dstTexel16 ? vrt_grid::texel16_value(m) : m;
                 if (R.material != VRT_STAMP_MATERIAL_KEEP) {
                     unsigned id = 0u;
-                    if (R.material == VRT_STAMP_MATERIAL_SOURCE) id = src[source_at(S::nearest(c[0], f[0]), S::nearest(c[1], f[1]), S::nearest(c[2], f[2]))].Material;
+                    if (R.material == VRT_STAMP_MATERIAL_SOURCE) id = src[vrt_grid::index(Ns, vrt_grid::nearest(c[0], f[0]), vrt_grid::nearest(c[1], f[1]), vrt_grid::nearest(c[2], f[2]))].Material;
                     voxel.Material = (uint8_t)S::written_material(R.op, R.material, m, id);
                 }
                 out.Lo = VIntVector(std::min(out.Lo.X, x), std::min(out.Lo.Y, y), std::min(out.Lo.Z, z));

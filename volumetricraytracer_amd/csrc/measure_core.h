@@ -23,16 +23,11 @@ constexpr int kSub = 4; /* VRT_MEASURE_SUBSAMPLES */
 /* the fraction of sub-sample i of an axis: 1/8, 3/8, 5/8, 7/8, all exact */
 VRT_HD float fraction(int i) { return 0.125f + 0.25f * (float)i; }
 
-/* vrt_volume_stamp's step 4: x, then y, then z */
-VRT_HD float lerp(float s0, float s1, float u) { return (s0 * (1.0f - u)) + (s1 * u); }
-VRT_HD float trilinear(const float f[8], float ux, float uy, float uz) {
-    const float c00 = lerp(f[0], f[1], ux), c10 = lerp(f[2], f[3], ux), c01 = lerp(f[4], f[5], ux), c11 = lerp(f[6], f[7], ux);
-    return lerp(lerp(c00, c10, uy), lerp(c01, c11, uy), uz);
+/* Sub-sample (ix, iy, iz) of an ACTIVE cell with the corner values f is INSIDE, by grid_core.h's sampler.  (A cell with all corners of
+   one class is not sampled: 64 or none, by rule.) */
+VRT_HD bool subsample_inside(const float f[8], int ix, int iy, int iz) {
+    return !(vrt_grid::trilinear(f, fraction(ix), fraction(iy), fraction(iz)) > 0.0f);
 }
-
-/* Sub-sample (ix, iy, iz) of an ACTIVE cell with the corner values f is INSIDE.  (A cell with all corners of one class is not
-   sampled: 64 or none, by rule.) */
-VRT_HD bool subsample_inside(const float f[8], int ix, int iy, int iz) { return !(trilinear(f, fraction(ix), fraction(iy), fraction(iz)) > 0.0f); }
 
 /* the integer position of sub-sample i of cell c on one axis, in cell / 8 from sample 0; <= 8 * 511 + 7 = 4095 */
 VRT_HD uint32_t position(int c, int i) { return (uint32_t)(8 * c + 2 * i + 1); }

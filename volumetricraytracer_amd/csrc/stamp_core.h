@@ -3,9 +3,9 @@
  * hipcc) and the host pass (csrc/host/VolumeConverter.cpp, g++).
  *
  * Plain floats, every expression evaluated as parenthesised, no fused multiply-add on either side (both builds compile without
- * contraction): the two builds produce the same bits.  Vectors and indices are xyz; corner j of a source cell is the sample at offset
- * (j & 1, (j >> 1) & 1, j >> 2).  The second half (host only) holds what the host derives once per call: the argument rules, the
- * density-unit factors and the footprint box.
+ * contraction): the two builds produce the same bits.  Vectors and indices are xyz; a source cell, its corners and its sampler are
+ * grid_core.h's.  The second half (host only) holds what the host derives once per call: the argument rules, the density-unit factors
+ * and the footprint box.
  */
 #ifndef VRT_STAMP_CORE_H
 #define VRT_STAMP_CORE_H
@@ -38,20 +38,7 @@ VRT_HD float source_coord(const float* m, int a, float px, float py, float pz) {
 }
 VRT_HD bool inside(float u, int ns) { return u >= 0.0f && u <= (float)(ns - 1); }
 
-/* Step 2: the cell of an inside coordinate; its fraction is u - (float)cell, in [0, 1]. */
-VRT_HD int cell_of(float u, int ns) {
-    const int i = (int)floorf(u);
-    return i < 0 ? 0 : (i > ns - 2 ? ns - 2 : i);
-}
-
-/* Step 4: exact at both ends. */
-VRT_HD float lerp(float s0, float s1, float f) { return (s0 * (1.0f - f)) + (s1 * f); }
-VRT_HD float trilinear(const float s[8], float fx, float fy, float fz) {
-    const float c00 = lerp(s[0], s[1], fx), c10 = lerp(s[2], s[3], fx), c01 = lerp(s[4], s[5], fx), c11 = lerp(s[6], s[7], fx);
-    return lerp(lerp(c00, c10, fy), lerp(c01, c11, fy), fz);
-}
-
-/* Step 5. */
+/* Steps 2 and 4, the cell of an inside coordinate and the lerps, are grid_core.h's cell_of and trilinear.  Step 5. */
 VRT_HD float value(float t, float gain, float off) { return (t * gain) - off; }
 
 /* Step 6: what the sample would store (m, in the caller's units) and whether it is written; d: its decoded density. */
@@ -68,9 +55,8 @@ VRT_HD bool merge(int op, float d, float v, float k, float rv, float& m) {
     return v < rv && m > d;
 }
 
-/* Step 7: the source sample whose material id VRT_STAMP_MATERIAL_SOURCE takes, per axis. */
-VRT_HD int nearest(int cell, float f) { return cell + (f >= 0.5f ? 1 : 0); }
-/* The id a written sample gets; material != VRT_STAMP_MATERIAL_KEEP.  source_id: the source's id at the nearest sample. */
+/* Step 7: the id a written sample gets; material != VRT_STAMP_MATERIAL_KEEP.  source_id: the source's id at the nearest sample
+   (grid_core.h's nearest, per axis). */
 VRT_HD unsigned written_material(int op, int material, float m, unsigned source_id) {
     if (material >= 0) return m <= 0.0f ? (unsigned)material : 0u;
     if (op == VRT_STAMP_REPLACE) return source_id;

@@ -1,6 +1,8 @@
 /* vrt_launch.h — what one unit launches for another: the march and the ray queries (vrt_kernels.hip), what a slot derives from its dense
    grid (vrt_volume.hip), and the box and report records every edit unit shares with its kernels.  A volume call's own launches, scratch
-   layout and kernarg structs live in its vrt_<call>.hip. */
+   layout and kernarg structs live in its vrt_<call>.hip; what the calls that only read a slot share on the device — the walk over runs of
+   cells, the corner and tap loads, the runs' records, their scan and its scratch layout — lives in grid_device.h, as what the edit
+   kernels share lives in edit_report.h. */
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stddef.h>

@@ -1,9 +1,9 @@
 /* vrt_measure.hip — vrt_volume_measure and vrt_measure_properties (include/vrt.h), kernels to driver: how much of a resident volume
  * there is and where it sits, as integer sums over a box of its samples.  The rule is csrc/measure_core.h.
  *
- * One pass, one kernel.  The unit of work is a run, as in vrt_mesh.hip: 64 consecutive samples along y of one (x, z) row of the SAMPLE
- * box, one wave, lane = sample = the cell whose corner 0 it is.  A workgroup (4 waves) walks over runs with the grid's stride, so the
- * number of atomics does not grow with the box.
+ * One pass, one kernel.  The unit of work is a run (csrc/grid_device.h, as in vrt_mesh.hip): 64 consecutive samples along y of one
+ * (x, z) row of the SAMPLE box, one wave, lane = sample = the cell whose corner 0 it is.  A workgroup (4 waves) walks over runs with
+ * the grid's stride, so the number of atomics does not grow with the box.
  *   loads   a lane reads its cell's eight corners straight from the grid, each guarded by the box: a sample is read by the (at most)
  *           eight cells around it, a bounded number of times, and the rows of a run are whole 256-byte lines that the caches serve
  *           to the neighbouring rows.  This is what the mesh count pass does, at 66 us for 257^3; an LDS tile with its apron would
@@ -29,21 +29,12 @@
 #include <math.h>
 
 #include "measure_core.h"
+#include "grid_device.h"
 #include "vrt_context.h"
 
 namespace vrt {
 
 namespace {
-
-typedef unsigned long long u64;
-
-/* The sample box (xyz): its first sample, its samples per axis and how many runs of 64 samples a row along y has. */
-struct MeasureGrid {
-    int N;
-    int lo[3];
-    int n[3];
-    int runs_y;
-};
 
 /* The accumulators, 64-bit words: what vrt_measure_result sums, the material counts, and (two 32-bit halves to a word) the cells' box. */
 enum { kS0 = 0, kS1 = 1, kS2 = 4, kSolid = 10, kActive = 11, kCross = 12, kQuads = 15, kArea = 16, kSumWords = 17, kMaterial = 17,
@@ -74,28 +65,11 @@ __device__ __forceinline__ int wave_max(int v) {
 }
 __device__ __forceinline__ float lane_value(float v, int lane) { return __int_as_float(__builtin_amdgcn_readlane(__float_as_int(v), lane)); }
 
-/* The eight corner values of cell c, every corner of which is a sample of the box. */
-template <bool TEXEL16>
-__device__ __forceinline__ void load_corners(const float* __restrict__ dense, int N, const int c[3], float iso, float f[8]) {
-    const size_t i0 = vrt_grid::index(N, c[0], c[1], c[2]);
-#pragma unroll
-    for (int j = 0; j < 8; j++) {
-        const size_t i = i0 + (size_t)(j & 1) * N * N + (size_t)((j >> 1) & 1) + (size_t)(j >> 2) * N;
-        f[j] = vrt_mesh::field(vrt_grid::decode(dense[i], TEXEL16), iso);
-    }
-}
-
 /* Lane `lane` of run r: where its sample sits in the box, whether it lies in the box (live) and whether its neighbour one index up
    on each axis does (more). */
-struct Run {
-    unsigned ry;
-    int rx, rz, rel_y;
+struct BoxLane : RunPlace {
     bool live, more[3];
-    __device__ __forceinline__ Run(const MeasureGrid& G, unsigned r, int lane) {
-        ry = r % (unsigned)G.runs_y;
-        const unsigned t = r / (unsigned)G.runs_y;
-        rx = (int)(t / (unsigned)G.n[2]), rz = (int)(t % (unsigned)G.n[2]);
-        rel_y = (int)ry * 64 + lane;
+    __device__ __forceinline__ BoxLane(const RunGrid& G, unsigned r, int lane) : RunPlace(run_place(G, r, lane)) {
         live = rel_y < G.n[1];
         more[0] = rx + 1 < G.n[0], more[1] = rel_y + 1 < G.n[1], more[2] = rz + 1 < G.n[2];
     }
@@ -109,9 +83,9 @@ struct Fetched {
     float stored[8];
     int id;
 };
-__device__ __forceinline__ Fetched fetch(const float* __restrict__ dense, const uint8_t* __restrict__ material, const MeasureGrid& G, unsigned r,
+__device__ __forceinline__ Fetched fetch(const float* __restrict__ dense, const uint8_t* __restrict__ material, const RunGrid& G, unsigned r,
                                          int lane) {
-    const Run at(G, r, lane);
+    const BoxLane at(G, r, lane);
     const size_t i0 = vrt_grid::index(G.N, G.lo[0] + at.rx, G.lo[1] + at.rel_y, G.lo[2] + at.rz);
     Fetched out;
 #pragma unroll
@@ -124,7 +98,7 @@ __device__ __forceinline__ Fetched fetch(const float* __restrict__ dense, const 
 }
 
 template <bool TEXEL16>
-__global__ __launch_bounds__(256) void measure_kernel(const float* __restrict__ dense, const uint8_t* __restrict__ material, MeasureGrid G, float iso,
+__global__ __launch_bounds__(256) void measure_kernel(const float* __restrict__ dense, const uint8_t* __restrict__ material, RunGrid G, float iso,
                                                       unsigned n_runs, u64* __restrict__ acc) {
     namespace M = vrt_mesh;
     namespace R = vrt_measure;
@@ -153,7 +127,7 @@ __global__ __launch_bounds__(256) void measure_kernel(const float* __restrict__ 
     for (; r < n_runs; r += stride) {
         const Fetched now = next;
         if (r + stride < n_runs) next = fetch(dense, material, G, r + stride, lane); /* in flight while this run is summed */
-        const Run at(G, r, lane);
+        const BoxLane at(G, r, lane);
         const int rx = at.rx, rz = at.rz, rel_y = at.rel_y;
         const unsigned ry = at.ry;
         const int c[3] = {G.lo[0] + rx, G.lo[1] + rel_y, G.lo[2] + rz};
@@ -222,7 +196,7 @@ __global__ __launch_bounds__(256) void measure_kernel(const float* __restrict__ 
 #pragma unroll
                         for (int j = 0; j < 8; j++) g[j] = f[j];
                     } else {
-                        load_corners<TEXEL16>(dense, G.N, cells[i], iso, g);
+                        load_corners(dense, G.N, cells[i], iso, TEXEL16, g);
                     }
                     const M::Vertex v = M::cell_vertex(cells[i], g);
                     q[i][0] = v.p[0], q[i][1] = v.p[1], q[i][2] = v.p[2];
@@ -261,8 +235,8 @@ __global__ __launch_bounds__(256) void measure_kernel(const float* __restrict__ 
     if (tid < 3 && box[3 + tid] >= 0) atomicMin(&out_box[tid], box[tid]), atomicMax(&out_box[3 + tid], box[3 + tid]);
 }
 
-hipError_t launch_measure(const float* dense, const uint8_t* material, bool texel16, const MeasureGrid& G, float iso, u64* acc, hipStream_t stream) {
-    const unsigned n_runs = (unsigned)G.n[0] * (unsigned)G.n[2] * (unsigned)G.runs_y;
+hipError_t launch_measure(const float* dense, const uint8_t* material, bool texel16, const RunGrid& G, float iso, u64* acc, hipStream_t stream) {
+    const unsigned n_runs = runs_of(G);
     unsigned blocks = (n_runs + kWavesPerBlock - 1) / kWavesPerBlock;
     if (blocks > kMaxBlocks) blocks = kMaxBlocks;
     hipLaunchKernelGGL(measure_clear_kernel, dim3(1), dim3(320), 0, stream, acc, G.N);
@@ -298,10 +272,7 @@ int vrt_volume_measure(vrt_ctx* ctx, int slot, float iso, const int* origin, con
     if (rc != VRT_OK) return rc;
     rc = quiesce(ctx);
     if (rc != VRT_OK) return rc;
-    MeasureGrid G;
-    G.N = N;
-    for (int a = 0; a < 3; a++) G.lo[a] = lo[a], G.n[a] = hi[a] - lo[a] + 1;
-    G.runs_y = (G.n[1] + 63) / 64;
+    const RunGrid G = run_grid(N, lo, hi); /* the samples lo..hi */
     DeviceState& D = ctx->dev[0];
     HIP_TRY(hipSetDevice(D.ordinal));
     rc = ensure_buffer(D.buf[kBufMeasure], kWords * sizeof(u64));

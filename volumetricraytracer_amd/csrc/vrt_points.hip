@@ -6,16 +6,17 @@
  * dense grid trilinearly, or outside it, where the distance to the box is the bound.  The dense grid holds N^3 floats on either format
  * (the integer field on VRT_FORMAT_TEXEL16), so one code path serves both and nothing else of a slot is read but its material ids.
  * The eight taps of a lane share nothing with its neighbours': few registers, and occupancy hides the gather, as in vrt_stamp.hip.  The
- * taps are four y-adjacent pairs, written as adjacent loads for the compiler to merge into 8-byte ones (the fp32 bricks' fetch of the
- * march does the same; tools/microbench/gather16.hip checked such loads at 4-byte alignment).  A projection re-enters the evaluation,
- * which is why its loop is not unrolled.  The 16-B point is one load, the 64-B record four 16-B stores. */
+ * taps are four y-adjacent pairs (grid_device.h's load_taps).  The rule's steps are csrc/points_core.h's, which vrt_query_contacts
+ * shares; this file feeds them from the scene's records and keeps the minimum over the instances.  A projection re-enters the
+ * evaluation, which is why its loop is not unrolled.  The 16-B point is one load, the 64-B record four 16-B stores. */
 #include <hip/hip_runtime.h>
 
 #include <string.h>
 
 #include <cmath>
 
-#include "grid_core.h"
+#include "grid_device.h"
+#include "points_core.h"
 #include "vrt_context.h"
 
 namespace vrt {
@@ -25,7 +26,6 @@ namespace {
 constexpr int kPointThreads = 256;
 typedef float pf4 __attribute__((ext_vector_type(4)));
 typedef unsigned pu4 __attribute__((ext_vector_type(4)));
-typedef const float __attribute__((address_space(1))) * pgfloat_p;
 
 /* The kernarg of a launch.  vols / inst / n_inst: the scene as build_frame fills a ray query's; material: the slots' N^3 material grids,
    as DQuery::material; density_scale: the caller's per slot, without the 0.01 that DVolume::density_scale folds in on VRT_FORMAT_TEXEL16
@@ -42,79 +42,55 @@ struct DPoints {
     float density_scale[VRT_MAX_VOLUMES];
 };
 
-__device__ __forceinline__ float lerp(float s0, float s1, float f) { return (s0 * (1.0f - f)) + (s1 * f); }
-__device__ __forceinline__ float dot(float ax, float ay, float az, float bx, float by, float bz) { return (ax * bx + ay * by) + az * bz; }
+namespace P = vrt_points;
 
 /* What a lane keeps of the best instance so far while it walks the scene. */
 struct Best {
     float value;        /* the minimum; +inf with instance -1 */
     int instance;
     bool sampled;
-    float hx, hy, hz;   /* w2o^T G of a sampled minimum */
-    int vx, vy, vz;     /* its nearest grid sample */
+    float h[3];         /* w2o^T G of a sampled minimum */
+    int v[3];           /* its nearest grid sample */
     const uint8_t* mat; /* that sample's material id, or null */
 };
 
 /* E(p) of the rule in vrt.h, steps 1-5 and the h of step 6. */
 __device__ __forceinline__ void evaluate(const DPoints& Q, float px, float py, float pz, Best& B) {
+    const float p[3] = {px, py, pz};
     B.value = __builtin_inff();
     B.instance = -1;
     B.sampled = false;
-    B.hx = B.hy = B.hz = 0.0f;
-    B.vx = B.vy = B.vz = -1;
+    B.h[0] = B.h[1] = B.h[2] = 0.0f;
+    B.v[0] = B.v[1] = B.v[2] = -1;
     B.mat = nullptr;
-    if (!(__builtin_isfinite(px) && __builtin_isfinite(py) && __builtin_isfinite(pz))) return;
+    if (!P::finite(p)) return;
     for (int k = 0; k < Q.n_inst; k++) {
         const DInstance* __restrict__ I = Q.inst + k;
         const int slot = I->slot;
         const DVolume* __restrict__ V = Q.vols + slot;
-        const float* m = I->w2o;
-        const float rx = px - I->pos[0], ry = py - I->pos[1], rz = pz - I->pos[2];
-        const float qx = dot(m[0], m[1], m[2], rx, ry, rz), qy = dot(m[3], m[4], m[5], rx, ry, rz), qz = dot(m[6], m[7], m[8], rx, ry, rz);
         const float ext = V->extent, smin = I->smin;
-        const float ex = fabsf(qx) - ext, ey = fabsf(qy) - ext, ez = fabsf(qz) - ext;
-        float value;
-        if (ex <= 0.0f && ey <= 0.0f && ez <= 0.0f) {
+        float q[3], e[3], value;
+        P::object_point(I->w2o, I->pos, p, q);
+        if (P::in_box(q, ext, e)) {
             const int N = V->N;
-            const float ic = V->inv_cell;
-            const float gx = (qx + ext) * ic, gy = (qy + ext) * ic, gz = (qz + ext) * ic;
-            const int cx = min(max((int)floorf(gx), 0), N - 2), cy = min(max((int)floorf(gy), 0), N - 2), cz = min(max((int)floorf(gz), 0), N - 2);
-            const float fx = gx - (float)cx, fy = gy - (float)cy, fz = gz - (float)cz;
-            /* [x][z][y], 0 <= c <= N - 2 on every axis: all eight taps lie inside the grid; N <= 513, so a byte offset fits 32 bits */
-            const unsigned n = (unsigned)N;
-            const unsigned at = ((unsigned)cx * n + (unsigned)cz) * n + (unsigned)cy;
-            const pgfloat_p b00 = (pgfloat_p)(V->dense) + at; /* x, z */
-            const pgfloat_p b01 = b00 + n, b10 = b00 + n * n, b11 = b10 + n;
-            const bool t16 = V->format == VRT_FORMAT_TEXEL16;
-            /* s<dx><dy><dz> */
-            const float s000 = vrt_grid::decode(b00[0], t16), s010 = vrt_grid::decode(b00[1], t16);
-            const float s001 = vrt_grid::decode(b01[0], t16), s011 = vrt_grid::decode(b01[1], t16);
-            const float s100 = vrt_grid::decode(b10[0], t16), s110 = vrt_grid::decode(b10[1], t16);
-            const float s101 = vrt_grid::decode(b11[0], t16), s111 = vrt_grid::decode(b11[1], t16);
-            const float t = lerp(lerp(lerp(s000, s100, fx), lerp(s010, s110, fx), fy), lerp(lerp(s001, s101, fx), lerp(s011, s111, fx), fy), fz);
-            if (t != t) continue; /* contributes nothing */
-            float d = t * Q.density_scale[slot];
-            const float sm = V->step_max; /* +inf for a slot whose step_max is not positive (fill_dvolume) */
-            if (sm < __builtin_inff() && sm > 0.0f) d = fminf(d, sm);
-            value = d * smin;
+            const bool t16 = V->format == VRT_FORMAT_TEXEL16; /* read here, beside N: read at the call below it costs two VGPRs */
+            float g[3], f[3], s[8];
+            int c[3];
+            P::cell_and_fractions(q, ext, V->inv_cell, N, g, c, f);
+            load_taps(V->dense, N, c, t16, s);
+            /* step_max: +inf for a slot whose step_max is not positive (fill_dvolume) */
+            if (!P::value_at(s, f, Q.density_scale[slot], V->step_max, smin, value)) continue; /* contributes nothing */
             if (!(B.instance < 0 || value < B.value)) continue;
-            const float Gx = lerp(lerp(s100 - s000, s110 - s010, fy), lerp(s101 - s001, s111 - s011, fy), fz);
-            const float Gy = lerp(lerp(s010 - s000, s110 - s100, fx), lerp(s011 - s001, s111 - s101, fx), fz);
-            const float Gz = lerp(lerp(s001 - s000, s101 - s100, fx), lerp(s011 - s010, s111 - s110, fx), fy);
-            B.hx = (m[0] * Gx + m[3] * Gy) + m[6] * Gz;
-            B.hy = (m[1] * Gx + m[4] * Gy) + m[7] * Gz;
-            B.hz = (m[2] * Gx + m[5] * Gy) + m[8] * Gz;
-            /* the nearest grid sample, as vrt_hit::voxel */
-            const float nmax = (float)(N - 1);
-            B.vx = (int)__builtin_amdgcn_fmed3f(floorf(gx + 0.5f), 0.0f, nmax);
-            B.vy = (int)__builtin_amdgcn_fmed3f(floorf(gy + 0.5f), 0.0f, nmax);
-            B.vz = (int)__builtin_amdgcn_fmed3f(floorf(gz + 0.5f), 0.0f, nmax);
+            float G[3];
+            P::gradient_at(s, f, G);
+            P::transposed_times(I->w2o, G, B.h);
+            P::nearest_sample(g, N, B.v);
             const uint8_t* mat = Q.material[slot];
-            B.mat = mat != nullptr ? mat + (((unsigned)B.vx * n + (unsigned)B.vz) * n + (unsigned)B.vy) : nullptr;
+            const unsigned n = (unsigned)N;
+            B.mat = mat != nullptr ? mat + (((unsigned)B.v[0] * n + (unsigned)B.v[2]) * n + (unsigned)B.v[1]) : nullptr;
             B.sampled = true;
         } else {
-            const float mx = fmaxf(ex, 0.0f), my = fmaxf(ey, 0.0f), mz = fmaxf(ez, 0.0f);
-            value = sqrtf(dot(mx, my, mz, mx, my, mz)) * smin;
+            value = P::box_bound(e, smin);
             if (!(B.instance < 0 || value < B.value)) continue;
             B.sampled = false;
         }
@@ -130,32 +106,24 @@ __global__ __launch_bounds__(kPointThreads) void points_kernel(const DPoints Q) 
     float px = rec.x, py = rec.y, pz = rec.z;
     unsigned moves = 0u;
     Best B;
-    float nx, ny, nz;
+    float n[3];
 #pragma nounroll
     for (;;) {
         evaluate(Q, px, py, pz, B);
-        nx = ny = nz = 0.0f;
-        if (B.sampled) {
-            const float H = dot(B.hx, B.hy, B.hz, B.hx, B.hy, B.hz);
-            if (H != 0.0f && __builtin_isfinite(H)) {
-                const float len = sqrtf(H);
-                nx = B.hx / len;
-                ny = B.hy / len;
-                nz = B.hz / len;
-            }
-        }
-        if (moves >= (unsigned)Q.iterations || !B.sampled || (nx == 0.0f && ny == 0.0f && nz == 0.0f) || fabsf(B.value) <= Q.tolerance) break;
-        px = px - (nx * B.value);
-        py = py - (ny * B.value);
-        pz = pz - (nz * B.value);
+        n[0] = n[1] = n[2] = 0.0f;
+        if (B.sampled) P::normalised(B.h, n);
+        if (moves >= (unsigned)Q.iterations || !B.sampled || (n[0] == 0.0f && n[1] == 0.0f && n[2] == 0.0f) || fabsf(B.value) <= Q.tolerance) break;
+        px = px - (n[0] * B.value);
+        py = py - (n[1] * B.value);
+        pz = pz - (n[2] * B.value);
         moves++;
     }
     unsigned material = 0u;
     if (B.sampled && B.mat != nullptr) material = *B.mat;
-    if (!B.sampled) B.vx = B.vy = B.vz = -1;
+    if (!B.sampled) B.v[0] = B.v[1] = B.v[2] = -1;
     pu4* out = reinterpret_cast<pu4*>(Q.results) + 4 * (size_t)i;
-    out[0] = pu4{__float_as_uint(B.value), __float_as_uint(nx), __float_as_uint(ny), __float_as_uint(nz)};
-    out[1] = pu4{(unsigned)B.instance, (unsigned)B.vx, (unsigned)B.vy, (unsigned)B.vz};
+    out[0] = pu4{__float_as_uint(B.value), __float_as_uint(n[0]), __float_as_uint(n[1]), __float_as_uint(n[2])};
+    out[1] = pu4{(unsigned)B.instance, (unsigned)B.v[0], (unsigned)B.v[1], (unsigned)B.v[2]};
     out[2] = pu4{material, B.sampled ? (unsigned)VRT_POINT_SAMPLED : 0u, moves, __float_as_uint(px)};
     out[3] = pu4{__float_as_uint(py), __float_as_uint(pz), 0u, 0u};
 }

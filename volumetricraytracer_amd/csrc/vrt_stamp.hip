@@ -39,7 +39,7 @@ __global__ __launch_bounds__(256) void stamp_region_kernel(vrt_stamp_core::Rule 
             const float px = (float)x, py = (float)y, pz = (float)z;
             const float ux = S::source_coord(R.m, 0, px, py, pz), uy = S::source_coord(R.m, 1, px, py, pz), uz = S::source_coord(R.m, 2, px, py, pz);
             if (!(S::inside(ux, ns) && S::inside(uy, ns) && S::inside(uz, ns))) continue;
-            const int cx = S::cell_of(ux, ns), cy = S::cell_of(uy, ns), cz = S::cell_of(uz, ns);
+            const int cx = vrt_grid::cell_of(ux, ns), cy = vrt_grid::cell_of(uy, ns), cz = vrt_grid::cell_of(uz, ns);
             const float fx = ux - (float)cx, fy = uy - (float)cy, fz = uz - (float)cz;
             /* the source's grid is [x][z][y] like every dense grid: 0 <= c <= ns - 2 on every axis, so all eight taps lie inside it */
             const size_t at = vrt_grid::index(ns, cx, cy, cz);
@@ -53,14 +53,14 @@ __global__ __launch_bounds__(256) void stamp_region_kernel(vrt_stamp_core::Rule 
             const size_t g = vrt_grid::index(N, x, y, z);
             const float stored = dense[g];
             const float d = vrt_grid::decode(stored, DST16);
-            const float v = S::value(S::trilinear(s, fx, fy, fz), R.gain, R.off);
+            const float v = S::value(vrt_grid::trilinear(s, fx, fy, fz), R.gain, R.off);
             float m;
             if (!S::merge(R.op, d, v, R.k, R.rv, m)) continue;
             dense[g] = DST16 ? vrt_grid::texel16_value(m) : m;
             if (R.material != VRT_STAMP_MATERIAL_KEEP) {
                 unsigned id = 0u;
                 if (R.material == VRT_STAMP_MATERIAL_SOURCE) /* grid_core.h's index, the nearest sample of each axis found where it is used */
-                    id = src_material[((size_t)S::nearest(cx, fx) * ns + (size_t)S::nearest(cz, fz)) * ns + (size_t)S::nearest(cy, fy)];
+                    id = src_material[((size_t)vrt_grid::nearest(cx, fx) * ns + (size_t)vrt_grid::nearest(cz, fz)) * ns + (size_t)vrt_grid::nearest(cy, fy)];
                 material[g] = (uint8_t)S::written_material(R.op, R.material, m, id);
             }
             report.add(N, x, y, z, true); /* every write is a density write */

@@ -4,7 +4,7 @@
  *
  * Plain floats, every expression evaluated as parenthesised, no fused multiply-add on either side (both builds compile without
  * contraction): the two builds produce the same bits.  The region's distance s is brush_core.h's, the one the brushes use; the cell,
- * the lerps and the nearest sample are stamp_core.h's, the decode and the texel grid_core.h's.  The second half (host only) holds
+ * the lerps, the nearest sample, the decode and the texel are grid_core.h's, the source coordinate stamp_core.h's.  The second half (host only) holds
  * what the host derives once per call: the argument rules, the offset in density units, the region's box and the record of a motion.
  */
 #ifndef VRT_WARP_CORE_H
@@ -62,19 +62,19 @@ VRT_HD bool evaluate(const vrt_warp& r, float off, int N, bool texel16, int x, i
     const float g = gain(w, r.length_scale), wo = w * off;
     if (rx == px && ry == py && rz == pz && g == 1.0f && wo == 0.0f) return false; /* step 5: still */
     const float ux = clamped(rx, N), uy = clamped(ry, N), uz = clamped(rz, N);
-    const int cx = S::cell_of(ux, N), cy = S::cell_of(uy, N), cz = S::cell_of(uz, N);
+    const int cx = vrt_grid::cell_of(ux, N), cy = vrt_grid::cell_of(uy, N), cz = vrt_grid::cell_of(uz, N);
     const float fx = ux - (float)cx, fy = uy - (float)cy, fz = uz - (float)cz;
-    /* 0 <= c <= N - 2 on every axis, so all eight taps lie inside the grid; corner j as in stamp_core.h */
+    /* 0 <= c <= N - 2 on every axis, so all eight taps lie inside the grid; corner j as in grid_core.h */
     const size_t at = vrt_grid::index(N, cx, cy, cz);
     const size_t tx = (size_t)N * N, tz = (size_t)N;
     float raw[8], s[8];
     for (int j = 0; j < 8; j++) raw[j] = stored_at(at + (j & 1 ? tx : 0) + (j & 2 ? 1 : 0) + (j & 4 ? tz : 0));
     for (int j = 0; j < 8; j++) s[j] = vrt_grid::decode(raw[j], texel16);
-    const float m = value(S::trilinear(s, fx, fy, fz), g, wo);
+    const float m = value(vrt_grid::trilinear(s, fx, fy, fz), g, wo);
     if (!(m == m)) return false; /* NaN is never written */
     store = texel16 ? vrt_grid::texel16_value(m) : m;
     if (r.material >= 0) id = m <= 0.0f ? (unsigned)r.material : 0u;
-    else if (r.material == VRT_WARP_MATERIAL_SOURCE) id = id_at(vrt_grid::index(N, S::nearest(cx, fx), S::nearest(cy, fy), S::nearest(cz, fz)));
+    else if (r.material == VRT_WARP_MATERIAL_SOURCE) id = id_at(vrt_grid::index(N, vrt_grid::nearest(cx, fx), vrt_grid::nearest(cy, fy), vrt_grid::nearest(cz, fz)));
     else id = kKeepId;
     return true;
 }
