@@ -53,6 +53,7 @@
  *   vrt_trace_rays*, vrt_camera_rays (no reference analogue: its DXR TraceRay calls live only inside its shaders)
  *   vrt_query_points*               (no reference analogue: the distance from a point to the scene's nearest surface, its direction, and
  *                                   the point's projection onto that surface)
+ *   vrt_query_sweeps*               (no reference analogue: where a sphere, its centre moved along a line, first touches the scene)
  *   vrt_query_contacts              (no reference analogue: where the surface of one placed instance touches or enters another — the
  *                                   surface points of A in or near B, as compact contact records)
  *
@@ -1357,8 +1358,8 @@ int vrt_camera_rays(const vrt_scene* scene, int width, int height, int n, const 
 
 /* Distance queries (no reference analogue): how far a world-space point is from the nearest surface of the resident scene and in which
  * direction (iterations == 0), and where the nearest surface point is (iterations > 0: the point is moved onto the surface).  Colliding
- * particles against a sculpt, resting a brush or a stamp on the surface, snapping a placement to it, sphere-casting (the caller marches
- * its own spheres with the returned radius).  A ray query cannot stand in: a ray needs a direction, and the normal is what is asked for.
+ * particles against a sculpt, resting a brush or a stamp on the surface, snapping a placement to it (a sphere cast through the scene is a
+ * call of its own, vrt_query_sweeps below).  A ray query cannot stand in: a ray needs a direction, and the normal is what is asked for.
  *
  * What the number is worth.  It is exact (up to the trilinear interpolant) on a slot that holds a true signed distance, i.e. after
  * vrt_volume_redistance, within its band.  On the Voxelizer's shells it is, through density_scale / step_max (vrt_volume_set_metric), a
@@ -1429,6 +1430,84 @@ int vrt_query_points(vrt_ctx* ctx, int iterations, float tolerance, int n, const
 /* The same from and into host arrays, synchronous: staged through a context-owned device buffer (vrt_trace_rays_host's), reallocated
  * only when a larger batch arrives. */
 int vrt_query_points_host(vrt_ctx* ctx, int iterations, float tolerance, int n, const vrt_point* points, vrt_point_result* results);
+
+/* Sweep queries (no reference analogue): where a sphere of radius r, its centre moved from `origin` along `direction`, first touches
+ * the resident scene — a thrown object, the end caps of a character's capsule, a camera boom, a brush of finite size coming to rest on
+ * the surface, continuous collision between two frames.  One launch marches every record to its end on the device; the K launches of
+ * vrt_query_points with a caller-written update between them that this replaces give the same records (consequence (b)).  A ray query
+ * cannot stand in: it finds the interpolant's root for a line of zero thickness and culls by the boxes, not by the boxes grown by r.
+ *
+ * What the caller provides.  A field that is a distance or a lower bound of one: a slot after vrt_volume_redistance, or a Voxelizer
+ * shell with its density_scale / step_max (vrt_volume_set_metric) — the march steps by the clearance it reads, and a field that
+ * overstates it steps through surfaces.  A slot's value never exceeds its step_max, so a sphere whose radius is not below it is in
+ * contact wherever its centre is in the box: sweep against a redistanced slot with step_max raised to the band.  And a margin of `radius` between a shape and its box (the `reach` that vrt_volume_stamp
+ * advises): a volume has no surface outside its box, and a sweep tests the sphere only where its centre is in a box.
+ *
+ * The rule is part of the contract.  All arithmetic is fp32, evaluated as parenthesised, no fused multiply-add; sqrtf and / are
+ * correctly rounded; dot as in vrt_query_points.  o: origin, d: direction.
+ *   0. Bad record.  A non-finite origin or direction; L = dot(d,d) equal to 0 or not finite; a t_max that is NaN, negative or infinite;
+ *      a radius that is NaN, negative or infinite.  A bad record is not an error: it gets the miss record with steps 0 and
+ *      position = origin echoed.
+ *   1. Direction.  inv = 1.0f / sqrtf(L); u_a = d_a * inv.
+ *   2. Candidates, once per record and per instance k: smax = fmaxf(fmaxf(|sx|,|sy|),|sz|) of the instance's scale;
+ *      Rb = sqrtf((3.0f * extent) * extent) * smax; m = position_k - o; s = fminf(fmaxf(dot(m,u), 0.0f), t_max); e_a = m_a - (u_a * s);
+ *      B = (Rb + radius) * 1.0001f.  Instance k is a CANDIDATE iff dot(e,e) <= B * B.  An instance that is not a candidate takes no part
+ *      in the record — this is the rule, not a shortcut: the step lengths depend on it.
+ *   3. Evaluation at t.  p_a = o_a + (u_a * t).  A non-finite p: nothing contributes.  For every candidate, in index order,
+ *      vrt_query_points' steps 1 to 4 for that instance alone: IN THE BOX with an interpolant that is not NaN, its clearance is
+ *      c = value - radius, SAMPLED; outside the box, c = the box bound, not SAMPLED, the radius not subtracted; a NaN interpolant,
+ *      nothing.  The minimum as in vrt_query_points' step 5, over c: the first contributor, then every later one whose c is < the
+ *      minimum so far.
+ *   4. Loop.  t = 0, steps = 0.  Repeat: t > t_max: miss.  steps == max_steps: EXHAUSTED.  steps++, evaluate.  Nothing contributes:
+ *      miss.  The minimum is SAMPLED and c <= tolerance: HIT.  Otherwise t = t + fmaxf(c, step_min).
+ *   5. Records.  HIT: t; position p; instance k; distance = the instance's value at p (radius not subtracted); normal, voxel and
+ *      material as vrt_query_points' step 6 for instance k at p; flags VRT_SWEEP_HIT, with VRT_SWEEP_INITIAL when steps == 1.  Miss:
+ *      t -1, normal 0, instance and voxel -1, material 0, flags 0, distance +inf, position = o + u*t of the final t.  EXHAUSTED: as a
+ *      miss, but t is the t reached and the flag is set; a caller continues from `position` with t_max less t.
+ * Consequences.
+ *   (a) A HIT's distance, normal, voxel and material are, bit for bit, what vrt_query_points (iterations 0) reports at `position` in a
+ *       scene holding instance k alone.
+ *   (b) In a one-instance scene a sweep is its evaluations chained on the host through vrt_query_points, each link taking
+ *       c = SAMPLED ? distance - radius : distance, while the instance is a candidate.
+ *   (c) With rotation (0,0,0,1) and scales that are powers of two every rounding is pinned, whatever the position. */
+#define VRT_MAX_SWEEP_STEPS 4096
+#define VRT_SWEEP_HIT       1  /* the sphere touches a surface at t */
+#define VRT_SWEEP_EXHAUSTED 2  /* max_steps evaluations made, neither hit nor past t_max: continue from `position` */
+#define VRT_SWEEP_INITIAL   4  /* with HIT: in contact at t == 0 (the first evaluation) */
+
+typedef struct vrt_sweep {       /* 32 B: vrt_ray with the spare word put to use */
+    float origin[3];             /* world space */
+    float t_max;                 /* the centre travels t in [0, t_max] along the normalised direction */
+    float direction[3];          /* need not be unit */
+    float radius;                /* >= 0, world units; 0 = a conservative march of a point */
+} vrt_sweep;
+
+typedef struct vrt_sweep_hit {   /* 64 B: four 16-byte words */
+    float t;              /* -1 for a miss; for EXHAUSTED the t reached */
+    float normal[3];      /* as vrt_point_result; 0 unless HIT */
+    int32_t instance;     /* -1 unless HIT */
+    int32_t voxel[3];     /* as vrt_point_result; -1 unless HIT */
+    uint32_t material;    /* 0 unless HIT */
+    uint32_t flags;       /* VRT_SWEEP_* */
+    uint32_t steps;       /* evaluations made */
+    float distance;       /* the hit instance's value at `position` (radius not subtracted); +inf unless HIT */
+    float position[3];    /* the centre where the record was decided */
+    uint32_t reserved_;
+} vrt_sweep_hit;
+
+/* n records from device memory into n records in device memory, asynchronous on hip_stream, on the first device of the context.
+ * Argument errors are checked before anything is enqueued: VRT_ERR_INVALID for a NULL context, a NULL buffer with n > 0, n < 0,
+ * max_steps outside 1 .. VRT_MAX_SWEEP_STEPS, a tolerance that is negative or not finite, or a step_min that is not finite or not > 0;
+ * VRT_ERR_NOT_READY without a scene; n == 0 is OK and launches nothing.  Everything else is vrt_query_points': it allocates nothing, so
+ * it can be captured into a hipGraph (a region edit or a brush dab shows in a replay, a full re-upload or a new scene does not); a
+ * vrt_scene_set that was deferred while frames were in flight is applied ahead of the query, which on a capturing stream is
+ * VRT_ERR_NOT_READY; the render's bookkeeping reads the same before and after; the kernel reads the slots' dense grids and material ids
+ * only, so every data path and both formats answer alike. */
+int vrt_query_sweeps(vrt_ctx* ctx, int max_steps, float tolerance, float step_min, int n, const vrt_sweep* device_sweeps,
+                     vrt_sweep_hit* device_hits, void* hip_stream);
+/* The same from and into host arrays, synchronous: staged through the context-owned device buffer of vrt_query_points_host. */
+int vrt_query_sweeps_host(vrt_ctx* ctx, int max_steps, float tolerance, float step_min, int n, const vrt_sweep* sweeps,
+                          vrt_sweep_hit* hits);
 
 /* Contact queries (no reference analogue): where two placed instances of the resident scene touch — two sculpts, a stamp source held
  * over its target, an object dropped on another.  The surface points of instance A (vrt_volume_extract_mesh's vertices at iso 0 over

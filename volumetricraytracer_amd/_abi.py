@@ -241,6 +241,29 @@ class vrt_point_result(C.Structure):
     ]
 
 
+MAX_SWEEP_STEPS = 4096
+SWEEP_HIT, SWEEP_EXHAUSTED, SWEEP_INITIAL = 1, 2, 4  # vrt_sweep_hit.flags
+
+
+class vrt_sweep(C.Structure):
+    _fields_ = [("origin", C.c_float * 3), ("t_max", C.c_float), ("direction", C.c_float * 3), ("radius", C.c_float)]
+
+
+class vrt_sweep_hit(C.Structure):
+    _fields_ = [
+        ("t", C.c_float),
+        ("normal", C.c_float * 3),
+        ("instance", C.c_int32),
+        ("voxel", C.c_int32 * 3),
+        ("material", C.c_uint32),
+        ("flags", C.c_uint32),
+        ("steps", C.c_uint32),
+        ("distance", C.c_float),
+        ("position", C.c_float * 3),
+        ("reserved_", C.c_uint32),
+    ]
+
+
 class vrt_contact(C.Structure):
     _fields_ = [
         ("position", C.c_float * 3),
@@ -543,6 +566,8 @@ SYMBOLS = {
     "vrt_camera_rays": (C.c_int, [C.POINTER(vrt_scene), C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
     "vrt_query_points": (C.c_int, [C.c_void_p, C.c_int, C.c_float, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]),
     "vrt_query_points_host": (C.c_int, [C.c_void_p, C.c_int, C.c_float, C.c_int, C.c_void_p, C.c_void_p]),
+    "vrt_query_sweeps": (C.c_int, [C.c_void_p, C.c_int, C.c_float, C.c_float, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "vrt_query_sweeps_host": (C.c_int, [C.c_void_p, C.c_int, C.c_float, C.c_float, C.c_int, C.c_void_p, C.c_void_p]),
     "vrt_query_contacts": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_float, C.c_void_p, C.c_size_t, C.POINTER(vrt_contacts_result)]),
     "vrt_last_timing": (C.c_int, [C.c_void_p, C.POINTER(vrt_timing)]),
     "vrt_timing_history": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(C.c_float)]),

@@ -11,7 +11,7 @@ cd "$tmp"
 # VRT_LIB_NAME / VRT_EXTRA_DEFS: A/B builds of kernel variants next to the product library (tools/ab_lib_variants.sh)
 name="${VRT_LIB_NAME:-libvrt_hip.so}"
 # the translation units, once: the compile line, the kept listings and the clean-up all follow from this list
-units="vrt_api vrt_slots vrt_render vrt_comm vrt_kernels vrt_volume vrt_brush vrt_fill vrt_redistance vrt_mesh vrt_stamp vrt_smooth vrt_warp vrt_components vrt_history vrt_points vrt_measure vrt_contacts vrt_mask"
+units="vrt_api vrt_slots vrt_render vrt_comm vrt_kernels vrt_volume vrt_brush vrt_fill vrt_redistance vrt_mesh vrt_stamp vrt_smooth vrt_warp vrt_components vrt_history vrt_points vrt_sweeps vrt_measure vrt_contacts vrt_mask"
 srcs=()
 for u in $units; do srcs+=("$here/$u.hip"); done
 hipcc --offload-arch=gfx950 -O3 -ffp-contract=off -fno-slp-vectorize -fPIC -shared -std=c++17 -Wall -Wextra \

@@ -774,6 +774,21 @@ bool VHipRenderer::QueryPoints(const std::vector<VVector>& points, int iteration
     return ok(vrt_query_points_host(Ctx, iterations, tolerance, (int)in.size(), in.data(), results.data()), "vrt_query_points_host");
 }
 
+bool VHipRenderer::SweepSpheres(const std::vector<vrt_sweep>& sweeps, int maxSteps, float tolerance, float stepMin,
+                                std::vector<vrt_sweep_hit>& hits) {
+    if (!IsActive()) {
+        V_LOG_WARNING("SweepSpheres() on an inactive renderer");
+        return false;
+    }
+    const VObjectPtr<Scene::VScene> scene = SceneRef.lock();
+    if (!scene || sweeps.size() > (size_t)INT32_MAX) return false;
+    if (!SyncWithScene(*scene)) return false;
+    vrt_scene s;
+    if (!FillSceneStruct(*scene, s, &QueryObjects)) return false;
+    hits.resize(sweeps.size());
+    return ok(vrt_query_sweeps_host(Ctx, maxSteps, tolerance, stepMin, (int)sweeps.size(), sweeps.data(), hits.data()), "vrt_query_sweeps_host");
+}
+
 bool VHipRenderer::QueryContacts(const Scene::VVoxelObject& objectA, const Scene::VVoxelObject& objectB, float margin,
                                  std::vector<vrt_contact>& contacts, vrt_contacts_result* result) {
     if (!IsActive()) {

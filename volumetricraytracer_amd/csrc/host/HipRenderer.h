@@ -111,6 +111,11 @@ public:
        are first moved onto that surface (at most that many moves, stopping within `tolerance` world units of it).  HitObject-style
        lookup: the records' instance indexes the same objects as a hit's.  False (after logging) on failure. */
     bool QueryPoints(const std::vector<VVector>& points, int iterations, float tolerance, std::vector<vrt_point_result>& results);
+    /* Sweep queries on the GPU (vrt_query_sweeps_host) against the scene Render() would draw now (synced first): spheres whose centres
+       move along world-space lines in, one vrt_sweep_hit per sphere out — where it first touches a surface, within `tolerance` world
+       units, after at most maxSteps evaluations that advance by at least stepMin.  The records' instance indexes the same objects as
+       a hit's.  False (after logging) on failure. */
+    bool SweepSpheres(const std::vector<vrt_sweep>& sweeps, int maxSteps, float tolerance, float stepMin, std::vector<vrt_sweep_hit>& hits);
     /* Contact queries on the GPU (vrt_query_contacts) between two placed objects of the scene Render() would draw now (synced first):
        the points of objectA's surface that lie in objectB or within `margin` world units of its surface, as vrt_contact records in
        the order of objectA's cells — counted, then fetched.  One-sided: swap the objects for objectB's surface in objectA.  False

@@ -60,6 +60,8 @@
  *            [--probe X Y Z]                every frame asks how far the world point (X, Y, Z) is from the nearest surface (VHipRenderer::QueryPoints: a
  *                                           GPU distance query) and prints the record, ahead of the frame's edit; with --edit-brush --edit-device the
  *                                           distance moves as the dabs carve towards the point or away from it
+ *            [--sweep X Y Z DX DY DZ R]     every frame asks where a sphere of radius R, its centre moved from (X, Y, Z) along (DX, DY, DZ), first touches
+ *                                           the scene (VHipRenderer::SweepSpheres: a GPU sweep query) and prints the record, ahead of the frame's edit
  *            [--contacts I J]               after the last frame: where the surface of the scene's I-th voxel object touches or enters the J-th
  *                                           (VHipRenderer::QueryContacts, vrt_query_contacts: a GPU contact query, one-sided) — one line with the
  *                                           contact count, the candidates and the deepest distance
@@ -153,6 +155,8 @@ int main(int argc, char** argv) {
     int pickX = 0, pickY = 0;
     bool probe = false;
     VVector probeAt;
+    bool sweep = false;
+    vrt_sweep sweepRec = {{0.f, 0.f, 0.f}, 10000.f, {1.f, 0.f, 0.f}, 0.f};
     int contactsA = -1, contactsB = -1;
     int mode = 0, inFlight = 3, block = 0; /* three frames in flight: the reference's swap chain (FrameCount, DXConstants.cpp:23) */
     std::string format = "bgra8", volumes = "texel16";
@@ -198,6 +202,11 @@ int main(int argc, char** argv) {
             probeAt.X = (float)atof(argv[++i]);
             probeAt.Y = (float)atof(argv[++i]);
             probeAt.Z = (float)atof(argv[++i]);
+        } else if (!strcmp(argv[i], "--sweep") && i + 7 < argc) {
+            sweep = true;
+            for (int a = 0; a < 3; a++) sweepRec.origin[a] = (float)atof(argv[++i]);
+            for (int a = 0; a < 3; a++) sweepRec.direction[a] = (float)atof(argv[++i]);
+            sweepRec.radius = (float)atof(argv[++i]);
         }
     }
 
@@ -272,6 +281,10 @@ int main(int argc, char** argv) {
     }
     if (probe && (!hip || block > 0)) {
         fprintf(stderr, "--probe asks the HIP renderer once per frame: drop --block\n");
+        return 1;
+    }
+    if (sweep && (!hip || block > 0)) {
+        fprintf(stderr, "--sweep asks the HIP renderer once per frame: drop --block\n");
         return 1;
     }
     if (contactsA >= 0 && !hip) {
@@ -488,6 +501,20 @@ int main(int argc, char** argv) {
         sphere1->Position = VQuat::FromAxisAngle(VVector::UP, angle) * rel1;
         sphere2->Position = VQuat::FromAxisAngle(VVector::RIGHT, angle) * rel2;
         scene->Touch();
+        if (sweep) { /* where the sphere first touches the scene now, before this frame's edit */
+            std::vector<vrt_sweep_hit> rec;
+            const vrt_sweep& q = sweepRec;
+            if (!hip->SweepSpheres({q}, 512, 0.01f, 0.01f, rec) || rec.size() != 1) {
+                if (!warmUp) printf("frame %d sweep (%g, %g, %g) + t (%g, %g, %g) radius %g: failed\n", f, q.origin[0], q.origin[1], q.origin[2],
+                                    q.direction[0], q.direction[1], q.direction[2], q.radius);
+            } else if (!warmUp) {
+                const vrt_sweep_hit& r = rec[0];
+                printf("frame %d sweep (%g, %g, %g) + t (%g, %g, %g) radius %g: flags %u t %.4f instance %d distance %.4f normal (%.4f, %.4f, %.4f) "
+                       "voxel (%d, %d, %d) material %u steps %u\n", f, q.origin[0], q.origin[1], q.origin[2], q.direction[0], q.direction[1],
+                       q.direction[2], q.radius, r.flags, r.t, r.instance, r.distance, r.normal[0], r.normal[1], r.normal[2], r.voxel[0],
+                       r.voxel[1], r.voxel[2], r.material, r.steps);
+            }
+        }
         if (probe) { /* how far the world point is from the nearest surface now, before this frame's edit */
             std::vector<vrt_point_result> rec;
             if (!hip->QueryPoints({probeAt}, 0, 0.f, rec) || rec.size() != 1) {

@@ -45,6 +45,34 @@ def point_results_to_dict(res: np.ndarray) -> dict:
             "moves": res["moves"].copy(), "position": res["position"].copy()}
 
 
+SWEEP_DTYPE = np.dtype([("origin", "<f4", 3), ("t_max", "<f4"), ("direction", "<f4", 3), ("radius", "<f4")])
+SWEEP_HIT_DTYPE = np.dtype([("t", "<f4"), ("normal", "<f4", 3), ("instance", "<i4"), ("voxel", "<i4", 3), ("material", "<u4"), ("flags", "<u4"),
+                            ("steps", "<u4"), ("distance", "<f4"), ("position", "<f4", 3), ("reserved_", "<u4")])
+assert SWEEP_DTYPE.itemsize == C.sizeof(_abi.vrt_sweep) and SWEEP_HIT_DTYPE.itemsize == C.sizeof(_abi.vrt_sweep_hit)
+
+
+def make_sweeps(origins, directions, radius=0.0, t_max=10000.0) -> np.ndarray:
+    """A vrt_sweep array from [n, 3] origins and directions and a scalar or per-record radius and t_max."""
+    o = np.asarray(origins, dtype=np.float32).reshape(-1, 3)
+    d = np.asarray(directions, dtype=np.float32).reshape(-1, 3)
+    if len(o) != len(d):
+        raise ValueError("origins and directions differ in length")
+    out = np.zeros(len(o), SWEEP_DTYPE)
+    out["origin"], out["direction"] = o, d
+    out["radius"] = np.broadcast_to(np.asarray(radius, dtype=np.float32), (len(o),))
+    out["t_max"] = np.broadcast_to(np.asarray(t_max, dtype=np.float32), (len(o),))
+    return out
+
+
+def sweep_hits_to_dict(res: np.ndarray) -> dict:
+    """The fields of a vrt_sweep_hit array as separate numpy arrays; hit, exhausted and initial are the bits of flags."""
+    out = {k: res[k].copy() for k in ("t", "normal", "instance", "voxel", "material", "flags", "steps", "distance", "position")}
+    out["hit"] = (res["flags"] & _abi.SWEEP_HIT) != 0
+    out["exhausted"] = (res["flags"] & _abi.SWEEP_EXHAUSTED) != 0
+    out["initial"] = (res["flags"] & _abi.SWEEP_INITIAL) != 0
+    return out
+
+
 def contacts_to_dict(rec: np.ndarray, res: "_abi.vrt_contacts_result") -> dict:
     """A CONTACT_DTYPE array and its vrt_contacts_result as one dict: the records' fields as separate numpy arrays, and the result's."""
     out = {k: rec[k].copy() for k in ("position", "distance", "normal", "material_a", "normal_a", "material_b", "cell_a")}
@@ -837,6 +865,28 @@ class VHipRenderer:
         """The points moved onto the nearest surface: up to `iterations` moves of p - normal * distance, stopping within `tolerance`
         (world units) of it; the records of the moved points, `position` being where they ended."""
         return self.query_points(points, iterations=iterations, tolerance=tolerance)
+
+    # -- sweep queries (vrt_query_sweeps*) ------------------------------------------------------------------------------------------------
+    def sweep_spheres(self, origins, directions, radius=0.0, t_max=10000.0, max_steps: int = 256, tolerance: float = 1e-3,
+                      step_min: float = 1e-3) -> dict:
+        """Where spheres of `radius`, their centres moved from `origins` along `directions` for at most `t_max`, first touch the synced
+        scene, on the GPU (vrt_query_sweeps_host): a dict of numpy arrays t, normal, instance, voxel, material, flags, steps, distance,
+        position, hit, exhausted, initial.  tolerance and step_min are world units.  Syncs the scene first."""
+        self._require()
+        self.SyncWithScene()
+        rec = make_sweeps(origins, directions, radius, t_max)
+        res = np.zeros(len(rec), SWEEP_HIT_DTYPE)
+        _abi.check(self._lib.vrt_query_sweeps_host(self._ctx, int(max_steps), float(tolerance), float(step_min), len(rec),
+                                                   rec.ctypes.data_as(C.c_void_p), res.ctypes.data_as(C.c_void_p)), "vrt_query_sweeps_host")
+        return sweep_hits_to_dict(res)
+
+    def sweep_spheres_device(self, max_steps: int, tolerance: float, step_min: float, n: int, sweeps_ptr: int, hits_ptr: int,
+                             stream: int = 0) -> None:
+        """Asynchronous sweep of n vrt_sweep records in device memory into n vrt_sweep_hit records (vrt_query_sweeps); allocates
+        nothing, so it can be captured into a graph.  Does not sync the scene."""
+        self._require()
+        _abi.check(self._lib.vrt_query_sweeps(self._ctx, int(max_steps), float(tolerance), float(step_min), int(n), C.c_void_p(sweeps_ptr),
+                                              C.c_void_p(hits_ptr), C.c_void_p(stream)), "vrt_query_sweeps")
 
     # -- contact queries (vrt_query_contacts) ----------------------------------------------------------------------------------------
     def query_contacts(self, a: int, b: int, margin: float = 0.0) -> dict:
